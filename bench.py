@@ -28,6 +28,11 @@ How N > 1 runs:
 One JSON line on stdout (rank 0).  `roofline` prices the escape+colour kernel against the gfx950
 VECTOR peak of the arithmetic type (this path is neither HBM- nor MFMA-bound, SURVEY.md §8d);
 `cpu_baseline` is the oracle's row-parallel driver timed on this box's host cores.
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write the last step's image if
+--dump-outputs DIR is given, print the line.  Everything else it can measure or check (the same box without speculative
+blocks, the other BASELINE configs, host-path and GUI latency, the exact cycle shortcut, the CPU baseline and its byte
+comparisons, the host-buffer variant of N > 1, the per-rank diagnosis under a launcher) runs only with --full.
 """
 import argparse
 import ctypes as C
@@ -85,14 +90,25 @@ def parse_args():
                     help="measure with the exact periodicity shortcut on (never the headline: it skips iterations)")
     ap.add_argument("--force-blocks", action="store_true",
                     help="N=1 only: render block by block like a rank of an N>1 run does (tuning of --block-rows)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (profiling runs)")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core this process may use")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the same box's run without speculative blocks, the other BASELINE configs, "
+                         "host-path and GUI-latency timings, the CPU baseline and its byte comparison (N = 1); the host-buffer "
+                         "variant (N > 1, one process); the per-rank diagnosis and roofline launches (under a launcher)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the image the last one rendered to DIR as float32 .npy (whole when "
+                         "small, else a fixed seeded sample of its pixels)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU legs")
+    ap.add_argument("--no-extras", action="store_true", help="headline only, even with --full (profiling runs)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: 0 = every core this process may use")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)  # the measured run of a plain --gpus N (see supervise)
     ap.add_argument("--child-timeout", type=float, default=float(os.environ.get("FR_BENCH_CHILD_TIMEOUT", "900")),
                     help="plain --gpus N: seconds a measured child process may take before it is killed and the peer-DMA "
                          "gather is tried in a fresh one")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    args.extras = args.full and not args.no_extras
+    return args
 
 
 def make_config(fr, view, edge, iterations):
@@ -108,6 +124,29 @@ def make_config(fr, view, edge, iterations):
     if julia:
         cfg.julia_set.re, cfg.julia_set.im = julia
     return cfg
+
+
+DUMP_WHOLE_BYTES = 60 * 10**6  # --dump-outputs writes the whole image as float32 up to this size ...
+DUMP_SAMPLE_PIXELS = 1 << 21  # ... else this many pixels of it (24 MB) and their indices (16 MB)
+DUMP_SEED = 20260101
+
+
+def dump_outputs(torch, image, out_dir):
+    """--dump-outputs: the (H, W, 3) uint8 device image the last timed step rendered, as float32 .npy files in out_dir —
+    image.npy whole when it fits in DUMP_WHOLE_BYTES, else image_sample.npy, the colours of a fixed seeded sample of
+    pixels (rows in order of image_sample_index.npy, float64 y * W + x): the same pixels for every run with the same
+    arguments, so two builds can be compared output for output."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    h, w, ch = image.shape
+    if h * w * ch * 4 <= DUMP_WHOLE_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), image.cpu().numpy().astype(np.float32))
+        return
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, h * w, size=DUMP_SAMPLE_PIXELS, dtype=np.int64))
+    sample = image.reshape(h * w, ch).index_select(0, torch.from_numpy(idx).to(image.device))
+    np.save(os.path.join(out_dir, "image_sample.npy"), sample.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "image_sample_index.npy"), idx.astype(np.float64))
 
 
 def usable_cores():
@@ -446,6 +485,8 @@ def run_single(args, torch, fr, lib, native):
     else:
         m = sg.measure(cfg, prec, args.steps, args.warmup)
     total, img = m["total"], m["image"]
+    if args.dump_outputs:
+        dump_outputs(torch, img, args.dump_outputs)
     rate = total * args.steps / m["dt"]
     out = {
         "metric": "pixel_iterations_per_sec",
@@ -475,7 +516,7 @@ def run_single(args, torch, fr, lib, native):
                                                           m["kernel"] + " (fused coordinate map + orbit loop + colour map)", None),
                                            pmc_record(cfg, args.precision, args.view, fr.build_id())), note=ROOFLINE_NOTE),
     }
-    if args.no_extras:
+    if not args.extras:
         print(json.dumps(out), flush=True)
         return
 
@@ -718,13 +759,8 @@ def run_in_library(args, torch, fr, lib, native):
     dt = time.perf_counter() - t0
     st = fr.multi_stats()
     total, _ = fr.count_iterations(cfg, 0, cfg.height, 1, 1, prec)
-    # the host-buffer variant: every GPU DMAs its blocks to the caller's buffer over its own PCIe link
-    hbuf = np.empty((cfg.height, cfg.width, 3), dtype=np.uint8)
-    fr.get_image_multi(cfg, prec, args.block_rows, out=hbuf)
-    th = time.perf_counter()
-    fr.get_image_multi(cfg, prec, args.block_rows, out=hbuf)
-    host_ms = (time.perf_counter() - th) * 1e3
-    same = bool((hbuf[::61] == d_img.view(cfg.height, cfg.width, 3)[::61].cpu().numpy()).all())
+    if args.dump_outputs:
+        dump_outputs(torch, d_img.view(cfg.height, cfg.width, 3), args.dump_outputs)
     kmax = max(st["kernel_ms"])
     pixels = cfg.width * cfg.height
     out = {
@@ -765,10 +801,18 @@ def run_in_library(args, torch, fr, lib, native):
         "roofline": dict(roofline_block(args.precision, total / world, kmax, pixels // world,
                                         "escape kernels of the slowest device's share (summed over its chunk launches)",
                                         None), note=ROOFLINE_NOTE),
-        "host_buffer_variant": {"ms": host_ms, "value": total / (host_ms * 1e-3), "bytes_identical_to_gathered_image": same,
-                                "note": "fr_render_rgb8_multi: each device DMAs its blocks straight to their place in the "
-                                        "caller's pinned host buffer over its own PCIe link; resident buffer"},
     }
+    if args.extras:
+        # the host-buffer variant: every GPU DMAs its blocks to the caller's buffer over its own PCIe link
+        hbuf = np.empty((cfg.height, cfg.width, 3), dtype=np.uint8)
+        fr.get_image_multi(cfg, prec, args.block_rows, out=hbuf)
+        th = time.perf_counter()
+        fr.get_image_multi(cfg, prec, args.block_rows, out=hbuf)
+        host_ms = (time.perf_counter() - th) * 1e3
+        same = bool((hbuf[::61] == d_img.view(cfg.height, cfg.width, 3)[::61].cpu().numpy()).all())
+        out["host_buffer_variant"] = {"ms": host_ms, "value": total / (host_ms * 1e-3), "bytes_identical_to_gathered_image": same,
+                                      "note": "fr_render_rgb8_multi: each device DMAs its blocks straight to their place in the "
+                                              "caller's pinned host buffer over its own PCIe link; resident buffer"}
     if gather_note:
         out["config"]["exchange_note"] = gather_note
     if logical:
@@ -808,10 +852,8 @@ def run_distributed(args, torch, fr, lib, native, world, rank, local_rank):
     prec = fr.Precision.F32 if args.precision == "f32" else fr.Precision.F64
     edge = workload_edge(args, world)
     cfg = make_config(fr, args.view, edge, args.iterations)
-    row_bytes = 3 * cfg.width
     B = args.block_rows
     renderer = P.DistributedRenderer(cfg, prec, B, device=device, root_share=args.root_share)
-    stream = torch.cuda.current_stream(device)
 
     def fence():
         torch.cuda.synchronize(device)
@@ -823,12 +865,76 @@ def run_distributed(args, torch, fr, lib, native, world, rank, local_rank):
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        renderer.render()
+        img = renderer.render()  # the full image on rank 0, None elsewhere
     fence()
     dt = time.perf_counter() - t0
     t = torch.tensor([dt], dtype=torch.float64, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, img, args.dump_outputs)
+    del img
+    y0 = cfg.height * rank // world
+    y1 = cfg.height * (rank + 1) // world
+    total, _ = fr.count_iterations(cfg, y0, y1, 1, 1, prec)
+    t = torch.tensor([total], dtype=torch.int64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    total = int(t.item())
+    if args.extras:
+        reports, kavg, kernel_name = distributed_diagnosis(args, torch, lib, native, P, renderer, cfg, prec, fence, rank, world,
+                                                           device)
+    if rank == 0:
+        pixels = cfg.width * cfg.height
+        out = {
+            "metric": "pixel_iterations_per_sec", "value": total * args.steps / dt, "unit": "pixel-iterations/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak" if args.workload == "weak" else "strong", "vs_baseline": None,
+            "dtype": args.precision, "data": "synthetic (deterministic: the image is a pure function of the Config)",
+            "config": {
+                "workload": "%s %dx%d max_iter=%d %s view=%s (BASELINE %s)" % (
+                    VIEWS[args.view][0], cfg.width, cfg.height, cfg.iterations, args.precision, args.view,
+                    workload_label(args, world, edge)),
+                "per_gpu_pixels": pixels // world,
+                "partition": "row-block-cyclic, %d-row blocks, %d ranks (one process per GPU)" % (B, world),
+                "exchange": "RCCL point-to-point gather of finished row blocks to rank 0, pipelined behind the "
+                            "rendering, inside the timed step",
+            },
+            "mpixels_per_sec": pixels * args.steps / dt / 1e6,
+            "pixel_iterations_per_image": total,
+            "build_id": fr.build_id(),
+            "root_share": args.root_share,
+        }
+        if args.extras:
+            out.update({
+                "kernel_ms_avg": kavg,
+                "roofline": dict(roofline_block(args.precision, total / world, kavg, pixels // world,
+                                                kernel_name + " over one rank's whole share (slowest rank)", None),
+                                 note=ROOFLINE_NOTE),
+                "per_rank": {
+                    "ranks": reports,
+                    "note": "ONE extra step after the timed ones, device events on each rank (ms): kernel_ms = its chunk kernels "
+                            "summed; compute_span_ms = first kernel start to last kernel end; transfer_ms = its grouped RCCL "
+                            "point-to-point calls on the communication stream (sends on a peer, receives on rank 0), summed; "
+                            "step_ms = the step on the device; idle_ms = step - compute span.  bytes_sent is what the rank's "
+                            "xGMI link to rank 0 carried.",
+                    "link_GBps": [r["bytes_sent"] / (r["transfer_span_ms"] * 1e-3) / 1e9 if r and r["transfer_span_ms"] > 0
+                                  else None for r in reports],
+                    "prediction": multi_gpu_prediction(world, pixels, total),
+                },
+            })
+        print(json.dumps(out), flush=True)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def distributed_diagnosis(args, torch, lib, native, P, renderer, cfg, prec, fence, rank, world, device):
+    """--full under a launcher: the per-rank step report and the slowest rank's kernel time for the roofline.
+    Returns (every rank's report, the slowest rank's kernel ms, the kernel's name)."""
+    import torch.distributed as dist
+
+    B = args.block_rows
+    row_bytes = 3 * cfg.width
+    stream = torch.cuda.current_stream(device)
     # the dominant kernel's duration for the roofline: this rank's whole share as ONE launch, timed
     # with HIP events outside the timed region (the step itself launches per chunk of blocks)
     # one more step, outside the timed region, with device events around every chunk kernel and every step's transfers:
@@ -857,53 +963,9 @@ def run_distributed(args, torch, fr, lib, native, world, rank, local_rank):
                 native.check(lib.fr_last_kernel_name(name, len(name)))
         kernel_ms.append(tot)
     del share
-    y0 = cfg.height * rank // world
-    y1 = cfg.height * (rank + 1) // world
-    total, _ = fr.count_iterations(cfg, y0, y1, 1, 1, prec)
-    t = torch.tensor([total], dtype=torch.int64, device=device)
-    dist.all_reduce(t, op=dist.ReduceOp.SUM)
-    total = int(t.item())
     k = torch.tensor([sum(kernel_ms) / len(kernel_ms)], dtype=torch.float64, device=device)
     dist.all_reduce(k, op=dist.ReduceOp.MAX)
-    kavg = float(k.item())
-    if rank == 0:
-        pixels = cfg.width * cfg.height
-        out = {
-            "metric": "pixel_iterations_per_sec", "value": total * args.steps / dt, "unit": "pixel-iterations/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak" if args.workload == "weak" else "strong", "vs_baseline": None,
-            "dtype": args.precision, "data": "synthetic (deterministic: the image is a pure function of the Config)",
-            "config": {
-                "workload": "%s %dx%d max_iter=%d %s view=%s (BASELINE %s)" % (
-                    VIEWS[args.view][0], cfg.width, cfg.height, cfg.iterations, args.precision, args.view,
-                    workload_label(args, world, edge)),
-                "per_gpu_pixels": pixels // world,
-                "partition": "row-block-cyclic, %d-row blocks, %d ranks (one process per GPU)" % (B, world),
-                "exchange": "RCCL point-to-point gather of finished row blocks to rank 0, pipelined behind the "
-                            "rendering, inside the timed step",
-            },
-            "mpixels_per_sec": pixels * args.steps / dt / 1e6,
-            "pixel_iterations_per_image": total,
-            "kernel_ms_avg": kavg,
-            "build_id": fr.build_id(),
-            "roofline": dict(roofline_block(args.precision, total / world, kavg, pixels // world,
-                                            name.value.decode() + " over one rank's whole share (slowest rank)", None),
-                             note=ROOFLINE_NOTE),
-            "root_share": args.root_share,
-            "per_rank": {
-                "ranks": reports,
-                "note": "ONE extra step after the timed ones, device events on each rank (ms): kernel_ms = its chunk kernels summed; "
-                        "compute_span_ms = first kernel start to last kernel end; transfer_ms = its grouped RCCL point-to-point "
-                        "calls on the communication stream (sends on a peer, receives on rank 0), summed; step_ms = the step on "
-                        "the device; idle_ms = step - compute span.  bytes_sent is what the rank's xGMI link to rank 0 carried.",
-                "link_GBps": [r["bytes_sent"] / (r["transfer_span_ms"] * 1e-3) / 1e9 if r and r["transfer_span_ms"] > 0 else None
-                              for r in reports],
-                "prediction": multi_gpu_prediction(world, pixels, total),
-            },
-        }
-        print(json.dumps(out), flush=True)
-    dist.barrier()
-    dist.destroy_process_group()
+    return reports, float(k.item()), name.value.decode()
 
 
 def supervise(args):

@@ -300,7 +300,7 @@ def test_bench_plain_gpus_n_without_a_launcher():
     if torch.cuda.device_count() < 2:
         d = _bench(["--gpus", "2"])
         assert d["value"] is None and d["n_gpus"] == 2 and "needs 2 devices" in d["error"]
-    d = _bench(["--gpus", "3", "--logical", "--size", "3072", "--steps", "2", "--warmup", "1"])
+    d = _bench(["--gpus", "3", "--logical", "--size", "3072", "--steps", "2", "--warmup", "1", "--full"])
     assert d["n_gpus"] == 3 and d["value"] > 1e9 and d["scaling"] == "strong"
     assert d["config"]["logical_devices_on_one_gpu"] is True and "ONE process" in d["config"]["partition"]
     assert len(d["per_device_kernel_ms"]) == 3 and all(ms > 0 for ms in d["per_device_kernel_ms"])
@@ -322,7 +322,8 @@ def test_bench_under_the_launcher_at_world_size_one():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "4096"]
+           "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "4096",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

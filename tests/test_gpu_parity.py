@@ -708,7 +708,7 @@ def oracle_sample_both_modes(ocfg, step, prec=O.F64):
 def test_full_size_c2_sampled_against_oracle(fr):
     """C2 (16384^2, 1024 iterations): every 16th pixel in x and y, colours and executed-iteration
     sum, against the oracle; plus row-split invariance of the full image.  (The WHOLE C2 image is compared with the CPU
-    oracle, byte for byte, by bench.py's cpu_baseline leg in every default run: 8 s of CPU there, not repeated here.)"""
+    oracle, byte for byte, by bench.py's cpu_baseline leg in every --full run: 8 s of CPU there, not repeated here.)"""
     ocfg = O.cli_config(16384, 16384, iterations=1024)
     cfg = to_fr(fr, ocfg)
     img = fr.get_image(cfg)
@@ -833,7 +833,7 @@ def test_bench_smoke_small():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--size", "2048", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--size", "2048", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -845,6 +845,42 @@ def test_bench_smoke_small():
     # the box's own reference: the same workload without the speculative blocks, same bytes
     ref = d["roofline"]["same_box_without_speculative_blocks"]
     assert ref["byte_sums_identical"] is True and ref["kernel_ms_avg"] > 0 and -0.5 < ref["speculative_blocks_gain"] < 0.5
+
+
+def test_bench_plain_run_and_dump_outputs(fr, tmp_path):
+    """A plain bench.py run times exactly --steps steps, prints the headline without the --full legs, and
+    --dump-outputs writes the image of the last timed step: whole for a small image, a fixed sample of pixels for a
+    large one — both equal to the library's own render of the same Config."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for edge in (2048, 4608):
+        out_dir = tmp_path / str(edge)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--size", str(edge), "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["metric"] == "pixel_iterations_per_sec" and d["unit"] == "pixel-iterations/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f64" and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 1e9
+        assert not {"cpu_baseline", "end_to_end", "exact_cycle_shortcut", "other_configs", "gui_latency"} & set(d)
+        assert "same_box_without_speculative_blocks" not in d["roofline"]
+        want = fr.get_image(bench.make_config(fr, "default", edge, 1024))
+        files = sorted(os.listdir(out_dir))
+        assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 * 2**20
+        if edge == 2048:
+            assert files == ["image.npy"]
+            got = np.load(out_dir / "image.npy")
+            assert got.dtype == np.float32 and np.array_equal(got, want.astype(np.float32))
+        else:
+            assert files == ["image_sample.npy", "image_sample_index.npy"]
+            got, idx = np.load(out_dir / "image_sample.npy"), np.load(out_dir / "image_sample_index.npy")
+            assert got.dtype == np.float32 and idx.dtype == np.float64 and len(got) == len(idx) == bench.DUMP_SAMPLE_PIXELS
+            assert np.array_equal(got, want.reshape(-1, 3)[idx.astype(np.int64)].astype(np.float32))
 
 
 def test_rccl_p2p_call_pattern_self_send():

@@ -4,7 +4,7 @@ TAG=$1; shift
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"; cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD -d "$OUT" -o b -- python3 "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/err.log"
+rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD -d "$OUT" -o b -- python3 "$REPO/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/err.log"
 python3 - "$OUT" <<'PY'
 import sqlite3,glob,sys
 db=glob.glob(sys.argv[1]+"/*.db")[0]

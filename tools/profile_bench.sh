@@ -11,7 +11,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 5 --warmup 1 --no-cpu-baseline $*"
+ARGS="--steps 5 --warmup 1 --full --no-cpu-baseline $*"
 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o bench -- python3 "$REPO/bench.py" $ARGS > "$OUT/stats.json" 2> "$OUT/stats.err"
 echo "stats rc=$?"
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/pmc_write" -o bench -- python3 "$REPO/bench.py" $ARGS > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"
