@@ -17,6 +17,7 @@ every compute call raises.
 """
 import ctypes as C
 import enum
+from fractions import Fraction
 
 import numpy as np
 
@@ -27,7 +28,7 @@ __all__ = [
     "Algo", "Config", "Imaginary", "RGB", "Precision", "FractalHipError",
     "get_image", "get_image_rows", "get_image_rgba", "get_recursive_pixel", "recursive", "recursive_batch",
     "escape_rows", "colour_image", "count_iterations", "init", "shutdown", "device_count", "device_name",
-    "RenderOpts", "init_devices", "get_image_multi", "multi_stats", "build_id", "get_image_fern",
+    "RenderOpts", "init_devices", "get_image_multi", "multi_stats", "build_id", "get_image_fern", "split_dd",
 ]
 
 
@@ -53,6 +54,34 @@ class Algo(enum.IntEnum):
 class Precision(enum.IntEnum):
     F64 = 0  # the reference's arithmetic
     F32 = 1  # build-defined fast path (include/fractal_hip.h, fr_precision)
+    DD = 2  # double-double deep zoom, ~106-bit significands (include/fractal_hip.h, fr_precision)
+
+
+def split_dd(value):
+    """An exact value -> (hi, lo), two floats with hi = the nearest f64 and lo = the nearest f64 to the rest, so that
+    hi + lo carries ~106 significant bits and (hi, lo) is a normalised pos / pos_lo pair.  `value` may be a str
+    ("-0.743643887037158704752191506114774"), a Decimal, a Fraction, an int, a float or an mpmath mpf (converted through
+    its exact binary value): the split is done in rational arithmetic, with no rounding before the two f64 roundings."""
+    if isinstance(value, str):
+        f = Fraction(value.strip())
+    elif isinstance(value, Fraction):
+        f = value
+    elif hasattr(value, "man_exp"):  # mpmath.mpf: mantissa * 2^exponent, exactly
+        man, exp = value.man_exp
+        f = Fraction(int(man)) * (Fraction(2) ** int(exp))
+    else:  # int, float, Decimal: Fraction takes each exactly
+        f = Fraction(value)
+    hi = float(f)
+    lo = float(f - Fraction(hi))
+    return hi, lo
+
+
+def _pos_lo(pos_lo):
+    """pos_lo argument -> (pointer for the C call, keep-alive); None = (0, 0), the C NULL"""
+    if pos_lo is None:
+        return None, None
+    lo = Imaginary(*(float(v) for v in pos_lo))
+    return C.byref(lo), lo
 
 
 class Config(_native.fr_config):
@@ -134,11 +163,17 @@ def device_name():
     return buf.value.decode()
 
 
-def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None):
+def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None, pos_lo=None):
     """Rows [y0, y1) of get_image — the unit of the reference's rayon loop (src/lib.rs:256-264).
-    Returns uint8 [y1-y0, width, 3]."""
+    Returns uint8 [y1-y0, width, 3].  pos_lo (Precision.DD only): the low halves (re, im) of the view centre
+    (split_dd), so that the centre is pos + pos_lo; None = (0, 0)."""
     if out is None:
         out = np.empty((max(int(y1) - int(y0), 0), config.width, 3), dtype=np.uint8)
+    if pos_lo is not None:
+        _dd_only(precision)
+        lo, _keep = _pos_lo(pos_lo)
+        _native.check(_native.load().fr_render_rows_dd(C.byref(config), lo, y0, y1, 3, out.ctypes.data, out.nbytes))
+        return out
     _native.check(
         _native.load().fr_render_rows_rgb8_opts(C.byref(config), int(precision), y0, y1, out.ctypes.data, out.nbytes,
                                                 C.byref(opts) if opts is not None else None)
@@ -146,15 +181,21 @@ def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None)
     return out
 
 
-def get_image(config, precision=Precision.F64):
+def get_image(config, precision=Precision.F64, pos_lo=None):
     """get_image(&Config) -> Vec<RGB> (src/lib.rs:253-270): uint8 [height, width, 3], row-major,
     bytes r,g,b.  Algo.BarnsleyFern is outside this path (random IFS, src/lib.rs:271-319): the
-    per-pixel function returns BLACK for it (calc/src/lib.rs:211) and so does this."""
+    per-pixel function returns BLACK for it (calc/src/lib.rs:211) and so does this.
+    pos_lo: see get_image_rows (Precision.DD only)."""
     out = np.empty((config.height, config.width, 3), dtype=np.uint8)
-    if int(precision) == Precision.F64:
+    if int(precision) == Precision.F64 and pos_lo is None:
         _native.check(_native.load().fr_render_rgb8(C.byref(config), out.ctypes.data, out.nbytes))
         return out
-    return get_image_rows(config, 0, config.height, precision, out)
+    return get_image_rows(config, 0, config.height, precision, out, pos_lo=pos_lo)
+
+
+def _dd_only(precision):
+    if int(precision) != Precision.DD:
+        raise ValueError("pos_lo needs precision=Precision.DD")
 
 
 def get_image_fern(config, threads=1, seed=0, walkers=0):
@@ -166,11 +207,17 @@ def get_image_fern(config, threads=1, seed=0, walkers=0):
     return out
 
 
-def get_image_rgba(config, precision=Precision.F64, out=None):
+def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None):
     """get_image as RGBA8 (alpha 255): uint8 [height, width, 4] — the GUI's upload format
-    (src/gui.rs:71-72) produced on the device."""
+    (src/gui.rs:71-72) produced on the device.  pos_lo: see get_image_rows (Precision.DD only)."""
     if out is None:
         out = np.empty((config.height, config.width, 4), dtype=np.uint8)
+    if pos_lo is not None:
+        _dd_only(precision)
+        lo, _keep = _pos_lo(pos_lo)
+        _native.check(_native.load().fr_render_rows_dd(C.byref(config), lo, 0, config.height, 4, out.ctypes.data,
+                                                       out.nbytes))
+        return out
     _native.check(
         _native.load().fr_render_rows_rgba8(C.byref(config), int(precision), 0, config.height, out.ctypes.data,
                                             out.nbytes)
@@ -210,10 +257,18 @@ def recursive_batch(iterations, start, c, limit, precision=Precision.F64):
     return pos, it
 
 
-def escape_rows(config, y0=0, y1=None, precision=Precision.F64):
+def escape_rows(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, with_lo=False):
     """recursive() results of every pixel of rows [y0, y1): (z float64 [rows, width, 2],
-    iters uint32 [rows, width])."""
+    iters uint32 [rows, width]).  Precision.DD: z holds the hi parts; with_lo=True returns z as [rows, width, 4] =
+    re.hi, re.lo, im.hi, im.lo.  pos_lo: see get_image_rows (Precision.DD only)."""
     y1 = config.height if y1 is None else y1
+    if pos_lo is not None or with_lo:
+        _dd_only(precision)
+        lo, _keep = _pos_lo(pos_lo)
+        z = np.empty((y1 - y0, config.width, 4), dtype=np.float64)
+        it = np.empty((y1 - y0, config.width), dtype=np.uint32)
+        _native.check(_native.load().fr_escape_rows_dd(C.byref(config), lo, y0, y1, z.ctypes.data, it.ctypes.data))
+        return (z if with_lo else np.ascontiguousarray(z[..., 0::2])), it
     z = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
     it = np.empty((y1 - y0, config.width), dtype=np.uint32)
     _native.check(

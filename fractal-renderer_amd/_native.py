@@ -193,6 +193,14 @@ PROTOTYPES = {
         [C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p, C.c_void_p],
     ),
     "fr_escape_rows": (C.c_int, [C.POINTER(fr_config), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "fr_render_rows_dd": (
+        C.c_int, [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
+    "fr_render_rows_dd_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "fr_escape_rows_dd": (
+        C.c_int, [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "fr_colour_rgb8": (C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "fr_colour_rgb8_device": (
         C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

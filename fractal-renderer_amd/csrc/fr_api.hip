@@ -665,8 +665,66 @@ static int check_rows(const fr_config *cfg, uint32_t y0, uint32_t y1) {
 }
 
 int check_precision(int precision) {
+    if (precision == FR_PRECISION_DD)
+        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_DD is single-device only: the row renders, fr_pixel_p, fr_escape_rows(_dd) "
+                                             "and fr_count_iterations take it");
     if (precision != FR_PRECISION_F64 && precision != FR_PRECISION_F32)
         return fail(FR_ERR_INVALID_ARGUMENT, "precision must be FR_PRECISION_F64 or FR_PRECISION_F32");
+    return FR_OK;
+}
+
+/* FR_PRECISION_DD's domain (include/fractal_hip.h, fr_precision): with it every hi product stays finite up to the escape
+ * test — |z| <= limit <= 2^500 before a step, so |z^2| <= 2^1000 and the dd additions cannot overflow; only the escape
+ * test's own dist may reach +inf, which escapes as f64 would */
+int check_dd(const fr_config *cfg, const fr_imaginary *pos_lo) {
+    if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    const double lo_re = pos_lo ? pos_lo->re : 0.0, lo_im = pos_lo ? pos_lo->im : 0.0;
+    const double fields[] = {cfg->limit,    cfg->stable_limit, cfg->pos.re,       cfg->pos.im,       cfg->scale.re, cfg->scale.im,
+                             cfg->exposure, cfg->color_weight, cfg->julia_set.re, cfg->julia_set.im, lo_re,         lo_im};
+    for (double v : fields)
+        if (!std::isfinite(v)) return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_DD: every field of the view must be finite");
+    if (!(cfg->limit > 0.0 && cfg->limit <= 0x1p500))
+        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_DD: limit must lie in (0, 2^500]");
+    if (std::fabs(cfg->pos.re) > 0x1p64 || std::fabs(cfg->pos.im) > 0x1p64 || std::fabs(cfg->julia_set.re) > 0x1p64 ||
+        std::fabs(cfg->julia_set.im) > 0x1p64)
+        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_DD: |pos| and |julia_set| must be <= 2^64");
+    if (std::fabs(cfg->scale.re) < 0x1p-64 || std::fabs(cfg->scale.im) < 0x1p-64)
+        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_DD: |scale| must be >= 2^-64 on both axes");
+    if (cfg->pos.re + lo_re != cfg->pos.re || cfg->pos.im + lo_im != cfg->pos.im)
+        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_DD: pos_lo is not normalised (pos + pos_lo must round to pos)");
+    return FR_OK;
+}
+
+int check_precision_or_dd(const fr_config *cfg, int precision) {
+    return precision == FR_PRECISION_DD ? check_dd(cfg, nullptr) : check_precision(precision);
+}
+
+int render_dd_device(const fr_config *cfg, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0, uint32_t y1, unsigned bpp,
+                     void *d_out, hipStream_t stream) {
+    fr_kparams p;
+    fill_params(cfg, o, p); /* the colour constants; no loop plan, no kernel choice, no view sample */
+    p.nrows = y1 - y0;
+    p.y_first = y0;
+    p.block_rows = p.nrows;
+    p.y_stride = 0;
+    p.out_rgba = bpp == 4 ? 1u : 0u;
+    fr_kout out{};
+    out.rgb = static_cast<uint8_t *>(d_out);
+    Profiling &pr = tl_prof;
+    if (pr.enabled) {
+        if (!pr.e0) {
+            HIP_TRY(hipEventCreate(&pr.e0));
+            HIP_TRY(hipEventCreate(&pr.e1));
+        }
+        HIP_TRY(hipEventRecord(pr.e0, stream));
+    }
+    const char *kname = "";
+    HIP_TRY(fr_launch_escape_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, FR_OUT_RGB, out, false, stream, &kname));
+    if (pr.enabled) {
+        HIP_TRY(hipEventRecord(pr.e1, stream));
+        pr.have = true;
+        pr.kernel = kname;
+    }
     return FR_OK;
 }
 
@@ -1165,9 +1223,10 @@ void fr_render_opts_init(fr_render_opts *opts) {
 /* ---- device-pointer renders: asynchronous, lock-free apart from the palette slot ring ---------- */
 
 static int render_rows_device(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, void *d_out,
-                              size_t out_len, void *hip_stream, unsigned bytes_per_pixel, const fr_render_opts *opts) {
+                              size_t out_len, void *hip_stream, unsigned bytes_per_pixel, const fr_render_opts *opts,
+                              const fr_imaginary *pos_lo = nullptr) {
     int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = check_precision(precision);
+    if (rc == FR_OK) rc = precision == FR_PRECISION_DD ? check_dd(cfg, pos_lo) : check_precision(precision);
     Opts o;
     if (rc == FR_OK) rc = resolve_opts(opts, o);
     if (rc != FR_OK) return rc;
@@ -1181,6 +1240,8 @@ static int render_rows_device(const fr_config *cfg, int precision, uint32_t y0, 
     Ctx *ctx;
     rc = primary(&ctx);
     if (rc != FR_OK) return rc;
+    if (precision == FR_PRECISION_DD)
+        return render_dd_device(cfg, pos_lo, o, y0, y1, bytes_per_pixel, d_out, static_cast<hipStream_t>(hip_stream));
     fr_kparams p;
     fill_params(cfg, o, p);
     p.nrows = y1 - y0;
@@ -1230,6 +1291,8 @@ int fr_render_block_cyclic_range_rgb8_device_opts(const fr_config *cfg, int prec
     int rc = resolve_opts(opts, o);
     if (rc != FR_OK) return rc;
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    rc = check_precision(precision); /* before the device: FR_PRECISION_DD is refused here without one too */
+    if (rc != FR_OK) return rc;
     LifeShared ls;
     Ctx *ctx;
     rc = primary(&ctx);
@@ -1264,12 +1327,13 @@ int fr_render_block_cyclic_rgb8(const fr_config *cfg, int precision, uint32_t bl
     const uint64_t rows = fr_block_cyclic_rows(cfg->height, block_rows, first_block, block_stride);
     if (rows_written) *rows_written = rows;
     const size_t need = (size_t)3 * cfg->width * (size_t)rows;
-    if (need == 0) return check_precision(precision);
+    int rc = check_precision(precision);
+    if (need == 0 || rc != FR_OK) return rc;
     if (!out) return fail(FR_ERR_INVALID_ARGUMENT, "out is NULL");
     if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < 3*width*rows");
     LifeShared ls;
     Ctx *ctx;
-    int rc = primary(&ctx);
+    rc = primary(&ctx);
     if (rc != FR_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     rc = ctx->reserve(ctx->rgb, need);
@@ -1296,6 +1360,25 @@ int fr_render_rows_rgba8(const fr_config *cfg, int precision, uint32_t y0, uint3
     return fr_host_render_rows(cfg, precision, y0, y1, out, out_len, 4, nullptr);
 }
 
+static int dd_channels(int channels) {
+    if (channels != 3 && channels != 4) return fail(FR_ERR_INVALID_ARGUMENT, "channels must be 3 (RGB) or 4 (RGBA)");
+    return FR_OK;
+}
+
+int fr_render_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
+                      uint8_t *out, size_t out_len) {
+    const int rc = dd_channels(channels);
+    if (rc != FR_OK) return rc;
+    return fr_host_render_rows_dd(cfg, pos_lo, y0, y1, out, out_len, (unsigned)channels, nullptr);
+}
+
+int fr_render_rows_dd_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
+                             void *d_out, size_t out_len, void *hip_stream) {
+    const int rc = dd_channels(channels);
+    if (rc != FR_OK) return rc;
+    return render_rows_device(cfg, FR_PRECISION_DD, y0, y1, d_out, out_len, hip_stream, (unsigned)channels, nullptr, pos_lo);
+}
+
 int fr_render_rgb8(const fr_config *cfg, uint8_t *out, size_t out_len) {
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
     return fr_host_render_rows(cfg, FR_PRECISION_F64, 0, cfg->height, out, out_len, 3, nullptr);
@@ -1303,7 +1386,7 @@ int fr_render_rgb8(const fr_config *cfg, uint8_t *out, size_t out_len) {
 
 int fr_pixel_p(const fr_config *cfg, int precision, uint32_t x, uint32_t y, fr_rgb *out) {
     if (!cfg || !out) return fail(FR_ERR_INVALID_ARGUMENT, "cfg or out is NULL");
-    int rc = check_precision(precision);
+    int rc = check_precision_or_dd(cfg, precision);
     if (rc != FR_OK) return rc;
     /* get_recursive_pixel takes any u32 x, y — it does not clamp to width/height */
     LifeShared ls;
@@ -1320,10 +1403,14 @@ int fr_pixel_p(const fr_config *cfg, int precision, uint32_t x, uint32_t y, fr_r
     p.nrows = 1;
     p.x_first = x;
     p.y_first = y;
-    plan_loop(cfg, precision, o, p);
     fr_kout ko{};
     ko.rgb = static_cast<uint8_t *>(ctx->misc.ptr);
-    HIP_TRY(fr_launch_escape(p, precision, FR_OUT_RGB, ko, o.tile, ctx->stream, nullptr));
+    if (precision == FR_PRECISION_DD) {
+        HIP_TRY(fr_launch_escape_dd(p, 0.0, 0.0, FR_OUT_RGB, ko, false, ctx->stream, nullptr));
+    } else {
+        plan_loop(cfg, precision, o, p);
+        HIP_TRY(fr_launch_escape(p, precision, FR_OUT_RGB, ko, o.tile, ctx->stream, nullptr));
+    }
     uint8_t rgb[3];
     HIP_TRY(hipMemcpyAsync(rgb, ctx->misc.ptr, 3, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1370,10 +1457,11 @@ int fr_recursive(uint32_t iterations, fr_imaginary start, fr_imaginary c, double
     return fr_recursive_batch(iterations, &start, &c, 1, limit, FR_PRECISION_F64, out_pos, out_iters);
 }
 
-int fr_escape_rows(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, double *z_re_im,
-                   uint32_t *iters) {
+/* fr_escape_rows and fr_escape_rows_dd: `zw` doubles per pixel (2: re, im — DD: the hi parts; 4: DD with the lo parts) */
+static int escape_rows(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
+                       double *z_re_im, uint32_t *iters, unsigned zw) {
     int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = check_precision(precision);
+    if (rc == FR_OK) rc = precision == FR_PRECISION_DD ? check_dd(cfg, pos_lo) : check_precision(precision);
     if (rc != FR_OK) return rc;
     const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
     if (npx == 0 || (!z_re_im && !iters)) return FR_OK;
@@ -1382,7 +1470,7 @@ int fr_escape_rows(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1
     rc = primary(&ctx);
     if (rc != FR_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (z_re_im) rc = ctx->reserve(ctx->z, npx * 2 * sizeof(double));
+    if (z_re_im) rc = ctx->reserve(ctx->z, npx * zw * sizeof(double));
     if (rc == FR_OK && iters) rc = ctx->reserve(ctx->iters, npx * sizeof(uint32_t));
     if (rc != FR_OK) return rc;
     const Opts o = default_opts();
@@ -1392,15 +1480,30 @@ int fr_escape_rows(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1
     p.y_first = y0;
     p.block_rows = p.nrows;
     p.y_stride = 0;
-    plan_loop(cfg, precision, o, p);
     fr_kout ko{};
     ko.z = z_re_im ? static_cast<double *>(ctx->z.ptr) : nullptr;
     ko.iters = iters ? static_cast<uint32_t *>(ctx->iters.ptr) : nullptr;
-    HIP_TRY(fr_launch_escape(p, precision, FR_OUT_ESCAPE, ko, o.tile, ctx->stream, nullptr));
-    if (z_re_im) HIP_TRY(hipMemcpyAsync(z_re_im, ctx->z.ptr, npx * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (precision == FR_PRECISION_DD) {
+        HIP_TRY(fr_launch_escape_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, FR_OUT_ESCAPE, ko, zw == 4,
+                                    ctx->stream, nullptr));
+    } else {
+        plan_loop(cfg, precision, o, p);
+        HIP_TRY(fr_launch_escape(p, precision, FR_OUT_ESCAPE, ko, o.tile, ctx->stream, nullptr));
+    }
+    if (z_re_im) HIP_TRY(hipMemcpyAsync(z_re_im, ctx->z.ptr, npx * zw * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (iters) HIP_TRY(hipMemcpyAsync(iters, ctx->iters.ptr, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FR_OK;
+}
+
+int fr_escape_rows(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, double *z_re_im,
+                   uint32_t *iters) {
+    return escape_rows(cfg, precision, nullptr, y0, y1, z_re_im, iters, 2);
+}
+
+int fr_escape_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z,
+                      uint32_t *iters) {
+    return escape_rows(cfg, FR_PRECISION_DD, pos_lo, y0, y1, z, iters, 4);
 }
 
 int fr_colour_rgb8(const fr_config *cfg, const double *z_re_im, const uint32_t *iters, size_t n, uint8_t *out,
@@ -1445,7 +1548,7 @@ int fr_colour_rgb8_device(const fr_config *cfg, const void *d_z_re_im, const voi
 int fr_count_iterations(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint32_t sx, uint32_t sy,
                         uint64_t *total, uint64_t *pixels) {
     int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = check_precision(precision);
+    if (rc == FR_OK) rc = check_precision_or_dd(cfg, precision);
     if (rc != FR_OK) return rc;
     if (!total) return fail(FR_ERR_INVALID_ARGUMENT, "total is NULL");
     if (sx == 0) sx = 1;
@@ -1472,10 +1575,14 @@ int fr_count_iterations(const fr_config *cfg, int precision, uint32_t y0, uint32
     rc = ctx->reserve(ctx->misc, slot_bytes);
     if (rc != FR_OK) return rc;
     HIP_TRY(hipMemsetAsync(ctx->misc.ptr, 0, slot_bytes, ctx->stream));
-    plan_loop(cfg, precision, o, p);
     fr_kout ko{};
     ko.count = static_cast<unsigned long long *>(ctx->misc.ptr);
-    HIP_TRY(fr_launch_escape(p, precision, FR_OUT_COUNT, ko, o.tile, ctx->stream, nullptr));
+    if (precision == FR_PRECISION_DD) {
+        HIP_TRY(fr_launch_escape_dd(p, 0.0, 0.0, FR_OUT_COUNT, ko, false, ctx->stream, nullptr));
+    } else {
+        plan_loop(cfg, precision, o, p);
+        HIP_TRY(fr_launch_escape(p, precision, FR_OUT_COUNT, ko, o.tile, ctx->stream, nullptr));
+    }
     std::vector<unsigned long long> host(FR_COUNT_SLOTS);
     HIP_TRY(hipMemcpyAsync(host.data(), ctx->misc.ptr, slot_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -170,6 +170,15 @@ int render_block_cyclic(Ctx &ctx, const fr_config *cfg, int precision, const Opt
 
 int check_precision(int precision);
 
+/* FR_PRECISION_DD (fr_dd.hip): the domain check of include/fractal_hip.h (pos_lo NULL = (0, 0)); no device needed */
+int check_dd(const fr_config *cfg, const fr_imaginary *pos_lo);
+/* check_precision, or for FR_PRECISION_DD check_dd with pos_lo = 0: the single-device calls that accept DD */
+int check_precision_or_dd(const fr_config *cfg, int precision);
+/* DD rows [y0, y1) as RGB (bpp 3) / RGBA (bpp 4) into device memory on `stream`; arguments already checked.  Records the
+ * profiling events and the kernel's name like render_device.  No host synchronisation. */
+int render_dd_device(const fr_config *cfg, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0, uint32_t y1, unsigned bpp,
+                     void *d_out, hipStream_t stream);
+
 /* choose_kernel for rows [y0, y1) of the image as ONE launch, recorded in `o` (tile 0 only): callers that render those
  * rows in several launches then sample the view once, not once per launch.  The calling thread must be on ctx's device. */
 void decide_kernel(Ctx &ctx, const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, Opts &o, hipStream_t stream,
@@ -247,5 +256,8 @@ void multi_shutdown_locked();
 /* shared body of the host-buffer row renders (fr_host.hip) */
 int fr_host_render_rows(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint8_t *out, size_t out_len,
                         unsigned bytes_per_pixel, const fr_render_opts *opts);
+/* the same for FR_PRECISION_DD with the centre's low halves (fr_host.hip) */
+int fr_host_render_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, uint8_t *out,
+                           size_t out_len, unsigned bytes_per_pixel, const fr_render_opts *opts);
 
 #endif

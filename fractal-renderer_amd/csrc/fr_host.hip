@@ -691,6 +691,7 @@ int fr_host_render_rows(const fr_config *cfg, int precision, uint32_t y0, uint32
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
     if (y0 > y1) return fail(FR_ERR_INVALID_ARGUMENT, "y0 > y1");
     if (y1 > cfg->height) return fail(FR_ERR_INVALID_ARGUMENT, "y1 > height");
+    if (precision == FR_PRECISION_DD) return fr_host_render_rows_dd(cfg, nullptr, y0, y1, out, out_len, bpp, opts);
     int rc = check_precision(precision);
     Opts o;
     if (rc == FR_OK) rc = resolve_opts(opts, o);
@@ -706,4 +707,35 @@ int fr_host_render_rows(const fr_config *cfg, int precision, uint32_t y0, uint32
     if (rc != FR_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     return host_render_rows(*ctx, cfg, precision, o, y0, y1, out, bpp);
+}
+
+/* FR_PRECISION_DD into a HOST buffer: one kernel into device scratch, one copy, no bands.  A DD pixel costs ~14x an f64
+ * one on the device ("Double-double deep zoom"), so the copy that the f64 road works hard to hide is a few
+ * per cent of the call here. */
+int fr_host_render_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, uint8_t *out,
+                           size_t out_len, unsigned bpp, const fr_render_opts *opts) {
+    if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (y0 > y1) return fail(FR_ERR_INVALID_ARGUMENT, "y0 > y1");
+    if (y1 > cfg->height) return fail(FR_ERR_INVALID_ARGUMENT, "y1 > height");
+    int rc = check_dd(cfg, pos_lo);
+    Opts o;
+    if (rc == FR_OK) rc = resolve_opts(opts, o);
+    if (rc != FR_OK) return rc;
+    const size_t need = (size_t)bpp * cfg->width * (size_t)(y1 - y0);
+    if (need == 0) return FR_OK;
+    if (!out) return fail(FR_ERR_INVALID_ARGUMENT, "out is NULL");
+    if (out_len < need)
+        return fail(FR_ERR_BUFFER_TOO_SMALL, bpp == 4 ? "out_len < 4*width*(y1-y0)" : "out_len < 3*width*(y1-y0)");
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = ctx->reserve(ctx->rgb, need);
+    if (rc != FR_OK) return rc;
+    rc = render_dd_device(cfg, pos_lo, o, y0, y1, bpp, ctx->rgb.ptr, ctx->stream);
+    if (rc != FR_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FR_OK;
 }

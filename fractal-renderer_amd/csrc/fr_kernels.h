@@ -140,6 +140,12 @@ struct fr_kout {
 hipError_t fr_launch_escape(const fr_kparams &p, int precision, int mode, const fr_kout &out, int tile,
                             hipStream_t stream, const char **kernel_name);
 
+/* FR_PRECISION_DD (fr_dd.hip: escape_dd_kernel): the launch's local grid, colour and limit from `p` (no loop plan, no
+ * kernel choice), the low halves of the view centre as (pos_lo_re, pos_lo_im).  MODE ESCAPE writes re.hi, re.lo, im.hi,
+ * im.lo per pixel into out.z when with_lo, else re.hi, im.hi.  *kernel_name (may be NULL) receives the kernel's name. */
+hipError_t fr_launch_escape_dd(const fr_kparams &p, double pos_lo_re, double pos_lo_im, int mode, const fr_kout &out,
+                               bool with_lo, hipStream_t stream, const char **kernel_name);
+
 /* Would fr_launch_escape(p, ..., FR_OUT_RGB, ..., tile) pick the work-queue kernel if p.work_counter were set?
  * (The caller then lends a counter and zeroes it on the launch stream.) */
 bool fr_wants_work_queue(const fr_kparams &p, int tile);

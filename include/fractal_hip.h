@@ -95,7 +95,36 @@ typedef struct fr_config {
  * claim against it).  F32 is this build's fast path for shallow zooms, defined as: coordinates
  * (calc/src/lib.rs:181-197) in f64, start / c / limit narrowed to f32, recursive() evaluated in
  * f32 with the same operation order, final position widened to f64, colour mapping in f64. */
-typedef enum fr_precision { FR_PRECISION_F64 = 0, FR_PRECISION_F32 = 1 } fr_precision;
+/*
+ * DD (double-double) is for zooms past the f64 limit: once a pixel is narrower than about one f64 ulp of pos (scale
+ * >~ 10^13 near |pos| ~ 0.75 at 1080 rows) neighbouring pixels get the same f64 start and the image turns into flat
+ * blocks.  A dd is a pair (hi, lo) of f64 values (about 106-bit significands).  DD is DEFINED by this exact operation
+ * sequence (each fma one correctly rounded fused multiply-add, nothing else fused):
+ *   two_sum(a,b):      s = a+b; bb = s-a; e = (a-(s-bb)) + (b-bb)                              -> (s, e)
+ *   fast_two_sum(a,b): s = a+b; e = b-(s-a)                                                    -> (s, e)
+ *   add_dd(a,b):       (sh,sl) = two_sum(a.hi,b.hi); (th,tl) = two_sum(a.lo,b.lo)
+ *                      sl = sl+th; (sh,sl) = fast_two_sum(sh,sl); sl = sl+tl; (sh,sl) = fast_two_sum(sh,sl)
+ *   add_d(a,d):        (sh,sl) = two_sum(a.hi,d); sl = sl+a.lo; (sh,sl) = fast_two_sum(sh,sl)
+ *   sqr(x):            p = x.hi*x.hi; e = fma(x.hi,x.hi,-p); e = fma(x.hi+x.hi, x.lo, e); fast_two_sum(p,e)
+ *   twice_mul(x,y):    p = x.hi*y.hi; e = fma(x.hi,y.hi,-p); e = fma(x.hi,y.lo,e); e = fma(x.lo,y.hi,e)
+ *                      (h,l) = fast_two_sum(p,e); -> (h+h, l+l)
+ *   negation negates both halves.
+ * Start: off_re = ((x/h) - ((w/h)/2)) / scale.re, off_im = ((y/h) - 0.5) / scale.im (one f64 operation each, in this
+ * order: coord_to_space without the final + pos), start = add_d((pos, pos_lo), off) per axis.  With pos_lo = 0,
+ * start.hi is the f64 start bit for bit.
+ * One iteration: re' = add_dd(add_dd(sqr(re), -sqr(im)), c.re), im' = add_dd(twice_mul(re, im), c.im); Mandelbrot:
+ * c = start (dd); Julia: c = julia_set (f64) and the two outer add_dd are add_d.
+ * Escape test and loop semantics are recursive()'s (calc/src/lib.rs:245-257) with dist = re'.hi*re'.hi + im'.hi*im'.hi
+ * and dist > limit*limit in f64: on escape `next` with index i, on exhaustion `previous` with `iterations`.
+ * Colour: the colour map applied to the hi parts (r2 = re.hi*re.hi, i2 = im.hi*im.hi): fr_colour_rgb8 over the hi
+ * parts of fr_escape_rows(_dd) reproduces the DD image.
+ * Domain (else FR_ERR_INVALID_ARGUMENT, before any device work): every double field of the config and of pos_lo finite;
+ * 0 < limit <= 2^500; |pos|, |julia_set| <= 2^64 and |scale| >= 2^-64 on either axis; pos_lo normalised
+ * (pos.re + pos_lo.re == pos.re in f64, same for im).  This keeps every hi product finite up to the escape test.
+ * DD runs on one device: the single-device row renders, fr_pixel_p, fr_escape_rows (hi parts), fr_count_iterations
+ * (all with pos_lo = 0) and the fr_*_dd calls below take it; block-cyclic, multi-device and fr_recursive_batch do not.
+ * Implementation selectors (fr_set_tile, fr_render_opts, ...) select nothing for DD: it has one kernel. */
+typedef enum fr_precision { FR_PRECISION_F64 = 0, FR_PRECISION_F32 = 1, FR_PRECISION_DD = 2 } fr_precision;
 
 /* ---- lifetime ---------------------------------------------------------------------------- */
 
@@ -277,6 +306,21 @@ int fr_unpin_host_buffer(void *ptr);
  * fr_render_rgb8 itself keeps rendering BarnsleyFern BLACK, as calc::get_recursive_pixel does (:211). */
 int fr_render_fern_rgb8(const fr_config *cfg, uint32_t threads, uint64_t seed, uint32_t walkers, uint8_t *out,
                         size_t out_len);
+
+/* ---- deep zoom: FR_PRECISION_DD with the low halves of the view centre ------------------------- */
+
+/* pos_lo (NULL = (0, 0)) is the low half of the view centre: the centre is pos + pos_lo exactly, so a deep view can
+ * be centred anywhere, not only on f64 grid points.  Rows [y0, y1) as r,g,b (channels 3) or r,g,b,255 (channels 4)
+ * into a HOST buffer of at least channels*width*(y1-y0) bytes, or into DEVICE memory asynchronously on `hip_stream`
+ * (RGBA: 4-byte aligned). */
+int fr_render_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
+                      uint8_t *out, size_t out_len);
+int fr_render_rows_dd_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
+                             void *d_out, size_t out_len, void *hip_stream);
+/* recursive() results in DD of every pixel of rows [y0, y1) (host arrays, either may be NULL): z[4k .. 4k+3] =
+ * re.hi, re.lo, im.hi, im.lo of the final position, iters[k] = escape index, k = (y-y0)*width + x. */
+int fr_escape_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z,
+                      uint32_t *iters);
 
 /* ---- get_recursive_pixel — calc/src/lib.rs:199-235 ---------------------------------------- */
 

@@ -53,6 +53,8 @@ pub const FR_OK: c_int = 0;
 pub const FR_ABI_VERSION: c_int = 3;
 pub const FR_PRECISION_F64: c_int = 0;
 pub const FR_PRECISION_F32: c_int = 1;
+/// Double-double (~106-bit) arithmetic for zooms past the f64 limit (include/fractal_hip.h, `fr_precision`).
+pub const FR_PRECISION_DD: c_int = 2;
 
 extern "C" {
     pub fn fr_init(device: c_int) -> c_int;
@@ -85,6 +87,10 @@ extern "C" {
     pub fn fr_set_dispatch_sampling(enabled: c_int) -> c_int;
     // Algo::BarnsleyFern (src/lib.rs:271-319, 417-463) on the GPU
     pub fn fr_render_fern_rgb8(cfg: *const fr_config, threads: u32, seed: u64, walkers: u32, out: *mut u8, out_len: usize) -> c_int;
+    // deep zoom: FR_PRECISION_DD with the low halves of the view centre (NULL = (0, 0))
+    pub fn fr_render_rows_dd(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, channels: c_int, out: *mut u8, out_len: usize) -> c_int;
+    pub fn fr_render_rows_dd_device(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, channels: c_int, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_escape_rows_dd(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, z: *mut f64, iters: *mut u32) -> c_int;
 }
 
 /// Message of the last failing call on this thread.
@@ -197,6 +203,23 @@ pub fn render_rgba_into(cfg: &fr_config, frame: &mut [u8]) -> Result<(), String>
     }
     let rc = unsafe { fr_render_rows_rgba8(cfg, FR_PRECISION_F64, 0, cfg.height, frame.as_mut_ptr(), frame.len()) };
     if rc != FR_OK { Err(last_error()) } else { Ok(()) }
+}
+
+/// `get_image` for a deep zoom (src/gui.rs zooms on scroll without bound): the whole image in double-double arithmetic
+/// into a caller-owned pixel vector.  The view centre is `cfg.pos + pos_lo` exactly — `pos_lo` holds the low halves,
+/// normalised (`pos.re + pos_lo.re == pos.re` in f64; split a decimal centre with rational arithmetic: hi = nearest
+/// f64, lo = nearest f64 to the rest).  `P` must be a 3-byte `#[repr(C)]` pixel.
+pub fn get_image_dd<P: Copy>(cfg: &fr_config, pos_lo: fr_imaginary, image: &mut Vec<P>) -> Result<(), String> {
+    assert_eq!(std::mem::size_of::<P>(), 3, "pixel type must be 3 packed bytes");
+    let n = cfg.width as usize * cfg.height as usize;
+    image.clear();
+    image.reserve_exact(n);
+    let rc = unsafe { fr_render_rows_dd(cfg, &pos_lo, 0, cfg.height, 3, image.as_mut_ptr() as *mut u8, n * 3) };
+    if rc != FR_OK {
+        return Err(last_error());
+    }
+    unsafe { image.set_len(n) }; // every byte was written by the library
+    Ok(())
 }
 
 /// The loaded library must speak the ABI these declarations describe (include/fractal_hip.h: FR_ABI_VERSION).
