@@ -55,6 +55,7 @@ class Precision(enum.IntEnum):
     F64 = 0  # the reference's arithmetic
     F32 = 1  # build-defined fast path (include/fractal_hip.h, fr_precision)
     DD = 2  # double-double deep zoom, ~106-bit significands (include/fractal_hip.h, fr_precision)
+    PT = 3  # perturbation deep zoom: one dd reference orbit, f64 offsets per pixel (include/fractal_hip.h, fr_precision)
 
 
 def split_dd(value):
@@ -165,14 +166,14 @@ def device_name():
 
 def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None, pos_lo=None):
     """Rows [y0, y1) of get_image — the unit of the reference's rayon loop (src/lib.rs:256-264).
-    Returns uint8 [y1-y0, width, 3].  pos_lo (Precision.DD only): the low halves (re, im) of the view centre
-    (split_dd), so that the centre is pos + pos_lo; None = (0, 0)."""
+    Returns uint8 [y1-y0, width, 3].  pos_lo (Precision.DD or Precision.PT only): the low halves (re, im) of the view
+    centre (split_dd), so that the centre is pos + pos_lo; None = (0, 0)."""
     if out is None:
         out = np.empty((max(int(y1) - int(y0), 0), config.width, 3), dtype=np.uint8)
     if pos_lo is not None:
-        _dd_only(precision)
+        render = _render_rows_lo(precision)
         lo, _keep = _pos_lo(pos_lo)
-        _native.check(_native.load().fr_render_rows_dd(C.byref(config), lo, y0, y1, 3, out.ctypes.data, out.nbytes))
+        _native.check(render(C.byref(config), lo, y0, y1, 3, out.ctypes.data, out.nbytes))
         return out
     _native.check(
         _native.load().fr_render_rows_rgb8_opts(C.byref(config), int(precision), y0, y1, out.ctypes.data, out.nbytes,
@@ -185,7 +186,7 @@ def get_image(config, precision=Precision.F64, pos_lo=None):
     """get_image(&Config) -> Vec<RGB> (src/lib.rs:253-270): uint8 [height, width, 3], row-major,
     bytes r,g,b.  Algo.BarnsleyFern is outside this path (random IFS, src/lib.rs:271-319): the
     per-pixel function returns BLACK for it (calc/src/lib.rs:211) and so does this.
-    pos_lo: see get_image_rows (Precision.DD only)."""
+    pos_lo: see get_image_rows (Precision.DD or Precision.PT only)."""
     out = np.empty((config.height, config.width, 3), dtype=np.uint8)
     if int(precision) == Precision.F64 and pos_lo is None:
         _native.check(_native.load().fr_render_rgb8(C.byref(config), out.ctypes.data, out.nbytes))
@@ -196,6 +197,15 @@ def get_image(config, precision=Precision.F64, pos_lo=None):
 def _dd_only(precision):
     if int(precision) != Precision.DD:
         raise ValueError("pos_lo needs precision=Precision.DD")
+
+
+def _render_rows_lo(precision):
+    """the C row render that takes pos_lo for this precision"""
+    if int(precision) == Precision.PT:
+        return _native.load().fr_render_rows_pt
+    if int(precision) != Precision.DD:
+        raise ValueError("pos_lo needs precision=Precision.DD or Precision.PT")
+    return _native.load().fr_render_rows_dd
 
 
 def get_image_fern(config, threads=1, seed=0, walkers=0):
@@ -209,14 +219,13 @@ def get_image_fern(config, threads=1, seed=0, walkers=0):
 
 def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None):
     """get_image as RGBA8 (alpha 255): uint8 [height, width, 4] — the GUI's upload format
-    (src/gui.rs:71-72) produced on the device.  pos_lo: see get_image_rows (Precision.DD only)."""
+    (src/gui.rs:71-72) produced on the device.  pos_lo: see get_image_rows (Precision.DD or Precision.PT only)."""
     if out is None:
         out = np.empty((config.height, config.width, 4), dtype=np.uint8)
     if pos_lo is not None:
-        _dd_only(precision)
+        render = _render_rows_lo(precision)
         lo, _keep = _pos_lo(pos_lo)
-        _native.check(_native.load().fr_render_rows_dd(C.byref(config), lo, 0, config.height, 4, out.ctypes.data,
-                                                       out.nbytes))
+        _native.check(render(C.byref(config), lo, 0, config.height, 4, out.ctypes.data, out.nbytes))
         return out
     _native.check(
         _native.load().fr_render_rows_rgba8(C.byref(config), int(precision), 0, config.height, out.ctypes.data,
@@ -260,8 +269,14 @@ def recursive_batch(iterations, start, c, limit, precision=Precision.F64):
 def escape_rows(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, with_lo=False):
     """recursive() results of every pixel of rows [y0, y1): (z float64 [rows, width, 2],
     iters uint32 [rows, width]).  Precision.DD: z holds the hi parts; with_lo=True returns z as [rows, width, 4] =
-    re.hi, re.lo, im.hi, im.lo.  pos_lo: see get_image_rows (Precision.DD only)."""
+    re.hi, re.lo, im.hi, im.lo (Precision.DD only).  pos_lo: see get_image_rows (Precision.DD or Precision.PT only)."""
     y1 = config.height if y1 is None else y1
+    if pos_lo is not None and not with_lo and int(precision) == Precision.PT:
+        lo, _keep = _pos_lo(pos_lo)
+        z = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
+        it = np.empty((y1 - y0, config.width), dtype=np.uint32)
+        _native.check(_native.load().fr_escape_rows_pt(C.byref(config), lo, y0, y1, z.ctypes.data, it.ctypes.data))
+        return z, it
     if pos_lo is not None or with_lo:
         _dd_only(precision)
         lo, _keep = _pos_lo(pos_lo)

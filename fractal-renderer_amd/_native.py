@@ -201,6 +201,16 @@ PROTOTYPES = {
     ),
     "fr_escape_rows_dd": (
         C.c_int, [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "fr_render_rows_pt": (
+        C.c_int, [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
+    "fr_render_rows_pt_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "fr_escape_rows_pt": (
+        C.c_int, [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "fr_debug_reference_orbit": (
+        C.c_int, [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "fr_colour_rgb8": (C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "fr_colour_rgb8_device": (
         C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

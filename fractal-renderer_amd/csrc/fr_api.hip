@@ -259,6 +259,10 @@ void Ctx::destroy() {
         if (surv_block) (void)hipFree(surv_block);
         surv_block = nullptr, surv_slot_cap = 0;
     }
+    {
+        std::lock_guard<std::mutex> pl(pt_mu);
+        pt_orbit.reset();
+    }
     for (hipEvent_t e : events) (void)hipEventDestroy(e);
     events.clear();
     if (copy_pool) destroy_copy_pool(copy_pool);
@@ -668,6 +672,9 @@ int check_precision(int precision) {
     if (precision == FR_PRECISION_DD)
         return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_DD is single-device only: the row renders, fr_pixel_p, fr_escape_rows(_dd) "
                                              "and fr_count_iterations take it");
+    if (precision == FR_PRECISION_PT)
+        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_PT is single-device only: the row renders, fr_pixel_p, fr_escape_rows(_pt) "
+                                             "and fr_count_iterations take it");
     if (precision != FR_PRECISION_F64 && precision != FR_PRECISION_F32)
         return fail(FR_ERR_INVALID_ARGUMENT, "precision must be FR_PRECISION_F64 or FR_PRECISION_F32");
     return FR_OK;
@@ -675,32 +682,49 @@ int check_precision(int precision) {
 
 /* FR_PRECISION_DD's domain (include/fractal_hip.h, fr_precision): with it every hi product stays finite up to the escape
  * test — |z| <= limit <= 2^500 before a step, so |z^2| <= 2^1000 and the dd additions cannot overflow; only the escape
- * test's own dist may reach +inf, which escapes as f64 would */
-int check_dd(const fr_config *cfg, const fr_imaginary *pos_lo) {
+ * test's own dist may reach +inf, which escapes as f64 would.  FR_PRECISION_PT shares it (`name` names the precision in
+ * the messages): |dz| <= |z| + |X_m| stays below 2^501, so (2 X_m + dz) dz stays finite too. */
+static int check_deep(const fr_config *cfg, const fr_imaginary *pos_lo, const char *name) {
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    const std::string n(name);
     const double lo_re = pos_lo ? pos_lo->re : 0.0, lo_im = pos_lo ? pos_lo->im : 0.0;
     const double fields[] = {cfg->limit,    cfg->stable_limit, cfg->pos.re,       cfg->pos.im,       cfg->scale.re, cfg->scale.im,
                              cfg->exposure, cfg->color_weight, cfg->julia_set.re, cfg->julia_set.im, lo_re,         lo_im};
     for (double v : fields)
-        if (!std::isfinite(v)) return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_DD: every field of the view must be finite");
+        if (!std::isfinite(v)) return fail(FR_ERR_INVALID_ARGUMENT, n + ": every field of the view must be finite");
     if (!(cfg->limit > 0.0 && cfg->limit <= 0x1p500))
-        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_DD: limit must lie in (0, 2^500]");
+        return fail(FR_ERR_INVALID_ARGUMENT, n + ": limit must lie in (0, 2^500]");
     if (std::fabs(cfg->pos.re) > 0x1p64 || std::fabs(cfg->pos.im) > 0x1p64 || std::fabs(cfg->julia_set.re) > 0x1p64 ||
         std::fabs(cfg->julia_set.im) > 0x1p64)
-        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_DD: |pos| and |julia_set| must be <= 2^64");
+        return fail(FR_ERR_INVALID_ARGUMENT, n + ": |pos| and |julia_set| must be <= 2^64");
     if (std::fabs(cfg->scale.re) < 0x1p-64 || std::fabs(cfg->scale.im) < 0x1p-64)
-        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_DD: |scale| must be >= 2^-64 on both axes");
+        return fail(FR_ERR_INVALID_ARGUMENT, n + ": |scale| must be >= 2^-64 on both axes");
     if (cfg->pos.re + lo_re != cfg->pos.re || cfg->pos.im + lo_im != cfg->pos.im)
-        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_DD: pos_lo is not normalised (pos + pos_lo must round to pos)");
+        return fail(FR_ERR_INVALID_ARGUMENT, n + ": pos_lo is not normalised (pos + pos_lo must round to pos)");
     return FR_OK;
 }
 
-int check_precision_or_dd(const fr_config *cfg, int precision) {
-    return precision == FR_PRECISION_DD ? check_dd(cfg, nullptr) : check_precision(precision);
+int check_dd(const fr_config *cfg, const fr_imaginary *pos_lo) { return check_deep(cfg, pos_lo, "FR_PRECISION_DD"); }
+
+int check_pt(const fr_config *cfg, const fr_imaginary *pos_lo) {
+    const int rc = check_deep(cfg, pos_lo, "FR_PRECISION_PT");
+    if (rc != FR_OK) return rc;
+    if (cfg->iterations > FR_PT_MAX_ITERATIONS)
+        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_PT: iterations must be <= FR_PT_MAX_ITERATIONS (2^24): the reference "
+                                             "orbit takes 16 bytes per iteration");
+    return FR_OK;
 }
 
-int render_dd_device(const fr_config *cfg, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0, uint32_t y1, unsigned bpp,
-                     void *d_out, hipStream_t stream) {
+int check_precision_lo(const fr_config *cfg, int precision, const fr_imaginary *pos_lo) {
+    if (precision == FR_PRECISION_DD) return check_dd(cfg, pos_lo);
+    if (precision == FR_PRECISION_PT) return check_pt(cfg, pos_lo);
+    return check_precision(precision);
+}
+
+int check_precision_or_deep(const fr_config *cfg, int precision) { return check_precision_lo(cfg, precision, nullptr); }
+
+int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0,
+                       uint32_t y1, unsigned bpp, void *d_out, hipStream_t stream) {
     fr_kparams p;
     fill_params(cfg, o, p); /* the colour constants; no loop plan, no kernel choice, no view sample */
     p.nrows = y1 - y0;
@@ -719,7 +743,13 @@ int render_dd_device(const fr_config *cfg, const fr_imaginary *pos_lo, const Opt
         HIP_TRY(hipEventRecord(pr.e0, stream));
     }
     const char *kname = "";
-    HIP_TRY(fr_launch_escape_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, FR_OUT_RGB, out, false, stream, &kname));
+    if (precision == FR_PRECISION_PT) {
+        const int rc = launch_pt(ctx, cfg, pos_lo, p, FR_OUT_RGB, out, stream, &kname);
+        if (rc != FR_OK) return rc;
+    } else {
+        HIP_TRY(fr_launch_escape_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, FR_OUT_RGB, out, false, stream,
+                                    &kname));
+    }
     if (pr.enabled) {
         HIP_TRY(hipEventRecord(pr.e1, stream));
         pr.have = true;
@@ -1226,7 +1256,7 @@ static int render_rows_device(const fr_config *cfg, int precision, uint32_t y0, 
                               size_t out_len, void *hip_stream, unsigned bytes_per_pixel, const fr_render_opts *opts,
                               const fr_imaginary *pos_lo = nullptr) {
     int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = precision == FR_PRECISION_DD ? check_dd(cfg, pos_lo) : check_precision(precision);
+    if (rc == FR_OK) rc = check_precision_lo(cfg, precision, pos_lo);
     Opts o;
     if (rc == FR_OK) rc = resolve_opts(opts, o);
     if (rc != FR_OK) return rc;
@@ -1240,8 +1270,9 @@ static int render_rows_device(const fr_config *cfg, int precision, uint32_t y0, 
     Ctx *ctx;
     rc = primary(&ctx);
     if (rc != FR_OK) return rc;
-    if (precision == FR_PRECISION_DD)
-        return render_dd_device(cfg, pos_lo, o, y0, y1, bytes_per_pixel, d_out, static_cast<hipStream_t>(hip_stream));
+    if (precision == FR_PRECISION_DD || precision == FR_PRECISION_PT)
+        return render_deep_device(*ctx, precision, cfg, pos_lo, o, y0, y1, bytes_per_pixel, d_out,
+                                  static_cast<hipStream_t>(hip_stream));
     fr_kparams p;
     fill_params(cfg, o, p);
     p.nrows = y1 - y0;
@@ -1369,7 +1400,7 @@ int fr_render_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t
                       uint8_t *out, size_t out_len) {
     const int rc = dd_channels(channels);
     if (rc != FR_OK) return rc;
-    return fr_host_render_rows_dd(cfg, pos_lo, y0, y1, out, out_len, (unsigned)channels, nullptr);
+    return fr_host_render_rows_deep(cfg, FR_PRECISION_DD, pos_lo, y0, y1, out, out_len, (unsigned)channels, nullptr);
 }
 
 int fr_render_rows_dd_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
@@ -1379,6 +1410,20 @@ int fr_render_rows_dd_device(const fr_config *cfg, const fr_imaginary *pos_lo, u
     return render_rows_device(cfg, FR_PRECISION_DD, y0, y1, d_out, out_len, hip_stream, (unsigned)channels, nullptr, pos_lo);
 }
 
+int fr_render_rows_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
+                      uint8_t *out, size_t out_len) {
+    const int rc = dd_channels(channels);
+    if (rc != FR_OK) return rc;
+    return fr_host_render_rows_deep(cfg, FR_PRECISION_PT, pos_lo, y0, y1, out, out_len, (unsigned)channels, nullptr);
+}
+
+int fr_render_rows_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
+                             void *d_out, size_t out_len, void *hip_stream) {
+    const int rc = dd_channels(channels);
+    if (rc != FR_OK) return rc;
+    return render_rows_device(cfg, FR_PRECISION_PT, y0, y1, d_out, out_len, hip_stream, (unsigned)channels, nullptr, pos_lo);
+}
+
 int fr_render_rgb8(const fr_config *cfg, uint8_t *out, size_t out_len) {
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
     return fr_host_render_rows(cfg, FR_PRECISION_F64, 0, cfg->height, out, out_len, 3, nullptr);
@@ -1386,7 +1431,7 @@ int fr_render_rgb8(const fr_config *cfg, uint8_t *out, size_t out_len) {
 
 int fr_pixel_p(const fr_config *cfg, int precision, uint32_t x, uint32_t y, fr_rgb *out) {
     if (!cfg || !out) return fail(FR_ERR_INVALID_ARGUMENT, "cfg or out is NULL");
-    int rc = check_precision_or_dd(cfg, precision);
+    int rc = check_precision_or_deep(cfg, precision);
     if (rc != FR_OK) return rc;
     /* get_recursive_pixel takes any u32 x, y — it does not clamp to width/height */
     LifeShared ls;
@@ -1407,6 +1452,9 @@ int fr_pixel_p(const fr_config *cfg, int precision, uint32_t x, uint32_t y, fr_r
     ko.rgb = static_cast<uint8_t *>(ctx->misc.ptr);
     if (precision == FR_PRECISION_DD) {
         HIP_TRY(fr_launch_escape_dd(p, 0.0, 0.0, FR_OUT_RGB, ko, false, ctx->stream, nullptr));
+    } else if (precision == FR_PRECISION_PT) {
+        rc = launch_pt(*ctx, cfg, nullptr, p, FR_OUT_RGB, ko, ctx->stream, nullptr);
+        if (rc != FR_OK) return rc;
     } else {
         plan_loop(cfg, precision, o, p);
         HIP_TRY(fr_launch_escape(p, precision, FR_OUT_RGB, ko, o.tile, ctx->stream, nullptr));
@@ -1457,11 +1505,12 @@ int fr_recursive(uint32_t iterations, fr_imaginary start, fr_imaginary c, double
     return fr_recursive_batch(iterations, &start, &c, 1, limit, FR_PRECISION_F64, out_pos, out_iters);
 }
 
-/* fr_escape_rows and fr_escape_rows_dd: `zw` doubles per pixel (2: re, im — DD: the hi parts; 4: DD with the lo parts) */
+/* fr_escape_rows, fr_escape_rows_dd and fr_escape_rows_pt: `zw` doubles per pixel (2: re, im — DD: the hi parts; 4: DD with
+ * the lo parts) */
 static int escape_rows(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
                        double *z_re_im, uint32_t *iters, unsigned zw) {
     int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = precision == FR_PRECISION_DD ? check_dd(cfg, pos_lo) : check_precision(precision);
+    if (rc == FR_OK) rc = check_precision_lo(cfg, precision, pos_lo);
     if (rc != FR_OK) return rc;
     const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
     if (npx == 0 || (!z_re_im && !iters)) return FR_OK;
@@ -1486,6 +1535,9 @@ static int escape_rows(const fr_config *cfg, int precision, const fr_imaginary *
     if (precision == FR_PRECISION_DD) {
         HIP_TRY(fr_launch_escape_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, FR_OUT_ESCAPE, ko, zw == 4,
                                     ctx->stream, nullptr));
+    } else if (precision == FR_PRECISION_PT) {
+        rc = launch_pt(*ctx, cfg, pos_lo, p, FR_OUT_ESCAPE, ko, ctx->stream, nullptr);
+        if (rc != FR_OK) return rc;
     } else {
         plan_loop(cfg, precision, o, p);
         HIP_TRY(fr_launch_escape(p, precision, FR_OUT_ESCAPE, ko, o.tile, ctx->stream, nullptr));
@@ -1504,6 +1556,11 @@ int fr_escape_rows(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1
 int fr_escape_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z,
                       uint32_t *iters) {
     return escape_rows(cfg, FR_PRECISION_DD, pos_lo, y0, y1, z, iters, 4);
+}
+
+int fr_escape_rows_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z,
+                      uint32_t *iters) {
+    return escape_rows(cfg, FR_PRECISION_PT, pos_lo, y0, y1, z, iters, 2);
 }
 
 int fr_colour_rgb8(const fr_config *cfg, const double *z_re_im, const uint32_t *iters, size_t n, uint8_t *out,
@@ -1548,7 +1605,7 @@ int fr_colour_rgb8_device(const fr_config *cfg, const void *d_z_re_im, const voi
 int fr_count_iterations(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint32_t sx, uint32_t sy,
                         uint64_t *total, uint64_t *pixels) {
     int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = check_precision_or_dd(cfg, precision);
+    if (rc == FR_OK) rc = check_precision_or_deep(cfg, precision);
     if (rc != FR_OK) return rc;
     if (!total) return fail(FR_ERR_INVALID_ARGUMENT, "total is NULL");
     if (sx == 0) sx = 1;
@@ -1579,6 +1636,9 @@ int fr_count_iterations(const fr_config *cfg, int precision, uint32_t y0, uint32
     ko.count = static_cast<unsigned long long *>(ctx->misc.ptr);
     if (precision == FR_PRECISION_DD) {
         HIP_TRY(fr_launch_escape_dd(p, 0.0, 0.0, FR_OUT_COUNT, ko, false, ctx->stream, nullptr));
+    } else if (precision == FR_PRECISION_PT) {
+        rc = launch_pt(*ctx, cfg, nullptr, p, FR_OUT_COUNT, ko, ctx->stream, nullptr);
+        if (rc != FR_OK) return rc;
     } else {
         plan_loop(cfg, precision, o, p);
         HIP_TRY(fr_launch_escape(p, precision, FR_OUT_COUNT, ko, o.tile, ctx->stream, nullptr));

@@ -87,6 +87,8 @@ struct SurvSlot {
 };
 constexpr int kSurvSlots = 3;
 
+struct PtOrbit; /* fr_pt.hip */
+
 struct Ctx {
     int hip_device = -1;
     std::mutex mu; /* serialises the host-buffer entry points (they share streams + scratch) */
@@ -144,6 +146,11 @@ struct Ctx {
     struct CopyPool *copy_pool = nullptr;
     int reserve_stage(size_t bytes);
 
+    /* FR_PRECISION_PT (fr_pt.hip): the last view's reference orbits in device memory, shared with the launches that read
+     * them (the last reference frees the memory, after the device has finished with it) */
+    std::mutex pt_mu;
+    std::shared_ptr<PtOrbit> pt_orbit;
+
     int create(int device); /* hipSetDevice + streams; the calling thread stays on `device` */
     void destroy();         /* frees everything (caller made sure nothing is in flight) */
     int reserve(Scratch &s, size_t bytes);
@@ -172,12 +179,22 @@ int check_precision(int precision);
 
 /* FR_PRECISION_DD (fr_dd.hip): the domain check of include/fractal_hip.h (pos_lo NULL = (0, 0)); no device needed */
 int check_dd(const fr_config *cfg, const fr_imaginary *pos_lo);
-/* check_precision, or for FR_PRECISION_DD check_dd with pos_lo = 0: the single-device calls that accept DD */
-int check_precision_or_dd(const fr_config *cfg, int precision);
-/* DD rows [y0, y1) as RGB (bpp 3) / RGBA (bpp 4) into device memory on `stream`; arguments already checked.  Records the
- * profiling events and the kernel's name like render_device.  No host synchronisation. */
-int render_dd_device(const fr_config *cfg, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0, uint32_t y1, unsigned bpp,
-                     void *d_out, hipStream_t stream);
+/* FR_PRECISION_PT: DD's domain plus iterations <= FR_PT_MAX_ITERATIONS (include/fractal_hip.h); no device needed */
+int check_pt(const fr_config *cfg, const fr_imaginary *pos_lo);
+/* check_dd / check_pt (pos_lo = 0) for FR_PRECISION_DD / FR_PRECISION_PT, else check_precision: the single-device calls
+ * that accept the deep-zoom precisions */
+int check_precision_or_deep(const fr_config *cfg, int precision);
+/* check_dd / check_pt with pos_lo for the deep-zoom precisions, else check_precision */
+int check_precision_lo(const fr_config *cfg, int precision, const fr_imaginary *pos_lo);
+/* DD or PT rows [y0, y1) as RGB (bpp 3) / RGBA (bpp 4) into device memory on `stream`; arguments already checked.
+ * Records the profiling events and the kernel's name like render_device.  No host synchronisation (PT: apart from
+ * computing and uploading the view's reference orbit when the context does not hold it yet). */
+int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0,
+                       uint32_t y1, unsigned bpp, void *d_out, hipStream_t stream);
+/* FR_PRECISION_PT (fr_pt.hip: escape_pt_kernel): the launch's local grid, colour and limit from `p` as for DD; the view's
+ * reference orbits from ctx's cache (computed and uploaded on a miss).  MODE ESCAPE writes re, im per pixel. */
+int launch_pt(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, int mode, const fr_kout &out,
+              hipStream_t stream, const char **kernel_name);
 
 /* choose_kernel for rows [y0, y1) of the image as ONE launch, recorded in `o` (tile 0 only): callers that render those
  * rows in several launches then sample the view once, not once per launch.  The calling thread must be on ctx's device. */
@@ -256,8 +273,8 @@ void multi_shutdown_locked();
 /* shared body of the host-buffer row renders (fr_host.hip) */
 int fr_host_render_rows(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint8_t *out, size_t out_len,
                         unsigned bytes_per_pixel, const fr_render_opts *opts);
-/* the same for FR_PRECISION_DD with the centre's low halves (fr_host.hip) */
-int fr_host_render_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, uint8_t *out,
-                           size_t out_len, unsigned bytes_per_pixel, const fr_render_opts *opts);
+/* the same for FR_PRECISION_DD / FR_PRECISION_PT with the centre's low halves (fr_host.hip) */
+int fr_host_render_rows_deep(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
+                             uint8_t *out, size_t out_len, unsigned bytes_per_pixel, const fr_render_opts *opts);
 
 #endif

@@ -98,11 +98,12 @@ inline void use_devices(const std::vector<int> &devices) {
 // get_image(&Config) -> Vec<RGB> — src/lib.rs:253-270 (Mandelbrot | Julia arm).
 // get_image(config, FR_PRECISION_DD) renders a deep zoom in double-double arithmetic (include/fractal_hip.h,
 // fr_precision) on one GPU, whatever use_devices chose; a view centre off the f64 grid needs its low halves:
-// fr_render_rows_dd(&config, &pos_lo, 0, config.height, 3, out, out_len).
+// fr_render_rows_dd(&config, &pos_lo, 0, config.height, 3, out, out_len).  FR_PRECISION_PT (perturbation: the same deep
+// views, far cheaper on long orbits) renders on one GPU the same way; its low halves go through fr_render_rows_pt.
 inline std::vector<RGB> get_image(const Config &config, int precision = FR_PRECISION_F64) {
     std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
     uint8_t *out = reinterpret_cast<uint8_t *>(image.data());
-    if (multi_devices() > 1 && precision != FR_PRECISION_DD)
+    if (multi_devices() > 1 && precision != FR_PRECISION_DD && precision != FR_PRECISION_PT)
         check(fr_render_rgb8_multi(&config, precision, 0, out, image.size() * sizeof(RGB)));
     else
         check(fr_render_rows_rgb8(&config, precision, 0, config.height, out, image.size() * sizeof(RGB)));

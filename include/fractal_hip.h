@@ -124,7 +124,42 @@ typedef struct fr_config {
  * DD runs on one device: the single-device row renders, fr_pixel_p, fr_escape_rows (hi parts), fr_count_iterations
  * (all with pos_lo = 0) and the fr_*_dd calls below take it; block-cyclic, multi-device and fr_recursive_batch do not.
  * Implementation selectors (fr_set_tile, fr_render_opts, ...) select nothing for DD: it has one kernel. */
-typedef enum fr_precision { FR_PRECISION_F64 = 0, FR_PRECISION_F32 = 1, FR_PRECISION_DD = 2 } fr_precision;
+/*
+ * PT (perturbation) is DD's deep zoom at near-f64 cost for long orbits: one reference orbit per view in dd, stored as its
+ * f64 hi parts, and each pixel iterates in f64 only its offset from that orbit (with rebasing, so one orbit serves every
+ * pixel).  PT is DEFINED by this exact operation sequence (the dd operations are DD's above):
+ *   C = (pos, pos_lo) as a dd; off = DD's off (one f64 operation each, as above); a pixel's point is C + off.
+ *   Reference orbits, each iterated in dd with DD's operations of one iteration, stored as (re.hi, im.hi) per entry:
+ *     Mandelbrot R: R_0 = 0, R_1 = C, R_{k+1} = add_dd(add_dd(sqr(R_k.re), -sqr(R_k.im)), C.re),
+ *                                              add_dd(twice_mul(R_k.re, R_k.im), C.im)
+ *     Julia V (view orbit): V_0 = C, V_{k+1} = add_d(add_dd(sqr(V_k.re), -sqr(V_k.im)), J.re), add_d(twice_mul(..), J.im)
+ *     Julia K (critical orbit): K_0 = 0, K_{k+1} = the same with K for V          (J = julia_set, f64)
+ *   An orbit X stores entries X_0 .. X_last: it stops at the first k >= kmin whose stored hi parts have
+ *   re*re + im*im > 4 (f64), else at k = kmax.  R: kmin = 2, kmax = iterations + 1; V and K: kmin = 1,
+ *   kmax = max(iterations, 1).
+ *   Pixel state (X, m, z, dz, dc): the orbit followed, an index into it, the f64 position z and its offset dz from X_m.
+ *     Mandelbrot: X = R, m = 1, dz = off, dc = off.  Julia: X = V, m = 0, dz = off, dc = 0.  Then z = X_m + dz (f64).
+ *   Step i = 0 .. iterations-1:
+ *     t   = X_m + z                                                       (per axis: 2 X_m + dz of z' = z^2 + c)
+ *     dz' = (fma(t.re, dz.re, fma(-t.im, dz.im, dc.re)), fma(t.re, dz.im, fma(t.im, dz.re, dc.im)))
+ *     m   = m + 1;  z' = X_m + dz' (per axis, f64);  z = z', dz = dz'
+ *     dist = z.re*z.re + z.im*z.im: dist > limit*limit -> escape with (z, i), as recursive() (calc/src/lib.rs:245-257)
+ *     else rebase when dist < dz.re*dz.re + dz.im*dz.im or m == last of X: dz = z, m = 0 (z unchanged); Julia then
+ *     follows K (and stays on K).
+ *   Exhaustion: (z, iterations).  Colour: the colour map on the f64 z (r2 = z.re*z.re, i2 = z.im*z.im):
+ *   fr_colour_rgb8 over fr_escape_rows(_pt) reproduces the PT image.
+ * Domain: DD's (with its messages naming FR_PRECISION_PT), plus iterations <= FR_PT_MAX_ITERATIONS: the orbit takes
+ * 16 B per entry in host and device memory, so the cap bounds one orbit to 256 MiB (512 MiB for a Julia view's two).
+ * PT runs on one device exactly where DD does (pos_lo = 0 through fr_render_rows_rgb8 & co), plus the fr_*_pt calls
+ * below; block-cyclic, multi-device and fr_recursive_batch refuse it.  The library keeps the last view's orbit per
+ * context, so frames of one view, row pieces and fr_pixel_p do not recompute it. */
+#define FR_PT_MAX_ITERATIONS (1u << 24)
+typedef enum fr_precision {
+    FR_PRECISION_F64 = 0,
+    FR_PRECISION_F32 = 1,
+    FR_PRECISION_DD = 2,
+    FR_PRECISION_PT = 3
+} fr_precision;
 
 /* ---- lifetime ---------------------------------------------------------------------------- */
 
@@ -321,6 +356,22 @@ int fr_render_rows_dd_device(const fr_config *cfg, const fr_imaginary *pos_lo, u
  * re.hi, re.lo, im.hi, im.lo of the final position, iters[k] = escape index, k = (y-y0)*width + x. */
 int fr_escape_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z,
                       uint32_t *iters);
+
+/* ---- deep zoom: FR_PRECISION_PT (perturbation) with the low halves of the view centre ----------------- */
+
+/* as fr_render_rows_dd / fr_render_rows_dd_device / fr_escape_rows_dd in FR_PRECISION_PT; z holds 2 doubles per pixel
+ * (z[2k] = re, z[2k+1] = im) */
+int fr_render_rows_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
+                      uint8_t *out, size_t out_len);
+int fr_render_rows_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
+                             void *d_out, size_t out_len, void *hip_stream);
+int fr_escape_rows_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z,
+                      uint32_t *iters);
+/* FR_PRECISION_PT's reference orbit of the view, computed on the host (no device needed): which 0 = R (Mandelbrot) or V
+ * (Julia), 1 = K (Julia only).  *len receives the number of entries; min(*len, cap) of them are written to out as
+ * re, im pairs (2 doubles per entry). */
+int fr_debug_reference_orbit(const fr_config *cfg, const fr_imaginary *pos_lo, int which, double *out, size_t cap,
+                             uint32_t *len);
 
 /* ---- get_recursive_pixel — calc/src/lib.rs:199-235 ---------------------------------------- */
 

@@ -55,6 +55,8 @@ pub const FR_PRECISION_F64: c_int = 0;
 pub const FR_PRECISION_F32: c_int = 1;
 /// Double-double (~106-bit) arithmetic for zooms past the f64 limit (include/fractal_hip.h, `fr_precision`).
 pub const FR_PRECISION_DD: c_int = 2;
+/// Perturbation: one double-double reference orbit per view, f64 offsets per pixel (include/fractal_hip.h, `fr_precision`).
+pub const FR_PRECISION_PT: c_int = 3;
 
 extern "C" {
     pub fn fr_init(device: c_int) -> c_int;
@@ -91,6 +93,10 @@ extern "C" {
     pub fn fr_render_rows_dd(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, channels: c_int, out: *mut u8, out_len: usize) -> c_int;
     pub fn fr_render_rows_dd_device(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, channels: c_int, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
     pub fn fr_escape_rows_dd(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, z: *mut f64, iters: *mut u32) -> c_int;
+    // deep zoom: FR_PRECISION_PT (perturbation) with the low halves of the view centre (NULL = (0, 0))
+    pub fn fr_render_rows_pt(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, channels: c_int, out: *mut u8, out_len: usize) -> c_int;
+    pub fn fr_render_rows_pt_device(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, channels: c_int, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_escape_rows_pt(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, z: *mut f64, iters: *mut u32) -> c_int;
 }
 
 /// Message of the last failing call on this thread.
@@ -215,6 +221,21 @@ pub fn get_image_dd<P: Copy>(cfg: &fr_config, pos_lo: fr_imaginary, image: &mut 
     image.clear();
     image.reserve_exact(n);
     let rc = unsafe { fr_render_rows_dd(cfg, &pos_lo, 0, cfg.height, 3, image.as_mut_ptr() as *mut u8, n * 3) };
+    if rc != FR_OK {
+        return Err(last_error());
+    }
+    unsafe { image.set_len(n) }; // every byte was written by the library
+    Ok(())
+}
+
+/// `get_image_dd` in perturbation arithmetic (`FR_PRECISION_PT`): the same deep views at near-f64 cost on long orbits.
+/// The view's reference orbit is computed on the host once and kept for the next frames of the same view.
+pub fn get_image_pt<P: Copy>(cfg: &fr_config, pos_lo: fr_imaginary, image: &mut Vec<P>) -> Result<(), String> {
+    assert_eq!(std::mem::size_of::<P>(), 3, "pixel type must be 3 packed bytes");
+    let n = cfg.width as usize * cfg.height as usize;
+    image.clear();
+    image.reserve_exact(n);
+    let rc = unsafe { fr_render_rows_pt(cfg, &pos_lo, 0, cfg.height, 3, image.as_mut_ptr() as *mut u8, n * 3) };
     if rc != FR_OK {
         return Err(last_error());
     }
