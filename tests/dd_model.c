@@ -156,6 +156,22 @@ void ddm_escape_rows(const ddm_config *cfg, double lo_re, double lo_im, uint32_t
     }
 }
 
+/* one pixel at any (x, y), inside the image or not (get_recursive_pixel does not clamp x, y to the image, and off_re
+ * depends on the width, so no row range stands in for it): z4 = re.hi, re.lo, im.hi, im.lo; returns the escape index */
+uint32_t ddm_pixel(const ddm_config *cfg, double lo_re, double lo_im, uint32_t x, uint32_t y, double z4[4]) {
+    ddv re = {0.0, 0.0}, im = {0.0, 0.0};
+    uint32_t it = 0;
+    if (escape_algo(cfg)) {
+        start_of(cfg, lo_re, lo_im, x, y, &re, &im);
+        it = orbit(cfg, &re, &im);
+    }
+    z4[0] = re.hi;
+    z4[1] = re.lo;
+    z4[2] = im.hi;
+    z4[3] = im.lo;
+    return it;
+}
+
 /* the start coordinates alone (iterations = 0 gives the same through ddm_escape_rows) */
 void ddm_start(const ddm_config *cfg, double lo_re, double lo_im, uint32_t x, uint32_t y, double out4[4]) {
     ddv re, im;

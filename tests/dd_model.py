@@ -37,6 +37,8 @@ def lib():
     L.ddm_escape_rows.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]
     L.ddm_start.restype = None
     L.ddm_start.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ddm_pixel.restype = C.c_uint32
+    L.ddm_pixel.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_void_p]
     L.ddm_count_iterations.restype = C.c_uint64
     L.ddm_count_iterations.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
     _lib = L
@@ -61,6 +63,13 @@ def start(cfg, x, y, pos_lo=(0.0, 0.0)):
     out = np.empty(4, dtype=np.float64)
     lib().ddm_start(_cfg_ptr(cfg), float(pos_lo[0]), float(pos_lo[1]), x, y, out.ctypes.data)
     return out
+
+
+def pixel(cfg, x, y, pos_lo=(0.0, 0.0)):
+    """one pixel at any u32 (x, y), inside the image or not: (z float64 [4] = re.hi, re.lo, im.hi, im.lo, index)"""
+    z = np.empty(4, dtype=np.float64)
+    it = lib().ddm_pixel(_cfg_ptr(cfg), float(pos_lo[0]), float(pos_lo[1]), x, y, z.ctypes.data)
+    return z, int(it)
 
 
 def count_iterations(cfg, y0=0, y1=None):

@@ -233,6 +233,19 @@ int ptm_escape_rows(const ptm_config *cfg, double lo_re, double lo_im, uint32_t 
     return 1;
 }
 
+/* one pixel at any (x, y), inside the image or not (as ddm_pixel): z2 = re, im; *iters = the escape index.  Returns 0 on
+ * allocation failure. */
+int ptm_pixel(const ptm_config *cfg, double lo_re, double lo_im, uint32_t x, uint32_t y, double z2[2], uint32_t *iters) {
+    z2[0] = z2[1] = 0.0;
+    *iters = 0;
+    if (!escape_algo(cfg)) return 1;
+    orbits o;
+    if (!make_orbits(cfg, lo_re, lo_im, &o)) return 0;
+    *iters = pixel(cfg, &o, x, y, &z2[0], &z2[1]);
+    free_orbits(&o);
+    return 1;
+}
+
 /* executed iterations over rows [y0, y1) with pos_lo = 0: escape at index i -> i + 1, exhaustion -> iterations */
 uint64_t ptm_count_iterations(const ptm_config *cfg, uint32_t y0, uint32_t y1, int threads) {
     uint64_t total = 0;

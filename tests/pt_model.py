@@ -40,6 +40,8 @@ def lib():
     L = C.CDLL(so)
     L.ptm_escape_rows.restype = C.c_int
     L.ptm_escape_rows.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]
+    L.ptm_pixel.restype = C.c_int
+    L.ptm_pixel.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.ptm_count_iterations.restype = C.c_uint64
     L.ptm_count_iterations.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
     L.ptm_orbit_capacity.restype = C.c_uint32
@@ -64,6 +66,15 @@ def escape_rows(cfg, pos_lo=(0.0, 0.0), y0=0, y1=None):
                                THREADS)
     assert ok, "pt_model: out of memory"
     return z, it
+
+
+def pixel(cfg, x, y, pos_lo=(0.0, 0.0)):
+    """one pixel at any u32 (x, y), inside the image or not: (z float64 [2] = re, im, index)"""
+    z = np.empty(2, dtype=np.float64)
+    it = C.c_uint32(0)
+    ok = lib().ptm_pixel(_cfg_ptr(cfg), float(pos_lo[0]), float(pos_lo[1]), x, y, z.ctypes.data, C.byref(it))
+    assert ok, "pt_model: out of memory"
+    return z, it.value
 
 
 def count_iterations(cfg, y0=0, y1=None):

@@ -171,7 +171,9 @@ def test_count_iterations(fr, name):
 
 def test_two_threads_render_two_views(fr):
     """Two threads, two different PT views, many frames each at the same time: the orbit cache of the context is
-    replaced under the other thread's feet, and each thread still gets its own view's image every time."""
+    replaced under the other thread's feet, and each thread still gets its own view's image every time.  A DD thread
+    (host and device renders) and an F64 thread on the staged host-buffer road run beside them: the deep host path and
+    the F64 road share the context's lock and scratch."""
     import torch
 
     from fractal_renderer_amd import _native
@@ -179,6 +181,15 @@ def test_two_threads_render_two_views(fr):
     lib = _native.load()
     views = [view(fr, "deep_mandelbrot", 160, 96, 3000)[0], view(fr, "julia_rebase", 160, 96)[0]]
     want = [model_colours(c, *M.escape_rows(c)) for c in views]
+    dd_cfg = view(fr, "deep_julia", 160, 96)[0]
+    dz, dit = D.escape_rows(dd_cfg)
+    views.append(dd_cfg)
+    want.append(model_colours(dd_cfg, np.ascontiguousarray(dz[..., 0::2]), dit))
+    f64_cfg = view(fr, "default", 700, 500)[0]
+    views.append(f64_cfg)
+    O.set_log2_mode(O.LOG2_SOFT)  # the F64 kernels' log2
+    want.append(O.get_image(O.Config.from_buffer_copy(bytes(f64_cfg))))
+    O.set_log2_mode(O.LOG2_LIBM)
     errors = []
 
     def worker(k):
@@ -187,11 +198,13 @@ def test_two_threads_render_two_views(fr):
             stream = torch.cuda.Stream(torch.device("cuda", 0))
             d = torch.zeros(cfg.width * cfg.height * 3, dtype=torch.uint8, device=torch.device("cuda", 0))
             for frame in range(12):
-                if frame % 2:
-                    img = fr.get_image(cfg, fr.Precision.PT)
+                if k == 3:  # F64 through the host-buffer road
+                    img = fr.get_image(cfg)
+                elif frame % 2:
+                    img = fr.get_image(cfg, fr.Precision.DD if k == 2 else fr.Precision.PT)
                 else:
-                    _native.check(lib.fr_render_rows_pt_device(C.byref(cfg), None, 0, cfg.height, 3, d.data_ptr(), d.numel(),
-                                                               stream.cuda_stream))
+                    render = lib.fr_render_rows_dd_device if k == 2 else lib.fr_render_rows_pt_device
+                    _native.check(render(C.byref(cfg), None, 0, cfg.height, 3, d.data_ptr(), d.numel(), stream.cuda_stream))
                     stream.synchronize()
                     img = d.cpu().numpy().reshape(cfg.height, cfg.width, 3)
                 if not np.array_equal(img, want[k]):
@@ -199,7 +212,7 @@ def test_two_threads_render_two_views(fr):
         except Exception as e:  # noqa: BLE001 - reported below
             errors.append((k, repr(e)))
 
-    threads = [threading.Thread(target=worker, args=(k,)) for k in range(2)]
+    threads = [threading.Thread(target=worker, args=(k,)) for k in range(len(views))]
     for t in threads:
         t.start()
     for t in threads:
