@@ -225,6 +225,8 @@ PROTOTYPES = {
     "fr_set_loop_mode": (C.c_int, [C.c_int]),
     "fr_debug_loop_plan": (C.c_int, [C.POINTER(fr_config), C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                                      C.POINTER(C.c_uint32)]),
+    "fr_debug_set_spec_maxlen": (C.c_int, [C.c_uint32]),
+    "fr_debug_spec_maxlen": (C.c_int, [C.POINTER(fr_config), C.c_int, C.POINTER(C.c_uint32)]),
     "fr_set_palette": (C.c_int, [C.c_int]),
     "fr_set_cycle_shortcut": (C.c_int, [C.c_int]),
     "fr_set_refill_policy": (C.c_int, [C.c_int, C.c_int]),

@@ -52,6 +52,7 @@ std::atomic<int> g_loop_mode{-1}; /* -1 auto, 0 unscaled, 2 / 4 scaled with that
 std::atomic<int> g_colour_filter{1};
 std::atomic<unsigned long long *> g_queue_trace{nullptr}; /* tuning aid, see fr_debug_set_queue_trace */
 std::atomic<uint32_t> g_two_pass_list_entries{0};          /* test aid, see fr_debug_set_two_pass_capacity */
+std::atomic<uint32_t> g_spec_maxlen{0};                    /* test / tool aid, see fr_debug_set_spec_maxlen; 0 = kSpecMaxLen */
 
 bool valid_tile(int tile) {
     switch (tile) {
@@ -584,6 +585,18 @@ static double host_coord(double coord, double max, double offset, double pos, do
 }
 
 constexpr uint32_t kSpecQuiet = 16;
+/* The scaled loop's speculative blocks start at kSpecBlock iterations (FR_SPEC_M of fr_kernels.hip) and double while the
+ * tile stays quiet, up to kSpecMaxLen (fr_kparams::loop_spec_max). */
+constexpr uint32_t kSpecBlock = 16, kSpecMaxLen = 128;
+
+/* the longest speculative block of this process's renders: the default, or what fr_debug_set_spec_maxlen asked for,
+ * brought to what the kernel's block policy takes (a power-of-two multiple of kSpecBlock) */
+static uint32_t spec_maxlen() {
+    const uint32_t asked = g_spec_maxlen.load(), want = asked ? asked : kSpecMaxLen;
+    uint32_t len = kSpecBlock;
+    while (len < 0x8000u && 2u * len <= want) len *= 2u; /* the largest kSpecBlock * 2^k <= want */
+    return len;
+}
 
 /* Choose the orbit-loop plan for a launch whose local grid is already set in `p`
  * (see fr_kernels.hip, "orbit loop, scaled form", for what the kernel does with it and why it is
@@ -596,6 +609,7 @@ void plan_loop(const fr_config *cfg, int precision, const Opts &o, fr_kparams &p
     p.loop_mode = 0;
     p.skip_t = 0.0;
     p.loop_spec = 0;
+    p.loop_spec_max = 0;
     /* 5 = automatic, but without the speculative long blocks (A/B and tests) */
     const bool no_spec = o.loop_mode == 5;
     const int forced = no_spec ? -1 : o.loop_mode;
@@ -637,6 +651,7 @@ void plan_loop(const fr_config *cfg, int precision, const Opts &o, fr_kparams &p
     if (!no_spec && lim2 >= 16.0 && lim2 <= (f32 ? 0x1p100 : 0x1p1000) && cmax <= lim2 / 8.0 && smax <= (f32 ? 0x1p120 : 0x1p1000)) {
         static const int dbg = getenv("FR_DEBUG_SPEC_QUIET") ? atoi(getenv("FR_DEBUG_SPEC_QUIET")) : 0; /* tuning aid */
         p.loop_spec = dbg > 0 ? (uint32_t)dbg : kSpecQuiet;
+        p.loop_spec_max = spec_maxlen();
     }
     if (forced == 0) return;
     if (!(std::fabs(cfg->limit) <= range_hi)) return; /* also rejects NaN */
@@ -655,7 +670,7 @@ void plan_loop(const fr_config *cfg, int precision, const Opts &o, fr_kparams &p
         if (t >= 4.5 || (forced == m && t > 0.0)) {
             p.loop_mode = (uint32_t)m;
             p.skip_t = t;
-            if (!(t < lim2)) p.loop_spec = 0; /* (cannot happen: T <= sqrt(limit^2 / 2); the scaled blocks test against T) */
+            if (!(t < lim2)) p.loop_spec = p.loop_spec_max = 0; /* (cannot happen: T <= sqrt(limit^2 / 2); the scaled blocks test against T) */
             return;
         }
     }
@@ -1798,6 +1813,29 @@ int fr_debug_view_choice(const fr_config *cfg, int precision, uint32_t y0, uint3
         *strip_tiles = v.strip_tiles;
         break;
     }
+    return FR_OK;
+}
+
+/* test / tool aid: the longest speculative block of the scaled loop for every later render of this process (0 = the
+ * default); the A/B tool and the tests switch it between renders of one process */
+int fr_debug_set_spec_maxlen(uint32_t maxlen) {
+    g_spec_maxlen.store(maxlen);
+    return FR_OK;
+}
+
+/* what fr_debug_loop_plan's launch would run with: host arithmetic only */
+int fr_debug_spec_maxlen(const fr_config *cfg, int precision, uint32_t *maxlen) {
+    if (!cfg || !maxlen) return fail(FR_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = check_precision(precision);
+    if (rc != FR_OK) return rc;
+    const Opts o = default_opts();
+    fr_kparams p;
+    fill_params(cfg, o, p);
+    p.nrows = cfg->height;
+    p.block_rows = cfg->height ? cfg->height : 1;
+    p.y_stride = 0;
+    plan_loop(cfg, precision, o, p);
+    *maxlen = p.loop_spec_max;
     return FR_OK;
 }
 

@@ -49,6 +49,11 @@ struct fr_kparams {
      * escape inside a block is visible at its end — fr_api.hip: plan_loop — was asked not to, or the view's statistics say
      * that nothing stays).  The two-iteration scaled blocks (loop_mode 2) do not speculate. */
     uint32_t loop_spec;
+    /* loop_mode 4's speculative blocks grow while a tile stays quiet: FR_SPEC_M iterations, doubling after every block
+     * that passes its end test, up to this many (a power-of-two multiple of FR_SPEC_M; FR_SPEC_M or less = blocks of
+     * FR_SPEC_M only), and FR_SPEC_M for good once the tile has thrown a block away (fr_kernels.hip: FR_SC_SPEC_BODY).
+     * 0 wherever loop_spec is 0. */
+    uint32_t loop_spec_max;
     uint32_t first_no_spec; /* 1: the two-pass render's first kernel runs in its plain form whatever loop_spec says (the view's
                              * statistics: nothing stays in its tiles; fr_api.hip: decide_from_sample) */
     /* smooth == false only: palette[i] = packed r | g << 8 | b << 16 of an OUTSIDE pixel whose

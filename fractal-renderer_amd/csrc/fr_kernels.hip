@@ -108,7 +108,7 @@ constexpr int kWaves = 4; /* 256-thread workgroups */
 #define FR_ORBIT_RECORD_A(TAG, OFFSET)             \
     FR_ORBIT_RECORD_(TAG, OFFSET, "s_add_u32 %[sspec], %[si], %[specq]\n" "s_cselect_b32 %[sspec], -1, %[sspec]\n" "s_min_u32 %[sspec], %[sspec], %[n]\n")
 
-/* length of a speculative block (FR_ORBIT_ASM, FR_SC_SPEC_BODY, FR_FB_SPEC_LOOP): FR_SPEC_M iterations */
+/* length of a speculative block (FR_ORBIT_ASM, FR_FB_SPEC_LOOP) and of the shortest one of FR_SC_SPEC_BODY, whose blocks grow: FR_SPEC_M iterations */
 #ifndef FR_SPEC_M
 #define FR_SPEC_M 16
 #endif
@@ -349,24 +349,47 @@ __device__ __forceinline__ uint32_t orbit(uint32_t iterations, T &re, T &im, T c
     "s_add_u32 %[sspec], %[si], %[specq]\n"                                        \
     "s_cselect_b32 %[sspec], -1, %[sspec]\n"                                       \
     "s_min_u32 %[sspec], %[sspec], %[n]\n"
+/* Blocks that GROW while a tile stays quiet.  The rollback needs only that a block never overwrites its start state, and
+ * after its first iteration a block works in place in the other register set anyway: so a block may be any multiple of
+ * FR_SPEC_M long at no register cost — one iteration S -> D, L - 1 in place in D, ONE test, the next block D -> S.  The
+ * exactness argument above does not depend on L: past limit^2 the distances only grow, through +inf to NaN, however
+ * long the block goes on, and v_cmp_nge is true for all of them; a lane that wandered above T and came back under it
+ * inside a block was iterated by the same six instructions it would have been given on the checked road.
+ * Policy: every entry from the checked code starts at L = FR_SPEC_M; L doubles after each block that passes its test,
+ * up to %[lcap] (fr_kparams::loop_spec_max, a power-of-two multiple of FR_SPEC_M), and is halved until it fits the
+ * iterations left to the cap (under FR_SPEC_M left: back to the blocks of four).  A tile that has thrown a block away
+ * sets %[lcap] = FR_SPEC_M and keeps it: ragged tiles that regrow lose more in thrown-away work than the tests they save.
+ * An interior tile of C2 (cap 1024) is tested at 16, 32, 64, 128 x 7: 10 times where blocks of 16 test 63 times.
+ * %[nrem] is free once the remainder loop is done and carries L; %[stmp] counts a block's iterations down. */
+#define FR_SC_SPEC_BLOCK(SFX, MSTR, REST, TAG, S, D, RB, NEXT, EXIT)               \
+    ".Lblk" TAG "_%=:\n" FR_SC_IT_R(SFX, S, D)                                     \
+    "s_mov_b32 %[stmp], %[nrem]\n"                                                 \
+    ".Lmid" TAG "_%=:\n" REST(SFX, D)                                              \
+    "s_sub_u32 %[stmp], %[stmp], " MSTR "\n"                                       \
+    "s_cmp_lt_u32 %[stmp], " MSTR "\n"                                             \
+    "s_cbranch_scc1 .Ltst" TAG "_%=\n"                                             \
+    FR_SC_IT_R(SFX, D, D)                                                          \
+    "s_branch .Lmid" TAG "_%=\n"                                                   \
+    ".Ltst" TAG "_%=:\n"                                                           \
+    "v_add_" SFX " %[t], %[A" D "], %[B" D "]\n"                                   \
+    "v_cmp_nge_" SFX " vcc, %[t4lim], %[t]\n"                                      \
+    "s_cbranch_vccnz " RB "\n"                                                     \
+    "s_add_u32 %[si], %[si], %[nrem]\n"                                            \
+    "s_lshl_b32 %[nrem], %[nrem], 1\n"                                             \
+    "s_min_u32 %[nrem], %[nrem], %[lcap]\n"                                        \
+    "s_sub_u32 %[stmp], %[n], %[si]\n"                                             \
+    ".Lfit" TAG "_%=:\n"                                                           \
+    "s_cmp_le_u32 %[nrem], %[stmp]\n"                                              \
+    "s_cbranch_scc1 " NEXT "\n"                                                    \
+    "s_lshr_b32 %[nrem], %[nrem], 1\n"                                             \
+    "s_cmp_ge_u32 %[nrem], " MSTR "\n"                                             \
+    "s_cbranch_scc1 .Lfit" TAG "_%=\n"                                             \
+    "s_branch " EXIT "\n"
 #define FR_SC_SPEC_BODY(SFX, MOV, MSTR, REST)                                      \
-    ".Lspec_%=:\n" FR_SC_IT_R(SFX, "", "1") REST(SFX, "1")                         \
-    "v_add_" SFX " %[t], %[A1], %[B1]\n"                                           \
-    "v_cmp_nge_" SFX " vcc, %[t4lim], %[t]\n"                                      \
-    "s_cbranch_vccnz .LrbA_%=\n"                                                   \
-    "s_add_u32 %[si], %[si], " MSTR "\n"                                           \
-    "s_sub_u32 %[stmp], %[n], %[si]\n"                                             \
-    "s_cmp_ge_u32 %[stmp], " MSTR "\n"                                             \
-    "s_cbranch_scc0 .LexA_%=\n"                                                    \
-    FR_SC_IT_R(SFX, "1", "") REST(SFX, "")                                         \
-    "v_add_" SFX " %[t], %[A], %[B]\n"                                             \
-    "v_cmp_nge_" SFX " vcc, %[t4lim], %[t]\n"                                      \
-    "s_cbranch_vccnz .LrbB_%=\n"                                                   \
-    "s_add_u32 %[si], %[si], " MSTR "\n"                                           \
-    "s_sub_u32 %[stmp], %[n], %[si]\n"                                             \
-    "s_cmp_ge_u32 %[stmp], " MSTR "\n"                                             \
-    "s_cbranch_scc1 .Lspec_%=\n"                                                   \
-    "s_branch .Lspecout_%=\n"                                                      \
+    ".Lspec_%=:\n"                                                                 \
+    "s_mov_b32 %[nrem], " MSTR "\n"                                                \
+    FR_SC_SPEC_BLOCK(SFX, MSTR, REST, "A", "", "1", ".LrbA_%=", ".LblkB_%=", ".LexA_%=") \
+    FR_SC_SPEC_BLOCK(SFX, MSTR, REST, "B", "1", "", ".LrbB_%=", ".LblkA_%=", ".Lspecout_%=") \
     ".LexA_%=:\n"                                                                  \
     MOV " %[X], %[X1]\n" MOV " %[Y], %[Y1]\n" MOV " %[A], %[A1]\n" MOV " %[B], %[B1]\n" \
     ".Lspecout_%=:\n"                                                              \
@@ -377,6 +400,7 @@ __device__ __forceinline__ uint32_t orbit(uint32_t iterations, T &re, T &im, T c
     ".LrbB_%=:\n"                                                                  \
     MOV " %[X], %[X1]\n" MOV " %[Y], %[Y1]\n" MOV " %[A], %[A1]\n" MOV " %[B], %[B1]\n" \
     ".LrbA_%=:\n"                                                                  \
+    "s_mov_b32 %[lcap], " MSTR "\n"                                                \
     "s_lshl_b32 %[specq], %[specq], 1\n"                                           \
     "s_min_u32 %[specq], %[specq], 0x8000\n"                                       \
     FR_SC_SPEC_ARM                                                                 \
@@ -501,7 +525,7 @@ __device__ __forceinline__ uint32_t orbit(uint32_t iterations, T &re, T &im, T c
 #define FR_SC_ASM_M4(SFX) FR_SC_ASM_M4_(SFX, "", "", "", "", "", FR_SC_NOSPEC_ENTRY, "")
 #define FR_SC_ASM_M2(SFX) FR_SC_ASM_M2_(SFX, "", "", "")
 #define FR_SC_ASM_M4_SPEC(SFX, MOV)                                                                 \
-    FR_SC_ASM_M4_(SFX, "", "", "", "s_min_u32 %[sspec], %[specq], %[n]\n", FR_SC_SPEC_ARM, FR_SC_SPEC_ENTRY(FR_SPEC_MSTR), \
+    FR_SC_ASM_M4_(SFX, "", "", "", "s_min_u32 %[sspec], %[specq], %[n]\n" "s_max_u32 %[lcap], %[lcap], " FR_SPEC_MSTR "\n", FR_SC_SPEC_ARM, FR_SC_SPEC_ENTRY(FR_SPEC_MSTR), \
                   FR_SC_SPEC_BODY(SFX, MOV, FR_SPEC_MSTR, FR_SC_SPEC_REST))
 #define FR_SC_CYC_HANDLERS(MOV) \
     FR_SC_CYC_HANDLER("F") FR_SC_CYC_HANDLER("S") FR_SC_CYC_SAVE(MOV, "F") FR_SC_CYC_SAVE(MOV, "S")
@@ -543,12 +567,14 @@ template <typename T, int M, bool CYC>
 __device__ __forceinline__ uint32_t orbit_scaled_run(uint32_t iterations, T &X, T &Y, T &A, T &B, T c2re, T c2im,
                                                      T squared, T skip_t, EpisodeCtl ctl, uint32_t &completed,
                                                      T *pXs = nullptr, T *pYs = nullptr,
-                                                     uint32_t *saved_index = nullptr, uint32_t spec_quiet = 0u) {
+                                                     uint32_t *saved_index = nullptr, uint32_t spec_quiet = 0u,
+                                                     uint32_t spec_maxlen = 0u) {
     uint32_t it;
     T t, q;
     T X1, Y1, A1, B1; /* M == 4 && !CYC: the second register set of the speculative blocks (FR_SC_SPEC_BODY) */
     uint32_t sspec;
     uint32_t specq = __builtin_amdgcn_readfirstlane(spec_quiet ? spec_quiet : 0xFFFFFFFFu); /* 0 = never; doubles with every block thrown away */
+    uint32_t lcap = __builtin_amdgcn_readfirstlane(spec_maxlen); /* the blocks grow up to this length (FR_SC_SPEC_BODY); FR_SPEC_M once one was thrown away */
     T Xs = CYC ? *pXs : T(0), Ys = CYC ? *pYs : T(0);
     uint32_t vsaved = 0xFFFFFFFFu; /* CYC: the run's iteration count at this lane's latest save, if any */
     uint32_t snext = 32u;          /* CYC: next save point of Brent's schedule within this run */
@@ -567,7 +593,7 @@ __device__ __forceinline__ uint32_t orbit_scaled_run(uint32_t iterations, T &X, 
 #define FR_SC_OPERANDS : FR_SC_OUTPUTS : FR_SC_INPUTS : "vcc", "scc"
 #define FR_SC_OPERANDS_SPEC                                                                                     \
     : FR_SC_OUTPUTS, [X1] "=&v"(X1), [Y1] "=&v"(Y1), [A1] "=&v"(A1), [B1] "=&v"(B1), [sspec] "=&s"(sspec),      \
-      [specq] "+&s"(specq)                                                                                      \
+      [specq] "+&s"(specq), [lcap] "+&s"(lcap)                                                                  \
     : FR_SC_INPUTS                                                                                              \
     : "vcc", "scc"
 #define FR_SC_OPERANDS_CYC                                                                                      \
@@ -602,7 +628,7 @@ __device__ __forceinline__ uint32_t orbit_scaled_run(uint32_t iterations, T &X, 
     }
     (void)scyc;
     (void)snext;
-    (void)X1, (void)Y1, (void)A1, (void)B1, (void)sspec, (void)specq;
+    (void)X1, (void)Y1, (void)A1, (void)B1, (void)sspec, (void)specq, (void)lcap;
     if constexpr (CYC) {
         *pXs = Xs;
         *pYs = Ys;
@@ -615,11 +641,11 @@ __device__ __forceinline__ uint32_t orbit_scaled_run(uint32_t iterations, T &X, 
 /* recursive() from the start through the scaled loop.  Same contract as orbit(). */
 template <typename T, int M>
 __device__ __forceinline__ uint32_t orbit_scaled(uint32_t iterations, T &re, T &im, T cre, T cim, T squared,
-                                                 T skip_t, T &r2, T &i2, uint32_t spec_quiet = 0u) {
+                                                 T skip_t, T &r2, T &i2, uint32_t spec_quiet = 0u, uint32_t spec_maxlen = 0u) {
     T X = re + re, Y = im + im, A = X * X, B = Y * Y;
     uint32_t completed;
     const uint32_t it = orbit_scaled_run<T, M, false>(iterations, X, Y, A, B, cre + cre, cim + cim, squared, skip_t,
-                                               EpisodeCtl{0, 0}, completed, nullptr, nullptr, nullptr, spec_quiet);
+                                               EpisodeCtl{0, 0}, completed, nullptr, nullptr, nullptr, spec_quiet, spec_maxlen);
     re = X * (T)0.5; /* exact */
     im = Y * (T)0.5;
     r2 = re * re; /* recomputed from the final position: the reference's own re*re, im*im */
@@ -633,13 +659,13 @@ __device__ __forceinline__ uint32_t orbit_scaled(uint32_t iterations, T &re, T &
 template <typename T>
 __device__ __forceinline__ uint32_t orbit_auto(uint32_t loop_mode, uint32_t iterations, T &re, T &im, T cre, T cim,
                                                T squared, T skip_t, T &r2, T &i2, int strip_scalable = -1,
-                                               uint32_t spec_quiet = 0u) {
+                                               uint32_t spec_quiet = 0u, uint32_t spec_maxlen = 0u) {
     if (loop_mode != 0 && strip_scalable != 0) {
         /* admissibility: decided once per strip by the caller (1), or per call from the lanes' values */
         bool all_ok = strip_scalable == 1;
         if (strip_scalable < 0) all_ok = __ballot(!lane_is_scalable<T>(re, im, cre, cim)) == 0ull;
         if (all_ok) {
-            if (loop_mode == 4) return orbit_scaled<T, 4>(iterations, re, im, cre, cim, squared, skip_t, r2, i2, spec_quiet);
+            if (loop_mode == 4) return orbit_scaled<T, 4>(iterations, re, im, cre, cim, squared, skip_t, r2, i2, spec_quiet, spec_maxlen);
             return orbit_scaled<T, 2>(iterations, re, im, cre, cim, squared, skip_t, r2, i2);
         }
     }
@@ -765,11 +791,17 @@ __device__ __forceinline__ uint32_t colour_packed(bool valid, bool fast_colour, 
             d32 = (float)(r2 + i2);
         else
             d32 = r2 + i2; /* within 2^-23 of the reference's f64 sum: see colour_pixel */
-        uint32_t pk;
-        const bool decided = colour_fast32(f, d32, (float)(iters + 1u), pk); /* exact: iterations < 2^24 (the host checks) */
-        const bool ok = valid && d32 >= f.lo && d32 <= 0x1.ffffep119f && decided;
-        packed = ok ? pk : 0u;
-        todo &= ~ballot64(ok);
+        /* wave-uniform: a tile with no lane outside (a quarter of C2's tiles lie inside the set) skips the stage — the two
+         * logs, the windows, the six casts — whose results rule 1 would drop lane by lane anyway.  The test is on the
+         * distance alone, as the rule is: a lane may sit at the cap with a large distance. */
+        const unsigned long long outside = ballot64(valid && d32 >= f.lo);
+        if (outside != 0ull) {
+            uint32_t pk;
+            const bool decided = colour_fast32(f, d32, (float)(iters + 1u), pk); /* exact: iterations < 2^24 (the host checks) */
+            const bool ok = lane_in(outside) && d32 <= 0x1.ffffep119f && decided;
+            packed = ok ? pk : 0u;
+            todo &= ~ballot64(ok);
+        }
     }
     if (todo != 0ull) { /* wave-uniform */
         bool inside_done = false;
@@ -819,14 +851,14 @@ __device__ __forceinline__ void render_pixel(const fr_kparams &p, const fr_kout 
             tre = sre;
             tim = sim;
             iters = orbit_auto<double>(p.loop_mode, p.iterations, tre, tim, cre, cim, p.limit * p.limit, p.skip_t,
-                                       tr2, ti2, strip_scalable, p.loop_spec);
+                                       tr2, ti2, strip_scalable, p.loop_spec, p.loop_spec_max);
             zre = tre;
             zim = tim;
         } else {
             tre = (float)sre, tim = (float)sim;
             const float lim = (float)p.limit;
             iters = orbit_auto<float>(p.loop_mode, p.iterations, tre, tim, (float)cre, (float)cim, lim * lim,
-                                      (float)p.skip_t, tr2, ti2, strip_scalable, p.loop_spec);
+                                      (float)p.skip_t, tr2, ti2, strip_scalable, p.loop_spec, p.loop_spec_max);
             zre = (double)tre;
             zim = (double)tim;
         }
@@ -2100,7 +2132,7 @@ __device__ __forceinline__ void refill_patch(const fr_kparams &p, const fr_kout 
                 it = orbit_run<T>(n, a0, a1, c0, c1, squared, a2, a3, ctl, completed, p.loop_spec);
             else
                 it = orbit_scaled_run<T, FORM, CYC>(n, a0, a1, a2, a3, c0, c1, squared, skip_t, ctl, completed, &xs, &ys,
-                                                    &saved_index, p.loop_spec);
+                                                    &saved_index, p.loop_spec, p.loop_spec_max);
         }
         /* ---- retire the lanes that finished */
         if (busy) {

@@ -528,6 +528,14 @@ int fr_set_loop_mode(int mode);
  * under the current selectors — *loop_mode = 0 / 2 / 4 as above, *skip_t = the squared distance under which escape
  * checks are skipped, *spec_quiet = iterations a wave must stay under it before it speculates (0 = never). */
 int fr_debug_loop_plan(const fr_config *cfg, int precision, uint32_t *loop_mode, double *skip_t, uint32_t *spec_quiet);
+/* The speculative blocks of the four-iteration scaled loop grow while a tile stays quiet: 16 iterations, doubling after
+ * every block that passes its end test, up to `maxlen` (default 128; brought down to 16 * 2^k), and 16 for good once the
+ * tile has thrown a block away.  Tool / test hook: sets `maxlen` for every later render of the process (0 = the
+ * default, 16 = blocks of 16 only); every value produces the same bytes. */
+int fr_debug_set_spec_maxlen(uint32_t maxlen);
+/* Host arithmetic only, as fr_debug_loop_plan: *maxlen = the longest block the launch of (cfg, precision) would run
+ * with — 0 wherever *spec_quiet is 0. */
+int fr_debug_spec_maxlen(const fr_config *cfg, int precision, uint32_t *maxlen);
 
 /* Test hook (not part of the reference surface): elementwise DEVICE arithmetic over host arrays —
  * which = 0: the kernels' software log2, 1: sqrt, 2: in[k] / in[(k+1) % n], 3: the `as u8` cast —

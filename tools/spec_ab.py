@@ -3,6 +3,8 @@
 so that clock drift hits both alike: loop_mode -1 (automatic: speculation where the host can prove it) against 5 (the same
 without speculation), on the BASELINE views at SPEC_SIZE^2 (default 16384) plus the views the default dispatch sends through
 other kernels.  Prints best / median kernel ms (HIP events around the launch) and whether the bytes agree.
+SPEC_MAXLENS=16,64,128,1024 interleaves instead the longest block the speculative blocks may grow to
+(fr_debug_set_spec_maxlen; loop_mode -1 throughout; the last one listed is the base of the percentages).
 Usage (GPU box): python tools/spec_ab.py [c2 c2f32 c1 gui4k filled c4 c4f64 c3]"""
 import ctypes as C
 import os
@@ -19,6 +21,9 @@ size = int(os.environ.get("SPEC_SIZE", "16384"))
 reps = int(os.environ.get("SPEC_REPS", "9"))  # c3: 3
 modes = [int(m) for m in os.environ.get("SPEC_MODES", "-1,5").split(",")]
 tile = int(os.environ.get("SPEC_TILE", "0"))
+maxlens = [int(m) for m in os.environ.get("SPEC_MAXLENS", "").split(",") if m]
+if maxlens:  # the variants are block lengths, not loop modes
+    modes = maxlens
 
 
 import bench  # noqa: E402  (the views of bench.py: the same kernels are chosen)
@@ -85,7 +90,10 @@ for name in names:
     names = {}
     for rep in range(3 if name == "c3" else reps):
         for m in modes:
-            _native.check(lib.fr_set_loop_mode(m))
+            if maxlens:
+                _native.check(lib.fr_debug_set_spec_maxlen(m))
+            else:
+                _native.check(lib.fr_set_loop_mode(m))
             _native.check(lib.fr_render_rows_rgb8_device(C.byref(cfg), int(prec), 0, cfg.height, C.c_void_p(outs[m].data_ptr()), nbytes, None))
             ms = C.c_float()
             _native.check(lib.fr_last_kernel_ms(C.byref(ms)))
@@ -95,14 +103,15 @@ for name in names:
             lib.fr_last_kernel_name(kn, 256)
             names[m] = kn.value.decode()
     lib.fr_set_loop_mode(-1)
+    lib.fr_debug_set_spec_maxlen(0)
     torch.cuda.synchronize()
     base = sorted(times[modes[-1]])
     for m in modes:
         ts = sorted(times[m])
         same = bool(torch.equal(outs[m], outs[modes[-1]]))
         label = name if not name.startswith("v13_") else "%s %s" % (name.rsplit("_", 1)[1], VIEWS13[int(name.split("_")[1])][0])
-        print("%-44s %dx%d i=%d loop_mode %2d: best %8.3f ms  median %8.3f  (%+5.1f %% vs mode %d)  bytes identical: %s  [%s]" % (
-            label, cfg.width, cfg.height, cfg.iterations, m, ts[0], ts[len(ts) // 2], 100.0 * (ts[len(ts) // 2] / base[len(base) // 2] - 1.0),
+        print("%-44s %dx%d i=%d %s %2d: best %8.3f ms  median %8.3f  (%+5.2f %% vs %d)  bytes identical: %s  [%s]" % (
+            label, cfg.width, cfg.height, cfg.iterations, "max block" if maxlens else "loop_mode", m, ts[0], ts[len(ts) // 2], 100.0 * (ts[len(ts) // 2] / base[len(base) // 2] - 1.0),
             modes[-1], same, names[m][:60]), flush=True)
     del outs
     torch.cuda.empty_cache()
