@@ -29,6 +29,7 @@ __all__ = [
     "get_image", "get_image_rows", "get_image_rgba", "get_recursive_pixel", "recursive", "recursive_batch",
     "escape_rows", "colour_image", "count_iterations", "init", "shutdown", "device_count", "device_name",
     "RenderOpts", "init_devices", "get_image_multi", "multi_stats", "build_id", "get_image_fern", "split_dd",
+    "box_filter", "ss_workspace_bytes", "SS_MAX",
 ]
 
 
@@ -164,12 +165,52 @@ def device_name():
     return buf.value.decode()
 
 
-def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None, pos_lo=None):
+SS_MAX = 8  # FR_SS_MAX
+
+
+def _render_rows_ss(config, y0, y1, precision, out, channels, opts, pos_lo, supersample):
+    """fr_render_rows_ss: rows [y0, y1) with supersample x supersample samples per pixel, box-filtered on the device"""
+    lo, _keep = _pos_lo(pos_lo)
+    _native.check(
+        _native.load().fr_render_rows_ss(C.byref(config), int(precision), lo, int(supersample), y0, y1, channels,
+                                         out.ctypes.data, out.nbytes, C.byref(opts) if opts is not None else None)
+    )
+    return out
+
+
+def ss_workspace_bytes(config, supersample, y0=0, y1=None):
+    """fr_ss_workspace_bytes: (min_bytes, best_bytes) of the device workspace fr_render_rows_ss_device wants for rows
+    [y0, y1) — one band of 8 * supersample source rows, and the whole range (at most 1 GiB)."""
+    y1 = config.height if y1 is None else y1
+    mn, best = C.c_size_t(0), C.c_size_t(0)
+    _native.check(_native.load().fr_ss_workspace_bytes(C.byref(config), int(supersample), y0, y1, C.byref(mn), C.byref(best)))
+    return mn.value, best.value
+
+
+def box_filter(image, s, channels=3):
+    """The box filter of the supersampled renders alone (fr_box_filter_rgb8): image uint8 [s*rows, s*width, 3] ->
+    uint8 [rows, width, channels], each byte (sum of its s x s block + s*s // 2) // (s*s); channels=4 adds alpha 255.
+    E.g. to re-filter a large render the caller already holds."""
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    s = int(s)
+    if image.ndim != 3 or image.shape[2] != 3 or s < 1 or image.shape[0] % s or image.shape[1] % s:
+        raise ValueError("image must be uint8 [s*rows, s*width, 3]")
+    rows, width = image.shape[0] // s, image.shape[1] // s
+    out = np.empty((rows, width, channels), dtype=np.uint8)
+    _native.check(_native.load().fr_box_filter_rgb8(image.ctypes.data, width, rows, s, channels, out.ctypes.data, out.nbytes))
+    return out
+
+
+def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None, pos_lo=None, supersample=1):
     """Rows [y0, y1) of get_image — the unit of the reference's rayon loop (src/lib.rs:256-264).
     Returns uint8 [y1-y0, width, 3].  pos_lo (Precision.DD or Precision.PT only): the low halves (re, im) of the view
-    centre (split_dd), so that the centre is pos + pos_lo; None = (0, 0)."""
+    centre (split_dd), so that the centre is pos + pos_lo; None = (0, 0).
+    supersample = s > 1: s x s samples per pixel, box-filtered on the device (include/fractal_hip.h, "supersampled
+    rendering"); only the [y1-y0, width] result leaves the device."""
     if out is None:
         out = np.empty((max(int(y1) - int(y0), 0), config.width, 3), dtype=np.uint8)
+    if supersample != 1:
+        return _render_rows_ss(config, y0, y1, precision, out, 3, opts, pos_lo, supersample)
     if pos_lo is not None:
         render = _render_rows_lo(precision)
         lo, _keep = _pos_lo(pos_lo)
@@ -182,12 +223,14 @@ def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None,
     return out
 
 
-def get_image(config, precision=Precision.F64, pos_lo=None):
+def get_image(config, precision=Precision.F64, pos_lo=None, supersample=1):
     """get_image(&Config) -> Vec<RGB> (src/lib.rs:253-270): uint8 [height, width, 3], row-major,
     bytes r,g,b.  Algo.BarnsleyFern is outside this path (random IFS, src/lib.rs:271-319): the
     per-pixel function returns BLACK for it (calc/src/lib.rs:211) and so does this.
-    pos_lo: see get_image_rows (Precision.DD or Precision.PT only)."""
+    pos_lo: see get_image_rows (Precision.DD or Precision.PT only).  supersample: see get_image_rows."""
     out = np.empty((config.height, config.width, 3), dtype=np.uint8)
+    if supersample != 1:
+        return _render_rows_ss(config, 0, config.height, precision, out, 3, None, pos_lo, supersample)
     if int(precision) == Precision.F64 and pos_lo is None:
         _native.check(_native.load().fr_render_rgb8(C.byref(config), out.ctypes.data, out.nbytes))
         return out
@@ -217,11 +260,14 @@ def get_image_fern(config, threads=1, seed=0, walkers=0):
     return out
 
 
-def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None):
+def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None, supersample=1):
     """get_image as RGBA8 (alpha 255): uint8 [height, width, 4] — the GUI's upload format
-    (src/gui.rs:71-72) produced on the device.  pos_lo: see get_image_rows (Precision.DD or Precision.PT only)."""
+    (src/gui.rs:71-72) produced on the device.  pos_lo: see get_image_rows (Precision.DD or Precision.PT only).
+    supersample: see get_image_rows."""
     if out is None:
         out = np.empty((config.height, config.width, 4), dtype=np.uint8)
+    if supersample != 1:
+        return _render_rows_ss(config, 0, config.height, precision, out, 4, None, pos_lo, supersample)
     if pos_lo is not None:
         render = _render_rows_lo(precision)
         lo, _keep = _pos_lo(pos_lo)

@@ -211,6 +211,22 @@ PROTOTYPES = {
         C.c_int, [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "fr_debug_reference_orbit": (
         C.c_int, [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "fr_ss_workspace_bytes": (
+        C.c_int, [C.POINTER(fr_config), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "fr_render_rows_ss_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_int, C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
+         C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, _OPTS],
+    ),
+    "fr_render_rows_ss": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_int, C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
+         C.c_size_t, _OPTS],
+    ),
+    "fr_box_filter_rgb8": (
+        C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
+    "fr_box_filter_rgb8_device": (
+        C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "fr_colour_rgb8": (C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "fr_colour_rgb8_device": (
         C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

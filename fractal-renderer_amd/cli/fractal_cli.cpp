@@ -66,7 +66,7 @@ int main(int argc, char **argv) {
     std::string width = "750", height = "500", limit = "65536", stable_limit = "2", pos_y = "0", scale = "0.4",
                 exposure = "5", filename = "output", algo_s = "mandelbrot", color_weight = "0.01";
     std::optional<std::string> iterations, pos_x, scale_x, scale_y, primary, secondary, julia_re, julia_im, devices, threads_s,
-        seed_s;
+        seed_s, supersample_s;
     bool disable_inside = false, unsmooth = false, f32 = false, quiet = false;
     std::vector<std::string> positionals;
 
@@ -95,6 +95,7 @@ int main(int argc, char **argv) {
         else if (a == "--julia-imaginary") julia_im = value(i, "--julia-imaginary");
         else if (a == "-w" || a == "--color-weight") color_weight = value(i, "-w");
         else if (a == "--f32") f32 = true;       // this build's extension (no counterpart upstream)
+        else if (a == "--supersample") supersample_s = value(i, "--supersample"); // N x N samples per pixel, box-filtered on the device
         else if (a == "--devices") devices = value(i, "--devices");
         else if (a == "--threads") threads_s = value(i, "--threads");
         else if (a == "--seed") seed_s = value(i, "--seed");
@@ -175,7 +176,8 @@ int main(int argc, char **argv) {
             }
             image = get_image_fern(cfg, threads, seed);
         } else {
-            image = get_image(cfg, f32 ? FR_PRECISION_F32 : FR_PRECISION_F64);
+            const int precision = f32 ? FR_PRECISION_F32 : FR_PRECISION_F64;
+            image = supersample_s ? get_image(cfg, precision, to_u32(*supersample_s, "--supersample")) : get_image(cfg, precision);
         }
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         const std::string path = filename + ".ppm";  // the reference appends ".avif" (src/lib.rs:192-195)

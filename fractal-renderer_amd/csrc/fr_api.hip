@@ -241,7 +241,7 @@ void Ctx::destroy() {
     if (hip_device < 0) return;
     (void)hipSetDevice(hip_device);
     /* hipFree waits for the device, so nothing below can still be in use by a kernel in flight */
-    for (Scratch *s : {&rgb, &z, &iters, &misc}) {
+    for (Scratch *s : {&rgb, &z, &iters, &misc, &ss_work}) {
         if (s->ptr) (void)hipFree(s->ptr);
         *s = Scratch();
     }

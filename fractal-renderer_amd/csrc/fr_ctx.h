@@ -97,6 +97,7 @@ struct Ctx {
     hipStream_t copy_stream = nullptr; /* D2H / peer copies, overlapped with the next band's kernel */
     std::vector<hipEvent_t> events;
     Scratch rgb, z, iters, misc;
+    Scratch ss_work; /* fr_ss.hip: the host road's band workspace (at most 256 MiB) / fr_box_filter_rgb8's source */
     PaletteSlot palette_slots[kPaletteSlots];
     SurvSlot surv_slots[kSurvSlots];
     void *surv_block = nullptr; /* kSurvSlots x surv_slot_cap bytes */

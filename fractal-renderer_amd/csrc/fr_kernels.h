@@ -194,6 +194,13 @@ hipError_t fr_launch_palette(const fr_kparams &p, uint32_t *palette, hipStream_t
 hipError_t fr_launch_colour(const fr_kparams &p, const double *z, const uint32_t *iters, size_t n, uint8_t *rgb,
                             hipStream_t stream);
 
+/* Box filter of supersampled rendering (fr_ss.hip: box_filter_kernel): src = packed r,g,b rows of s * width pixels
+ * (s * rows of them), dst = packed rows of `width` pixels, bpp 3 (r,g,b) or 4 (r,g,b,255; dst 4-byte aligned); each
+ * output byte = (sum of its s x s block + floor(s*s / 2)) / (s*s).  s = 1 .. FR_SS_MAX; any alignment otherwise;
+ * 64-bit byte offsets.  Device arrays. */
+hipError_t fr_launch_box_filter(const void *src, uint32_t width, uint64_t rows, uint32_t s, uint32_t bpp, void *dst,
+                                hipStream_t stream);
+
 /* n independent orbits, device arrays (re, im interleaved) */
 hipError_t fr_launch_recursive_batch(uint32_t iterations, const double *start, const double *c, size_t n,
                                      double limit, int precision, double *out_pos, uint32_t *out_iters,

@@ -110,6 +110,16 @@ inline std::vector<RGB> get_image(const Config &config, int precision = FR_PRECI
     return image;
 }
 
+// get_image anti-aliased: supersample x supersample samples per pixel, box-filtered on the device (include/fractal_hip.h,
+// "supersampled rendering"; 1 <= supersample <= FR_SS_MAX).  Only the width x height result crosses PCIe.  One GPU,
+// whatever use_devices chose; supersample = 1 is get_image(config, precision) on that GPU, byte for byte.
+inline std::vector<RGB> get_image(const Config &config, int precision, uint32_t supersample) {
+    std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
+    check(fr_render_rows_ss(&config, precision, nullptr, supersample, 0, config.height, 3,
+                            reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB), nullptr));
+    return image;
+}
+
 // get_image's Algo::BarnsleyFern arm — src/lib.rs:271-319 + fern() :417-463.  threads = what
 // rayon::current_num_threads() is on the machine being stood in for (the reference returns ONE thread's image of
 // iterations / threads points); seed replaces SmallRng::from_entropy() (src/lib.rs:428).

@@ -373,6 +373,57 @@ int fr_escape_rows_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t
 int fr_debug_reference_orbit(const fr_config *cfg, const fr_imaginary *pos_lo, int which, double *out, size_t cap,
                              uint32_t *len);
 
+/* ---- supersampled rendering: render s times as large, box-filter on the device ------------------------ */
+
+/* The reference's own remedy for "the aliasing of the borders" (--unsmooth's help text) is to render large and scale
+ * down (its README screenshot is a 3000 x 3000 render shown at 1000 x 1000).  Here that happens on the device, so that
+ * only the small image crosses PCIe and the large one never exists whole.  DEFINITION, for supersample = s,
+ * 1 <= s <= FR_SS_MAX:
+ *   cfg_s = cfg with width * s and height * s, every other field unchanged;
+ *   H     = the image of cfg_s at the requested precision (with pos_lo for DD and PT): the bytes
+ *           fr_render_rows_rgb8 / fr_render_rows_dd / fr_render_rows_pt produce for cfg_s;
+ *   out(X, Y, c) = (sum over j < s, i < s of H(s*X + i, s*Y + j, c) + floor(s*s / 2)) / (s*s)
+ *           in integer arithmetic, truncating (the sums fit in 16 bits); with 4 channels alpha is 255.
+ * s = 1 is the plain render, byte for byte.  Algo::BarnsleyFern stays black.
+ * This is literally "render s times as large and box-filter": the s*s samples of pixel (X, Y) cover [X, X+1) x [Y, Y+1)
+ * from its top-left corner, so the image sits (s-1)/(2s) of a pixel away (right and down) from the s = 1 render, whose one
+ * sample is that corner.
+ * Domain (else FR_ERR_INVALID_ARGUMENT, before any device work): s in 1 .. FR_SS_MAX; s * width and s * height fit in
+ * 32 bits; the precision's own domain on cfg_s; pos_lo non-NULL only for DD and PT; channels 3 or 4.  One device. */
+#define FR_SS_MAX 8
+
+/* Workspace of fr_render_rows_ss_device for rows [y0, y1): rows [s*y0, s*y1) of cfg_s are rendered in bands of B source
+ * rows (packed r,g,b, 3 * s * width bytes a row) into the workspace, each band filtered into its place in the output.
+ * *min_bytes = one band of 8 * s source rows (or all the rows if there are fewer); *best_bytes = the whole range, at most
+ * 1 GiB (never under *min_bytes).  Any length from *min_bytes up is accepted and used: Bmax = the multiple of 8 * s rows
+ * that fit (or all the rows), nb = ceil(rows / Bmax) bands, B = ceil(rows / nb) rounded up to 8 * s — whole tile rows and
+ * whole output rows per band, no sliver at the end.  s = 1: both 0.  Either pointer may be NULL.  No device needed. */
+int fr_ss_workspace_bytes(const fr_config *cfg, uint32_t supersample, uint32_t y0, uint32_t y1, size_t *min_bytes,
+                          size_t *best_bytes);
+/* Rows [y0, y1) of the supersampled image as r,g,b (channels 3) or r,g,b,255 (channels 4; d_out 4-byte aligned) into
+ * DEVICE memory, asynchronously on `hip_stream`.  The caller lends the workspace d_work (device memory, work_len bytes,
+ * any alignment; NULL / 0 for s = 1) until the work queued on the stream has finished; the library allocates nothing and
+ * takes no lock beyond its slot rings: re-entrant, each thread with a workspace and a stream of its own.  A work_len
+ * under *min_bytes gives FR_ERR_BUFFER_TOO_SMALL.  F64 and F32 choose ONE kernel for the whole source range (as the
+ * bands of the host path do); PT computes the view's orbit once.  With profiling on, fr_last_kernel_ms returns the span
+ * of the whole call on the stream, first band's kernel to last filter, and fr_last_kernel_name the render kernel. */
+int fr_render_rows_ss_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t supersample,
+                             uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len, void *d_work,
+                             size_t work_len, void *hip_stream, const fr_render_opts *opts);
+/* The same into a HOST buffer of at least channels*width*(y1-y0) bytes.  The workspace (at most 256 MiB) and the result
+ * live in the context's scratch memory; the result leaves the device in one copy: only the small image crosses PCIe.
+ * y0 == y1 is legal (no-op) without a device. */
+int fr_render_rows_ss(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t supersample, uint32_t y0,
+                      uint32_t y1, int channels, uint8_t *out, size_t out_len, const fr_render_opts *opts);
+/* The filter alone — e.g. over a large render the caller already holds: src = packed r,g,b rows of supersample * width
+ * pixels, supersample * rows of them; out = `rows` packed rows of `width` pixels, channels 3 or 4 (out_len >=
+ * channels*width*rows).  Host arrays, or device arrays (any alignment; RGBA output 4-byte aligned) + stream for the
+ * _device form. */
+int fr_box_filter_rgb8(const uint8_t *src, uint32_t width, uint32_t rows, uint32_t supersample, int channels, uint8_t *out,
+                       size_t out_len);
+int fr_box_filter_rgb8_device(const void *d_src, uint32_t width, uint32_t rows, uint32_t supersample, int channels,
+                              void *d_out, size_t out_len, void *hip_stream);
+
 /* ---- get_recursive_pixel — calc/src/lib.rs:199-235 ---------------------------------------- */
 
 int fr_pixel(const fr_config *cfg, uint32_t x, uint32_t y, fr_rgb *out);

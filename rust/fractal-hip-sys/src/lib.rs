@@ -48,7 +48,23 @@ pub struct fr_config {
     pub julia_set: fr_imaginary,
 }
 
+/// The implementation selectors of ONE call (include/fractal_hip.h, `fr_render_opts`); fill with `fr_render_opts_init`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fr_render_opts {
+    pub size: u32,
+    pub tile: i32,
+    pub loop_mode: i32,
+    pub palette: i32,
+    pub cycle_shortcut: i32,
+    pub refill_minrun: i32,
+    pub refill_quit16: i32,
+    pub colour_filter: i32,
+}
+
 pub const FR_OK: c_int = 0;
+/// Largest `supersample` of the supersampled renders (include/fractal_hip.h, "supersampled rendering").
+pub const FR_SS_MAX: u32 = 8;
 /// `FR_ABI_VERSION` of the header these declarations were written against; `check_abi()` compares it with the library's.
 pub const FR_ABI_VERSION: c_int = 3;
 pub const FR_PRECISION_F64: c_int = 0;
@@ -97,6 +113,12 @@ extern "C" {
     pub fn fr_render_rows_pt(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, channels: c_int, out: *mut u8, out_len: usize) -> c_int;
     pub fn fr_render_rows_pt_device(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, channels: c_int, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
     pub fn fr_escape_rows_pt(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, z: *mut f64, iters: *mut u32) -> c_int;
+    // supersampled rendering: render `supersample` times as large, box-filter on the device (pos_lo NULL unless DD / PT; opts NULL = defaults)
+    pub fn fr_ss_workspace_bytes(cfg: *const fr_config, supersample: u32, y0: u32, y1: u32, min_bytes: *mut usize, best_bytes: *mut usize) -> c_int;
+    pub fn fr_render_rows_ss_device(cfg: *const fr_config, precision: c_int, pos_lo: *const fr_imaginary, supersample: u32, y0: u32, y1: u32, channels: c_int, d_out: *mut c_void, out_len: usize, d_work: *mut c_void, work_len: usize, hip_stream: *mut c_void, opts: *const fr_render_opts) -> c_int;
+    pub fn fr_render_rows_ss(cfg: *const fr_config, precision: c_int, pos_lo: *const fr_imaginary, supersample: u32, y0: u32, y1: u32, channels: c_int, out: *mut u8, out_len: usize, opts: *const fr_render_opts) -> c_int;
+    pub fn fr_box_filter_rgb8(src: *const u8, width: u32, rows: u32, supersample: u32, channels: c_int, out: *mut u8, out_len: usize) -> c_int;
+    pub fn fr_box_filter_rgb8_device(d_src: *const c_void, width: u32, rows: u32, supersample: u32, channels: c_int, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
 }
 
 /// Message of the last failing call on this thread.
@@ -236,6 +258,24 @@ pub fn get_image_pt<P: Copy>(cfg: &fr_config, pos_lo: fr_imaginary, image: &mut 
     image.clear();
     image.reserve_exact(n);
     let rc = unsafe { fr_render_rows_pt(cfg, &pos_lo, 0, cfg.height, 3, image.as_mut_ptr() as *mut u8, n * 3) };
+    if rc != FR_OK {
+        return Err(last_error());
+    }
+    unsafe { image.set_len(n) }; // every byte was written by the library
+    Ok(())
+}
+
+/// `get_image` anti-aliased: the image of `cfg` with `supersample` x `supersample` samples per pixel, box-filtered on the
+/// device (include/fractal_hip.h, "supersampled rendering"), into a caller-owned pixel vector.  Only the
+/// `width * height` result crosses PCIe.  `pos_lo` is for `FR_PRECISION_DD` / `FR_PRECISION_PT` (see `get_image_dd`),
+/// `None` otherwise.  `P` must be a 3-byte `#[repr(C)]` pixel.
+pub fn render_ss_into<P: Copy>(cfg: &fr_config, precision: c_int, pos_lo: Option<fr_imaginary>, supersample: u32, image: &mut Vec<P>) -> Result<(), String> {
+    assert_eq!(std::mem::size_of::<P>(), 3, "pixel type must be 3 packed bytes");
+    let n = cfg.width as usize * cfg.height as usize;
+    image.clear();
+    image.reserve_exact(n);
+    let lo = pos_lo.as_ref().map_or(std::ptr::null(), |p| p as *const fr_imaginary);
+    let rc = unsafe { fr_render_rows_ss(cfg, precision, lo, supersample, 0, cfg.height, 3, image.as_mut_ptr() as *mut u8, n * 3, std::ptr::null()) };
     if rc != FR_OK {
         return Err(last_error());
     }
