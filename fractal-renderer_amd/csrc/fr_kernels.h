@@ -1,6 +1,6 @@
 /*
  * fr_kernels.h — internal (C++) interface between the C ABI (fr_api.hip) and the gfx950 kernels
- * (fr_kernels.hip).  Not installed; the public boundary is include/fractal_hip.h.
+ * (fr_kernels.hip; which of them a render gets: fr_dispatch.hip).  Not installed; the public boundary is include/fractal_hip.h.
  */
 #ifndef FR_KERNELS_H
 #define FR_KERNELS_H

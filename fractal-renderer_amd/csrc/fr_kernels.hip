@@ -1,34 +1,25 @@
 /*
- * fr_kernels.hip — gfx950 (MI355X / CDNA4) kernels of the escape-time hot path.
+ * fr_kernels.hip — gfx950 (MI355X / CDNA4) kernels of the escape-time hot path, and their launchers.
  *
  * Written for gfx950 only.  MUST be compiled with -ffp-contract=off and without fast-math: the
  * reference (Rust) rounds every multiply and add separately (calc/src/lib.rs:87-107), so an implicit
  * v_fma_f64 in the orbit loop breaks bit parity.  (The loops contain exactly one explicit fma, which
  * is exact by construction — see "orbit loop, scaled form".)
  *
- * What runs where (reference lines in brackets):
- *   coordinate map   [calc/src/lib.rs:181-197]  re depends only on x and im only on y, so a strip's
- *                    56 column values and 8 row values are evaluated in one pass by the wave that
- *                    renders it (the reference's 3 IEEE divisions per pixel become 2 per 7 pixels,
- *                    same values) and handed to the pixel lanes by cross-lane reads;
- *   orbit loop       [calc/src/lib.rs:245-257, 87-107]  one wavefront lane per pixel, state in VGPRs,
- *                    hand-written ISA; a wave leaves it when every lane has escaped (EXEC == 0), when
- *                    the wave-uniform counter reaches the cap, or — refilling kernel — when enough
- *                    lanes are idle to be worth handing them new pixels;
- *   colour map       [calc/src/lib.rs:199-235, 133-139]  fused behind the loop; log2 is the software
- *                    fr_log2 (fr_math.h) whose 3 KB table is staged in LDS; with smooth == false the
- *                    outside colour comes from an LDS-staged palette instead;
- *   image assembly   [src/lib.rs:253-270]  bytes r,g,b at 3*(row*ncols + col); a wave writes 8-pixel
- *                    (24-byte) runs of 8 rows per tile, 192-byte runs per strip row.
- *
- * Kernels: escape_strip_kernel (small launches; large interior-heavy views); escape_first_kernel (round 3: 7-tile strips
- * in episodes, lanes past T frozen and finished once per tile, the common tile in one asm block) — alone (tile = 13) or
- * followed by escape_queue_kernel<.., 1> over the survivor lists (two passes, tile = 11), which of the three a large
- * launch gets being decided from view_sample_kernel's sample of the image (fr_api.hip: choose_kernel);
- * escape_first_v1_kernel (round 2's first pass, tile = 12, kept for A/B); escape_queue_kernel<.., 0> (the work queue
- * over the image, tile = 10); escape_refill_kernel (tile = 9, the opt-in periodicity shortcut, COUNT / ESCAPE outputs of
- * large Julia images); escape_kernel (the first, 4-wave design; kept for the tile-shape study); palette_kernel,
- * colour_kernel, recursive_batch_kernel; math_probe_kernel, nu_scan_kernel, cast_scan_kernel (test hooks).
+ * In this order: the orbit loops in hand-written ISA (plain, then scaled); what turns a pixel index into coordinates
+ * [calc/src/lib.rs:181-197] and a finished orbit into bytes [calc/src/lib.rs:199-235; fr_colour.h]; then the kernels, each
+ * with the loops only it uses in front of it:
+ *   escape_kernel (the first, 4-wave design; kept for the tile-shape study), escape_strip_kernel (THE DEFAULT);
+ *   escape_first_v1_kernel (round 2's first pass, tile = 12, comparison only) and escape_first_kernel (the two-pass
+ *   render's first pass, or alone: the default for large Julia views);
+ *   escape_refill_kernel (tile = 9; the default behind the periodicity shortcut and for COUNT / ESCAPE outputs of large
+ *   Julia images);
+ *   escape_queue_kernel (<.., 0>: the work queue over the image, tile = 10; <.., 1>: round 2's second pass, tiles 12 and 14,
+ *   comparison only) and escape_second_kernel (the two-pass render's second pass since round 3);
+ *   recursive_batch_kernel, view_sample_kernel, palette_kernel, colour_kernel, copy_out_kernel; math_probe_kernel,
+ *   cast_scan_kernel, nu_scan_kernel (test hooks).
+ * Which of them a render gets is decided in fr_dispatch.hip (host only), which calls the plain launchers at the end of
+ * this file (fr_launch.h).  tools/isa_digest.py shows that an edit here left every kernel's ISA alone.
  */
 #include "fr_kernels.h"
 
@@ -36,6 +27,7 @@
 
 #include <cstdlib>
 
+#include "fr_launch.h"
 #include "fr_math.h"
 
 namespace {
@@ -67,14 +59,19 @@ constexpr int kWaves = 4; /* 256-thread workgroups */
  *   - the wave leaves the loop when EXEC == 0 (every lane escaped) or the counter hits the cap;
  *   - unrolled x4 so the scalar loop control is amortised; the remainder runs first.
  * EXEC is restored before the block ends, so the compiler's view of control flow is unchanged. */
+
+/* The unscaled iteration without its distance add and compare, reading the state in register set S and writing it to
+ * set D ("" = re, im, r2, i2; "1" = re1, im1, r21, i21): 7 vector instructions. */
+#define FR_ORBIT_IT_R(SFX, S, D)                           \
+    "v_add_" SFX " %[t], %[r2" S "], -%[i2" S "]\n"        \
+    "v_add_" SFX " %[x], %[re" S "], %[re" S "]\n"         \
+    "v_add_" SFX " %[re" D "], %[t], %[cre]\n"             \
+    "v_mul_" SFX " %[x], %[x], %[im" S "]\n"               \
+    "v_add_" SFX " %[im" D "], %[x], %[cim]\n"             \
+    "v_mul_" SFX " %[r2" D "], %[re" D "], %[re" D "]\n"   \
+    "v_mul_" SFX " %[i2" D "], %[im" D "], %[im" D "]\n"
 #define FR_ORBIT_STEP(SFX, TAG)                    \
-    "v_add_" SFX " %[t], %[r2], -%[i2]\n"          \
-    "v_add_" SFX " %[x], %[re], %[re]\n"           \
-    "v_add_" SFX " %[re], %[t], %[cre]\n"          \
-    "v_mul_" SFX " %[x], %[x], %[im]\n"            \
-    "v_add_" SFX " %[im], %[x], %[cim]\n"          \
-    "v_mul_" SFX " %[r2], %[re], %[re]\n"          \
-    "v_mul_" SFX " %[i2], %[im], %[im]\n"          \
+    FR_ORBIT_IT_R(SFX, "", "")                     \
     "v_add_" SFX " %[t], %[r2], %[i2]\n"           \
     "s_mov_b64 %[sprev], exec\n"                   \
     "v_cmpx_nlt_" SFX " %[lim2], %[t]\n"           \
@@ -129,16 +126,6 @@ constexpr int kWaves = 4; /* 256-thread workgroups */
 #else
 #error "FR_SPEC_M must be 8, 16 or 32"
 #endif
-/* The unscaled iteration without its distance add and compare, reading the state in register set S and writing it to
- * set D ("" = re, im, r2, i2; "1" = re1, im1, r21, i21): 7 vector instructions. */
-#define FR_ORBIT_IT_R(SFX, S, D)                           \
-    "v_add_" SFX " %[t], %[r2" S "], -%[i2" S "]\n"        \
-    "v_add_" SFX " %[x], %[re" S "], %[re" S "]\n"         \
-    "v_add_" SFX " %[re" D "], %[t], %[cre]\n"             \
-    "v_mul_" SFX " %[x], %[x], %[im" S "]\n"               \
-    "v_add_" SFX " %[im" D "], %[x], %[cim]\n"             \
-    "v_mul_" SFX " %[r2" D "], %[re" D "], %[re" D "]\n"   \
-    "v_mul_" SFX " %[i2" D "], %[im" D "], %[im" D "]\n"
 #define FR_ORBIT_IT_R5(SFX, S) \
     FR_ORBIT_IT_R(SFX, S, S) FR_ORBIT_IT_R(SFX, S, S) FR_ORBIT_IT_R(SFX, S, S) FR_ORBIT_IT_R(SFX, S, S) FR_ORBIT_IT_R(SFX, S, S)
 #define FR_ORBIT_SPEC_MOVS(MOV) \
@@ -215,6 +202,26 @@ constexpr int kWaves = 4; /* 256-thread workgroups */
     ".Ldone_%=:\n"                                                                 \
     "s_mov_b64 exec, %[sorig]\n"
 
+/* the bits of a wave-uniform T in an SGPR (f32) or an SGPR pair (f64): how the loops take limit^2 and T, as src0 of v_cmpx */
+template <typename T>
+struct UBits {
+    typedef uint32_t type;
+};
+template <>
+struct UBits<double> {
+    typedef uint64_t type;
+};
+template <typename T>
+__device__ __forceinline__ typename UBits<T>::type uniform_bits(T v) {
+    if constexpr (sizeof(T) == 8) {
+        const uint64_t b = fr_bits_of(v);
+        return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b) |
+               ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32);
+    } else {
+        return (uint32_t)__builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, v));
+    }
+}
+
 /* The wave-control knobs of one run of the loop ("episode"): stop early when at most `thr` lanes are
  * still running and at least `minrun` iterations have been done.  {0, 0} = run until every lane has
  * escaped or the cap is reached. */
@@ -243,16 +250,11 @@ __device__ __forceinline__ uint32_t orbit_run(uint32_t iterations, T &re, T &im,
       [i21] "=&v"(i21), [sspec] "=&s"(sspec), [specq] "+&s"(specq)                                                 \
     : [cre] "v"(cre), [cim] "v"(cim), [lim2] "s"(lim2), [n] "s"(n), [thr] "s"(thr), [minrun] "s"(minrun)           \
     : "vcc", "scc"
-    if constexpr (sizeof(T) == 8) {
-        /* limit^2 is wave-uniform: pin it in an SGPR pair (v_cmpx's src0) */
-        const uint64_t sq_bits = fr_bits_of(squared);
-        const uint64_t lim2 = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)sq_bits) |
-                              ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(sq_bits >> 32)) << 32);
+    const auto lim2 = uniform_bits<T>(squared); /* limit^2 is wave-uniform: pinned in scalar registers (v_cmpx's src0) */
+    if constexpr (sizeof(T) == 8)
         asm volatile(FR_ORBIT_ASM("f64", "v_mov_b64") FR_ORBIT_OPERANDS);
-    } else {
-        const uint32_t lim2 = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, squared));
+    else
         asm volatile(FR_ORBIT_ASM("f32", "v_mov_b32") FR_ORBIT_OPERANDS);
-    }
     (void)re1, (void)im1, (void)r21, (void)i21, (void)sspec;
     completed = si;
     return it;
@@ -294,15 +296,7 @@ __device__ __forceinline__ uint32_t orbit(uint32_t iterations, T &re, T &im, T c
  * (v_cmp, no EXEC write) and, only if some lane exceeds T, exactly against limit^2 (v_cmpx).
  * A wave with a lane above T ("in transit") runs M fully-checked iterations at a time until all
  * its live lanes are back under T.  The fast block is M*6 + 2 VALU instructions. */
-#define FR_SC_IT(SFX)                              \
-    "v_add_" SFX " %[t], %[A], -%[B]\n"            \
-    "v_mul_" SFX " %[q], %[X], %[Y]\n"             \
-    "v_fma_" SFX " %[X], %[t], 0.5, %[c2re]\n"     \
-    "v_add_" SFX " %[Y], %[q], %[c2im]\n"          \
-    "v_mul_" SFX " %[A], %[X], %[X]\n"             \
-    "v_mul_" SFX " %[B], %[Y], %[Y]\n"
-
-/* The same iteration reading the state in register set S and writing it to set D ("" = X, Y, A, B;
+/* The iteration, reading the state in register set S and writing it to set D ("" = X, Y, A, B;
  * "1" = X1, Y1, A1, B1): the speculative blocks below keep their start state by never writing to it. */
 #define FR_SC_IT_R(SFX, S, D)                              \
     "v_add_" SFX " %[t], %[A" S "], -%[B" S "]\n"          \
@@ -311,7 +305,21 @@ __device__ __forceinline__ uint32_t orbit(uint32_t iterations, T &re, T &im, T c
     "v_add_" SFX " %[Y" D "], %[q], %[c2im]\n"             \
     "v_mul_" SFX " %[A" D "], %[X" D "], %[X" D "]\n"      \
     "v_mul_" SFX " %[B" D "], %[Y" D "], %[Y" D "]\n"
+#define FR_SC_IT(SFX) FR_SC_IT_R(SFX, "", "")
 #define FR_SC_IT_R5(SFX, S) FR_SC_IT_R(SFX, S, S) FR_SC_IT_R(SFX, S, S) FR_SC_IT_R(SFX, S, S) FR_SC_IT_R(SFX, S, S) FR_SC_IT_R(SFX, S, S)
+/* M iterations in place, M = 2 or 4: the unchecked blocks of every scaled loop of this file */
+#define FR_SC_ITS2(SFX) FR_SC_IT(SFX) FR_SC_IT(SFX)
+#define FR_SC_ITS4(SFX) FR_SC_ITS2(SFX) FR_SC_ITS2(SFX)
+/* STMT(SFX, ITS, STEP); for the T and M in scope: ITS = the M iterations of a block, STEP = M as an f32 literal (a block's count) */
+#define FR_SC_BY_T_M(STMT)                                 \
+    if constexpr (sizeof(T) == 8 && M == 4)                \
+        STMT("f64", FR_SC_ITS4("f64"), "4.0");             \
+    else if constexpr (sizeof(T) == 8)                     \
+        STMT("f64", FR_SC_ITS2("f64"), "2.0");             \
+    else if constexpr (M == 4)                             \
+        STMT("f32", FR_SC_ITS4("f32"), "4.0");             \
+    else                                                   \
+        STMT("f32", FR_SC_ITS2("f32"), "2.0")
 
 /* Speculative long blocks (round 4).  A wave that has been QUIET for %[specq] iterations — no lane above T at any block
  * end: waves of interior pixels, which carry 97 % of C2's work — stops paying the distance add and the compare every
@@ -512,14 +520,14 @@ __device__ __forceinline__ uint32_t orbit(uint32_t iterations, T &re, T &im, T c
     "s_branch .Ldone_%=\n"
 
 #define FR_SC_ASM_M4_(SFX, CYC_F, CYC_S, CYC_H, SP_INIT, SP_ARM, SP_ENTRY, SP_BODY)                 \
-    FR_SC_ASM(SFX, "4", FR_SC_IT(SFX) FR_SC_IT(SFX) FR_SC_IT(SFX) FR_SC_IT(SFX),                    \
+    FR_SC_ASM(SFX, "4", FR_SC_ITS4(SFX),                    \
               FR_SC_CHECKED_STEP(SFX, "A") FR_SC_CHECKED_STEP(SFX, "B") FR_SC_CHECKED_STEP(SFX, "C") \
                   FR_SC_CHECKED_STEP(SFX, "D"),                                                     \
               FR_ORBIT_RECORD("A", "0") FR_ORBIT_RECORD("B", "1") FR_ORBIT_RECORD("C", "2")         \
                   FR_ORBIT_RECORD("D", "3"),                                                        \
               CYC_F, CYC_S, CYC_H, SP_INIT, SP_ARM, SP_ENTRY, SP_BODY)
 #define FR_SC_ASM_M2_(SFX, CYC_F, CYC_S, CYC_H)                                            \
-    FR_SC_ASM(SFX, "2", FR_SC_IT(SFX) FR_SC_IT(SFX),                                        \
+    FR_SC_ASM(SFX, "2", FR_SC_ITS2(SFX),                                        \
               FR_SC_CHECKED_STEP(SFX, "A") FR_SC_CHECKED_STEP(SFX, "B"),                    \
               FR_ORBIT_RECORD("A", "0") FR_ORBIT_RECORD("B", "1"), CYC_F, CYC_S, CYC_H, "", "", FR_SC_NOSPEC_ENTRY, "")
 #define FR_SC_ASM_M4(SFX) FR_SC_ASM_M4_(SFX, "", "", "", "", "", FR_SC_NOSPEC_ENTRY, "")
@@ -600,12 +608,8 @@ __device__ __forceinline__ uint32_t orbit_scaled_run(uint32_t iterations, T &X, 
     : FR_SC_OUTPUTS, [scyc] "=&s"(scyc), [Xs] "+v"(Xs), [Ys] "+v"(Ys), [vsaved] "+v"(vsaved), [snext] "+s"(snext) \
     : FR_SC_INPUTS                                                                                              \
     : "vcc", "scc"
+    const auto lim4 = uniform_bits<T>(lim4_v), t4lim = uniform_bits<T>(t4_v);
     if constexpr (sizeof(T) == 8) {
-        const uint64_t lb = fr_bits_of(lim4_v), tb = fr_bits_of(t4_v);
-        const uint64_t lim4 = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)lb) |
-                              ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(lb >> 32)) << 32);
-        const uint64_t t4lim = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)tb) |
-                               ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(tb >> 32)) << 32);
         if constexpr (M == 4 && CYC)
             asm volatile(FR_SC_ASM_M4_CYC("f64", "v_cmp_eq_u64", "v_mov_b64") FR_SC_OPERANDS_CYC);
         else if constexpr (M == 4)
@@ -615,8 +619,6 @@ __device__ __forceinline__ uint32_t orbit_scaled_run(uint32_t iterations, T &X, 
         else
             asm volatile(FR_SC_ASM_M2("f64") FR_SC_OPERANDS);
     } else {
-        const uint32_t lim4 = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, lim4_v));
-        const uint32_t t4lim = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, t4_v));
         if constexpr (M == 4 && CYC)
             asm volatile(FR_SC_ASM_M4_CYC("f32", "v_cmp_eq_u32", "v_mov_b32") FR_SC_OPERANDS_CYC);
         else if constexpr (M == 4)
@@ -1302,25 +1304,6 @@ __global__ __launch_bounds__(64) void escape_first_v1_kernel(const fr_kparams p,
  * Coordinates are narrowed to T once per block, not per tile; 3-byte pixels leave as one 16-bit and one 8-bit
  * store.  Same bytes: every pixel's orbit is recursive()'s arithmetic whichever loop runs it (the scaled form's
  * exactness and the choice of T are argued at "orbit loop, scaled form"). */
-template <typename T>
-struct UBits {
-    typedef uint32_t type;
-};
-template <>
-struct UBits<double> {
-    typedef uint64_t type;
-};
-template <typename T>
-__device__ __forceinline__ typename UBits<T>::type uniform_bits(T v) {
-    if constexpr (sizeof(T) == 8) {
-        const uint64_t b = fr_bits_of(v);
-        return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b) |
-               ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32);
-    } else {
-        return (uint32_t)__builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, v));
-    }
-}
-
 /* Blocks of M unchecked scaled iterations for the lanes of `mask` (a subset of EXEC, not empty), one |z|^2 <= T
  * test per block: a lane that fails it freezes with the state and t = A + B it has at that moment, and its count is
  * SET then — to `base` + M x the blocks run so far — by a scalar handler on the blocks in which EXEC changed; lanes
@@ -1502,7 +1485,7 @@ __device__ __forceinline__ unsigned long long first_blocks(unsigned long long ma
             const uint32_t nb = kc + 1u; /* the blocks to run; kc becomes the stretch counter */
             uint32_t kend;
             unsigned long long squiet;
-            asm volatile(FR_FBC_SPEC_ASM("f32", "v_mov_b32", FR_SC_IT("f32") FR_SC_IT("f32") FR_SC_IT("f32") FR_SC_IT("f32"), "4.0",
+            asm volatile(FR_FBC_SPEC_ASM("f32", "v_mov_b32", FR_SC_ITS4("f32"), "4.0",
                                          FR_SC_SPEC_REST, FR_SPEC_KB, FR_SPEC_STEP)
                          : [X] "+v"(X), [Y] "+v"(Y), [A] "+v"(A), [B] "+v"(B), [t] "+v"(t), [cnt] "+v"(cnt), [q] "=&v"(q),
                            [sorig] "=&s"(sorig), [srun] "=&s"(srun), [squiet] "=&s"(squiet), [k] "=&s"(kc), [kend] "=&s"(kend),
@@ -1518,9 +1501,9 @@ __device__ __forceinline__ unsigned long long first_blocks(unsigned long long ma
     : [c2re] "v"(c2re), [c2im] "v"(c2im), [t4lim] "s"(t4lim), [mask] "s"(mask)                                   \
     : "vcc", "scc"
         if constexpr (M == 4)
-            asm volatile(FR_FBC_ASM("f32", FR_SC_IT("f32") FR_SC_IT("f32") FR_SC_IT("f32") FR_SC_IT("f32"), "4.0") FR_FBC_OPERANDS);
+            asm volatile(FR_FBC_ASM("f32", FR_SC_ITS4("f32"), "4.0") FR_FBC_OPERANDS);
         else
-            asm volatile(FR_FBC_ASM("f32", FR_SC_IT("f32") FR_SC_IT("f32"), "2.0") FR_FBC_OPERANDS);
+            asm volatile(FR_FBC_ASM("f32", FR_SC_ITS2("f32"), "2.0") FR_FBC_OPERANDS);
         return srun;
     }
     const uint32_t n0 = __builtin_amdgcn_readfirstlane(nblocks), base = __builtin_amdgcn_readfirstlane(done_before);
@@ -1536,7 +1519,7 @@ __device__ __forceinline__ unsigned long long first_blocks(unsigned long long ma
         {
             uint32_t kend; /* blocks left behind the current stretch; k becomes the stretch counter */
             unsigned long long squiet;
-            asm volatile(FR_FB_SPEC_ASM("f64", "v_mov_b64", FR_SC_IT("f64") FR_SC_IT("f64") FR_SC_IT("f64") FR_SC_IT("f64"), "2",
+            asm volatile(FR_FB_SPEC_ASM("f64", "v_mov_b64", FR_SC_ITS4("f64"), "2",
                                         FR_SC_SPEC_REST, FR_SPEC_KB)
                          : [X] "+v"(X), [Y] "+v"(Y), [A] "+v"(A), [B] "+v"(B), [t] "+v"(t), [cnt] "+v"(cnt), [q] "=&v"(q),
                            [sorig] "=&s"(sorig), [srun] "=&s"(srun), [sprev] "=&s"(sprev), [sdiff] "=&s"(sdiff), [k] "=&s"(k),
@@ -1546,9 +1529,9 @@ __device__ __forceinline__ unsigned long long first_blocks(unsigned long long ma
                          : "vcc", "scc");
         }
         else if constexpr (M == 4)
-            asm volatile(FR_FB_ASM("f64", FR_SC_IT("f64") FR_SC_IT("f64") FR_SC_IT("f64") FR_SC_IT("f64"), "2") FR_FB_OPERANDS);
+            asm volatile(FR_FB_ASM("f64", FR_SC_ITS4("f64"), "2") FR_FB_OPERANDS);
         else
-            asm volatile(FR_FB_ASM("f64", FR_SC_IT("f64") FR_SC_IT("f64"), "1") FR_FB_OPERANDS);
+            asm volatile(FR_FB_ASM("f64", FR_SC_ITS2("f64"), "1") FR_FB_OPERANDS);
     }
     return srun;
 }
@@ -1693,12 +1676,12 @@ __device__ __forceinline__ uint32_t tile_fast(uint32_t nblk, T sre, T Y0, T B0, 
     : "vcc", "scc", "memory"
     if constexpr (sizeof(T) == 8) {
         if constexpr (M == 4)
-            asm volatile(FR_TILE_ASM("f64", "v_mov_b64", FR_SC_IT("f64") FR_SC_IT("f64") FR_SC_IT("f64"), "4.0") FR_TILE_OPERANDS);
+            asm volatile(FR_TILE_ASM("f64", "v_mov_b64", FR_SC_ITS2("f64") FR_SC_IT("f64"), "4.0") FR_TILE_OPERANDS);
         else
             asm volatile(FR_TILE_ASM("f64", "v_mov_b64", FR_SC_IT("f64"), "2.0") FR_TILE_OPERANDS);
     } else {
         if constexpr (M == 4)
-            asm volatile(FR_TILE_ASM("f32", "v_mov_b32", FR_SC_IT("f32") FR_SC_IT("f32") FR_SC_IT("f32"), "4.0") FR_TILE_OPERANDS);
+            asm volatile(FR_TILE_ASM("f32", "v_mov_b32", FR_SC_ITS2("f32") FR_SC_IT("f32"), "4.0") FR_TILE_OPERANDS);
         else
             asm volatile(FR_TILE_ASM("f32", "v_mov_b32", FR_SC_IT("f32"), "2.0") FR_TILE_OPERANDS);
     }
@@ -2233,20 +2216,20 @@ __global__ __launch_bounds__(64) void escape_refill_kernel(const fr_kparams p, c
         refill_patch<T, MODE, kStripTiles, 0, false>(p, out, s_tab, s_pal, cols, rows, out_rows, tile0, row0, lane);
 }
 
+/* launch KERNEL(MODE) — an instantiation with the output mode as a parameter — for the run-time `mode`, on grid x block */
+#define FR_LAUNCH_BY_MODE(KERNEL)                                                                              \
+    switch (mode) {                                                                                            \
+    case FR_OUT_RGB: hipLaunchKernelGGL((KERNEL(FR_OUT_RGB)), grid, block, 0, stream, p, out); break;          \
+    case FR_OUT_ESCAPE: hipLaunchKernelGGL((KERNEL(FR_OUT_ESCAPE)), grid, block, 0, stream, p, out); break;    \
+    default: hipLaunchKernelGGL((KERNEL(FR_OUT_COUNT)), grid, block, 0, stream, p, out); break;                \
+    }
+
 template <typename T, int kStripTiles, int FORM, bool CYC>
 hipError_t launch_refill_form(const fr_kparams &p, int mode, const fr_kout &out, dim3 grid, hipStream_t stream) {
     dim3 block(64);
-    switch (mode) {
-    case FR_OUT_RGB:
-        hipLaunchKernelGGL((escape_refill_kernel<T, FR_OUT_RGB, kStripTiles, FORM, CYC>), grid, block, 0, stream, p, out);
-        break;
-    case FR_OUT_ESCAPE:
-        hipLaunchKernelGGL((escape_refill_kernel<T, FR_OUT_ESCAPE, kStripTiles, FORM, CYC>), grid, block, 0, stream, p, out);
-        break;
-    default:
-        hipLaunchKernelGGL((escape_refill_kernel<T, FR_OUT_COUNT, kStripTiles, FORM, CYC>), grid, block, 0, stream, p, out);
-        break;
-    }
+#define FR_K(MODE) escape_refill_kernel<T, MODE, kStripTiles, FORM, CYC>
+    FR_LAUNCH_BY_MODE(FR_K);
+#undef FR_K
     return hipGetLastError();
 }
 
@@ -2296,35 +2279,45 @@ hipError_t launch_refill(const fr_kparams &p, int mode, const fr_kout &out, hipS
 constexpr uint32_t kQPatchW = 64, kQPatchH = 32;
 constexpr uint32_t kQStack = 128;
 
-/* One run of the main loop: blocks of M unchecked scaled iterations, one |z|^2 <= T test per block.
- * In: the active lanes (EXEC) all have A + B <= 4T.  Out: `running` = the lanes that passed every test
- * (the others froze at the end of the block whose test they failed), `cnt` += M per block while running,
- * return value = blocks done.  Ends when no lane runs, after `n` blocks, or — once `minrun` blocks were done —
- * when at most `thr` lanes still run. */
-#define FR_QB_ASM(SFX, BLOCK_ITS, STEP)                                            \
-    "s_mov_b64 %[sorig], exec\n"                                                   \
-    "s_mov_b32 %[si], 0\n"                                                         \
-    "s_cbranch_execz .Lqdone_%=\n"                                                 \
-    ".Lqloop_%=:\n" BLOCK_ITS                                                      \
+/* One run of the main loop of the queue kernel and of the second pass: blocks of M unchecked scaled iterations, one
+ * |z|^2 <= T test per block.  In: the lanes to run all have A + B <= 4T.  Out: %[srun] = the lanes that passed every test
+ * (the others froze at the end of the block whose test they failed), %[cnt] += M per block while running, %[si] = blocks
+ * done.  Ends when no lane runs, after %[n] blocks, or — once %[minrun] blocks were done — when at most %[thr] lanes still run.
+ * PROLOGUE says where the lanes come from: EXEC as it is, possibly empty (the queue kernel), or a mask that is not (the
+ * second pass). */
+#define FR_BLK_FROM_EXEC "s_mov_b32 %[si], 0\n" "s_cbranch_execz .Lbdone_%=\n"
+#define FR_BLK_FROM_MASK "s_mov_b64 exec, %[mask]\n" "s_mov_b32 %[si], 0\n"
+#define FR_BLK_ASM(PROLOGUE, SFX, BLOCK_ITS, STEP)                                 \
+    "s_mov_b64 %[sorig], exec\n" PROLOGUE                                          \
+    ".Lbloop_%=:\n" BLOCK_ITS                                                      \
     "v_add_" SFX " %[t], %[A], %[B]\n"                                             \
     "v_add_f32 %[cnt], %[cnt], " STEP "\n"                                         \
     "v_cmpx_nlt_" SFX " %[t4lim], %[t]\n"                                          \
     "s_add_u32 %[si], %[si], 1\n"                                                  \
-    "s_cbranch_execz .Lqdone_%=\n"                                                 \
+    "s_cbranch_execz .Lbdone_%=\n"                                                 \
     "s_bcnt1_i32_b64 %[scnt], exec\n"                                              \
     "s_cmp_gt_u32 %[scnt], %[thr]\n"                                               \
-    "s_cbranch_scc0 .Lqmaybe_%=\n"                                                 \
-    ".Lqcont_%=:\n"                                                                \
+    "s_cbranch_scc0 .Lbmaybe_%=\n"                                                 \
+    ".Lbcont_%=:\n"                                                                \
     "s_cmp_lt_u32 %[si], %[n]\n"                                                   \
-    "s_cbranch_scc1 .Lqloop_%=\n"                                                  \
-    "s_branch .Lqdone_%=\n"                                                        \
-    ".Lqmaybe_%=:\n"                                                               \
+    "s_cbranch_scc1 .Lbloop_%=\n"                                                  \
+    "s_branch .Lbdone_%=\n"                                                        \
+    ".Lbmaybe_%=:\n"                                                               \
     "s_cmp_lt_u32 %[si], %[minrun]\n"                                              \
-    "s_cbranch_scc1 .Lqcont_%=\n"                                                  \
-    ".Lqdone_%=:\n"                                                                \
+    "s_cbranch_scc1 .Lbcont_%=\n"                                                  \
+    ".Lbdone_%=:\n"                                                                \
     "s_mov_b64 %[srun], exec\n"                                                    \
     "s_mov_b64 exec, %[sorig]\n"
+/* the loop's operands, by the names both callers give them; MASK_IN: the mask operand where the prologue takes one */
+#define FR_BLK_MASK_IN [mask] "s"(mask),
+#define FR_BLK_NO_MASK_IN
+#define FR_BLK_OPERANDS(MASK_IN)                                                                                  \
+    : [X] "+v"(X), [Y] "+v"(Y), [A] "+v"(A), [B] "+v"(B), [cnt] "+v"(cnt), [t] "=&v"(t), [q] "=&v"(q),          \
+      [sorig] "=&s"(sorig), [srun] "=&s"(srun), [si] "=&s"(si), [scnt] "=&s"(scnt)                              \
+    : [c2re] "v"(c2re), [c2im] "v"(c2im), [t4lim] "s"(t4lim), MASK_IN [n] "s"(n)    , [thr] "s"(sthr), [minrun] "s"(smin) \
+    : "vcc", "scc"
 
+/* the queue kernel's run: the active lanes (EXEC) run; `running` = the lanes that passed every test; returns the blocks done */
 template <typename T, int M>
 __device__ __forceinline__ uint32_t queue_block_run(uint32_t nblocks, T &X, T &Y, T &A, T &B, T c2re, T c2im, T skip_t,
                                                     float &cnt, uint32_t thr, uint32_t minrun, unsigned long long &running) {
@@ -2334,27 +2327,9 @@ __device__ __forceinline__ uint32_t queue_block_run(uint32_t nblocks, T &X, T &Y
     uint32_t si, scnt;
     const uint32_t n = __builtin_amdgcn_readfirstlane(nblocks);
     const uint32_t sthr = __builtin_amdgcn_readfirstlane(thr), smin = __builtin_amdgcn_readfirstlane(minrun);
-    const T t4_v = (T)4 * skip_t;
-#define FR_QB_OPERANDS                                                                                          \
-    : [X] "+v"(X), [Y] "+v"(Y), [A] "+v"(A), [B] "+v"(B), [cnt] "+v"(cnt), [t] "=&v"(t), [q] "=&v"(q),          \
-      [sorig] "=&s"(sorig), [srun] "=&s"(srun), [si] "=&s"(si), [scnt] "=&s"(scnt)                              \
-    : [c2re] "v"(c2re), [c2im] "v"(c2im), [t4lim] "s"(t4lim), [n] "s"(n), [thr] "s"(sthr), [minrun] "s"(smin)   \
-    : "vcc", "scc"
-    if constexpr (sizeof(T) == 8) {
-        const uint64_t tb = fr_bits_of(t4_v);
-        const uint64_t t4lim = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)tb) |
-                               ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(tb >> 32)) << 32);
-        if constexpr (M == 4)
-            asm volatile(FR_QB_ASM("f64", FR_SC_IT("f64") FR_SC_IT("f64") FR_SC_IT("f64") FR_SC_IT("f64"), "4.0") FR_QB_OPERANDS);
-        else
-            asm volatile(FR_QB_ASM("f64", FR_SC_IT("f64") FR_SC_IT("f64"), "2.0") FR_QB_OPERANDS);
-    } else {
-        const uint32_t t4lim = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, t4_v));
-        if constexpr (M == 4)
-            asm volatile(FR_QB_ASM("f32", FR_SC_IT("f32") FR_SC_IT("f32") FR_SC_IT("f32") FR_SC_IT("f32"), "4.0") FR_QB_OPERANDS);
-        else
-            asm volatile(FR_QB_ASM("f32", FR_SC_IT("f32") FR_SC_IT("f32"), "2.0") FR_QB_OPERANDS);
-    }
+    const auto t4lim = uniform_bits<T>((T)4 * skip_t);
+#define FR_QB_STMT(SFX, ITS, STEP) asm volatile(FR_BLK_ASM(FR_BLK_FROM_EXEC, SFX, ITS, STEP) FR_BLK_OPERANDS(FR_BLK_NO_MASK_IN))
+    FR_SC_BY_T_M(FR_QB_STMT);
     running = srun;
     return si;
 }
@@ -2368,13 +2343,7 @@ __device__ __forceinline__ uint32_t queue_block_run(uint32_t nblocks, T &X, T &Y
     "s_mov_b32 %[si], 0\n"                             \
     "s_cbranch_execz .Lfdone_%=\n"                     \
     ".Lfloop_%=:\n"                                    \
-    "v_add_" SFX " %[t], %[r2], -%[i2]\n"              \
-    "v_add_" SFX " %[x], %[re], %[re]\n"               \
-    "v_add_" SFX " %[re], %[t], %[cre]\n"              \
-    "v_mul_" SFX " %[x], %[x], %[im]\n"                \
-    "v_add_" SFX " %[im], %[x], %[cim]\n"              \
-    "v_mul_" SFX " %[r2], %[re], %[re]\n"              \
-    "v_mul_" SFX " %[i2], %[im], %[im]\n"              \
+    FR_ORBIT_IT_R(SFX, "", "")                         \
     "v_add_" SFX " %[t], %[r2], %[i2]\n"               \
     "v_add_f32 %[fc], 1.0, %[fc]\n"                    \
     "v_cmpx_nlt_" SFX " %[lim2], %[t]\n"               \
@@ -2398,15 +2367,11 @@ __device__ __forceinline__ unsigned long long finish_run(uint32_t iterations, T 
       [sorig] "=&s"(sorig), [srun] "=&s"(srun), [si] "=&s"(si)                                                \
     : [cre] "v"(cre), [cim] "v"(cim), [lim2] "s"(lim2), [n] "s"(n)                                            \
     : "vcc", "scc"
-    if constexpr (sizeof(T) == 8) {
-        const uint64_t sq_bits = fr_bits_of(squared);
-        const uint64_t lim2 = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)sq_bits) |
-                              ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(sq_bits >> 32)) << 32);
+    const auto lim2 = uniform_bits<T>(squared);
+    if constexpr (sizeof(T) == 8)
         asm volatile(FR_FIN_ASM("f64") FR_FIN_OPERANDS);
-    } else {
-        const uint32_t lim2 = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, squared));
+    else
         asm volatile(FR_FIN_ASM("f32") FR_FIN_OPERANDS);
-    }
     return srun;
 }
 
@@ -2802,56 +2767,17 @@ __global__ __launch_bounds__(64) void escape_queue_kernel(const fr_kparams p, co
  *   - which lanes are busy, still running, or leaving are 64-bit masks; the main loop sets its own EXEC from the mask
  *     and returns scalars; the per-lane test against the cap runs only when the wave's largest count is within M of it.
  * Same bytes: a pixel's orbit is recursive()'s arithmetic whichever loop runs it (see "orbit loop, scaled form"). */
-#define FR_SB_ASM(SFX, BLOCK_ITS, STEP)                                            \
-    "s_mov_b64 %[sorig], exec\n"                                                   \
-    "s_mov_b64 exec, %[mask]\n"                                                    \
-    "s_mov_b32 %[si], 0\n"                                                         \
-    ".Lsloop_%=:\n" BLOCK_ITS                                                      \
-    "v_add_" SFX " %[t], %[A], %[B]\n"                                             \
-    "v_add_f32 %[cnt], %[cnt], " STEP "\n"                                         \
-    "v_cmpx_nlt_" SFX " %[t4lim], %[t]\n"                                          \
-    "s_add_u32 %[si], %[si], 1\n"                                                  \
-    "s_cbranch_execz .Lsdone_%=\n"                                                 \
-    "s_bcnt1_i32_b64 %[scnt], exec\n"                                              \
-    "s_cmp_gt_u32 %[scnt], %[thr]\n"                                               \
-    "s_cbranch_scc0 .Lsmaybe_%=\n"                                                 \
-    ".Lscont_%=:\n"                                                                \
-    "s_cmp_lt_u32 %[si], %[n]\n"                                                   \
-    "s_cbranch_scc1 .Lsloop_%=\n"                                                  \
-    "s_branch .Lsdone_%=\n"                                                        \
-    ".Lsmaybe_%=:\n"                                                               \
-    "s_cmp_lt_u32 %[si], %[minrun]\n"                                              \
-    "s_cbranch_scc1 .Lscont_%=\n"                                                  \
-    ".Lsdone_%=:\n"                                                                \
-    "s_mov_b64 %[srun], exec\n"                                                    \
-    "s_mov_b64 exec, %[sorig]\n"
-
-/* One run of the main loop for the lanes of `mask` (not empty; each with A + B <= 4T and count + M * nblocks <= cap,
- * nblocks >= 1): as queue_block_run, but the mask is an argument and everything that comes back is a scalar. */
+/* One run of the main loop for the lanes of `mask` (not empty; each with A + B <= 4T and count + M * n <= cap,
+ * n >= 1 blocks; sthr, smin: FR_BLK_ASM's %[thr], %[minrun]): FR_BLK_ASM as in queue_block_run, but the mask is an argument and everything that comes back is a scalar. */
 template <typename T, int M>
-__device__ __forceinline__ uint32_t second_block_run(unsigned long long mask, uint32_t nblocks, T &X, T &Y, T &A, T &B, T c2re,
-                                                     T c2im, typename UBits<T>::type t4lim, float &cnt, uint32_t thr,
-                                                     uint32_t minrun, unsigned long long &running) {
+__device__ __forceinline__ uint32_t second_block_run(unsigned long long mask, uint32_t n, T &X, T &Y, T &A, T &B, T c2re,
+                                                     T c2im, typename UBits<T>::type t4lim, float &cnt, uint32_t sthr,
+                                                     uint32_t smin, unsigned long long &running) {
     T t, q;
     unsigned long long sorig, srun;
     uint32_t si, scnt;
-#define FR_SB_OPERANDS                                                                                          \
-    : [X] "+v"(X), [Y] "+v"(Y), [A] "+v"(A), [B] "+v"(B), [cnt] "+v"(cnt), [t] "=&v"(t), [q] "=&v"(q),          \
-      [sorig] "=&s"(sorig), [srun] "=&s"(srun), [si] "=&s"(si), [scnt] "=&s"(scnt)                              \
-    : [c2re] "v"(c2re), [c2im] "v"(c2im), [t4lim] "s"(t4lim), [mask] "s"(mask), [n] "s"(nblocks), [thr] "s"(thr), \
-      [minrun] "s"(minrun)                                                                                      \
-    : "vcc", "scc"
-    if constexpr (sizeof(T) == 8) {
-        if constexpr (M == 4)
-            asm volatile(FR_SB_ASM("f64", FR_SC_IT("f64") FR_SC_IT("f64") FR_SC_IT("f64") FR_SC_IT("f64"), "4.0") FR_SB_OPERANDS);
-        else
-            asm volatile(FR_SB_ASM("f64", FR_SC_IT("f64") FR_SC_IT("f64"), "2.0") FR_SB_OPERANDS);
-    } else {
-        if constexpr (M == 4)
-            asm volatile(FR_SB_ASM("f32", FR_SC_IT("f32") FR_SC_IT("f32") FR_SC_IT("f32") FR_SC_IT("f32"), "4.0") FR_SB_OPERANDS);
-        else
-            asm volatile(FR_SB_ASM("f32", FR_SC_IT("f32") FR_SC_IT("f32"), "2.0") FR_SB_OPERANDS);
-    }
+#define FR_SB_STMT(SFX, ITS, STEP) asm volatile(FR_BLK_ASM(FR_BLK_FROM_MASK, SFX, ITS, STEP) FR_BLK_OPERANDS(FR_BLK_MASK_IN))
+    FR_SC_BY_T_M(FR_SB_STMT);
     running = srun;
     return si;
 }
@@ -3236,76 +3162,66 @@ hipError_t launch_queue_form(const fr_kparams &p, const fr_kout &out, hipStream_
     return hipGetLastError();
 }
 
-/* RGB output only; needs p.work_counter (zeroed on the launch stream by the caller) */
-template <typename T>
-hipError_t launch_queue(const fr_kparams &p, const fr_kout &out, hipStream_t stream) {
-    if (p.loop_mode == 4) return launch_queue_form<T, 4, 0>(p, out, stream);
-    return launch_queue_form<T, 2, 0>(p, out, stream);
+template <typename T, int M, int K, int BANDS, bool SPEC, bool V1>
+void launch_first_form(const fr_kparams &p, const fr_kout &out, dim3 grid, hipStream_t stream) {
+    if constexpr (V1)
+        hipLaunchKernelGGL((escape_first_v1_kernel<T, M, K, BANDS>), grid, dim3(64), 0, stream, p, out);
+    else
+        hipLaunchKernelGGL((escape_first_kernel<T, M, K, BANDS, SPEC>), grid, dim3(64), 0, stream, p, out);
 }
 
-/* the first-pass kernel's form: later episodes in speculative blocks where the plan allows them, unless this is the two-pass
- * render (tiles hand their stragglers over) of a view whose statistics say that nothing stays */
-static bool first_pass_speculates(const fr_kparams &p) {
-    return p.loop_mode == 4 && p.loop_spec != 0 && !(p.first_no_spec && !p.first_only);
+/* four strips per workgroup exist for 7-tile strips only */
+template <typename T, int M, int K, bool SPEC, bool V1>
+void launch_first_bands(const fr_kparams &p, const fr_kout &out, dim3 grid, int bands, hipStream_t stream) {
+    if constexpr (K == 7) {
+        if (bands == 4) return launch_first_form<T, M, K, 4, SPEC, V1>(p, out, grid, stream);
+    }
+    launch_first_form<T, M, K, 1, SPEC, V1>(p, out, grid, stream);
 }
 
-/* Two passes, RGB output only; needs the survivor lists and p.work_counter (all counters zeroed on the launch
- * stream by the caller) and 0 < p.first_cap < p.iterations */
-template <typename T, int kStripTiles>
+/* RGB output only; needs 0 < p.first_cap < p.iterations and, unless p.first_only, the survivor lists (their counters
+ * zeroed on the launch stream by the caller).  K = the strip length, 7 or 4.  Which instantiation runs, first match:
+ *
+ *   v1 && K == 7 && loop_mode == 4    escape_first_v1_kernel<T, 4, 7, bands>        round 2's first pass (tile 12)
+ *   fr_first_pass_speculates(p)       escape_first_kernel<T, 4, K, bands, true>     the later episodes may speculate (first_blocks)
+ *   loop_mode == 4                    escape_first_kernel<T, 4, K, bands, false>
+ *   otherwise                         escape_first_kernel<T, 2, K, bands, false>
+ *
+ * with bands = 4 or 1 for K = 7 (below) and 1 for K = 4. */
+template <typename T, int K>
 hipError_t launch_first_pass(const fr_kparams &p, const fr_kout &out, hipStream_t stream, bool v1) {
-    const uint64_t gx = ((uint64_t)p.ncols + 8 * kStripTiles - 1) / (8 * kStripTiles);
+    const uint64_t gx = ((uint64_t)p.ncols + 8 * K - 1) / (8 * K);
     const uint64_t row_tiles = ((uint64_t)p.nrows + 7) / 8;
     /* Four strips per workgroup share its fixed costs (-1.5 % on the 16384^2 C4 in f64) but leave a quarter of the
      * workgroups to balance over the chip: at 8192^2 (37 000 of them for 8192 resident waves) C4's dust takes 0.86 ms
      * instead of 0.72, and filled sets, whose workgroups differ a thousandfold in cost, lose more.  So: only while
      * at least 131 072 workgroups remain (7-tile strips only: the short strips are for launches far below that). */
-    const int bands = (kStripTiles == 7 && !p.first_one_band && gx * ((row_tiles + 3) / 4) >= 131072) ? 4 : 1;
+    const int bands = (K == 7 && !p.first_one_band && gx * ((row_tiles + 3) / 4) >= 131072) ? 4 : 1;
     const uint64_t row_blocks = (row_tiles + bands - 1) / bands;
     const uint64_t gy = row_blocks < 32768 ? row_blocks : 32768;
     const uint64_t gz = (row_blocks + gy - 1) / gy;
     if (gx > 0x7FFFFFFFull || gz > 65535) return hipErrorInvalidConfiguration;
     const dim3 grid((uint32_t)gx, (uint32_t)gy, (uint32_t)gz);
-    if constexpr (kStripTiles == 7) {
-        if (v1 && p.loop_mode == 4 && bands == 4) /* round 2's first pass, kept for comparison (tile 12) */
-            hipLaunchKernelGGL((escape_first_v1_kernel<T, 4, kStripTiles, 4>), grid, dim3(64), 0, stream, p, out);
-        else if (v1 && p.loop_mode == 4)
-            hipLaunchKernelGGL((escape_first_v1_kernel<T, 4, kStripTiles, 1>), grid, dim3(64), 0, stream, p, out);
-        else if (bands == 4 && first_pass_speculates(p)) /* <.., true>: the later episodes may speculate (first_blocks) */
-            hipLaunchKernelGGL((escape_first_kernel<T, 4, kStripTiles, 4, true>), grid, dim3(64), 0, stream, p, out);
-        else if (first_pass_speculates(p))
-            hipLaunchKernelGGL((escape_first_kernel<T, 4, kStripTiles, 1, true>), grid, dim3(64), 0, stream, p, out);
-        else if (p.loop_mode == 4 && bands == 4)
-            hipLaunchKernelGGL((escape_first_kernel<T, 4, kStripTiles, 4>), grid, dim3(64), 0, stream, p, out);
-        else if (p.loop_mode == 4)
-            hipLaunchKernelGGL((escape_first_kernel<T, 4, kStripTiles, 1>), grid, dim3(64), 0, stream, p, out);
-        else if (bands == 4)
-            hipLaunchKernelGGL((escape_first_kernel<T, 2, kStripTiles, 4>), grid, dim3(64), 0, stream, p, out);
-        else
-            hipLaunchKernelGGL((escape_first_kernel<T, 2, kStripTiles, 1>), grid, dim3(64), 0, stream, p, out);
-    } else {
-        if (first_pass_speculates(p))
-            hipLaunchKernelGGL((escape_first_kernel<T, 4, kStripTiles, 1, true>), grid, dim3(64), 0, stream, p, out);
-        else if (p.loop_mode == 4)
-            hipLaunchKernelGGL((escape_first_kernel<T, 4, kStripTiles, 1>), grid, dim3(64), 0, stream, p, out);
-        else
-            hipLaunchKernelGGL((escape_first_kernel<T, 2, kStripTiles, 1>), grid, dim3(64), 0, stream, p, out);
+    if constexpr (K == 7) {
+        if (v1 && p.loop_mode == 4) {
+            launch_first_bands<T, 4, K, false, true>(p, out, grid, bands, stream);
+            return hipGetLastError();
+        }
     }
+    if (fr_first_pass_speculates(p))
+        launch_first_bands<T, 4, K, true, false>(p, out, grid, bands, stream);
+    else if (p.loop_mode == 4)
+        launch_first_bands<T, 4, K, false, false>(p, out, grid, bands, stream);
+    else
+        launch_first_bands<T, 2, K, false, false>(p, out, grid, bands, stream);
     return hipGetLastError();
 }
 
-/* Two passes, RGB output only; needs the survivor lists and p.work_counter (all counters zeroed on the launch
- * stream by the caller) and 0 < p.first_cap < p.iterations.  p.strip_tiles = 4: the first pass in 4-tile strips
- * (GUI-sized launches: four times as many workgroups to balance over the chip), else 7. */
+/* p.strip_tiles = 4: 4-tile strips (GUI-sized launches: four times as many workgroups to balance over the chip), else 7;
+ * round 2's first pass has 7-tile strips only */
 template <typename T>
-hipError_t launch_two_pass(const fr_kparams &p, const fr_kout &out, hipStream_t stream, bool v1 = false) {
-    if (p.ncols == 0 || p.nrows == 0) return hipSuccess;
-    const hipError_t e = (p.strip_tiles == 4 && !v1) ? launch_first_pass<T, 4>(p, out, stream, false)
-                                                           : launch_first_pass<T, 7>(p, out, stream, v1);
-    if (e != hipSuccess) return e;
-    if (p.first_only) return hipSuccess; /* nothing was handed over: there are no lists */
-    if (p.debug_ablate & 2u) return hipSuccess; /* measurement aid: the first pass's cost on its own */
-    if (p.loop_mode == 4) return launch_queue_form<T, 4, 1>(p, out, stream);
-    return launch_queue_form<T, 2, 1>(p, out, stream);
+hipError_t launch_first_pass_len(const fr_kparams &p, bool v1, const fr_kout &out, hipStream_t stream) {
+    return (p.strip_tiles == 4 && !v1) ? launch_first_pass<T, 4>(p, out, stream, false) : launch_first_pass<T, 7>(p, out, stream, v1);
 }
 
 template <typename T, int kStripTiles>
@@ -3317,17 +3233,9 @@ hipError_t launch_strips(const fr_kparams &p, int mode, const fr_kout &out, hipS
     const uint64_t gz = (row_tiles + gy - 1) / gy;
     if (gx > 0x7FFFFFFFull || gz > 65535) return hipErrorInvalidConfiguration;
     dim3 grid((uint32_t)gx, (uint32_t)gy, (uint32_t)gz), block(64);
-    switch (mode) {
-    case FR_OUT_RGB:
-        hipLaunchKernelGGL((escape_strip_kernel<T, FR_OUT_RGB, kStripTiles>), grid, block, 0, stream, p, out);
-        break;
-    case FR_OUT_ESCAPE:
-        hipLaunchKernelGGL((escape_strip_kernel<T, FR_OUT_ESCAPE, kStripTiles>), grid, block, 0, stream, p, out);
-        break;
-    default:
-        hipLaunchKernelGGL((escape_strip_kernel<T, FR_OUT_COUNT, kStripTiles>), grid, block, 0, stream, p, out);
-        break;
-    }
+#define FR_K(MODE) escape_strip_kernel<T, MODE, kStripTiles>
+    FR_LAUNCH_BY_MODE(FR_K);
+#undef FR_K
     return hipGetLastError();
 }
 
@@ -3340,150 +3248,10 @@ hipError_t launch_tile(const fr_kparams &p, int mode, const fr_kout &out, hipStr
     if (blocks == 0) return hipSuccess;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     dim3 grid((uint32_t)blocks), block(64 * kWaves);
-    switch (mode) {
-    case FR_OUT_RGB:
-        hipLaunchKernelGGL((escape_kernel<T, TW, TH, WX, WY, FR_OUT_RGB>), grid, block, 0, stream, p, out);
-        break;
-    case FR_OUT_ESCAPE:
-        hipLaunchKernelGGL((escape_kernel<T, TW, TH, WX, WY, FR_OUT_ESCAPE>), grid, block, 0, stream, p, out);
-        break;
-    default:
-        hipLaunchKernelGGL((escape_kernel<T, TW, TH, WX, WY, FR_OUT_COUNT>), grid, block, 0, stream, p, out);
-        break;
-    }
+#define FR_K(MODE) escape_kernel<T, TW, TH, WX, WY, MODE>
+    FR_LAUNCH_BY_MODE(FR_K);
+#undef FR_K
     return hipGetLastError();
-}
-
-#define FR_KNAME(base, k) (sizeof(T) == 8 ? base "<double, " k ">" : base "<float, " k ">")
-
-template <typename T>
-const char *first_pass_name(const fr_kparams &p) {
-    /* which form of the first pass runs (launch_first_pass): the one whose later episodes may speculate, or the plain one */
-    const bool spec = first_pass_speculates(p);
-#define FR_FIRST_NAMES(SUFFIX)                                                                                                       \
-    (p.strip_tiles == 4                                                                                                              \
-         ? (p.first_only ? FR_KNAME("escape_first_kernel", "4-tile strips in episodes, every tile finished in place" SUFFIX)         \
-                         : FR_KNAME("escape_first_kernel + escape_second_kernel",                                                    \
-                                    "4-tile strips, then persistent waves over the survivor lists" SUFFIX))                          \
-         : (p.first_only ? FR_KNAME("escape_first_kernel", "7-tile strips in episodes, every tile finished in place" SUFFIX)         \
-                         : FR_KNAME("escape_first_kernel + escape_second_kernel",                                                    \
-                                    "7-tile strips, then persistent waves over the survivor lists" SUFFIX)))
-    return spec ? FR_FIRST_NAMES("; speculative blocks in the later episodes") : FR_FIRST_NAMES("");
-#undef FR_FIRST_NAMES
-}
-
-template <typename T>
-hipError_t launch_precision(const fr_kparams &p, int mode, const fr_kout &out, int tile, hipStream_t stream,
-                            const char *&name) {
-    if (p.out_in_place && tile > 16) tile = 0; /* only the strip kernels know in-place addressing */
-    switch (tile) {
-    case 6401:
-        name = FR_KNAME("escape_kernel", "64x1");
-        return launch_tile<T, 64, 1, 1, 4>(p, mode, out, stream);
-    case 3202:
-        name = FR_KNAME("escape_kernel", "32x2");
-        return launch_tile<T, 32, 2, 2, 2>(p, mode, out, stream);
-    case 1604:
-        name = FR_KNAME("escape_kernel", "16x4");
-        return launch_tile<T, 16, 4, 2, 2>(p, mode, out, stream);
-    case 808:
-        name = FR_KNAME("escape_kernel", "8x8");
-        return launch_tile<T, 8, 8, 2, 2>(p, mode, out, stream);
-    case 0: {
-        /* strip length by image size: long strips amortise the per-workgroup setup, short ones
-         * keep every SIMD supplied with several waves when the image is small (GUI frames) */
-        const uint64_t tiles = (((uint64_t)p.ncols + 7) / 8) * (((uint64_t)p.nrows + 7) / 8);
-        if (mode == FR_OUT_RGB && p.first_cap != 0 && (p.first_only || (p.surv_counts && p.work_counter))) {
-            /* Julia views are mostly short orbits with a heavy tail: two passes (see escape_first_kernel; the
-             * host asks for it from 65 536 tiles up: fr_wants_two_pass) */
-            name = first_pass_name<T>(p);
-            return launch_two_pass<T>(p, out, stream);
-        }
-        if (tiles >= 262144) {
-            /* patch refill: behind the periodicity shortcut, and for the COUNT / ESCAPE outputs of Julia images
-             * (RGB renders of Julia images this large take the two-pass kernels above) */
-            if ((p.algo == 2 && mode != FR_OUT_RGB) || p.cycle_shortcut) {
-                name = FR_KNAME("escape_refill_kernel", "7x2-tile patches");
-                return launch_refill<T, 7>(p, mode, out, stream);
-            }
-        }
-        /* p.strip_tiles: the length the view's own statistics call for (fr_api.hip: choose_kernel); else by launch size */
-        /* By size (round 4, tools/strip_length_study.py -> profiles/r04_strip_length_by_size.txt): ONE tile per workgroup up to
-         * 4096^2 — below that a launch has too few workgroups for longer strips to fill and balance the chip's 8192 wave
-         * slots (1920 x 1080, default view, f64: 0.122 ms against 0.158 / 0.244 / 0.294 for 2 / 4 / 7 tiles; still 13-23 %
-         * at 4096^2) — and the longest strips from 8192 x 4096 up, where the per-workgroup costs they amortise are what is
-         * left (8192^2: 7 tiles best on six views of eight).  Views of very short orbits prefer long strips at every size;
-         * the view's statistics say so from the second frame on (strip_tiles). */
-        const uint32_t k_len = (mode == FR_OUT_RGB && p.strip_tiles) ? p.strip_tiles : tiles >= 524288 ? 7u : 1u;
-        if (k_len >= 7u) {
-            name = FR_KNAME("escape_strip_kernel", "7 tiles");
-            return launch_strips<T, 7>(p, mode, out, stream);
-        }
-        if (k_len >= 4u) {
-            name = FR_KNAME("escape_strip_kernel", "4 tiles");
-            return launch_strips<T, 4>(p, mode, out, stream);
-        }
-        if (k_len >= 2u) {
-            name = FR_KNAME("escape_strip_kernel", "2 tiles");
-            return launch_strips<T, 2>(p, mode, out, stream);
-        }
-        name = FR_KNAME("escape_strip_kernel", "1 tile");
-        return launch_strips<T, 1>(p, mode, out, stream);
-    }
-    case 8:
-        name = FR_KNAME("escape_strip_kernel", "7 tiles");
-        return launch_strips<T, 7>(p, mode, out, stream);
-    case 13: /* the first pass alone: no tile is handed over, no lists, no second kernel */
-    case 16: /* ... in 4-tile strips */
-    case 12: /* two passes with round 2's first pass (comparison only) */
-        if (mode == FR_OUT_RGB && p.first_cap != 0 && (p.first_only || (p.surv_counts && p.work_counter))) {
-            if (tile == 12) {
-                name = FR_KNAME("escape_first_v1_kernel + escape_queue_kernel", "round 2's first pass, then persistent waves over the survivor lists");
-                return launch_two_pass<T>(p, out, stream, true);
-            }
-            name = first_pass_name<T>(p);
-            return launch_two_pass<T>(p, out, stream);
-        }
-        [[fallthrough]];
-    case 14: /* two passes with round 2's second-pass kernel (comparison only) */
-    case 15: /* two passes, the first in 4-tile strips */
-    case 11: /* two passes: strips to first_cap, then persistent waves over the survivors (otherwise as 9) */
-        if (mode == FR_OUT_RGB && p.first_cap != 0 && (p.first_only || (p.surv_counts && p.work_counter))) {
-            name = tile == 14 ? FR_KNAME("escape_first_kernel + escape_queue_kernel", "7-tile strips, then round 2's persistent waves over the survivor lists")
-                              : first_pass_name<T>(p);
-            return launch_two_pass<T>(p, out, stream);
-        }
-        if (p.algo != 0 && p.algo != 2) {
-            name = FR_KNAME("escape_strip_kernel", "7 tiles");
-            return launch_strips<T, 7>(p, mode, out, stream);
-        }
-        name = FR_KNAME("escape_refill_kernel", "7x2-tile patches");
-        return launch_refill<T, 7>(p, mode, out, stream);
-    case 10: /* the work-queue kernel (RGB output of an escape-time algorithm; otherwise as 9) */
-        if (mode == FR_OUT_RGB && p.work_counter && fr_wants_work_queue(p, 10)) {
-            name = FR_KNAME("escape_queue_kernel", "persistent waves, 64x32-px patches");
-            return launch_queue<T>(p, out, stream);
-        }
-        [[fallthrough]];
-    case 9: /* refilling strips; only the escape-time algorithms have orbits to refill */
-        if (p.algo != 0 && p.algo != 2) {
-            name = FR_KNAME("escape_strip_kernel", "7 tiles");
-            return launch_strips<T, 7>(p, mode, out, stream);
-        }
-        name = FR_KNAME("escape_refill_kernel", "7x2-tile patches");
-        return launch_refill<T, 7>(p, mode, out, stream);
-    case 1:
-        name = FR_KNAME("escape_strip_kernel", "1 tile");
-        return launch_strips<T, 1>(p, mode, out, stream);
-    case 2:
-        name = FR_KNAME("escape_strip_kernel", "2 tiles");
-        return launch_strips<T, 2>(p, mode, out, stream);
-    case 4:
-        name = FR_KNAME("escape_strip_kernel", "4 tiles");
-        return launch_strips<T, 4>(p, mode, out, stream);
-    default:
-        return hipErrorInvalidValue;
-    }
 }
 
 /* ---- recursive() for arbitrary (start, c) pairs — calc/src/lib.rs:245-257 ------------------ */
@@ -3718,73 +3486,6 @@ hipError_t fr_launch_copy_out(const void *src, void *dst, size_t bytes, unsigned
     return hipGetLastError();
 }
 
-bool fr_wants_work_queue(const fr_kparams &p, int tile) {
-    if (p.cycle_shortcut || (p.algo != 0 && p.algo != 2)) return false;
-    /* its main loop is the scaled form in blocks of loop_mode iterations, counted in an f32 */
-    if (p.loop_mode == 0 || p.iterations >= (1u << 24)) return false;
-    /* only on request: over a whole image (BASELINE C4) it runs 3.5 ms (f32) / 4.9 ms (f64) against the patch-refill
-     * kernel's 3.1 / 4.5; the default for large Julia images is the two-pass render, whose second pass this kernel
-     * is (fr_wants_two_pass) */
-    return tile == 10;
-}
-
-bool fr_wants_two_pass(fr_kparams &p, int precision, int tile, int hint) {
-    p.first_cap = 0;
-    p.first_only = 0;
-    if (p.cycle_shortcut || (p.algo != 0 && p.algo != 2)) return false;
-    if (p.loop_mode == 0 || p.iterations >= (1u << 24)) return false; /* as for the work-queue kernel */
-    if (p.ncols == 0 || p.nrows == 0 || (uint64_t)p.ncols * p.nrows > 0xFFF00000ull) return false;
-    if (p.algo == 2 && tile == 0) {
-        /* a Julia constant the scaled loop may not run with (a component that is zero, tiny or huge — the dendrite c = i):
-         * the first pass would take its plain-loop fallback on every strip; the strip kernel is the better plain loop */
-        const double lo = precision == 1 ? 0x1p-30 : 0x1p-300, hi = precision == 1 ? 0x1p30 : 0x1p400;
-        const double jr = precision == 1 ? std::fabs((double)(float)p.julia_re) : std::fabs(p.julia_re);
-        const double ji = precision == 1 ? std::fabs((double)(float)p.julia_im) : std::fabs(p.julia_im);
-        if (!(jr >= lo && jr <= hi && ji >= lo && ji <= hi)) return false;
-    }
-    if (tile == 0) {
-        /* the default dispatch: Julia images from 2048^2 up.  Measured (tools/two_pass_sizes.py, C4's view, f32 /
-         * f64, against the strips the default would otherwise pick): 65 536 tiles 0.17 / 0.21 ms against 0.18 / 0.30,
-         * 131 072 tiles 0.17 / 0.22 against 0.20 / 0.33; at 32 768 tiles and below the strips win in f32 */
-        const uint64_t tiles = (((uint64_t)p.ncols + 7) / 8) * (((uint64_t)p.nrows + 7) / 8);
-        if (tiles < 262144 && hint < 1) return false; /* (a MEASURED view may ask for them from 4096 tiles up) */
-        if (tiles < 4096) return false;
-        /* which of the two suits the IMAGE is measured where that pays (hint: 1 two passes, 0 strips — fr_api.hip:
-         * choose_kernel); without a measurement, by the algorithm: Julia views are mostly short orbits with a heavy tail */
-        if (hint == 0 || (hint < 0 && p.algo != 2)) return false;
-        /* ... and only where a tail can be long: under a cap of 512 the lists have nothing to save (a 256-iteration dust at
-         * 2048^2: 0.055 ms in two passes, 0.039 in strips; profiles/r03_kernel_choice_views.txt, mid-size section) */
-        if (hint < 0 && p.iterations < 512u) return false;
-        p.first_only = hint == 2 ? 1u : 0u;
-    } else if (tile == 13 || tile == 16) {
-        p.first_only = 1u;
-    } else if (tile != 11 && tile != 12 && tile != 14 && tile != 15) {
-        return false;
-    }
-    if (tile == 15 || tile == 16) p.strip_tiles = 4u;
-    /* first_cap: a multiple of the loop's block length; the second pass must have something left to do */
-    uint32_t k1 = p.two_pass_cap ? p.two_pass_cap : 64u; /* measured on C4: 64 / 48 (tools/sweep_two_pass.py) */
-    k1 = (k1 + 3u) & ~3u;
-    if (k1 + 8u > p.iterations) return false;
-    p.first_cap = k1;
-    if (p.first_keep == 0 || p.first_keep > 64) p.first_keep = 48;
-    return true;
-}
-
-fr_two_pass_layout fr_two_pass_bytes(const fr_kparams &p, int precision, uint32_t sub_capacity) {
-    const size_t entries = (size_t)sub_capacity * FR_SURV_QUEUES;
-    const size_t pair = precision == 1 ? 8 : 16;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    fr_two_pass_layout l{};
-    l.z_off = 0;
-    l.pos_off = up(entries * pair);
-    l.cnt_off = l.pos_off + up(entries * 8);
-    l.c_off = l.cnt_off + up(entries * 4);
-    l.counts_off = l.c_off + (p.algo == 2 ? 0 : up(entries * pair));
-    l.total = l.counts_off + FR_SURV_QUEUES * FR_SURV_COUNT_STRIDE * sizeof(uint32_t);
-    return l;
-}
-
 hipError_t fr_launch_nu_scan(uint32_t lo_bits, uint32_t hi_bits, double *out, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(out, 0, sizeof(double), stream);
     if (e != hipSuccess) return e;
@@ -3799,15 +3500,6 @@ hipError_t fr_launch_cast_scan(uint32_t lo_bits, uint32_t hi_bits, double *out, 
     hipLaunchKernelGGL(cast_scan_kernel, dim3(256 * 16), dim3(256), 0, stream, lo_bits, hi_bits,
                        reinterpret_cast<unsigned long long *>(out));
     return hipGetLastError();
-}
-
-hipError_t fr_launch_escape(const fr_kparams &p, int precision, int mode, const fr_kout &out, int tile,
-                            hipStream_t stream, const char **kernel_name) {
-    const char *name = "";
-    const hipError_t e = precision == 1 ? launch_precision<float>(p, mode, out, tile, stream, name)
-                                        : launch_precision<double>(p, mode, out, tile, stream, name);
-    if (kernel_name) *kernel_name = name;
-    return e;
 }
 
 hipError_t fr_launch_recursive_batch(uint32_t iterations, const double *start, const double *c, size_t n,
@@ -3855,4 +3547,65 @@ hipError_t fr_launch_math_probe(int which, const double *in, double *out, size_t
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(math_probe_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, which, in, out, n);
     return hipGetLastError();
+}
+
+/* ---- the launchers fr_dispatch.hip calls (fr_launch.h): plain functions, precision 1 = f32, otherwise f64 ---- */
+
+template <typename T>
+static hipError_t launch_tile_shape(const fr_kparams &p, int mode, int tile, const fr_kout &out, hipStream_t stream) {
+    switch (tile) {
+    case 6401:
+        return launch_tile<T, 64, 1, 1, 4>(p, mode, out, stream);
+    case 3202:
+        return launch_tile<T, 32, 2, 2, 2>(p, mode, out, stream);
+    case 1604:
+        return launch_tile<T, 16, 4, 2, 2>(p, mode, out, stream);
+    case 808:
+        return launch_tile<T, 8, 8, 2, 2>(p, mode, out, stream);
+    default:
+        return hipErrorInvalidValue;
+    }
+}
+
+hipError_t fr_launch_tile(const fr_kparams &p, int precision, int mode, int tile, const fr_kout &out, hipStream_t stream) {
+    return precision == 1 ? launch_tile_shape<float>(p, mode, tile, out, stream) : launch_tile_shape<double>(p, mode, tile, out, stream);
+}
+
+template <typename T>
+static hipError_t launch_strips_len(const fr_kparams &p, int mode, int strip_tiles, const fr_kout &out, hipStream_t stream) {
+    switch (strip_tiles) {
+    case 7:
+        return launch_strips<T, 7>(p, mode, out, stream);
+    case 4:
+        return launch_strips<T, 4>(p, mode, out, stream);
+    case 2:
+        return launch_strips<T, 2>(p, mode, out, stream);
+    case 1:
+        return launch_strips<T, 1>(p, mode, out, stream);
+    default:
+        return hipErrorInvalidValue;
+    }
+}
+
+hipError_t fr_launch_strips(const fr_kparams &p, int precision, int mode, int strip_tiles, const fr_kout &out, hipStream_t stream) {
+    return precision == 1 ? launch_strips_len<float>(p, mode, strip_tiles, out, stream)
+                          : launch_strips_len<double>(p, mode, strip_tiles, out, stream);
+}
+
+hipError_t fr_launch_refill(const fr_kparams &p, int precision, int mode, const fr_kout &out, hipStream_t stream) {
+    return precision == 1 ? launch_refill<float, 7>(p, mode, out, stream) : launch_refill<double, 7>(p, mode, out, stream);
+}
+
+hipError_t fr_launch_first_pass(const fr_kparams &p, int precision, bool v1, const fr_kout &out, hipStream_t stream) {
+    return precision == 1 ? launch_first_pass_len<float>(p, v1, out, stream) : launch_first_pass_len<double>(p, v1, out, stream);
+}
+
+template <typename T>
+static hipError_t launch_queue_src(const fr_kparams &p, int src, const fr_kout &out, hipStream_t stream) {
+    if (p.loop_mode == 4) return src == 1 ? launch_queue_form<T, 4, 1>(p, out, stream) : launch_queue_form<T, 4, 0>(p, out, stream);
+    return src == 1 ? launch_queue_form<T, 2, 1>(p, out, stream) : launch_queue_form<T, 2, 0>(p, out, stream);
+}
+
+hipError_t fr_launch_queue(const fr_kparams &p, int precision, int src, const fr_kout &out, hipStream_t stream) {
+    return precision == 1 ? launch_queue_src<float>(p, src, out, stream) : launch_queue_src<double>(p, src, out, stream);
 }

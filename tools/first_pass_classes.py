@@ -113,9 +113,11 @@ def main():
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import scan_asm_hazards
     flags = scan_asm_hazards.build_flags()[0] + ["--cuda-device-only", "-S"]
+    # the file of build.py's KERNEL_SOURCES that defines the first-pass kernel
+    source = next(f for f in scan_asm_hazards.build_module().KERNEL_SOURCES if "void escape_first_kernel(" in open(os.path.join(CSRC, f)).read())
     with tempfile.TemporaryDirectory() as td:
         s = os.path.join(td, "k.s")
-        subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-o", s, os.path.join(CSRC, "fr_kernels.hip")], check=True, cwd=CSRC,
+        subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-o", s, os.path.join(CSRC, source)], check=True, cwd=CSRC,
                        stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         asm = open(s).readlines()
     dyn = json.loads(subprocess.run([sys.executable, os.path.join(ROOT, "tools", "sim", "first_pass_dynamics.py"), "40000"],

@@ -34,7 +34,7 @@ The look-back follows the control flow: at a label it continues both through the
 branch that targets the label (so a reader at a loop head sees the writer at the loop's end); it stops at unconditional
 transfers.  A register overwritten on the way by another instruction is dropped from the search.  A lint, not a proof.
 
-Usage: python tools/scan_asm_hazards.py [listing.s]    (no argument: compiles fr_kernels.hip with the build's flags)
+Usage: python tools/scan_asm_hazards.py [listing.s]    (no argument: compiles build.py's KERNEL_SOURCES with the build's flags)
 Exit code 1 if a pattern is found."""
 import importlib.util
 import os
@@ -340,32 +340,46 @@ def scan(lines, only_asm=True):
     return uniq
 
 
-def build_flags():
-    """The flags the library is built with (fractal-renderer_amd/build.py), so that the ISA linted is the ISA that ships."""
+def build_module():
+    """fractal-renderer_amd/build.py: the flags the library is built with and the files that hold its kernels."""
     spec = importlib.util.spec_from_file_location("_fr_build", os.path.join(ROOT, "fractal-renderer_amd", "build.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
+    return mod
+
+
+def build_flags():
+    """The flags the library is built with (fractal-renderer_amd/build.py), so that the ISA linted is the ISA that ships."""
+    mod = build_module()
     return [f for f in mod.HIPCC_FLAGS if f not in ("-shared", "-fPIC", "-pthread")], mod.find_hipcc()
 
 
-def listing():
+def listings():
+    """-> [(source, lines)]: one listing per file of build.KERNEL_SOURCES (local labels are per translation unit)."""
     flags, hipcc = build_flags()
+    out = []
     with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "k.s")
-        subprocess.run([hipcc] + flags + ["--cuda-device-only", "-S", "-o", out, os.path.join(CSRC, "fr_kernels.hip")], check=True, cwd=CSRC,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        return open(out).read().split("\n")
+        for src in build_module().KERNEL_SOURCES:
+            lst = os.path.join(td, src + ".s")
+            subprocess.run([hipcc] + flags + ["--cuda-device-only", "-S", "-o", lst, os.path.join(CSRC, src)], check=True, cwd=CSRC,
+                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+            out.append((src, open(lst).read().split("\n")))
+    return out
 
 
 def main(argv=()):
-    lines = open(argv[0]).read().split("\n") if len(argv) > 0 else listing()
-    bad = scan(lines)
-    for name, rl, rt, wl, wt, between, waits, regs in bad:
-        print("[%s] line %d: %s   <-   line %d: %s   (%s; %d wait states in between, %d needed)" % (name, rl, rt, wl, wt, ",".join(regs), between, waits))
-    ins, _, blocks = parse(lines)
-    print("%d instructions, %d of them in %d asm statements, %d rules: %d hazard patterns" % (
-        len(ins), sum(1 for x in ins if x.in_asm), len(blocks), len(RULES) + 1, len(bad)))
-    return 1 if bad else 0
+    todo = [(argv[0], open(argv[0]).read().split("\n"))] if len(argv) > 0 else listings()
+    nins = nasm = nblocks = nbad = 0
+    for src, lines in todo:
+        bad = scan(lines)
+        for name, rl, rt, wl, wt, between, waits, regs in bad:
+            print("[%s] %s line %d: %s   <-   line %d: %s   (%s; %d wait states in between, %d needed)" % (
+                name, src, rl, rt, wl, wt, ",".join(regs), between, waits))
+        ins, _, blocks = parse(lines)
+        nins, nasm, nblocks, nbad = nins + len(ins), nasm + sum(1 for x in ins if x.in_asm), nblocks + len(blocks), nbad + len(bad)
+    print("%d listings, %d instructions, %d of them in %d asm statements, %d rules: %d hazard patterns" % (
+        len(todo), nins, nasm, nblocks, len(RULES) + 1, nbad))
+    return 1 if nbad else 0
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Strip length of the strip kernel (1 / 2 / 4 / 7 tiles per one-wave workgroup) against launch size: kernel ms by HIP events
 (second best of five) for a handful of views at sizes from 1280x720 to 8192^2, f32 and f64.  What the by-size rule of the
-default dispatch (fr_kernels.hip: launch_precision, case 0) is fitted to."""
+default dispatch (fr_dispatch.hip: launch_precision, case 0) is fitted to."""
 import ctypes as C
 import os
 import sys
