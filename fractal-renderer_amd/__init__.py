@@ -30,6 +30,7 @@ __all__ = [
     "escape_rows", "colour_image", "count_iterations", "init", "shutdown", "device_count", "device_name",
     "RenderOpts", "init_devices", "get_image_multi", "multi_stats", "build_id", "get_image_fern", "split_dd",
     "box_filter", "ss_workspace_bytes", "SS_MAX",
+    "escape_rows_device", "extend_rows_device", "extend_rows", "colour_rows_device",
 ]
 
 
@@ -336,6 +337,65 @@ def escape_rows(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, wit
         _native.load().fr_escape_rows(C.byref(config), int(precision), y0, y1, z.ctypes.data, it.ctypes.data)
     )
     return z, it
+
+
+def _stream(stream):
+    """a hipStream_t handle as an int (None = the null stream) -> void pointer for the C call"""
+    return C.c_void_p(int(stream)) if stream else None
+
+
+def _rows(config, y0, y1):
+    return int(y0), int(config.height if y1 is None else y1)
+
+
+def escape_rows_device(config, z_ptr, iters_ptr, y0=0, y1=None, precision=Precision.F64, pos_lo=None, z_width=2, stream=None,
+                       opts=None):
+    """fr_escape_rows_device: recursive() results of rows [y0, y1) into DEVICE arrays, asynchronously on `stream`.
+    z_ptr / iters_ptr: raw device pointers as ints (either may be 0 / None) to z_width float64 and one uint32 per pixel;
+    z_width=4 (Precision.DD only) keeps the low parts.  This is the state a GUI keeps per view: 20 bytes per pixel, 36 for
+    DD with its low parts."""
+    y0, y1 = _rows(config, y0, y1)
+    lo, _keep = _pos_lo(pos_lo)
+    _native.check(_native.load().fr_escape_rows_device(C.byref(config), int(precision), lo, y0, y1, int(z_width), z_ptr or None,
+                                                       iters_ptr or None, _stream(stream), C.byref(opts) if opts is not None else None))
+
+
+def extend_rows_device(config, z_ptr, iters_ptr, from_iterations, y0=0, y1=None, precision=Precision.F64, pos_lo=None, z_width=2,
+                       stream=None, opts=None):
+    """fr_escape_extend_device: raise the cap of the stored results of rows [y0, y1) from `from_iterations` to
+    config.iterations IN PLACE, asynchronously on `stream`.  The arrays must hold what escape_rows_device wrote for the same
+    view at the lower cap (the library cannot check that); afterwards they hold the render at config.iterations, bit for
+    bit.  Precision.DD needs z_width=4; Precision.PT is refused."""
+    y0, y1 = _rows(config, y0, y1)
+    lo, _keep = _pos_lo(pos_lo)
+    _native.check(_native.load().fr_escape_extend_device(C.byref(config), int(precision), lo, y0, y1, int(from_iterations),
+                                                         int(z_width), z_ptr or None, iters_ptr or None, _stream(stream),
+                                                         C.byref(opts) if opts is not None else None))
+
+
+def extend_rows(config, z, iters, from_iterations, precision=Precision.F64, pos_lo=None, y0=0, y1=None):
+    """fr_escape_extend over numpy arrays: z float64 [rows, width, 2] ([rows, width, 4] for Precision.DD) and iters uint32
+    [rows, width] as escape_rows returned them at the cap `from_iterations` -> the same pair at config.iterations (copies;
+    the arguments are left alone)."""
+    y0, y1 = _rows(config, y0, y1)
+    zw = 4 if int(precision) == Precision.DD else 2
+    z = np.array(z, dtype=np.float64, order="C")
+    iters = np.array(iters, dtype=np.uint32, order="C")
+    shape = (max(y1 - y0, 0), config.width)
+    if z.shape != shape + (zw,) or iters.shape != shape:
+        raise ValueError("z must be [rows, width, %d] and iters [rows, width] for rows [y0, y1)" % zw)
+    lo, _keep = _pos_lo(pos_lo)
+    _native.check(_native.load().fr_escape_extend(C.byref(config), int(precision), lo, y0, y1, int(from_iterations), zw,
+                                                  z.ctypes.data, iters.ctypes.data))
+    return z, iters
+
+
+def colour_rows_device(config, z_ptr, iters_ptr, n, out_ptr, channels=3, z_width=2, stream=None):
+    """fr_colour_rows_device: the colour map alone over n stored results in DEVICE memory into channels * n bytes at out_ptr
+    (3: r,g,b; 4: r,g,b,255, 4-byte aligned), asynchronously on `stream`.  z_width=4 colours DD results on their hi parts."""
+    n = int(n)
+    _native.check(_native.load().fr_colour_rows_device(C.byref(config), z_ptr or None, int(z_width), iters_ptr or None, n,
+                                                       int(channels), out_ptr or None, int(channels) * n, _stream(stream)))
 
 
 def colour_image(config, z, iters):

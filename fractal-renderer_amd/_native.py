@@ -230,6 +230,25 @@ PROTOTYPES = {
     "fr_colour_rgb8": (C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "fr_colour_rgb8_device": (
         C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fr_escape_rows_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_int, C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+         C.c_void_p, _OPTS],
+    ),
+    "fr_escape_extend_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_int, C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
+         C.c_void_p, C.c_void_p, _OPTS],
+    ),
+    "fr_escape_extend": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_int, C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
+         C.c_void_p],
+    ),
+    "fr_colour_rows_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
     "fr_count_iterations": (
         C.c_int,
         [C.POINTER(fr_config), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),

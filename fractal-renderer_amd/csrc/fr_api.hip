@@ -738,6 +738,27 @@ int check_precision_lo(const fr_config *cfg, int precision, const fr_imaginary *
 
 int check_precision_or_deep(const fr_config *cfg, int precision) { return check_precision_lo(cfg, precision, nullptr); }
 
+/* profiling (fr_set_profiling) around the launches of one device-pointer call on `stream`: events before and after, and
+ * the name fr_last_kernel_name reports */
+static int prof_begin(hipStream_t stream) {
+    Profiling &pr = tl_prof;
+    if (!pr.enabled) return FR_OK;
+    if (!pr.e0) {
+        HIP_TRY(hipEventCreate(&pr.e0));
+        HIP_TRY(hipEventCreate(&pr.e1));
+    }
+    HIP_TRY(hipEventRecord(pr.e0, stream));
+    return FR_OK;
+}
+static int prof_end(hipStream_t stream, const char *kname) {
+    Profiling &pr = tl_prof;
+    if (!pr.enabled) return FR_OK;
+    HIP_TRY(hipEventRecord(pr.e1, stream));
+    pr.have = true;
+    pr.kernel = kname;
+    return FR_OK;
+}
+
 int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0,
                        uint32_t y1, unsigned bpp, void *d_out, hipStream_t stream) {
     fr_kparams p;
@@ -749,14 +770,8 @@ int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const fr_i
     p.out_rgba = bpp == 4 ? 1u : 0u;
     fr_kout out{};
     out.rgb = static_cast<uint8_t *>(d_out);
-    Profiling &pr = tl_prof;
-    if (pr.enabled) {
-        if (!pr.e0) {
-            HIP_TRY(hipEventCreate(&pr.e0));
-            HIP_TRY(hipEventCreate(&pr.e1));
-        }
-        HIP_TRY(hipEventRecord(pr.e0, stream));
-    }
+    int prc = prof_begin(stream);
+    if (prc != FR_OK) return prc;
     const char *kname = "";
     if (precision == FR_PRECISION_PT) {
         const int rc = launch_pt(ctx, cfg, pos_lo, p, FR_OUT_RGB, out, stream, &kname);
@@ -765,12 +780,7 @@ int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const fr_i
         HIP_TRY(fr_launch_escape_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, FR_OUT_RGB, out, false, stream,
                                     &kname));
     }
-    if (pr.enabled) {
-        HIP_TRY(hipEventRecord(pr.e1, stream));
-        pr.have = true;
-        pr.kernel = kname;
-    }
-    return FR_OK;
+    return prof_end(stream, kname);
 }
 
 std::atomic<int> g_dispatch_sampling{1};
@@ -1110,22 +1120,11 @@ int render_device(Ctx &ctx, const fr_config *cfg, fr_kparams &p, int precision, 
     fr_kout out{};
     out.rgb = static_cast<uint8_t *>(d_out);
     out.trace = g_queue_trace.load();
-    Profiling &pr = tl_prof;
-    if (pr.enabled) {
-        if (!pr.e0) {
-            HIP_TRY(hipEventCreate(&pr.e0));
-            HIP_TRY(hipEventCreate(&pr.e1));
-        }
-        HIP_TRY(hipEventRecord(pr.e0, stream));
-    }
+    int prc = prof_begin(stream);
+    if (prc != FR_OK) return prc;
     const char *kname = "";
     HIP_TRY(fr_launch_escape(p, precision, FR_OUT_RGB, out, o.tile, stream, &kname));
-    if (pr.enabled) {
-        HIP_TRY(hipEventRecord(pr.e1, stream));
-        pr.have = true;
-        pr.kernel = kname;
-    }
-    return FR_OK;
+    return prof_end(stream, kname);
 }
 
 int render_block_cyclic(Ctx &ctx, const fr_config *cfg, int precision, const Opts &o, uint32_t block_rows,
@@ -1576,6 +1575,176 @@ int fr_escape_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t
 int fr_escape_rows_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z,
                       uint32_t *iters) {
     return escape_rows(cfg, FR_PRECISION_PT, pos_lo, y0, y1, z, iters, 2);
+}
+
+/* ---- a view kept on the device: raw results into device arrays, their cap raised in place ------- */
+
+static void rows_grid(fr_kparams &p, uint32_t y0, uint32_t y1) {
+    p.nrows = y1 - y0;
+    p.y_first = y0;
+    p.block_rows = p.nrows;
+    p.y_stride = 0;
+}
+
+/* what escape_rows() launches, on the caller's stream into the caller's arrays: no scratch, no copy, no ctx->mu */
+static int escape_rows_launch(Ctx &ctx, const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0,
+                              uint32_t y1, unsigned zw, double *d_z, uint32_t *d_iters, hipStream_t stream) {
+    fr_kparams p;
+    fill_params(cfg, o, p);
+    rows_grid(p, y0, y1);
+    fr_kout ko{};
+    ko.z = d_z;
+    ko.iters = d_iters;
+    int rc = prof_begin(stream);
+    if (rc != FR_OK) return rc;
+    const char *kname = "";
+    if (precision == FR_PRECISION_DD) {
+        HIP_TRY(fr_launch_escape_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, FR_OUT_ESCAPE, ko, zw == 4, stream, &kname));
+    } else if (precision == FR_PRECISION_PT) {
+        rc = launch_pt(ctx, cfg, pos_lo, p, FR_OUT_ESCAPE, ko, stream, &kname);
+        if (rc != FR_OK) return rc;
+    } else {
+        plan_loop(cfg, precision, o, p);
+        HIP_TRY(fr_launch_escape(p, precision, FR_OUT_ESCAPE, ko, o.tile, stream, &kname));
+    }
+    return prof_end(stream, kname);
+}
+
+static int check_pos_lo_precision(int precision, const fr_imaginary *pos_lo) {
+    if (pos_lo && precision != FR_PRECISION_DD && precision != FR_PRECISION_PT)
+        return fail(FR_ERR_INVALID_ARGUMENT, "pos_lo is for FR_PRECISION_DD and FR_PRECISION_PT only");
+    return FR_OK;
+}
+
+int fr_escape_rows_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
+                          int z_width, void *d_z, void *d_iters, void *hip_stream, const fr_render_opts *opts) {
+    int rc = check_rows(cfg, y0, y1);
+    if (rc == FR_OK) rc = check_pos_lo_precision(precision, pos_lo);
+    if (rc == FR_OK) rc = check_precision_lo(cfg, precision, pos_lo);
+    if (rc != FR_OK) return rc;
+    if (z_width != 2 && !(z_width == 4 && precision == FR_PRECISION_DD))
+        return fail(FR_ERR_INVALID_ARGUMENT, "z_width must be 2, or 4 with FR_PRECISION_DD (re.hi, re.lo, im.hi, im.lo)");
+    Opts o;
+    rc = resolve_opts(opts, o);
+    if (rc != FR_OK) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    if (npx == 0 || (!d_z && !d_iters)) return FR_OK;
+    if (reinterpret_cast<uintptr_t>(d_z) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_z must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_iters) & 3u) return fail(FR_ERR_INVALID_ARGUMENT, "d_iters must be 4-byte aligned");
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    return escape_rows_launch(*ctx, cfg, precision, pos_lo, o, y0, y1, (unsigned)z_width, static_cast<double *>(d_z),
+                              static_cast<uint32_t *>(d_iters), static_cast<hipStream_t>(hip_stream));
+}
+
+/* The domain of the extension (include/fractal_hip.h), checked before any device work.  *work = false: a legal call with
+ * nothing to do (no rows, M == N, or an algorithm without orbits: its stored results do not depend on the cap). */
+static int check_extend(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
+                        uint32_t from_iterations, int z_width, const void *z, const void *iters, const fr_render_opts *opts, Opts &o,
+                        bool *work) {
+    *work = false;
+    int rc = check_rows(cfg, y0, y1);
+    if (rc != FR_OK) return rc;
+    if (precision == FR_PRECISION_PT)
+        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_PT results cannot be extended: a pixel's state is (X, m, dz), not the stored z, "
+                                             "and the step at which it meets the end of its reference orbit depends on the cap");
+    rc = check_pos_lo_precision(precision, pos_lo);
+    if (rc == FR_OK) rc = check_precision_lo(cfg, precision, pos_lo);
+    if (rc != FR_OK) return rc;
+    if (precision == FR_PRECISION_DD ? z_width != 4 : z_width != 2)
+        return fail(FR_ERR_INVALID_ARGUMENT, "z_width must be 2 for FR_PRECISION_F64 / FR_PRECISION_F32 and 4 for FR_PRECISION_DD "
+                                             "(the low parts are state)");
+    if (cfg->iterations < from_iterations)
+        return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from stored results");
+    rc = resolve_opts(opts, o);
+    if (rc != FR_OK) return rc;
+    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
+    if (!z || !iters) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the extension needs both z and iters");
+    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "z must be 8-byte aligned and iters 4-byte aligned");
+    *work = cfg->iterations != from_iterations && (cfg->algo == FR_ALGO_MANDELBROT || cfg->algo == FR_ALGO_JULIA);
+    return FR_OK;
+}
+
+static int extend_launch(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0, uint32_t y1,
+                         uint32_t from_iterations, double *d_z, uint32_t *d_iters, hipStream_t stream) {
+    fr_kparams p;
+    fill_params(cfg, o, p);
+    rows_grid(p, y0, y1);
+    int rc = prof_begin(stream);
+    if (rc != FR_OK) return rc;
+    const char *kname = "";
+    if (precision == FR_PRECISION_DD) {
+        HIP_TRY(fr_launch_escape_extend_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, from_iterations, d_z, d_iters,
+                                           stream, &kname));
+    } else {
+        plan_loop(cfg, precision, o, p); /* loop_spec: the speculative blocks, unless opts->loop_mode == 5 */
+        HIP_TRY(fr_launch_escape_extend(p, precision, from_iterations, d_z, d_iters, stream, &kname));
+    }
+    return prof_end(stream, kname);
+}
+
+int fr_escape_extend_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
+                            uint32_t from_iterations, int z_width, void *d_z, void *d_iters, void *hip_stream,
+                            const fr_render_opts *opts) {
+    Opts o;
+    bool work;
+    int rc = check_extend(cfg, precision, pos_lo, y0, y1, from_iterations, z_width, d_z, d_iters, opts, o, &work);
+    if (rc != FR_OK || !work) return rc;
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    return extend_launch(cfg, precision, pos_lo, o, y0, y1, from_iterations, static_cast<double *>(d_z),
+                         static_cast<uint32_t *>(d_iters), static_cast<hipStream_t>(hip_stream));
+}
+
+int fr_escape_extend(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
+                     uint32_t from_iterations, int z_width, double *z, uint32_t *iters) {
+    Opts o;
+    bool work;
+    int rc = check_extend(cfg, precision, pos_lo, y0, y1, from_iterations, z_width, z, iters, nullptr, o, &work);
+    if (rc != FR_OK || !work) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    const size_t zb = npx * (size_t)z_width * sizeof(double), ib = npx * sizeof(uint32_t);
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = ctx->reserve(ctx->z, zb);
+    if (rc == FR_OK) rc = ctx->reserve(ctx->iters, ib);
+    if (rc != FR_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->z.ptr, z, zb, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->iters.ptr, iters, ib, hipMemcpyHostToDevice, ctx->stream));
+    rc = extend_launch(cfg, precision, pos_lo, o, y0, y1, from_iterations, static_cast<double *>(ctx->z.ptr),
+                       static_cast<uint32_t *>(ctx->iters.ptr), ctx->stream);
+    if (rc != FR_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(z, ctx->z.ptr, zb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(iters, ctx->iters.ptr, ib, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FR_OK;
+}
+
+int fr_colour_rows_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, size_t n, int channels,
+                          void *d_out, size_t out_len, void *hip_stream) {
+    if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (z_width != 2 && z_width != 4) return fail(FR_ERR_INVALID_ARGUMENT, "z_width must be 2 (re, im) or 4 (re.hi, re.lo, im.hi, im.lo)");
+    if (channels != 3 && channels != 4) return fail(FR_ERR_INVALID_ARGUMENT, "channels must be 3 (RGB) or 4 (RGBA)");
+    if (n == 0) return FR_OK;
+    if (!d_z || !d_iters || !d_out) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array");
+    if (n > SIZE_MAX / 4 || out_len < (size_t)channels * n) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*n");
+    if ((reinterpret_cast<uintptr_t>(d_z) & 7u) || (reinterpret_cast<uintptr_t>(d_iters) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "d_z must be 8-byte aligned and d_iters 4-byte aligned");
+    if (channels == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "RGBA8 output must be 4-byte aligned");
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    HIP_TRY(fr_launch_colour_rows(p, static_cast<const double *>(d_z), (uint32_t)z_width, static_cast<const uint32_t *>(d_iters), n,
+                                  (uint32_t)channels, d_out, static_cast<hipStream_t>(hip_stream)));
+    return FR_OK;
 }
 
 int fr_colour_rgb8(const fr_config *cfg, const double *z_re_im, const uint32_t *iters, size_t n, uint8_t *out,

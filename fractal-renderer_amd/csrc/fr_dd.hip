@@ -203,7 +203,76 @@ __global__ __launch_bounds__(64 * kDdWaves) void escape_dd_kernel(const fr_kpara
     }
 }
 
+/* Raise the cap of stored DD results in place (include/fractal_hip.h, fr_escape_extend_device): a stored (re, im, iters ==
+ * N) — all four doubles, the low parts are state — is recursive()'s `previous` after N unescaped steps, and orbit_dd takes
+ * it on for M - N more with the c the render uses (start_dd of the pixel, or julia_set).  escape_dd_kernel's shape: 4
+ * waves, 16 x 16 pixels.  `iters` is read first; a workgroup with no pixel at N ends there, having written nothing, and a
+ * finished pixel's z is neither loaded nor stored. */
+__global__ __launch_bounds__(64 * kDdWaves) void escape_extend_dd_kernel(const fr_kparams p, double *z, uint32_t *iters,
+                                                                        const uint32_t from, const double lo_re, const double lo_im) {
+    __shared__ dd s_re[kDdBlockW];
+    __shared__ dd s_im[kDdBlockH];
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDdBlockW - 1) / kDdBlockW);
+    const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+    const uint32_t col0 = bx * kDdBlockW, row0 = by * kDdBlockH;
+    const uint32_t wave = tid >> 6, lane = tid & 63;
+    const uint32_t lx = (wave % kDdWavesX) * kDdTileW + lane % kDdTileW;
+    const uint32_t ly = (wave / kDdWavesX) * kDdTileH + lane / kDdTileW;
+    const uint32_t cx = col0 + lx, r = row0 + ly;
+    const bool valid = cx < p.ncols && r < p.nrows;
+    const uint64_t k = (uint64_t)r * p.ncols + cx;
+    uint32_t done = 0;
+    if (valid) done = iters[k];
+    const bool running = valid && done == from;
+    if (!__syncthreads_or(running ? 1 : 0)) return; /* whole workgroup (uniform) */
+
+    const bool julia = p.algo == 2;
+    if (!julia) { /* uniform: c = the pixel's start, staged as escape_dd_kernel stages it */
+        if (tid < kDdBlockW + kDdBlockH) {
+            const double width = (double)p.width, height = (double)p.height;
+            if (tid < kDdBlockW) {
+                const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
+                s_re[tid] = start_dd((double)x, height, (width / height) / 2.0, p.pos_re, lo_re, p.scale_re);
+            } else {
+                const uint32_t rr = row0 + (tid - kDdBlockW);
+                const uint64_t y = (uint64_t)p.y_first + (uint64_t)(rr / p.block_rows) * p.y_stride + rr % p.block_rows;
+                s_im[tid - kDdBlockW] = start_dd((double)y, height, 0.5, p.pos_im, lo_im, p.scale_im);
+            }
+        }
+        __syncthreads();
+    }
+    if (running) {
+        dd re{z[4 * k], z[4 * k + 1]}, im{z[4 * k + 2], z[4 * k + 3]};
+        const double squared = p.limit * p.limit; /* calc/src/lib.rs:246 */
+        const uint32_t n = p.iterations - from;
+        uint32_t it;
+        if (julia)
+            it = orbit_dd<true>(n, re, im, dd{p.julia_re, 0.0}, dd{p.julia_im, 0.0}, squared);
+        else
+            it = orbit_dd<false>(n, re, im, s_re[lx], s_im[ly], squared);
+        z[4 * k] = re.hi;
+        z[4 * k + 1] = re.lo;
+        z[4 * k + 2] = im.hi;
+        z[4 * k + 3] = im.lo;
+        iters[k] = from + it; /* it == n on exhaustion: the new cap */
+    }
+}
+
 }  // namespace
+
+hipError_t fr_launch_escape_extend_dd(const fr_kparams &p, double pos_lo_re, double pos_lo_im, uint32_t from_iterations,
+                                      double *z, uint32_t *iters, hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = "escape_extend_dd_kernel";
+    if (p.ncols == 0 || p.nrows == 0) return hipSuccess;
+    if (p.iterations < from_iterations || (p.algo != 0 && p.algo != 2)) return hipErrorInvalidValue;
+    const uint64_t tiles = (((uint64_t)p.ncols + kDdBlockW - 1) / kDdBlockW) * (((uint64_t)p.nrows + kDdBlockH - 1) / kDdBlockH);
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    escape_extend_dd_kernel<<<dim3((uint32_t)tiles), dim3(64 * kDdWaves), 0, stream>>>(p, z, iters, from_iterations, pos_lo_re,
+                                                                                     pos_lo_im);
+    return hipGetLastError();
+}
 
 hipError_t fr_launch_escape_dd(const fr_kparams &p, double pos_lo_re, double pos_lo_im, int mode, const fr_kout &out,
                                bool with_lo, hipStream_t stream, const char **kernel_name) {

@@ -194,6 +194,22 @@ hipError_t fr_launch_palette(const fr_kparams &p, uint32_t *palette, hipStream_t
 hipError_t fr_launch_colour(const fr_kparams &p, const double *z, const uint32_t *iters, size_t n, uint8_t *rgb,
                             hipStream_t stream);
 
+/* Raise the cap of stored recursive() results in place (fr_kernels.hip: escape_extend_kernel<T>; include/fractal_hip.h,
+ * fr_escape_extend_device): the launch's local grid from `p` as the render takes it (y_first, nrows, block_rows = nrows),
+ * p.iterations = the new cap M >= from_iterations = N, p.loop_spec from plan_loop; z = 2 doubles per pixel, both arrays
+ * required.  Pixels with iters[k] != N are not touched.  Escape-time algorithms only.  precision 1 = f32, otherwise f64. */
+hipError_t fr_launch_escape_extend(const fr_kparams &p, int precision, uint32_t from_iterations, double *z, uint32_t *iters,
+                                   hipStream_t stream, const char **kernel_name);
+/* the same for FR_PRECISION_DD (fr_dd.hip: escape_extend_dd_kernel): z = re.hi, re.lo, im.hi, im.lo per pixel */
+hipError_t fr_launch_escape_extend_dd(const fr_kparams &p, double pos_lo_re, double pos_lo_im, uint32_t from_iterations,
+                                      double *z, uint32_t *iters, hipStream_t stream, const char **kernel_name);
+
+/* colour map only over n stored results with a z stride (fr_kernels.hip: colour_rows_kernel): z_width 2 (re, im) or 4
+ * (re.hi, re.lo, im.hi, im.lo: colour on the hi parts), channels 3 (r,g,b; any alignment) or 4 (r,g,b,255; out 4-byte
+ * aligned).  Device arrays; the same bytes as fr_launch_colour and as the renders. */
+hipError_t fr_launch_colour_rows(const fr_kparams &p, const double *z, uint32_t z_width, const uint32_t *iters, size_t n,
+                                 uint32_t channels, void *out, hipStream_t stream);
+
 /* Box filter of supersampled rendering (fr_ss.hip: box_filter_kernel): src = packed r,g,b rows of s * width pixels
  * (s * rows of them), dst = packed rows of `width` pixels, bpp 3 (r,g,b) or 4 (r,g,b,255; dst 4-byte aligned); each
  * output byte = (sum of its s x s block + floor(s*s / 2)) / (s*s).  s = 1 .. FR_SS_MAX; any alignment otherwise;

@@ -17,7 +17,7 @@
  *   escape_queue_kernel (<.., 0>: the work queue over the image, tile = 10; <.., 1>: round 2's second pass, tiles 12 and 14,
  *   comparison only) and escape_second_kernel (the two-pass render's second pass since round 3);
  *   recursive_batch_kernel, view_sample_kernel, palette_kernel, colour_kernel, copy_out_kernel; math_probe_kernel,
- *   cast_scan_kernel, nu_scan_kernel (test hooks).
+ *   cast_scan_kernel, nu_scan_kernel (test hooks); escape_extend_kernel and colour_rows_kernel (a view kept on the device).
  * Which of them a render gets is decided in fr_dispatch.hip (host only), which calls the plain launchers at the end of
  * this file (fr_launch.h).  tools/isa_digest.py shows that an edit here left every kernel's ISA alone.
  */
@@ -3470,7 +3470,159 @@ __global__ __launch_bounds__(256) void copy_out_kernel(const uint8_t *src, uint8
     }
 }
 
+/* ---- a view kept on the device: raise the cap of stored results, recolour them (include/fractal_hip.h) ----------
+ *
+ * escape_extend_kernel: recursive()'s state after N unescaped steps is `previous`, which is what exhaustion stores, and c
+ * is a function of the pixel — so a stored (z, iters == N) is an orbit paused at step N, and orbit_run (state in, count
+ * in, speculative blocks included: the primitive every episode kernel resumes orbits with) takes it to the new cap M
+ * with the values and the index the render at M produces.  One wave per 8 x 8 tile, as the one-tile strip kernel:
+ *   - `iters` first (256 bytes a tile); a tile with no lane at N — the exterior: most tiles of most views — ends there,
+ *     having written nothing;
+ *   - z is loaded for the running lanes only, c recomputed with the strip kernel's coordinate pass (the same
+ *     expression on the same operands, 8 column lanes + 8 row lanes, handed out with cross-lane reads);
+ *   - the orbit loop runs with EXEC restricted to the running lanes, and only they store.  A finished pixel's z is
+ *     never loaded and nothing of it is written; an index above N is foreign data and is left alone too.
+ * 64-bit element offsets throughout. */
+template <typename T>
+__global__ __launch_bounds__(64) void escape_extend_kernel(const fr_kparams p, double *z, uint32_t *iters, const uint32_t from) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t row0 = (blockIdx.y + gridDim.y * blockIdx.z) * 8u;
+    if (row0 >= p.nrows) return; /* whole workgroup (uniform) */
+    const uint32_t col0 = blockIdx.x * 8u;
+    const uint32_t lx = lane & 7u, ly = lane >> 3;
+    const uint32_t cx = col0 + lx, r = row0 + ly;
+    const bool valid = cx < p.ncols && r < p.nrows;
+    const uint64_t k = (uint64_t)r * p.ncols + cx;
+    uint32_t done = 0;
+    if (valid) done = iters[k];
+    const bool running = valid && done == from;
+    if (ballot64(running) == 0ull) return; /* wave-uniform: nothing of this tile is still running */
+
+    /* c: the pixel's coordinate (Mandelbrot) or julia_set (calc/src/lib.rs:209-210).  Lanes 0-7 evaluate the tile's column
+     * coordinates, lanes 8-15 its rows: ((coord / height) - offset) / scale + pos with per-lane operands */
+    double cre = p.julia_re, cim = p.julia_im;
+    if (p.algo == 0) {
+        const bool row_lane = lane >= 8u;
+        uint32_t coord_u;
+        if (row_lane) {
+            const uint32_t rr = row0 + ((lane - 8u) & 7u);
+            coord_u = p.y_first + (rr / p.block_rows) * p.y_stride + rr % p.block_rows;
+        } else {
+            coord_u = p.x_first + (col0 + lane) * p.x_stride;
+        }
+        const double width = (double)p.width, height = (double)p.height;
+        const double coord_lane = coord_to_space((double)coord_u, height, row_lane ? 0.5 : (width / height) / 2.0,
+                                                 row_lane ? p.pos_im : p.pos_re, row_lane ? p.scale_im : p.scale_re);
+        cre = __shfl(coord_lane, lx, 64);
+        cim = __shfl(coord_lane, 8 + ly, 64);
+    }
+    if (running) {
+        const uint32_t n = p.iterations - from;
+        uint32_t it, completed;
+        if constexpr (sizeof(T) == 8) {
+            double re = z[2 * k], im = z[2 * k + 1];
+            double r2 = re * re, i2 = im * im;
+            it = orbit_run<double>(n, re, im, cre, cim, p.limit * p.limit, r2, i2, EpisodeCtl{0, 0}, completed, p.loop_spec);
+            z[2 * k] = re;
+            z[2 * k + 1] = im;
+        } else {
+            /* the stored doubles are widened f32 values: narrowing them back is exact */
+            float re = (float)z[2 * k], im = (float)z[2 * k + 1];
+            float r2 = re * re, i2 = im * im;
+            const float lim = (float)p.limit;
+            it = orbit_run<float>(n, re, im, (float)cre, (float)cim, lim * lim, r2, i2, EpisodeCtl{0, 0}, completed, p.loop_spec);
+            z[2 * k] = (double)re;
+            z[2 * k + 1] = (double)im;
+        }
+        iters[k] = it >= completed ? p.iterations : from + it;
+    }
+}
+
+/* The colour map over stored results with a z stride (2: re, im; 4: re.hi, re.lo, im.hi, im.lo — colour on the hi
+ * parts) and RGB or RGBA output: what a GUI's exposure slider sits on.  A workgroup of 256 takes four helpings of 256 pixels,
+ * a grid's width apart, so the 3 KB log2 table is staged once per 1024 pixels, not once per 256, and only when the colour
+ * map reads it.  One pixel per lane, coalesced loads; RGBA leaves as one dword per pixel, RGB as whole dwords too where
+ * `out` is 4-byte aligned: a full wave's 64 pixels are 48 dwords, dword L of them holds bytes of the pixels 4L / 3 and
+ * 4L / 3 + 1, fetched from their lanes with two cross-lane reads.  (A wave's first pixel is a multiple of 64, so its 192
+ * bytes start on a dword.)  The last, partial wave and an unaligned `out` store bytes. */
+__global__ __launch_bounds__(256) void colour_rows_kernel(const fr_kparams p, const double *z, const uint32_t zw, const uint32_t *iters,
+                                                        const size_t n, const uint32_t bpp, uint8_t *out) {
+    __shared__ double s_tab[FR_LOG2_N * 3];
+    const bool escape_algo = p.algo == 0 || p.algo == 2;
+    if (escape_algo && p.smooth) { /* uniform */
+        const double *gt = &g_log2_tab[0][0];
+        for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += 256) s_tab[k] = gt[k];
+        __syncthreads();
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool dwords = (reinterpret_cast<uintptr_t>(out) & 3u) == 0;
+    const uint32_t im_at = zw >> 1;
+    for (size_t base = (size_t)blockIdx.x * 256; base < n; base += (size_t)gridDim.x * 256) {
+        const size_t k = base + threadIdx.x;
+        const bool valid = k < n;
+        uint32_t packed = 0;
+        if (valid && escape_algo) {
+            const double re = z[(size_t)zw * k], im = z[(size_t)zw * k + im_at];
+            uint8_t rgb[3] = {0, 0, 0};
+            /* the ~40 constants of the colour map are read where they are used (scalar loads from the kernel-argument
+             * segment, once per 256 pixels): held across the loop they overflow the scalar file */
+            FR_COLD_PARAMS(kp);
+            const ColourConsts cc = make_colour_consts(*kp);
+            colour_of(cc, re * re + im * im, iters[k], s_tab, nullptr, rgb); /* pos.squared_distance(), :214 */
+            packed = (uint32_t)rgb[0] | ((uint32_t)rgb[1] << 8) | ((uint32_t)rgb[2] << 16);
+        }
+        if (bpp == 4u) {
+            if (valid) reinterpret_cast<uint32_t *>(out)[k] = packed | 0xFF000000u;
+            continue;
+        }
+        const size_t wave0 = k - lane; /* the wave's first pixel */
+        if (dwords && wave0 + 64 <= n) { /* wave-uniform */
+            const uint32_t first = (4u * lane) / 3u, shift = 8u * ((4u * lane) % 3u);
+            const uint32_t a = __shfl(packed, first & 63u, 64), b = __shfl(packed, (first + 1u) & 63u, 64);
+            const uint64_t both = (uint64_t)a | ((uint64_t)b << 24);
+            if (lane < 48u) reinterpret_cast<uint32_t *>(out + 3 * wave0)[lane] = (uint32_t)(both >> shift);
+        } else if (valid) {
+            uint8_t *o = out + 3 * k;
+            o[0] = (uint8_t)packed;
+            o[1] = (uint8_t)(packed >> 8);
+            o[2] = (uint8_t)(packed >> 16);
+        }
+    }
+}
+
 } /* namespace */
+
+hipError_t fr_launch_escape_extend(const fr_kparams &p, int precision, uint32_t from_iterations, double *z, uint32_t *iters,
+                                   hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = precision == 1 ? "escape_extend_kernel<float>" : "escape_extend_kernel<double>";
+    if (p.ncols == 0 || p.nrows == 0) return hipSuccess;
+    if (p.iterations < from_iterations || (p.algo != 0 && p.algo != 2)) return hipErrorInvalidValue;
+    const uint64_t gx = ((uint64_t)p.ncols + 7) / 8;
+    const uint64_t row_tiles = ((uint64_t)p.nrows + 7) / 8;
+    const uint64_t gy = row_tiles < 32768 ? row_tiles : 32768;
+    const uint64_t gz = (row_tiles + gy - 1) / gy;
+    if (gx > 0x7FFFFFFFull || gz > 65535) return hipErrorInvalidConfiguration;
+    const dim3 grid((uint32_t)gx, (uint32_t)gy, (uint32_t)gz), block(64);
+    if (precision == 1)
+        hipLaunchKernelGGL(escape_extend_kernel<float>, grid, block, 0, stream, p, z, iters, from_iterations);
+    else
+        hipLaunchKernelGGL(escape_extend_kernel<double>, grid, block, 0, stream, p, z, iters, from_iterations);
+    return hipGetLastError();
+}
+
+hipError_t fr_launch_colour_rows(const fr_kparams &p, const double *z, uint32_t z_width, const uint32_t *iters, size_t n,
+                                 uint32_t channels, void *out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if ((z_width != 2 && z_width != 4) || (channels != 3 && channels != 4)) return hipErrorInvalidValue;
+    /* four helpings of 256 pixels per workgroup, a grid's width apart: the table is staged once per 1024 pixels, and there
+     * are still thousands of workgroups for the dispatcher to balance (a fixed grid of 2048 measured 0.059 ms on a
+     * 3840 x 2160 frame: an eighth of it did not fit the chip at once and ran as a second round) */
+    uint64_t blocks = ((n + 255) / 256 + 3) / 4;
+    if (blocks > 0x7FFFFFFFull) blocks = 0x7FFFFFFFull; /* the kernel strides on */
+    hipLaunchKernelGGL(colour_rows_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, p, z, z_width, iters, n, channels,
+                       static_cast<uint8_t *>(out));
+    return hipGetLastError();
+}
 
 hipError_t fr_launch_copy_out(const void *src, void *dst, size_t bytes, unsigned int *counter, unsigned long long *flag,
                               unsigned long long seq, hipStream_t stream) {

@@ -129,5 +129,33 @@ inline std::vector<RGB> get_image_fern(const Config &config, uint32_t threads, u
     return image;
 }
 
+// ---- a view kept on the device (include/fractal_hip.h, "a view kept on the device"): thin wrappers ----------------
+// A GUI keeps (z, iters) of the current view in device memory (20 bytes per pixel, 36 for FR_PRECISION_DD with its low
+// parts): escape_rows_device once per view, extend_rows_device on an iterations change, colour_rows_device on every
+// control that only feeds the colour map.  Device pointers and a hipStream_t, all asynchronous.
+inline void escape_rows_device(const Config &config, void *d_z, void *d_iters, void *hip_stream = nullptr,
+                               int precision = FR_PRECISION_F64, const fr_imaginary *pos_lo = nullptr, int z_width = 2) {
+    check(fr_escape_rows_device(&config, precision, pos_lo, 0, config.height, z_width, d_z, d_iters, hip_stream, nullptr));
+}
+// config.iterations is the new cap; the arrays hold the same view at from_iterations (the library cannot check that)
+inline void extend_rows_device(const Config &config, uint32_t from_iterations, void *d_z, void *d_iters, void *hip_stream = nullptr,
+                               int precision = FR_PRECISION_F64, const fr_imaginary *pos_lo = nullptr, int z_width = 2) {
+    check(fr_escape_extend_device(&config, precision, pos_lo, 0, config.height, from_iterations, z_width, d_z, d_iters, hip_stream,
+                                  nullptr));
+}
+// the same over host vectors as fr_escape_rows filled them (z: 2 doubles per pixel), in the f64 arithmetic fr_escape_rows
+// used; FR_PRECISION_DD state is four doubles per pixel and goes through fr_escape_extend itself
+inline void extend_rows(const Config &config, uint32_t from_iterations, std::vector<double> &z, std::vector<uint32_t> &iters) {
+    const size_t n = static_cast<size_t>(config.width) * config.height;
+    if (z.size() != 2 * n || iters.size() != n) throw Error(FR_ERR_INVALID_ARGUMENT, "extend_rows: z needs 2 * width * height doubles, iters width * height");
+    check(fr_escape_extend(&config, FR_PRECISION_F64, nullptr, 0, config.height, from_iterations, 2, z.data(), iters.data()));
+}
+// channels 3 (r,g,b) or 4 (r,g,b,255; d_out 4-byte aligned) over the whole stored view
+inline void colour_rows_device(const Config &config, const void *d_z, const void *d_iters, void *d_out, int channels = 4,
+                               void *hip_stream = nullptr, int z_width = 2) {
+    const size_t n = static_cast<size_t>(config.width) * config.height;
+    check(fr_colour_rows_device(&config, d_z, z_width, d_iters, n, channels, d_out, static_cast<size_t>(channels) * n, hip_stream));
+}
+
 }  // namespace fractal
 #endif

@@ -454,6 +454,53 @@ int fr_colour_rgb8(const fr_config *cfg, const double *z_re_im, const uint32_t *
 int fr_colour_rgb8_device(const fr_config *cfg, const void *d_z_re_im, const void *d_iters, size_t n, void *d_out,
                           size_t out_len, void *hip_stream);
 
+/* ---- a view kept on the device: raw results, a higher cap, colours ------------------------------------ */
+
+/* A GUI keeps (z, iters) of the current view in DEVICE memory — 20 bytes per pixel, 36 for DD with its low parts — and
+ * answers an iterations change with fr_escape_extend_device and every control that only feeds the colour map (exposure,
+ * colours, smooth, inside) with fr_colour_rows_device; only pan, zoom and limit need new orbits.  The device forms are
+ * asynchronous on `hip_stream`, allocate nothing, take no lock beyond what the render they wrap takes (PT: the context's
+ * orbit cache), are re-entrant, and the caller owns every buffer. */
+
+/* recursive() results of rows [y0, y1) into DEVICE arrays: what fr_escape_rows / _dd / _pt copy to the host.
+ * z_width 2: re, im (DD: the hi parts); z_width 4: re.hi, re.lo, im.hi, im.lo (FR_PRECISION_DD only).
+ * d_z: z_width doubles per pixel, 8-byte aligned; d_iters: uint32 per pixel; either may be NULL; k = (y-y0)*width + x.
+ * pos_lo non-NULL only for DD and PT.  opts: NULL = defaults (selects what fr_escape_rows' launch takes: tile, loop_mode). */
+int fr_escape_rows_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
+                          int z_width, void *d_z, void *d_iters, void *hip_stream, const fr_render_opts *opts);
+
+/* Raise the iteration cap of stored results IN PLACE.  DEFINITION, with N = from_iterations, M = cfg->iterations and
+ * cfg_N = cfg with iterations = N:
+ *   Precondition: the arrays hold what fr_escape_rows_device(cfg_N, precision, pos_lo, y0, y1, z_width, ...) writes.
+ *   Result: after the call they hold what the same call writes for cfg, bit for bit, z and iters alike.
+ *   A pixel with iters[k] != N is finished: only its iters[k] is read, nothing of it is written, its z is never loaded.
+ *   Values of iters[k] above N are foreign data and are left alone like finished pixels.
+ * The library CANNOT check the precondition: arrays that come from another view, precision or cap are continued as if
+ * they were this one's, and the result is then whatever that orbit gives.  Nor is the call idempotent: in arrays that
+ * already hold cap M, iters[k] == N means "escaped at step N", and a second call N -> M would continue those orbits.
+ * Why the bytes are the render's: recursive() (calc/src/lib.rs:245-257) returns `previous` after exactly N steps when the
+ * cap is reached — the loop's whole state — and c is a function of the pixel, recomputed by the render's own coordinate
+ * code; continuing for M - N steps is the loop at cap M.
+ * Domain (else FR_ERR_INVALID_ARGUMENT, before any device work): M >= N — M == N is a legal no-op that needs no device; a
+ * lower cap cannot be derived from stored results.  FR_PRECISION_F64 and FR_PRECISION_F32 take z_width 2 (for F32 the
+ * stored doubles are widened f32 values, and narrowing them back is exact); FR_PRECISION_DD takes z_width 4 only — the low
+ * parts are state — with DD's domain on cfg and pos_lo.  FR_PRECISION_PT is refused: its per-pixel state is (X, m, dz), not
+ * z, and the step at which a pixel meets "m == last of X" depends on the cap (the orbit's length does), so a stored z does
+ * not determine the continuation.  Both d_z and d_iters are required (y0 == y1 needs neither).  pos_lo non-NULL only for
+ * DD.  opts: NULL = defaults; loop_mode 5 = no speculative blocks (same bytes).
+ * With profiling on, fr_last_kernel_name reports escape_extend_kernel<double> / <float> / escape_extend_dd_kernel. */
+int fr_escape_extend_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
+                            uint32_t from_iterations, int z_width, void *d_z, void *d_iters, void *hip_stream,
+                            const fr_render_opts *opts);
+/* the same over HOST arrays (upload, extend, download, synchronise; scratch from the context as fr_colour_rgb8 does) */
+int fr_escape_extend(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
+                     uint32_t from_iterations, int z_width, double *z, uint32_t *iters);
+
+/* The colour map over stored results in DEVICE memory: channels 3 (r,g,b) or 4 (r,g,b,255; d_out 4-byte aligned),
+ * z_width 2 or 4 (colour on the hi parts, as the DD definition says).  out_len >= channels * n. */
+int fr_colour_rows_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, size_t n, int channels,
+                          void *d_out, size_t out_len, void *hip_stream);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* Exact sum of EXECUTED loop iterations over the pixels (x, y) with x % sx == 0, y % sy == 0 of

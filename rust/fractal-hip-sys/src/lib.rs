@@ -119,6 +119,11 @@ extern "C" {
     pub fn fr_render_rows_ss(cfg: *const fr_config, precision: c_int, pos_lo: *const fr_imaginary, supersample: u32, y0: u32, y1: u32, channels: c_int, out: *mut u8, out_len: usize, opts: *const fr_render_opts) -> c_int;
     pub fn fr_box_filter_rgb8(src: *const u8, width: u32, rows: u32, supersample: u32, channels: c_int, out: *mut u8, out_len: usize) -> c_int;
     pub fn fr_box_filter_rgb8_device(d_src: *const c_void, width: u32, rows: u32, supersample: u32, channels: c_int, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    // a view kept on the device (include/fractal_hip.h): raw results into device arrays, their cap raised in place, the colour map over them
+    pub fn fr_escape_rows_device(cfg: *const fr_config, precision: c_int, pos_lo: *const fr_imaginary, y0: u32, y1: u32, z_width: c_int, d_z: *mut c_void, d_iters: *mut c_void, hip_stream: *mut c_void, opts: *const fr_render_opts) -> c_int;
+    pub fn fr_escape_extend_device(cfg: *const fr_config, precision: c_int, pos_lo: *const fr_imaginary, y0: u32, y1: u32, from_iterations: u32, z_width: c_int, d_z: *mut c_void, d_iters: *mut c_void, hip_stream: *mut c_void, opts: *const fr_render_opts) -> c_int;
+    pub fn fr_escape_extend(cfg: *const fr_config, precision: c_int, pos_lo: *const fr_imaginary, y0: u32, y1: u32, from_iterations: u32, z_width: c_int, z: *mut f64, iters: *mut u32) -> c_int;
+    pub fn fr_colour_rows_device(cfg: *const fr_config, d_z: *const c_void, z_width: c_int, d_iters: *const c_void, n: usize, channels: c_int, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
 }
 
 /// Message of the last failing call on this thread.
@@ -203,6 +208,20 @@ pub fn escape_rows(cfg: &fr_config, y0: u32, y1: u32) -> Result<(Vec<f64>, Vec<u
     }
     unsafe { z.set_len(2 * n); iters.set_len(n); } // every element was written by the library
     Ok((z, iters))
+}
+
+/// Raise the iteration cap of what `escape_rows(cfg_N, y0, y1)` returned, IN PLACE, from `from_iterations` to
+/// `cfg.iterations`: only the orbits still running at the old cap are continued, and the arrays then hold what
+/// `escape_rows(cfg, y0, y1)` returns, bit for bit (include/fractal_hip.h, `fr_escape_extend_device`) — the GUI's
+/// iterations control (src/gui.rs:180) without starting every orbit over.  The arrays must come from the same view at
+/// the lower cap; the library cannot check that.
+pub fn extend_rows(cfg: &fr_config, y0: u32, y1: u32, from_iterations: u32, z: &mut [f64], iters: &mut [u32]) -> Result<(), String> {
+    let n = cfg.width as usize * (y1.saturating_sub(y0)) as usize;
+    if z.len() != 2 * n || iters.len() != n {
+        return Err(format!("rows [{}, {}) hold {} pixels: z must have {} elements and iters {}", y0, y1, n, 2 * n, n));
+    }
+    let rc = unsafe { fr_escape_extend(cfg, FR_PRECISION_F64, std::ptr::null(), y0, y1, from_iterations, 2, z.as_mut_ptr(), iters.as_mut_ptr()) };
+    if rc != FR_OK { Err(last_error()) } else { Ok(()) }
 }
 
 /// The colour map alone (calc/src/lib.rs:214-234 + `color_multiply`) over stored `recursive()` results into a pixel
