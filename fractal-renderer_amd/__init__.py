@@ -31,6 +31,7 @@ __all__ = [
     "RenderOpts", "init_devices", "get_image_multi", "multi_stats", "build_id", "get_image_fern", "split_dd",
     "box_filter", "ss_workspace_bytes", "SS_MAX",
     "escape_rows_device", "extend_rows_device", "extend_rows", "colour_rows_device",
+    "escape_rows_pt_state", "extend_rows_pt", "escape_rows_pt_state_device", "extend_rows_pt_device", "pt_orbit_cache",
 ]
 
 
@@ -388,6 +389,62 @@ def extend_rows(config, z, iters, from_iterations, precision=Precision.F64, pos_
     _native.check(_native.load().fr_escape_extend(C.byref(config), int(precision), lo, y0, y1, int(from_iterations), zw,
                                                   z.ctypes.data, iters.ctypes.data))
     return z, iters
+
+
+def escape_rows_pt_state(config, pos_lo=None, y0=0, y1=None):
+    """fr_escape_rows_pt_state: rows [y0, y1) in Precision.PT with their resumable state: (z float64 [rows, width, 2], iters
+    uint32 [rows, width], dz float64 [rows, width, 2], m uint32 [rows, width]; bit 31 of m: a Julia pixel on K).  z and iters
+    are escape_rows' for Precision.PT, bit for bit (include/fractal_hip.h, "RESUMABLE PT")."""
+    y0, y1 = _rows(config, y0, y1)
+    shape = (max(y1 - y0, 0), config.width)
+    z, dz = np.empty(shape + (2,), dtype=np.float64), np.empty(shape + (2,), dtype=np.float64)
+    it, m = np.empty(shape, dtype=np.uint32), np.empty(shape, dtype=np.uint32)
+    lo, _keep = _pos_lo(pos_lo)
+    _native.check(_native.load().fr_escape_rows_pt_state(C.byref(config), lo, y0, y1, z.ctypes.data, it.ctypes.data,
+                                                         dz.ctypes.data, m.ctypes.data))
+    return z, it, dz, m
+
+
+def extend_rows_pt(config, z, iters, dz, m, from_iterations, pos_lo=None, y0=0, y1=None):
+    """fr_escape_extend_pt over numpy arrays: the state escape_rows_pt_state returned at the cap `from_iterations` -> the
+    state at config.iterations (copies; the arguments are left alone).  The arrays must be that view's; the library cannot
+    check it."""
+    y0, y1 = _rows(config, y0, y1)
+    shape = (max(y1 - y0, 0), config.width)
+    z, dz = np.array(z, dtype=np.float64, order="C"), np.array(dz, dtype=np.float64, order="C")
+    iters, m = np.array(iters, dtype=np.uint32, order="C"), np.array(m, dtype=np.uint32, order="C")
+    if z.shape != shape + (2,) or dz.shape != shape + (2,) or iters.shape != shape or m.shape != shape:
+        raise ValueError("z and dz must be [rows, width, 2], iters and m [rows, width] for rows [y0, y1)")
+    lo, _keep = _pos_lo(pos_lo)
+    _native.check(_native.load().fr_escape_extend_pt(C.byref(config), lo, y0, y1, int(from_iterations), z.ctypes.data,
+                                                     iters.ctypes.data, dz.ctypes.data, m.ctypes.data))
+    return z, iters, dz, m
+
+
+def escape_rows_pt_state_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, y0=0, y1=None, pos_lo=None, stream=None):
+    """fr_escape_rows_pt_state_device: the Precision.PT state of rows [y0, y1) into DEVICE arrays (raw pointers as ints:
+    z, dz 2 float64 per pixel, iters, m one uint32), asynchronously on `stream`: 40 bytes per pixel."""
+    y0, y1 = _rows(config, y0, y1)
+    lo, _keep = _pos_lo(pos_lo)
+    _native.check(_native.load().fr_escape_rows_pt_state_device(C.byref(config), lo, y0, y1, z_ptr or None, iters_ptr or None,
+                                                                dz_ptr or None, m_ptr or None, _stream(stream)))
+
+
+def extend_rows_pt_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, from_iterations, y0=0, y1=None, pos_lo=None, stream=None):
+    """fr_escape_extend_pt_device: raise the cap of the stored Precision.PT state of rows [y0, y1) from `from_iterations` to
+    config.iterations IN PLACE, asynchronously on `stream`; the view's reference orbit is continued, not recomputed."""
+    y0, y1 = _rows(config, y0, y1)
+    lo, _keep = _pos_lo(pos_lo)
+    _native.check(_native.load().fr_escape_extend_pt_device(C.byref(config), lo, y0, y1, int(from_iterations), z_ptr or None,
+                                                            iters_ptr or None, dz_ptr or None, m_ptr or None, _stream(stream)))
+
+
+def pt_orbit_cache():
+    """fr_debug_pt_orbit_cache: (iterations the cached PT orbit is for, entries of X, entries of K, entries the last request
+    computed on the host)."""
+    out = (C.c_uint32 * 4)()
+    _native.check(_native.load().fr_debug_pt_orbit_cache(out))
+    return tuple(out)
 
 
 def colour_rows_device(config, z_ptr, iters_ptr, n, out_ptr, channels=3, z_width=2, stream=None):

@@ -245,6 +245,26 @@ PROTOTYPES = {
         [C.POINTER(fr_config), C.c_int, C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
          C.c_void_p],
     ),
+    "fr_escape_rows_pt_state_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p],
+    ),
+    "fr_escape_extend_pt_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p],
+    ),
+    "fr_escape_rows_pt_state": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "fr_escape_extend_pt": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p],
+    ),
+    "fr_debug_pt_orbit_cache": (C.c_int, [C.POINTER(C.c_uint32)]),
     "fr_colour_rows_device": (
         C.c_int,
         [C.POINTER(fr_config), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],

@@ -495,6 +495,11 @@ int primary(Ctx **out) {
     return FR_OK;
 }
 
+Ctx *primary_if_created() {
+    std::lock_guard<std::mutex> lk(g_primary_mu);
+    return g_primary_inited ? &g_primary : nullptr;
+}
+
 /* calc::Config -> kernel arguments; the local grid is filled in by the caller */
 void fill_params(const fr_config *cfg, const Opts &o, fr_kparams &p) {
     memset(&p, 0, sizeof p);
@@ -1649,7 +1654,8 @@ static int check_extend(const fr_config *cfg, int precision, const fr_imaginary 
     if (rc != FR_OK) return rc;
     if (precision == FR_PRECISION_PT)
         return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_PT results cannot be extended: a pixel's state is (X, m, dz), not the stored z, "
-                                             "and the step at which it meets the end of its reference orbit depends on the cap");
+                                             "and the step at which it meets the end of its reference orbit depends on the cap; "
+                                             "fr_escape_rows_pt_state(_device) stores that state and fr_escape_extend_pt(_device) continues it");
     rc = check_pos_lo_precision(precision, pos_lo);
     if (rc == FR_OK) rc = check_precision_lo(cfg, precision, pos_lo);
     if (rc != FR_OK) return rc;
@@ -1726,6 +1732,109 @@ int fr_escape_extend(const fr_config *cfg, int precision, const fr_imaginary *po
     HIP_TRY(hipMemcpyAsync(iters, ctx->iters.ptr, ib, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FR_OK;
+}
+
+/* ---- resumable perturbation: FR_PRECISION_PT rows with their state, and that state continued to a higher cap ------- */
+
+/* The domain of the four calls (include/fractal_hip.h), checked before any device work: `from` = nullptr for the state render.
+ * *work = false: a legal call with nothing to do (no rows; for the extension also M == N or an algorithm without orbits). */
+static int check_pt_state(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, const uint32_t *from,
+                          const void *z, const void *iters, const void *dz, const void *m, bool *work) {
+    *work = false;
+    int rc = check_rows(cfg, y0, y1);
+    if (rc == FR_OK) rc = check_pt(cfg, pos_lo);
+    if (rc != FR_OK) return rc;
+    if (from && cfg->iterations < *from)
+        return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from a stored state");
+    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
+    if (!z || !iters || !dz || !m) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the PT state is z, iters, dz and m, all four");
+    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(dz) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u) ||
+        (reinterpret_cast<uintptr_t>(m) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "z and dz must be 8-byte aligned, iters and m 4-byte aligned");
+    *work = !from || (cfg->iterations != *from && (cfg->algo == FR_ALGO_MANDELBROT || cfg->algo == FR_ALGO_JULIA));
+    return FR_OK;
+}
+
+/* from == nullptr: the state render; else the extension from *from.  On the caller's stream, into the caller's arrays. */
+static int pt_state_launch(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, const uint32_t *from,
+                           double *d_z, uint32_t *d_iters, double *d_dz, uint32_t *d_m, hipStream_t stream) {
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    rows_grid(p, y0, y1);
+    int rc = prof_begin(stream);
+    if (rc != FR_OK) return rc;
+    const char *kname = "";
+    rc = from ? launch_pt_extend(ctx, cfg, pos_lo, p, *from, d_z, d_iters, d_dz, d_m, stream, &kname)
+              : launch_pt_state(ctx, cfg, pos_lo, p, d_z, d_iters, d_dz, d_m, stream, &kname);
+    if (rc != FR_OK) return rc;
+    return prof_end(stream, kname);
+}
+
+static int pt_state_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z,
+                           void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
+    bool work;
+    int rc = check_pt_state(cfg, pos_lo, y0, y1, from, d_z, d_iters, d_dz, d_m, &work);
+    if (rc != FR_OK || !work) return rc;
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    return pt_state_launch(*ctx, cfg, pos_lo, y0, y1, from, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
+                           static_cast<double *>(d_dz), static_cast<uint32_t *>(d_m), static_cast<hipStream_t>(hip_stream));
+}
+
+/* the host forms: z and dz share the context's z scratch, iters and m its iters scratch */
+static int pt_state_host(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, const uint32_t *from, double *z,
+                         uint32_t *iters, double *dz, uint32_t *m) {
+    bool work;
+    int rc = check_pt_state(cfg, pos_lo, y0, y1, from, z, iters, dz, m, &work);
+    if (rc != FR_OK || !work) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    const size_t zb = npx * 2 * sizeof(double), ib = npx * sizeof(uint32_t);
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = ctx->reserve(ctx->z, 2 * zb);
+    if (rc == FR_OK) rc = ctx->reserve(ctx->iters, 2 * ib);
+    if (rc != FR_OK) return rc;
+    double *d_z = static_cast<double *>(ctx->z.ptr), *d_dz = d_z + 2 * npx;
+    uint32_t *d_iters = static_cast<uint32_t *>(ctx->iters.ptr), *d_m = d_iters + npx;
+    if (from) {
+        HIP_TRY(hipMemcpyAsync(d_z, z, zb, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_dz, dz, zb, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_iters, iters, ib, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_m, m, ib, hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = pt_state_launch(*ctx, cfg, pos_lo, y0, y1, from, d_z, d_iters, d_dz, d_m, ctx->stream);
+    if (rc != FR_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(z, d_z, zb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dz, d_dz, zb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(iters, d_iters, ib, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(m, d_m, ib, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FR_OK;
+}
+
+int fr_escape_rows_pt_state_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, void *d_z,
+                                   void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
+    return pt_state_device(cfg, pos_lo, y0, y1, nullptr, d_z, d_iters, d_dz, d_m, hip_stream);
+}
+
+int fr_escape_extend_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, uint32_t from_iterations,
+                               void *d_z, void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
+    return pt_state_device(cfg, pos_lo, y0, y1, &from_iterations, d_z, d_iters, d_dz, d_m, hip_stream);
+}
+
+int fr_escape_rows_pt_state(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z, uint32_t *iters,
+                            double *dz, uint32_t *m) {
+    return pt_state_host(cfg, pos_lo, y0, y1, nullptr, z, iters, dz, m);
+}
+
+int fr_escape_extend_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, uint32_t from_iterations,
+                        double *z, uint32_t *iters, double *dz, uint32_t *m) {
+    return pt_state_host(cfg, pos_lo, y0, y1, &from_iterations, z, iters, dz, m);
 }
 
 int fr_colour_rows_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, size_t n, int channels,

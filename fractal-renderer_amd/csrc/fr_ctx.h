@@ -197,6 +197,15 @@ int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const fr_i
 int launch_pt(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, int mode, const fr_kout &out,
               hipStream_t stream, const char **kernel_name);
 
+/* FR_PRECISION_PT with its resumable state (fr_pt.hip: escape_pt_state_kernel, escape_extend_pt_kernel; include/fractal_hip.h,
+ * "resumable perturbation"): the local grid from `p` as launch_pt takes it, z and dz as re, im per pixel, m with bit 31 =
+ * on K.  The extension continues the arrays from from_iterations to p.iterations on the orbits of the new cap, which the
+ * context's cache continues from those of the old one. */
+int launch_pt_state(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, double *z, uint32_t *iters,
+                    double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name);
+int launch_pt_extend(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, uint32_t from_iterations,
+                     double *z, uint32_t *iters, double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name);
+
 /* choose_kernel for rows [y0, y1) of the image as ONE launch, recorded in `o` (tile 0 only): callers that render those
  * rows in several launches then sample the view once, not once per launch.  The calling thread must be on ctx's device. */
 void decide_kernel(Ctx &ctx, const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, Opts &o, hipStream_t stream,
@@ -205,6 +214,8 @@ void decide_kernel(Ctx &ctx, const fr_config *cfg, int precision, uint32_t y0, u
 /* the primary context (what fr_init selected); locks and lazily creates it.  Callers hold
  * `life_shared()` while they use it. */
 int primary(Ctx **out);
+/* the primary context if it exists, else nullptr: creates nothing and touches no device (test hooks) */
+Ctx *primary_if_created();
 
 /* Lifetime lock: entry points that enqueue on library state hold it shared; fr_init (device switch),
  * fr_init_devices and fr_shutdown hold it exclusively, so state is never torn down under a call. */

@@ -21,6 +21,12 @@
  *     16-byte load of an interleaved (re, im) entry is one cache line for the whole wave; afterwards it gathers, from
  *     an orbit that the L2 holds (16 B per entry);
  *   - outputs as escape_dd_kernel's: RGB / RGBA, ESCAPE (z, index), COUNT; 64-bit output offsets.
+ *
+ * Resumable PT (include/fractal_hip.h, "RESUMABLE PT"; tests/pt_state_model.c restates it): escape_pt_state_kernel<JULIA>
+ * is the ESCAPE render with the state rule — no rebase at the end of an orbit that the cap cut — and stores the whole
+ * state (z, iters, dz, m); escape_extend_pt_kernel<JULIA> continues such a state to a higher cap in place, on orbits that
+ * the host continued from their dd tails instead of recomputing them (orbit_for).  escape_pt_kernel and orbit_pt are the
+ * PT definition's and stay as they are.
  */
 #include <cmath>
 #include <cstring>
@@ -187,6 +193,190 @@ hipError_t launch(const fr_kparams &p, int mode, const fr_kout &out, const doubl
     return hipGetLastError();
 }
 
+/* ---- device: the resumable state (include/fractal_hip.h, "resumable perturbation") --------------------------------- */
+
+/* A pixel's state between steps: z, dz, the index m into the orbit it follows and whether that orbit is K (Julia after a
+ * rebase).  orbit_pt_state runs `steps` steps of the PT sequence from it with the state rule's rebase condition — dist <
+ * |dz|^2, or m == last of an orbit that is ENDED BY ESCAPE (x_end / k_end: that last index, or ~0 for an orbit cut by the
+ * cap, which m never equals) — and leaves the state after the last step in `s`; on escape the state is (z, 0, 0).  Returns
+ * the steps completed before the escape (`steps`: none).  x_last / k_last only clamp the loads. */
+struct PtState {
+    double zr, zi, dzr, dzi;
+    uint32_t m;
+    bool on_k;
+};
+
+template <bool JULIA>
+__device__ __forceinline__ uint32_t orbit_pt_state(uint32_t steps, double dcr, double dci, const double2 *x_orbit,
+                                                   const double2 *k_orbit, uint32_t x_last, uint32_t k_last, uint32_t x_end,
+                                                   uint32_t k_end, double squared, PtState &s) {
+    const bool on_k = JULIA && s.on_k;
+    const double2 *X = on_k ? k_orbit : x_orbit;
+    uint32_t last = on_k ? k_last : x_last, end = on_k ? k_end : x_end;
+    uint32_t m = s.m;
+    bool k_now = on_k;
+    double dzr = s.dzr, dzi = s.dzi, zr = s.zr, zi = s.zi;
+    double2 Z = X[min(m, last)], N = X[min(m + 1u, last)]; /* m < last at the top of every step */
+    const double2 K1 = k_orbit[1];                         /* the entry after a rebase; K_0 = R_0 = 0 */
+    uint32_t i = 0;
+    for (; i < steps; i++) {
+        const double2 P = X[min(m + 2u, last)]; /* X_{m+2}: next step's X_{m+1} if it does not rebase */
+        const double tr = Z.x + zr, ti = Z.y + zi;
+        const double ndr = __builtin_fma(tr, dzr, __builtin_fma(-ti, dzi, dcr));
+        const double ndi = __builtin_fma(tr, dzi, __builtin_fma(ti, dzr, dci));
+        m++;
+        zr = N.x + ndr;
+        zi = N.y + ndi;
+        dzr = ndr;
+        dzi = ndi;
+        const double dist = zr * zr + zi * zi;
+        if (dist > squared) break; /* this lane leaves EXEC; the wave goes on while any lane is left */
+        if (dist < dzr * dzr + dzi * dzi || m == end) {
+            dzr = zr;
+            dzi = zi;
+            m = 0;
+            if (JULIA) {
+                X = k_orbit;
+                last = k_last;
+                end = k_end;
+                k_now = true;
+            }
+            Z = make_double2(0.0, 0.0);
+            N = K1;
+        } else {
+            Z = N;
+            N = P;
+        }
+    }
+    const bool escaped = i < steps; /* (z, 0, 0) for an escaped lane */
+    s.zr = zr;
+    s.zi = zi;
+    s.dzr = escaped ? 0.0 : dzr;
+    s.dzi = escaped ? 0.0 : dzi;
+    s.m = escaped ? 0u : m;
+    s.on_k = !escaped && k_now;
+    return i;
+}
+
+constexpr uint32_t kPtOnK = 0x80000000u; /* bit 31 of the stored m: the pixel follows K */
+
+/* 16 column and 16 row offsets of the workgroup's pixels into LDS (escape_pt_kernel's staging); the caller synchronises */
+__device__ __forceinline__ void stage_offsets(const fr_kparams &p, uint32_t tid, uint32_t col0, uint32_t row0, double *s_re,
+                                              double *s_im) {
+    if (tid < kPtBlockW + kPtBlockH) {
+        const double width = (double)p.width, height = (double)p.height;
+        if (tid < kPtBlockW) {
+            const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
+            s_re[tid] = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
+        } else {
+            const uint32_t r = row0 + (tid - kPtBlockW);
+            const uint64_t y = (uint64_t)p.y_first + (uint64_t)(r / p.block_rows) * p.y_stride + r % p.block_rows;
+            s_im[tid - kPtBlockW] = (((double)y / height) - 0.5) / p.scale_im;
+        }
+    }
+}
+
+/* escape_pt_kernel<FR_OUT_ESCAPE>'s shape with the state rule, storing the whole state: z and dz as re, im per pixel, iters,
+ * m (bit 31: on K).  `ended`: bit 0 = X, bit 1 = K is ended by escape.  An algorithm without orbits writes zeros. */
+template <bool JULIA>
+__global__ __launch_bounds__(64 * kPtWaves) void escape_pt_state_kernel(const fr_kparams p, double *__restrict__ z,
+                                                                       uint32_t *__restrict__ iters, double *__restrict__ dz,
+                                                                       uint32_t *__restrict__ mm,
+                                                                       const double2 *__restrict__ x_orbit,
+                                                                       const double2 *__restrict__ k_orbit, const uint32_t x_last,
+                                                                       const uint32_t k_last, const uint32_t ended) {
+    __shared__ double s_re[kPtBlockW];
+    __shared__ double s_im[kPtBlockH];
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kPtBlockW - 1) / kPtBlockW);
+    const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+    const uint32_t col0 = bx * kPtBlockW, row0 = by * kPtBlockH;
+    stage_offsets(p, tid, col0, row0, s_re, s_im);
+    __syncthreads();
+
+    const uint32_t wave = tid >> 6, lane = tid & 63;
+    const uint32_t lx = (wave % kPtWavesX) * kPtTileW + lane % kPtTileW;
+    const uint32_t ly = (wave / kPtWavesX) * kPtTileH + lane / kPtTileW;
+    const uint32_t cx = col0 + lx, r = row0 + ly;
+    if (cx >= p.ncols || r >= p.nrows) return;
+    const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0; /* the host picks JULIA from the algorithm */
+
+    PtState s{0.0, 0.0, 0.0, 0.0, 0u, false};
+    uint32_t it = 0;
+    if (escape_algo) {
+        const double off_re = s_re[lx], off_im = s_im[ly];
+        s.m = JULIA ? 0u : 1u;
+        s.dzr = off_re;
+        s.dzi = off_im;
+        const double2 X0 = x_orbit[min(s.m, x_last)];
+        s.zr = X0.x + s.dzr;
+        s.zi = X0.y + s.dzi;
+        it = orbit_pt_state<JULIA>(p.iterations, JULIA ? 0.0 : off_re, JULIA ? 0.0 : off_im, x_orbit, k_orbit, x_last, k_last,
+                                   (ended & 1u) ? x_last : ~0u, (ended & 2u) ? k_last : ~0u, p.limit * p.limit, s);
+    }
+    const uint64_t k = (uint64_t)r * p.ncols + cx;
+    z[2 * k] = s.zr;
+    z[2 * k + 1] = s.zi;
+    iters[k] = it;
+    dz[2 * k] = s.dzr;
+    dz[2 * k + 1] = s.dzi;
+    mm[k] = s.m | (s.on_k ? kPtOnK : 0u);
+}
+
+/* Continue a stored state from cap `from` to p.iterations in place (escape_extend_dd_kernel's early-out): `iters` is read
+ * first and a workgroup with no pixel at `from` ends there, having written nothing; a finished pixel's z, dz and m are
+ * neither loaded nor stored.  The orbits are those of the new cap. */
+template <bool JULIA>
+__global__ __launch_bounds__(64 * kPtWaves) void escape_extend_pt_kernel(const fr_kparams p, double *z, uint32_t *iters, double *dz,
+                                                                        uint32_t *mm, const uint32_t from,
+                                                                        const double2 *__restrict__ x_orbit,
+                                                                        const double2 *__restrict__ k_orbit, const uint32_t x_last,
+                                                                        const uint32_t k_last, const uint32_t ended) {
+    __shared__ double s_re[kPtBlockW];
+    __shared__ double s_im[kPtBlockH];
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kPtBlockW - 1) / kPtBlockW);
+    const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+    const uint32_t col0 = bx * kPtBlockW, row0 = by * kPtBlockH;
+    const uint32_t wave = tid >> 6, lane = tid & 63;
+    const uint32_t lx = (wave % kPtWavesX) * kPtTileW + lane % kPtTileW;
+    const uint32_t ly = (wave / kPtWavesX) * kPtTileH + lane / kPtTileW;
+    const uint32_t cx = col0 + lx, r = row0 + ly;
+    const bool valid = cx < p.ncols && r < p.nrows;
+    const uint64_t k = (uint64_t)r * p.ncols + cx;
+    uint32_t done = 0;
+    if (valid) done = iters[k];
+    const bool running = valid && done == from;
+    if (!__syncthreads_or(running ? 1 : 0)) return; /* whole workgroup (uniform) */
+
+    if (!JULIA) { /* dc = the pixel's offset, staged as the render stages it; Julia's dc is 0 */
+        stage_offsets(p, tid, col0, row0, s_re, s_im);
+        __syncthreads();
+    }
+    if (running) {
+        const uint32_t word = mm[k];
+        PtState s;
+        s.zr = z[2 * k];
+        s.zi = z[2 * k + 1];
+        s.dzr = dz[2 * k];
+        s.dzi = dz[2 * k + 1];
+        s.on_k = JULIA && (word & kPtOnK) != 0;
+        /* m < last of the orbit followed in every state this view produces; the clamp keeps foreign data inside the orbit */
+        s.m = min(word & ~kPtOnK, (s.on_k ? k_last : x_last) - 1u);
+        const uint32_t it = orbit_pt_state<JULIA>(p.iterations - from, JULIA ? 0.0 : s_re[lx], JULIA ? 0.0 : s_im[ly], x_orbit, k_orbit,
+                                                  x_last, k_last, (ended & 1u) ? x_last : ~0u, (ended & 2u) ? k_last : ~0u,
+                                                  p.limit * p.limit, s);
+        z[2 * k] = s.zr;
+        z[2 * k + 1] = s.zi;
+        dz[2 * k] = s.dzr;
+        dz[2 * k + 1] = s.dzi;
+        mm[k] = s.m | (s.on_k ? kPtOnK : 0u);
+        iters[k] = from + it; /* it == M - N on exhaustion: the new cap */
+    }
+}
+
 /* ---- host: the reference orbits, DD's operations (include/fractal_hip.h) with std::fma where the definition has fma -- */
 
 struct ddh {
@@ -237,21 +427,40 @@ ddh twice_mul(ddh x, ddh y) {
 
 ddh neg(ddh x) { return {-x.hi, -x.lo}; }
 
-/* orbit `which` (0: R or V, 1: K) of the view as re, im pairs of the hi parts; at most iterations + 2 entries */
-void reference_orbit(const fr_config *cfg, double lo_re, double lo_im, int which, std::vector<double> &out) {
+/* how an orbit's last stored entry came about, and that entry in dd: what continuing the recurrence needs */
+struct OrbitEnd {
+    bool ended = false; /* ended by escape (identical at every higher cap); false: cut by the cap at k == kmax */
+    ddh re{0.0, 0.0}, im{0.0, 0.0};
+};
+
+/* Orbit `which` (0: R or V, 1: K) of the view as re, im pairs of the hi parts, appended to `out`; at most iterations + 2
+ * entries in all.  from == nullptr: the whole orbit, entry 0 first.  Otherwise entries 0 .. last of an orbit CUT BY THE CAP
+ * exist already (`last` = its kmax, *from its end) and the recurrence goes on from entry last + 1: the same operations on
+ * the same dd values, so the entries are those of the whole orbit at cfg's cap. */
+void reference_orbit(const fr_config *cfg, double lo_re, double lo_im, int which, std::vector<double> &out, OrbitEnd &end,
+                     const OrbitEnd *from = nullptr, uint32_t last = 0) {
     const bool julia = cfg->algo == 2;
     const uint32_t kmin = julia ? 1u : 2u;
     const uint32_t kmax = julia ? (cfg->iterations > 1 ? cfg->iterations : 1u) : cfg->iterations + 1u;
     const ddh cre{cfg->pos.re, lo_re}, cim{cfg->pos.im, lo_im};
     ddh zr{0.0, 0.0}, zi{0.0, 0.0};
     if (julia && which == 0) zr = cre, zi = cim;
-    out.clear();
-    out.reserve(2 * ((size_t)kmax + 1));
-    for (uint32_t k = 0;; k++) {
-        out.push_back(zr.hi);
-        out.push_back(zi.hi);
-        if (k >= kmin && zr.hi * zr.hi + zi.hi * zi.hi > 4.0) break;
-        if (k == kmax) break;
+    bool stored = false; /* entry k is in the orbit already and has passed its tests */
+    uint32_t k = 0;
+    if (from) {
+        end = *from;
+        if (from->ended || last >= kmax) return;
+        zr = from->re, zi = from->im, k = last, stored = true;
+    }
+    out.reserve(out.size() + 2 * ((size_t)(kmax - k) + 1));
+    for (;; k++) {
+        if (!stored) {
+            out.push_back(zr.hi);
+            out.push_back(zi.hi);
+            end.ended = k >= kmin && zr.hi * zr.hi + zi.hi * zi.hi > 4.0;
+            if (end.ended || k == kmax) break;
+        }
+        stored = false;
         if (!julia && k == 0) {
             zr = cre, zi = cim; /* R_1 = C */
         } else {
@@ -266,6 +475,7 @@ void reference_orbit(const fr_config *cfg, double lo_re, double lo_im, int which
             }
         }
     }
+    end.re = zr, end.im = zi;
 }
 
 }  // namespace
@@ -279,6 +489,9 @@ struct PtOrbit {
     double2 *dev = nullptr;
     uint32_t x_last = 0, k_last = 0;
     size_t k_offset = 0; /* entries */
+    OrbitEnd x_end, k_end;  /* Mandelbrot: k_end = x_end */
+    uint32_t computed = 0;  /* entries the last request for this view computed on the host (fr_debug_pt_orbit_cache) */
+    uint32_t ended() const { return (x_end.ended ? 1u : 0u) | (k_end.ended ? 2u : 0u); } /* the kernels' `ended` */
     ~PtOrbit() {
         if (dev) (void)hipFree(dev); /* hipFree waits for the device: no kernel still reads the orbit */
     }
@@ -295,35 +508,70 @@ void view_key(const fr_config *cfg, const fr_imaginary *pos_lo, double key[6]) {
     key[5] = cfg->algo == 2 ? cfg->julia_set.im : 0.0;
 }
 
-/* the view's orbits, from the context's cache or computed and uploaded; the caller keeps `out` alive until its launch
- * has been enqueued (a later view may replace the cache entry meanwhile; the last reference frees it) */
+/* The view's orbits, from the context's cache or computed and uploaded; the caller keeps `out` alive until its launch
+ * has been enqueued (a later view may replace the cache entry meanwhile; the last reference frees it).
+ * The same view at a HIGHER cap continues what the cache holds (include/fractal_hip.h, "resumable perturbation"): an orbit
+ * ended by escape is the same at every cap, so if all are, the entry is re-keyed and nothing is computed; otherwise the
+ * recurrence goes on from the stored dd tail for the missing entries only, into a NEW PtOrbit — launches in flight hold the
+ * old one — whose old entries arrive by a device-to-device copy. */
 int orbit_for(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, std::shared_ptr<PtOrbit> &out) {
     double key[6];
     view_key(cfg, pos_lo, key);
+    const bool julia = cfg->algo == 2;
     std::lock_guard<std::mutex> lk(ctx.pt_mu);
-    const std::shared_ptr<PtOrbit> &c = ctx.pt_orbit;
-    if (c && c->algo == cfg->algo && c->iterations == cfg->iterations && memcmp(c->key, key, sizeof key) == 0) {
+    const std::shared_ptr<PtOrbit> c = ctx.pt_orbit;
+    const bool same_view = c && c->algo == cfg->algo && memcmp(c->key, key, sizeof key) == 0;
+    if (same_view && c->iterations == cfg->iterations) {
+        c->computed = 0;
         out = c;
         return FR_OK;
     }
-    std::vector<double> x, k;
-    reference_orbit(cfg, key[2], key[3], 0, x);
-    if (cfg->algo == 2) reference_orbit(cfg, key[2], key[3], 1, k);
+    const bool resume = same_view && c->iterations < cfg->iterations;
+    if (resume && c->x_end.ended && c->k_end.ended) {
+        c->iterations = cfg->iterations; /* only orbit_for reads it, under pt_mu */
+        c->computed = 0;
+        out = c;
+        return FR_OK;
+    }
+    std::vector<double> x, k; /* the entries to upload: all of them, or those behind the cached ones */
     auto o = std::make_shared<PtOrbit>();
+    reference_orbit(cfg, key[2], key[3], 0, x, o->x_end, resume ? &c->x_end : nullptr, resume ? c->x_last : 0u);
+    if (julia) reference_orbit(cfg, key[2], key[3], 1, k, o->k_end, resume ? &c->k_end : nullptr, resume ? c->k_last : 0u);
+    const size_t x_old = resume ? (size_t)c->x_last + 1 : 0, k_old = resume && julia ? (size_t)c->k_last + 1 : 0;
+    const size_t x_n = x_old + x.size() / 2, k_n = k_old + k.size() / 2;
     o->algo = cfg->algo;
     o->iterations = cfg->iterations;
     memcpy(o->key, key, sizeof key);
-    o->x_last = (uint32_t)(x.size() / 2 - 1);
-    o->k_offset = x.size() / 2;
-    o->k_last = k.empty() ? o->x_last : (uint32_t)(k.size() / 2 - 1);
-    const size_t bytes = (x.size() + k.size()) * sizeof(double);
-    ctx.pt_orbit.reset(); /* the previous view's orbit goes first: its memory is free for this one */
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&o->dev), bytes));
-    HIP_TRY(hipMemcpy(o->dev, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (!k.empty()) HIP_TRY(hipMemcpy(o->dev + o->k_offset, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice));
+    o->x_last = (uint32_t)(x_n - 1);
+    o->k_offset = x_n;
+    o->k_last = julia ? (uint32_t)(k_n - 1) : o->x_last;
+    if (!julia) o->k_end = o->x_end;
+    o->computed = (uint32_t)(x.size() / 2 + k.size() / 2);
+    if (!resume) ctx.pt_orbit.reset(); /* the previous view's orbit goes first: its memory is free for this one */
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&o->dev), (x_n + k_n) * sizeof(double2)));
+    if (x_old) HIP_TRY(hipMemcpyAsync(o->dev, c->dev, x_old * sizeof(double2), hipMemcpyDeviceToDevice, nullptr));
+    if (k_old) HIP_TRY(hipMemcpyAsync(o->dev + o->k_offset, c->dev + c->k_offset, k_old * sizeof(double2), hipMemcpyDeviceToDevice, nullptr));
+    if (x_old || k_old) HIP_TRY(hipStreamSynchronize(nullptr)); /* the copies are done before a launch on any stream reads them */
+    if (!x.empty()) HIP_TRY(hipMemcpy(o->dev + x_old, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (!k.empty()) HIP_TRY(hipMemcpy(o->dev + o->k_offset + k_old, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice));
     ctx.pt_orbit = o;
     out = std::move(o);
     return FR_OK;
+}
+
+template <bool JULIA>
+hipError_t launch_state(const fr_kparams &p, uint32_t from, bool extend, double *z, uint32_t *iters, double *dz, uint32_t *m,
+                        const PtOrbit *o, hipStream_t stream) {
+    const uint64_t tiles = (((uint64_t)p.ncols + kPtBlockW - 1) / kPtBlockW) * (((uint64_t)p.nrows + kPtBlockH - 1) / kPtBlockH);
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)tiles), block(64 * kPtWaves);
+    const double2 *x = o ? o->dev : nullptr, *k = o ? (JULIA ? o->dev + o->k_offset : o->dev) : nullptr;
+    const uint32_t x_last = o ? o->x_last : 0u, k_last = o ? o->k_last : 0u, ended = o ? o->ended() : 0u;
+    if (extend)
+        escape_extend_pt_kernel<JULIA><<<grid, block, 0, stream>>>(p, z, iters, dz, m, from, x, k, x_last, k_last, ended);
+    else
+        escape_pt_state_kernel<JULIA><<<grid, block, 0, stream>>>(p, z, iters, dz, m, x, k, x_last, k_last, ended);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -348,7 +596,54 @@ int launch_pt(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const 
     return FR_OK;
 }
 
+int launch_pt_state(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, double *z, uint32_t *iters,
+                    double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = "escape_pt_state_kernel";
+    if (p.ncols == 0 || p.nrows == 0) return FR_OK;
+    const bool julia = cfg->algo == 2;
+    if (cfg->algo != 0 && !julia) { /* no escape-time algorithm: zeros in all four arrays */
+        HIP_TRY(launch_state<false>(p, 0, false, z, iters, dz, m, nullptr, stream));
+        return FR_OK;
+    }
+    std::shared_ptr<PtOrbit> o;
+    const int rc = orbit_for(ctx, cfg, pos_lo, o);
+    if (rc != FR_OK) return rc;
+    HIP_TRY(julia ? launch_state<true>(p, 0, false, z, iters, dz, m, o.get(), stream)
+                  : launch_state<false>(p, 0, false, z, iters, dz, m, o.get(), stream));
+    return FR_OK;
+}
+
+int launch_pt_extend(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, uint32_t from_iterations,
+                     double *z, uint32_t *iters, double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = "escape_extend_pt_kernel";
+    const bool julia = cfg->algo == 2;
+    if (p.ncols == 0 || p.nrows == 0 || p.iterations <= from_iterations || (cfg->algo != 0 && !julia)) return FR_OK;
+    std::shared_ptr<PtOrbit> o;
+    const int rc = orbit_for(ctx, cfg, pos_lo, o);
+    if (rc != FR_OK) return rc;
+    HIP_TRY(julia ? launch_state<true>(p, from_iterations, true, z, iters, dz, m, o.get(), stream)
+                  : launch_state<false>(p, from_iterations, true, z, iters, dz, m, o.get(), stream));
+    return FR_OK;
+}
+
 }  // namespace fr
+
+int fr_debug_pt_orbit_cache(uint32_t out[4]) {
+    using namespace fr;
+    if (!out) return fail(FR_ERR_INVALID_ARGUMENT, "out is NULL");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    LifeShared ls;
+    Ctx *ctx = primary_if_created();
+    if (!ctx) return FR_OK;
+    std::lock_guard<std::mutex> lk(ctx->pt_mu);
+    const PtOrbit *o = ctx->pt_orbit.get();
+    if (!o) return FR_OK;
+    out[0] = o->iterations;
+    out[1] = o->x_last + 1;
+    out[2] = o->algo == 2 ? o->k_last + 1 : 0;
+    out[3] = o->computed;
+    return FR_OK;
+}
 
 int fr_debug_reference_orbit(const fr_config *cfg, const fr_imaginary *pos_lo, int which, double *out, size_t cap,
                              uint32_t *len) {
@@ -361,7 +656,8 @@ int fr_debug_reference_orbit(const fr_config *cfg, const fr_imaginary *pos_lo, i
     if (!len) return fail(FR_ERR_INVALID_ARGUMENT, "len is NULL");
     if (cap && !out) return fail(FR_ERR_INVALID_ARGUMENT, "out is NULL");
     std::vector<double> v;
-    reference_orbit(cfg, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, which, v);
+    OrbitEnd end;
+    reference_orbit(cfg, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, which, v, end);
     *len = (uint32_t)(v.size() / 2);
     const size_t n = std::min(cap, v.size() / 2);
     if (n) memcpy(out, v.data(), n * 2 * sizeof(double));

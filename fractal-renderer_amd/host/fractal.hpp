@@ -157,5 +157,19 @@ inline void colour_rows_device(const Config &config, const void *d_z, const void
     check(fr_colour_rows_device(&config, d_z, z_width, d_iters, n, channels, d_out, static_cast<size_t>(channels) * n, hip_stream));
 }
 
+
+// ---- resumable perturbation (include/fractal_hip.h, "resumable perturbation"): thin wrappers ----------------------
+// A deep view kept on the device in FR_PRECISION_PT is (z, iters, dz, m), 40 bytes per pixel: pt_state_rows_device once per
+// view, extend_pt_rows_device on an iterations change (config.iterations is the new cap; the arrays hold the same view at
+// from_iterations, which the library cannot check), colour_rows_device over (d_z, d_iters) with z_width 2.
+inline void pt_state_rows_device(const Config &config, void *d_z, void *d_iters, void *d_dz, void *d_m, void *hip_stream = nullptr,
+                                 const fr_imaginary *pos_lo = nullptr) {
+    check(fr_escape_rows_pt_state_device(&config, pos_lo, 0, config.height, d_z, d_iters, d_dz, d_m, hip_stream));
+}
+inline void extend_pt_rows_device(const Config &config, uint32_t from_iterations, void *d_z, void *d_iters, void *d_dz, void *d_m,
+                                  void *hip_stream = nullptr, const fr_imaginary *pos_lo = nullptr) {
+    check(fr_escape_extend_pt_device(&config, pos_lo, 0, config.height, from_iterations, d_z, d_iters, d_dz, d_m, hip_stream));
+}
+
 }  // namespace fractal
 #endif

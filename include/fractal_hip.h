@@ -152,7 +152,24 @@ typedef struct fr_config {
  * 16 B per entry in host and device memory, so the cap bounds one orbit to 256 MiB (512 MiB for a Julia view's two).
  * PT runs on one device exactly where DD does (pos_lo = 0 through fr_render_rows_rgb8 & co), plus the fr_*_pt calls
  * below; block-cyclic, multi-device and fr_recursive_batch refuse it.  The library keeps the last view's orbit per
- * context, so frames of one view, row pieces and fr_pixel_p do not recompute it. */
+ * context, so frames of one view, row pieces and fr_pixel_p do not recompute it.
+ *
+ * RESUMABLE PT (fr_escape_rows_pt_state, fr_escape_extend_pt below): the state that lets a PT view's cap be raised in place.
+ *   An orbit X (R, V or K) is ENDED BY ESCAPE if its last stored entry stopped it by the escape test (last >= kmin and
+ *   re*re + im*im > 4 on the stored hi parts); otherwise it is CUT BY THE CAP, at k == kmax.  An orbit ended by escape is
+ *   identical at every cap >= its length; an orbit cut at cap N is a proper prefix of the orbit at any cap M > N.
+ *   The resumable state of a pixel after N steps is (z, dz, m, onK), produced by the step sequence above with ONE change,
+ *   to the rebase condition: rebase when dist < |dz|^2, or when m == last of X AND X is ended by escape.
+ *   Stored form: z (2 doubles, as fr_escape_rows_pt gives it), iters, dz (2 doubles), m as uint32 whose bit 31 is set when
+ *   a Julia pixel follows K (never for Mandelbrot).  An escaped pixel stores dz = (0, 0), m = 0.  N = 0 stores the initial
+ *   state (Mandelbrot: m = 1, dz = off; Julia: m = 0, dz = off; z = X_m + dz).
+ *   CLAIM: for every N, z and iters of the state run equal PT's at cap N bit for bit, and continuing the state from N for
+ *   M - N steps on the orbits of cap M gives the state run at cap M, bit for bit in all four arrays.
+ *   Why: after step i, m <= i + 2 (Mandelbrot) or i + 1 (Julia on V), and on K after a rebase m <= N - 1; an orbit cut by
+ *   the cap has last = N + 1 (R) or N (V, K).  So on a cut orbit m == last can only be met at the final step i = N - 1, by
+ *   a pixel that never rebased.  There PT's rebase changes (dz, m) and leaves z alone: it is invisible in PT's output, and
+ *   it is the only event of the sequence that depends on the cap.  The state rule leaves it out, so a state run to N is
+ *   a prefix of the state run to M; an orbit ended by escape and the dist test do not depend on the cap at all. */
 #define FR_PT_MAX_ITERATIONS (1u << 24)
 typedef enum fr_precision {
     FR_PRECISION_F64 = 0,
@@ -486,7 +503,8 @@ int fr_escape_rows_device(const fr_config *cfg, int precision, const fr_imaginar
  * stored doubles are widened f32 values, and narrowing them back is exact); FR_PRECISION_DD takes z_width 4 only — the low
  * parts are state — with DD's domain on cfg and pos_lo.  FR_PRECISION_PT is refused: its per-pixel state is (X, m, dz), not
  * z, and the step at which a pixel meets "m == last of X" depends on the cap (the orbit's length does), so a stored z does
- * not determine the continuation.  Both d_z and d_iters are required (y0 == y1 needs neither).  pos_lo non-NULL only for
+ * not determine the continuation (fr_escape_rows_pt_state_device / fr_escape_extend_pt_device below keep and continue
+ * that state).  Both d_z and d_iters are required (y0 == y1 needs neither).  pos_lo non-NULL only for
  * DD.  opts: NULL = defaults; loop_mode 5 = no speculative blocks (same bytes).
  * With profiling on, fr_last_kernel_name reports escape_extend_kernel<double> / <float> / escape_extend_dd_kernel. */
 int fr_escape_extend_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
@@ -500,6 +518,45 @@ int fr_escape_extend(const fr_config *cfg, int precision, const fr_imaginary *po
  * z_width 2 or 4 (colour on the hi parts, as the DD definition says).  out_len >= channels * n. */
 int fr_colour_rows_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, size_t n, int channels,
                           void *d_out, size_t out_len, void *hip_stream);
+
+/* ---- resumable perturbation: a deep view's cap raised in place ----------------------------------------- */
+
+/* A GUI keeps a PT view as (z, iters, dz, m) in DEVICE memory — 40 bytes per pixel — and answers an iterations change with
+ * fr_escape_extend_pt_device; fr_colour_rows_device over (z, iters) with z_width 2 colours it.  The definition of the state
+ * and why continuing it is the render at the higher cap: fr_precision above, "RESUMABLE PT".  The library keeps the view's
+ * reference orbits per context and CONTINUES them for a higher cap of the same view: orbits that are all ended by escape
+ * are served as they are; otherwise only the missing entries are computed on the host, from the stored dd tail. */
+
+/* Rows [y0, y1) in FR_PRECISION_PT with their resumable state into DEVICE arrays, asynchronously on `hip_stream`:
+ * d_z, d_dz 2 doubles per pixel (re, im), 8-byte aligned; d_iters, d_m one uint32 per pixel, 4-byte aligned; all four
+ * required (y0 == y1 needs none and no device); k = (y-y0)*width + x.  d_z and d_iters receive what fr_escape_rows_pt gives,
+ * bit for bit.  Domain: FR_PRECISION_PT's on cfg and pos_lo.  An algorithm without orbits (BarnsleyFern) writes zeros.
+ * With profiling on, fr_last_kernel_name reports escape_pt_state_kernel. */
+int fr_escape_rows_pt_state_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, void *d_z,
+                                   void *d_iters, void *d_dz, void *d_m, void *hip_stream);
+/* Raise the cap of a stored state IN PLACE, N = from_iterations -> M = cfg->iterations, cfg_N = cfg with iterations = N:
+ *   Precondition: the arrays hold what fr_escape_rows_pt_state_device(cfg_N, pos_lo, y0, y1, ...) writes.
+ *   Result: after the call they hold what the same call writes for cfg, bit for bit in all four arrays.
+ *   A pixel with iters[k] != N is finished: only that word is read; its z, dz and m are neither loaded nor written.  Values
+ *   of iters[k] above N are foreign data and are left alone like finished pixels.
+ * The library CANNOT check the precondition: arrays from another view or cap are continued as if they were this one's (an
+ * index m beyond the orbit is brought inside it, nothing more).  Nor is the call idempotent: in arrays that already hold
+ * cap M, iters[k] == N means "escaped at step N", and a second call N -> M would continue those pixels.
+ * Domain (else FR_ERR_INVALID_ARGUMENT, before any device work): M >= N — M == N is a legal no-op that needs no device;
+ * FR_PRECISION_PT's domain on cfg (with iterations <= FR_PT_MAX_ITERATIONS) and pos_lo; all four arrays, aligned as above
+ * (y0 == y1 needs none).  An algorithm without orbits: nothing is done.
+ * With profiling on, fr_last_kernel_name reports escape_extend_pt_kernel. */
+int fr_escape_extend_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
+                               uint32_t from_iterations, void *d_z, void *d_iters, void *d_dz, void *d_m, void *hip_stream);
+/* the same over HOST arrays (context scratch; upload, launch, download, synchronise, as fr_escape_extend does) */
+int fr_escape_rows_pt_state(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z,
+                            uint32_t *iters, double *dz, uint32_t *m);
+int fr_escape_extend_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, uint32_t from_iterations,
+                        double *z, uint32_t *iters, double *dz, uint32_t *m);
+/* Test hook: out[0] = the iterations the context's cached PT orbit is for, out[1] / out[2] = entries of X / K (K: Julia
+ * only), out[3] = entries the last request for it computed on the host (0 = served as it was).  Zeros without a cached
+ * orbit.  Touches no device. */
+int fr_debug_pt_orbit_cache(uint32_t out[4]);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 

@@ -124,6 +124,11 @@ extern "C" {
     pub fn fr_escape_extend_device(cfg: *const fr_config, precision: c_int, pos_lo: *const fr_imaginary, y0: u32, y1: u32, from_iterations: u32, z_width: c_int, d_z: *mut c_void, d_iters: *mut c_void, hip_stream: *mut c_void, opts: *const fr_render_opts) -> c_int;
     pub fn fr_escape_extend(cfg: *const fr_config, precision: c_int, pos_lo: *const fr_imaginary, y0: u32, y1: u32, from_iterations: u32, z_width: c_int, z: *mut f64, iters: *mut u32) -> c_int;
     pub fn fr_colour_rows_device(cfg: *const fr_config, d_z: *const c_void, z_width: c_int, d_iters: *const c_void, n: usize, channels: c_int, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    // resumable perturbation (include/fractal_hip.h): a PT view's state (z, iters, dz, m) and its cap raised in place
+    pub fn fr_escape_rows_pt_state_device(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, d_z: *mut c_void, d_iters: *mut c_void, d_dz: *mut c_void, d_m: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_escape_extend_pt_device(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, from_iterations: u32, d_z: *mut c_void, d_iters: *mut c_void, d_dz: *mut c_void, d_m: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_escape_rows_pt_state(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, z: *mut f64, iters: *mut u32, dz: *mut f64, m: *mut u32) -> c_int;
+    pub fn fr_escape_extend_pt(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, from_iterations: u32, z: *mut f64, iters: *mut u32, dz: *mut f64, m: *mut u32) -> c_int;
 }
 
 /// Message of the last failing call on this thread.
