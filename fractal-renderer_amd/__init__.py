@@ -32,6 +32,7 @@ __all__ = [
     "box_filter", "ss_workspace_bytes", "SS_MAX",
     "escape_rows_device", "extend_rows_device", "extend_rows", "colour_rows_device",
     "escape_rows_pt_state", "extend_rows_pt", "escape_rows_pt_state_device", "extend_rows_pt_device", "pt_orbit_cache",
+    "WideCentre", "reference_orbit_wide",
 ]
 
 
@@ -86,6 +87,86 @@ def _pos_lo(pos_lo):
         return None, None
     lo = Imaginary(*(float(v) for v in pos_lo))
     return C.byref(lo), lo
+
+
+class WideCentre:
+    """The view centre of WIDE PT (include/fractal_hip.h, "WIDE PT"): per axis `words` little-endian uint64 words in two's
+    complement, value I / 2^(64 words - 8) — up to 1016 bits where (pos, pos_lo) carries ~106.  Pass it as centre= to
+    get_image, get_image_rows, get_image_rgba, escape_rows and the PT state calls with precision=Precision.PT."""
+
+    def __init__(self, words, re=None, im=None):
+        self.words = int(words)
+        if not 2 <= self.words <= _native.FR_WIDE_MAX_WORDS:
+            raise ValueError("a wide centre has 2 .. %d words" % _native.FR_WIDE_MAX_WORDS)
+        self.re = np.zeros(self.words, dtype=np.uint64) if re is None else np.array(re, dtype=np.uint64)
+        self.im = np.zeros(self.words, dtype=np.uint64) if im is None else np.array(im, dtype=np.uint64)
+        if self.re.shape != (self.words,) or self.im.shape != (self.words,):
+            raise ValueError("re and im hold `words` uint64 words each")
+
+    @staticmethod
+    def words_for_scale(scale):
+        """the smallest word count of the domain rule F >= e + 64, where max |scale| = f 2^e with 0.5 <= f < 1"""
+        import math
+
+        e = math.frexp(max(abs(float(v)) for v in (scale if hasattr(scale, "__iter__") else (scale,))))[1]
+        return max(2, -(-(e + 72) // 64))
+
+    @classmethod
+    def from_str(cls, re_text, im_text, scale=None, words=None):
+        """Decimal strings of any length ("-0.2281554936539618...", "1e-3") through fr_wide_from_decimal: each component is
+        the floor of the string's exact value.  words: the word count, or None to size it from `scale` (a number or the
+        config's scale pair) by the domain rule."""
+        if words is None:
+            if scale is None:
+                raise ValueError("from_str needs words= or scale=")
+            words = cls.words_for_scale(scale)
+        c = cls(words)
+        for text, w in ((re_text, c.re), (im_text, c.im)):
+            _native.check(_native.load().fr_wide_from_decimal(str(text).strip().encode(), w.ctypes.data, c.words))
+        return c
+
+    def add(self, dre, dim):
+        """pan: I += floor(d 2^F) per axis (fr_wide_add_double) — a pan step or a clicked pixel's off; returns self"""
+        _native.check(_native.load().fr_wide_add_double(self.re.ctypes.data, self.words, float(dre)))
+        _native.check(_native.load().fr_wide_add_double(self.im.ctypes.data, self.words, float(dim)))
+        return self
+
+    def to_dd(self):
+        """((re_hi, im_hi), (re_lo, im_lo)) through fr_wide_to_double: a normalised pos / pos_lo pair, which hands the view
+        over to Precision.PT or Precision.DD at shallow scales"""
+        out = []
+        for w in (self.re, self.im):
+            hi, lo = C.c_double(0.0), C.c_double(0.0)
+            _native.check(_native.load().fr_wide_to_double(w.ctypes.data, self.words, C.byref(hi), C.byref(lo)))
+            out.append((hi.value, lo.value))
+        return (out[0][0], out[1][0]), (out[0][1], out[1][1])
+
+    def c_struct(self):
+        """the fr_wide_centre of the C calls; it points into this object's arrays, which must outlive the call"""
+        p64 = C.POINTER(C.c_uint64)
+        return _native.fr_wide_centre(self.words, self.re.ctypes.data_as(p64), self.im.ctypes.data_as(p64))
+
+
+def _wide(centre, precision, pos_lo=None, supersample=1):
+    """centre= argument -> (pointer for the C call, keep-alive)"""
+    if int(precision) != Precision.PT:
+        raise ValueError("centre= needs precision=Precision.PT")
+    if pos_lo is not None:
+        raise ValueError("centre= and pos_lo= exclude each other")
+    if supersample != 1:
+        raise ValueError("supersample does not take centre= yet")
+    st = centre.c_struct()
+    return C.byref(st), (st, centre)
+
+
+def reference_orbit_wide(config, centre, which=0):
+    """fr_debug_reference_orbit_wide: WIDE PT's reference orbit on the host (no device needed), float64 [entries, 2]"""
+    st = centre.c_struct()
+    n = C.c_uint32(0)
+    out = np.empty((int(config.iterations) + 2, 2), dtype=np.float64)
+    _native.check(_native.load().fr_debug_reference_orbit_wide(C.byref(config), C.byref(st), int(which), out.ctypes.data, len(out),
+                                                               C.byref(n)))
+    return out[:n.value].copy()
 
 
 class Config(_native.fr_config):
@@ -203,14 +284,20 @@ def box_filter(image, s, channels=3):
     return out
 
 
-def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None, pos_lo=None, supersample=1):
+def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None, pos_lo=None, supersample=1, centre=None):
     """Rows [y0, y1) of get_image — the unit of the reference's rayon loop (src/lib.rs:256-264).
     Returns uint8 [y1-y0, width, 3].  pos_lo (Precision.DD or Precision.PT only): the low halves (re, im) of the view
     centre (split_dd), so that the centre is pos + pos_lo; None = (0, 0).
     supersample = s > 1: s x s samples per pixel, box-filtered on the device (include/fractal_hip.h, "supersampled
-    rendering"); only the [y1-y0, width] result leaves the device."""
+    rendering"); only the [y1-y0, width] result leaves the device.
+    centre (Precision.PT only, exclusive with pos_lo): a WideCentre in place of (config.pos, pos_lo) for views past a scale
+    of 10^30 (include/fractal_hip.h, "WIDE PT"); supersample does not take it yet."""
     if out is None:
         out = np.empty((max(int(y1) - int(y0), 0), config.width, 3), dtype=np.uint8)
+    if centre is not None:
+        ptr, _keep = _wide(centre, precision, pos_lo, supersample)
+        _native.check(_native.load().fr_render_rows_pt_wide(C.byref(config), ptr, y0, y1, 3, out.ctypes.data, out.nbytes))
+        return out
     if supersample != 1:
         return _render_rows_ss(config, y0, y1, precision, out, 3, opts, pos_lo, supersample)
     if pos_lo is not None:
@@ -225,12 +312,14 @@ def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None,
     return out
 
 
-def get_image(config, precision=Precision.F64, pos_lo=None, supersample=1):
+def get_image(config, precision=Precision.F64, pos_lo=None, supersample=1, centre=None):
     """get_image(&Config) -> Vec<RGB> (src/lib.rs:253-270): uint8 [height, width, 3], row-major,
     bytes r,g,b.  Algo.BarnsleyFern is outside this path (random IFS, src/lib.rs:271-319): the
     per-pixel function returns BLACK for it (calc/src/lib.rs:211) and so does this.
-    pos_lo: see get_image_rows (Precision.DD or Precision.PT only).  supersample: see get_image_rows."""
+    pos_lo: see get_image_rows (Precision.DD or Precision.PT only).  supersample, centre: see get_image_rows."""
     out = np.empty((config.height, config.width, 3), dtype=np.uint8)
+    if centre is not None:
+        return get_image_rows(config, 0, config.height, precision, out, pos_lo=pos_lo, supersample=supersample, centre=centre)
     if supersample != 1:
         return _render_rows_ss(config, 0, config.height, precision, out, 3, None, pos_lo, supersample)
     if int(precision) == Precision.F64 and pos_lo is None:
@@ -262,12 +351,16 @@ def get_image_fern(config, threads=1, seed=0, walkers=0):
     return out
 
 
-def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None, supersample=1):
+def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None, supersample=1, centre=None):
     """get_image as RGBA8 (alpha 255): uint8 [height, width, 4] — the GUI's upload format
     (src/gui.rs:71-72) produced on the device.  pos_lo: see get_image_rows (Precision.DD or Precision.PT only).
-    supersample: see get_image_rows."""
+    supersample, centre: see get_image_rows."""
     if out is None:
         out = np.empty((config.height, config.width, 4), dtype=np.uint8)
+    if centre is not None:
+        ptr, _keep = _wide(centre, precision, pos_lo, supersample)
+        _native.check(_native.load().fr_render_rows_pt_wide(C.byref(config), ptr, 0, config.height, 4, out.ctypes.data, out.nbytes))
+        return out
     if supersample != 1:
         return _render_rows_ss(config, 0, config.height, precision, out, 4, None, pos_lo, supersample)
     if pos_lo is not None:
@@ -314,11 +407,20 @@ def recursive_batch(iterations, start, c, limit, precision=Precision.F64):
     return pos, it
 
 
-def escape_rows(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, with_lo=False):
+def escape_rows(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, with_lo=False, centre=None):
     """recursive() results of every pixel of rows [y0, y1): (z float64 [rows, width, 2],
     iters uint32 [rows, width]).  Precision.DD: z holds the hi parts; with_lo=True returns z as [rows, width, 4] =
-    re.hi, re.lo, im.hi, im.lo (Precision.DD only).  pos_lo: see get_image_rows (Precision.DD or Precision.PT only)."""
+    re.hi, re.lo, im.hi, im.lo (Precision.DD only).  pos_lo: see get_image_rows (Precision.DD or Precision.PT only).
+    centre: a WideCentre (Precision.PT only, exclusive with pos_lo): fr_escape_rows_pt_wide."""
     y1 = config.height if y1 is None else y1
+    if centre is not None:
+        if with_lo:
+            raise ValueError("with_lo needs precision=Precision.DD")
+        ptr, _keep = _wide(centre, precision, pos_lo)
+        z = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
+        it = np.empty((y1 - y0, config.width), dtype=np.uint32)
+        _native.check(_native.load().fr_escape_rows_pt_wide(C.byref(config), ptr, y0, y1, z.ctypes.data, it.ctypes.data))
+        return z, it
     if pos_lo is not None and not with_lo and int(precision) == Precision.PT:
         lo, _keep = _pos_lo(pos_lo)
         z = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
@@ -391,7 +493,7 @@ def extend_rows(config, z, iters, from_iterations, precision=Precision.F64, pos_
     return z, iters
 
 
-def escape_rows_pt_state(config, pos_lo=None, y0=0, y1=None):
+def escape_rows_pt_state(config, pos_lo=None, y0=0, y1=None, centre=None):
     """fr_escape_rows_pt_state: rows [y0, y1) in Precision.PT with their resumable state: (z float64 [rows, width, 2], iters
     uint32 [rows, width], dz float64 [rows, width, 2], m uint32 [rows, width]; bit 31 of m: a Julia pixel on K).  z and iters
     are escape_rows' for Precision.PT, bit for bit (include/fractal_hip.h, "RESUMABLE PT")."""
@@ -399,13 +501,18 @@ def escape_rows_pt_state(config, pos_lo=None, y0=0, y1=None):
     shape = (max(y1 - y0, 0), config.width)
     z, dz = np.empty(shape + (2,), dtype=np.float64), np.empty(shape + (2,), dtype=np.float64)
     it, m = np.empty(shape, dtype=np.uint32), np.empty(shape, dtype=np.uint32)
+    if centre is not None:
+        ptr, _keep = _wide(centre, Precision.PT, pos_lo)
+        _native.check(_native.load().fr_escape_rows_pt_wide_state(C.byref(config), ptr, y0, y1, z.ctypes.data, it.ctypes.data,
+                                                                  dz.ctypes.data, m.ctypes.data))
+        return z, it, dz, m
     lo, _keep = _pos_lo(pos_lo)
     _native.check(_native.load().fr_escape_rows_pt_state(C.byref(config), lo, y0, y1, z.ctypes.data, it.ctypes.data,
                                                          dz.ctypes.data, m.ctypes.data))
     return z, it, dz, m
 
 
-def extend_rows_pt(config, z, iters, dz, m, from_iterations, pos_lo=None, y0=0, y1=None):
+def extend_rows_pt(config, z, iters, dz, m, from_iterations, pos_lo=None, y0=0, y1=None, centre=None):
     """fr_escape_extend_pt over numpy arrays: the state escape_rows_pt_state returned at the cap `from_iterations` -> the
     state at config.iterations (copies; the arguments are left alone).  The arrays must be that view's; the library cannot
     check it."""
@@ -415,25 +522,43 @@ def extend_rows_pt(config, z, iters, dz, m, from_iterations, pos_lo=None, y0=0, 
     iters, m = np.array(iters, dtype=np.uint32, order="C"), np.array(m, dtype=np.uint32, order="C")
     if z.shape != shape + (2,) or dz.shape != shape + (2,) or iters.shape != shape or m.shape != shape:
         raise ValueError("z and dz must be [rows, width, 2], iters and m [rows, width] for rows [y0, y1)")
+    if centre is not None:
+        ptr, _keep = _wide(centre, Precision.PT, pos_lo)
+        _native.check(_native.load().fr_escape_extend_pt_wide(C.byref(config), ptr, y0, y1, int(from_iterations), z.ctypes.data,
+                                                              iters.ctypes.data, dz.ctypes.data, m.ctypes.data))
+        return z, iters, dz, m
     lo, _keep = _pos_lo(pos_lo)
     _native.check(_native.load().fr_escape_extend_pt(C.byref(config), lo, y0, y1, int(from_iterations), z.ctypes.data,
                                                      iters.ctypes.data, dz.ctypes.data, m.ctypes.data))
     return z, iters, dz, m
 
 
-def escape_rows_pt_state_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, y0=0, y1=None, pos_lo=None, stream=None):
+def escape_rows_pt_state_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, y0=0, y1=None, pos_lo=None, stream=None, centre=None):
     """fr_escape_rows_pt_state_device: the Precision.PT state of rows [y0, y1) into DEVICE arrays (raw pointers as ints:
     z, dz 2 float64 per pixel, iters, m one uint32), asynchronously on `stream`: 40 bytes per pixel."""
     y0, y1 = _rows(config, y0, y1)
+    if centre is not None:
+        ptr, _keep = _wide(centre, Precision.PT, pos_lo)
+        _native.check(_native.load().fr_escape_rows_pt_wide_state_device(C.byref(config), ptr, y0, y1, z_ptr or None,
+                                                                         iters_ptr or None, dz_ptr or None, m_ptr or None,
+                                                                         _stream(stream)))
+        return
     lo, _keep = _pos_lo(pos_lo)
     _native.check(_native.load().fr_escape_rows_pt_state_device(C.byref(config), lo, y0, y1, z_ptr or None, iters_ptr or None,
                                                                 dz_ptr or None, m_ptr or None, _stream(stream)))
 
 
-def extend_rows_pt_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, from_iterations, y0=0, y1=None, pos_lo=None, stream=None):
+def extend_rows_pt_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, from_iterations, y0=0, y1=None, pos_lo=None, stream=None,
+                          centre=None):
     """fr_escape_extend_pt_device: raise the cap of the stored Precision.PT state of rows [y0, y1) from `from_iterations` to
     config.iterations IN PLACE, asynchronously on `stream`; the view's reference orbit is continued, not recomputed."""
     y0, y1 = _rows(config, y0, y1)
+    if centre is not None:
+        ptr, _keep = _wide(centre, Precision.PT, pos_lo)
+        _native.check(_native.load().fr_escape_extend_pt_wide_device(C.byref(config), ptr, y0, y1, int(from_iterations),
+                                                                     z_ptr or None, iters_ptr or None, dz_ptr or None,
+                                                                     m_ptr or None, _stream(stream)))
+        return
     lo, _keep = _pos_lo(pos_lo)
     _native.check(_native.load().fr_escape_extend_pt_device(C.byref(config), lo, y0, y1, int(from_iterations), z_ptr or None,
                                                             iters_ptr or None, dz_ptr or None, m_ptr or None, _stream(stream)))

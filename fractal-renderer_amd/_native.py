@@ -108,7 +108,15 @@ class fr_multi_stats(C.Structure):
     ]
 
 
+class fr_wide_centre(C.Structure):
+    """include/fractal_hip.h fr_wide_centre: the view centre of WIDE PT, n_words little-endian uint64 words per axis."""
+
+    _fields_ = [("n_words", C.c_uint32), ("re", C.POINTER(C.c_uint64)), ("im", C.POINTER(C.c_uint64))]
+
+
+FR_WIDE_MAX_WORDS = 16
 _OPTS = C.POINTER(fr_render_opts)
+_WIDE = C.POINTER(fr_wide_centre)
 
 # name -> (restype, argtypes); every symbol include/fractal_hip.h declares
 PROTOTYPES = {
@@ -265,6 +273,32 @@ PROTOTYPES = {
          C.c_void_p],
     ),
     "fr_debug_pt_orbit_cache": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "fr_wide_from_double": (C.c_int, [C.c_double, C.c_void_p, C.c_uint32]),
+    "fr_wide_add_double": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double]),
+    "fr_wide_to_double": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "fr_wide_from_decimal": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32]),
+    "fr_render_rows_pt_wide": (
+        C.c_int, [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
+    "fr_render_rows_pt_wide_device": (
+        C.c_int, [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fr_escape_rows_pt_wide": (C.c_int, [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "fr_escape_rows_pt_wide_state_device": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "fr_escape_extend_pt_wide_device": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p],
+    ),
+    "fr_escape_rows_pt_wide_state": (
+        C.c_int, [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fr_escape_extend_pt_wide": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "fr_debug_reference_orbit_wide": (
+        C.c_int, [C.POINTER(fr_config), _WIDE, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "fr_colour_rows_device": (
         C.c_int,
         [C.POINTER(fr_config), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],

@@ -8,6 +8,8 @@
 //   ./fractal_cli 3000 3000 -i 1024 -s 1000000 -x -0.7436447860 -y 0.1318252536 -o zoom
 //
 // Extensions (no counterpart upstream): --f32; --devices 0,1,... (spread the image over several GPUs);
+// --perturbation (deep zooms: FR_PRECISION_PT on a wide centre; -x / -y are then read as decimal strings of any length, at
+// the word count the scale asks for, and scales up to 2^440 render — include/fractal_hip.h, "WIDE PT");
 // for -a fern: --threads N (the rayon thread count being stood in for; default: this machine's hardware
 // threads, what rayon would use) and --seed N (default: from the OS, as the reference seeds from entropy).
 // Not handled here (by design): --gui, --open.
@@ -67,7 +69,7 @@ int main(int argc, char **argv) {
                 exposure = "5", filename = "output", algo_s = "mandelbrot", color_weight = "0.01";
     std::optional<std::string> iterations, pos_x, scale_x, scale_y, primary, secondary, julia_re, julia_im, devices, threads_s,
         seed_s, supersample_s;
-    bool disable_inside = false, unsmooth = false, f32 = false, quiet = false;
+    bool disable_inside = false, unsmooth = false, f32 = false, quiet = false, perturbation = false;
     std::vector<std::string> positionals;
 
     auto value = [&](int &i, const char *flag) -> std::string {
@@ -95,6 +97,7 @@ int main(int argc, char **argv) {
         else if (a == "--julia-imaginary") julia_im = value(i, "--julia-imaginary");
         else if (a == "-w" || a == "--color-weight") color_weight = value(i, "-w");
         else if (a == "--f32") f32 = true;       // this build's extension (no counterpart upstream)
+        else if (a == "--perturbation") perturbation = true; // this build's extension: deep zooms on a wide centre
         else if (a == "--supersample") supersample_s = value(i, "--supersample"); // N x N samples per pixel, box-filtered on the device
         else if (a == "--devices") devices = value(i, "--devices");
         else if (a == "--threads") threads_s = value(i, "--threads");
@@ -118,6 +121,8 @@ int main(int argc, char **argv) {
     else die("invalid algorithm name");
     if (algo == Algo::Julia && (!julia_re || !julia_im)) die("--julia-real and --julia-imaginary are required with -a julia");
     if ((scale_x || scale_y) && scale != "0.4") die("--scale conflicts with --scale-x/--scale-y");
+    if (perturbation && (f32 || supersample_s || devices || algo == Algo::BarnsleyFern))
+        die("--perturbation does not combine with --f32, --supersample, --devices or -a fern");
 
     // src/lib.rs:207-226
     Config cfg = Config::make(algo);
@@ -126,7 +131,8 @@ int main(int argc, char **argv) {
     if (iterations) cfg.iterations = to_u32(*iterations, "iterations");
     cfg.limit = to_f64(limit, "limit");
     cfg.stable_limit = to_f64(stable_limit, "stable-limit");
-    cfg.pos.re = to_f64(pos_x ? *pos_x : (algo == Algo::Julia ? "0" : "-0.6"), "-x"); /* src/lib.rs:66-72: 0 only for julia, so -0.6 for the fern too */
+    const std::string pos_x_s = pos_x ? *pos_x : (algo == Algo::Julia ? "0" : "-0.6"); /* src/lib.rs:66-72: 0 only for julia, so -0.6 for the fern too */
+    cfg.pos.re = to_f64(pos_x_s, "-x");
     cfg.pos.im = to_f64(pos_y, "-y");
     cfg.scale.re = to_f64(scale_x ? *scale_x : scale, "scale");
     cfg.scale.im = to_f64(scale_y ? *scale_y : scale, "scale");
@@ -175,6 +181,10 @@ int main(int argc, char **argv) {
                 seed = (static_cast<uint64_t>(rd()) << 32) | rd();
             }
             image = get_image_fern(cfg, threads, seed);
+        } else if (perturbation) {
+            // the centre keeps every digit of -x / -y; cfg.pos (their f64 roundings) is not read
+            const WideCentre centre = WideCentre::from_decimal(pos_x_s, pos_y, WideCentre::words_for_scale(cfg.scale.re, cfg.scale.im));
+            image = get_image(cfg, centre.c());
         } else {
             const int precision = f32 ? FR_PRECISION_F32 : FR_PRECISION_F64;
             image = supersample_s ? get_image(cfg, precision, to_u32(*supersample_s, "--supersample")) : get_image(cfg, precision);

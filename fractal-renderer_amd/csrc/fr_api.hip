@@ -765,7 +765,7 @@ static int prof_end(hipStream_t stream, const char *kname) {
 }
 
 int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0,
-                       uint32_t y1, unsigned bpp, void *d_out, hipStream_t stream) {
+                       uint32_t y1, unsigned bpp, void *d_out, hipStream_t stream, const fr_wide_centre *wide) {
     fr_kparams p;
     fill_params(cfg, o, p); /* the colour constants; no loop plan, no kernel choice, no view sample */
     p.nrows = y1 - y0;
@@ -779,7 +779,7 @@ int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const fr_i
     if (prc != FR_OK) return prc;
     const char *kname = "";
     if (precision == FR_PRECISION_PT) {
-        const int rc = launch_pt(ctx, cfg, pos_lo, p, FR_OUT_RGB, out, stream, &kname);
+        const int rc = launch_pt(ctx, cfg, pos_lo, p, FR_OUT_RGB, out, stream, &kname, wide);
         if (rc != FR_OK) return rc;
     } else {
         HIP_TRY(fr_launch_escape_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, FR_OUT_RGB, out, false, stream,
@@ -1273,9 +1273,9 @@ void fr_render_opts_init(fr_render_opts *opts) {
 
 static int render_rows_device(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, void *d_out,
                               size_t out_len, void *hip_stream, unsigned bytes_per_pixel, const fr_render_opts *opts,
-                              const fr_imaginary *pos_lo = nullptr) {
+                              const fr_imaginary *pos_lo = nullptr, const fr_wide_centre *wide = nullptr) {
     int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = check_precision_lo(cfg, precision, pos_lo);
+    if (rc == FR_OK) rc = wide ? check_pt_wide(cfg, wide) : check_precision_lo(cfg, precision, pos_lo);
     Opts o;
     if (rc == FR_OK) rc = resolve_opts(opts, o);
     if (rc != FR_OK) return rc;
@@ -1291,7 +1291,7 @@ static int render_rows_device(const fr_config *cfg, int precision, uint32_t y0, 
     if (rc != FR_OK) return rc;
     if (precision == FR_PRECISION_DD || precision == FR_PRECISION_PT)
         return render_deep_device(*ctx, precision, cfg, pos_lo, o, y0, y1, bytes_per_pixel, d_out,
-                                  static_cast<hipStream_t>(hip_stream));
+                                  static_cast<hipStream_t>(hip_stream), wide);
     fr_kparams p;
     fill_params(cfg, o, p);
     p.nrows = y1 - y0;
@@ -1527,9 +1527,9 @@ int fr_recursive(uint32_t iterations, fr_imaginary start, fr_imaginary c, double
 /* fr_escape_rows, fr_escape_rows_dd and fr_escape_rows_pt: `zw` doubles per pixel (2: re, im — DD: the hi parts; 4: DD with
  * the lo parts) */
 static int escape_rows(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
-                       double *z_re_im, uint32_t *iters, unsigned zw) {
+                       double *z_re_im, uint32_t *iters, unsigned zw, const fr_wide_centre *wide = nullptr) {
     int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = check_precision_lo(cfg, precision, pos_lo);
+    if (rc == FR_OK) rc = wide ? check_pt_wide(cfg, wide) : check_precision_lo(cfg, precision, pos_lo);
     if (rc != FR_OK) return rc;
     const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
     if (npx == 0 || (!z_re_im && !iters)) return FR_OK;
@@ -1555,7 +1555,7 @@ static int escape_rows(const fr_config *cfg, int precision, const fr_imaginary *
         HIP_TRY(fr_launch_escape_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, FR_OUT_ESCAPE, ko, zw == 4,
                                     ctx->stream, nullptr));
     } else if (precision == FR_PRECISION_PT) {
-        rc = launch_pt(*ctx, cfg, pos_lo, p, FR_OUT_ESCAPE, ko, ctx->stream, nullptr);
+        rc = launch_pt(*ctx, cfg, pos_lo, p, FR_OUT_ESCAPE, ko, ctx->stream, nullptr, wide);
         if (rc != FR_OK) return rc;
     } else {
         plan_loop(cfg, precision, o, p);
@@ -1738,11 +1738,11 @@ int fr_escape_extend(const fr_config *cfg, int precision, const fr_imaginary *po
 
 /* The domain of the four calls (include/fractal_hip.h), checked before any device work: `from` = nullptr for the state render.
  * *work = false: a legal call with nothing to do (no rows; for the extension also M == N or an algorithm without orbits). */
-static int check_pt_state(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, const uint32_t *from,
-                          const void *z, const void *iters, const void *dz, const void *m, bool *work) {
+static int check_pt_state(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, uint32_t y0, uint32_t y1,
+                          const uint32_t *from, const void *z, const void *iters, const void *dz, const void *m, bool *work) {
     *work = false;
     int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = check_pt(cfg, pos_lo);
+    if (rc == FR_OK) rc = wide ? check_pt_wide(cfg, wide) : check_pt(cfg, pos_lo);
     if (rc != FR_OK) return rc;
     if (from && cfg->iterations < *from)
         return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from a stored state");
@@ -1756,38 +1756,39 @@ static int check_pt_state(const fr_config *cfg, const fr_imaginary *pos_lo, uint
 }
 
 /* from == nullptr: the state render; else the extension from *from.  On the caller's stream, into the caller's arrays. */
-static int pt_state_launch(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, const uint32_t *from,
-                           double *d_z, uint32_t *d_iters, double *d_dz, uint32_t *d_m, hipStream_t stream) {
+static int pt_state_launch(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, uint32_t y0,
+                           uint32_t y1, const uint32_t *from, double *d_z, uint32_t *d_iters, double *d_dz, uint32_t *d_m,
+                           hipStream_t stream) {
     fr_kparams p;
     fill_params(cfg, default_opts(), p);
     rows_grid(p, y0, y1);
     int rc = prof_begin(stream);
     if (rc != FR_OK) return rc;
     const char *kname = "";
-    rc = from ? launch_pt_extend(ctx, cfg, pos_lo, p, *from, d_z, d_iters, d_dz, d_m, stream, &kname)
-              : launch_pt_state(ctx, cfg, pos_lo, p, d_z, d_iters, d_dz, d_m, stream, &kname);
+    rc = from ? launch_pt_extend(ctx, cfg, pos_lo, p, *from, d_z, d_iters, d_dz, d_m, stream, &kname, wide)
+              : launch_pt_state(ctx, cfg, pos_lo, p, d_z, d_iters, d_dz, d_m, stream, &kname, wide);
     if (rc != FR_OK) return rc;
     return prof_end(stream, kname);
 }
 
-static int pt_state_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z,
-                           void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
+static int pt_state_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, uint32_t y0, uint32_t y1,
+                           const uint32_t *from, void *d_z, void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
     bool work;
-    int rc = check_pt_state(cfg, pos_lo, y0, y1, from, d_z, d_iters, d_dz, d_m, &work);
+    int rc = check_pt_state(cfg, pos_lo, wide, y0, y1, from, d_z, d_iters, d_dz, d_m, &work);
     if (rc != FR_OK || !work) return rc;
     LifeShared ls;
     Ctx *ctx;
     rc = primary(&ctx);
     if (rc != FR_OK) return rc;
-    return pt_state_launch(*ctx, cfg, pos_lo, y0, y1, from, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
+    return pt_state_launch(*ctx, cfg, pos_lo, wide, y0, y1, from, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
                            static_cast<double *>(d_dz), static_cast<uint32_t *>(d_m), static_cast<hipStream_t>(hip_stream));
 }
 
 /* the host forms: z and dz share the context's z scratch, iters and m its iters scratch */
-static int pt_state_host(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, const uint32_t *from, double *z,
-                         uint32_t *iters, double *dz, uint32_t *m) {
+static int pt_state_host(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, uint32_t y0, uint32_t y1,
+                         const uint32_t *from, double *z, uint32_t *iters, double *dz, uint32_t *m) {
     bool work;
-    int rc = check_pt_state(cfg, pos_lo, y0, y1, from, z, iters, dz, m, &work);
+    int rc = check_pt_state(cfg, pos_lo, wide, y0, y1, from, z, iters, dz, m, &work);
     if (rc != FR_OK || !work) return rc;
     const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
     const size_t zb = npx * 2 * sizeof(double), ib = npx * sizeof(uint32_t);
@@ -1807,7 +1808,7 @@ static int pt_state_host(const fr_config *cfg, const fr_imaginary *pos_lo, uint3
         HIP_TRY(hipMemcpyAsync(d_iters, iters, ib, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipMemcpyAsync(d_m, m, ib, hipMemcpyHostToDevice, ctx->stream));
     }
-    rc = pt_state_launch(*ctx, cfg, pos_lo, y0, y1, from, d_z, d_iters, d_dz, d_m, ctx->stream);
+    rc = pt_state_launch(*ctx, cfg, pos_lo, wide, y0, y1, from, d_z, d_iters, d_dz, d_m, ctx->stream);
     if (rc != FR_OK) return rc;
     HIP_TRY(hipMemcpyAsync(z, d_z, zb, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(dz, d_dz, zb, hipMemcpyDeviceToHost, ctx->stream));
@@ -1819,22 +1820,80 @@ static int pt_state_host(const fr_config *cfg, const fr_imaginary *pos_lo, uint3
 
 int fr_escape_rows_pt_state_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, void *d_z,
                                    void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
-    return pt_state_device(cfg, pos_lo, y0, y1, nullptr, d_z, d_iters, d_dz, d_m, hip_stream);
+    return pt_state_device(cfg, pos_lo, nullptr, y0, y1, nullptr, d_z, d_iters, d_dz, d_m, hip_stream);
 }
 
 int fr_escape_extend_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, uint32_t from_iterations,
                                void *d_z, void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
-    return pt_state_device(cfg, pos_lo, y0, y1, &from_iterations, d_z, d_iters, d_dz, d_m, hip_stream);
+    return pt_state_device(cfg, pos_lo, nullptr, y0, y1, &from_iterations, d_z, d_iters, d_dz, d_m, hip_stream);
 }
 
 int fr_escape_rows_pt_state(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z, uint32_t *iters,
                             double *dz, uint32_t *m) {
-    return pt_state_host(cfg, pos_lo, y0, y1, nullptr, z, iters, dz, m);
+    return pt_state_host(cfg, pos_lo, nullptr, y0, y1, nullptr, z, iters, dz, m);
 }
 
 int fr_escape_extend_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, uint32_t from_iterations,
                         double *z, uint32_t *iters, double *dz, uint32_t *m) {
-    return pt_state_host(cfg, pos_lo, y0, y1, &from_iterations, z, iters, dz, m);
+    return pt_state_host(cfg, pos_lo, nullptr, y0, y1, &from_iterations, z, iters, dz, m);
+}
+
+/* ---- WIDE PT (include/fractal_hip.h): the PT calls above with a fixed-point view centre in place of (pos, pos_lo) ------- */
+
+/* a NULL centre must not fall through to the dd road */
+static int need_centre(const fr_wide_centre *centre) {
+    if (!centre) return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_PT, wide centre: centre is NULL");
+    return FR_OK;
+}
+
+int fr_render_rows_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, int channels, uint8_t *out,
+                           size_t out_len) {
+    int rc = dd_channels(channels);
+    if (rc == FR_OK) rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return fr_host_render_rows_deep(cfg, FR_PRECISION_PT, nullptr, y0, y1, out, out_len, (unsigned)channels, nullptr, centre);
+}
+
+int fr_render_rows_pt_wide_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, int channels,
+                                  void *d_out, size_t out_len, void *hip_stream) {
+    int rc = dd_channels(channels);
+    if (rc == FR_OK) rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return render_rows_device(cfg, FR_PRECISION_PT, y0, y1, d_out, out_len, hip_stream, (unsigned)channels, nullptr, nullptr, centre);
+}
+
+int fr_escape_rows_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z, uint32_t *iters) {
+    const int rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return escape_rows(cfg, FR_PRECISION_PT, nullptr, y0, y1, z, iters, 2, centre);
+}
+
+int fr_escape_rows_pt_wide_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, void *d_z,
+                                        void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
+    const int rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return pt_state_device(cfg, nullptr, centre, y0, y1, nullptr, d_z, d_iters, d_dz, d_m, hip_stream);
+}
+
+int fr_escape_extend_pt_wide_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
+                                    uint32_t from_iterations, void *d_z, void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
+    const int rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return pt_state_device(cfg, nullptr, centre, y0, y1, &from_iterations, d_z, d_iters, d_dz, d_m, hip_stream);
+}
+
+int fr_escape_rows_pt_wide_state(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z,
+                                 uint32_t *iters, double *dz, uint32_t *m) {
+    const int rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return pt_state_host(cfg, nullptr, centre, y0, y1, nullptr, z, iters, dz, m);
+}
+
+int fr_escape_extend_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, uint32_t from_iterations,
+                             double *z, uint32_t *iters, double *dz, uint32_t *m) {
+    const int rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return pt_state_host(cfg, nullptr, centre, y0, y1, &from_iterations, z, iters, dz, m);
 }
 
 int fr_colour_rows_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, size_t n, int channels,

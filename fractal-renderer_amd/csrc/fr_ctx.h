@@ -22,6 +22,7 @@
 
 #include "../../include/fractal_hip.h"
 #include "fr_kernels.h"
+#include "fr_wide.h"
 
 namespace fr {
 
@@ -191,20 +192,23 @@ int check_precision_lo(const fr_config *cfg, int precision, const fr_imaginary *
  * Records the profiling events and the kernel's name like render_device.  No host synchronisation (PT: apart from
  * computing and uploading the view's reference orbit when the context does not hold it yet). */
 int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0,
-                       uint32_t y1, unsigned bpp, void *d_out, hipStream_t stream);
+                       uint32_t y1, unsigned bpp, void *d_out, hipStream_t stream, const fr_wide_centre *wide = nullptr);
+/* `wide` in the PT calls below: the view's wide centre (include/fractal_hip.h, "WIDE PT"; checked with check_pt_wide,
+ * fr_wide.h) in place of (cfg->pos, pos_lo); nullptr = the dd centre. */
 /* FR_PRECISION_PT (fr_pt.hip: escape_pt_kernel): the launch's local grid, colour and limit from `p` as for DD; the view's
  * reference orbits from ctx's cache (computed and uploaded on a miss).  MODE ESCAPE writes re, im per pixel. */
 int launch_pt(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, int mode, const fr_kout &out,
-              hipStream_t stream, const char **kernel_name);
+              hipStream_t stream, const char **kernel_name, const fr_wide_centre *wide = nullptr);
 
 /* FR_PRECISION_PT with its resumable state (fr_pt.hip: escape_pt_state_kernel, escape_extend_pt_kernel; include/fractal_hip.h,
  * "resumable perturbation"): the local grid from `p` as launch_pt takes it, z and dz as re, im per pixel, m with bit 31 =
  * on K.  The extension continues the arrays from from_iterations to p.iterations on the orbits of the new cap, which the
  * context's cache continues from those of the old one. */
 int launch_pt_state(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, double *z, uint32_t *iters,
-                    double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name);
+                    double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name, const fr_wide_centre *wide = nullptr);
 int launch_pt_extend(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, uint32_t from_iterations,
-                     double *z, uint32_t *iters, double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name);
+                     double *z, uint32_t *iters, double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name,
+                     const fr_wide_centre *wide = nullptr);
 
 /* choose_kernel for rows [y0, y1) of the image as ONE launch, recorded in `o` (tile 0 only): callers that render those
  * rows in several launches then sample the view once, not once per launch.  The calling thread must be on ctx's device. */
@@ -287,6 +291,7 @@ int fr_host_render_rows(const fr_config *cfg, int precision, uint32_t y0, uint32
                         unsigned bytes_per_pixel, const fr_render_opts *opts);
 /* the same for FR_PRECISION_DD / FR_PRECISION_PT with the centre's low halves (fr_host.hip) */
 int fr_host_render_rows_deep(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
-                             uint8_t *out, size_t out_len, unsigned bytes_per_pixel, const fr_render_opts *opts);
+                             uint8_t *out, size_t out_len, unsigned bytes_per_pixel, const fr_render_opts *opts,
+                             const fr_wide_centre *wide = nullptr);
 
 #endif

@@ -714,11 +714,11 @@ int fr_host_render_rows(const fr_config *cfg, int precision, uint32_t y0, uint32
  * costs ~14x an f64 one on the device ("Double-double deep zoom"), and PT serves the long orbits of deep
  * views, so the copy that the f64 road works hard to hide is a few per cent of the call here. */
 int fr_host_render_rows_deep(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
-                             uint8_t *out, size_t out_len, unsigned bpp, const fr_render_opts *opts) {
+                             uint8_t *out, size_t out_len, unsigned bpp, const fr_render_opts *opts, const fr_wide_centre *wide) {
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
     if (y0 > y1) return fail(FR_ERR_INVALID_ARGUMENT, "y0 > y1");
     if (y1 > cfg->height) return fail(FR_ERR_INVALID_ARGUMENT, "y1 > height");
-    int rc = check_precision_lo(cfg, precision, pos_lo);
+    int rc = wide ? check_pt_wide(cfg, wide) : check_precision_lo(cfg, precision, pos_lo);
     Opts o;
     if (rc == FR_OK) rc = resolve_opts(opts, o);
     if (rc != FR_OK) return rc;
@@ -734,7 +734,7 @@ int fr_host_render_rows_deep(const fr_config *cfg, int precision, const fr_imagi
     std::lock_guard<std::mutex> lk(ctx->mu);
     rc = ctx->reserve(ctx->rgb, need);
     if (rc != FR_OK) return rc;
-    rc = render_deep_device(*ctx, precision, cfg, pos_lo, o, y0, y1, bpp, ctx->rgb.ptr, ctx->stream);
+    rc = render_deep_device(*ctx, precision, cfg, pos_lo, o, y0, y1, bpp, ctx->rgb.ptr, ctx->stream, wide);
     if (rc != FR_OK) return rc;
     HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

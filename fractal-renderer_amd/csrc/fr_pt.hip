@@ -35,6 +35,7 @@
 
 #include "fr_ctx.h"
 #include "fr_math.h"
+#include "fr_wide.h"
 
 namespace {
 
@@ -431,6 +432,7 @@ ddh neg(ddh x) { return {-x.hi, -x.lo}; }
 struct OrbitEnd {
     bool ended = false; /* ended by escape (identical at every higher cap); false: cut by the cap at k == kmax */
     ddh re{0.0, 0.0}, im{0.0, 0.0};
+    fr::WideTail wide; /* that entry as integers, for a view with a wide centre (fr_wide.hip) */
 };
 
 /* Orbit `which` (0: R or V, 1: K) of the view as re, im pairs of the hi parts, appended to `out`; at most iterations + 2
@@ -478,6 +480,17 @@ void reference_orbit(const fr_config *cfg, double lo_re, double lo_im, int which
     end.re = zr, end.im = zi;
 }
 
+/* reference_orbit for a view with a wide centre (include/fractal_hip.h, "WIDE PT"): the same contract, the recurrence in
+ * fixed point from the stored integer tail */
+void reference_orbit_wide(const fr_config *cfg, const fr_wide_centre *wide, int which, std::vector<double> &out, OrbitEnd &end,
+                          const OrbitEnd *from = nullptr, uint32_t last = 0) {
+    if (from) {
+        end = *from;
+        if (from->ended) return;
+    }
+    fr::wide_reference_orbit(cfg, wide, which, out, end.ended, end.wide, from ? &from->wide : nullptr, last);
+}
+
 }  // namespace
 
 namespace fr {
@@ -486,6 +499,7 @@ namespace fr {
 struct PtOrbit {
     uint32_t algo = 0, iterations = 0;
     double key[6] = {}; /* pos.re, pos.im, pos_lo.re, pos_lo.im, julia_set.re, julia_set.im, compared bit for bit */
+    std::vector<uint64_t> wide_key; /* a wide centre's n and words (then key[0 .. 3] are 0); empty: a dd view */
     double2 *dev = nullptr;
     uint32_t x_last = 0, k_last = 0;
     size_t k_offset = 0; /* entries */
@@ -499,9 +513,9 @@ struct PtOrbit {
 
 namespace {
 
-void view_key(const fr_config *cfg, const fr_imaginary *pos_lo, double key[6]) {
-    key[0] = cfg->pos.re;
-    key[1] = cfg->pos.im;
+void view_key(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, double key[6]) {
+    key[0] = wide ? 0.0 : cfg->pos.re; /* a wide view does not read cfg->pos */
+    key[1] = wide ? 0.0 : cfg->pos.im;
     key[2] = pos_lo ? pos_lo->re : 0.0;
     key[3] = pos_lo ? pos_lo->im : 0.0;
     key[4] = cfg->algo == 2 ? cfg->julia_set.re : 0.0;
@@ -514,13 +528,15 @@ void view_key(const fr_config *cfg, const fr_imaginary *pos_lo, double key[6]) {
  * ended by escape is the same at every cap, so if all are, the entry is re-keyed and nothing is computed; otherwise the
  * recurrence goes on from the stored dd tail for the missing entries only, into a NEW PtOrbit — launches in flight hold the
  * old one — whose old entries arrive by a device-to-device copy. */
-int orbit_for(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, std::shared_ptr<PtOrbit> &out) {
+int orbit_for(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, std::shared_ptr<PtOrbit> &out) {
     double key[6];
-    view_key(cfg, pos_lo, key);
+    view_key(cfg, pos_lo, wide, key);
+    std::vector<uint64_t> wkey; /* one slot, two roads: a wide view never matches a dd view, nor other words or another n */
+    if (wide) wide_key(wide, wkey);
     const bool julia = cfg->algo == 2;
     std::lock_guard<std::mutex> lk(ctx.pt_mu);
     const std::shared_ptr<PtOrbit> c = ctx.pt_orbit;
-    const bool same_view = c && c->algo == cfg->algo && memcmp(c->key, key, sizeof key) == 0;
+    const bool same_view = c && c->algo == cfg->algo && memcmp(c->key, key, sizeof key) == 0 && c->wide_key == wkey;
     if (same_view && c->iterations == cfg->iterations) {
         c->computed = 0;
         out = c;
@@ -535,13 +551,19 @@ int orbit_for(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, std::s
     }
     std::vector<double> x, k; /* the entries to upload: all of them, or those behind the cached ones */
     auto o = std::make_shared<PtOrbit>();
-    reference_orbit(cfg, key[2], key[3], 0, x, o->x_end, resume ? &c->x_end : nullptr, resume ? c->x_last : 0u);
-    if (julia) reference_orbit(cfg, key[2], key[3], 1, k, o->k_end, resume ? &c->k_end : nullptr, resume ? c->k_last : 0u);
+    if (wide) {
+        reference_orbit_wide(cfg, wide, 0, x, o->x_end, resume ? &c->x_end : nullptr, resume ? c->x_last : 0u);
+        if (julia) reference_orbit_wide(cfg, wide, 1, k, o->k_end, resume ? &c->k_end : nullptr, resume ? c->k_last : 0u);
+    } else {
+        reference_orbit(cfg, key[2], key[3], 0, x, o->x_end, resume ? &c->x_end : nullptr, resume ? c->x_last : 0u);
+        if (julia) reference_orbit(cfg, key[2], key[3], 1, k, o->k_end, resume ? &c->k_end : nullptr, resume ? c->k_last : 0u);
+    }
     const size_t x_old = resume ? (size_t)c->x_last + 1 : 0, k_old = resume && julia ? (size_t)c->k_last + 1 : 0;
     const size_t x_n = x_old + x.size() / 2, k_n = k_old + k.size() / 2;
     o->algo = cfg->algo;
     o->iterations = cfg->iterations;
     memcpy(o->key, key, sizeof key);
+    o->wide_key = std::move(wkey);
     o->x_last = (uint32_t)(x_n - 1);
     o->k_offset = x_n;
     o->k_last = julia ? (uint32_t)(k_n - 1) : o->x_last;
@@ -577,7 +599,7 @@ hipError_t launch_state(const fr_kparams &p, uint32_t from, bool extend, double 
 }  // namespace
 
 int launch_pt(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, int mode, const fr_kout &out,
-              hipStream_t stream, const char **kernel_name) {
+              hipStream_t stream, const char **kernel_name, const fr_wide_centre *wide) {
     if (kernel_name) *kernel_name = "escape_pt_kernel";
     if (p.ncols == 0 || p.nrows == 0) return FR_OK;
     const bool julia = cfg->algo == 2;
@@ -586,7 +608,7 @@ int launch_pt(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const 
         return FR_OK;
     }
     std::shared_ptr<PtOrbit> o;
-    const int rc = orbit_for(ctx, cfg, pos_lo, o);
+    const int rc = orbit_for(ctx, cfg, pos_lo, wide, o);
     if (rc != FR_OK) return rc;
     if (julia) {
         HIP_TRY(launch<true>(p, mode, out, o->dev, o->dev + o->k_offset, o->x_last, o->k_last, stream));
@@ -597,7 +619,7 @@ int launch_pt(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const 
 }
 
 int launch_pt_state(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, double *z, uint32_t *iters,
-                    double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name) {
+                    double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name, const fr_wide_centre *wide) {
     if (kernel_name) *kernel_name = "escape_pt_state_kernel";
     if (p.ncols == 0 || p.nrows == 0) return FR_OK;
     const bool julia = cfg->algo == 2;
@@ -606,7 +628,7 @@ int launch_pt_state(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, 
         return FR_OK;
     }
     std::shared_ptr<PtOrbit> o;
-    const int rc = orbit_for(ctx, cfg, pos_lo, o);
+    const int rc = orbit_for(ctx, cfg, pos_lo, wide, o);
     if (rc != FR_OK) return rc;
     HIP_TRY(julia ? launch_state<true>(p, 0, false, z, iters, dz, m, o.get(), stream)
                   : launch_state<false>(p, 0, false, z, iters, dz, m, o.get(), stream));
@@ -614,12 +636,13 @@ int launch_pt_state(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, 
 }
 
 int launch_pt_extend(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, uint32_t from_iterations,
-                     double *z, uint32_t *iters, double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name) {
+                     double *z, uint32_t *iters, double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name,
+                     const fr_wide_centre *wide) {
     if (kernel_name) *kernel_name = "escape_extend_pt_kernel";
     const bool julia = cfg->algo == 2;
     if (p.ncols == 0 || p.nrows == 0 || p.iterations <= from_iterations || (cfg->algo != 0 && !julia)) return FR_OK;
     std::shared_ptr<PtOrbit> o;
-    const int rc = orbit_for(ctx, cfg, pos_lo, o);
+    const int rc = orbit_for(ctx, cfg, pos_lo, wide, o);
     if (rc != FR_OK) return rc;
     HIP_TRY(julia ? launch_state<true>(p, from_iterations, true, z, iters, dz, m, o.get(), stream)
                   : launch_state<false>(p, from_iterations, true, z, iters, dz, m, o.get(), stream));

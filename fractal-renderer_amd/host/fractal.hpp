@@ -18,6 +18,7 @@
 #ifndef FRACTAL_HPP
 #define FRACTAL_HPP
 
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -169,6 +170,57 @@ inline void pt_state_rows_device(const Config &config, void *d_z, void *d_iters,
 inline void extend_pt_rows_device(const Config &config, uint32_t from_iterations, void *d_z, void *d_iters, void *d_dz, void *d_m,
                                   void *hip_stream = nullptr, const fr_imaginary *pos_lo = nullptr) {
     check(fr_escape_extend_pt_device(&config, pos_lo, 0, config.height, from_iterations, d_z, d_iters, d_dz, d_m, hip_stream));
+}
+// ---- WIDE PT (include/fractal_hip.h, "WIDE PT"): a fixed-point view centre of up to 1016 bits ------------------------
+// FR_PRECISION_PT past a scale of 10^30: the centre is words x 64 bits per axis instead of (pos, pos_lo); config.pos is not
+// read.  A GUI pans with add() and hands the view back to (pos, pos_lo) at shallow scales with to_double().
+struct WideCentre {
+    std::vector<uint64_t> re, im;  // little-endian words, two's complement, value I / 2^(64 words - 8)
+    explicit WideCentre(uint32_t words = 2) : re(words, 0), im(words, 0) {}
+    // the smallest word count of the domain rule F >= e + 64, where max |scale| = f 2^e with 0.5 <= f < 1
+    static uint32_t words_for_scale(double scale_re, double scale_im) {
+        int e = 0;
+        (void)std::frexp(std::fmax(std::fabs(scale_re), std::fabs(scale_im)), &e);
+        const int n = (e + 72 + 63) / 64;
+        return static_cast<uint32_t>(n < 2 ? 2 : n);
+    }
+    // decimal strings of any length, each component the floor of the string's exact value (fr_wide_from_decimal)
+    static WideCentre from_decimal(const std::string &re_text, const std::string &im_text, uint32_t words) {
+        WideCentre c(words);
+        check(fr_wide_from_decimal(re_text.c_str(), c.re.data(), words));
+        check(fr_wide_from_decimal(im_text.c_str(), c.im.data(), words));
+        return c;
+    }
+    uint32_t words() const { return static_cast<uint32_t>(re.size()); }
+    void add(double dre, double dim) {
+        check(fr_wide_add_double(re.data(), words(), dre));
+        check(fr_wide_add_double(im.data(), words(), dim));
+    }
+    // (pos, pos_lo): the nearest f64 per axis and the nearest f64 to the rest
+    std::pair<Imaginary, Imaginary> to_double() const {
+        Imaginary hi, lo;
+        check(fr_wide_to_double(re.data(), words(), &hi.re, &lo.re));
+        check(fr_wide_to_double(im.data(), words(), &hi.im, &lo.im));
+        return {hi, lo};
+    }
+    fr_wide_centre c() const { return fr_wide_centre{words(), re.data(), im.data()}; }  // points into this object
+};
+
+// get_image in FR_PRECISION_PT centred on a wide centre (one GPU, whatever use_devices chose)
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre) {
+    std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
+    check(fr_render_rows_pt_wide(&config, &centre, 0, config.height, 3, reinterpret_cast<uint8_t *>(image.data()),
+                                 image.size() * sizeof(RGB)));
+    return image;
+}
+// the resumable state of such a view and its cap raised in place: pt_state_rows_device / extend_pt_rows_device above
+inline void pt_state_rows_device(const Config &config, const fr_wide_centre &centre, void *d_z, void *d_iters, void *d_dz, void *d_m,
+                                 void *hip_stream = nullptr) {
+    check(fr_escape_rows_pt_wide_state_device(&config, &centre, 0, config.height, d_z, d_iters, d_dz, d_m, hip_stream));
+}
+inline void extend_pt_rows_device(const Config &config, const fr_wide_centre &centre, uint32_t from_iterations, void *d_z,
+                                  void *d_iters, void *d_dz, void *d_m, void *hip_stream = nullptr) {
+    check(fr_escape_extend_pt_wide_device(&config, &centre, 0, config.height, from_iterations, d_z, d_iters, d_dz, d_m, hip_stream));
 }
 
 }  // namespace fractal

@@ -169,8 +169,37 @@ typedef struct fr_config {
  *   the cap has last = N + 1 (R) or N (V, K).  So on a cut orbit m == last can only be met at the final step i = N - 1, by
  *   a pixel that never rebased.  There PT's rebase changes (dz, m) and leaves z alone: it is invisible in PT's output, and
  *   it is the only event of the sequence that depends on the cap.  The state rule leaves it out, so a state run to N is
- *   a prefix of the state run to M; an orbit ended by escape and the dist test do not depend on the cap at all. */
+ *   a prefix of the state run to M; an orbit ended by escape and the dist test do not depend on the cap at all.
+ *
+ * WIDE PT (the fr_*_pt_wide calls below): PT past a scale of 10^30.  A dd centre says ~106 bits about where the view is;
+ * nothing else in PT has that limit (off is one f64 division; the pixel loop sees only off and the stored f64 entries).  WIDE
+ * PT is PT's definition with ONE replacement, the reference orbits, which are iterated in fixed point from a wide centre:
+ *   A wide number is n little-endian uint64_t words in two's complement, 2 <= n <= FR_WIDE_MAX_WORDS; its value is
+ *   I / 2^F with F = 64 n - 8 (8 integer bits including the sign, so the range is [-128, 128)).
+ *   mul(a, b) = floor(a b / 2^F) and mul2(a, b) = floor(2 a b / 2^F), on the exact integer product (an arithmetic shift);
+ *   additions and subtractions are exact.
+ *   C = (Cre, Cim) is the centre (fr_wide_centre); J = (floor(julia_set.re 2^F), floor(julia_set.im 2^F)).
+ *   One step: next(X, A) = (mul(X.re, X.re) - mul(X.im, X.im) + A.re, mul2(X.re, X.im) + A.im).
+ *   Orbits: R: R_0 = 0, R_1 = C, R_{k+1} = next(R_k, C).  V: V_0 = C, V_{k+1} = next(V_k, J).  K: K_0 = 0,
+ *   K_{k+1} = next(K_k, J).
+ *   A stored entry is the f64 nearest to I / 2^F (ties to even), per axis.
+ *   Applied to the stored f64 entries, word for word PT's: the stop rule with kmin and kmax, "ended by escape" and "cut by
+ *   the cap", the pixel state and the step sequence, the state rule of RESUMABLE PT (with its claim), the colour.
+ *   cfg->pos is not read.
+ *   Fixed point cannot overflow: an entry that does not stop its orbit has re*re + im*im <= 4 on its stored values, so each
+ *   component is at most 2 + 2^-51 in magnitude and the next entry is below 5 + 5 + 3 < 16; an entry that is not tested
+ *   (k < kmin: R_1 = C, V_0 = C, and 0) has components within [-2, 2], and what follows it is below 8 + 3 < 16 as well.
+ *   The range is 128.
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): PT's domain on the remaining fields
+ * (finite, 0 < limit <= 2^500, |scale| >= 2^-64, iterations <= FR_PT_MAX_ITERATIONS); every component of the centre and of
+ * julia_set within [-2, 2]; n in 2 .. FR_WIDE_MAX_WORDS with non-NULL words; |scale| <= 2^440 on both axes — past about 2^458
+ * the squares of the rebase test, |dz|^2 of an off that is 2^-53 of the pixel spacing, leave f64's normal range, and a scaled
+ * pixel loop is not part of this definition; and F >= e + 64, where max(|scale.re|, |scale.im|) = f 2^e with 0.5 <= f < 1:
+ * the orbit carries 64 guard bits beyond the pixel spacing.  A centre too coarse for its scale is the caller's mistake and
+ * is refused, not rendered as a flat image.  One device; supersampling, block-cyclic and multi-device renders do not take
+ * a wide centre. */
 #define FR_PT_MAX_ITERATIONS (1u << 24)
+#define FR_WIDE_MAX_WORDS 16
 typedef enum fr_precision {
     FR_PRECISION_F64 = 0,
     FR_PRECISION_F32 = 1,
@@ -557,6 +586,52 @@ int fr_escape_extend_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32
  * only), out[3] = entries the last request for it computed on the host (0 = served as it was).  Zeros without a cached
  * orbit.  Touches no device. */
 int fr_debug_pt_orbit_cache(uint32_t out[4]);
+
+/* ---- WIDE PT: perturbation with a fixed-point view centre of up to 1016 bits ----------------------------------- */
+
+/* The view centre of WIDE PT (fr_precision above, "WIDE PT"): re and im point to n_words little-endian uint64_t words each,
+ * two's complement, value I / 2^(64 n_words - 8).  The caller owns the words; the library copies what it keeps. */
+typedef struct fr_wide_centre { uint32_t n_words; const uint64_t *re; const uint64_t *im; } fr_wide_centre;
+
+/* Host-only helpers on one component (w: n words, 2 <= n <= FR_WIDE_MAX_WORDS); none needs a device.  Each refuses, with
+ * FR_ERR_INVALID_ARGUMENT and w unchanged, a result outside |v| <= 2, a non-finite input and an n out of range.
+ *   fr_wide_from_double   w = floor(v 2^F): exact whenever v is representable.
+ *   fr_wide_add_double    I += floor(delta 2^F): a pan step, or a clicked pixel's off, added to the centre.
+ *   fr_wide_to_double     *hi = the f64 nearest to the value (ties to even), *lo (may be NULL) = the f64 nearest to the rest
+ *                         (at most half an ulp of *hi): a (pos, pos_lo) pair, which hands the view over to PT or DD at
+ *                         shallow scales.
+ *   fr_wide_from_decimal  w = floor of the decimal's exact value: [+-]digits[.digits][e[+-]digits] (at least one digit, at
+ *                         most four in the exponent, nothing else — no blanks); a malformed string is refused. */
+int fr_wide_from_double(double v, uint64_t *w, uint32_t n);
+int fr_wide_add_double(uint64_t *w, uint32_t n, double delta);
+int fr_wide_to_double(const uint64_t *w, uint32_t n, double *hi, double *lo);
+int fr_wide_from_decimal(const char *text, uint64_t *w, uint32_t n);
+
+/* Each call is the exact counterpart of the PT call it is named after, with `centre` where that one takes pos_lo (and
+ * cfg->pos): fr_render_rows_pt / _device, fr_escape_rows_pt, fr_escape_rows_pt_state(_device), fr_escape_extend_pt(_device)
+ * — the same buffers, alignment, asynchrony, precondition / result contract of the extension (a finished pixel has only its
+ * iters word read; M == N is a no-op that needs no device; y0 == y1 needs none either).  Domain: WIDE PT's.  The context's
+ * single orbit slot serves both roads: a wide view is told from a dd view and from a wide view with other words or another
+ * n, and raising the cap of the same wide view computes only the missing entries, from the orbit's last entry kept as
+ * integers (nothing when every orbit is ended by escape).  fr_debug_pt_orbit_cache reports a wide orbit the same way. */
+int fr_render_rows_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, int channels,
+                           uint8_t *out, size_t out_len);
+int fr_render_rows_pt_wide_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, int channels,
+                                  void *d_out, size_t out_len, void *hip_stream);
+int fr_escape_rows_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z,
+                           uint32_t *iters);
+int fr_escape_rows_pt_wide_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, void *d_z,
+                                        void *d_iters, void *d_dz, void *d_m, void *hip_stream);
+int fr_escape_extend_pt_wide_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
+                                    uint32_t from_iterations, void *d_z, void *d_iters, void *d_dz, void *d_m, void *hip_stream);
+int fr_escape_rows_pt_wide_state(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z,
+                                 uint32_t *iters, double *dz, uint32_t *m);
+int fr_escape_extend_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, uint32_t from_iterations,
+                             double *z, uint32_t *iters, double *dz, uint32_t *m);
+/* WIDE PT's reference orbit of the view on the host (no device needed), as fr_debug_reference_orbit: which 0 = R or V,
+ * 1 = K (Julia only); *len = the number of entries, min(*len, cap) of them written to out as re, im pairs. */
+int fr_debug_reference_orbit_wide(const fr_config *cfg, const fr_wide_centre *centre, int which, double *out, size_t cap,
+                                  uint32_t *len);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 

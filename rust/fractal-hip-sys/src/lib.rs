@@ -62,7 +62,19 @@ pub struct fr_render_opts {
     pub colour_filter: i32,
 }
 
+/// The view centre of WIDE PT (include/fractal_hip.h, "WIDE PT"): `n_words` little-endian words per axis, two's complement,
+/// value `I / 2^(64 n_words - 8)`.  The caller owns the words.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct fr_wide_centre {
+    pub n_words: u32,
+    pub re: *const u64,
+    pub im: *const u64,
+}
+
 pub const FR_OK: c_int = 0;
+/// Largest word count of a wide centre.
+pub const FR_WIDE_MAX_WORDS: u32 = 16;
 /// Largest `supersample` of the supersampled renders (include/fractal_hip.h, "supersampled rendering").
 pub const FR_SS_MAX: u32 = 8;
 /// `FR_ABI_VERSION` of the header these declarations were written against; `check_abi()` compares it with the library's.
@@ -129,6 +141,19 @@ extern "C" {
     pub fn fr_escape_extend_pt_device(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, from_iterations: u32, d_z: *mut c_void, d_iters: *mut c_void, d_dz: *mut c_void, d_m: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn fr_escape_rows_pt_state(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, z: *mut f64, iters: *mut u32, dz: *mut f64, m: *mut u32) -> c_int;
     pub fn fr_escape_extend_pt(cfg: *const fr_config, pos_lo: *const fr_imaginary, y0: u32, y1: u32, from_iterations: u32, z: *mut f64, iters: *mut u32, dz: *mut f64, m: *mut u32) -> c_int;
+    // WIDE PT (include/fractal_hip.h): a fixed-point view centre of up to 1016 bits; the helpers are host only
+    pub fn fr_wide_from_double(v: f64, w: *mut u64, n: u32) -> c_int;
+    pub fn fr_wide_add_double(w: *mut u64, n: u32, delta: f64) -> c_int;
+    pub fn fr_wide_to_double(w: *const u64, n: u32, hi: *mut f64, lo: *mut f64) -> c_int;
+    pub fn fr_wide_from_decimal(text: *const c_char, w: *mut u64, n: u32) -> c_int;
+    pub fn fr_render_rows_pt_wide(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, channels: c_int, out: *mut u8, out_len: usize) -> c_int;
+    pub fn fr_render_rows_pt_wide_device(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, channels: c_int, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_escape_rows_pt_wide(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, z: *mut f64, iters: *mut u32) -> c_int;
+    pub fn fr_escape_rows_pt_wide_state_device(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, d_z: *mut c_void, d_iters: *mut c_void, d_dz: *mut c_void, d_m: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_escape_extend_pt_wide_device(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, from_iterations: u32, d_z: *mut c_void, d_iters: *mut c_void, d_dz: *mut c_void, d_m: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_escape_rows_pt_wide_state(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, z: *mut f64, iters: *mut u32, dz: *mut f64, m: *mut u32) -> c_int;
+    pub fn fr_escape_extend_pt_wide(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, from_iterations: u32, z: *mut f64, iters: *mut u32, dz: *mut f64, m: *mut u32) -> c_int;
+    pub fn fr_debug_reference_orbit_wide(cfg: *const fr_config, centre: *const fr_wide_centre, which: c_int, out: *mut f64, cap: usize, len: *mut u32) -> c_int;
 }
 
 /// Message of the last failing call on this thread.
