@@ -33,6 +33,7 @@ __all__ = [
     "escape_rows_device", "extend_rows_device", "extend_rows", "colour_rows_device",
     "escape_rows_pt_state", "extend_rows_pt", "escape_rows_pt_state_device", "extend_rows_pt_device", "pt_orbit_cache",
     "WideCentre", "reference_orbit_wide",
+    "bla_table", "bla_count", "bla_cache", "BLA_DEFAULT_BITS",
 ]
 
 
@@ -169,6 +170,57 @@ def reference_orbit_wide(config, centre, which=0):
     return out[:n.value].copy()
 
 
+BLA_DEFAULT_BITS = _native.FR_BLA_DEFAULT_BITS
+
+
+def _bla_args(precision, pos_lo, centre, bla, supersample=1, opts=None):
+    """bla= argument -> (pos_lo pointer, centre pointer, bits, keep-alive) of the fr_*_pt_bla calls"""
+    if int(precision) != Precision.PT:
+        raise ValueError("bla= needs precision=Precision.PT")
+    if supersample != 1:
+        raise ValueError("supersample does not take bla=")
+    if opts is not None:
+        raise ValueError("bla= takes no opts: BLA-PT has one kernel")
+    bits = int(bla)
+    if bits != 0 and not 24 <= bits <= 53:
+        raise ValueError("bla= is None (off), 0 (%d bits) or 24 .. 53" % BLA_DEFAULT_BITS)
+    if centre is not None:
+        ptr, keep = _wide(centre, precision, pos_lo)
+        return None, ptr, bits, keep
+    lo, keep = _pos_lo(pos_lo)
+    return lo, None, bits, keep
+
+
+def bla_table(config, level, which=0, pos_lo=None, centre=None, bla=0):
+    """fr_debug_bla_table: level `level` of the BLA-PT table of orbit `which` (0: R or V, 1: K, Julia only) on the host (no
+    device needed): float64 [n_level, 5] = A.re, A.im, B.re, B.im, r2; empty past the top level."""
+    lo, ptr, bits, _keep = _bla_args(Precision.PT, pos_lo, centre, bla)
+    n = C.c_uint32(0)
+    lib = _native.load()
+    _native.check(lib.fr_debug_bla_table(C.byref(config), lo, ptr, bits, int(which), int(level), None, 0, C.byref(n)))
+    out = np.empty((n.value, 5), dtype=np.float64)
+    _native.check(lib.fr_debug_bla_table(C.byref(config), lo, ptr, bits, int(which), int(level), out.ctypes.data, len(out), C.byref(n)))
+    return out
+
+
+def bla_count(config, y0=0, y1=None, pos_lo=None, centre=None, bla=0):
+    """fr_debug_bla_count over rows [y0, y1): (passes through the BLA loop, nominal iterations), summed over the pixels on
+    the device; their ratio is what the skips save."""
+    y1 = config.height if y1 is None else y1
+    lo, ptr, bits, _keep = _bla_args(Precision.PT, pos_lo, centre, bla)
+    passes, steps = C.c_uint64(0), C.c_uint64(0)
+    _native.check(_native.load().fr_debug_bla_count(C.byref(config), lo, ptr, bits, y0, y1, C.byref(passes), C.byref(steps)))
+    return passes.value, steps.value
+
+
+def bla_cache():
+    """fr_debug_bla_cache: (bits of the cached table, levels of X's table, entries of all levels, 1 if the last request built
+    it / 0 if it was served)."""
+    out = (C.c_uint32 * 4)()
+    _native.check(_native.load().fr_debug_bla_cache(out))
+    return tuple(out)
+
+
 class Config(_native.fr_config):
     """calc::Config (calc/src/lib.rs:21-37).  Fields keep the reference's names; colours hold the
     stored RGB struct fields."""
@@ -284,16 +336,23 @@ def box_filter(image, s, channels=3):
     return out
 
 
-def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None, pos_lo=None, supersample=1, centre=None):
+def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None, pos_lo=None, supersample=1, centre=None,
+                   bla=None):
     """Rows [y0, y1) of get_image — the unit of the reference's rayon loop (src/lib.rs:256-264).
     Returns uint8 [y1-y0, width, 3].  pos_lo (Precision.DD or Precision.PT only): the low halves (re, im) of the view
     centre (split_dd), so that the centre is pos + pos_lo; None = (0, 0).
     supersample = s > 1: s x s samples per pixel, box-filtered on the device (include/fractal_hip.h, "supersampled
     rendering"); only the [y1-y0, width] result leaves the device.
     centre (Precision.PT only, exclusive with pos_lo): a WideCentre in place of (config.pos, pos_lo) for views past a scale
-    of 10^30 (include/fractal_hip.h, "WIDE PT"); supersample does not take it yet."""
+    of 10^30 (include/fractal_hip.h, "WIDE PT"); supersample does not take it yet.
+    bla (Precision.PT only, with pos_lo or centre or neither): None = plain PT; 0 or 24 .. 53 = BLA-PT at that many bits
+    (0: BLA_DEFAULT_BITS), PT with iterations skipped in bulk — an approximation, defined in include/fractal_hip.h, "BLA-PT"."""
     if out is None:
         out = np.empty((max(int(y1) - int(y0), 0), config.width, 3), dtype=np.uint8)
+    if bla is not None:
+        lo, ptr, bits, _keep = _bla_args(precision, pos_lo, centre, bla, supersample, opts)
+        _native.check(_native.load().fr_render_rows_pt_bla(C.byref(config), lo, ptr, bits, y0, y1, 3, out.ctypes.data, out.nbytes))
+        return out
     if centre is not None:
         ptr, _keep = _wide(centre, precision, pos_lo, supersample)
         _native.check(_native.load().fr_render_rows_pt_wide(C.byref(config), ptr, y0, y1, 3, out.ctypes.data, out.nbytes))
@@ -312,12 +371,15 @@ def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None,
     return out
 
 
-def get_image(config, precision=Precision.F64, pos_lo=None, supersample=1, centre=None):
+def get_image(config, precision=Precision.F64, pos_lo=None, supersample=1, centre=None, bla=None):
     """get_image(&Config) -> Vec<RGB> (src/lib.rs:253-270): uint8 [height, width, 3], row-major,
     bytes r,g,b.  Algo.BarnsleyFern is outside this path (random IFS, src/lib.rs:271-319): the
     per-pixel function returns BLACK for it (calc/src/lib.rs:211) and so does this.
-    pos_lo: see get_image_rows (Precision.DD or Precision.PT only).  supersample, centre: see get_image_rows."""
+    pos_lo: see get_image_rows (Precision.DD or Precision.PT only).  supersample, centre, bla: see get_image_rows."""
     out = np.empty((config.height, config.width, 3), dtype=np.uint8)
+    if bla is not None:
+        return get_image_rows(config, 0, config.height, precision, out, pos_lo=pos_lo, supersample=supersample, centre=centre,
+                              bla=bla)
     if centre is not None:
         return get_image_rows(config, 0, config.height, precision, out, pos_lo=pos_lo, supersample=supersample, centre=centre)
     if supersample != 1:
@@ -351,12 +413,17 @@ def get_image_fern(config, threads=1, seed=0, walkers=0):
     return out
 
 
-def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None, supersample=1, centre=None):
+def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None, supersample=1, centre=None, bla=None):
     """get_image as RGBA8 (alpha 255): uint8 [height, width, 4] — the GUI's upload format
     (src/gui.rs:71-72) produced on the device.  pos_lo: see get_image_rows (Precision.DD or Precision.PT only).
-    supersample, centre: see get_image_rows."""
+    supersample, centre, bla: see get_image_rows."""
     if out is None:
         out = np.empty((config.height, config.width, 4), dtype=np.uint8)
+    if bla is not None:
+        lo, ptr, bits, _keep = _bla_args(precision, pos_lo, centre, bla, supersample)
+        _native.check(_native.load().fr_render_rows_pt_bla(C.byref(config), lo, ptr, bits, 0, config.height, 4, out.ctypes.data,
+                                                           out.nbytes))
+        return out
     if centre is not None:
         ptr, _keep = _wide(centre, precision, pos_lo, supersample)
         _native.check(_native.load().fr_render_rows_pt_wide(C.byref(config), ptr, 0, config.height, 4, out.ctypes.data, out.nbytes))
@@ -407,12 +474,21 @@ def recursive_batch(iterations, start, c, limit, precision=Precision.F64):
     return pos, it
 
 
-def escape_rows(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, with_lo=False, centre=None):
+def escape_rows(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, with_lo=False, centre=None, bla=None):
     """recursive() results of every pixel of rows [y0, y1): (z float64 [rows, width, 2],
     iters uint32 [rows, width]).  Precision.DD: z holds the hi parts; with_lo=True returns z as [rows, width, 4] =
     re.hi, re.lo, im.hi, im.lo (Precision.DD only).  pos_lo: see get_image_rows (Precision.DD or Precision.PT only).
-    centre: a WideCentre (Precision.PT only, exclusive with pos_lo): fr_escape_rows_pt_wide."""
+    centre: a WideCentre (Precision.PT only, exclusive with pos_lo): fr_escape_rows_pt_wide.
+    bla (Precision.PT only): see get_image_rows; fr_escape_rows_pt_bla."""
     y1 = config.height if y1 is None else y1
+    if bla is not None:
+        if with_lo:
+            raise ValueError("with_lo needs precision=Precision.DD")
+        lo, ptr, bits, _keep = _bla_args(precision, pos_lo, centre, bla)
+        z = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
+        it = np.empty((y1 - y0, config.width), dtype=np.uint32)
+        _native.check(_native.load().fr_escape_rows_pt_bla(C.byref(config), lo, ptr, bits, y0, y1, z.ctypes.data, it.ctypes.data))
+        return z, it
     if centre is not None:
         if with_lo:
             raise ValueError("with_lo needs precision=Precision.DD")

@@ -115,6 +115,7 @@ class fr_wide_centre(C.Structure):
 
 
 FR_WIDE_MAX_WORDS = 16
+FR_BLA_DEFAULT_BITS = 40
 _OPTS = C.POINTER(fr_render_opts)
 _WIDE = C.POINTER(fr_wide_centre)
 
@@ -299,6 +300,31 @@ PROTOTYPES = {
     ),
     "fr_debug_reference_orbit_wide": (
         C.c_int, [C.POINTER(fr_config), _WIDE, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "fr_render_rows_pt_bla": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
+    "fr_render_rows_pt_bla_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t,
+         C.c_void_p],
+    ),
+    "fr_escape_rows_pt_bla": (
+        C.c_int, [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "fr_escape_rows_pt_bla_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "fr_debug_bla_table": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t,
+         C.POINTER(C.c_uint32)],
+    ),
+    "fr_debug_bla_count": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
+         C.POINTER(C.c_uint64)],
+    ),
+    "fr_debug_bla_cache": (C.c_int, [C.POINTER(C.c_uint32)]),
     "fr_colour_rows_device": (
         C.c_int,
         [C.POINTER(fr_config), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],

@@ -10,6 +10,8 @@
 // Extensions (no counterpart upstream): --f32; --devices 0,1,... (spread the image over several GPUs);
 // --perturbation (deep zooms: FR_PRECISION_PT on a wide centre; -x / -y are then read as decimal strings of any length, at
 // the word count the scale asks for, and scales up to 2^440 render — include/fractal_hip.h, "WIDE PT");
+// --bla or --bla=BITS beside --perturbation (BLA-PT: the same view with iterations skipped in bulk, an approximation defined
+// in include/fractal_hip.h, "BLA-PT"; BITS is 24 .. 53, default 40);
 // for -a fern: --threads N (the rayon thread count being stood in for; default: this machine's hardware
 // threads, what rayon would use) and --seed N (default: from the OS, as the reference seeds from entropy).
 // Not handled here (by design): --gui, --open.
@@ -69,7 +71,8 @@ int main(int argc, char **argv) {
                 exposure = "5", filename = "output", algo_s = "mandelbrot", color_weight = "0.01";
     std::optional<std::string> iterations, pos_x, scale_x, scale_y, primary, secondary, julia_re, julia_im, devices, threads_s,
         seed_s, supersample_s;
-    bool disable_inside = false, unsmooth = false, f32 = false, quiet = false, perturbation = false;
+    bool disable_inside = false, unsmooth = false, f32 = false, quiet = false, perturbation = false, bla = false;
+    int bla_bits = 0;
     std::vector<std::string> positionals;
 
     auto value = [&](int &i, const char *flag) -> std::string {
@@ -98,6 +101,12 @@ int main(int argc, char **argv) {
         else if (a == "-w" || a == "--color-weight") color_weight = value(i, "-w");
         else if (a == "--f32") f32 = true;       // this build's extension (no counterpart upstream)
         else if (a == "--perturbation") perturbation = true; // this build's extension: deep zooms on a wide centre
+        else if (a == "--bla") bla = true; // BLA-PT at the default bits
+        else if (a.rfind("--bla=", 0) == 0) { // ... or at 24 .. 53 (written with '=': a bare number after --bla is <width>)
+            bla = true;
+            bla_bits = static_cast<int>(to_u32(a.substr(6), "--bla"));
+            if (bla_bits < 24 || bla_bits > 53) die("--bla takes 24 .. 53 bits");
+        }
         else if (a == "--supersample") supersample_s = value(i, "--supersample"); // N x N samples per pixel, box-filtered on the device
         else if (a == "--devices") devices = value(i, "--devices");
         else if (a == "--threads") threads_s = value(i, "--threads");
@@ -123,6 +132,7 @@ int main(int argc, char **argv) {
     if ((scale_x || scale_y) && scale != "0.4") die("--scale conflicts with --scale-x/--scale-y");
     if (perturbation && (f32 || supersample_s || devices || algo == Algo::BarnsleyFern))
         die("--perturbation does not combine with --f32, --supersample, --devices or -a fern");
+    if (bla && !perturbation) die("--bla needs --perturbation");
 
     // src/lib.rs:207-226
     Config cfg = Config::make(algo);
@@ -184,7 +194,7 @@ int main(int argc, char **argv) {
         } else if (perturbation) {
             // the centre keeps every digit of -x / -y; cfg.pos (their f64 roundings) is not read
             const WideCentre centre = WideCentre::from_decimal(pos_x_s, pos_y, WideCentre::words_for_scale(cfg.scale.re, cfg.scale.im));
-            image = get_image(cfg, centre.c());
+            image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}) : get_image(cfg, centre.c());
         } else {
             const int precision = f32 ? FR_PRECISION_F32 : FR_PRECISION_F64;
             image = supersample_s ? get_image(cfg, precision, to_u32(*supersample_s, "--supersample")) : get_image(cfg, precision);

@@ -263,6 +263,7 @@ void Ctx::destroy() {
     {
         std::lock_guard<std::mutex> pl(pt_mu);
         pt_orbit.reset();
+        bla_table.reset();
     }
     for (hipEvent_t e : events) (void)hipEventDestroy(e);
     events.clear();

@@ -88,7 +88,8 @@ struct SurvSlot {
 };
 constexpr int kSurvSlots = 3;
 
-struct PtOrbit; /* fr_pt.hip */
+struct PtOrbit;  /* fr_pt.hip */
+struct BlaTable; /* fr_bla.hip */
 
 struct Ctx {
     int hip_device = -1;
@@ -152,6 +153,9 @@ struct Ctx {
      * them (the last reference frees the memory, after the device has finished with it) */
     std::mutex pt_mu;
     std::shared_ptr<PtOrbit> pt_orbit;
+    /* BLA-PT (fr_bla.hip): the skip tables of the last BLA view in device memory, kept and shared like the orbit they
+     * were built from, under pt_mu */
+    std::shared_ptr<BlaTable> bla_table;
 
     int create(int device); /* hipSetDevice + streams; the calling thread stays on `device` */
     void destroy();         /* frees everything (caller made sure nothing is in flight) */
@@ -209,6 +213,17 @@ int launch_pt_state(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, 
 int launch_pt_extend(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, uint32_t from_iterations,
                      double *z, uint32_t *iters, double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name,
                      const fr_wide_centre *wide = nullptr);
+
+/* For BLA-PT (fr_bla.hip), from fr_pt.hip: the view's orbits in device memory as launch_pt finds them (the context's cache,
+ * computed and uploaded on a miss) — `keep` holds them alive and is their identity, v.k == v.x for Mandelbrot — and orbit
+ * `which` (0: R or V, 1: K) on the host as re, im pairs appended to `out`, no device needed.  Arguments already checked. */
+struct PtOrbitView {
+    const double2 *x = nullptr, *k = nullptr;
+    uint32_t x_last = 0, k_last = 0;
+};
+int pt_orbit_view(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide,
+                  std::shared_ptr<PtOrbit> &keep, PtOrbitView &v);
+void pt_host_orbit(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, int which, std::vector<double> &out);
 
 /* choose_kernel for rows [y0, y1) of the image as ONE launch, recorded in `o` (tile 0 only): callers that render those
  * rows in several launches then sample the view once, not once per launch.  The calling thread must be on ctx's device. */

@@ -598,6 +598,27 @@ hipError_t launch_state(const fr_kparams &p, uint32_t from, bool extend, double 
 
 }  // namespace
 
+/* what fr_bla.hip needs of this file: the view's orbits in device memory (orbit_for's), and one orbit on the host */
+int pt_orbit_view(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide,
+                  std::shared_ptr<PtOrbit> &keep, PtOrbitView &v) {
+    const int rc = orbit_for(ctx, cfg, pos_lo, wide, keep);
+    if (rc != FR_OK) return rc;
+    const bool julia = cfg->algo == 2;
+    v.x = keep->dev;
+    v.k = julia ? keep->dev + keep->k_offset : keep->dev;
+    v.x_last = keep->x_last;
+    v.k_last = julia ? keep->k_last : keep->x_last;
+    return FR_OK;
+}
+
+void pt_host_orbit(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, int which, std::vector<double> &out) {
+    OrbitEnd end;
+    if (wide)
+        reference_orbit_wide(cfg, wide, which, out, end);
+    else
+        reference_orbit(cfg, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, which, out, end);
+}
+
 int launch_pt(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, int mode, const fr_kout &out,
               hipStream_t stream, const char **kernel_name, const fr_wide_centre *wide) {
     if (kernel_name) *kernel_name = "escape_pt_kernel";

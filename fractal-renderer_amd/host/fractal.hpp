@@ -223,5 +223,30 @@ inline void extend_pt_rows_device(const Config &config, const fr_wide_centre &ce
     check(fr_escape_extend_pt_wide_device(&config, &centre, 0, config.height, from_iterations, d_z, d_iters, d_dz, d_m, hip_stream));
 }
 
+// ---- BLA-PT (include/fractal_hip.h, "BLA-PT"): FR_PRECISION_PT that skips iterations in bulk ------------------------------
+// An approximation of PT, defined exactly; bits = 0 takes FR_BLA_DEFAULT_BITS, else 24 .. 53.  One GPU.
+struct Bla {
+    int bits = 0;
+};
+// get_image in BLA-PT centred on (config.pos, pos_lo)
+inline std::vector<RGB> get_image(const Config &config, Bla bla, const fr_imaginary *pos_lo = nullptr) {
+    std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
+    check(fr_render_rows_pt_bla(&config, pos_lo, nullptr, bla.bits, 0, config.height, 3, reinterpret_cast<uint8_t *>(image.data()),
+                                image.size() * sizeof(RGB)));
+    return image;
+}
+// ... and centred on a wide centre
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Bla bla) {
+    std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
+    check(fr_render_rows_pt_bla(&config, nullptr, &centre, bla.bits, 0, config.height, 3, reinterpret_cast<uint8_t *>(image.data()),
+                                image.size() * sizeof(RGB)));
+    return image;
+}
+// (z, iters) of the whole view into device arrays, for colour_rows_device; centre may be null
+inline void escape_rows_device(const Config &config, Bla bla, void *d_z, void *d_iters, void *hip_stream = nullptr,
+                               const fr_imaginary *pos_lo = nullptr, const fr_wide_centre *centre = nullptr) {
+    check(fr_escape_rows_pt_bla_device(&config, pos_lo, centre, bla.bits, 0, config.height, d_z, d_iters, hip_stream));
+}
+
 }  // namespace fractal
 #endif

@@ -197,7 +197,64 @@ typedef struct fr_config {
  * pixel loop is not part of this definition; and F >= e + 64, where max(|scale.re|, |scale.im|) = f 2^e with 0.5 <= f < 1:
  * the orbit carries 64 guard bits beyond the pixel spacing.  A centre too coarse for its scale is the caller's mistake and
  * is refused, not rendered as a flat image.  One device; supersampling, block-cyclic and multi-device renders do not take
- * a wide centre. */
+ * a wide centre.
+ *
+ * BLA-PT (the fr_*_pt_bla calls below): PT with bilinear-approximation skips.  While a pixel's offset dz from the reference
+ * orbit is far smaller than the orbit itself, the step dz' = (2 X_m + dz) dz + dc is linear in (dz, dc) to below f64 rounding,
+ * and 2^k composed linear steps are one tabulated dz' = A dz + B dc.  BLA-PT is an APPROXIMATION of PT (how close: DESIGN.md,
+ * "BLA-PT") and, like every mode here, is DEFINED exactly: PT's definition (WIDE PT's when a wide centre is given) with one
+ * change to the pixel loop, some steps being replaced by table skips.  The reference orbits and their stop rule, off, dc, the
+ * pixel's initial state, the plain step, the escape test, the rebase rule (dist < |dz|^2 or m == last) and the colour map on
+ * the f64 z are PT's, word for word.  Every operation below is one correctly rounded f64 operation; fma is fused and nothing
+ * else is; sqrt is IEEE.
+ *   Constants of a view: eps = 2^-bits with bits in 24 .. 53 (FR_BLA_DEFAULT_BITS = 40); b0 = 1 for Mandelbrot, 0 for Julia
+ *   (dc = 0 there); D bounds |dc| over the WHOLE image, not the rows of a call, so row pieces agree:
+ *     mr = max(|off_re(0)|, |off_re(width-1)|), mi = max(|off_im(0)|, |off_im(height-1)|), D = sqrt(mr*mr + mi*mi)
+ *     (an axis of 0 pixels contributes off(0) alone).
+ *   The table of an orbit X with last index `last` is a function of X's stored f64 entries, D, b0 and bits.  It is empty when
+ *   last < 2.
+ *     Level 0 has n_0 = last - 1 entries; entry j belongs to m = j + 1:
+ *       A = (X_m.re + X_m.re, X_m.im + X_m.im), B = (b0, 0), r = eps * sqrt(A.re*A.re + A.im*A.im).
+ *     Level k+1 has n_{k+1} = floor(n_k / 2) entries, built while n_k >= 2; entry j merges x = entry 2j (the first) with
+ *     y = entry 2j+1 of level k:
+ *       A = (fma(Ay.re, Ax.re, -(Ay.im*Ax.im)), fma(Ay.re, Ax.im, Ay.im*Ax.re))
+ *       B = (fma(Ay.re, Bx.re, -(Ay.im*Bx.im)) + By.re, fma(Ay.re, Bx.im, Ay.im*Bx.re) + By.im)
+ *       q = (ry - sqrt(Bx.re*Bx.re + Bx.im*Bx.im) * D) / sqrt(Ax.re*Ax.re + Ax.im*Ax.im); if !(q > 0) then q = 0 (NaN too)
+ *       r = rx < q ? rx : q.
+ *     Every entry stores r2 = r*r.  An entry with r2 == 0 is never applied and its A and B are unspecified (they may have
+ *     overflowed).  r is non-increasing in the level for a fixed first step (r <= rx).
+ *     Why A is finite where r2 > 0.  Invariant: r |A| < 2^-19 for every entry.  Level 0: an entry that does not end its
+ *     orbit has re*re + im*im <= 4 and the last entry is no level-0 entry (n_0 = last - 1), so |A| <= 4 (1 + 2^-51) and
+ *     r |A| = eps |A|^2 <= 16 eps (1 + 2^-49) <= 2^-20 (1 + 2^-49).  Merge: the subtraction only lowers ry and the division
+ *     rounds once, so r <= q <= (ry / |Ax|)(1 + 2^-51), and |A| <= |Ay| |Ax| (1 + 2^-50); hence r |A| <= ry |Ay| (1 + 2^-49),
+ *     y's own bound, and over at most 24 levels the factors stay below 1 + 2^-44.  r2 > 0 needs r > 2^-538, so such an entry
+ *     has |A| < 2^519: the product that A is did not overflow, given finite factors.  Ax is finite: rx >= r, so x is such an
+ *     entry itself.  Ay is finite by the same bound whenever ry*ry > 0.  What is left is 0 < ry < 2^-537 beside r > 2^-538,
+ *     that is |Ax| < 1: only if moreover |Ay| > 2^1024, hence |Ax| < 2^-505 — an orbit entry within 2^-506 of the critical
+ *     point followed, inside one block, by a stretch whose derivative passes 2^1024 — A is non-finite beside r2 > 0.  Then
+ *     A is still what this IEEE sequence gives, so the definition stays exact; |B| D <= ry bounds B the same way.
+ *   Pixel loop.  State as PT's, plus the table T of the orbit being followed: X's, and after a Julia rebase K's.  While
+ *   i < iterations:
+ *     1. d2 = dz.re*dz.re + dz.im*dz.im.  If m >= 1 let j = m - 1; K is the largest k >= 1 with j % 2^k == 0, (j >> k) < n_k,
+ *        i + 2^k <= iterations and d2 < r2 of entry j >> k of level k.  All four are monotone in k, so any search order
+ *        finds the same K.  There is no K when m == 0, when the table is empty, or when level 1 fails.
+ *     2. No K: one plain PT step, exactly PT's — the only way a single iteration is taken (level 0 exists only to build the
+ *        levels above it).  K found, with (A, B) = entry j >> K of level K:
+ *          dz'.re = fma(A.re, dz.re, fma(-A.im, dz.im, fma(B.re, dc.re, -(B.im*dc.im))))
+ *          dz'.im = fma(A.re, dz.im, fma(A.im, dz.re, fma(B.re, dc.im, B.im*dc.re)))
+ *          m += 2^K, i += 2^K, z = X_m + dz' per axis (m <= last always: 1 + ((j >> K) + 1) 2^K <= 1 + n_0).
+ *     3. In both cases test as PT does: dist = z.re*z.re + z.im*z.im; dist > limit*limit escapes with (z, i - 1), i already
+ *        advanced; otherwise rebase on PT's condition.
+ *     4. Exhaustion gives (z, iterations).
+ *   Escapes inside a skipped block are not looked for: that is part of the definition.  The radii keep z within a relative
+ *   eps of a reference entry that has not escaped.
+ * Domain: PT's, or WIDE PT's with a centre; bits 0 (= FR_BLA_DEFAULT_BITS) or 24 .. 53; iterations <= FR_PT_MAX_ITERATIONS,
+ * which bounds the tables: on the device an orbit's table holds fewer than `last` entries of 40 B (Mandelbrot) or 24 B (Julia,
+ * two orbits), beside the orbit's own 16 B per entry — at most 640 MiB (768 MiB for Julia's two) at the cap.  One device;
+ * supersampling, block-cyclic and multi-device renders do not take BLA-PT, nor do the resumable-state and extend calls: the
+ * condition i + 2^k <= iterations makes a run at cap N no prefix of the run at cap M, so there is no state to continue, and
+ * fr_escape_extend(_device) and fr_escape_extend_pt(_device) have no BLA form. */
+#define FR_BLA_DEFAULT_BITS 40
 #define FR_PT_MAX_ITERATIONS (1u << 24)
 #define FR_WIDE_MAX_WORDS 16
 typedef enum fr_precision {
@@ -632,6 +689,39 @@ int fr_escape_extend_pt_wide(const fr_config *cfg, const fr_wide_centre *centre,
  * 1 = K (Julia only); *len = the number of entries, min(*len, cap) of them written to out as re, im pairs. */
 int fr_debug_reference_orbit_wide(const fr_config *cfg, const fr_wide_centre *centre, int which, double *out, size_t cap,
                                   uint32_t *len);
+
+/* ---- BLA-PT: perturbation that skips iterations in bulk -------------------------------------------------------- */
+
+/* The BLA-PT calls (fr_precision above, "BLA-PT").  One road for both centres: `centre` non-NULL selects WIDE PT's orbits
+ * (pos_lo must then be NULL and cfg->pos is not read), otherwise the centre is PT's (cfg->pos, pos_lo), pos_lo NULL = (0, 0).
+ * bits: 0 = FR_BLA_DEFAULT_BITS, else 24 .. 53.  y0 == y1 and argument errors need no device.  The library builds the view's
+ * table on the host from the orbit PT's cache holds (computing it on a miss), uploads it once and keeps it per context beside
+ * the orbit, keyed by that orbit, D and bits: the same view with other rows or colours is served, anything else rebuilds.  PT
+ * and BLA-PT calls may alternate on one context.
+ * fr_render_rows_pt_bla(_device): the buffers, alignment and asynchrony of fr_render_rows_pt(_device).
+ * fr_escape_rows_pt_bla(_device): z is 2 doubles per pixel (re, im), as fr_escape_rows_pt / fr_escape_rows_device give it;
+ * fr_colour_rgb8 / fr_colour_rows_device over them reproduces the render.  With profiling on, fr_last_kernel_name reports
+ * escape_bla_kernel. */
+int fr_render_rows_pt_bla(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
+                          uint32_t y1, int channels, uint8_t *out, size_t out_len);
+int fr_render_rows_pt_bla_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits,
+                                 uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len, void *hip_stream);
+int fr_escape_rows_pt_bla(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
+                          uint32_t y1, double *z, uint32_t *iters);
+int fr_escape_rows_pt_bla_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits,
+                                 uint32_t y0, uint32_t y1, void *d_z, void *d_iters, void *hip_stream);
+/* Host only, no device: level `level` of the table of orbit `which` (0: R or V, 1: K, Julia only).  *len = n_level, or 0 past
+ * the top; min(*len, cap) entries are written to out as 5 doubles: A.re, A.im, B.re, B.im, r2. */
+int fr_debug_bla_table(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, int which,
+                       uint32_t level, double *out, size_t cap, uint32_t *len);
+/* On the device: over the pixels of rows [y0, y1), *passes = the passes through the BLA loop (each a plain step or one skip)
+ * and *steps = the nominal iterations (escape index + 1, or the cap): their ratio is what the skips save. */
+int fr_debug_bla_count(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
+                       uint32_t y1, uint64_t *passes, uint64_t *steps);
+/* Test hook: out[0] = bits of the context's cached table, out[1] = levels of X's table (level 0 included), out[2] = entries
+ * of all levels of X's and K's tables, out[3] = 1 if the last request built the table, 0 if it was served.  Zeros without a
+ * cached table.  Touches no device. */
+int fr_debug_bla_cache(uint32_t out[4]);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 

@@ -154,6 +154,14 @@ extern "C" {
     pub fn fr_escape_rows_pt_wide_state(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, z: *mut f64, iters: *mut u32, dz: *mut f64, m: *mut u32) -> c_int;
     pub fn fr_escape_extend_pt_wide(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, from_iterations: u32, z: *mut f64, iters: *mut u32, dz: *mut f64, m: *mut u32) -> c_int;
     pub fn fr_debug_reference_orbit_wide(cfg: *const fr_config, centre: *const fr_wide_centre, which: c_int, out: *mut f64, cap: usize, len: *mut u32) -> c_int;
+    // BLA-PT (include/fractal_hip.h): perturbation that skips iterations in bulk; centre non-null selects the wide road (pos_lo null then)
+    pub fn fr_render_rows_pt_bla(cfg: *const fr_config, pos_lo: *const fr_imaginary, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, channels: c_int, out: *mut u8, out_len: usize) -> c_int;
+    pub fn fr_render_rows_pt_bla_device(cfg: *const fr_config, pos_lo: *const fr_imaginary, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, channels: c_int, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_escape_rows_pt_bla(cfg: *const fr_config, pos_lo: *const fr_imaginary, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, z: *mut f64, iters: *mut u32) -> c_int;
+    pub fn fr_escape_rows_pt_bla_device(cfg: *const fr_config, pos_lo: *const fr_imaginary, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, d_z: *mut c_void, d_iters: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_debug_bla_table(cfg: *const fr_config, pos_lo: *const fr_imaginary, centre: *const fr_wide_centre, bits: c_int, which: c_int, level: u32, out: *mut f64, cap: usize, len: *mut u32) -> c_int;
+    pub fn fr_debug_bla_count(cfg: *const fr_config, pos_lo: *const fr_imaginary, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, passes: *mut u64, steps: *mut u64) -> c_int;
+    pub fn fr_debug_bla_cache(out: *mut u32) -> c_int;
 }
 
 /// Message of the last failing call on this thread.
