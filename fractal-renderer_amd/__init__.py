@@ -82,14 +82,6 @@ def split_dd(value):
     return hi, lo
 
 
-def _pos_lo(pos_lo):
-    """pos_lo argument -> (pointer for the C call, keep-alive); None = (0, 0), the C NULL"""
-    if pos_lo is None:
-        return None, None
-    lo = Imaginary(*(float(v) for v in pos_lo))
-    return C.byref(lo), lo
-
-
 class WideCentre:
     """The view centre of WIDE PT (include/fractal_hip.h, "WIDE PT"): per axis `words` little-endian uint64 words in two's
     complement, value I / 2^(64 words - 8) — up to 1016 bits where (pos, pos_lo) carries ~106.  Pass it as centre= to
@@ -148,16 +140,44 @@ class WideCentre:
         return _native.fr_wide_centre(self.words, self.re.ctypes.data_as(p64), self.im.ctypes.data_as(p64))
 
 
-def _wide(centre, precision, pos_lo=None, supersample=1):
-    """centre= argument -> (pointer for the C call, keep-alive)"""
-    if int(precision) != Precision.PT:
-        raise ValueError("centre= needs precision=Precision.PT")
-    if pos_lo is not None:
-        raise ValueError("centre= and pos_lo= exclude each other")
+def _deep_call(precision, pos_lo=None, centre=None, bla=None, supersample=1, opts=None):
+    """Which C family a call's keyword arguments select, in the order bla, centre, supersample, pos_lo:
+    (family, the family's leading arguments behind the config, what keeps their memory alive).
+      "bla"   (pos_lo pointer, centre pointer, bits)   the fr_*_pt_bla calls
+      "wide"  (centre pointer,)                        the fr_*_pt_wide calls
+      "ss"    (pos_lo pointer,)                        fr_render_rows_ss
+      "lo"    (pos_lo pointer,)                        the calls that take pos_lo
+      "plain" ()                                       pos_lo is None, the C NULL: the calls without one, or (None,)"""
+    if bla is not None:
+        if int(precision) != Precision.PT:
+            raise ValueError("bla= needs precision=Precision.PT")
+        if supersample != 1:
+            raise ValueError("supersample does not take bla=")
+        if opts is not None:
+            raise ValueError("bla= takes no opts: BLA-PT has one kernel")
+        bits = int(bla)
+        if bits != 0 and not 24 <= bits <= 53:
+            raise ValueError("bla= is None (off), 0 (%d bits) or 24 .. 53" % BLA_DEFAULT_BITS)
+    if centre is not None:
+        if int(precision) != Precision.PT:
+            raise ValueError("centre= needs precision=Precision.PT")
+        if pos_lo is not None:
+            raise ValueError("centre= and pos_lo= exclude each other")
+        if supersample != 1:
+            raise ValueError("supersample does not take centre= yet")
+        st = centre.c_struct()
+        if bla is not None:
+            return "bla", (None, C.byref(st), bits), (st, centre)
+        return "wide", (C.byref(st),), (st, centre)
+    lo = None if pos_lo is None else Imaginary(*(float(v) for v in pos_lo))
+    lo_ptr = None if lo is None else C.byref(lo)
+    if bla is not None:
+        return "bla", (lo_ptr, None, bits), lo
     if supersample != 1:
-        raise ValueError("supersample does not take centre= yet")
-    st = centre.c_struct()
-    return C.byref(st), (st, centre)
+        return "ss", (lo_ptr,), lo
+    if pos_lo is not None:
+        return "lo", (lo_ptr,), lo
+    return "plain", (), None
 
 
 def reference_orbit_wide(config, centre, which=0):
@@ -173,28 +193,10 @@ def reference_orbit_wide(config, centre, which=0):
 BLA_DEFAULT_BITS = _native.FR_BLA_DEFAULT_BITS
 
 
-def _bla_args(precision, pos_lo, centre, bla, supersample=1, opts=None):
-    """bla= argument -> (pos_lo pointer, centre pointer, bits, keep-alive) of the fr_*_pt_bla calls"""
-    if int(precision) != Precision.PT:
-        raise ValueError("bla= needs precision=Precision.PT")
-    if supersample != 1:
-        raise ValueError("supersample does not take bla=")
-    if opts is not None:
-        raise ValueError("bla= takes no opts: BLA-PT has one kernel")
-    bits = int(bla)
-    if bits != 0 and not 24 <= bits <= 53:
-        raise ValueError("bla= is None (off), 0 (%d bits) or 24 .. 53" % BLA_DEFAULT_BITS)
-    if centre is not None:
-        ptr, keep = _wide(centre, precision, pos_lo)
-        return None, ptr, bits, keep
-    lo, keep = _pos_lo(pos_lo)
-    return lo, None, bits, keep
-
-
 def bla_table(config, level, which=0, pos_lo=None, centre=None, bla=0):
     """fr_debug_bla_table: level `level` of the BLA-PT table of orbit `which` (0: R or V, 1: K, Julia only) on the host (no
     device needed): float64 [n_level, 5] = A.re, A.im, B.re, B.im, r2; empty past the top level."""
-    lo, ptr, bits, _keep = _bla_args(Precision.PT, pos_lo, centre, bla)
+    _, (lo, ptr, bits), _keep = _deep_call(Precision.PT, pos_lo, centre, bla)
     n = C.c_uint32(0)
     lib = _native.load()
     _native.check(lib.fr_debug_bla_table(C.byref(config), lo, ptr, bits, int(which), int(level), None, 0, C.byref(n)))
@@ -207,7 +209,7 @@ def bla_count(config, y0=0, y1=None, pos_lo=None, centre=None, bla=0):
     """fr_debug_bla_count over rows [y0, y1): (passes through the BLA loop, nominal iterations), summed over the pixels on
     the device; their ratio is what the skips save."""
     y1 = config.height if y1 is None else y1
-    lo, ptr, bits, _keep = _bla_args(Precision.PT, pos_lo, centre, bla)
+    _, (lo, ptr, bits), _keep = _deep_call(Precision.PT, pos_lo, centre, bla)
     passes, steps = C.c_uint64(0), C.c_uint64(0)
     _native.check(_native.load().fr_debug_bla_count(C.byref(config), lo, ptr, bits, y0, y1, C.byref(passes), C.byref(steps)))
     return passes.value, steps.value
@@ -303,13 +305,25 @@ def device_name():
 SS_MAX = 8  # FR_SS_MAX
 
 
-def _render_rows_ss(config, y0, y1, precision, out, channels, opts, pos_lo, supersample):
-    """fr_render_rows_ss: rows [y0, y1) with supersample x supersample samples per pixel, box-filtered on the device"""
-    lo, _keep = _pos_lo(pos_lo)
-    _native.check(
-        _native.load().fr_render_rows_ss(C.byref(config), int(precision), lo, int(supersample), y0, y1, channels,
-                                         out.ctypes.data, out.nbytes, C.byref(opts) if opts is not None else None)
-    )
+def _render_rows(config, y0, y1, channels, out, precision, opts, pos_lo, supersample, centre, bla):
+    """rows [y0, y1) into `out` as `channels` bytes per pixel, by the C row render of the arguments' family"""
+    lib, cfg = _native.load(), C.byref(config)
+    family, pre, _keep = _deep_call(precision, pos_lo, centre, bla, supersample, opts)
+    o = C.byref(opts) if opts is not None else None
+    tail = (y0, y1, channels, out.ctypes.data, out.nbytes)
+    if family == "bla":
+        rc = lib.fr_render_rows_pt_bla(cfg, *pre, *tail)
+    elif family == "wide":
+        rc = lib.fr_render_rows_pt_wide(cfg, *pre, *tail)
+    elif family == "ss":  # s x s samples per pixel, box-filtered on the device
+        rc = lib.fr_render_rows_ss(cfg, int(precision), *pre, int(supersample), *tail, o)
+    elif family == "lo":
+        rc = _render_rows_lo(precision)(cfg, *pre, *tail)
+    elif channels == 4:
+        rc = lib.fr_render_rows_rgba8(cfg, int(precision), y0, y1, out.ctypes.data, out.nbytes)
+    else:
+        rc = lib.fr_render_rows_rgb8_opts(cfg, int(precision), y0, y1, out.ctypes.data, out.nbytes, o)
+    _native.check(rc)
     return out
 
 
@@ -349,26 +363,7 @@ def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None,
     (0: BLA_DEFAULT_BITS), PT with iterations skipped in bulk — an approximation, defined in include/fractal_hip.h, "BLA-PT"."""
     if out is None:
         out = np.empty((max(int(y1) - int(y0), 0), config.width, 3), dtype=np.uint8)
-    if bla is not None:
-        lo, ptr, bits, _keep = _bla_args(precision, pos_lo, centre, bla, supersample, opts)
-        _native.check(_native.load().fr_render_rows_pt_bla(C.byref(config), lo, ptr, bits, y0, y1, 3, out.ctypes.data, out.nbytes))
-        return out
-    if centre is not None:
-        ptr, _keep = _wide(centre, precision, pos_lo, supersample)
-        _native.check(_native.load().fr_render_rows_pt_wide(C.byref(config), ptr, y0, y1, 3, out.ctypes.data, out.nbytes))
-        return out
-    if supersample != 1:
-        return _render_rows_ss(config, y0, y1, precision, out, 3, opts, pos_lo, supersample)
-    if pos_lo is not None:
-        render = _render_rows_lo(precision)
-        lo, _keep = _pos_lo(pos_lo)
-        _native.check(render(C.byref(config), lo, y0, y1, 3, out.ctypes.data, out.nbytes))
-        return out
-    _native.check(
-        _native.load().fr_render_rows_rgb8_opts(C.byref(config), int(precision), y0, y1, out.ctypes.data, out.nbytes,
-                                                C.byref(opts) if opts is not None else None)
-    )
-    return out
+    return _render_rows(config, y0, y1, 3, out, precision, opts, pos_lo, supersample, centre, bla)
 
 
 def get_image(config, precision=Precision.F64, pos_lo=None, supersample=1, centre=None, bla=None):
@@ -377,17 +372,10 @@ def get_image(config, precision=Precision.F64, pos_lo=None, supersample=1, centr
     per-pixel function returns BLACK for it (calc/src/lib.rs:211) and so does this.
     pos_lo: see get_image_rows (Precision.DD or Precision.PT only).  supersample, centre, bla: see get_image_rows."""
     out = np.empty((config.height, config.width, 3), dtype=np.uint8)
-    if bla is not None:
-        return get_image_rows(config, 0, config.height, precision, out, pos_lo=pos_lo, supersample=supersample, centre=centre,
-                              bla=bla)
-    if centre is not None:
-        return get_image_rows(config, 0, config.height, precision, out, pos_lo=pos_lo, supersample=supersample, centre=centre)
-    if supersample != 1:
-        return _render_rows_ss(config, 0, config.height, precision, out, 3, None, pos_lo, supersample)
-    if int(precision) == Precision.F64 and pos_lo is None:
+    if bla is None and centre is None and supersample == 1 and pos_lo is None and int(precision) == Precision.F64:
         _native.check(_native.load().fr_render_rgb8(C.byref(config), out.ctypes.data, out.nbytes))
         return out
-    return get_image_rows(config, 0, config.height, precision, out, pos_lo=pos_lo)
+    return _render_rows(config, 0, config.height, 3, out, precision, None, pos_lo, supersample, centre, bla)
 
 
 def _dd_only(precision):
@@ -419,27 +407,7 @@ def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None, super
     supersample, centre, bla: see get_image_rows."""
     if out is None:
         out = np.empty((config.height, config.width, 4), dtype=np.uint8)
-    if bla is not None:
-        lo, ptr, bits, _keep = _bla_args(precision, pos_lo, centre, bla, supersample)
-        _native.check(_native.load().fr_render_rows_pt_bla(C.byref(config), lo, ptr, bits, 0, config.height, 4, out.ctypes.data,
-                                                           out.nbytes))
-        return out
-    if centre is not None:
-        ptr, _keep = _wide(centre, precision, pos_lo, supersample)
-        _native.check(_native.load().fr_render_rows_pt_wide(C.byref(config), ptr, 0, config.height, 4, out.ctypes.data, out.nbytes))
-        return out
-    if supersample != 1:
-        return _render_rows_ss(config, 0, config.height, precision, out, 4, None, pos_lo, supersample)
-    if pos_lo is not None:
-        render = _render_rows_lo(precision)
-        lo, _keep = _pos_lo(pos_lo)
-        _native.check(render(C.byref(config), lo, 0, config.height, 4, out.ctypes.data, out.nbytes))
-        return out
-    _native.check(
-        _native.load().fr_render_rows_rgba8(C.byref(config), int(precision), 0, config.height, out.ctypes.data,
-                                            out.nbytes)
-    )
-    return out
+    return _render_rows(config, 0, config.height, 4, out, precision, None, pos_lo, supersample, centre, bla)
 
 
 def get_recursive_pixel(config, x, y, precision=Precision.F64):
@@ -481,41 +449,26 @@ def escape_rows(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, wit
     centre: a WideCentre (Precision.PT only, exclusive with pos_lo): fr_escape_rows_pt_wide.
     bla (Precision.PT only): see get_image_rows; fr_escape_rows_pt_bla."""
     y1 = config.height if y1 is None else y1
-    if bla is not None:
-        if with_lo:
-            raise ValueError("with_lo needs precision=Precision.DD")
-        lo, ptr, bits, _keep = _bla_args(precision, pos_lo, centre, bla)
-        z = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
-        it = np.empty((y1 - y0, config.width), dtype=np.uint32)
-        _native.check(_native.load().fr_escape_rows_pt_bla(C.byref(config), lo, ptr, bits, y0, y1, z.ctypes.data, it.ctypes.data))
-        return z, it
-    if centre is not None:
-        if with_lo:
-            raise ValueError("with_lo needs precision=Precision.DD")
-        ptr, _keep = _wide(centre, precision, pos_lo)
-        z = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
-        it = np.empty((y1 - y0, config.width), dtype=np.uint32)
-        _native.check(_native.load().fr_escape_rows_pt_wide(C.byref(config), ptr, y0, y1, z.ctypes.data, it.ctypes.data))
-        return z, it
-    if pos_lo is not None and not with_lo and int(precision) == Precision.PT:
-        lo, _keep = _pos_lo(pos_lo)
-        z = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
-        it = np.empty((y1 - y0, config.width), dtype=np.uint32)
-        _native.check(_native.load().fr_escape_rows_pt(C.byref(config), lo, y0, y1, z.ctypes.data, it.ctypes.data))
-        return z, it
-    if pos_lo is not None or with_lo:
+    if with_lo and (bla is not None or centre is not None):
+        raise ValueError("with_lo needs precision=Precision.DD")
+    lib = _native.load()
+    family, pre, _keep = _deep_call(precision, pos_lo, centre, bla)
+    zw = 2
+    if family == "bla":
+        fn = lib.fr_escape_rows_pt_bla
+    elif family == "wide":
+        fn = lib.fr_escape_rows_pt_wide
+    elif family == "lo" and not with_lo and int(precision) == Precision.PT:
+        fn = lib.fr_escape_rows_pt
+    elif family == "lo" or with_lo:
         _dd_only(precision)
-        lo, _keep = _pos_lo(pos_lo)
-        z = np.empty((y1 - y0, config.width, 4), dtype=np.float64)
-        it = np.empty((y1 - y0, config.width), dtype=np.uint32)
-        _native.check(_native.load().fr_escape_rows_dd(C.byref(config), lo, y0, y1, z.ctypes.data, it.ctypes.data))
-        return (z if with_lo else np.ascontiguousarray(z[..., 0::2])), it
-    z = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
+        fn, pre, zw = lib.fr_escape_rows_dd, pre or (None,), 4
+    else:
+        fn, pre = lib.fr_escape_rows, (int(precision),)
+    z = np.empty((y1 - y0, config.width, zw), dtype=np.float64)
     it = np.empty((y1 - y0, config.width), dtype=np.uint32)
-    _native.check(
-        _native.load().fr_escape_rows(C.byref(config), int(precision), y0, y1, z.ctypes.data, it.ctypes.data)
-    )
-    return z, it
+    _native.check(fn(C.byref(config), *pre, y0, y1, z.ctypes.data, it.ctypes.data))
+    return (z if zw == 2 or with_lo else np.ascontiguousarray(z[..., 0::2])), it
 
 
 def _stream(stream):
@@ -527,6 +480,20 @@ def _rows(config, y0, y1):
     return int(y0), int(config.height if y1 is None else y1)
 
 
+def _lo(pos_lo):
+    """pos_lo argument -> (pointer for the C call, keep-alive); None = (0, 0), the C NULL"""
+    _, pre, keep = _deep_call(Precision.DD, pos_lo)
+    return (pre or (None,))[0], keep
+
+
+def _pt_state_fn(name, device, pos_lo, centre):
+    """the PT state call `name` ("fr_escape_rows_pt%s_state" / "fr_escape_extend_pt%s"; %s: "_wide" with a centre) in its host or
+    device form, with its centre argument and what keeps it alive"""
+    family, pre, keep = _deep_call(Precision.PT, pos_lo, centre)
+    fn = getattr(_native.load(), name % ("_wide" if family == "wide" else "") + ("_device" if device else ""))
+    return fn, (pre or (None,))[0], keep
+
+
 def escape_rows_device(config, z_ptr, iters_ptr, y0=0, y1=None, precision=Precision.F64, pos_lo=None, z_width=2, stream=None,
                        opts=None):
     """fr_escape_rows_device: recursive() results of rows [y0, y1) into DEVICE arrays, asynchronously on `stream`.
@@ -534,7 +501,7 @@ def escape_rows_device(config, z_ptr, iters_ptr, y0=0, y1=None, precision=Precis
     z_width=4 (Precision.DD only) keeps the low parts.  This is the state a GUI keeps per view: 20 bytes per pixel, 36 for
     DD with its low parts."""
     y0, y1 = _rows(config, y0, y1)
-    lo, _keep = _pos_lo(pos_lo)
+    lo, _keep = _lo(pos_lo)
     _native.check(_native.load().fr_escape_rows_device(C.byref(config), int(precision), lo, y0, y1, int(z_width), z_ptr or None,
                                                        iters_ptr or None, _stream(stream), C.byref(opts) if opts is not None else None))
 
@@ -546,7 +513,7 @@ def extend_rows_device(config, z_ptr, iters_ptr, from_iterations, y0=0, y1=None,
     view at the lower cap (the library cannot check that); afterwards they hold the render at config.iterations, bit for
     bit.  Precision.DD needs z_width=4; Precision.PT is refused."""
     y0, y1 = _rows(config, y0, y1)
-    lo, _keep = _pos_lo(pos_lo)
+    lo, _keep = _lo(pos_lo)
     _native.check(_native.load().fr_escape_extend_device(C.byref(config), int(precision), lo, y0, y1, int(from_iterations),
                                                          int(z_width), z_ptr or None, iters_ptr or None, _stream(stream),
                                                          C.byref(opts) if opts is not None else None))
@@ -563,7 +530,7 @@ def extend_rows(config, z, iters, from_iterations, precision=Precision.F64, pos_
     shape = (max(y1 - y0, 0), config.width)
     if z.shape != shape + (zw,) or iters.shape != shape:
         raise ValueError("z must be [rows, width, %d] and iters [rows, width] for rows [y0, y1)" % zw)
-    lo, _keep = _pos_lo(pos_lo)
+    lo, _keep = _lo(pos_lo)
     _native.check(_native.load().fr_escape_extend(C.byref(config), int(precision), lo, y0, y1, int(from_iterations), zw,
                                                   z.ctypes.data, iters.ctypes.data))
     return z, iters
@@ -577,14 +544,8 @@ def escape_rows_pt_state(config, pos_lo=None, y0=0, y1=None, centre=None):
     shape = (max(y1 - y0, 0), config.width)
     z, dz = np.empty(shape + (2,), dtype=np.float64), np.empty(shape + (2,), dtype=np.float64)
     it, m = np.empty(shape, dtype=np.uint32), np.empty(shape, dtype=np.uint32)
-    if centre is not None:
-        ptr, _keep = _wide(centre, Precision.PT, pos_lo)
-        _native.check(_native.load().fr_escape_rows_pt_wide_state(C.byref(config), ptr, y0, y1, z.ctypes.data, it.ctypes.data,
-                                                                  dz.ctypes.data, m.ctypes.data))
-        return z, it, dz, m
-    lo, _keep = _pos_lo(pos_lo)
-    _native.check(_native.load().fr_escape_rows_pt_state(C.byref(config), lo, y0, y1, z.ctypes.data, it.ctypes.data,
-                                                         dz.ctypes.data, m.ctypes.data))
+    fn, where, _keep = _pt_state_fn("fr_escape_rows_pt%s_state", False, pos_lo, centre)
+    _native.check(fn(C.byref(config), where, y0, y1, z.ctypes.data, it.ctypes.data, dz.ctypes.data, m.ctypes.data))
     return z, it, dz, m
 
 
@@ -598,14 +559,9 @@ def extend_rows_pt(config, z, iters, dz, m, from_iterations, pos_lo=None, y0=0, 
     iters, m = np.array(iters, dtype=np.uint32, order="C"), np.array(m, dtype=np.uint32, order="C")
     if z.shape != shape + (2,) or dz.shape != shape + (2,) or iters.shape != shape or m.shape != shape:
         raise ValueError("z and dz must be [rows, width, 2], iters and m [rows, width] for rows [y0, y1)")
-    if centre is not None:
-        ptr, _keep = _wide(centre, Precision.PT, pos_lo)
-        _native.check(_native.load().fr_escape_extend_pt_wide(C.byref(config), ptr, y0, y1, int(from_iterations), z.ctypes.data,
-                                                              iters.ctypes.data, dz.ctypes.data, m.ctypes.data))
-        return z, iters, dz, m
-    lo, _keep = _pos_lo(pos_lo)
-    _native.check(_native.load().fr_escape_extend_pt(C.byref(config), lo, y0, y1, int(from_iterations), z.ctypes.data,
-                                                     iters.ctypes.data, dz.ctypes.data, m.ctypes.data))
+    fn, where, _keep = _pt_state_fn("fr_escape_extend_pt%s", False, pos_lo, centre)
+    _native.check(fn(C.byref(config), where, y0, y1, int(from_iterations), z.ctypes.data, iters.ctypes.data, dz.ctypes.data,
+                     m.ctypes.data))
     return z, iters, dz, m
 
 
@@ -613,15 +569,8 @@ def escape_rows_pt_state_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, y0=0, y
     """fr_escape_rows_pt_state_device: the Precision.PT state of rows [y0, y1) into DEVICE arrays (raw pointers as ints:
     z, dz 2 float64 per pixel, iters, m one uint32), asynchronously on `stream`: 40 bytes per pixel."""
     y0, y1 = _rows(config, y0, y1)
-    if centre is not None:
-        ptr, _keep = _wide(centre, Precision.PT, pos_lo)
-        _native.check(_native.load().fr_escape_rows_pt_wide_state_device(C.byref(config), ptr, y0, y1, z_ptr or None,
-                                                                         iters_ptr or None, dz_ptr or None, m_ptr or None,
-                                                                         _stream(stream)))
-        return
-    lo, _keep = _pos_lo(pos_lo)
-    _native.check(_native.load().fr_escape_rows_pt_state_device(C.byref(config), lo, y0, y1, z_ptr or None, iters_ptr or None,
-                                                                dz_ptr or None, m_ptr or None, _stream(stream)))
+    fn, where, _keep = _pt_state_fn("fr_escape_rows_pt%s_state", True, pos_lo, centre)
+    _native.check(fn(C.byref(config), where, y0, y1, z_ptr or None, iters_ptr or None, dz_ptr or None, m_ptr or None, _stream(stream)))
 
 
 def extend_rows_pt_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, from_iterations, y0=0, y1=None, pos_lo=None, stream=None,
@@ -629,15 +578,9 @@ def extend_rows_pt_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, from_iteratio
     """fr_escape_extend_pt_device: raise the cap of the stored Precision.PT state of rows [y0, y1) from `from_iterations` to
     config.iterations IN PLACE, asynchronously on `stream`; the view's reference orbit is continued, not recomputed."""
     y0, y1 = _rows(config, y0, y1)
-    if centre is not None:
-        ptr, _keep = _wide(centre, Precision.PT, pos_lo)
-        _native.check(_native.load().fr_escape_extend_pt_wide_device(C.byref(config), ptr, y0, y1, int(from_iterations),
-                                                                     z_ptr or None, iters_ptr or None, dz_ptr or None,
-                                                                     m_ptr or None, _stream(stream)))
-        return
-    lo, _keep = _pos_lo(pos_lo)
-    _native.check(_native.load().fr_escape_extend_pt_device(C.byref(config), lo, y0, y1, int(from_iterations), z_ptr or None,
-                                                            iters_ptr or None, dz_ptr or None, m_ptr or None, _stream(stream)))
+    fn, where, _keep = _pt_state_fn("fr_escape_extend_pt%s", True, pos_lo, centre)
+    _native.check(fn(C.byref(config), where, y0, y1, int(from_iterations), z_ptr or None, iters_ptr or None, dz_ptr or None,
+                     m_ptr or None, _stream(stream)))
 
 
 def pt_orbit_cache():

@@ -584,6 +584,15 @@ void fill_params(const fr_config *cfg, const Opts &o, fr_kparams &p) {
     p.filt_lo32 = (p.colour_filter32 && lo < 1e30) ? std::nextafterf((float)lo, INFINITY) : INFINITY;
 }
 
+void rows_params(const fr_config *cfg, const Opts &o, uint32_t y0, uint32_t y1, unsigned channels, fr_kparams &p) {
+    fill_params(cfg, o, p);
+    p.nrows = y1 - y0;
+    p.y_first = y0;
+    p.block_rows = p.nrows;
+    p.y_stride = 0;
+    p.out_rgba = channels == 4 ? 1u : 0u;
+}
+
 /* coord_to_space — calc/src/lib.rs:182-184 — evaluated on the host ONLY to bound |c| over a launch
  * (the kernels compute every coordinate themselves). */
 static double host_coord(double coord, double max, double offset, double pos, double scale) {
@@ -682,10 +691,15 @@ void plan_loop(const fr_config *cfg, int precision, const Opts &o, fr_kparams &p
     }
 }
 
-static int check_rows(const fr_config *cfg, uint32_t y0, uint32_t y1) {
+int check_rows(const fr_config *cfg, uint32_t y0, uint32_t y1) {
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
     if (y0 > y1) return fail(FR_ERR_INVALID_ARGUMENT, "y0 > y1");
     if (y1 > cfg->height) return fail(FR_ERR_INVALID_ARGUMENT, "y1 > height");
+    return FR_OK;
+}
+
+int check_channels(int channels) {
+    if (channels != 3 && channels != 4) return fail(FR_ERR_INVALID_ARGUMENT, "channels must be 3 (RGB) or 4 (RGBA)");
     return FR_OK;
 }
 
@@ -744,9 +758,11 @@ int check_precision_lo(const fr_config *cfg, int precision, const fr_imaginary *
 
 int check_precision_or_deep(const fr_config *cfg, int precision) { return check_precision_lo(cfg, precision, nullptr); }
 
-/* profiling (fr_set_profiling) around the launches of one device-pointer call on `stream`: events before and after, and
- * the name fr_last_kernel_name reports */
-static int prof_begin(hipStream_t stream) {
+int Centre::check(const fr_config *cfg, int precision) const {
+    return wide ? check_pt_wide(cfg, wide) : check_precision_lo(cfg, precision, pos_lo);
+}
+
+int prof_begin(hipStream_t stream) {
     Profiling &pr = tl_prof;
     if (!pr.enabled) return FR_OK;
     if (!pr.e0) {
@@ -756,7 +772,7 @@ static int prof_begin(hipStream_t stream) {
     HIP_TRY(hipEventRecord(pr.e0, stream));
     return FR_OK;
 }
-static int prof_end(hipStream_t stream, const char *kname) {
+int prof_end(hipStream_t stream, const char *kname) {
     Profiling &pr = tl_prof;
     if (!pr.enabled) return FR_OK;
     HIP_TRY(hipEventRecord(pr.e1, stream));
@@ -765,26 +781,20 @@ static int prof_end(hipStream_t stream, const char *kname) {
     return FR_OK;
 }
 
-int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0,
-                       uint32_t y1, unsigned bpp, void *d_out, hipStream_t stream, const fr_wide_centre *wide) {
+int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const Centre &c, const Opts &o, uint32_t y0, uint32_t y1,
+                       unsigned bpp, void *d_out, hipStream_t stream) {
     fr_kparams p;
-    fill_params(cfg, o, p); /* the colour constants; no loop plan, no kernel choice, no view sample */
-    p.nrows = y1 - y0;
-    p.y_first = y0;
-    p.block_rows = p.nrows;
-    p.y_stride = 0;
-    p.out_rgba = bpp == 4 ? 1u : 0u;
+    rows_params(cfg, o, y0, y1, bpp, p); /* the colour constants; no loop plan, no kernel choice, no view sample */
     fr_kout out{};
     out.rgb = static_cast<uint8_t *>(d_out);
     int prc = prof_begin(stream);
     if (prc != FR_OK) return prc;
     const char *kname = "";
     if (precision == FR_PRECISION_PT) {
-        const int rc = launch_pt(ctx, cfg, pos_lo, p, FR_OUT_RGB, out, stream, &kname, wide);
+        const int rc = launch_pt(ctx, cfg, c, p, FR_OUT_RGB, out, stream, &kname);
         if (rc != FR_OK) return rc;
     } else {
-        HIP_TRY(fr_launch_escape_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, FR_OUT_RGB, out, false, stream,
-                                    &kname));
+        HIP_TRY(fr_launch_escape_dd(p, c.lo_re(), c.lo_im(), FR_OUT_RGB, out, false, stream, &kname));
     }
     return prof_end(stream, kname);
 }
@@ -1006,11 +1016,7 @@ void decide_kernel(Ctx &ctx, const fr_config *cfg, int precision, uint32_t y0, u
                    bool allow_async) {
     if (o.tile != 0 || o.kernel_hint != -2 || y1 <= y0 || cfg->width == 0) return;
     fr_kparams p;
-    fill_params(cfg, o, p);
-    p.nrows = y1 - y0;
-    p.y_first = y0;
-    p.block_rows = p.nrows;
-    p.y_stride = 0;
+    rows_params(cfg, o, y0, y1, 0, p);
     plan_loop(cfg, precision, o, p);
     bool one_band = false, no_spec = false;
     uint32_t strip_tiles = 0;
@@ -1160,12 +1166,89 @@ int render_block_cyclic(Ctx &ctx, const fr_config *cfg, int precision, const Opt
         return fail(FR_ERR_BUFFER_TOO_SMALL, dest_is_image ? "out_len < 3*width*height" : "out_len < 3*width*rows");
     fr_kparams p;
     fill_params(cfg, o, p);
-    p.nrows = (uint32_t)rows;
+    p.nrows = (uint32_t)rows; /* not rows_params: blocks of block_rows rows, a stride apart */
     p.block_rows = block_rows;
     p.y_first = first_block * block_rows;
     p.y_stride = block_rows * block_stride;
     p.out_in_place = dest_is_image ? 1u : 0u;
     return render_device(ctx, cfg, p, precision, o, d_out, stream);
+}
+
+/* ---- the row calls' shared bodies (the entry points are below and, for FR_PRECISION_PT's own calls, in fr_pt.hip) ------- */
+
+int render_rows_device(const fr_config *cfg, int precision, const Centre &c, uint32_t y0, uint32_t y1, void *d_out, size_t out_len,
+                       void *hip_stream, unsigned bytes_per_pixel, const fr_render_opts *opts) {
+    int rc = check_rows(cfg, y0, y1);
+    if (rc == FR_OK) rc = c.check(cfg, precision);
+    Opts o;
+    if (rc == FR_OK) rc = resolve_opts(opts, o);
+    if (rc != FR_OK) return rc;
+    const size_t need = (size_t)bytes_per_pixel * cfg->width * (size_t)(y1 - y0);
+    if (need == 0) return FR_OK;
+    if (!d_out) return fail(FR_ERR_INVALID_ARGUMENT, "d_out is NULL");
+    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < bytes_per_pixel*width*(y1-y0)");
+    if (bytes_per_pixel == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "RGBA8 output must be 4-byte aligned");
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    if (precision == FR_PRECISION_DD || precision == FR_PRECISION_PT)
+        return render_deep_device(*ctx, precision, cfg, c, o, y0, y1, bytes_per_pixel, d_out, static_cast<hipStream_t>(hip_stream));
+    fr_kparams p;
+    rows_params(cfg, o, y0, y1, bytes_per_pixel, p);
+    return render_device(*ctx, cfg, p, precision, o, d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+/* the escape launch of the grid set in `p`, whatever the precision; `zw` doubles of z per pixel (2: re, im — DD: the hi
+ * parts; 4: DD with the lo parts) */
+static int launch_escape_rows(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const Opts &o, fr_kparams &p, unsigned zw,
+                              const fr_kout &ko, hipStream_t stream, const char **kname) {
+    if (precision == FR_PRECISION_PT) return launch_pt(ctx, cfg, c, p, FR_OUT_ESCAPE, ko, stream, kname);
+    if (precision == FR_PRECISION_DD) {
+        HIP_TRY(fr_launch_escape_dd(p, c.lo_re(), c.lo_im(), FR_OUT_ESCAPE, ko, zw == 4, stream, kname));
+    } else {
+        plan_loop(cfg, precision, o, p);
+        HIP_TRY(fr_launch_escape(p, precision, FR_OUT_ESCAPE, ko, o.tile, stream, kname));
+    }
+    return FR_OK;
+}
+
+/* fr_escape_rows, fr_escape_rows_dd, fr_escape_rows_pt and fr_escape_rows_pt_wide */
+int escape_rows(const fr_config *cfg, int precision, const Centre &c, uint32_t y0, uint32_t y1, double *z, uint32_t *iters,
+                unsigned zw) {
+    int rc = check_rows(cfg, y0, y1);
+    if (rc == FR_OK) rc = c.check(cfg, precision);
+    if (rc != FR_OK) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    if (npx == 0 || (!z && !iters)) return FR_OK;
+    return host_raw(z, npx * zw * sizeof(double), iters, npx * sizeof(uint32_t), nullptr, nullptr, false,
+                    [&](Ctx &ctx, double *d_z, uint32_t *d_iters, double *, uint32_t *, hipStream_t stream) {
+                        const Opts o = default_opts();
+                        fr_kparams p;
+                        rows_params(cfg, o, y0, y1, 0, p);
+                        fr_kout ko{};
+                        ko.z = d_z;
+                        ko.iters = d_iters;
+                        return launch_escape_rows(ctx, cfg, precision, c, o, p, zw, ko, stream, nullptr);
+                    });
+}
+
+/* what escape_rows() launches, on the caller's stream into the caller's arrays, between the profiling events: no scratch, no
+ * copy, no ctx->mu */
+static int escape_rows_launch(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const Opts &o, uint32_t y0, uint32_t y1,
+                              unsigned zw, double *d_z, uint32_t *d_iters, hipStream_t stream) {
+    fr_kparams p;
+    rows_params(cfg, o, y0, y1, 0, p);
+    fr_kout ko{};
+    ko.z = d_z;
+    ko.iters = d_iters;
+    int rc = prof_begin(stream);
+    if (rc != FR_OK) return rc;
+    const char *kname = "";
+    rc = launch_escape_rows(ctx, cfg, precision, c, o, p, zw, ko, stream, &kname);
+    if (rc != FR_OK) return rc;
+    return prof_end(stream, kname);
 }
 
 }  // namespace fr
@@ -1272,55 +1355,24 @@ void fr_render_opts_init(fr_render_opts *opts) {
 
 /* ---- device-pointer renders: asynchronous, lock-free apart from the palette slot ring ---------- */
 
-static int render_rows_device(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, void *d_out,
-                              size_t out_len, void *hip_stream, unsigned bytes_per_pixel, const fr_render_opts *opts,
-                              const fr_imaginary *pos_lo = nullptr, const fr_wide_centre *wide = nullptr) {
-    int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = wide ? check_pt_wide(cfg, wide) : check_precision_lo(cfg, precision, pos_lo);
-    Opts o;
-    if (rc == FR_OK) rc = resolve_opts(opts, o);
-    if (rc != FR_OK) return rc;
-    const size_t need = (size_t)bytes_per_pixel * cfg->width * (size_t)(y1 - y0);
-    if (need == 0) return FR_OK;
-    if (!d_out) return fail(FR_ERR_INVALID_ARGUMENT, "d_out is NULL");
-    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < bytes_per_pixel*width*(y1-y0)");
-    if (bytes_per_pixel == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u))
-        return fail(FR_ERR_INVALID_ARGUMENT, "RGBA8 output must be 4-byte aligned");
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    if (precision == FR_PRECISION_DD || precision == FR_PRECISION_PT)
-        return render_deep_device(*ctx, precision, cfg, pos_lo, o, y0, y1, bytes_per_pixel, d_out,
-                                  static_cast<hipStream_t>(hip_stream), wide);
-    fr_kparams p;
-    fill_params(cfg, o, p);
-    p.nrows = y1 - y0;
-    p.y_first = y0;
-    p.block_rows = p.nrows;
-    p.y_stride = 0;
-    p.out_rgba = bytes_per_pixel == 4 ? 1u : 0u;
-    return render_device(*ctx, cfg, p, precision, o, d_out, static_cast<hipStream_t>(hip_stream));
-}
-
 int fr_render_rows_rgb8_device_opts(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, void *d_out,
                                     size_t out_len, void *hip_stream, const fr_render_opts *opts) {
-    return render_rows_device(cfg, precision, y0, y1, d_out, out_len, hip_stream, 3, opts);
+    return render_rows_device(cfg, precision, Centre{}, y0, y1, d_out, out_len, hip_stream, 3, opts);
 }
 
 int fr_render_rows_rgba8_device_opts(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, void *d_out,
                                      size_t out_len, void *hip_stream, const fr_render_opts *opts) {
-    return render_rows_device(cfg, precision, y0, y1, d_out, out_len, hip_stream, 4, opts);
+    return render_rows_device(cfg, precision, Centre{}, y0, y1, d_out, out_len, hip_stream, 4, opts);
 }
 
 int fr_render_rows_rgb8_device(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, void *d_out,
                                size_t out_len, void *hip_stream) {
-    return render_rows_device(cfg, precision, y0, y1, d_out, out_len, hip_stream, 3, nullptr);
+    return render_rows_device(cfg, precision, Centre{}, y0, y1, d_out, out_len, hip_stream, 3, nullptr);
 }
 
 int fr_render_rows_rgba8_device(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, void *d_out,
                                 size_t out_len, void *hip_stream) {
-    return render_rows_device(cfg, precision, y0, y1, d_out, out_len, hip_stream, 4, nullptr);
+    return render_rows_device(cfg, precision, Centre{}, y0, y1, d_out, out_len, hip_stream, 4, nullptr);
 }
 
 uint64_t fr_block_cyclic_rows(uint32_t height, uint32_t block_rows, uint32_t first_block, uint32_t block_stride) {
@@ -1382,19 +1434,10 @@ int fr_render_block_cyclic_rgb8(const fr_config *cfg, int precision, uint32_t bl
     if (need == 0 || rc != FR_OK) return rc;
     if (!out) return fail(FR_ERR_INVALID_ARGUMENT, "out is NULL");
     if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < 3*width*rows");
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    rc = ctx->reserve(ctx->rgb, need);
-    if (rc != FR_OK) return rc;
-    rc = render_block_cyclic(*ctx, cfg, precision, default_opts(), block_rows, first_block, block_stride, 0, 0,
-                             ctx->rgb.ptr, need, ctx->stream, nullptr);
-    if (rc != FR_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FR_OK;
+    return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) {
+        return render_block_cyclic(ctx, cfg, precision, default_opts(), block_rows, first_block, block_stride, 0, 0, d_out, need,
+                                   stream, nullptr);
+    });
 }
 
 int fr_render_rows_rgb8_opts(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint8_t *out,
@@ -1411,37 +1454,32 @@ int fr_render_rows_rgba8(const fr_config *cfg, int precision, uint32_t y0, uint3
     return fr_host_render_rows(cfg, precision, y0, y1, out, out_len, 4, nullptr);
 }
 
-static int dd_channels(int channels) {
-    if (channels != 3 && channels != 4) return fail(FR_ERR_INVALID_ARGUMENT, "channels must be 3 (RGB) or 4 (RGBA)");
-    return FR_OK;
-}
-
 int fr_render_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
                       uint8_t *out, size_t out_len) {
-    const int rc = dd_channels(channels);
+    const int rc = check_channels(channels);
     if (rc != FR_OK) return rc;
-    return fr_host_render_rows_deep(cfg, FR_PRECISION_DD, pos_lo, y0, y1, out, out_len, (unsigned)channels, nullptr);
+    return fr_host_render_rows_deep(cfg, FR_PRECISION_DD, Centre{pos_lo, nullptr}, y0, y1, out, out_len, (unsigned)channels, nullptr);
 }
 
 int fr_render_rows_dd_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
                              void *d_out, size_t out_len, void *hip_stream) {
-    const int rc = dd_channels(channels);
+    const int rc = check_channels(channels);
     if (rc != FR_OK) return rc;
-    return render_rows_device(cfg, FR_PRECISION_DD, y0, y1, d_out, out_len, hip_stream, (unsigned)channels, nullptr, pos_lo);
+    return render_rows_device(cfg, FR_PRECISION_DD, Centre{pos_lo, nullptr}, y0, y1, d_out, out_len, hip_stream, (unsigned)channels, nullptr);
 }
 
 int fr_render_rows_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
                       uint8_t *out, size_t out_len) {
-    const int rc = dd_channels(channels);
+    const int rc = check_channels(channels);
     if (rc != FR_OK) return rc;
-    return fr_host_render_rows_deep(cfg, FR_PRECISION_PT, pos_lo, y0, y1, out, out_len, (unsigned)channels, nullptr);
+    return fr_host_render_rows_deep(cfg, FR_PRECISION_PT, Centre{pos_lo, nullptr}, y0, y1, out, out_len, (unsigned)channels, nullptr);
 }
 
 int fr_render_rows_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, int channels,
                              void *d_out, size_t out_len, void *hip_stream) {
-    const int rc = dd_channels(channels);
+    const int rc = check_channels(channels);
     if (rc != FR_OK) return rc;
-    return render_rows_device(cfg, FR_PRECISION_PT, y0, y1, d_out, out_len, hip_stream, (unsigned)channels, nullptr, pos_lo);
+    return render_rows_device(cfg, FR_PRECISION_PT, Centre{pos_lo, nullptr}, y0, y1, d_out, out_len, hip_stream, (unsigned)channels, nullptr);
 }
 
 int fr_render_rgb8(const fr_config *cfg, uint8_t *out, size_t out_len) {
@@ -1473,7 +1511,7 @@ int fr_pixel_p(const fr_config *cfg, int precision, uint32_t x, uint32_t y, fr_r
     if (precision == FR_PRECISION_DD) {
         HIP_TRY(fr_launch_escape_dd(p, 0.0, 0.0, FR_OUT_RGB, ko, false, ctx->stream, nullptr));
     } else if (precision == FR_PRECISION_PT) {
-        rc = launch_pt(*ctx, cfg, nullptr, p, FR_OUT_RGB, ko, ctx->stream, nullptr);
+        rc = launch_pt(*ctx, cfg, Centre{}, p, FR_OUT_RGB, ko, ctx->stream, nullptr);
         if (rc != FR_OK) return rc;
     } else {
         plan_loop(cfg, precision, o, p);
@@ -1525,96 +1563,22 @@ int fr_recursive(uint32_t iterations, fr_imaginary start, fr_imaginary c, double
     return fr_recursive_batch(iterations, &start, &c, 1, limit, FR_PRECISION_F64, out_pos, out_iters);
 }
 
-/* fr_escape_rows, fr_escape_rows_dd and fr_escape_rows_pt: `zw` doubles per pixel (2: re, im — DD: the hi parts; 4: DD with
- * the lo parts) */
-static int escape_rows(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
-                       double *z_re_im, uint32_t *iters, unsigned zw, const fr_wide_centre *wide = nullptr) {
-    int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = wide ? check_pt_wide(cfg, wide) : check_precision_lo(cfg, precision, pos_lo);
-    if (rc != FR_OK) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    if (npx == 0 || (!z_re_im && !iters)) return FR_OK;
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (z_re_im) rc = ctx->reserve(ctx->z, npx * zw * sizeof(double));
-    if (rc == FR_OK && iters) rc = ctx->reserve(ctx->iters, npx * sizeof(uint32_t));
-    if (rc != FR_OK) return rc;
-    const Opts o = default_opts();
-    fr_kparams p;
-    fill_params(cfg, o, p);
-    p.nrows = y1 - y0;
-    p.y_first = y0;
-    p.block_rows = p.nrows;
-    p.y_stride = 0;
-    fr_kout ko{};
-    ko.z = z_re_im ? static_cast<double *>(ctx->z.ptr) : nullptr;
-    ko.iters = iters ? static_cast<uint32_t *>(ctx->iters.ptr) : nullptr;
-    if (precision == FR_PRECISION_DD) {
-        HIP_TRY(fr_launch_escape_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, FR_OUT_ESCAPE, ko, zw == 4,
-                                    ctx->stream, nullptr));
-    } else if (precision == FR_PRECISION_PT) {
-        rc = launch_pt(*ctx, cfg, pos_lo, p, FR_OUT_ESCAPE, ko, ctx->stream, nullptr, wide);
-        if (rc != FR_OK) return rc;
-    } else {
-        plan_loop(cfg, precision, o, p);
-        HIP_TRY(fr_launch_escape(p, precision, FR_OUT_ESCAPE, ko, o.tile, ctx->stream, nullptr));
-    }
-    if (z_re_im) HIP_TRY(hipMemcpyAsync(z_re_im, ctx->z.ptr, npx * zw * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (iters) HIP_TRY(hipMemcpyAsync(iters, ctx->iters.ptr, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FR_OK;
-}
-
 int fr_escape_rows(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, double *z_re_im,
                    uint32_t *iters) {
-    return escape_rows(cfg, precision, nullptr, y0, y1, z_re_im, iters, 2);
+    return escape_rows(cfg, precision, Centre{}, y0, y1, z_re_im, iters, 2);
 }
 
 int fr_escape_rows_dd(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z,
                       uint32_t *iters) {
-    return escape_rows(cfg, FR_PRECISION_DD, pos_lo, y0, y1, z, iters, 4);
+    return escape_rows(cfg, FR_PRECISION_DD, Centre{pos_lo, nullptr}, y0, y1, z, iters, 4);
 }
 
 int fr_escape_rows_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z,
                       uint32_t *iters) {
-    return escape_rows(cfg, FR_PRECISION_PT, pos_lo, y0, y1, z, iters, 2);
+    return escape_rows(cfg, FR_PRECISION_PT, Centre{pos_lo, nullptr}, y0, y1, z, iters, 2);
 }
 
 /* ---- a view kept on the device: raw results into device arrays, their cap raised in place ------- */
-
-static void rows_grid(fr_kparams &p, uint32_t y0, uint32_t y1) {
-    p.nrows = y1 - y0;
-    p.y_first = y0;
-    p.block_rows = p.nrows;
-    p.y_stride = 0;
-}
-
-/* what escape_rows() launches, on the caller's stream into the caller's arrays: no scratch, no copy, no ctx->mu */
-static int escape_rows_launch(Ctx &ctx, const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0,
-                              uint32_t y1, unsigned zw, double *d_z, uint32_t *d_iters, hipStream_t stream) {
-    fr_kparams p;
-    fill_params(cfg, o, p);
-    rows_grid(p, y0, y1);
-    fr_kout ko{};
-    ko.z = d_z;
-    ko.iters = d_iters;
-    int rc = prof_begin(stream);
-    if (rc != FR_OK) return rc;
-    const char *kname = "";
-    if (precision == FR_PRECISION_DD) {
-        HIP_TRY(fr_launch_escape_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, FR_OUT_ESCAPE, ko, zw == 4, stream, &kname));
-    } else if (precision == FR_PRECISION_PT) {
-        rc = launch_pt(ctx, cfg, pos_lo, p, FR_OUT_ESCAPE, ko, stream, &kname);
-        if (rc != FR_OK) return rc;
-    } else {
-        plan_loop(cfg, precision, o, p);
-        HIP_TRY(fr_launch_escape(p, precision, FR_OUT_ESCAPE, ko, o.tile, stream, &kname));
-    }
-    return prof_end(stream, kname);
-}
 
 static int check_pos_lo_precision(int precision, const fr_imaginary *pos_lo) {
     if (pos_lo && precision != FR_PRECISION_DD && precision != FR_PRECISION_PT)
@@ -1641,7 +1605,7 @@ int fr_escape_rows_device(const fr_config *cfg, int precision, const fr_imaginar
     Ctx *ctx;
     rc = primary(&ctx);
     if (rc != FR_OK) return rc;
-    return escape_rows_launch(*ctx, cfg, precision, pos_lo, o, y0, y1, (unsigned)z_width, static_cast<double *>(d_z),
+    return escape_rows_launch(*ctx, cfg, precision, Centre{pos_lo, nullptr}, o, y0, y1, (unsigned)z_width, static_cast<double *>(d_z),
                               static_cast<uint32_t *>(d_iters), static_cast<hipStream_t>(hip_stream));
 }
 
@@ -1677,15 +1641,14 @@ static int check_extend(const fr_config *cfg, int precision, const fr_imaginary 
 
 static int extend_launch(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0, uint32_t y1,
                          uint32_t from_iterations, double *d_z, uint32_t *d_iters, hipStream_t stream) {
+    const Centre c{pos_lo, nullptr};
     fr_kparams p;
-    fill_params(cfg, o, p);
-    rows_grid(p, y0, y1);
+    rows_params(cfg, o, y0, y1, 0, p);
     int rc = prof_begin(stream);
     if (rc != FR_OK) return rc;
     const char *kname = "";
     if (precision == FR_PRECISION_DD) {
-        HIP_TRY(fr_launch_escape_extend_dd(p, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, from_iterations, d_z, d_iters,
-                                           stream, &kname));
+        HIP_TRY(fr_launch_escape_extend_dd(p, c.lo_re(), c.lo_im(), from_iterations, d_z, d_iters, stream, &kname));
     } else {
         plan_loop(cfg, precision, o, p); /* loop_spec: the speculative blocks, unless opts->loop_mode == 5 */
         HIP_TRY(fr_launch_escape_extend(p, precision, from_iterations, d_z, d_iters, stream, &kname));
@@ -1716,192 +1679,17 @@ int fr_escape_extend(const fr_config *cfg, int precision, const fr_imaginary *po
     if (rc != FR_OK || !work) return rc;
     const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
     const size_t zb = npx * (size_t)z_width * sizeof(double), ib = npx * sizeof(uint32_t);
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    rc = ctx->reserve(ctx->z, zb);
-    if (rc == FR_OK) rc = ctx->reserve(ctx->iters, ib);
-    if (rc != FR_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->z.ptr, z, zb, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->iters.ptr, iters, ib, hipMemcpyHostToDevice, ctx->stream));
-    rc = extend_launch(cfg, precision, pos_lo, o, y0, y1, from_iterations, static_cast<double *>(ctx->z.ptr),
-                       static_cast<uint32_t *>(ctx->iters.ptr), ctx->stream);
-    if (rc != FR_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(z, ctx->z.ptr, zb, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(iters, ctx->iters.ptr, ib, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FR_OK;
-}
-
-/* ---- resumable perturbation: FR_PRECISION_PT rows with their state, and that state continued to a higher cap ------- */
-
-/* The domain of the four calls (include/fractal_hip.h), checked before any device work: `from` = nullptr for the state render.
- * *work = false: a legal call with nothing to do (no rows; for the extension also M == N or an algorithm without orbits). */
-static int check_pt_state(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, uint32_t y0, uint32_t y1,
-                          const uint32_t *from, const void *z, const void *iters, const void *dz, const void *m, bool *work) {
-    *work = false;
-    int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = wide ? check_pt_wide(cfg, wide) : check_pt(cfg, pos_lo);
-    if (rc != FR_OK) return rc;
-    if (from && cfg->iterations < *from)
-        return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from a stored state");
-    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
-    if (!z || !iters || !dz || !m) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the PT state is z, iters, dz and m, all four");
-    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(dz) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u) ||
-        (reinterpret_cast<uintptr_t>(m) & 3u))
-        return fail(FR_ERR_INVALID_ARGUMENT, "z and dz must be 8-byte aligned, iters and m 4-byte aligned");
-    *work = !from || (cfg->iterations != *from && (cfg->algo == FR_ALGO_MANDELBROT || cfg->algo == FR_ALGO_JULIA));
-    return FR_OK;
-}
-
-/* from == nullptr: the state render; else the extension from *from.  On the caller's stream, into the caller's arrays. */
-static int pt_state_launch(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, uint32_t y0,
-                           uint32_t y1, const uint32_t *from, double *d_z, uint32_t *d_iters, double *d_dz, uint32_t *d_m,
-                           hipStream_t stream) {
-    fr_kparams p;
-    fill_params(cfg, default_opts(), p);
-    rows_grid(p, y0, y1);
-    int rc = prof_begin(stream);
-    if (rc != FR_OK) return rc;
-    const char *kname = "";
-    rc = from ? launch_pt_extend(ctx, cfg, pos_lo, p, *from, d_z, d_iters, d_dz, d_m, stream, &kname, wide)
-              : launch_pt_state(ctx, cfg, pos_lo, p, d_z, d_iters, d_dz, d_m, stream, &kname, wide);
-    if (rc != FR_OK) return rc;
-    return prof_end(stream, kname);
-}
-
-static int pt_state_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, uint32_t y0, uint32_t y1,
-                           const uint32_t *from, void *d_z, void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
-    bool work;
-    int rc = check_pt_state(cfg, pos_lo, wide, y0, y1, from, d_z, d_iters, d_dz, d_m, &work);
-    if (rc != FR_OK || !work) return rc;
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    return pt_state_launch(*ctx, cfg, pos_lo, wide, y0, y1, from, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
-                           static_cast<double *>(d_dz), static_cast<uint32_t *>(d_m), static_cast<hipStream_t>(hip_stream));
-}
-
-/* the host forms: z and dz share the context's z scratch, iters and m its iters scratch */
-static int pt_state_host(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, uint32_t y0, uint32_t y1,
-                         const uint32_t *from, double *z, uint32_t *iters, double *dz, uint32_t *m) {
-    bool work;
-    int rc = check_pt_state(cfg, pos_lo, wide, y0, y1, from, z, iters, dz, m, &work);
-    if (rc != FR_OK || !work) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    const size_t zb = npx * 2 * sizeof(double), ib = npx * sizeof(uint32_t);
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    rc = ctx->reserve(ctx->z, 2 * zb);
-    if (rc == FR_OK) rc = ctx->reserve(ctx->iters, 2 * ib);
-    if (rc != FR_OK) return rc;
-    double *d_z = static_cast<double *>(ctx->z.ptr), *d_dz = d_z + 2 * npx;
-    uint32_t *d_iters = static_cast<uint32_t *>(ctx->iters.ptr), *d_m = d_iters + npx;
-    if (from) {
-        HIP_TRY(hipMemcpyAsync(d_z, z, zb, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(d_dz, dz, zb, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(d_iters, iters, ib, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(d_m, m, ib, hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = pt_state_launch(*ctx, cfg, pos_lo, wide, y0, y1, from, d_z, d_iters, d_dz, d_m, ctx->stream);
-    if (rc != FR_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(z, d_z, zb, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dz, d_dz, zb, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(iters, d_iters, ib, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(m, d_m, ib, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FR_OK;
-}
-
-int fr_escape_rows_pt_state_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, void *d_z,
-                                   void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
-    return pt_state_device(cfg, pos_lo, nullptr, y0, y1, nullptr, d_z, d_iters, d_dz, d_m, hip_stream);
-}
-
-int fr_escape_extend_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, uint32_t from_iterations,
-                               void *d_z, void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
-    return pt_state_device(cfg, pos_lo, nullptr, y0, y1, &from_iterations, d_z, d_iters, d_dz, d_m, hip_stream);
-}
-
-int fr_escape_rows_pt_state(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z, uint32_t *iters,
-                            double *dz, uint32_t *m) {
-    return pt_state_host(cfg, pos_lo, nullptr, y0, y1, nullptr, z, iters, dz, m);
-}
-
-int fr_escape_extend_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, uint32_t from_iterations,
-                        double *z, uint32_t *iters, double *dz, uint32_t *m) {
-    return pt_state_host(cfg, pos_lo, nullptr, y0, y1, &from_iterations, z, iters, dz, m);
-}
-
-/* ---- WIDE PT (include/fractal_hip.h): the PT calls above with a fixed-point view centre in place of (pos, pos_lo) ------- */
-
-/* a NULL centre must not fall through to the dd road */
-static int need_centre(const fr_wide_centre *centre) {
-    if (!centre) return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_PT, wide centre: centre is NULL");
-    return FR_OK;
-}
-
-int fr_render_rows_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, int channels, uint8_t *out,
-                           size_t out_len) {
-    int rc = dd_channels(channels);
-    if (rc == FR_OK) rc = need_centre(centre);
-    if (rc != FR_OK) return rc;
-    return fr_host_render_rows_deep(cfg, FR_PRECISION_PT, nullptr, y0, y1, out, out_len, (unsigned)channels, nullptr, centre);
-}
-
-int fr_render_rows_pt_wide_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, int channels,
-                                  void *d_out, size_t out_len, void *hip_stream) {
-    int rc = dd_channels(channels);
-    if (rc == FR_OK) rc = need_centre(centre);
-    if (rc != FR_OK) return rc;
-    return render_rows_device(cfg, FR_PRECISION_PT, y0, y1, d_out, out_len, hip_stream, (unsigned)channels, nullptr, nullptr, centre);
-}
-
-int fr_escape_rows_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z, uint32_t *iters) {
-    const int rc = need_centre(centre);
-    if (rc != FR_OK) return rc;
-    return escape_rows(cfg, FR_PRECISION_PT, nullptr, y0, y1, z, iters, 2, centre);
-}
-
-int fr_escape_rows_pt_wide_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, void *d_z,
-                                        void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
-    const int rc = need_centre(centre);
-    if (rc != FR_OK) return rc;
-    return pt_state_device(cfg, nullptr, centre, y0, y1, nullptr, d_z, d_iters, d_dz, d_m, hip_stream);
-}
-
-int fr_escape_extend_pt_wide_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
-                                    uint32_t from_iterations, void *d_z, void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
-    const int rc = need_centre(centre);
-    if (rc != FR_OK) return rc;
-    return pt_state_device(cfg, nullptr, centre, y0, y1, &from_iterations, d_z, d_iters, d_dz, d_m, hip_stream);
-}
-
-int fr_escape_rows_pt_wide_state(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z,
-                                 uint32_t *iters, double *dz, uint32_t *m) {
-    const int rc = need_centre(centre);
-    if (rc != FR_OK) return rc;
-    return pt_state_host(cfg, nullptr, centre, y0, y1, nullptr, z, iters, dz, m);
-}
-
-int fr_escape_extend_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, uint32_t from_iterations,
-                             double *z, uint32_t *iters, double *dz, uint32_t *m) {
-    const int rc = need_centre(centre);
-    if (rc != FR_OK) return rc;
-    return pt_state_host(cfg, nullptr, centre, y0, y1, &from_iterations, z, iters, dz, m);
+    return host_raw(z, zb, iters, ib, nullptr, nullptr, true, [&](Ctx &, double *d_z, uint32_t *d_iters, double *, uint32_t *, hipStream_t stream) {
+        return extend_launch(cfg, precision, pos_lo, o, y0, y1, from_iterations, d_z, d_iters, stream);
+    });
 }
 
 int fr_colour_rows_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, size_t n, int channels,
                           void *d_out, size_t out_len, void *hip_stream) {
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
     if (z_width != 2 && z_width != 4) return fail(FR_ERR_INVALID_ARGUMENT, "z_width must be 2 (re, im) or 4 (re.hi, re.lo, im.hi, im.lo)");
-    if (channels != 3 && channels != 4) return fail(FR_ERR_INVALID_ARGUMENT, "channels must be 3 (RGB) or 4 (RGBA)");
+    const int rc = check_channels(channels);
+    if (rc != FR_OK) return rc;
     if (n == 0) return FR_OK;
     if (!d_z || !d_iters || !d_out) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array");
     if (n > SIZE_MAX / 4 || out_len < (size_t)channels * n) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*n");
@@ -1972,7 +1760,7 @@ int fr_count_iterations(const fr_config *cfg, int precision, uint32_t y0, uint32
     const uint64_t yf = ((uint64_t)y0 + sy - 1) / sy * sy; /* first sampled row >= y0 */
     p.nrows = yf < y1 ? (uint32_t)((y1 - 1 - yf) / sy + 1) : 0;
     p.y_first = (uint32_t)yf;
-    p.block_rows = 1;
+    p.block_rows = 1; /* not rows_params: every sy-th row */
     p.y_stride = sy;
     if (pixels) *pixels = (uint64_t)p.ncols * p.nrows;
     if (p.ncols == 0 || p.nrows == 0) return FR_OK;
@@ -1990,7 +1778,7 @@ int fr_count_iterations(const fr_config *cfg, int precision, uint32_t y0, uint32
     if (precision == FR_PRECISION_DD) {
         HIP_TRY(fr_launch_escape_dd(p, 0.0, 0.0, FR_OUT_COUNT, ko, false, ctx->stream, nullptr));
     } else if (precision == FR_PRECISION_PT) {
-        rc = launch_pt(*ctx, cfg, nullptr, p, FR_OUT_COUNT, ko, ctx->stream, nullptr);
+        rc = launch_pt(*ctx, cfg, Centre{}, p, FR_OUT_COUNT, ko, ctx->stream, nullptr);
         if (rc != FR_OK) return rc;
     } else {
         plan_loop(cfg, precision, o, p);
@@ -2090,10 +1878,7 @@ int fr_debug_sample_view(const fr_config *cfg, int precision, double out[8]) {
     rc = primary(&ctx);
     if (rc != FR_OK) return rc;
     fr_kparams p;
-    fill_params(cfg, default_opts(), p);
-    p.nrows = cfg->height;
-    p.block_rows = cfg->height ? cfg->height : 1;
-    p.y_stride = 0;
+    rows_params(cfg, default_opts(), 0, cfg->height, 0, p);
     if (p.ncols == 0 || p.nrows == 0) return fail(FR_ERR_INVALID_ARGUMENT, "empty image");
     double st[7];
     rc = sample_view(*ctx, p, precision, Ctx::kViewChoices, st);
@@ -2112,10 +1897,7 @@ int fr_debug_loop_plan(const fr_config *cfg, int precision, uint32_t *loop_mode,
     if (rc != FR_OK) return rc;
     const Opts o = default_opts();
     fr_kparams p;
-    fill_params(cfg, o, p);
-    p.nrows = cfg->height;
-    p.block_rows = cfg->height ? cfg->height : 1;
-    p.y_stride = 0;
+    rows_params(cfg, o, 0, cfg->height, 0, p);
     plan_loop(cfg, precision, o, p);
     *loop_mode = p.loop_mode;
     *skip_t = p.skip_t;
@@ -2134,11 +1916,7 @@ int fr_debug_view_choice(const fr_config *cfg, int precision, uint32_t y0, uint3
     rc = primary(&ctx);
     if (rc != FR_OK) return rc;
     fr_kparams p;
-    fill_params(cfg, default_opts(), p);
-    p.nrows = y1 - y0;
-    p.y_first = y0;
-    p.block_rows = p.nrows ? p.nrows : 1;
-    p.y_stride = 0;
+    rows_params(cfg, default_opts(), y0, y1, 0, p);
     const uint64_t key = view_key(cfg, p, precision);
     *state = 0, *choice = -1, *strip_tiles = 0;
     std::lock_guard<std::mutex> lk(ctx->sample_mu);
@@ -2168,10 +1946,7 @@ int fr_debug_spec_maxlen(const fr_config *cfg, int precision, uint32_t *maxlen) 
     if (rc != FR_OK) return rc;
     const Opts o = default_opts();
     fr_kparams p;
-    fill_params(cfg, o, p);
-    p.nrows = cfg->height;
-    p.block_rows = cfg->height ? cfg->height : 1;
-    p.y_stride = 0;
+    rows_params(cfg, o, 0, cfg->height, 0, p);
     plan_loop(cfg, precision, o, p);
     *maxlen = p.loop_spec_max;
     return FR_OK;

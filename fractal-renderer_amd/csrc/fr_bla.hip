@@ -360,17 +360,17 @@ namespace {
 
 /* The view's orbits (`orbit` holds them, `v` points into them) and tables, from the context's caches or built and uploaded;
  * the caller keeps `orbit` and `out` alive until its launch has been enqueued. */
-int table_for(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, int bits,
-              std::shared_ptr<PtOrbit> &orbit, PtOrbitView &v, std::shared_ptr<BlaTable> &out) {
-    const int rc = pt_orbit_view(ctx, cfg, pos_lo, wide, orbit, v);
+int table_for(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, std::shared_ptr<PtOrbit> &orbit, PtOrbitView &v,
+              std::shared_ptr<BlaTable> &out) {
+    const int rc = pt_orbit_view(ctx, cfg, c, orbit, v);
     if (rc != FR_OK) return rc;
     const bool julia = cfg->algo == 2;
     const double D = image_D(cfg);
     std::lock_guard<std::mutex> lk(ctx.pt_mu);
-    const std::shared_ptr<BlaTable> c = ctx.bla_table;
-    if (c && c->orbit.lock() == orbit && memcmp(&c->D, &D, sizeof D) == 0 && c->bits == bits) {
-        c->built = false;
-        out = c;
+    const std::shared_ptr<BlaTable> cached = ctx.bla_table;
+    if (cached && cached->orbit.lock() == orbit && memcmp(&cached->D, &D, sizeof D) == 0 && cached->bits == bits) {
+        cached->built = false;
+        out = cached;
         return FR_OK;
     }
     /* the stored entries come back from the device: the table is a function of them alone, and the cache keeps no host copy */
@@ -417,8 +417,8 @@ int table_for(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const 
     return FR_OK;
 }
 
-int launch_bla(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, int bits, const fr_kparams &p,
-               int mode, const fr_kout &out, hipStream_t stream) {
+int launch_bla(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_kparams &p, int mode, const fr_kout &out,
+               hipStream_t stream) {
     if (p.ncols == 0 || p.nrows == 0) return FR_OK;
     const bool julia = cfg->algo == 2;
     if (cfg->algo != 0 && !julia) { /* no escape-time algorithm: every pixel is black / zero, as PT's kernel gives */
@@ -428,7 +428,7 @@ int launch_bla(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const
     std::shared_ptr<PtOrbit> orbit;
     std::shared_ptr<BlaTable> table;
     PtOrbitView v;
-    const int rc = table_for(ctx, cfg, pos_lo, wide, bits, orbit, v, table);
+    const int rc = table_for(ctx, cfg, c, bits, orbit, v, table);
     if (rc != FR_OK) return rc;
     BlaDev t = table->view;
     t.x_orbit = v.x;
@@ -441,50 +441,27 @@ int launch_bla(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const
 
 /* ---- the calls ------------------------------------------------------------------------------------------------------ */
 
-int check_bla(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int &bits, uint32_t y0, uint32_t y1) {
-    if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
-    if (y0 > y1) return fail(FR_ERR_INVALID_ARGUMENT, "y0 > y1");
-    if (y1 > cfg->height) return fail(FR_ERR_INVALID_ARGUMENT, "y1 > height");
-    if (centre && pos_lo) return fail(FR_ERR_INVALID_ARGUMENT, "BLA-PT: pos_lo must be NULL when a wide centre is given");
-    const int rc = centre ? check_pt_wide(cfg, centre) : check_pt(cfg, pos_lo);
+int check_bla(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1) {
+    int rc = check_rows(cfg, y0, y1);
+    if (rc != FR_OK) return rc;
+    if (c.wide && c.pos_lo) return fail(FR_ERR_INVALID_ARGUMENT, "BLA-PT: pos_lo must be NULL when a wide centre is given");
+    rc = c.check(cfg, FR_PRECISION_PT);
     if (rc != FR_OK) return rc;
     if (bits == 0) bits = FR_BLA_DEFAULT_BITS;
     if (bits < 24 || bits > 53) return fail(FR_ERR_INVALID_ARGUMENT, "BLA-PT: bits must be 0 (FR_BLA_DEFAULT_BITS) or 24 .. 53");
     return FR_OK;
 }
 
-int check_channels(int channels) {
-    if (channels != 3 && channels != 4) return fail(FR_ERR_INVALID_ARGUMENT, "channels must be 3 (RGB) or 4 (RGBA)");
-    return FR_OK;
-}
-
-void rows_params(const fr_config *cfg, uint32_t y0, uint32_t y1, fr_kparams &p) {
-    fill_params(cfg, default_opts(), p); /* the colour constants; no loop plan, no kernel choice, no view sample */
-    p.nrows = y1 - y0;
-    p.y_first = y0;
-    p.block_rows = p.nrows;
-    p.y_stride = 0;
-}
-
-/* one launch on `stream` between the profiling events (fr_set_profiling), named for fr_last_kernel_name */
-int profiled_launch(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits,
-                    const fr_kparams &p, int mode, const fr_kout &out, hipStream_t stream) {
-    Profiling &pr = profiling();
-    if (pr.enabled) {
-        if (!pr.e0) {
-            HIP_TRY(hipEventCreate(&pr.e0));
-            HIP_TRY(hipEventCreate(&pr.e1));
-        }
-        HIP_TRY(hipEventRecord(pr.e0, stream));
-    }
-    const int rc = launch_bla(ctx, cfg, pos_lo, centre, bits, p, mode, out, stream);
+/* rows [y0, y1) on `stream` between the profiling events (fr_set_profiling), named for fr_last_kernel_name; the colour
+ * constants alone: no loop plan, no kernel choice, no view sample */
+int profiled_launch(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, unsigned channels, int mode,
+                    const fr_kout &out, hipStream_t stream) {
+    fr_kparams p;
+    rows_params(cfg, default_opts(), y0, y1, channels, p);
+    int rc = prof_begin(stream);
+    if (rc == FR_OK) rc = launch_bla(ctx, cfg, c, bits, p, mode, out, stream);
     if (rc != FR_OK) return rc;
-    if (pr.enabled) {
-        HIP_TRY(hipEventRecord(pr.e1, stream));
-        pr.have = true;
-        pr.kernel = "escape_bla_kernel";
-    }
-    return FR_OK;
+    return prof_end(stream, "escape_bla_kernel");
 }
 
 }  // namespace
@@ -494,8 +471,9 @@ using namespace fr;
 
 int fr_render_rows_pt_bla_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
                                  uint32_t y1, int channels, void *d_out, size_t out_len, void *hip_stream) {
+    const Centre c{pos_lo, centre};
     int rc = check_channels(channels);
-    if (rc == FR_OK) rc = check_bla(cfg, pos_lo, centre, bits, y0, y1);
+    if (rc == FR_OK) rc = check_bla(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
     const size_t need = (size_t)channels * cfg->width * (size_t)(y1 - y0);
     if (need == 0) return FR_OK;
@@ -507,45 +485,32 @@ int fr_render_rows_pt_bla_device(const fr_config *cfg, const fr_imaginary *pos_l
     Ctx *ctx;
     rc = primary(&ctx);
     if (rc != FR_OK) return rc;
-    fr_kparams p;
-    rows_params(cfg, y0, y1, p);
-    p.out_rgba = channels == 4 ? 1u : 0u;
     fr_kout ko{};
     ko.rgb = static_cast<uint8_t *>(d_out);
-    return profiled_launch(*ctx, cfg, pos_lo, centre, bits, p, FR_OUT_RGB, ko, static_cast<hipStream_t>(hip_stream));
+    return profiled_launch(*ctx, cfg, c, bits, y0, y1, (unsigned)channels, FR_OUT_RGB, ko, static_cast<hipStream_t>(hip_stream));
 }
 
 int fr_render_rows_pt_bla(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
                           uint32_t y1, int channels, uint8_t *out, size_t out_len) {
+    const Centre c{pos_lo, centre};
     int rc = check_channels(channels);
-    if (rc == FR_OK) rc = check_bla(cfg, pos_lo, centre, bits, y0, y1);
+    if (rc == FR_OK) rc = check_bla(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
     const size_t need = (size_t)channels * cfg->width * (size_t)(y1 - y0);
     if (need == 0) return FR_OK;
     if (!out) return fail(FR_ERR_INVALID_ARGUMENT, "out is NULL");
     if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*(y1-y0)");
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    rc = ctx->reserve(ctx->rgb, need);
-    if (rc != FR_OK) return rc;
-    fr_kparams p;
-    rows_params(cfg, y0, y1, p);
-    p.out_rgba = channels == 4 ? 1u : 0u;
-    fr_kout ko{};
-    ko.rgb = static_cast<uint8_t *>(ctx->rgb.ptr);
-    rc = profiled_launch(*ctx, cfg, pos_lo, centre, bits, p, FR_OUT_RGB, ko, ctx->stream);
-    if (rc != FR_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FR_OK;
+    return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) {
+        fr_kout ko{};
+        ko.rgb = static_cast<uint8_t *>(d_out);
+        return profiled_launch(ctx, cfg, c, bits, y0, y1, (unsigned)channels, FR_OUT_RGB, ko, stream);
+    });
 }
 
 int fr_escape_rows_pt_bla_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
                                  uint32_t y1, void *d_z, void *d_iters, void *hip_stream) {
-    int rc = check_bla(cfg, pos_lo, centre, bits, y0, y1);
+    const Centre c{pos_lo, centre};
+    int rc = check_bla(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
     const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
     if (npx == 0 || (!d_z && !d_iters)) return FR_OK;
@@ -555,44 +520,32 @@ int fr_escape_rows_pt_bla_device(const fr_config *cfg, const fr_imaginary *pos_l
     Ctx *ctx;
     rc = primary(&ctx);
     if (rc != FR_OK) return rc;
-    fr_kparams p;
-    rows_params(cfg, y0, y1, p);
     fr_kout ko{};
     ko.z = static_cast<double *>(d_z);
     ko.iters = static_cast<uint32_t *>(d_iters);
-    return profiled_launch(*ctx, cfg, pos_lo, centre, bits, p, FR_OUT_ESCAPE, ko, static_cast<hipStream_t>(hip_stream));
+    return profiled_launch(*ctx, cfg, c, bits, y0, y1, 0, FR_OUT_ESCAPE, ko, static_cast<hipStream_t>(hip_stream));
 }
 
 int fr_escape_rows_pt_bla(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
                           uint32_t y1, double *z, uint32_t *iters) {
-    int rc = check_bla(cfg, pos_lo, centre, bits, y0, y1);
+    const Centre c{pos_lo, centre};
+    int rc = check_bla(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
     const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
     if (npx == 0 || (!z && !iters)) return FR_OK;
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (z) rc = ctx->reserve(ctx->z, npx * 2 * sizeof(double));
-    if (rc == FR_OK && iters) rc = ctx->reserve(ctx->iters, npx * sizeof(uint32_t));
-    if (rc != FR_OK) return rc;
-    fr_kparams p;
-    rows_params(cfg, y0, y1, p);
-    fr_kout ko{};
-    ko.z = z ? static_cast<double *>(ctx->z.ptr) : nullptr;
-    ko.iters = iters ? static_cast<uint32_t *>(ctx->iters.ptr) : nullptr;
-    rc = profiled_launch(*ctx, cfg, pos_lo, centre, bits, p, FR_OUT_ESCAPE, ko, ctx->stream);
-    if (rc != FR_OK) return rc;
-    if (z) HIP_TRY(hipMemcpyAsync(z, ctx->z.ptr, npx * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (iters) HIP_TRY(hipMemcpyAsync(iters, ctx->iters.ptr, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FR_OK;
+    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), nullptr, nullptr, false,
+                    [&](Ctx &ctx, double *d_z, uint32_t *d_iters, double *, uint32_t *, hipStream_t stream) {
+                        fr_kout ko{};
+                        ko.z = d_z;
+                        ko.iters = d_iters;
+                        return profiled_launch(ctx, cfg, c, bits, y0, y1, 0, FR_OUT_ESCAPE, ko, stream);
+                    });
 }
 
 int fr_debug_bla_count(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
                        uint32_t y1, uint64_t *passes, uint64_t *steps) {
-    int rc = check_bla(cfg, pos_lo, centre, bits, y0, y1);
+    const Centre c{pos_lo, centre};
+    int rc = check_bla(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
     if (!passes || !steps) return fail(FR_ERR_INVALID_ARGUMENT, "passes or steps is NULL");
     *passes = *steps = 0;
@@ -606,11 +559,9 @@ int fr_debug_bla_count(const fr_config *cfg, const fr_imaginary *pos_lo, const f
     rc = ctx->reserve(ctx->misc, bytes);
     if (rc != FR_OK) return rc;
     HIP_TRY(hipMemsetAsync(ctx->misc.ptr, 0, bytes, ctx->stream));
-    fr_kparams p;
-    rows_params(cfg, y0, y1, p);
     fr_kout ko{};
     ko.count = static_cast<unsigned long long *>(ctx->misc.ptr);
-    rc = profiled_launch(*ctx, cfg, pos_lo, centre, bits, p, FR_OUT_COUNT, ko, ctx->stream);
+    rc = profiled_launch(*ctx, cfg, c, bits, y0, y1, 0, FR_OUT_COUNT, ko, ctx->stream);
     if (rc != FR_OK) return rc;
     std::vector<unsigned long long> host(2 * FR_COUNT_SLOTS);
     HIP_TRY(hipMemcpyAsync(host.data(), ctx->misc.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -624,7 +575,8 @@ int fr_debug_bla_count(const fr_config *cfg, const fr_imaginary *pos_lo, const f
 
 int fr_debug_bla_table(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, int which,
                        uint32_t level, double *out, size_t cap, uint32_t *len) {
-    int rc = check_bla(cfg, pos_lo, centre, bits, 0, 0);
+    const Centre c{pos_lo, centre};
+    int rc = check_bla(cfg, c, bits, 0, 0);
     if (rc != FR_OK) return rc;
     if (cfg->algo != 0 && cfg->algo != 2) return fail(FR_ERR_INVALID_ARGUMENT, "BLA-PT: tables exist for Mandelbrot and Julia");
     if (which != 0 && !(which == 1 && cfg->algo == 2))
@@ -632,7 +584,7 @@ int fr_debug_bla_table(const fr_config *cfg, const fr_imaginary *pos_lo, const f
     if (!len) return fail(FR_ERR_INVALID_ARGUMENT, "len is NULL");
     if (cap && !out) return fail(FR_ERR_INVALID_ARGUMENT, "out is NULL");
     std::vector<double> X;
-    pt_host_orbit(cfg, pos_lo, centre, which, X);
+    pt_host_orbit(cfg, c, which, X);
     const uint32_t last = (uint32_t)(X.size() / 2 - 1);
     const double b0 = cfg->algo == 2 ? 0.0 : 1.0;
     HostTable t;

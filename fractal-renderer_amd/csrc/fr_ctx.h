@@ -170,6 +170,9 @@ struct Ctx {
 /* calc::Config -> kernel arguments (the local grid is filled in by the caller) and the loop plan */
 void fill_params(const fr_config *cfg, const Opts &o, fr_kparams &p);
 void plan_loop(const fr_config *cfg, int precision, const Opts &o, fr_kparams &p);
+/* fill_params with rows [y0, y1) of the image as the local grid, one block of whole rows; channels == 4: RGBA output
+ * (0 for the calls that write no pixels) */
+void rows_params(const fr_config *cfg, const Opts &o, uint32_t y0, uint32_t y1, unsigned channels, fr_kparams &p);
 
 /* device-pointer render of the local grid set in `p`; `ctx` lends the palette slot (it must live
  * on the device `stream` belongs to).  No host synchronisation. */
@@ -182,6 +185,9 @@ int render_block_cyclic(Ctx &ctx, const fr_config *cfg, int precision, const Opt
                         void *d_out, size_t out_len, hipStream_t stream, uint64_t *rows_written);
 
 int check_precision(int precision);
+/* cfg not NULL and 0 <= y0 <= y1 <= height; channels 3 or 4 */
+int check_rows(const fr_config *cfg, uint32_t y0, uint32_t y1);
+int check_channels(int channels);
 
 /* FR_PRECISION_DD (fr_dd.hip): the domain check of include/fractal_hip.h (pos_lo NULL = (0, 0)); no device needed */
 int check_dd(const fr_config *cfg, const fr_imaginary *pos_lo);
@@ -192,27 +198,40 @@ int check_pt(const fr_config *cfg, const fr_imaginary *pos_lo);
 int check_precision_or_deep(const fr_config *cfg, int precision);
 /* check_dd / check_pt with pos_lo for the deep-zoom precisions, else check_precision */
 int check_precision_lo(const fr_config *cfg, int precision, const fr_imaginary *pos_lo);
+
+/* The view centre of a deep call: (cfg->pos, pos_lo) in double-double (pos_lo NULL = (0, 0)), or — FR_PRECISION_PT only —
+ * the wide centre that stands in their place (include/fractal_hip.h, "WIDE PT").  The public entry points build one on
+ * their first line; every road below them takes it whole, so none can drop the wide half on the way. */
+struct Centre {
+    const fr_imaginary *pos_lo; /* an aggregate, always written Centre{pos_lo, wide} */
+    const fr_wide_centre *wide;
+    double lo_re() const { return pos_lo ? pos_lo->re : 0.0; }
+    double lo_im() const { return pos_lo ? pos_lo->im : 0.0; }
+    /* the domain check: check_pt_wide (fr_wide.h) for a wide centre, else check_precision_lo; no device needed */
+    int check(const fr_config *cfg, int precision) const;
+};
+
+/* profiling (fr_set_profiling) around the launches of one call on `stream`: prof_begin creates the thread's events on first
+ * use and records the first; prof_end, called only after a successful launch, records the second and the name
+ * fr_last_kernel_name reports.  Both do nothing while profiling is off. */
+int prof_begin(hipStream_t stream);
+int prof_end(hipStream_t stream, const char *kernel_name);
+
 /* DD or PT rows [y0, y1) as RGB (bpp 3) / RGBA (bpp 4) into device memory on `stream`; arguments already checked.
  * Records the profiling events and the kernel's name like render_device.  No host synchronisation (PT: apart from
  * computing and uploading the view's reference orbit when the context does not hold it yet). */
-int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0,
-                       uint32_t y1, unsigned bpp, void *d_out, hipStream_t stream, const fr_wide_centre *wide = nullptr);
-/* `wide` in the PT calls below: the view's wide centre (include/fractal_hip.h, "WIDE PT"; checked with check_pt_wide,
- * fr_wide.h) in place of (cfg->pos, pos_lo); nullptr = the dd centre. */
+int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const Centre &c, const Opts &o, uint32_t y0, uint32_t y1,
+                       unsigned bpp, void *d_out, hipStream_t stream);
+/* The bodies of the deep row calls (fr_api.hip) that the PT entry points of fr_pt.hip share with the DD ones: every check,
+ * then render_deep_device / the escape launch.  zw: doubles of z per pixel (4: DD with its low parts). */
+int render_rows_device(const fr_config *cfg, int precision, const Centre &c, uint32_t y0, uint32_t y1, void *d_out, size_t out_len,
+                       void *hip_stream, unsigned bytes_per_pixel, const fr_render_opts *opts);
+int escape_rows(const fr_config *cfg, int precision, const Centre &c, uint32_t y0, uint32_t y1, double *z, uint32_t *iters,
+                unsigned zw);
 /* FR_PRECISION_PT (fr_pt.hip: escape_pt_kernel): the launch's local grid, colour and limit from `p` as for DD; the view's
  * reference orbits from ctx's cache (computed and uploaded on a miss).  MODE ESCAPE writes re, im per pixel. */
-int launch_pt(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, int mode, const fr_kout &out,
-              hipStream_t stream, const char **kernel_name, const fr_wide_centre *wide = nullptr);
-
-/* FR_PRECISION_PT with its resumable state (fr_pt.hip: escape_pt_state_kernel, escape_extend_pt_kernel; include/fractal_hip.h,
- * "resumable perturbation"): the local grid from `p` as launch_pt takes it, z and dz as re, im per pixel, m with bit 31 =
- * on K.  The extension continues the arrays from from_iterations to p.iterations on the orbits of the new cap, which the
- * context's cache continues from those of the old one. */
-int launch_pt_state(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, double *z, uint32_t *iters,
-                    double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name, const fr_wide_centre *wide = nullptr);
-int launch_pt_extend(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, uint32_t from_iterations,
-                     double *z, uint32_t *iters, double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name,
-                     const fr_wide_centre *wide = nullptr);
+int launch_pt(Ctx &ctx, const fr_config *cfg, const Centre &c, const fr_kparams &p, int mode, const fr_kout &out,
+              hipStream_t stream, const char **kernel_name);
 
 /* For BLA-PT (fr_bla.hip), from fr_pt.hip: the view's orbits in device memory as launch_pt finds them (the context's cache,
  * computed and uploaded on a miss) — `keep` holds them alive and is their identity, v.k == v.x for Mandelbrot — and orbit
@@ -221,9 +240,8 @@ struct PtOrbitView {
     const double2 *x = nullptr, *k = nullptr;
     uint32_t x_last = 0, k_last = 0;
 };
-int pt_orbit_view(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide,
-                  std::shared_ptr<PtOrbit> &keep, PtOrbitView &v);
-void pt_host_orbit(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, int which, std::vector<double> &out);
+int pt_orbit_view(Ctx &ctx, const fr_config *cfg, const Centre &c, std::shared_ptr<PtOrbit> &keep, PtOrbitView &v);
+void pt_host_orbit(const fr_config *cfg, const Centre &c, int which, std::vector<double> &out);
 
 /* choose_kernel for rows [y0, y1) of the image as ONE launch, recorded in `o` (tile 0 only): callers that render those
  * rows in several launches then sample the view once, not once per launch.  The calling thread must be on ctx's device. */
@@ -296,6 +314,56 @@ struct Profiling {
 };
 Profiling &profiling();
 
+/* ---- the host-buffer form of a call: the primary context under ctx->mu, its scratch, one launch on ctx->stream, the
+ * copy back, one synchronisation.  `launch` is any callable (a lambda: no allocation on the call path); every argument
+ * check comes before these. ------------------------------------------------------------------------------------------- */
+
+/* RGB: launch(ctx, d_out, stream) fills `need` bytes of ctx->rgb */
+template <class Launch>
+int host_rgb(uint8_t *out, size_t need, Launch &&launch) {
+    LifeShared ls;
+    Ctx *ctx;
+    int rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = ctx->reserve(ctx->rgb, need);
+    if (rc == FR_OK) rc = launch(*ctx, ctx->rgb.ptr, ctx->stream);
+    if (rc != FR_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FR_OK;
+}
+
+/* Raw results: launch(ctx, d_z, d_iters, d_dz, d_m, stream) over z (zb bytes) and iters (ib bytes) — either may be NULL,
+ * its device pointer then is too — and, where dz is given, the PT state's second pair dz / m of the same sizes behind them
+ * in the same two scratch buffers.  upload: the arrays go to the device first (the extensions continue them). */
+template <class Launch>
+int host_raw(double *z, size_t zb, uint32_t *iters, size_t ib, double *dz, uint32_t *m, bool upload, Launch &&launch) {
+    LifeShared ls;
+    Ctx *ctx;
+    int rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (z) rc = ctx->reserve(ctx->z, dz ? 2 * zb : zb);
+    if (rc == FR_OK && iters) rc = ctx->reserve(ctx->iters, m ? 2 * ib : ib);
+    if (rc != FR_OK) return rc;
+    char *const d_z = z ? static_cast<char *>(ctx->z.ptr) : nullptr, *const d_iters = iters ? static_cast<char *>(ctx->iters.ptr) : nullptr;
+    const struct {
+        void *host, *dev;
+        size_t bytes;
+    } arrays[4] = {{z, d_z, zb}, {iters, d_iters, ib}, {dz, dz ? d_z + zb : nullptr, zb}, {m, m ? d_iters + ib : nullptr, ib}};
+    if (upload)
+        for (const auto &a : arrays)
+            if (a.host) HIP_TRY(hipMemcpyAsync(a.dev, a.host, a.bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = launch(*ctx, static_cast<double *>(arrays[0].dev), static_cast<uint32_t *>(arrays[1].dev), static_cast<double *>(arrays[2].dev),
+                static_cast<uint32_t *>(arrays[3].dev), ctx->stream);
+    if (rc != FR_OK) return rc;
+    for (const auto &a : arrays)
+        if (a.host) HIP_TRY(hipMemcpyAsync(a.host, a.dev, a.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FR_OK;
+}
+
 /* multi-device teardown hook, called by fr_shutdown / fr_init_devices with the exclusive lock held */
 void multi_shutdown_locked();
 
@@ -304,9 +372,8 @@ void multi_shutdown_locked();
 /* shared body of the host-buffer row renders (fr_host.hip) */
 int fr_host_render_rows(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint8_t *out, size_t out_len,
                         unsigned bytes_per_pixel, const fr_render_opts *opts);
-/* the same for FR_PRECISION_DD / FR_PRECISION_PT with the centre's low halves (fr_host.hip) */
-int fr_host_render_rows_deep(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
-                             uint8_t *out, size_t out_len, unsigned bytes_per_pixel, const fr_render_opts *opts,
-                             const fr_wide_centre *wide = nullptr);
+/* the same for FR_PRECISION_DD / FR_PRECISION_PT with the view's centre (fr_host.hip) */
+int fr_host_render_rows_deep(const fr_config *cfg, int precision, const fr::Centre &c, uint32_t y0, uint32_t y1, uint8_t *out,
+                             size_t out_len, unsigned bytes_per_pixel, const fr_render_opts *opts);
 
 #endif

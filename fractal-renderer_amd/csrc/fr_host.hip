@@ -390,12 +390,7 @@ int host_render_staged(Ctx &ctx, const fr_config *cfg, int precision, const Opts
     mark();
     auto render_on = [&](hipStream_t st, uint32_t ya, uint32_t yb, uint8_t *dst) -> int {
         fr_kparams p;
-        fill_params(cfg, ob, p);
-        p.nrows = yb - ya;
-        p.y_first = ya;
-        p.block_rows = p.nrows;
-        p.y_stride = 0;
-        p.out_rgba = bpp == 4 ? 1u : 0u;
+        rows_params(cfg, ob, ya, yb, bpp, p);
         return render_device(ctx, cfg, p, precision, ob, dst, st);
     };
 
@@ -517,12 +512,7 @@ int host_render_rows(Ctx &ctx, const fr_config *cfg, int precision, const Opts &
     const Opts *use_opts = &o;
     auto render_on = [&](hipStream_t st, uint32_t ya, uint32_t yb, uint8_t *dst) -> int {
         fr_kparams p;
-        fill_params(cfg, *use_opts, p);
-        p.nrows = yb - ya;
-        p.y_first = ya;
-        p.block_rows = p.nrows;
-        p.y_stride = 0;
-        p.out_rgba = bpp == 4 ? 1u : 0u;
+        rows_params(cfg, *use_opts, ya, yb, bpp, p);
         return render_device(ctx, cfg, p, precision, *use_opts, dst, st);
     };
 
@@ -688,12 +678,11 @@ using namespace fr;
 /* Shared body of fr_render_rgb8 / fr_render_rows_rgb8(_opts) / fr_render_rows_rgba8. */
 int fr_host_render_rows(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint8_t *out, size_t out_len,
                         unsigned bpp, const fr_render_opts *opts) {
-    if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
-    if (y0 > y1) return fail(FR_ERR_INVALID_ARGUMENT, "y0 > y1");
-    if (y1 > cfg->height) return fail(FR_ERR_INVALID_ARGUMENT, "y1 > height");
+    int rc = check_rows(cfg, y0, y1);
+    if (rc != FR_OK) return rc;
     if (precision == FR_PRECISION_DD || precision == FR_PRECISION_PT)
-        return fr_host_render_rows_deep(cfg, precision, nullptr, y0, y1, out, out_len, bpp, opts);
-    int rc = check_precision(precision);
+        return fr_host_render_rows_deep(cfg, precision, Centre{}, y0, y1, out, out_len, bpp, opts);
+    rc = check_precision(precision);
     Opts o;
     if (rc == FR_OK) rc = resolve_opts(opts, o);
     if (rc != FR_OK) return rc;
@@ -713,12 +702,10 @@ int fr_host_render_rows(const fr_config *cfg, int precision, uint32_t y0, uint32
 /* FR_PRECISION_DD / FR_PRECISION_PT into a HOST buffer: one kernel into device scratch, one copy, no bands.  A DD pixel
  * costs ~14x an f64 one on the device ("Double-double deep zoom"), and PT serves the long orbits of deep
  * views, so the copy that the f64 road works hard to hide is a few per cent of the call here. */
-int fr_host_render_rows_deep(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
-                             uint8_t *out, size_t out_len, unsigned bpp, const fr_render_opts *opts, const fr_wide_centre *wide) {
-    if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
-    if (y0 > y1) return fail(FR_ERR_INVALID_ARGUMENT, "y0 > y1");
-    if (y1 > cfg->height) return fail(FR_ERR_INVALID_ARGUMENT, "y1 > height");
-    int rc = wide ? check_pt_wide(cfg, wide) : check_precision_lo(cfg, precision, pos_lo);
+int fr_host_render_rows_deep(const fr_config *cfg, int precision, const Centre &c, uint32_t y0, uint32_t y1, uint8_t *out,
+                             size_t out_len, unsigned bpp, const fr_render_opts *opts) {
+    int rc = check_rows(cfg, y0, y1);
+    if (rc == FR_OK) rc = c.check(cfg, precision);
     Opts o;
     if (rc == FR_OK) rc = resolve_opts(opts, o);
     if (rc != FR_OK) return rc;
@@ -727,16 +714,7 @@ int fr_host_render_rows_deep(const fr_config *cfg, int precision, const fr_imagi
     if (!out) return fail(FR_ERR_INVALID_ARGUMENT, "out is NULL");
     if (out_len < need)
         return fail(FR_ERR_BUFFER_TOO_SMALL, bpp == 4 ? "out_len < 4*width*(y1-y0)" : "out_len < 3*width*(y1-y0)");
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    rc = ctx->reserve(ctx->rgb, need);
-    if (rc != FR_OK) return rc;
-    rc = render_deep_device(*ctx, precision, cfg, pos_lo, o, y0, y1, bpp, ctx->rgb.ptr, ctx->stream, wide);
-    if (rc != FR_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FR_OK;
+    return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) {
+        return render_deep_device(ctx, precision, cfg, c, o, y0, y1, bpp, d_out, stream);
+    });
 }

@@ -27,6 +27,9 @@
  * state (z, iters, dz, m); escape_extend_pt_kernel<JULIA> continues such a state to a higher cap in place, on orbits that
  * the host continued from their dd tails instead of recomputing them (orbit_for).  escape_pt_kernel and orbit_pt are the
  * PT definition's and stay as they are.
+ *
+ * The entry points that only PT has live here beside their launches, at the end of the file: the state render and its
+ * extension, and every fr_*_pt_wide call (WIDE PT: the same launches with a Centre that holds a wide centre; fr_ctx.h).
  */
 #include <cmath>
 #include <cstring>
@@ -513,11 +516,11 @@ struct PtOrbit {
 
 namespace {
 
-void view_key(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, double key[6]) {
-    key[0] = wide ? 0.0 : cfg->pos.re; /* a wide view does not read cfg->pos */
-    key[1] = wide ? 0.0 : cfg->pos.im;
-    key[2] = pos_lo ? pos_lo->re : 0.0;
-    key[3] = pos_lo ? pos_lo->im : 0.0;
+void view_key(const fr_config *cfg, const Centre &c, double key[6]) {
+    key[0] = c.wide ? 0.0 : cfg->pos.re; /* a wide view does not read cfg->pos */
+    key[1] = c.wide ? 0.0 : cfg->pos.im;
+    key[2] = c.lo_re();
+    key[3] = c.lo_im();
     key[4] = cfg->algo == 2 ? cfg->julia_set.re : 0.0;
     key[5] = cfg->algo == 2 ? cfg->julia_set.im : 0.0;
 }
@@ -528,9 +531,10 @@ void view_key(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_ce
  * ended by escape is the same at every cap, so if all are, the entry is re-keyed and nothing is computed; otherwise the
  * recurrence goes on from the stored dd tail for the missing entries only, into a NEW PtOrbit — launches in flight hold the
  * old one — whose old entries arrive by a device-to-device copy. */
-int orbit_for(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, std::shared_ptr<PtOrbit> &out) {
+int orbit_for(Ctx &ctx, const fr_config *cfg, const Centre &centre, std::shared_ptr<PtOrbit> &out) {
+    const fr_wide_centre *wide = centre.wide;
     double key[6];
-    view_key(cfg, pos_lo, wide, key);
+    view_key(cfg, centre, key);
     std::vector<uint64_t> wkey; /* one slot, two roads: a wide view never matches a dd view, nor other words or another n */
     if (wide) wide_key(wide, wkey);
     const bool julia = cfg->algo == 2;
@@ -599,9 +603,8 @@ hipError_t launch_state(const fr_kparams &p, uint32_t from, bool extend, double 
 }  // namespace
 
 /* what fr_bla.hip needs of this file: the view's orbits in device memory (orbit_for's), and one orbit on the host */
-int pt_orbit_view(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide,
-                  std::shared_ptr<PtOrbit> &keep, PtOrbitView &v) {
-    const int rc = orbit_for(ctx, cfg, pos_lo, wide, keep);
+int pt_orbit_view(Ctx &ctx, const fr_config *cfg, const Centre &c, std::shared_ptr<PtOrbit> &keep, PtOrbitView &v) {
+    const int rc = orbit_for(ctx, cfg, c, keep);
     if (rc != FR_OK) return rc;
     const bool julia = cfg->algo == 2;
     v.x = keep->dev;
@@ -611,16 +614,16 @@ int pt_orbit_view(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, co
     return FR_OK;
 }
 
-void pt_host_orbit(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *wide, int which, std::vector<double> &out) {
+void pt_host_orbit(const fr_config *cfg, const Centre &c, int which, std::vector<double> &out) {
     OrbitEnd end;
-    if (wide)
-        reference_orbit_wide(cfg, wide, which, out, end);
+    if (c.wide)
+        reference_orbit_wide(cfg, c.wide, which, out, end);
     else
-        reference_orbit(cfg, pos_lo ? pos_lo->re : 0.0, pos_lo ? pos_lo->im : 0.0, which, out, end);
+        reference_orbit(cfg, c.lo_re(), c.lo_im(), which, out, end);
 }
 
-int launch_pt(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, int mode, const fr_kout &out,
-              hipStream_t stream, const char **kernel_name, const fr_wide_centre *wide) {
+int launch_pt(Ctx &ctx, const fr_config *cfg, const Centre &c, const fr_kparams &p, int mode, const fr_kout &out, hipStream_t stream,
+              const char **kernel_name) {
     if (kernel_name) *kernel_name = "escape_pt_kernel";
     if (p.ncols == 0 || p.nrows == 0) return FR_OK;
     const bool julia = cfg->algo == 2;
@@ -629,7 +632,7 @@ int launch_pt(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const 
         return FR_OK;
     }
     std::shared_ptr<PtOrbit> o;
-    const int rc = orbit_for(ctx, cfg, pos_lo, wide, o);
+    const int rc = orbit_for(ctx, cfg, c, o);
     if (rc != FR_OK) return rc;
     if (julia) {
         HIP_TRY(launch<true>(p, mode, out, o->dev, o->dev + o->k_offset, o->x_last, o->k_last, stream));
@@ -639,8 +642,12 @@ int launch_pt(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const 
     return FR_OK;
 }
 
-int launch_pt_state(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, double *z, uint32_t *iters,
-                    double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name, const fr_wide_centre *wide) {
+/* FR_PRECISION_PT with its resumable state (escape_pt_state_kernel, escape_extend_pt_kernel; include/fractal_hip.h, "resumable
+ * perturbation"): the local grid from `p` as launch_pt takes it, z and dz as re, im per pixel, m with bit 31 = on K.  The
+ * extension continues the arrays from from_iterations to p.iterations on the orbits of the new cap, which the context's
+ * cache continues from those of the old one. */
+static int launch_pt_state(Ctx &ctx, const fr_config *cfg, const Centre &c, const fr_kparams &p, double *z, uint32_t *iters, double *dz,
+                           uint32_t *m, hipStream_t stream, const char **kernel_name) {
     if (kernel_name) *kernel_name = "escape_pt_state_kernel";
     if (p.ncols == 0 || p.nrows == 0) return FR_OK;
     const bool julia = cfg->algo == 2;
@@ -649,24 +656,90 @@ int launch_pt_state(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, 
         return FR_OK;
     }
     std::shared_ptr<PtOrbit> o;
-    const int rc = orbit_for(ctx, cfg, pos_lo, wide, o);
+    const int rc = orbit_for(ctx, cfg, c, o);
     if (rc != FR_OK) return rc;
     HIP_TRY(julia ? launch_state<true>(p, 0, false, z, iters, dz, m, o.get(), stream)
                   : launch_state<false>(p, 0, false, z, iters, dz, m, o.get(), stream));
     return FR_OK;
 }
 
-int launch_pt_extend(Ctx &ctx, const fr_config *cfg, const fr_imaginary *pos_lo, const fr_kparams &p, uint32_t from_iterations,
-                     double *z, uint32_t *iters, double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name,
-                     const fr_wide_centre *wide) {
+static int launch_pt_extend(Ctx &ctx, const fr_config *cfg, const Centre &c, const fr_kparams &p, uint32_t from_iterations, double *z,
+                            uint32_t *iters, double *dz, uint32_t *m, hipStream_t stream, const char **kernel_name) {
     if (kernel_name) *kernel_name = "escape_extend_pt_kernel";
     const bool julia = cfg->algo == 2;
     if (p.ncols == 0 || p.nrows == 0 || p.iterations <= from_iterations || (cfg->algo != 0 && !julia)) return FR_OK;
     std::shared_ptr<PtOrbit> o;
-    const int rc = orbit_for(ctx, cfg, pos_lo, wide, o);
+    const int rc = orbit_for(ctx, cfg, c, o);
     if (rc != FR_OK) return rc;
     HIP_TRY(julia ? launch_state<true>(p, from_iterations, true, z, iters, dz, m, o.get(), stream)
                   : launch_state<false>(p, from_iterations, true, z, iters, dz, m, o.get(), stream));
+    return FR_OK;
+}
+
+/* ---- resumable perturbation: FR_PRECISION_PT rows with their state, and that state continued to a higher cap ------- */
+
+/* The domain of the calls (include/fractal_hip.h), checked before any device work: `from` = nullptr for the state render.
+ * *work = false: a legal call with nothing to do (no rows; for the extension also M == N or an algorithm without orbits). */
+static int check_pt_state(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, const void *z,
+                          const void *iters, const void *dz, const void *m, bool *work) {
+    *work = false;
+    int rc = check_rows(cfg, y0, y1);
+    if (rc == FR_OK) rc = c.check(cfg, FR_PRECISION_PT);
+    if (rc != FR_OK) return rc;
+    if (from && cfg->iterations < *from)
+        return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from a stored state");
+    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
+    if (!z || !iters || !dz || !m) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the PT state is z, iters, dz and m, all four");
+    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(dz) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u) ||
+        (reinterpret_cast<uintptr_t>(m) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "z and dz must be 8-byte aligned, iters and m 4-byte aligned");
+    *work = !from || (cfg->iterations != *from && (cfg->algo == FR_ALGO_MANDELBROT || cfg->algo == FR_ALGO_JULIA));
+    return FR_OK;
+}
+
+/* from == nullptr: the state render; else the extension from *from.  On the caller's stream, into the caller's arrays. */
+static int pt_state_launch(Ctx &ctx, const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, double *d_z,
+                           uint32_t *d_iters, double *d_dz, uint32_t *d_m, hipStream_t stream) {
+    fr_kparams p;
+    rows_params(cfg, default_opts(), y0, y1, 0, p);
+    int rc = prof_begin(stream);
+    if (rc != FR_OK) return rc;
+    const char *kname = "";
+    rc = from ? launch_pt_extend(ctx, cfg, c, p, *from, d_z, d_iters, d_dz, d_m, stream, &kname)
+              : launch_pt_state(ctx, cfg, c, p, d_z, d_iters, d_dz, d_m, stream, &kname);
+    if (rc != FR_OK) return rc;
+    return prof_end(stream, kname);
+}
+
+static int pt_state_device(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z, void *d_iters,
+                           void *d_dz, void *d_m, void *hip_stream) {
+    bool work;
+    int rc = check_pt_state(cfg, c, y0, y1, from, d_z, d_iters, d_dz, d_m, &work);
+    if (rc != FR_OK || !work) return rc;
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    return pt_state_launch(*ctx, cfg, c, y0, y1, from, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
+                           static_cast<double *>(d_dz), static_cast<uint32_t *>(d_m), static_cast<hipStream_t>(hip_stream));
+}
+
+/* the host forms: z and dz share the context's z scratch, iters and m its iters scratch */
+static int pt_state_host(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, double *z,
+                         uint32_t *iters, double *dz, uint32_t *m) {
+    bool work;
+    const int rc = check_pt_state(cfg, c, y0, y1, from, z, iters, dz, m, &work);
+    if (rc != FR_OK || !work) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), dz, m, from != nullptr,
+                    [&](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_dz, uint32_t *d_m, hipStream_t stream) {
+                        return pt_state_launch(ctx, cfg, c, y0, y1, from, d_z, d_iters, d_dz, d_m, stream);
+                    });
+}
+
+/* WIDE PT: a NULL centre must not fall through to the dd road */
+static int need_centre(const fr_wide_centre *centre) {
+    if (!centre) return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_PT, wide centre: centre is NULL");
     return FR_OK;
 }
 
@@ -706,4 +779,80 @@ int fr_debug_reference_orbit(const fr_config *cfg, const fr_imaginary *pos_lo, i
     const size_t n = std::min(cap, v.size() / 2);
     if (n) memcpy(out, v.data(), n * 2 * sizeof(double));
     return FR_OK;
+}
+
+/* ---- the calls of the resumable state --------------------------------------------------------------------------------- */
+
+using namespace fr;
+
+int fr_escape_rows_pt_state_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, void *d_z,
+                                   void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
+    return pt_state_device(cfg, Centre{pos_lo, nullptr}, y0, y1, nullptr, d_z, d_iters, d_dz, d_m, hip_stream);
+}
+
+int fr_escape_extend_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, uint32_t from_iterations,
+                               void *d_z, void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
+    return pt_state_device(cfg, Centre{pos_lo, nullptr}, y0, y1, &from_iterations, d_z, d_iters, d_dz, d_m, hip_stream);
+}
+
+int fr_escape_rows_pt_state(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z, uint32_t *iters,
+                            double *dz, uint32_t *m) {
+    return pt_state_host(cfg, Centre{pos_lo, nullptr}, y0, y1, nullptr, z, iters, dz, m);
+}
+
+int fr_escape_extend_pt(const fr_config *cfg, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, uint32_t from_iterations,
+                        double *z, uint32_t *iters, double *dz, uint32_t *m) {
+    return pt_state_host(cfg, Centre{pos_lo, nullptr}, y0, y1, &from_iterations, z, iters, dz, m);
+}
+
+/* ---- WIDE PT (include/fractal_hip.h): the PT calls with a fixed-point view centre in place of (pos, pos_lo) ------------- */
+
+int fr_render_rows_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, int channels, uint8_t *out,
+                           size_t out_len) {
+    int rc = check_channels(channels);
+    if (rc == FR_OK) rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return fr_host_render_rows_deep(cfg, FR_PRECISION_PT, Centre{nullptr, centre}, y0, y1, out, out_len, (unsigned)channels, nullptr);
+}
+
+int fr_render_rows_pt_wide_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, int channels,
+                                  void *d_out, size_t out_len, void *hip_stream) {
+    int rc = check_channels(channels);
+    if (rc == FR_OK) rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return render_rows_device(cfg, FR_PRECISION_PT, Centre{nullptr, centre}, y0, y1, d_out, out_len, hip_stream, (unsigned)channels, nullptr);
+}
+
+int fr_escape_rows_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z, uint32_t *iters) {
+    const int rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return escape_rows(cfg, FR_PRECISION_PT, Centre{nullptr, centre}, y0, y1, z, iters, 2);
+}
+
+int fr_escape_rows_pt_wide_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, void *d_z,
+                                        void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
+    const int rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return pt_state_device(cfg, Centre{nullptr, centre}, y0, y1, nullptr, d_z, d_iters, d_dz, d_m, hip_stream);
+}
+
+int fr_escape_extend_pt_wide_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
+                                    uint32_t from_iterations, void *d_z, void *d_iters, void *d_dz, void *d_m, void *hip_stream) {
+    const int rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return pt_state_device(cfg, Centre{nullptr, centre}, y0, y1, &from_iterations, d_z, d_iters, d_dz, d_m, hip_stream);
+}
+
+int fr_escape_rows_pt_wide_state(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z,
+                                 uint32_t *iters, double *dz, uint32_t *m) {
+    const int rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return pt_state_host(cfg, Centre{nullptr, centre}, y0, y1, nullptr, z, iters, dz, m);
+}
+
+int fr_escape_extend_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, uint32_t from_iterations,
+                             double *z, uint32_t *iters, double *dz, uint32_t *m) {
+    const int rc = need_centre(centre);
+    if (rc != FR_OK) return rc;
+    return pt_state_host(cfg, Centre{nullptr, centre}, y0, y1, &from_iterations, z, iters, dz, m);
 }

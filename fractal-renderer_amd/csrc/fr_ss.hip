@@ -203,11 +203,6 @@ struct SsPlan {
     size_t min_bytes, best_bytes;
 };
 
-int ss_channels(int channels) {
-    if (channels != 3 && channels != 4) return fail(FR_ERR_INVALID_ARGUMENT, "channels must be 3 (RGB) or 4 (RGBA)");
-    return FR_OK;
-}
-
 /* the part of the domain that needs no precision: cfg, s, the sizes, the rows */
 int ss_plan(const fr_config *cfg, uint32_t s, uint32_t y0, uint32_t y1, SsPlan &pl) {
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
@@ -216,8 +211,8 @@ int ss_plan(const fr_config *cfg, uint32_t s, uint32_t y0, uint32_t y1, SsPlan &
         return fail(FR_ERR_INVALID_ARGUMENT, "supersample * width does not fit in 32 bits");
     if ((uint64_t)cfg->height * s > 0xFFFFFFFFull)
         return fail(FR_ERR_INVALID_ARGUMENT, "supersample * height does not fit in 32 bits");
-    if (y0 > y1) return fail(FR_ERR_INVALID_ARGUMENT, "y0 > y1");
-    if (y1 > cfg->height) return fail(FR_ERR_INVALID_ARGUMENT, "y1 > height");
+    const int rc = check_rows(cfg, y0, y1); /* (cfg was read above: its NULL check stays in front of the sizes') */
+    if (rc != FR_OK) return rc;
     pl.cfg_s = *cfg;
     pl.cfg_s.width = cfg->width * s;
     pl.cfg_s.height = cfg->height * s;
@@ -271,15 +266,10 @@ int render_ss_device(Ctx &ctx, const SsPlan &pl, int precision, const fr_imagina
     for (uint64_t ya = Y0; ya < Y1 && rc == FR_OK; ya += band) {
         const uint32_t yb = (uint32_t)std::min<uint64_t>(ya + band, Y1);
         if (deep) {
-            rc = render_deep_device(ctx, precision, cs, pos_lo, o, (uint32_t)ya, yb, 3, d_work, stream);
+            rc = render_deep_device(ctx, precision, cs, Centre{pos_lo, nullptr}, o, (uint32_t)ya, yb, 3, d_work, stream);
         } else {
             fr_kparams p;
-            fill_params(cs, ob, p);
-            p.nrows = yb - (uint32_t)ya;
-            p.y_first = (uint32_t)ya;
-            p.block_rows = p.nrows;
-            p.y_stride = 0;
-            p.out_rgba = 0;
+            rows_params(cs, ob, (uint32_t)ya, yb, 3, p);
             rc = render_device(ctx, cs, p, precision, ob, d_work, stream);
         }
         if (rc != FR_OK) break;
@@ -297,7 +287,7 @@ int render_ss_device(Ctx &ctx, const SsPlan &pl, int precision, const fr_imagina
 int ss_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t s, uint32_t y0, uint32_t y1,
              int channels, const fr_render_opts *opts, SsPlan &pl, Opts &o) {
     int rc = ss_plan(cfg, s, y0, y1, pl);
-    if (rc == FR_OK) rc = ss_channels(channels);
+    if (rc == FR_OK) rc = check_channels(channels);
     if (rc != FR_OK) return rc;
     if (pos_lo && precision != FR_PRECISION_DD && precision != FR_PRECISION_PT)
         return fail(FR_ERR_INVALID_ARGUMENT, "pos_lo must be NULL unless precision is FR_PRECISION_DD or FR_PRECISION_PT");
@@ -310,7 +300,7 @@ int box_filter_check(uint32_t width, uint32_t rows, uint32_t s, int channels) {
     if (s < 1 || s > FR_SS_MAX) return fail(FR_ERR_INVALID_ARGUMENT, "supersample must be 1 .. FR_SS_MAX (8)");
     if ((uint64_t)width * s > 0xFFFFFFFFull || (uint64_t)rows * s > 0xFFFFFFFFull)
         return fail(FR_ERR_INVALID_ARGUMENT, "supersample * width and supersample * rows must fit in 32 bits");
-    return ss_channels(channels);
+    return check_channels(channels);
 }
 
 }  // namespace
@@ -355,14 +345,9 @@ int fr_render_rows_ss_device(const fr_config *cfg, int precision, const fr_imagi
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     if (supersample == 1) { /* the plain render, byte for byte */
         if (precision == FR_PRECISION_DD || precision == FR_PRECISION_PT)
-            return render_deep_device(*ctx, precision, cfg, pos_lo, o, y0, y1, (unsigned)channels, d_out, stream);
+            return render_deep_device(*ctx, precision, cfg, Centre{pos_lo, nullptr}, o, y0, y1, (unsigned)channels, d_out, stream);
         fr_kparams p;
-        fill_params(cfg, o, p);
-        p.nrows = y1 - y0;
-        p.y_first = y0;
-        p.block_rows = p.nrows;
-        p.y_stride = 0;
-        p.out_rgba = channels == 4 ? 1u : 0u;
+        rows_params(cfg, o, y0, y1, (unsigned)channels, p);
         return render_device(*ctx, cfg, p, precision, o, d_out, stream);
     }
     return render_ss_device(*ctx, pl, precision, pos_lo, supersample, y0, (unsigned)channels, d_out, d_work, work_len,
@@ -381,27 +366,17 @@ int fr_render_rows_ss(const fr_config *cfg, int precision, const fr_imaginary *p
     if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*(y1-y0)");
     if (supersample == 1) { /* the plain host roads */
         if (precision == FR_PRECISION_DD || precision == FR_PRECISION_PT)
-            return fr_host_render_rows_deep(cfg, precision, pos_lo, y0, y1, out, out_len, (unsigned)channels, opts);
+            return fr_host_render_rows_deep(cfg, precision, Centre{pos_lo, nullptr}, y0, y1, out, out_len, (unsigned)channels, opts);
         return fr_host_render_rows(cfg, precision, y0, y1, out, out_len, (unsigned)channels, opts);
     }
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t work_len = std::max(pl.min_bytes, std::min(pl.best_bytes, kSsHostWorkCap));
-    rc = ctx->reserve(ctx->rgb, need);
-    if (rc == FR_OK) rc = ctx->reserve(ctx->ss_work, work_len);
-    if (rc != FR_OK) return rc;
-    rc = render_ss_device(*ctx, pl, precision, pos_lo, supersample, y0, (unsigned)channels, ctx->rgb.ptr, ctx->ss_work.ptr,
-                          work_len, ctx->stream, o);
-    if (rc != FR_OK) {
-        (void)hipStreamSynchronize(ctx->stream); /* the scratch is reused by the next call */
+    return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) {
+        int rc = ctx.reserve(ctx.ss_work, work_len);
+        if (rc != FR_OK) return rc;
+        rc = render_ss_device(ctx, pl, precision, pos_lo, supersample, y0, (unsigned)channels, d_out, ctx.ss_work.ptr, work_len, stream, o);
+        if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
         return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FR_OK;
+    });
 }
 
 int fr_box_filter_rgb8_device(const void *d_src, uint32_t width, uint32_t rows, uint32_t supersample, int channels,
