@@ -140,9 +140,10 @@ class WideCentre:
         return _native.fr_wide_centre(self.words, self.re.ctypes.data_as(p64), self.im.ctypes.data_as(p64))
 
 
-def _deep_call(precision, pos_lo=None, centre=None, bla=None, supersample=1, opts=None):
-    """Which C family a call's keyword arguments select, in the order bla, centre, supersample, pos_lo:
+def _deep_call(precision, pos_lo=None, centre=None, bla=None, supersample=1, opts=None, scaled=False):
+    """Which C family a call's keyword arguments select, in the order bla, centre, scaled, supersample, pos_lo:
     (family, the family's leading arguments behind the config, what keeps their memory alive).
+      "scaled" (centre pointer, bits)                  the fr_*_pt_scaled calls; bits -1 without bla=
       "bla"   (pos_lo pointer, centre pointer, bits)   the fr_*_pt_bla calls
       "wide"  (centre pointer,)                        the fr_*_pt_wide calls
       "ss"    (pos_lo pointer,)                        fr_render_rows_ss
@@ -166,9 +167,15 @@ def _deep_call(precision, pos_lo=None, centre=None, bla=None, supersample=1, opt
         if supersample != 1:
             raise ValueError("supersample does not take centre= yet")
         st = centre.c_struct()
+        if scaled:
+            if opts is not None:
+                raise ValueError("scaled= takes no opts: SCALED PT has one kernel per form")
+            return "scaled", (C.byref(st), -1 if bla is None else bits), (st, centre)
         if bla is not None:
             return "bla", (None, C.byref(st), bits), (st, centre)
         return "wide", (C.byref(st),), (st, centre)
+    if scaled:
+        raise ValueError("scaled= needs centre= (a WideCentre); it takes neither pos_lo= nor supersample")
     lo = None if pos_lo is None else Imaginary(*(float(v) for v in pos_lo))
     lo_ptr = None if lo is None else C.byref(lo)
     if bla is not None:
@@ -193,12 +200,20 @@ def reference_orbit_wide(config, centre, which=0):
 BLA_DEFAULT_BITS = _native.FR_BLA_DEFAULT_BITS
 
 
-def bla_table(config, level, which=0, pos_lo=None, centre=None, bla=0):
+def bla_table(config, level, which=0, pos_lo=None, centre=None, bla=0, scaled=False):
     """fr_debug_bla_table: level `level` of the BLA-PT table of orbit `which` (0: R or V, 1: K, Julia only) on the host (no
-    device needed): float64 [n_level, 5] = A.re, A.im, B.re, B.im, r2; empty past the top level."""
-    _, (lo, ptr, bits), _keep = _deep_call(Precision.PT, pos_lo, centre, bla)
-    n = C.c_uint32(0)
+    device needed): float64 [n_level, 5] = A.re, A.im, B.re, B.im, r2; empty past the top level.
+    scaled=True (needs centre=): fr_debug_bla_table_scaled, SCALED PT's table, whose fifth column is the stored R."""
     lib = _native.load()
+    n = C.c_uint32(0)
+    if scaled:
+        _, (ptr, bits), _keep = _deep_call(Precision.PT, pos_lo, centre, bla, scaled=True)
+        _native.check(lib.fr_debug_bla_table_scaled(C.byref(config), ptr, bits, int(which), int(level), None, 0, C.byref(n)))
+        out = np.empty((n.value, 5), dtype=np.float64)
+        _native.check(lib.fr_debug_bla_table_scaled(C.byref(config), ptr, bits, int(which), int(level), out.ctypes.data, len(out),
+                                                    C.byref(n)))
+        return out
+    _, (lo, ptr, bits), _keep = _deep_call(Precision.PT, pos_lo, centre, bla)
     _native.check(lib.fr_debug_bla_table(C.byref(config), lo, ptr, bits, int(which), int(level), None, 0, C.byref(n)))
     out = np.empty((n.value, 5), dtype=np.float64)
     _native.check(lib.fr_debug_bla_table(C.byref(config), lo, ptr, bits, int(which), int(level), out.ctypes.data, len(out), C.byref(n)))
@@ -212,6 +227,16 @@ def bla_count(config, y0=0, y1=None, pos_lo=None, centre=None, bla=0):
     _, (lo, ptr, bits), _keep = _deep_call(Precision.PT, pos_lo, centre, bla)
     passes, steps = C.c_uint64(0), C.c_uint64(0)
     _native.check(_native.load().fr_debug_bla_count(C.byref(config), lo, ptr, bits, y0, y1, C.byref(passes), C.byref(steps)))
+    return passes.value, steps.value
+
+
+def pt_scaled_count(config, centre, y0=0, y1=None, bla=None):
+    """fr_debug_pt_scaled_count over rows [y0, y1): (passes through the scaled loop, nominal iterations), summed over the
+    pixels on the device; bla=None: the plain scaled loop, one pass per step."""
+    y1 = config.height if y1 is None else y1
+    _, (ptr, bits), _keep = _deep_call(Precision.PT, None, centre, bla, scaled=True)
+    passes, steps = C.c_uint64(0), C.c_uint64(0)
+    _native.check(_native.load().fr_debug_pt_scaled_count(C.byref(config), ptr, bits, y0, y1, C.byref(passes), C.byref(steps)))
     return passes.value, steps.value
 
 
@@ -305,13 +330,15 @@ def device_name():
 SS_MAX = 8  # FR_SS_MAX
 
 
-def _render_rows(config, y0, y1, channels, out, precision, opts, pos_lo, supersample, centre, bla):
+def _render_rows(config, y0, y1, channels, out, precision, opts, pos_lo, supersample, centre, bla, scaled=False):
     """rows [y0, y1) into `out` as `channels` bytes per pixel, by the C row render of the arguments' family"""
     lib, cfg = _native.load(), C.byref(config)
-    family, pre, _keep = _deep_call(precision, pos_lo, centre, bla, supersample, opts)
+    family, pre, _keep = _deep_call(precision, pos_lo, centre, bla, supersample, opts, scaled)
     o = C.byref(opts) if opts is not None else None
     tail = (y0, y1, channels, out.ctypes.data, out.nbytes)
-    if family == "bla":
+    if family == "scaled":
+        rc = lib.fr_render_rows_pt_scaled(cfg, *pre, *tail)
+    elif family == "bla":
         rc = lib.fr_render_rows_pt_bla(cfg, *pre, *tail)
     elif family == "wide":
         rc = lib.fr_render_rows_pt_wide(cfg, *pre, *tail)
@@ -351,7 +378,7 @@ def box_filter(image, s, channels=3):
 
 
 def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None, pos_lo=None, supersample=1, centre=None,
-                   bla=None):
+                   bla=None, scaled=False):
     """Rows [y0, y1) of get_image — the unit of the reference's rayon loop (src/lib.rs:256-264).
     Returns uint8 [y1-y0, width, 3].  pos_lo (Precision.DD or Precision.PT only): the low halves (re, im) of the view
     centre (split_dd), so that the centre is pos + pos_lo; None = (0, 0).
@@ -360,22 +387,25 @@ def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None,
     centre (Precision.PT only, exclusive with pos_lo): a WideCentre in place of (config.pos, pos_lo) for views past a scale
     of 10^30 (include/fractal_hip.h, "WIDE PT"); supersample does not take it yet.
     bla (Precision.PT only, with pos_lo or centre or neither): None = plain PT; 0 or 24 .. 53 = BLA-PT at that many bits
-    (0: BLA_DEFAULT_BITS), PT with iterations skipped in bulk — an approximation, defined in include/fractal_hip.h, "BLA-PT"."""
+    (0: BLA_DEFAULT_BITS), PT with iterations skipped in bulk — an approximation, defined in include/fractal_hip.h, "BLA-PT".
+    scaled=True (needs centre=; combines with bla=; no pos_lo, supersample or opts): SCALED PT, the pixel loop that carries
+    its offsets scaled by the view's exponent, for scales past 2^440 up to just under 2^952 (include/fractal_hip.h,
+    "SCALED PT"); inside WIDE PT's domain it gives the same bytes as the call without it."""
     if out is None:
         out = np.empty((max(int(y1) - int(y0), 0), config.width, 3), dtype=np.uint8)
-    return _render_rows(config, y0, y1, 3, out, precision, opts, pos_lo, supersample, centre, bla)
+    return _render_rows(config, y0, y1, 3, out, precision, opts, pos_lo, supersample, centre, bla, scaled)
 
 
-def get_image(config, precision=Precision.F64, pos_lo=None, supersample=1, centre=None, bla=None):
+def get_image(config, precision=Precision.F64, pos_lo=None, supersample=1, centre=None, bla=None, scaled=False):
     """get_image(&Config) -> Vec<RGB> (src/lib.rs:253-270): uint8 [height, width, 3], row-major,
     bytes r,g,b.  Algo.BarnsleyFern is outside this path (random IFS, src/lib.rs:271-319): the
     per-pixel function returns BLACK for it (calc/src/lib.rs:211) and so does this.
-    pos_lo: see get_image_rows (Precision.DD or Precision.PT only).  supersample, centre, bla: see get_image_rows."""
+    pos_lo: see get_image_rows (Precision.DD or Precision.PT only).  supersample, centre, bla, scaled: see get_image_rows."""
     out = np.empty((config.height, config.width, 3), dtype=np.uint8)
-    if bla is None and centre is None and supersample == 1 and pos_lo is None and int(precision) == Precision.F64:
+    if not scaled and bla is None and centre is None and supersample == 1 and pos_lo is None and int(precision) == Precision.F64:
         _native.check(_native.load().fr_render_rgb8(C.byref(config), out.ctypes.data, out.nbytes))
         return out
-    return _render_rows(config, 0, config.height, 3, out, precision, None, pos_lo, supersample, centre, bla)
+    return _render_rows(config, 0, config.height, 3, out, precision, None, pos_lo, supersample, centre, bla, scaled)
 
 
 def _dd_only(precision):
@@ -401,13 +431,13 @@ def get_image_fern(config, threads=1, seed=0, walkers=0):
     return out
 
 
-def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None, supersample=1, centre=None, bla=None):
+def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None, supersample=1, centre=None, bla=None, scaled=False):
     """get_image as RGBA8 (alpha 255): uint8 [height, width, 4] — the GUI's upload format
     (src/gui.rs:71-72) produced on the device.  pos_lo: see get_image_rows (Precision.DD or Precision.PT only).
-    supersample, centre, bla: see get_image_rows."""
+    supersample, centre, bla, scaled: see get_image_rows."""
     if out is None:
         out = np.empty((config.height, config.width, 4), dtype=np.uint8)
-    return _render_rows(config, 0, config.height, 4, out, precision, None, pos_lo, supersample, centre, bla)
+    return _render_rows(config, 0, config.height, 4, out, precision, None, pos_lo, supersample, centre, bla, scaled)
 
 
 def get_recursive_pixel(config, x, y, precision=Precision.F64):
@@ -442,19 +472,22 @@ def recursive_batch(iterations, start, c, limit, precision=Precision.F64):
     return pos, it
 
 
-def escape_rows(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, with_lo=False, centre=None, bla=None):
+def escape_rows(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, with_lo=False, centre=None, bla=None, scaled=False):
     """recursive() results of every pixel of rows [y0, y1): (z float64 [rows, width, 2],
     iters uint32 [rows, width]).  Precision.DD: z holds the hi parts; with_lo=True returns z as [rows, width, 4] =
     re.hi, re.lo, im.hi, im.lo (Precision.DD only).  pos_lo: see get_image_rows (Precision.DD or Precision.PT only).
     centre: a WideCentre (Precision.PT only, exclusive with pos_lo): fr_escape_rows_pt_wide.
-    bla (Precision.PT only): see get_image_rows; fr_escape_rows_pt_bla."""
+    bla (Precision.PT only): see get_image_rows; fr_escape_rows_pt_bla.
+    scaled (needs centre=; combines with bla=): see get_image_rows; fr_escape_rows_pt_scaled."""
     y1 = config.height if y1 is None else y1
     if with_lo and (bla is not None or centre is not None):
         raise ValueError("with_lo needs precision=Precision.DD")
     lib = _native.load()
-    family, pre, _keep = _deep_call(precision, pos_lo, centre, bla)
+    family, pre, _keep = _deep_call(precision, pos_lo, centre, bla, scaled=scaled)
     zw = 2
-    if family == "bla":
+    if family == "scaled":
+        fn = lib.fr_escape_rows_pt_scaled
+    elif family == "bla":
         fn = lib.fr_escape_rows_pt_bla
     elif family == "wide":
         fn = lib.fr_escape_rows_pt_wide

@@ -12,6 +12,8 @@
 // the word count the scale asks for, and scales up to 2^440 render — include/fractal_hip.h, "WIDE PT");
 // --bla or --bla=BITS beside --perturbation (BLA-PT: the same view with iterations skipped in bulk, an approximation defined
 // in include/fractal_hip.h, "BLA-PT"; BITS is 24 .. 53, default 40);
+// --scaled beside --perturbation (SCALED PT: the pixel loop that carries its offsets scaled by the view's exponent, so scales
+// past 2^440 render, up to just under 2^952; it combines with --bla — include/fractal_hip.h, "SCALED PT");
 // for -a fern: --threads N (the rayon thread count being stood in for; default: this machine's hardware
 // threads, what rayon would use) and --seed N (default: from the OS, as the reference seeds from entropy).
 // Not handled here (by design): --gui, --open.
@@ -71,7 +73,7 @@ int main(int argc, char **argv) {
                 exposure = "5", filename = "output", algo_s = "mandelbrot", color_weight = "0.01";
     std::optional<std::string> iterations, pos_x, scale_x, scale_y, primary, secondary, julia_re, julia_im, devices, threads_s,
         seed_s, supersample_s;
-    bool disable_inside = false, unsmooth = false, f32 = false, quiet = false, perturbation = false, bla = false;
+    bool disable_inside = false, unsmooth = false, f32 = false, quiet = false, perturbation = false, bla = false, scaled = false;
     int bla_bits = 0;
     std::vector<std::string> positionals;
 
@@ -101,6 +103,7 @@ int main(int argc, char **argv) {
         else if (a == "-w" || a == "--color-weight") color_weight = value(i, "-w");
         else if (a == "--f32") f32 = true;       // this build's extension (no counterpart upstream)
         else if (a == "--perturbation") perturbation = true; // this build's extension: deep zooms on a wide centre
+        else if (a == "--scaled") scaled = true; // SCALED PT: views past 2^440
         else if (a == "--bla") bla = true; // BLA-PT at the default bits
         else if (a.rfind("--bla=", 0) == 0) { // ... or at 24 .. 53 (written with '=': a bare number after --bla is <width>)
             bla = true;
@@ -133,6 +136,7 @@ int main(int argc, char **argv) {
     if (perturbation && (f32 || supersample_s || devices || algo == Algo::BarnsleyFern))
         die("--perturbation does not combine with --f32, --supersample, --devices or -a fern");
     if (bla && !perturbation) die("--bla needs --perturbation");
+    if (scaled && !perturbation) die("--scaled needs --perturbation");
 
     // src/lib.rs:207-226
     Config cfg = Config::make(algo);
@@ -194,7 +198,8 @@ int main(int argc, char **argv) {
         } else if (perturbation) {
             // the centre keeps every digit of -x / -y; cfg.pos (their f64 roundings) is not read
             const WideCentre centre = WideCentre::from_decimal(pos_x_s, pos_y, WideCentre::words_for_scale(cfg.scale.re, cfg.scale.im));
-            image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}) : get_image(cfg, centre.c());
+            if (scaled) image = get_image(cfg, centre.c(), Scaled{bla ? bla_bits : -1});
+            else image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}) : get_image(cfg, centre.c());
         } else {
             const int precision = f32 ? FR_PRECISION_F32 : FR_PRECISION_F64;
             image = supersample_s ? get_image(cfg, precision, to_u32(*supersample_s, "--supersample")) : get_image(cfg, precision);

@@ -759,7 +759,7 @@ int check_precision_lo(const fr_config *cfg, int precision, const fr_imaginary *
 int check_precision_or_deep(const fr_config *cfg, int precision) { return check_precision_lo(cfg, precision, nullptr); }
 
 int Centre::check(const fr_config *cfg, int precision) const {
-    return wide ? check_pt_wide(cfg, wide) : check_precision_lo(cfg, precision, pos_lo);
+    return wide || scaled ? check_pt_wide(cfg, wide, scaled) : check_precision_lo(cfg, precision, pos_lo);
 }
 
 int prof_begin(hipStream_t stream) {

@@ -6,7 +6,9 @@
  *
  * Host part: the table of an orbit, built from its stored f64 entries alone (the orbit comes from fr_pt.hip's cache, dd or
  * wide), with -ffp-contract=off and std::fma exactly where the definition has fma; uploaded once and kept per context
- * (Ctx::bla_table, under Ctx::pt_mu), keyed by the orbit's identity, D and bits.
+ * (Ctx::bla_table, under Ctx::pt_mu), keyed by the orbit's identity, D and bits.  SCALED PT's table (fr_scaled.hip) is the
+ * same build with eps S for eps, Dw for D and the scaled radius R stored where BLA-PT stores r2; it shares the slot, with its
+ * kind in the key (fr_bla.h).
  *
  * Device layout of one orbit's table: the levels k >= 1 one after another (level 0 only builds the levels above it and never
  * leaves the host); level k starts at entry bla_level_offset(n0, k), a closed form, so the kernel needs no offset array.  r2
@@ -33,20 +35,10 @@
 #include <memory>
 #include <vector>
 
+#include "fr_bla.h"
 #include "fr_ctx.h"
 #include "fr_math.h"
 #include "fr_wide.h"
-
-/* first entry of level k >= 1 among the levels 1, 2, ... of a table whose level 0 has n0 entries: the sum of n0 >> l over
- * l = 1 .. k-1, from the identity  sum over l >= 1 of (n >> l) = n - popcount(n)  applied to n0 and to n0 >> (k-1) */
-__host__ __device__ __forceinline__ uint32_t bla_level_offset(uint32_t n0, uint32_t k) {
-    const uint32_t t = n0 >> (k - 1);
-#ifdef __HIP_DEVICE_COMPILE__
-    return (n0 - (uint32_t)__popc(n0)) - (t - (uint32_t)__popc(t));
-#else
-    return (n0 - (uint32_t)__builtin_popcount(n0)) - (t - (uint32_t)__builtin_popcount(t));
-#endif
-}
 
 namespace {
 
@@ -265,7 +257,7 @@ hipError_t launch(const fr_kparams &p, int mode, const fr_kout &out, const BlaDe
 struct HostTable {
     uint32_t n0 = 0;          /* entries of level 0; 0: the table is empty */
     std::vector<double> coef; /* A.re, A.im, B.re, B.im per entry */
-    std::vector<double> r2;
+    std::vector<double> rad;  /* what an entry stores for the level search: r2, or SCALED PT's R */
     uint32_t levels() const { /* level 0 included */
         uint32_t k = 0;
         for (uint32_t n = n0; n; n >>= 1) k++;
@@ -301,16 +293,22 @@ Entry merge(const Entry &x, const Entry &y, double D) {
     return e;
 }
 
-/* X: re, im pairs of the entries 0 .. last */
-void build_table(const double *X, uint32_t last, double D, double b0, int bits, HostTable &t) {
+/* what an entry with radius r stores: BLA-PT r2 = r*r; SCALED PT (include/fractal_hip.h) R itself, or 0 below 2^-53 */
+double stored_radius(double r, bool scaled) {
+    if (!scaled) return r * r;
+    return r < 0x1p-53 ? 0.0 : r;
+}
+
+/* X: re, im pairs of the entries 0 .. last.  BLA-PT: S = 1 and D of the image; SCALED PT: S = 2^e and Dw (eps S is exact) */
+void build_table(const double *X, uint32_t last, double D, double b0, int bits, double S, bool scaled, HostTable &t) {
     t = HostTable();
     if (last < 2) return;
-    const double eps = std::ldexp(1.0, -bits);
+    const double eps = std::ldexp(1.0, -bits) * S;
     uint32_t n = last - 1;
     t.n0 = n;
     const size_t total = n - (uint32_t)__builtin_popcount(n);
     t.coef.resize(4 * total);
-    t.r2.resize(total);
+    t.rad.resize(total);
     std::vector<Entry> cur(n);
     for (uint32_t j = 0; j < n; j++) cur[j] = level0(X, j, b0, eps);
     size_t at = 0;
@@ -321,7 +319,7 @@ void build_table(const double *X, uint32_t last, double D, double b0, int bits, 
             cur[j] = e;
             double *c = &t.coef[4 * (at + j)];
             c[0] = e.are, c[1] = e.aim, c[2] = e.bre, c[3] = e.bim;
-            t.r2[at + j] = e.r * e.r;
+            t.rad[at + j] = stored_radius(e.r, scaled);
         }
         at += n;
     }
@@ -342,33 +340,23 @@ double image_D(const fr_config *cfg) {
 
 namespace fr {
 
-/* the tables of one view in device memory: one allocation, coefficients first (32-byte entries stay aligned) */
-struct BlaTable {
-    std::weak_ptr<PtOrbit> orbit; /* identity of the orbits the tables were built from; holds no device memory alive */
-    double D = 0.0;
-    int bits = 0;
-    void *dev = nullptr;
-    BlaDev view{};
-    uint32_t x_levels = 0, entries = 0; /* fr_debug_bla_cache */
-    bool built = false;                 /* the last request built the tables */
-    ~BlaTable() {
-        if (dev) (void)hipFree(dev); /* hipFree waits for the device: no kernel still reads the tables */
-    }
-};
-
-namespace {
-
-/* The view's orbits (`orbit` holds them, `v` points into them) and tables, from the context's caches or built and uploaded;
- * the caller keeps `orbit` and `out` alive until its launch has been enqueued. */
-int table_for(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, std::shared_ptr<PtOrbit> &orbit, PtOrbitView &v,
-              std::shared_ptr<BlaTable> &out) {
+/* fr_bla.h: one slot per context for both kinds of table, keyed by the orbit, D (or Dw), bits and the kind */
+int bla_table_for(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, bool scaled, std::shared_ptr<PtOrbit> &orbit,
+                  PtOrbitView &v, std::shared_ptr<BlaTable> &out) {
     const int rc = pt_orbit_view(ctx, cfg, c, orbit, v);
     if (rc != FR_OK) return rc;
     const bool julia = cfg->algo == 2;
-    const double D = image_D(cfg);
+    fr_config image = *cfg; /* Dw is D of the image with the scaled divisors (sre, sim) */
+    double S = 1.0;
+    if (scaled) {
+        const ScaledConsts k = scaled_consts(cfg);
+        image.scale.re = k.sre, image.scale.im = k.sim, S = k.S;
+    }
+    const double D = image_D(&image);
     std::lock_guard<std::mutex> lk(ctx.pt_mu);
     const std::shared_ptr<BlaTable> cached = ctx.bla_table;
-    if (cached && cached->orbit.lock() == orbit && memcmp(&cached->D, &D, sizeof D) == 0 && cached->bits == bits) {
+    if (cached && cached->orbit.lock() == orbit && memcmp(&cached->D, &D, sizeof D) == 0 && cached->bits == bits &&
+        cached->scaled == scaled) {
         cached->built = false;
         out = cached;
         return FR_OK;
@@ -380,14 +368,14 @@ int table_for(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, std::sh
     if (k_n) HIP_TRY(hipMemcpy(host.data() + 2 * x_n, v.k, k_n * sizeof(double2), hipMemcpyDeviceToHost));
     const double b0 = julia ? 0.0 : 1.0;
     HostTable tx, tk;
-    build_table(host.data(), v.x_last, D, b0, bits, tx);
-    if (julia) build_table(host.data() + 2 * x_n, v.k_last, D, b0, bits, tk);
-    const size_t xe = tx.r2.size(), ke = tk.r2.size(), cw = julia ? 2 : 4; /* doubles per coefficient entry */
+    build_table(host.data(), v.x_last, D, b0, bits, S, scaled, tx);
+    if (julia) build_table(host.data() + 2 * x_n, v.k_last, D, b0, bits, S, scaled, tk);
+    const size_t xe = tx.rad.size(), ke = tk.rad.size(), cw = julia ? 2 : 4; /* doubles per coefficient entry */
     std::vector<double> up(cw * (xe + ke) + xe + ke);
-    const auto pack = [&](const HostTable &t, double *coef, double *r2) {
-        for (size_t e = 0; e < t.r2.size(); e++)
+    const auto pack = [&](const HostTable &t, double *coef, double *rad) {
+        for (size_t e = 0; e < t.rad.size(); e++)
             for (size_t w = 0; w < cw; w++) coef[cw * e + w] = t.coef[4 * e + w];
-        if (!t.r2.empty()) memcpy(r2, t.r2.data(), t.r2.size() * sizeof(double));
+        if (!t.rad.empty()) memcpy(rad, t.rad.data(), t.rad.size() * sizeof(double));
     };
     double *h_xc = up.data(), *h_kc = h_xc + cw * xe, *h_xr = h_kc + cw * ke, *h_kr = h_xr + xe;
     pack(tx, h_xc, h_xr);
@@ -396,6 +384,7 @@ int table_for(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, std::sh
     t->orbit = orbit;
     t->D = D;
     t->bits = bits;
+    t->scaled = scaled;
     t->x_levels = tx.levels();
     t->entries = (uint32_t)(tx.entries() + tk.entries());
     t->built = true;
@@ -405,17 +394,19 @@ int table_for(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, std::sh
         HIP_TRY(hipMemcpy(t->dev, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     const double *d = static_cast<const double *>(t->dev);
-    BlaDev &b = t->view;
+    BlaTableDev &b = t->view;
     b.x_coef = d;
     b.k_coef = julia ? d + cw * xe : d;
-    b.x_r2 = d + cw * (xe + ke);
-    b.k_r2 = julia ? b.x_r2 + xe : b.x_r2;
+    b.x_rad = d + cw * (xe + ke);
+    b.k_rad = julia ? b.x_rad + xe : b.x_rad;
     b.x_n0 = tx.n0;
     b.k_n0 = julia ? tk.n0 : tx.n0;
     ctx.bla_table = t;
     out = std::move(t);
     return FR_OK;
 }
+
+namespace {
 
 int launch_bla(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_kparams &p, int mode, const fr_kout &out,
                hipStream_t stream) {
@@ -428,9 +419,13 @@ int launch_bla(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const 
     std::shared_ptr<PtOrbit> orbit;
     std::shared_ptr<BlaTable> table;
     PtOrbitView v;
-    const int rc = table_for(ctx, cfg, c, bits, orbit, v, table);
+    const int rc = bla_table_for(ctx, cfg, c, bits, false, orbit, v, table);
     if (rc != FR_OK) return rc;
-    BlaDev t = table->view;
+    const BlaTableDev &d = table->view;
+    BlaDev t{};
+    t.x_r2 = d.x_rad, t.k_r2 = d.k_rad;
+    t.x_coef = d.x_coef, t.k_coef = d.k_coef;
+    t.x_n0 = d.x_n0, t.k_n0 = d.k_n0;
     t.x_orbit = v.x;
     t.k_orbit = v.k;
     t.x_last = v.x_last;
@@ -576,8 +571,13 @@ int fr_debug_bla_count(const fr_config *cfg, const fr_imaginary *pos_lo, const f
 int fr_debug_bla_table(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, int which,
                        uint32_t level, double *out, size_t cap, uint32_t *len) {
     const Centre c{pos_lo, centre};
-    int rc = check_bla(cfg, c, bits, 0, 0);
+    const int rc = check_bla(cfg, c, bits, 0, 0);
     if (rc != FR_OK) return rc;
+    return bla_debug_table(cfg, c, bits, false, which, level, out, cap, len);
+}
+
+int fr::bla_debug_table(const fr_config *cfg, const Centre &c, int bits, bool scaled, int which, uint32_t level, double *out,
+                        size_t cap, uint32_t *len) {
     if (cfg->algo != 0 && cfg->algo != 2) return fail(FR_ERR_INVALID_ARGUMENT, "BLA-PT: tables exist for Mandelbrot and Julia");
     if (which != 0 && !(which == 1 && cfg->algo == 2))
         return fail(FR_ERR_INVALID_ARGUMENT, "which must be 0 (the table of R or V) or, for Julia, 1 (K's)");
@@ -587,17 +587,23 @@ int fr_debug_bla_table(const fr_config *cfg, const fr_imaginary *pos_lo, const f
     pt_host_orbit(cfg, c, which, X);
     const uint32_t last = (uint32_t)(X.size() / 2 - 1);
     const double b0 = cfg->algo == 2 ? 0.0 : 1.0;
+    fr_config image = *cfg;
+    double S = 1.0;
+    if (scaled) {
+        const ScaledConsts k = scaled_consts(cfg);
+        image.scale.re = k.sre, image.scale.im = k.sim, S = k.S;
+    }
     HostTable t;
-    build_table(X.data(), last, image_D(cfg), b0, bits, t);
+    build_table(X.data(), last, image_D(&image), b0, bits, S, scaled, t);
     const uint32_t n = level < 32 ? t.n0 >> level : 0;
     *len = n;
     const size_t w = std::min<size_t>(cap, n);
     if (level == 0) {
-        const double eps = std::ldexp(1.0, -bits);
+        const double eps = std::ldexp(1.0, -bits) * S;
         for (size_t j = 0; j < w; j++) {
             const Entry e = level0(X.data(), (uint32_t)j, b0, eps);
             double *o = out + 5 * j;
-            o[0] = e.are, o[1] = e.aim, o[2] = e.bre, o[3] = e.bim, o[4] = e.r * e.r;
+            o[0] = e.are, o[1] = e.aim, o[2] = e.bre, o[3] = e.bim, o[4] = stored_radius(e.r, scaled);
         }
         return FR_OK;
     }
@@ -605,7 +611,7 @@ int fr_debug_bla_table(const fr_config *cfg, const fr_imaginary *pos_lo, const f
     for (size_t j = 0; j < w; j++) {
         double *o = out + 5 * j;
         memcpy(o, &t.coef[4 * (at + j)], 4 * sizeof(double));
-        o[4] = t.r2[at + j];
+        o[4] = t.rad[at + j];
     }
     return FR_OK;
 }

@@ -203,11 +203,13 @@ int check_precision_lo(const fr_config *cfg, int precision, const fr_imaginary *
  * the wide centre that stands in their place (include/fractal_hip.h, "WIDE PT").  The public entry points build one on
  * their first line; every road below them takes it whole, so none can drop the wide half on the way. */
 struct Centre {
-    const fr_imaginary *pos_lo; /* an aggregate, always written Centre{pos_lo, wide} */
+    const fr_imaginary *pos_lo; /* an aggregate, always written Centre{pos_lo, wide}, or Centre{nullptr, wide, true} */
     const fr_wide_centre *wide;
+    bool scaled = false; /* a SCALED PT call: `wide` is required and checked against SCALED PT's domain */
     double lo_re() const { return pos_lo ? pos_lo->re : 0.0; }
     double lo_im() const { return pos_lo ? pos_lo->im : 0.0; }
-    /* the domain check: check_pt_wide (fr_wide.h) for a wide centre, else check_precision_lo; no device needed */
+    /* the domain check: check_pt_wide (fr_wide.h) for a wide centre or a scaled call, else check_precision_lo; no device
+     * needed */
     int check(const fr_config *cfg, int precision) const;
 };
 

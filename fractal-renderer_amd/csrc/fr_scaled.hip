@@ -1,0 +1,532 @@
+/*
+ * fr_scaled.hip — SCALED PT: WIDE PT and BLA-PT past a scale of 2^440 (include/fractal_hip.h, fr_precision: "SCALED PT";
+ * tests/pt_scaled_model.c restates it; tests/test_gpu_pt_scaled.py compares the two bit for bit).  The pixel's offset from
+ * the reference orbit is carried as w = dz 2^e, e the exponent of the view's scale, so that neither it nor the squares the
+ * loop compares leave f64's normal range; multiplying by a power of two commutes with every rounding, so inside WIDE PT's
+ * domain the kernels here give escape_pt_kernel's and escape_bla_kernel's results bit for bit.
+ *
+ * Host part: nothing of its own.  The orbits are WIDE PT's (fr_pt.hip's cache, shared with the wide calls), the table is
+ * fr_bla.hip's build in its scaled form (R in place of r2), cached in the context's one table slot.
+ *
+ * Device part: escape_pt_scaled_kernel<MODE, JULIA> (bits = -1, no table) and escape_bla_scaled_kernel<MODE, JULIA>, in the
+ * shape of the kernels they extend (cdna_hip_programming: one lane per pixel, LDS for what a workgroup shares) — a workgroup
+ * of 4 waves renders 16 x 16 pixels, each wave one 8 x 8 tile, woff and the log2 table staged in LDS, 64-bit output offsets,
+ * plain vector loads and stores.  woff is PT's off with the divisor scale 2^-e, so the staging code is PT's on a copy of the
+ * parameters that holds (sre, sim).  What a scaled step adds to its unscaled counterpart:
+ *   - z = fma(w', Sinv, X_m) where PT has an addition;
+ *   - the two-sided comparisons.  Both forms of the rebase test are  (z fl)^2 < (w fr)^2  with (fl, fr) = (1, Sinv) for a big
+ *     w and (S, 1) otherwise: the factors are SELECTED (two v_cndmask pairs) and the four multiplies, two squares-and-sums
+ *     and one compare run on one path for every lane; a multiplication by 1 is exact, so each lane computes exactly the
+ *     expression of its form.  The level search does the same with f = Sinv or 1 on w and on each R it probes.
+ */
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "fr_bla.h"
+#include "fr_ctx.h"
+#include "fr_math.h"
+#include "fr_wide.h"
+
+namespace {
+
+#include "fr_colour.h"
+
+constexpr int kWaves = 4;               /* 256-thread workgroups */
+constexpr int kTileW = 8, kTileH = 8;   /* one wave = 8 x 8 pixels */
+constexpr int kWavesX = 2, kWavesY = 2;
+constexpr int kBlockW = kTileW * kWavesX, kBlockH = kTileH * kWavesY; /* 16 x 16 pixels per workgroup */
+
+constexpr double kBig = 0x1p500; /* max(|w.re|, |w.im|) >= kBig: w is "big" and the comparisons scale w down, not z up */
+
+/* the orbits, the tables (escape_bla_scaled_kernel only) and the scale as the kernels see them; Mandelbrot: the k fields
+ * repeat the x fields */
+struct ScaledDev {
+    const double2 *x_orbit, *k_orbit;
+    const double *x_R, *k_R;       /* R of the levels >= 1 */
+    const double *x_coef, *k_coef; /* Mandelbrot: A.re, A.im, B.re, B.im per entry; Julia: A.re, A.im */
+    uint32_t x_last, k_last;
+    uint32_t x_n0, k_n0; /* entries of level 0: last - 1, or 0 for an empty table */
+    double S, Sinv;      /* 2^e, 2^-e */
+};
+
+__device__ __forceinline__ bool is_big(double wr, double wi) {
+    const double a = __builtin_fabs(wr), b = __builtin_fabs(wi);
+    return (a > b ? a : b) >= kBig;
+}
+
+/* the rebase test of the definition on one arithmetic path: (z fl)^2 < (w fr)^2 with the factors selected by `big` */
+__device__ __forceinline__ bool rebase_test(double zr, double zi, double wr, double wi, double S, double Sinv) {
+    const bool big = is_big(wr, wi);
+    const double fl = big ? 1.0 : S, fr = big ? Sinv : 1.0;
+    const double lr = zr * fl, li = zi * fl, rr = wr * fr, ri = wi * fr;
+    return lr * lr + li * li < rr * rr + ri * ri;
+}
+
+/* ---- device: the plain scaled loop (include/fractal_hip.h, "SCALED PT", bits = -1), operation for operation -------------- */
+
+/* orbit_pt (fr_pt.hip) with w for dz: X_0 = 0 and X_1 of the orbit rebased onto stay in registers, X_{m+2} is loaded one
+ * step ahead.  Returns the escape index (or `iterations`), the final z in (out_re, out_im). */
+template <bool JULIA>
+__device__ __forceinline__ uint32_t orbit_pt_scaled(uint32_t iterations, double woff_re, double woff_im, const ScaledDev &t,
+                                                    double squared, double &out_re, double &out_im) {
+    const double S = t.S, Sinv = t.Sinv;
+    const double2 *X = t.x_orbit;
+    uint32_t last = t.x_last;
+    uint32_t m = JULIA ? 0u : 1u;
+    double wr = woff_re, wi = woff_im;
+    const double wcr = JULIA ? 0.0 : woff_re, wci = JULIA ? 0.0 : woff_im;
+    double2 Z = X[m], N = X[min(m + 1u, last)]; /* m <= last - 1 at the top of every step (a cap of 0 takes none) */
+    const double2 K1 = t.k_orbit[1]; /* the entry after a rebase; K_0 = R_0 = 0 */
+    double zr = __builtin_fma(wr, Sinv, Z.x), zi = __builtin_fma(wi, Sinv, Z.y);
+    uint32_t i = 0;
+    for (; i < iterations; i++) {
+        const double2 P = X[min(m + 2u, last)]; /* X_{m+2}: next step's X_{m+1} if it does not rebase */
+        const double tr = Z.x + zr, ti = Z.y + zi;
+        const double nwr = __builtin_fma(tr, wr, __builtin_fma(-ti, wi, wcr));
+        const double nwi = __builtin_fma(tr, wi, __builtin_fma(ti, wr, wci));
+        m++;
+        zr = __builtin_fma(nwr, Sinv, N.x);
+        zi = __builtin_fma(nwi, Sinv, N.y);
+        wr = nwr;
+        wi = nwi;
+        const double dist = zr * zr + zi * zi;
+        if (dist > squared) break; /* this lane leaves EXEC; the wave goes on while any lane is left */
+        if (rebase_test(zr, zi, wr, wi, S, Sinv) || m == last) {
+            wr = zr * S;
+            wi = zi * S;
+            m = 0;
+            if (JULIA) {
+                X = t.k_orbit;
+                last = t.k_last;
+            }
+            Z = make_double2(0.0, 0.0);
+            N = K1;
+        } else {
+            Z = N;
+            N = P;
+        }
+    }
+    out_re = zr;
+    out_im = zi;
+    return i;
+}
+
+/* ---- device: the scaled loop with table skips (bits >= 0) ------------------------------------------------------------- */
+
+/* orbit_bla (fr_bla.hip) with w for dz and R for r2.  Returns the escape index (or `iterations`), the final z in (out_re,
+ * out_im), the passes through the loop in `passes`. */
+template <bool JULIA>
+__device__ __forceinline__ uint32_t orbit_bla_scaled(uint32_t iterations, double woff_re, double woff_im, const ScaledDev &t,
+                                                     double squared, double &out_re, double &out_im, uint32_t &passes) {
+    const double S = t.S, Sinv = t.Sinv;
+    const double2 *X = t.x_orbit;
+    const double *R = t.x_R, *CF = t.x_coef;
+    uint32_t last = t.x_last, n0 = t.x_n0;
+    uint32_t m = JULIA ? 0u : 1u;
+    double wr = woff_re, wi = woff_im;
+    const double wcr = JULIA ? 0.0 : woff_re, wci = JULIA ? 0.0 : woff_im;
+    double2 Z = X[m]; /* X_m of the orbit followed */
+    double zr = __builtin_fma(wr, Sinv, Z.x), zi = __builtin_fma(wi, Sinv, Z.y);
+    uint32_t i = 0, np = 0, result = iterations;
+    while (i < iterations) {
+        np++;
+        /* 1. the level: the largest k in 1 .. kc with (w f)^2 < (R f)^2 (R is non-increasing in k for a fixed first step) */
+        const uint32_t j = m - 1u;
+        uint32_t K = 0;
+        if (m >= 1u && j < n0) {
+            const double f = is_big(wr, wi) ? Sinv : 1.0;
+            const double ar = wr * f, ai = wi * f;
+            const double d2 = ar * ar + ai * ai;
+            uint32_t kc = j ? (uint32_t)__builtin_ctz(j) : 31u;          /* j % 2^k == 0 */
+            kc = min(kc, 31u - (uint32_t)__builtin_clz(n0 - j));         /* (j >> k) < n_k, that is j + 2^k <= n0 */
+            kc = min(kc, 31u - (uint32_t)__builtin_clz(iterations - i)); /* i + 2^k <= iterations */
+            uint32_t lo = 0, hi = kc;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi + 1u) >> 1;
+                const double Rf = R[bla_level_offset(n0, mid) + (j >> mid)] * f;
+                if (d2 < Rf * Rf)
+                    lo = mid;
+                else
+                    hi = mid - 1u;
+            }
+            K = lo;
+        }
+        /* 2. the step: A and the constant term c of w' = A w + c — one arithmetic path, only the loads behind the branch */
+        double ar, ai, cr = wcr, ci = wci;
+        uint32_t step = 1u;
+        if (K) {
+            const uint32_t e = bla_level_offset(n0, K) + (j >> K);
+            if (JULIA) { /* B wc: fma(B.re, 0, -(B.im * 0)) and fma(B.re, 0, B.im * 0) are +0 = wc for every finite B */
+                const double2 A = reinterpret_cast<const double2 *>(CF)[e];
+                ar = A.x, ai = A.y;
+            } else {
+                const double4 AB = reinterpret_cast<const double4 *>(CF)[e];
+                ar = AB.x, ai = AB.y;
+                cr = __builtin_fma(AB.z, wcr, -(AB.w * wci));
+                ci = __builtin_fma(AB.z, wci, AB.w * wcr);
+            }
+            step = 1u << K;
+        } else {
+            ar = Z.x + zr, ai = Z.y + zi; /* t = X_m + z */
+        }
+        const double nwr = __builtin_fma(ar, wr, __builtin_fma(-ai, wi, cr));
+        const double nwi = __builtin_fma(ar, wi, __builtin_fma(ai, wr, ci));
+        m += step;
+        i += step;
+        const double2 N = X[min(m, last)]; /* m <= last: 1 + ((j >> K) + 1) 2^K <= 1 + n0 */
+        zr = __builtin_fma(nwr, Sinv, N.x);
+        zi = __builtin_fma(nwi, Sinv, N.y);
+        wr = nwr;
+        wi = nwi;
+        /* 3. the tests, the plain scaled loop's */
+        const double dist = zr * zr + zi * zi;
+        if (dist > squared) { /* this lane leaves EXEC; the wave goes on while any lane is left */
+            result = i - 1u;
+            break;
+        }
+        if (rebase_test(zr, zi, wr, wi, S, Sinv) || m == last) {
+            wr = zr * S;
+            wi = zi * S;
+            m = 0;
+            if (JULIA) {
+                X = t.k_orbit;
+                R = t.k_R;
+                CF = t.k_coef;
+                last = t.k_last;
+                n0 = t.k_n0;
+            }
+            Z = make_double2(0.0, 0.0); /* K_0 = R_0 = 0 */
+        } else {
+            Z = N;
+        }
+    }
+    out_re = zr;
+    out_im = zi;
+    passes = np;
+    return result;
+}
+
+/* ---- device: the kernels: one body, the loop chosen by BLA ------------------------------------------------------------- */
+
+template <int MODE, bool JULIA, bool BLA>
+__device__ __forceinline__ void scaled_body(const fr_kparams &p, const fr_kout &out, const ScaledDev &t) {
+    __shared__ double s_tab[FR_LOG2_N * 3];
+    __shared__ double s_re[kBlockW];
+    __shared__ double s_im[kBlockH];
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kBlockW - 1) / kBlockW);
+    const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+    const uint32_t col0 = bx * kBlockW, row0 = by * kBlockH;
+
+    if (MODE == FR_OUT_RGB) {
+        const double *gt = &g_log2_tab[0][0];
+        for (uint32_t k = tid; k < FR_LOG2_N * 3; k += 64 * kWaves) s_tab[k] = gt[k];
+    }
+    if (tid < kBlockW + kBlockH) {
+        /* woff: PT's off with the scaled divisors — p.scale_re and p.scale_im hold sre and sim */
+        const double width = (double)p.width, height = (double)p.height;
+        if (tid < kBlockW) {
+            const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
+            s_re[tid] = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
+        } else {
+            const uint32_t r = row0 + (tid - kBlockW);
+            const uint64_t y = (uint64_t)p.y_first + (uint64_t)(r / p.block_rows) * p.y_stride + r % p.block_rows;
+            s_im[tid - kBlockW] = (((double)y / height) - 0.5) / p.scale_im;
+        }
+    }
+    __syncthreads();
+
+    const uint32_t wave = tid >> 6, lane = tid & 63;
+    const uint32_t lx = (wave % kWavesX) * kTileW + lane % kTileW;
+    const uint32_t ly = (wave / kWavesX) * kTileH + lane / kTileW;
+    const uint32_t cx = col0 + lx, r = row0 + ly;
+    const bool valid = cx < p.ncols && r < p.nrows;
+    const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0; /* the host picks JULIA from the algorithm */
+
+    double zr = 0.0, zi = 0.0;
+    uint32_t iters = 0, passes = 0;
+    if (valid && escape_algo) {
+        const double squared = p.limit * p.limit; /* calc/src/lib.rs:246 */
+        if constexpr (BLA) {
+            iters = orbit_bla_scaled<JULIA>(p.iterations, s_re[lx], s_im[ly], t, squared, zr, zi, passes);
+        } else {
+            iters = orbit_pt_scaled<JULIA>(p.iterations, s_re[lx], s_im[ly], t, squared, zr, zi);
+            passes = iters < p.iterations ? iters + 1u : p.iterations; /* every pass is one step */
+        }
+    }
+
+    if constexpr (MODE == FR_OUT_RGB) {
+        if (valid) {
+            uint8_t rgb[3] = {0, 0, 0};
+            if (escape_algo) {
+                const ColourConsts cc = make_colour_consts(p);
+                const double r2 = zr * zr, i2 = zi * zi;
+                colour_pixel<double>(cc, zr, zi, r2, i2, iters, s_tab, nullptr, rgb); /* :214-234 on the f64 z */
+            }
+            const uint64_t k = (uint64_t)r * p.ncols + cx;
+            if (p.out_rgba) {
+                reinterpret_cast<uint32_t *>(out.rgb)[k] =
+                    (uint32_t)rgb[0] | ((uint32_t)rgb[1] << 8) | ((uint32_t)rgb[2] << 16) | 0xFF000000u;
+            } else {
+                uint8_t *o = out.rgb + 3ull * k;
+                o[0] = rgb[0];
+                o[1] = rgb[1];
+                o[2] = rgb[2];
+            }
+        }
+    } else if constexpr (MODE == FR_OUT_ESCAPE) {
+        if (valid) {
+            const uint64_t k = (uint64_t)r * p.ncols + cx;
+            if (out.z) {
+                out.z[2 * k] = zr;
+                out.z[2 * k + 1] = zi;
+            }
+            if (out.iters) out.iters[k] = iters;
+        }
+    } else { /* COUNT: the passes into count[0 .. SLOTS), the nominal iterations into count[SLOTS .. 2 SLOTS) */
+        unsigned long long np = 0, n = 0;
+        if (valid && escape_algo) {
+            np = passes;
+            n = iters < p.iterations ? (unsigned long long)iters + 1ull : p.iterations;
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            np += __shfl_down(np, off, 64);
+            n += __shfl_down(n, off, 64);
+        }
+        if (lane == 0 && n) {
+            const uint32_t slot = (blockIdx.x + 131u * wave) % FR_COUNT_SLOTS;
+            atomicAdd(out.count + slot, np);
+            atomicAdd(out.count + FR_COUNT_SLOTS + slot, n);
+        }
+    }
+}
+
+template <int MODE, bool JULIA>
+__global__ __launch_bounds__(64 * kWaves) void escape_pt_scaled_kernel(const fr_kparams p, const fr_kout out, const ScaledDev t) {
+    scaled_body<MODE, JULIA, false>(p, out, t);
+}
+
+template <int MODE, bool JULIA>
+__global__ __launch_bounds__(64 * kWaves) void escape_bla_scaled_kernel(const fr_kparams p, const fr_kout out, const ScaledDev t) {
+    scaled_body<MODE, JULIA, true>(p, out, t);
+}
+
+template <bool JULIA, bool BLA>
+hipError_t launch(const fr_kparams &p, int mode, const fr_kout &out, const ScaledDev &t, hipStream_t stream) {
+    const uint64_t tiles = (((uint64_t)p.ncols + kBlockW - 1) / kBlockW) * (((uint64_t)p.nrows + kBlockH - 1) / kBlockH);
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)tiles), block(64 * kWaves);
+    if constexpr (BLA) {
+        if (mode == FR_OUT_RGB)
+            escape_bla_scaled_kernel<FR_OUT_RGB, JULIA><<<grid, block, 0, stream>>>(p, out, t);
+        else if (mode == FR_OUT_ESCAPE)
+            escape_bla_scaled_kernel<FR_OUT_ESCAPE, JULIA><<<grid, block, 0, stream>>>(p, out, t);
+        else
+            escape_bla_scaled_kernel<FR_OUT_COUNT, JULIA><<<grid, block, 0, stream>>>(p, out, t);
+    } else {
+        if (mode == FR_OUT_RGB)
+            escape_pt_scaled_kernel<FR_OUT_RGB, JULIA><<<grid, block, 0, stream>>>(p, out, t);
+        else if (mode == FR_OUT_ESCAPE)
+            escape_pt_scaled_kernel<FR_OUT_ESCAPE, JULIA><<<grid, block, 0, stream>>>(p, out, t);
+        else
+            escape_pt_scaled_kernel<FR_OUT_COUNT, JULIA><<<grid, block, 0, stream>>>(p, out, t);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch(bool julia, bool bla, const fr_kparams &p, int mode, const fr_kout &out, const ScaledDev &t, hipStream_t stream) {
+    if (bla) return julia ? launch<true, true>(p, mode, out, t, stream) : launch<false, true>(p, mode, out, t, stream);
+    return julia ? launch<true, false>(p, mode, out, t, stream) : launch<false, false>(p, mode, out, t, stream);
+}
+
+}  // namespace
+
+namespace fr {
+namespace {
+
+const char *kernel_name(int bits) { return bits < 0 ? "escape_pt_scaled_kernel" : "escape_bla_scaled_kernel"; }
+
+/* `p` holds the view's scale; the kernels get a copy with the scaled divisors.  bits < 0: no table. */
+int launch_scaled(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_kparams &p, int mode, const fr_kout &out,
+                  hipStream_t stream) {
+    if (p.ncols == 0 || p.nrows == 0) return FR_OK;
+    const bool julia = cfg->algo == 2, bla = bits >= 0;
+    if (cfg->algo != 0 && !julia) { /* no escape-time algorithm: every pixel is black / zero, as PT's kernel gives */
+        HIP_TRY(launch(false, bla, p, mode, out, ScaledDev{}, stream));
+        return FR_OK;
+    }
+    const ScaledConsts k = scaled_consts(cfg);
+    fr_kparams ps = p;
+    ps.scale_re = k.sre;
+    ps.scale_im = k.sim;
+    std::shared_ptr<PtOrbit> orbit;
+    std::shared_ptr<BlaTable> table;
+    PtOrbitView v;
+    ScaledDev t{};
+    if (bla) {
+        const int rc = bla_table_for(ctx, cfg, c, bits, true, orbit, v, table);
+        if (rc != FR_OK) return rc;
+        const BlaTableDev &d = table->view;
+        t.x_R = d.x_rad, t.k_R = d.k_rad;
+        t.x_coef = d.x_coef, t.k_coef = d.k_coef;
+        t.x_n0 = d.x_n0, t.k_n0 = d.k_n0;
+    } else {
+        const int rc = pt_orbit_view(ctx, cfg, c, orbit, v);
+        if (rc != FR_OK) return rc;
+    }
+    t.x_orbit = v.x;
+    t.k_orbit = v.k;
+    t.x_last = v.x_last;
+    t.k_last = v.k_last;
+    t.S = k.S;
+    t.Sinv = k.Sinv;
+    HIP_TRY(launch(julia, bla, ps, mode, out, t, stream));
+    return FR_OK;
+}
+
+/* ---- the calls ------------------------------------------------------------------------------------------------------ */
+
+/* SCALED PT's domain (include/fractal_hip.h); table: the call is about a table, so bits = -1 is no answer */
+int check_scaled(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1, bool table = false) {
+    int rc = check_rows(cfg, y0, y1);
+    if (rc == FR_OK) rc = c.check(cfg, FR_PRECISION_PT);
+    if (rc != FR_OK) return rc;
+    if (bits == 0) bits = FR_BLA_DEFAULT_BITS;
+    if (table && (bits < 24 || bits > 53))
+        return fail(FR_ERR_INVALID_ARGUMENT, "SCALED PT: the bits of a table are 0 (FR_BLA_DEFAULT_BITS) or 24 .. 53");
+    if (bits != -1 && (bits < 24 || bits > 53))
+        return fail(FR_ERR_INVALID_ARGUMENT, "SCALED PT: bits must be -1 (no table), 0 (FR_BLA_DEFAULT_BITS) or 24 .. 53");
+    return FR_OK;
+}
+
+/* rows [y0, y1) on `stream` between the profiling events (fr_set_profiling), named for fr_last_kernel_name; the colour
+ * constants alone: no loop plan, no kernel choice, no view sample */
+int profiled_launch(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, unsigned channels, int mode,
+                    const fr_kout &out, hipStream_t stream) {
+    fr_kparams p;
+    rows_params(cfg, default_opts(), y0, y1, channels, p);
+    int rc = prof_begin(stream);
+    if (rc == FR_OK) rc = launch_scaled(ctx, cfg, c, bits, p, mode, out, stream);
+    if (rc != FR_OK) return rc;
+    return prof_end(stream, kernel_name(bits));
+}
+
+}  // namespace
+}  // namespace fr
+
+using namespace fr;
+
+int fr_render_rows_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1,
+                                    int channels, void *d_out, size_t out_len, void *hip_stream) {
+    const Centre c{nullptr, centre, true};
+    int rc = check_channels(channels);
+    if (rc == FR_OK) rc = check_scaled(cfg, c, bits, y0, y1);
+    if (rc != FR_OK) return rc;
+    const size_t need = (size_t)channels * cfg->width * (size_t)(y1 - y0);
+    if (need == 0) return FR_OK;
+    if (!d_out) return fail(FR_ERR_INVALID_ARGUMENT, "d_out is NULL");
+    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*(y1-y0)");
+    if (channels == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "RGBA8 output must be 4-byte aligned");
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    fr_kout ko{};
+    ko.rgb = static_cast<uint8_t *>(d_out);
+    return profiled_launch(*ctx, cfg, c, bits, y0, y1, (unsigned)channels, FR_OUT_RGB, ko, static_cast<hipStream_t>(hip_stream));
+}
+
+int fr_render_rows_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, int channels,
+                             uint8_t *out, size_t out_len) {
+    const Centre c{nullptr, centre, true};
+    int rc = check_channels(channels);
+    if (rc == FR_OK) rc = check_scaled(cfg, c, bits, y0, y1);
+    if (rc != FR_OK) return rc;
+    const size_t need = (size_t)channels * cfg->width * (size_t)(y1 - y0);
+    if (need == 0) return FR_OK;
+    if (!out) return fail(FR_ERR_INVALID_ARGUMENT, "out is NULL");
+    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*(y1-y0)");
+    return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) {
+        fr_kout ko{};
+        ko.rgb = static_cast<uint8_t *>(d_out);
+        return profiled_launch(ctx, cfg, c, bits, y0, y1, (unsigned)channels, FR_OUT_RGB, ko, stream);
+    });
+}
+
+int fr_escape_rows_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, void *d_z,
+                                    void *d_iters, void *hip_stream) {
+    const Centre c{nullptr, centre, true};
+    int rc = check_scaled(cfg, c, bits, y0, y1);
+    if (rc != FR_OK) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    if (npx == 0 || (!d_z && !d_iters)) return FR_OK;
+    if (reinterpret_cast<uintptr_t>(d_z) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_z must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_iters) & 3u) return fail(FR_ERR_INVALID_ARGUMENT, "d_iters must be 4-byte aligned");
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    fr_kout ko{};
+    ko.z = static_cast<double *>(d_z);
+    ko.iters = static_cast<uint32_t *>(d_iters);
+    return profiled_launch(*ctx, cfg, c, bits, y0, y1, 0, FR_OUT_ESCAPE, ko, static_cast<hipStream_t>(hip_stream));
+}
+
+int fr_escape_rows_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, double *z,
+                             uint32_t *iters) {
+    const Centre c{nullptr, centre, true};
+    int rc = check_scaled(cfg, c, bits, y0, y1);
+    if (rc != FR_OK) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    if (npx == 0 || (!z && !iters)) return FR_OK;
+    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), nullptr, nullptr, false,
+                    [&](Ctx &ctx, double *d_z, uint32_t *d_iters, double *, uint32_t *, hipStream_t stream) {
+                        fr_kout ko{};
+                        ko.z = d_z;
+                        ko.iters = d_iters;
+                        return profiled_launch(ctx, cfg, c, bits, y0, y1, 0, FR_OUT_ESCAPE, ko, stream);
+                    });
+}
+
+int fr_debug_pt_scaled_count(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, uint64_t *passes,
+                             uint64_t *steps) {
+    const Centre c{nullptr, centre, true};
+    int rc = check_scaled(cfg, c, bits, y0, y1);
+    if (rc != FR_OK) return rc;
+    if (!passes || !steps) return fail(FR_ERR_INVALID_ARGUMENT, "passes or steps is NULL");
+    *passes = *steps = 0;
+    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t bytes = sizeof(unsigned long long) * 2 * FR_COUNT_SLOTS;
+    rc = ctx->reserve(ctx->misc, bytes);
+    if (rc != FR_OK) return rc;
+    HIP_TRY(hipMemsetAsync(ctx->misc.ptr, 0, bytes, ctx->stream));
+    fr_kout ko{};
+    ko.count = static_cast<unsigned long long *>(ctx->misc.ptr);
+    rc = profiled_launch(*ctx, cfg, c, bits, y0, y1, 0, FR_OUT_COUNT, ko, ctx->stream);
+    if (rc != FR_OK) return rc;
+    std::vector<unsigned long long> host(2 * FR_COUNT_SLOTS);
+    HIP_TRY(hipMemcpyAsync(host.data(), ctx->misc.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (uint32_t s = 0; s < FR_COUNT_SLOTS; s++) {
+        *passes += host[s];
+        *steps += host[FR_COUNT_SLOTS + s];
+    }
+    return FR_OK;
+}
+
+int fr_debug_bla_table_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, int which, uint32_t level, double *out,
+                              size_t cap, uint32_t *len) {
+    const Centre c{nullptr, centre, true};
+    const int rc = check_scaled(cfg, c, bits, 0, 0, true);
+    if (rc != FR_OK) return rc;
+    return bla_debug_table(cfg, c, bits, true, which, level, out, cap, len);
+}

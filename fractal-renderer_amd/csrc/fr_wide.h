@@ -17,8 +17,9 @@ struct WideTail {
     std::vector<uint64_t> re, im; /* n words each; empty: no wide orbit */
 };
 
-/* WIDE PT's domain (include/fractal_hip.h); no device needed */
-int check_pt_wide(const fr_config *cfg, const fr_wide_centre *centre);
+/* WIDE PT's domain (include/fractal_hip.h), or — `scaled` — SCALED PT's: limit <= 2^20, the axes of scale within 2^32 of
+ * each other, and no 2^440 rule (F >= e + 64 bounds the scale); no device needed */
+int check_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, bool scaled = false);
 
 /* Orbit `which` (0: R or V, 1: K) of the view as re, im pairs of the stored f64 entries, appended to `out`; at most
  * iterations + 2 entries in all.  from == nullptr: the whole orbit, entry 0 first.  Otherwise entries 0 .. last of an orbit

@@ -229,8 +229,8 @@ void wide_key(const fr_wide_centre *centre, std::vector<uint64_t> &key) {
     key.insert(key.end(), centre->im, centre->im + n);
 }
 
-int check_pt_wide(const fr_config *cfg, const fr_wide_centre *centre) {
-    const std::string name("FR_PRECISION_PT, wide centre: ");
+int check_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, bool scaled) {
+    const std::string name(scaled ? "SCALED PT: " : "FR_PRECISION_PT, wide centre: ");
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
     if (!centre) return fail(FR_ERR_INVALID_ARGUMENT, name + "centre is NULL");
     const uint32_t n = centre->n_words;
@@ -241,13 +241,18 @@ int check_pt_wide(const fr_config *cfg, const fr_wide_centre *centre) {
                              cfg->exposure, cfg->color_weight, cfg->julia_set.re, cfg->julia_set.im};
     for (double v : fields)
         if (!std::isfinite(v)) return fail(FR_ERR_INVALID_ARGUMENT, name + "every field of the view must be finite");
+    if (scaled && !(cfg->limit > 0.0 && cfg->limit <= 0x1p20))
+        return fail(FR_ERR_INVALID_ARGUMENT, name + "limit must lie in (0, 2^20]: the scaled offset, at most about (limit^2 + 2) 2^e, "
+                                                    "must stay finite");
     if (!(cfg->limit > 0.0 && cfg->limit <= 0x1p500)) return fail(FR_ERR_INVALID_ARGUMENT, name + "limit must lie in (0, 2^500]");
     if (cfg->iterations > FR_PT_MAX_ITERATIONS)
         return fail(FR_ERR_INVALID_ARGUMENT, name + "iterations must be <= FR_PT_MAX_ITERATIONS (2^24): the reference orbit takes "
                                                     "16 bytes per iteration");
     const double sre = std::fabs(cfg->scale.re), sim = std::fabs(cfg->scale.im);
     if (sre < 0x1p-64 || sim < 0x1p-64) return fail(FR_ERR_INVALID_ARGUMENT, name + "|scale| must be >= 2^-64 on both axes");
-    if (sre > 0x1p440 || sim > 0x1p440)
+    if (scaled && (sre < sim ? sre : sim) < 0x1p-32 * (sre > sim ? sre : sim))
+        return fail(FR_ERR_INVALID_ARGUMENT, name + "min |scale| must be >= 2^-32 max |scale| over the two axes");
+    if (!scaled && (sre > 0x1p440 || sim > 0x1p440))
         return fail(FR_ERR_INVALID_ARGUMENT, name + "|scale| must be <= 2^440 on both axes (deeper views need a scaled pixel loop)");
     if (std::fabs(cfg->julia_set.re) > 2.0 || std::fabs(cfg->julia_set.im) > 2.0)
         return fail(FR_ERR_INVALID_ARGUMENT, name + "the components of julia_set must lie in [-2, 2]");

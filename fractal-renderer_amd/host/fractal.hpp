@@ -248,5 +248,22 @@ inline void escape_rows_device(const Config &config, Bla bla, void *d_z, void *d
     check(fr_escape_rows_pt_bla_device(&config, pos_lo, centre, bla.bits, 0, config.height, d_z, d_iters, hip_stream));
 }
 
+// ---- SCALED PT (include/fractal_hip.h, "SCALED PT"): the wide-centre roads past a scale of 2^440, up to just under 2^952 ------
+// bits = -1: the plain scaled loop (WIDE PT's results wherever WIDE PT renders); 0 or 24 .. 53: with BLA-PT's skips.  One GPU.
+struct Scaled {
+    int bits = -1;
+};
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Scaled scaled) {
+    std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
+    check(fr_render_rows_pt_scaled(&config, &centre, scaled.bits, 0, config.height, 3, reinterpret_cast<uint8_t *>(image.data()),
+                                   image.size() * sizeof(RGB)));
+    return image;
+}
+// (z, iters) of the whole view into device arrays, for colour_rows_device
+inline void escape_rows_device(const Config &config, const fr_wide_centre &centre, Scaled scaled, void *d_z, void *d_iters,
+                               void *hip_stream = nullptr) {
+    check(fr_escape_rows_pt_scaled_device(&config, &centre, scaled.bits, 0, config.height, d_z, d_iters, hip_stream));
+}
+
 }  // namespace fractal
 #endif

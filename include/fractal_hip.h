@@ -253,7 +253,60 @@ typedef struct fr_config {
  * two orbits), beside the orbit's own 16 B per entry — at most 640 MiB (768 MiB for Julia's two) at the cap.  One device;
  * supersampling, block-cyclic and multi-device renders do not take BLA-PT, nor do the resumable-state and extend calls: the
  * condition i + 2^k <= iterations makes a run at cap N no prefix of the run at cap M, so there is no state to continue, and
- * fr_escape_extend(_device) and fr_escape_extend_pt(_device) have no BLA form. */
+ * fr_escape_extend(_device) and fr_escape_extend_pt(_device) have no BLA form.
+ *
+ * SCALED PT (the fr_*_pt_scaled calls below): WIDE PT and BLA-PT past a scale of 2^440, down to just under 2^952.  The pixel
+ * loops above work in absolute units, and past 2^440 the squares they compare (|dz|^2 in the rebase test, r2 and d2 in
+ * BLA-PT) leave f64's normal range.  SCALED PT carries the pixel's offset as w = dz 2^e, e the exponent of the view's scale.
+ * The reference orbits and their stop rule, "ended by escape", the escape test and the colour map on the f64 z are WIDE PT's,
+ * word for word, and the orbit cache is shared: a scaled call and a wide call of the same view, words and cap serve each
+ * other's orbit.  Every operation below is one correctly rounded f64 operation; fma is fused and nothing else is; sqrt is IEEE.
+ *   Constants of a view: max(|scale.re|, |scale.im|) = f 2^e with 0.5 <= f < 1 (the e of F >= e + 64); S = 2^e, Sinv = 2^-e;
+ *   sre = scale.re * Sinv and sim = scale.im * Sinv, both exact;
+ *     woff_re = ((x / h) - ((w / h) / 2)) / sre, woff_im = ((y / h) - 0.5) / sim
+ *   — PT's operations of off with the scaled divisor; off itself is never formed; wc = woff for Mandelbrot, 0 for Julia.
+ *   Pixel state (X, m, z, w): m starts as in PT, w = woff, z = fma(w, Sinv, X_m) per axis.
+ *   Step i = 0 .. iterations-1:
+ *     t  = X_m + z
+ *     w' = (fma(t.re, w.re, fma(-t.im, w.im, wc.re)), fma(t.re, w.im, fma(t.im, w.re, wc.im)))
+ *     m  = m + 1;  z = fma(w', Sinv, X_m) per axis;  w = w'
+ *     dist = z.re*z.re + z.im*z.im: dist > limit*limit -> escape with (z, i)
+ *     Rebase test.  w is BIG when max(|w.re|, |w.im|) >= 2^500.  BIG: d = w * Sinv per axis and the test is
+ *     dist < d.re*d.re + d.im*d.im.  Otherwise a = z * S per axis and the test is a.re*a.re + a.im*a.im < w.re*w.re + w.im*w.im;
+ *     an infinite left side makes it false, which is intended and IEEE-defined.  Rebase on the test or on m == last of X, as
+ *     PT does: w = z * S per axis, m = 0 (z unchanged), and Julia then follows K.
+ *   Exhaustion: (z, iterations).
+ *   With a table (bits >= 0) the loop is BLA-PT's on (w, wc): the table of an orbit has BLA-PT's A and B unchanged and one
+ *   replacement, the entry's scaled radius R where BLA-PT has r:
+ *     Level 0: R = (eps * S) * sqrt(A.re*A.re + A.im*A.im)                                            (eps * S is exact)
+ *     Merge:   Q = (Ry - sqrt(Bx.re*Bx.re + Bx.im*Bx.im) * Dw) / sqrt(Ax.re*Ax.re + Ax.im*Ax.im); if !(Q > 0) then Q = 0;
+ *              R = Rx < Q ? Rx : Q
+ *     Dw = sqrt(mrw*mrw + miw*miw) with mrw = max(|woff_re(0)|, |woff_re(width-1)|), miw = max(|woff_im(0)|,
+ *     |woff_im(height-1)|): D's expression on woff, over the WHOLE image.
+ *     An entry STORES R itself, not its square, and stores 0 when R < 2^-53; a stored 0 is never applied.  (A merge reads
+ *     the R of its two entries as computed, before that rule.)
+ *     Why A is finite where R > 0 is stored.  BLA-PT's invariant reads R |A| < 2^(e-19) here (it scales with S), and a stored
+ *     R is at least 2^-53, so |A| < 2^(e+34) <= 2^986: no product that A is has overflowed, given finite factors, and the
+ *     factors are entries with Rx >= R and Ry >= R |Ax| (1 - 2^-50) > 0 by the same two roundings.  There is no footnote case:
+ *     nothing here depends on a radius below 2^-53, let alone on a subnormal one.
+ *   Level search: BLA-PT's four conditions with the fourth as (w.re*f)*(w.re*f) + (w.im*f)*(w.im*f) < (R*f)*(R*f), where
+ *   f = Sinv when w is BIG and 1 otherwise — one multiplication per operand, and the same two-sided IEEE behaviour as the
+ *   rebase test: (R*f)*(R*f) may be +inf (then the condition holds for every finite left side) or 0.
+ *   The skip is BLA-PT's expression on (w, wc) with (A, B) of the entry, followed by m += 2^K, i += 2^K and
+ *   z = fma(w', Sinv, X_m) per axis; the tests are the plain scaled loop's, with (z, i - 1) on escape.
+ *   w stays finite: a w that is not rebased has |w Sinv|^2 <= dist <= limit^2, and one step multiplies |w| by at most
+ *   |X_m + z| <= 2 + limit + ... and adds |wc| <= 2^e, so |w| stays below about (limit^2 + 2) 2^e <= (2^40 + 2) 2^952 <
+ *   2^1023 with limit <= 2^20; a rebase sets |w| = |z| S <= limit 2^e.
+ *   CLAIM: for every view in WIDE PT's domain with limit <= 2^20 in which no intermediate of the unscaled run is subnormal,
+ *   the scaled calls give WIDE PT's z and iters bit for bit with bits = -1, and BLA-PT's z and iters with bits >= 0
+ *   (multiplying by 2^e commutes with every rounding: w = dz 2^e, R = r 2^e, Dw = D 2^e, and each comparison is the unscaled
+ *   one with both sides scaled by the same power of two).  The pass counts may differ only for a pixel with |w| < 2^-53:
+ *   BLA-PT may apply to it an entry whose R is stored as 0 here.
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): WIDE PT's, with a centre REQUIRED, and with
+ * these changes: limit <= 2^20 (the default, 65536, is inside); min(|scale.re|, |scale.im|) >= 2^-32 max(|scale.re|,
+ * |scale.im|); no 2^440 rule — what bounds the scale is F >= e + 64 with n <= 16, so e <= 952 and |scale| < 2^952; bits = -1
+ * (no table: the plain scaled loop), 0 (= FR_BLA_DEFAULT_BITS) or 24 .. 53.  One device.  OUT OF SCOPE: supersampling,
+ * block-cyclic and multi-device renders do not take SCALED PT, and it has no resumable state and no extend form. */
 #define FR_BLA_DEFAULT_BITS 40
 #define FR_PT_MAX_ITERATIONS (1u << 24)
 #define FR_WIDE_MAX_WORDS 16
@@ -722,6 +775,33 @@ int fr_debug_bla_count(const fr_config *cfg, const fr_imaginary *pos_lo, const f
  * of all levels of X's and K's tables, out[3] = 1 if the last request built the table, 0 if it was served.  Zeros without a
  * cached table.  Touches no device. */
 int fr_debug_bla_cache(uint32_t out[4]);
+
+/* ---- SCALED PT: WIDE PT and BLA-PT down to a scale of 2^951 -------------------------------------------------------- */
+
+/* The SCALED PT calls (fr_precision above, "SCALED PT").  `centre` is required; cfg->pos is not read.  bits: -1 = no table
+ * (the plain scaled loop, WIDE PT's counterpart), 0 = FR_BLA_DEFAULT_BITS, else 24 .. 53 (BLA-PT's counterpart).  y0 == y1 and
+ * argument errors need no device.  The orbit is the one the fr_*_pt_wide calls cache (either road serves the other); the
+ * table is built, uploaded and kept per context as BLA-PT's is, in the same slot, keyed by the orbit, Dw, bits and its kind.
+ * fr_render_rows_pt_scaled(_device): the buffers, channels, alignment and asynchrony of fr_render_rows_pt_wide(_device).
+ * fr_escape_rows_pt_scaled(_device): as fr_escape_rows_pt_bla(_device); fr_colour_rgb8 / fr_colour_rows_device over the
+ * results reproduces the render.  With profiling on, fr_last_kernel_name reports escape_pt_scaled_kernel (bits = -1) or
+ * escape_bla_scaled_kernel. */
+int fr_render_rows_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, int channels,
+                             uint8_t *out, size_t out_len);
+int fr_render_rows_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1,
+                                    int channels, void *d_out, size_t out_len, void *hip_stream);
+int fr_escape_rows_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, double *z,
+                             uint32_t *iters);
+int fr_escape_rows_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1,
+                                    void *d_z, void *d_iters, void *hip_stream);
+/* Host only, no device: as fr_debug_bla_table for the scaled table (bits 0 or 24 .. 53); 5 doubles per entry: A.re, A.im,
+ * B.re, B.im and the stored R. */
+int fr_debug_bla_table_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, int which, uint32_t level, double *out,
+                              size_t cap, uint32_t *len);
+/* On the device, as fr_debug_bla_count: *passes = the passes through the scaled loop (bits = -1: one per step), *steps = the
+ * nominal iterations. */
+int fr_debug_pt_scaled_count(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1,
+                             uint64_t *passes, uint64_t *steps);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 

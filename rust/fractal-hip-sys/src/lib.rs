@@ -162,6 +162,12 @@ extern "C" {
     pub fn fr_debug_bla_table(cfg: *const fr_config, pos_lo: *const fr_imaginary, centre: *const fr_wide_centre, bits: c_int, which: c_int, level: u32, out: *mut f64, cap: usize, len: *mut u32) -> c_int;
     pub fn fr_debug_bla_count(cfg: *const fr_config, pos_lo: *const fr_imaginary, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, passes: *mut u64, steps: *mut u64) -> c_int;
     pub fn fr_debug_bla_cache(out: *mut u32) -> c_int;
+    pub fn fr_render_rows_pt_scaled(cfg: *const fr_config, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, channels: c_int, out: *mut u8, out_len: usize) -> c_int;
+    pub fn fr_render_rows_pt_scaled_device(cfg: *const fr_config, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, channels: c_int, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_escape_rows_pt_scaled(cfg: *const fr_config, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, z: *mut f64, iters: *mut u32) -> c_int;
+    pub fn fr_escape_rows_pt_scaled_device(cfg: *const fr_config, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, d_z: *mut c_void, d_iters: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_debug_bla_table_scaled(cfg: *const fr_config, centre: *const fr_wide_centre, bits: c_int, which: c_int, level: u32, out: *mut f64, cap: usize, len: *mut u32) -> c_int;
+    pub fn fr_debug_pt_scaled_count(cfg: *const fr_config, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, passes: *mut u64, steps: *mut u64) -> c_int;
 }
 
 /// Message of the last failing call on this thread.
