@@ -519,11 +519,12 @@ def _lo(pos_lo):
     return (pre or (None,))[0], keep
 
 
-def _pt_state_fn(name, device, pos_lo, centre):
-    """the PT state call `name` ("fr_escape_rows_pt%s_state" / "fr_escape_extend_pt%s"; %s: "_wide" with a centre) in its host or
-    device form, with its centre argument and what keeps it alive"""
-    family, pre, keep = _deep_call(Precision.PT, pos_lo, centre)
-    fn = getattr(_native.load(), name % ("_wide" if family == "wide" else "") + ("_device" if device else ""))
+def _pt_state_fn(name, device, pos_lo, centre, scaled=False):
+    """the PT state call `name` ("fr_escape_rows_pt%s_state" / "fr_escape_extend_pt%s"; %s: "_wide" with a centre, "_scaled"
+    with a centre and scaled=True) in its host or device form, with its centre argument and what keeps it alive"""
+    family, pre, keep = _deep_call(Precision.PT, pos_lo, centre, scaled=scaled)
+    infix = {"wide": "_wide", "scaled": "_scaled"}.get(family, "")  # the scaled state calls take no bits: pre[0] alone
+    fn = getattr(_native.load(), name % infix + ("_device" if device else ""))
     return fn, (pre or (None,))[0], keep
 
 
@@ -569,49 +570,55 @@ def extend_rows(config, z, iters, from_iterations, precision=Precision.F64, pos_
     return z, iters
 
 
-def escape_rows_pt_state(config, pos_lo=None, y0=0, y1=None, centre=None):
+def escape_rows_pt_state(config, pos_lo=None, y0=0, y1=None, centre=None, scaled=False):
     """fr_escape_rows_pt_state: rows [y0, y1) in Precision.PT with their resumable state: (z float64 [rows, width, 2], iters
     uint32 [rows, width], dz float64 [rows, width, 2], m uint32 [rows, width]; bit 31 of m: a Julia pixel on K).  z and iters
-    are escape_rows' for Precision.PT, bit for bit (include/fractal_hip.h, "RESUMABLE PT")."""
+    are escape_rows' for Precision.PT, bit for bit (include/fractal_hip.h, "RESUMABLE PT").
+    scaled=True (needs centre=): fr_escape_rows_pt_scaled_state, the state of SCALED PT's plain loop for views past 2^440;
+    the third array then holds w = dz 2^e, not dz ("RESUMABLE SCALED PT"), and only the scaled extension continues it."""
     y0, y1 = _rows(config, y0, y1)
     shape = (max(y1 - y0, 0), config.width)
     z, dz = np.empty(shape + (2,), dtype=np.float64), np.empty(shape + (2,), dtype=np.float64)
     it, m = np.empty(shape, dtype=np.uint32), np.empty(shape, dtype=np.uint32)
-    fn, where, _keep = _pt_state_fn("fr_escape_rows_pt%s_state", False, pos_lo, centre)
+    fn, where, _keep = _pt_state_fn("fr_escape_rows_pt%s_state", False, pos_lo, centre, scaled)
     _native.check(fn(C.byref(config), where, y0, y1, z.ctypes.data, it.ctypes.data, dz.ctypes.data, m.ctypes.data))
     return z, it, dz, m
 
 
-def extend_rows_pt(config, z, iters, dz, m, from_iterations, pos_lo=None, y0=0, y1=None, centre=None):
+def extend_rows_pt(config, z, iters, dz, m, from_iterations, pos_lo=None, y0=0, y1=None, centre=None, scaled=False):
     """fr_escape_extend_pt over numpy arrays: the state escape_rows_pt_state returned at the cap `from_iterations` -> the
     state at config.iterations (copies; the arguments are left alone).  The arrays must be that view's; the library cannot
-    check it."""
+    check it.  scaled=True (needs centre=): fr_escape_extend_pt_scaled, on a state that escape_rows_pt_state(scaled=True)
+    returned (dz is its w)."""
     y0, y1 = _rows(config, y0, y1)
     shape = (max(y1 - y0, 0), config.width)
     z, dz = np.array(z, dtype=np.float64, order="C"), np.array(dz, dtype=np.float64, order="C")
     iters, m = np.array(iters, dtype=np.uint32, order="C"), np.array(m, dtype=np.uint32, order="C")
     if z.shape != shape + (2,) or dz.shape != shape + (2,) or iters.shape != shape or m.shape != shape:
         raise ValueError("z and dz must be [rows, width, 2], iters and m [rows, width] for rows [y0, y1)")
-    fn, where, _keep = _pt_state_fn("fr_escape_extend_pt%s", False, pos_lo, centre)
+    fn, where, _keep = _pt_state_fn("fr_escape_extend_pt%s", False, pos_lo, centre, scaled)
     _native.check(fn(C.byref(config), where, y0, y1, int(from_iterations), z.ctypes.data, iters.ctypes.data, dz.ctypes.data,
                      m.ctypes.data))
     return z, iters, dz, m
 
 
-def escape_rows_pt_state_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, y0=0, y1=None, pos_lo=None, stream=None, centre=None):
+def escape_rows_pt_state_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, y0=0, y1=None, pos_lo=None, stream=None, centre=None,
+                                scaled=False):
     """fr_escape_rows_pt_state_device: the Precision.PT state of rows [y0, y1) into DEVICE arrays (raw pointers as ints:
-    z, dz 2 float64 per pixel, iters, m one uint32), asynchronously on `stream`: 40 bytes per pixel."""
+    z, dz 2 float64 per pixel, iters, m one uint32), asynchronously on `stream`: 40 bytes per pixel.  scaled=True (needs
+    centre=): fr_escape_rows_pt_scaled_state_device; dz_ptr then receives w."""
     y0, y1 = _rows(config, y0, y1)
-    fn, where, _keep = _pt_state_fn("fr_escape_rows_pt%s_state", True, pos_lo, centre)
+    fn, where, _keep = _pt_state_fn("fr_escape_rows_pt%s_state", True, pos_lo, centre, scaled)
     _native.check(fn(C.byref(config), where, y0, y1, z_ptr or None, iters_ptr or None, dz_ptr or None, m_ptr or None, _stream(stream)))
 
 
 def extend_rows_pt_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, from_iterations, y0=0, y1=None, pos_lo=None, stream=None,
-                          centre=None):
+                          centre=None, scaled=False):
     """fr_escape_extend_pt_device: raise the cap of the stored Precision.PT state of rows [y0, y1) from `from_iterations` to
-    config.iterations IN PLACE, asynchronously on `stream`; the view's reference orbit is continued, not recomputed."""
+    config.iterations IN PLACE, asynchronously on `stream`; the view's reference orbit is continued, not recomputed.
+    scaled=True (needs centre=): fr_escape_extend_pt_scaled_device, on a state the scaled state render wrote."""
     y0, y1 = _rows(config, y0, y1)
-    fn, where, _keep = _pt_state_fn("fr_escape_extend_pt%s", True, pos_lo, centre)
+    fn, where, _keep = _pt_state_fn("fr_escape_extend_pt%s", True, pos_lo, centre, scaled)
     _native.check(fn(C.byref(config), where, y0, y1, int(from_iterations), z_ptr or None, iters_ptr or None, dz_ptr or None,
                      m_ptr or None, _stream(stream)))
 

@@ -336,6 +336,21 @@ PROTOTYPES = {
         C.c_int, [C.POINTER(fr_config), _WIDE, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "fr_debug_pt_scaled_count": (
         C.c_int, [C.POINTER(fr_config), _WIDE, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fr_escape_rows_pt_scaled_state_device": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "fr_escape_extend_pt_scaled_device": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p],
+    ),
+    "fr_escape_rows_pt_scaled_state": (
+        C.c_int, [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fr_escape_extend_pt_scaled": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
     "fr_colour_rows_device": (
         C.c_int,
         [C.POINTER(fr_config), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],

@@ -237,10 +237,12 @@ int launch_pt(Ctx &ctx, const fr_config *cfg, const Centre &c, const fr_kparams 
 
 /* For BLA-PT (fr_bla.hip), from fr_pt.hip: the view's orbits in device memory as launch_pt finds them (the context's cache,
  * computed and uploaded on a miss) — `keep` holds them alive and is their identity, v.k == v.x for Mandelbrot — and orbit
- * `which` (0: R or V, 1: K) on the host as re, im pairs appended to `out`, no device needed.  Arguments already checked. */
+ * `which` (0: R or V, 1: K) on the host as re, im pairs appended to `out`, no device needed.  Arguments already checked.
+ * `ended`: bit 0 = X, bit 1 = K is ended by escape (PtOrbit::ended(); the state kernels' rebase rule reads it). */
 struct PtOrbitView {
     const double2 *x = nullptr, *k = nullptr;
     uint32_t x_last = 0, k_last = 0;
+    uint32_t ended = 0;
 };
 int pt_orbit_view(Ctx &ctx, const fr_config *cfg, const Centre &c, std::shared_ptr<PtOrbit> &keep, PtOrbitView &v);
 void pt_host_orbit(const fr_config *cfg, const Centre &c, int which, std::vector<double> &out);

@@ -611,6 +611,7 @@ int pt_orbit_view(Ctx &ctx, const fr_config *cfg, const Centre &c, std::shared_p
     v.k = julia ? keep->dev + keep->k_offset : keep->dev;
     v.x_last = keep->x_last;
     v.k_last = julia ? keep->k_last : keep->x_last;
+    v.ended = keep->ended();
     return FR_OK;
 }
 

@@ -18,6 +18,14 @@
  *     w and (S, 1) otherwise: the factors are SELECTED (two v_cndmask pairs) and the four multiplies, two squares-and-sums
  *     and one compare run on one path for every lane; a multiplication by 1 is exact, so each lane computes exactly the
  *     expression of its form.  The level search does the same with f = Sinv or 1 on w and on each R it probes.
+ *
+ * Resumable SCALED PT (include/fractal_hip.h, "RESUMABLE SCALED PT"; tests/pt_scaled_state_model.c restates it;
+ * tests/test_gpu_pt_scaled_state.py compares the two bit for bit): escape_pt_scaled_state_kernel<JULIA> is the plain loop's
+ * ESCAPE render with the state rule — no rebase at the end of an orbit that the cap cut — and stores the whole state
+ * (z, iters, w, m); escape_extend_pt_scaled_kernel<JULIA> continues such a state to a higher cap in place, on orbits that
+ * fr_pt.hip's cache continued from their integer tails.  They are to orbit_pt_scaled what fr_pt.hip's escape_pt_state_kernel
+ * and escape_extend_pt_kernel are to orbit_pt, in their shape; escape_pt_scaled_kernel and orbit_pt_scaled are SCALED PT's and
+ * stay as they are.  The table form has no state (BLA-PT's reason: i + 2^k <= iterations).
  */
 #include <cmath>
 #include <cstring>
@@ -111,6 +119,187 @@ __device__ __forceinline__ uint32_t orbit_pt_scaled(uint32_t iterations, double 
     out_re = zr;
     out_im = zi;
     return i;
+}
+
+/* ---- device: the resumable state of the plain scaled loop (include/fractal_hip.h, "RESUMABLE SCALED PT") ----------------- */
+
+/* A pixel's state between steps: z, w, the index m into the orbit it follows and whether that orbit is K (Julia after a
+ * rebase).  orbit_pt_scaled_state is orbit_pt_state (fr_pt.hip) with w for dz: it runs `steps` steps of the plain scaled loop
+ * from the state with the state rule's rebase condition — the scaled rebase test, or m == last of an orbit that is ENDED BY
+ * ESCAPE (x_end / k_end: that last index, or ~0 for an orbit cut by the cap, which m never equals) — and leaves the state
+ * after the last step in `s`; on escape the state is (z, 0, 0).  Returns the steps completed before the escape (`steps`:
+ * none).  t.x_last / t.k_last only clamp the loads. */
+struct ScaledState {
+    double zr, zi, wr, wi;
+    uint32_t m;
+    bool on_k;
+};
+
+template <bool JULIA>
+__device__ __forceinline__ uint32_t orbit_pt_scaled_state(uint32_t steps, double wcr, double wci, const ScaledDev &t, uint32_t x_end,
+                                                          uint32_t k_end, double squared, ScaledState &s) {
+    const double S = t.S, Sinv = t.Sinv;
+    const bool on_k = JULIA && s.on_k;
+    const double2 *X = on_k ? t.k_orbit : t.x_orbit;
+    uint32_t last = on_k ? t.k_last : t.x_last, end = on_k ? k_end : x_end;
+    uint32_t m = s.m;
+    bool k_now = on_k;
+    double wr = s.wr, wi = s.wi, zr = s.zr, zi = s.zi;
+    double2 Z = X[min(m, last)], N = X[min(m + 1u, last)]; /* m < last at the top of every step */
+    const double2 K1 = t.k_orbit[1];                       /* the entry after a rebase; K_0 = R_0 = 0 */
+    uint32_t i = 0;
+    for (; i < steps; i++) {
+        const double2 P = X[min(m + 2u, last)]; /* X_{m+2}: next step's X_{m+1} if it does not rebase */
+        const double tr = Z.x + zr, ti = Z.y + zi;
+        const double nwr = __builtin_fma(tr, wr, __builtin_fma(-ti, wi, wcr));
+        const double nwi = __builtin_fma(tr, wi, __builtin_fma(ti, wr, wci));
+        m++;
+        zr = __builtin_fma(nwr, Sinv, N.x);
+        zi = __builtin_fma(nwi, Sinv, N.y);
+        wr = nwr;
+        wi = nwi;
+        const double dist = zr * zr + zi * zi;
+        if (dist > squared) break; /* this lane leaves EXEC; the wave goes on while any lane is left */
+        if (rebase_test(zr, zi, wr, wi, S, Sinv) || m == end) {
+            wr = zr * S;
+            wi = zi * S;
+            m = 0;
+            if (JULIA) {
+                X = t.k_orbit;
+                last = t.k_last;
+                end = k_end;
+                k_now = true;
+            }
+            Z = make_double2(0.0, 0.0);
+            N = K1;
+        } else {
+            Z = N;
+            N = P;
+        }
+    }
+    const bool escaped = i < steps; /* (z, 0, 0) for an escaped lane */
+    s.zr = zr;
+    s.zi = zi;
+    s.wr = escaped ? 0.0 : wr;
+    s.wi = escaped ? 0.0 : wi;
+    s.m = escaped ? 0u : m;
+    s.on_k = !escaped && k_now;
+    return i;
+}
+
+constexpr uint32_t kOnK = 0x80000000u; /* bit 31 of the stored m: the pixel follows K */
+
+/* 16 column and 16 row values of woff for the workgroup's pixels into LDS (scaled_body's staging: p.scale_re and p.scale_im
+ * hold sre and sim); the caller synchronises */
+__device__ __forceinline__ void stage_woff(const fr_kparams &p, uint32_t tid, uint32_t col0, uint32_t row0, double *s_re, double *s_im) {
+    if (tid < kBlockW + kBlockH) {
+        const double width = (double)p.width, height = (double)p.height;
+        if (tid < kBlockW) {
+            const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
+            s_re[tid] = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
+        } else {
+            const uint32_t r = row0 + (tid - kBlockW);
+            const uint64_t y = (uint64_t)p.y_first + (uint64_t)(r / p.block_rows) * p.y_stride + r % p.block_rows;
+            s_im[tid - kBlockW] = (((double)y / height) - 0.5) / p.scale_im;
+        }
+    }
+}
+
+/* escape_pt_scaled_kernel<FR_OUT_ESCAPE>'s shape with the state rule, storing the whole state: z and w as re, im per pixel,
+ * iters, m (bit 31: on K).  `ended`: bit 0 = X, bit 1 = K is ended by escape.  An algorithm without orbits writes zeros. */
+template <bool JULIA>
+__global__ __launch_bounds__(64 * kWaves) void escape_pt_scaled_state_kernel(const fr_kparams p, double *__restrict__ z,
+                                                                            uint32_t *__restrict__ iters, double *__restrict__ w,
+                                                                            uint32_t *__restrict__ mm, const ScaledDev t,
+                                                                            const uint32_t ended) {
+    __shared__ double s_re[kBlockW];
+    __shared__ double s_im[kBlockH];
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kBlockW - 1) / kBlockW);
+    const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+    const uint32_t col0 = bx * kBlockW, row0 = by * kBlockH;
+    stage_woff(p, tid, col0, row0, s_re, s_im);
+    __syncthreads();
+
+    const uint32_t wave = tid >> 6, lane = tid & 63;
+    const uint32_t lx = (wave % kWavesX) * kTileW + lane % kTileW;
+    const uint32_t ly = (wave / kWavesX) * kTileH + lane / kTileW;
+    const uint32_t cx = col0 + lx, r = row0 + ly;
+    if (cx >= p.ncols || r >= p.nrows) return;
+    const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0; /* the host picks JULIA from the algorithm */
+
+    ScaledState s{0.0, 0.0, 0.0, 0.0, 0u, false};
+    uint32_t it = 0;
+    if (escape_algo) {
+        const double woff_re = s_re[lx], woff_im = s_im[ly];
+        s.m = JULIA ? 0u : 1u;
+        s.wr = woff_re;
+        s.wi = woff_im;
+        const double2 X0 = t.x_orbit[min(s.m, t.x_last)];
+        s.zr = __builtin_fma(s.wr, t.Sinv, X0.x);
+        s.zi = __builtin_fma(s.wi, t.Sinv, X0.y);
+        it = orbit_pt_scaled_state<JULIA>(p.iterations, JULIA ? 0.0 : woff_re, JULIA ? 0.0 : woff_im, t, (ended & 1u) ? t.x_last : ~0u,
+                                          (ended & 2u) ? t.k_last : ~0u, p.limit * p.limit, s);
+    }
+    const uint64_t k = (uint64_t)r * p.ncols + cx;
+    z[2 * k] = s.zr;
+    z[2 * k + 1] = s.zi;
+    iters[k] = it;
+    w[2 * k] = s.wr;
+    w[2 * k + 1] = s.wi;
+    mm[k] = s.m | (s.on_k ? kOnK : 0u);
+}
+
+/* Continue a stored state from cap `from` to p.iterations in place (escape_extend_pt_kernel's early-out): `iters` is read
+ * first and a workgroup with no pixel at `from` ends there, having written nothing; a finished pixel's z, w and m are
+ * neither loaded nor stored.  The orbits are those of the new cap. */
+template <bool JULIA>
+__global__ __launch_bounds__(64 * kWaves) void escape_extend_pt_scaled_kernel(const fr_kparams p, double *z, uint32_t *iters, double *w,
+                                                                             uint32_t *mm, const uint32_t from, const ScaledDev t,
+                                                                             const uint32_t ended) {
+    __shared__ double s_re[kBlockW];
+    __shared__ double s_im[kBlockH];
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kBlockW - 1) / kBlockW);
+    const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+    const uint32_t col0 = bx * kBlockW, row0 = by * kBlockH;
+    const uint32_t wave = tid >> 6, lane = tid & 63;
+    const uint32_t lx = (wave % kWavesX) * kTileW + lane % kTileW;
+    const uint32_t ly = (wave / kWavesX) * kTileH + lane / kTileW;
+    const uint32_t cx = col0 + lx, r = row0 + ly;
+    const bool valid = cx < p.ncols && r < p.nrows;
+    const uint64_t k = (uint64_t)r * p.ncols + cx;
+    uint32_t done = 0;
+    if (valid) done = iters[k];
+    const bool running = valid && done == from;
+    if (!__syncthreads_or(running ? 1 : 0)) return; /* whole workgroup (uniform) */
+
+    if (!JULIA) { /* wc = the pixel's woff, staged as the render stages it; Julia's wc is 0 */
+        stage_woff(p, tid, col0, row0, s_re, s_im);
+        __syncthreads();
+    }
+    if (running) {
+        const uint32_t word = mm[k];
+        ScaledState s;
+        s.zr = z[2 * k];
+        s.zi = z[2 * k + 1];
+        s.wr = w[2 * k];
+        s.wi = w[2 * k + 1];
+        s.on_k = JULIA && (word & kOnK) != 0;
+        /* m < last of the orbit followed in every state this view produces; the clamp keeps foreign data inside the orbit */
+        s.m = min(word & ~kOnK, (s.on_k ? t.k_last : t.x_last) - 1u);
+        const uint32_t it = orbit_pt_scaled_state<JULIA>(p.iterations - from, JULIA ? 0.0 : s_re[lx], JULIA ? 0.0 : s_im[ly], t,
+                                                         (ended & 1u) ? t.x_last : ~0u, (ended & 2u) ? t.k_last : ~0u,
+                                                         p.limit * p.limit, s);
+        z[2 * k] = s.zr;
+        z[2 * k + 1] = s.zi;
+        w[2 * k] = s.wr;
+        w[2 * k + 1] = s.wi;
+        mm[k] = s.m | (s.on_k ? kOnK : 0u);
+        iters[k] = from + it; /* it == M - N on exhaustion: the new cap */
+    }
 }
 
 /* ---- device: the scaled loop with table skips (bits >= 0) ------------------------------------------------------------- */
@@ -342,6 +531,20 @@ hipError_t launch(bool julia, bool bla, const fr_kparams &p, int mode, const fr_
     return julia ? launch<true, false>(p, mode, out, t, stream) : launch<false, false>(p, mode, out, t, stream);
 }
 
+/* the state render, or — extend — the extension from `from` */
+template <bool JULIA>
+hipError_t launch_state(const fr_kparams &p, uint32_t from, bool extend, double *z, uint32_t *iters, double *w, uint32_t *m,
+                        const ScaledDev &t, uint32_t ended, hipStream_t stream) {
+    const uint64_t tiles = (((uint64_t)p.ncols + kBlockW - 1) / kBlockW) * (((uint64_t)p.nrows + kBlockH - 1) / kBlockH);
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)tiles), block(64 * kWaves);
+    if (extend)
+        escape_extend_pt_scaled_kernel<JULIA><<<grid, block, 0, stream>>>(p, z, iters, w, m, from, t, ended);
+    else
+        escape_pt_scaled_state_kernel<JULIA><<<grid, block, 0, stream>>>(p, z, iters, w, m, t, ended);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 namespace fr {
@@ -412,6 +615,90 @@ int profiled_launch(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, u
     if (rc == FR_OK) rc = launch_scaled(ctx, cfg, c, bits, p, mode, out, stream);
     if (rc != FR_OK) return rc;
     return prof_end(stream, kernel_name(bits));
+}
+
+/* ---- RESUMABLE SCALED PT: the plain loop's rows with their state, and that state continued to a higher cap -------------- */
+
+/* The domain of the four calls (include/fractal_hip.h), checked before any device work: `from` = nullptr for the state
+ * render.  *work = false: a legal call with nothing to do (no rows; for the extension also M == N or an algorithm without
+ * orbits). */
+int check_scaled_state(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, const void *z,
+                       const void *iters, const void *w, const void *m, bool *work) {
+    *work = false;
+    int bits = -1; /* the calls are the plain loop's */
+    const int rc = check_scaled(cfg, c, bits, y0, y1);
+    if (rc != FR_OK) return rc;
+    if (from && cfg->iterations < *from)
+        return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from a stored state");
+    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
+    if (!z || !iters || !w || !m) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the SCALED PT state is z, iters, w and m, all four");
+    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(w) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u) ||
+        (reinterpret_cast<uintptr_t>(m) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "z and w must be 8-byte aligned, iters and m 4-byte aligned");
+    *work = !from || (cfg->iterations != *from && (cfg->algo == FR_ALGO_MANDELBROT || cfg->algo == FR_ALGO_JULIA));
+    return FR_OK;
+}
+
+/* from == nullptr: the state render; else the extension from *from, on the orbits of cfg's cap, which pt_orbit_view's cache
+ * continues from those of the old one.  On the caller's stream, into the caller's arrays, between the profiling events. */
+int scaled_state_launch(Ctx &ctx, const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, double *d_z,
+                        uint32_t *d_iters, double *d_w, uint32_t *d_m, hipStream_t stream) {
+    fr_kparams p;
+    rows_params(cfg, default_opts(), y0, y1, 0, p);
+    int rc = prof_begin(stream);
+    if (rc != FR_OK) return rc;
+    const char *kname = from ? "escape_extend_pt_scaled_kernel" : "escape_pt_scaled_state_kernel";
+    const bool julia = cfg->algo == 2, extend = from != nullptr;
+    if (cfg->algo != 0 && !julia) { /* no escape-time algorithm: zeros in all four arrays (the extension never gets here) */
+        HIP_TRY(launch_state<false>(p, 0, false, d_z, d_iters, d_w, d_m, ScaledDev{}, 0, stream));
+        return prof_end(stream, kname);
+    }
+    const ScaledConsts k = scaled_consts(cfg);
+    p.scale_re = k.sre;
+    p.scale_im = k.sim;
+    std::shared_ptr<PtOrbit> orbit;
+    PtOrbitView v;
+    rc = pt_orbit_view(ctx, cfg, c, orbit, v);
+    if (rc != FR_OK) return rc;
+    ScaledDev t{};
+    t.x_orbit = v.x;
+    t.k_orbit = v.k;
+    t.x_last = v.x_last;
+    t.k_last = v.k_last;
+    t.S = k.S;
+    t.Sinv = k.Sinv;
+    const uint32_t n = extend ? *from : 0u;
+    HIP_TRY(julia ? launch_state<true>(p, n, extend, d_z, d_iters, d_w, d_m, t, v.ended, stream)
+                  : launch_state<false>(p, n, extend, d_z, d_iters, d_w, d_m, t, v.ended, stream));
+    return prof_end(stream, kname);
+}
+
+int scaled_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z,
+                        void *d_iters, void *d_w, void *d_m, void *hip_stream) {
+    const Centre c{nullptr, centre, true};
+    bool work;
+    int rc = check_scaled_state(cfg, c, y0, y1, from, d_z, d_iters, d_w, d_m, &work);
+    if (rc != FR_OK || !work) return rc;
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    return scaled_state_launch(*ctx, cfg, c, y0, y1, from, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
+                               static_cast<double *>(d_w), static_cast<uint32_t *>(d_m), static_cast<hipStream_t>(hip_stream));
+}
+
+/* the host forms: z and w share the context's z scratch, iters and m its iters scratch (pt_state_host's road) */
+int scaled_state_host(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, const uint32_t *from, double *z,
+                      uint32_t *iters, double *w, uint32_t *m) {
+    const Centre c{nullptr, centre, true};
+    bool work;
+    const int rc = check_scaled_state(cfg, c, y0, y1, from, z, iters, w, m, &work);
+    if (rc != FR_OK || !work) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), w, m, from != nullptr,
+                    [&](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_w, uint32_t *d_m, hipStream_t stream) {
+                        return scaled_state_launch(ctx, cfg, c, y0, y1, from, d_z, d_iters, d_w, d_m, stream);
+                    });
 }
 
 }  // namespace
@@ -529,4 +816,26 @@ int fr_debug_bla_table_scaled(const fr_config *cfg, const fr_wide_centre *centre
     const int rc = check_scaled(cfg, c, bits, 0, 0, true);
     if (rc != FR_OK) return rc;
     return bla_debug_table(cfg, c, bits, true, which, level, out, cap, len);
+}
+
+/* ---- the calls of the resumable state (the plain loop's: no bits) -------------------------------------------------------- */
+
+int fr_escape_rows_pt_scaled_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, void *d_z,
+                                          void *d_iters, void *d_w, void *d_m, void *hip_stream) {
+    return scaled_state_device(cfg, centre, y0, y1, nullptr, d_z, d_iters, d_w, d_m, hip_stream);
+}
+
+int fr_escape_extend_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
+                                      uint32_t from_iterations, void *d_z, void *d_iters, void *d_w, void *d_m, void *hip_stream) {
+    return scaled_state_device(cfg, centre, y0, y1, &from_iterations, d_z, d_iters, d_w, d_m, hip_stream);
+}
+
+int fr_escape_rows_pt_scaled_state(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z,
+                                   uint32_t *iters, double *w, uint32_t *m) {
+    return scaled_state_host(cfg, centre, y0, y1, nullptr, z, iters, w, m);
+}
+
+int fr_escape_extend_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, uint32_t from_iterations,
+                               double *z, uint32_t *iters, double *w, uint32_t *m) {
+    return scaled_state_host(cfg, centre, y0, y1, &from_iterations, z, iters, w, m);
 }

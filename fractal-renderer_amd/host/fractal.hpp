@@ -264,6 +264,19 @@ inline void escape_rows_device(const Config &config, const fr_wide_centre &centr
                                void *hip_stream = nullptr) {
     check(fr_escape_rows_pt_scaled_device(&config, &centre, scaled.bits, 0, config.height, d_z, d_iters, hip_stream));
 }
+// A view past 2^440 kept on the device is (z, iters, w, m), 40 bytes per pixel ("RESUMABLE SCALED PT"): the scaled counterparts
+// of pt_state_rows_device / extend_pt_rows_device above.  The plain loop's (scaled.bits must be -1: the table form has no state);
+// d_w holds the scaled offset w, so only the scaled extension continues what the scaled state render wrote.
+inline void pt_state_rows_device(const Config &config, const fr_wide_centre &centre, Scaled scaled, void *d_z, void *d_iters, void *d_w,
+                                 void *d_m, void *hip_stream = nullptr) {
+    if (scaled.bits != -1) throw std::invalid_argument("SCALED PT: only the plain loop (bits = -1) has a resumable state");
+    check(fr_escape_rows_pt_scaled_state_device(&config, &centre, 0, config.height, d_z, d_iters, d_w, d_m, hip_stream));
+}
+inline void extend_pt_rows_device(const Config &config, const fr_wide_centre &centre, Scaled scaled, uint32_t from_iterations, void *d_z,
+                                  void *d_iters, void *d_w, void *d_m, void *hip_stream = nullptr) {
+    if (scaled.bits != -1) throw std::invalid_argument("SCALED PT: only the plain loop (bits = -1) has a resumable state");
+    check(fr_escape_extend_pt_scaled_device(&config, &centre, 0, config.height, from_iterations, d_z, d_iters, d_w, d_m, hip_stream));
+}
 
 }  // namespace fractal
 #endif

@@ -306,7 +306,34 @@ typedef struct fr_config {
  * these changes: limit <= 2^20 (the default, 65536, is inside); min(|scale.re|, |scale.im|) >= 2^-32 max(|scale.re|,
  * |scale.im|); no 2^440 rule — what bounds the scale is F >= e + 64 with n <= 16, so e <= 952 and |scale| < 2^952; bits = -1
  * (no table: the plain scaled loop), 0 (= FR_BLA_DEFAULT_BITS) or 24 .. 53.  One device.  OUT OF SCOPE: supersampling,
- * block-cyclic and multi-device renders do not take SCALED PT, and it has no resumable state and no extend form. */
+ * block-cyclic and multi-device renders do not take SCALED PT.  Its plain loop (bits = -1) has a resumable state and an extend
+ * form, RESUMABLE SCALED PT below; its table form (bits >= 0) has neither, for BLA-PT's reason: the condition
+ * i + 2^k <= iterations makes a run at cap N no prefix of the run at cap M.  A state written by the fr_*_pt_wide_state calls is
+ * no input of the scaled extension: it holds dz where the scaled state holds w.
+ *
+ * RESUMABLE SCALED PT (fr_escape_rows_pt_scaled_state, fr_escape_extend_pt_scaled below): the state that lets a SCALED PT
+ * view's cap be raised in place.  It is SCALED PT's plain loop (bits = -1) with ONE change, to the rebase condition: rebase on
+ * the scaled rebase test, or when m == last of X AND X is ended by escape.  Both forms of the scaled rebase test (BIG and
+ * not) stay as they are; "ended by escape" and "cut by the cap" are RESUMABLE PT's terms, applied to the stored f64 entries.
+ *   The resumable state of a pixel after N steps is (z, w, m, onK).  Stored form, 40 bytes per pixel, in RESUMABLE PT's
+ *   layout: z (2 doubles, as fr_escape_rows_pt_scaled gives it with bits = -1), iters (one uint32), w (2 doubles: the SCALED
+ *   offset — this array holds w, not dz), m as uint32 whose bit 31 is set when a Julia pixel follows K (never for
+ *   Mandelbrot).  An escaped pixel stores w = (0, 0), m = 0.  N = 0 stores the initial state (Mandelbrot: m = 1; Julia:
+ *   m = 0; w = woff; z = fma(w, Sinv, X_m) per axis).
+ *   CLAIM 1: for every N, z and iters of the state run equal SCALED PT's at cap N with bits = -1, bit for bit.
+ *   CLAIM 2: continuing the state from N for M - N steps on the orbits of cap M gives the state run at cap M, bit for bit in
+ *   all four arrays.
+ *   Why: RESUMABLE PT's argument, word for word.  It uses only the bounds on m (after step i, m <= i + 2 for Mandelbrot or
+ *   i + 1 for Julia on V, and m <= N - 1 on K after a rebase) and last = N + 1 (R) or N (V, K) of an orbit cut by the cap; the
+ *   scaling touches neither.  So on a cut orbit m == last is met only at the final step i = N - 1, by a pixel that never
+ *   rebased; there SCALED PT's rebase changes (w, m) and leaves z alone, which is invisible in its output and is the only
+ *   event of the loop that depends on the cap.  The state rule leaves it out.
+ *   CLAIM 3: for every view in WIDE PT's domain with limit <= 2^20 in which no intermediate of the unscaled run is subnormal,
+ *   z, iters and m equal those of fr_escape_rows_pt_wide_state bit for bit, and w equals dz 2^e exactly (multiplication by
+ *   a power of two commutes with every rounding).
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): SCALED PT's, with the centre REQUIRED; there
+ * is no bits argument, the calls are the plain loop's; for the extension M >= N (M == N is a legal no-op that needs no
+ * device, as y0 == y1 is); all four arrays, z and w 8-byte aligned, iters and m 4-byte aligned (y0 == y1 needs none). */
 #define FR_BLA_DEFAULT_BITS 40
 #define FR_PT_MAX_ITERATIONS (1u << 24)
 #define FR_WIDE_MAX_WORDS 16
@@ -802,6 +829,38 @@ int fr_debug_bla_table_scaled(const fr_config *cfg, const fr_wide_centre *centre
  * nominal iterations. */
 int fr_debug_pt_scaled_count(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1,
                              uint64_t *passes, uint64_t *steps);
+
+/* RESUMABLE SCALED PT (fr_precision above): a GUI keeps a view past 2^440 as (z, iters, w, m) in DEVICE memory — 40 bytes per
+ * pixel — and answers an iterations change with fr_escape_extend_pt_scaled_device; fr_colour_rows_device over (z, iters) with
+ * z_width 2 colours it.  The calls are the plain scaled loop's and take no bits.  Each is the exact counterpart of the
+ * fr_*_pt_wide call it is named after, with d_w / w where that one has d_dz / dz: the same buffers, alignment and asynchrony
+ * on `hip_stream`, nothing allocated, and the same precondition / result contract of the extension.
+ *   fr_escape_rows_pt_scaled_state(_device): rows [y0, y1) with their state; d_z, d_w 2 doubles per pixel (re, im), 8-byte
+ *   aligned; d_iters, d_m one uint32 per pixel, 4-byte aligned; all four required (y0 == y1 needs none and no device);
+ *   k = (y-y0)*width + x.  d_z and d_iters receive what fr_escape_rows_pt_scaled gives with bits = -1, bit for bit.  An
+ *   algorithm without orbits (BarnsleyFern) writes zeros.  fr_last_kernel_name reports escape_pt_scaled_state_kernel.
+ *   fr_escape_extend_pt_scaled(_device): raise the cap of a stored state IN PLACE, N = from_iterations -> M = cfg->iterations,
+ *   cfg_N = cfg with iterations = N.
+ *     Precondition: the arrays hold what fr_escape_rows_pt_scaled_state_device(cfg_N, centre, y0, y1, ...) writes.
+ *     Result: after the call they hold what the same call writes for cfg, bit for bit in all four arrays.
+ *     A pixel with iters[k] != N is finished: only that word is read; its z, w and m are neither loaded nor written.  Values
+ *     of iters[k] above N are foreign data and are left alone like finished pixels.
+ *   The library CANNOT check the precondition: arrays from another view or cap — or a state of the fr_*_pt_wide_state calls,
+ *   which holds dz, not w — are continued as if they were this view's (an index m beyond the orbit is brought inside it,
+ *   nothing more).  Nor is the call idempotent: in arrays that already hold cap M, iters[k] == N means "escaped at step N",
+ *   and a second call N -> M would continue those pixels.  M == N is a legal no-op that needs no device; an algorithm without
+ *   orbits: nothing is done.  fr_last_kernel_name reports escape_extend_pt_scaled_kernel.
+ * The orbit is the shared slot's: raising the cap of a scaled view computes only the missing entries, from the orbit's last
+ * entry kept as integers, and nothing when every orbit is ended by escape (fr_debug_pt_orbit_cache shows it).  The host
+ * forms go through the context's scratch: upload (extension), launch, download, synchronise. */
+int fr_escape_rows_pt_scaled_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, void *d_z,
+                                          void *d_iters, void *d_w, void *d_m, void *hip_stream);
+int fr_escape_extend_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
+                                      uint32_t from_iterations, void *d_z, void *d_iters, void *d_w, void *d_m, void *hip_stream);
+int fr_escape_rows_pt_scaled_state(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z,
+                                   uint32_t *iters, double *w, uint32_t *m);
+int fr_escape_extend_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, uint32_t from_iterations,
+                               double *z, uint32_t *iters, double *w, uint32_t *m);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 

@@ -168,6 +168,10 @@ extern "C" {
     pub fn fr_escape_rows_pt_scaled_device(cfg: *const fr_config, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, d_z: *mut c_void, d_iters: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn fr_debug_bla_table_scaled(cfg: *const fr_config, centre: *const fr_wide_centre, bits: c_int, which: c_int, level: u32, out: *mut f64, cap: usize, len: *mut u32) -> c_int;
     pub fn fr_debug_pt_scaled_count(cfg: *const fr_config, centre: *const fr_wide_centre, bits: c_int, y0: u32, y1: u32, passes: *mut u64, steps: *mut u64) -> c_int;
+    pub fn fr_escape_rows_pt_scaled_state_device(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, d_z: *mut c_void, d_iters: *mut c_void, d_w: *mut c_void, d_m: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_escape_extend_pt_scaled_device(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, from_iterations: u32, d_z: *mut c_void, d_iters: *mut c_void, d_w: *mut c_void, d_m: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn fr_escape_rows_pt_scaled_state(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, z: *mut f64, iters: *mut u32, w: *mut f64, m: *mut u32) -> c_int;
+    pub fn fr_escape_extend_pt_scaled(cfg: *const fr_config, centre: *const fr_wide_centre, y0: u32, y1: u32, from_iterations: u32, z: *mut f64, iters: *mut u32, w: *mut f64, m: *mut u32) -> c_int;
 }
 
 /// Message of the last failing call on this thread.
