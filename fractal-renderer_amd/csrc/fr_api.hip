@@ -783,20 +783,14 @@ int prof_end(hipStream_t stream, const char *kname) {
 
 int render_deep_device(Ctx &ctx, int precision, const fr_config *cfg, const Centre &c, const Opts &o, uint32_t y0, uint32_t y1,
                        unsigned bpp, void *d_out, hipStream_t stream) {
-    fr_kparams p;
-    rows_params(cfg, o, y0, y1, bpp, p); /* the colour constants; no loop plan, no kernel choice, no view sample */
     fr_kout out{};
     out.rgb = static_cast<uint8_t *>(d_out);
-    int prc = prof_begin(stream);
-    if (prc != FR_OK) return prc;
-    const char *kname = "";
-    if (precision == FR_PRECISION_PT) {
-        const int rc = launch_pt(ctx, cfg, c, p, FR_OUT_RGB, out, stream, &kname);
-        if (rc != FR_OK) return rc;
-    } else {
+    /* the colour constants; no loop plan, no kernel choice, no view sample */
+    return profiled_rows(cfg, o, y0, y1, bpp, stream, [&](fr_kparams &p, const char *&kname) -> int {
+        if (precision == FR_PRECISION_PT) return launch_pt(ctx, cfg, c, p, FR_OUT_RGB, out, stream, &kname);
         HIP_TRY(fr_launch_escape_dd(p, c.lo_re(), c.lo_im(), FR_OUT_RGB, out, false, stream, &kname));
-    }
-    return prof_end(stream, kname);
+        return FR_OK;
+    });
 }
 
 std::atomic<int> g_dispatch_sampling{1};
@@ -1189,15 +1183,13 @@ int render_rows_device(const fr_config *cfg, int precision, const Centre &c, uin
     if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < bytes_per_pixel*width*(y1-y0)");
     if (bytes_per_pixel == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u))
         return fail(FR_ERR_INVALID_ARGUMENT, "RGBA8 output must be 4-byte aligned");
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    if (precision == FR_PRECISION_DD || precision == FR_PRECISION_PT)
-        return render_deep_device(*ctx, precision, cfg, c, o, y0, y1, bytes_per_pixel, d_out, static_cast<hipStream_t>(hip_stream));
-    fr_kparams p;
-    rows_params(cfg, o, y0, y1, bytes_per_pixel, p);
-    return render_device(*ctx, cfg, p, precision, o, d_out, static_cast<hipStream_t>(hip_stream));
+    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
+        if (precision == FR_PRECISION_DD || precision == FR_PRECISION_PT)
+            return render_deep_device(ctx, precision, cfg, c, o, y0, y1, bytes_per_pixel, d_out, stream);
+        fr_kparams p;
+        rows_params(cfg, o, y0, y1, bytes_per_pixel, p);
+        return render_device(ctx, cfg, p, precision, o, d_out, stream);
+    });
 }
 
 /* the escape launch of the grid set in `p`, whatever the precision; `zw` doubles of z per pixel (2: re, im — DD: the hi
@@ -1220,35 +1212,12 @@ int escape_rows(const fr_config *cfg, int precision, const Centre &c, uint32_t y
     int rc = check_rows(cfg, y0, y1);
     if (rc == FR_OK) rc = c.check(cfg, precision);
     if (rc != FR_OK) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    if (npx == 0 || (!z && !iters)) return FR_OK;
-    return host_raw(z, npx * zw * sizeof(double), iters, npx * sizeof(uint32_t), nullptr, nullptr, false,
-                    [&](Ctx &ctx, double *d_z, uint32_t *d_iters, double *, uint32_t *, hipStream_t stream) {
-                        const Opts o = default_opts();
-                        fr_kparams p;
-                        rows_params(cfg, o, y0, y1, 0, p);
-                        fr_kout ko{};
-                        ko.z = d_z;
-                        ko.iters = d_iters;
-                        return launch_escape_rows(ctx, cfg, precision, c, o, p, zw, ko, stream, nullptr);
-                    });
-}
-
-/* what escape_rows() launches, on the caller's stream into the caller's arrays, between the profiling events: no scratch, no
- * copy, no ctx->mu */
-static int escape_rows_launch(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const Opts &o, uint32_t y0, uint32_t y1,
-                              unsigned zw, double *d_z, uint32_t *d_iters, hipStream_t stream) {
-    fr_kparams p;
-    rows_params(cfg, o, y0, y1, 0, p);
-    fr_kout ko{};
-    ko.z = d_z;
-    ko.iters = d_iters;
-    int rc = prof_begin(stream);
-    if (rc != FR_OK) return rc;
-    const char *kname = "";
-    rc = launch_escape_rows(ctx, cfg, precision, c, o, p, zw, ko, stream, &kname);
-    if (rc != FR_OK) return rc;
-    return prof_end(stream, kname);
+    return raw_rows_host(cfg, y0, y1, z, iters, zw, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
+        const Opts o = default_opts();
+        fr_kparams p;
+        rows_params(cfg, o, y0, y1, 0, p);
+        return launch_escape_rows(ctx, cfg, precision, c, o, p, zw, ko, stream, nullptr);
+    });
 }
 
 }  // namespace fr
@@ -1396,12 +1365,10 @@ int fr_render_block_cyclic_range_rgb8_device_opts(const fr_config *cfg, int prec
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
     rc = check_precision(precision); /* before the device: FR_PRECISION_DD is refused here without one too */
     if (rc != FR_OK) return rc;
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    return render_block_cyclic(*ctx, cfg, precision, o, block_rows, first_block, block_stride, max_blocks, dest_is_image,
-                               d_out, out_len, static_cast<hipStream_t>(hip_stream), rows_written);
+    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
+        return render_block_cyclic(ctx, cfg, precision, o, block_rows, first_block, block_stride, max_blocks, dest_is_image, d_out, out_len,
+                                   stream, rows_written);
+    });
 }
 
 int fr_render_block_cyclic_range_rgb8_device(const fr_config *cfg, int precision, uint32_t block_rows,
@@ -1597,16 +1564,12 @@ int fr_escape_rows_device(const fr_config *cfg, int precision, const fr_imaginar
     Opts o;
     rc = resolve_opts(opts, o);
     if (rc != FR_OK) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    if (npx == 0 || (!d_z && !d_iters)) return FR_OK;
-    if (reinterpret_cast<uintptr_t>(d_z) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_z must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_iters) & 3u) return fail(FR_ERR_INVALID_ARGUMENT, "d_iters must be 4-byte aligned");
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    return escape_rows_launch(*ctx, cfg, precision, Centre{pos_lo, nullptr}, o, y0, y1, (unsigned)z_width, static_cast<double *>(d_z),
-                              static_cast<uint32_t *>(d_iters), static_cast<hipStream_t>(hip_stream));
+    /* what escape_rows() launches, on the caller's stream into the caller's arrays, between the profiling events */
+    return raw_rows_device(cfg, y0, y1, d_z, d_iters, hip_stream, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
+        return profiled_rows(cfg, o, y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) {
+            return launch_escape_rows(ctx, cfg, precision, Centre{pos_lo, nullptr}, o, p, (unsigned)z_width, ko, stream, &kname);
+        });
+    });
 }
 
 /* The domain of the extension (include/fractal_hip.h), checked before any device work.  *work = false: a legal call with
@@ -1642,18 +1605,15 @@ static int check_extend(const fr_config *cfg, int precision, const fr_imaginary 
 static int extend_launch(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const Opts &o, uint32_t y0, uint32_t y1,
                          uint32_t from_iterations, double *d_z, uint32_t *d_iters, hipStream_t stream) {
     const Centre c{pos_lo, nullptr};
-    fr_kparams p;
-    rows_params(cfg, o, y0, y1, 0, p);
-    int rc = prof_begin(stream);
-    if (rc != FR_OK) return rc;
-    const char *kname = "";
-    if (precision == FR_PRECISION_DD) {
-        HIP_TRY(fr_launch_escape_extend_dd(p, c.lo_re(), c.lo_im(), from_iterations, d_z, d_iters, stream, &kname));
-    } else {
-        plan_loop(cfg, precision, o, p); /* loop_spec: the speculative blocks, unless opts->loop_mode == 5 */
-        HIP_TRY(fr_launch_escape_extend(p, precision, from_iterations, d_z, d_iters, stream, &kname));
-    }
-    return prof_end(stream, kname);
+    return profiled_rows(cfg, o, y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) -> int {
+        if (precision == FR_PRECISION_DD) {
+            HIP_TRY(fr_launch_escape_extend_dd(p, c.lo_re(), c.lo_im(), from_iterations, d_z, d_iters, stream, &kname));
+        } else {
+            plan_loop(cfg, precision, o, p); /* loop_spec: the speculative blocks, unless opts->loop_mode == 5 */
+            HIP_TRY(fr_launch_escape_extend(p, precision, from_iterations, d_z, d_iters, stream, &kname));
+        }
+        return FR_OK;
+    });
 }
 
 int fr_escape_extend_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
@@ -1663,12 +1623,10 @@ int fr_escape_extend_device(const fr_config *cfg, int precision, const fr_imagin
     bool work;
     int rc = check_extend(cfg, precision, pos_lo, y0, y1, from_iterations, z_width, d_z, d_iters, opts, o, &work);
     if (rc != FR_OK || !work) return rc;
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    return extend_launch(cfg, precision, pos_lo, o, y0, y1, from_iterations, static_cast<double *>(d_z),
-                         static_cast<uint32_t *>(d_iters), static_cast<hipStream_t>(hip_stream));
+    return device_form(hip_stream, [&](Ctx &, hipStream_t stream) {
+        return extend_launch(cfg, precision, pos_lo, o, y0, y1, from_iterations, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
+                             stream);
+    });
 }
 
 int fr_escape_extend(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1,
@@ -1764,33 +1722,17 @@ int fr_count_iterations(const fr_config *cfg, int precision, uint32_t y0, uint32
     p.y_stride = sy;
     if (pixels) *pixels = (uint64_t)p.ncols * p.nrows;
     if (p.ncols == 0 || p.nrows == 0) return FR_OK;
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    const size_t slot_bytes = sizeof(unsigned long long) * FR_COUNT_SLOTS;
-    rc = ctx->reserve(ctx->misc, slot_bytes);
-    if (rc != FR_OK) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->misc.ptr, 0, slot_bytes, ctx->stream));
-    fr_kout ko{};
-    ko.count = static_cast<unsigned long long *>(ctx->misc.ptr);
-    if (precision == FR_PRECISION_DD) {
-        HIP_TRY(fr_launch_escape_dd(p, 0.0, 0.0, FR_OUT_COUNT, ko, false, ctx->stream, nullptr));
-    } else if (precision == FR_PRECISION_PT) {
-        rc = launch_pt(*ctx, cfg, Centre{}, p, FR_OUT_COUNT, ko, ctx->stream, nullptr);
-        if (rc != FR_OK) return rc;
-    } else {
-        plan_loop(cfg, precision, o, p);
-        HIP_TRY(fr_launch_escape(p, precision, FR_OUT_COUNT, ko, o.tile, ctx->stream, nullptr));
-    }
-    std::vector<unsigned long long> host(FR_COUNT_SLOTS);
-    HIP_TRY(hipMemcpyAsync(host.data(), ctx->misc.ptr, slot_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    unsigned long long sum = 0;
-    for (unsigned long long v : host) sum += v;
-    *total = sum;
-    return FR_OK;
+    uint64_t *const sums[1] = {total};
+    return count_rows(sums, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) -> int {
+        if (precision == FR_PRECISION_PT) return launch_pt(ctx, cfg, Centre{}, p, FR_OUT_COUNT, ko, stream, nullptr);
+        if (precision == FR_PRECISION_DD) {
+            HIP_TRY(fr_launch_escape_dd(p, 0.0, 0.0, FR_OUT_COUNT, ko, false, stream, nullptr));
+        } else {
+            plan_loop(cfg, precision, o, p);
+            HIP_TRY(fr_launch_escape(p, precision, FR_OUT_COUNT, ko, o.tile, stream, nullptr));
+        }
+        return FR_OK;
+    });
 }
 
 int fr_set_profiling(int enabled) {

@@ -29,6 +29,10 @@
  *   - one 16-byte gather of X at the new m, which is also the next plain step's X_m.  After the first skip the lanes of a
  *     wave no longer share m, so PT's one-step-ahead load of X_{m+2} has nothing to aim at and is not carried over: the
  *     latency is covered by the other waves of the CU (the kernel runs at 8 waves per SIMD).
+ *
+ * The calls, at the end of the file: each builds its Centre, runs check_bla and hands bla_rows — the profiled launch of its
+ * rows — to the row-call body of its form in fr_ctx.h (rgb_rows_device, rgb_rows_host, raw_rows_device, raw_rows_host,
+ * count_rows).  The workgroup's geometry and the launch's grid are the deep kernels' (fr_kernels.h: kDeep*, fr_deep_grid).
  */
 #include <cmath>
 #include <cstring>
@@ -43,11 +47,6 @@
 namespace {
 
 #include "fr_colour.h"
-
-constexpr int kWaves = 4;               /* 256-thread workgroups */
-constexpr int kTileW = 8, kTileH = 8;   /* one wave = 8 x 8 pixels */
-constexpr int kWavesX = 2, kWavesY = 2;
-constexpr int kBlockW = kTileW * kWavesX, kBlockH = kTileH * kWavesY; /* 16 x 16 pixels per workgroup */
 
 /* the orbits and their tables as the kernel sees them; Mandelbrot: the k fields repeat the x fields */
 struct BlaDev {
@@ -149,37 +148,37 @@ __device__ __forceinline__ uint32_t orbit_bla(uint32_t iterations, double off_re
 }
 
 template <int MODE, bool JULIA>
-__global__ __launch_bounds__(64 * kWaves) void escape_bla_kernel(const fr_kparams p, const fr_kout out, const BlaDev t) {
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_bla_kernel(const fr_kparams p, const fr_kout out, const BlaDev t) {
     __shared__ double s_tab[FR_LOG2_N * 3];
-    __shared__ double s_re[kBlockW];
-    __shared__ double s_im[kBlockH];
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
 
     const uint32_t tid = threadIdx.x;
-    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kBlockW - 1) / kBlockW);
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
     const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
-    const uint32_t col0 = bx * kBlockW, row0 = by * kBlockH;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
 
     if (MODE == FR_OUT_RGB) {
         const double *gt = &g_log2_tab[0][0];
-        for (uint32_t k = tid; k < FR_LOG2_N * 3; k += 64 * kWaves) s_tab[k] = gt[k];
+        for (uint32_t k = tid; k < FR_LOG2_N * 3; k += 64 * kDeepWaves) s_tab[k] = gt[k];
     }
-    if (tid < kBlockW + kBlockH) {
+    if (tid < kDeepBlockW + kDeepBlockH) {
         /* off: coord_to_space (calc/src/lib.rs:181-197) without the final `+ pos`, PT's off */
         const double width = (double)p.width, height = (double)p.height;
-        if (tid < kBlockW) {
+        if (tid < kDeepBlockW) {
             const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
             s_re[tid] = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
         } else {
-            const uint32_t r = row0 + (tid - kBlockW);
+            const uint32_t r = row0 + (tid - kDeepBlockW);
             const uint64_t y = (uint64_t)p.y_first + (uint64_t)(r / p.block_rows) * p.y_stride + r % p.block_rows;
-            s_im[tid - kBlockW] = (((double)y / height) - 0.5) / p.scale_im;
+            s_im[tid - kDeepBlockW] = (((double)y / height) - 0.5) / p.scale_im;
         }
     }
     __syncthreads();
 
     const uint32_t wave = tid >> 6, lane = tid & 63;
-    const uint32_t lx = (wave % kWavesX) * kTileW + lane % kTileW;
-    const uint32_t ly = (wave / kWavesX) * kTileH + lane / kTileW;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
     const uint32_t cx = col0 + lx, r = row0 + ly;
     const bool valid = cx < p.ncols && r < p.nrows;
     const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0; /* the host picks JULIA from the algorithm */
@@ -239,9 +238,9 @@ __global__ __launch_bounds__(64 * kWaves) void escape_bla_kernel(const fr_kparam
 
 template <bool JULIA>
 hipError_t launch(const fr_kparams &p, int mode, const fr_kout &out, const BlaDev &t, hipStream_t stream) {
-    const uint64_t tiles = (((uint64_t)p.ncols + kBlockW - 1) / kBlockW) * (((uint64_t)p.nrows + kBlockH - 1) / kBlockH);
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const dim3 grid((uint32_t)tiles), block(64 * kWaves);
+    dim3 grid, block;
+    const hipError_t e = fr_deep_grid(p, grid, block);
+    if (e != hipSuccess) return e;
     if (mode == FR_OUT_RGB)
         escape_bla_kernel<FR_OUT_RGB, JULIA><<<grid, block, 0, stream>>>(p, out, t);
     else if (mode == FR_OUT_ESCAPE)
@@ -447,16 +446,15 @@ int check_bla(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uin
     return FR_OK;
 }
 
-/* rows [y0, y1) on `stream` between the profiling events (fr_set_profiling), named for fr_last_kernel_name; the colour
- * constants alone: no loop plan, no kernel choice, no view sample */
-int profiled_launch(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, unsigned channels, int mode,
-                    const fr_kout &out, hipStream_t stream) {
-    fr_kparams p;
-    rows_params(cfg, default_opts(), y0, y1, channels, p);
-    int rc = prof_begin(stream);
-    if (rc == FR_OK) rc = launch_bla(ctx, cfg, c, bits, p, mode, out, stream);
-    if (rc != FR_OK) return rc;
-    return prof_end(stream, "escape_bla_kernel");
+/* The launch every row call below hands to its helper (fr_ctx.h): rows [y0, y1) in `mode` on `stream` between the profiling
+ * events; the colour constants alone: no loop plan, no kernel choice, no view sample */
+auto bla_rows(const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, unsigned channels, int mode) {
+    return [=](Ctx &ctx, const fr_kout &out, hipStream_t stream) {
+        return profiled_rows(cfg, default_opts(), y0, y1, channels, stream, [&](fr_kparams &p, const char *&kname) {
+            kname = "escape_bla_kernel";
+            return launch_bla(ctx, cfg, c, bits, p, mode, out, stream);
+        });
+    };
 }
 
 }  // namespace
@@ -470,19 +468,7 @@ int fr_render_rows_pt_bla_device(const fr_config *cfg, const fr_imaginary *pos_l
     int rc = check_channels(channels);
     if (rc == FR_OK) rc = check_bla(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
-    const size_t need = (size_t)channels * cfg->width * (size_t)(y1 - y0);
-    if (need == 0) return FR_OK;
-    if (!d_out) return fail(FR_ERR_INVALID_ARGUMENT, "d_out is NULL");
-    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*(y1-y0)");
-    if (channels == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u))
-        return fail(FR_ERR_INVALID_ARGUMENT, "RGBA8 output must be 4-byte aligned");
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    fr_kout ko{};
-    ko.rgb = static_cast<uint8_t *>(d_out);
-    return profiled_launch(*ctx, cfg, c, bits, y0, y1, (unsigned)channels, FR_OUT_RGB, ko, static_cast<hipStream_t>(hip_stream));
+    return rgb_rows_device(cfg, y0, y1, channels, d_out, out_len, hip_stream, bla_rows(cfg, c, bits, y0, y1, (unsigned)channels, FR_OUT_RGB));
 }
 
 int fr_render_rows_pt_bla(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
@@ -491,81 +477,35 @@ int fr_render_rows_pt_bla(const fr_config *cfg, const fr_imaginary *pos_lo, cons
     int rc = check_channels(channels);
     if (rc == FR_OK) rc = check_bla(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
-    const size_t need = (size_t)channels * cfg->width * (size_t)(y1 - y0);
-    if (need == 0) return FR_OK;
-    if (!out) return fail(FR_ERR_INVALID_ARGUMENT, "out is NULL");
-    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*(y1-y0)");
-    return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) {
-        fr_kout ko{};
-        ko.rgb = static_cast<uint8_t *>(d_out);
-        return profiled_launch(ctx, cfg, c, bits, y0, y1, (unsigned)channels, FR_OUT_RGB, ko, stream);
-    });
+    return rgb_rows_host(cfg, y0, y1, channels, out, out_len, bla_rows(cfg, c, bits, y0, y1, (unsigned)channels, FR_OUT_RGB));
 }
 
 int fr_escape_rows_pt_bla_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
                                  uint32_t y1, void *d_z, void *d_iters, void *hip_stream) {
     const Centre c{pos_lo, centre};
-    int rc = check_bla(cfg, c, bits, y0, y1);
+    const int rc = check_bla(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    if (npx == 0 || (!d_z && !d_iters)) return FR_OK;
-    if (reinterpret_cast<uintptr_t>(d_z) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_z must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_iters) & 3u) return fail(FR_ERR_INVALID_ARGUMENT, "d_iters must be 4-byte aligned");
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    fr_kout ko{};
-    ko.z = static_cast<double *>(d_z);
-    ko.iters = static_cast<uint32_t *>(d_iters);
-    return profiled_launch(*ctx, cfg, c, bits, y0, y1, 0, FR_OUT_ESCAPE, ko, static_cast<hipStream_t>(hip_stream));
+    return raw_rows_device(cfg, y0, y1, d_z, d_iters, hip_stream, bla_rows(cfg, c, bits, y0, y1, 0, FR_OUT_ESCAPE));
 }
 
 int fr_escape_rows_pt_bla(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
                           uint32_t y1, double *z, uint32_t *iters) {
     const Centre c{pos_lo, centre};
-    int rc = check_bla(cfg, c, bits, y0, y1);
+    const int rc = check_bla(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    if (npx == 0 || (!z && !iters)) return FR_OK;
-    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), nullptr, nullptr, false,
-                    [&](Ctx &ctx, double *d_z, uint32_t *d_iters, double *, uint32_t *, hipStream_t stream) {
-                        fr_kout ko{};
-                        ko.z = d_z;
-                        ko.iters = d_iters;
-                        return profiled_launch(ctx, cfg, c, bits, y0, y1, 0, FR_OUT_ESCAPE, ko, stream);
-                    });
+    return raw_rows_host(cfg, y0, y1, z, iters, 2, bla_rows(cfg, c, bits, y0, y1, 0, FR_OUT_ESCAPE));
 }
 
 int fr_debug_bla_count(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
                        uint32_t y1, uint64_t *passes, uint64_t *steps) {
     const Centre c{pos_lo, centre};
-    int rc = check_bla(cfg, c, bits, y0, y1);
+    const int rc = check_bla(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
     if (!passes || !steps) return fail(FR_ERR_INVALID_ARGUMENT, "passes or steps is NULL");
     *passes = *steps = 0;
     if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    const size_t bytes = sizeof(unsigned long long) * 2 * FR_COUNT_SLOTS;
-    rc = ctx->reserve(ctx->misc, bytes);
-    if (rc != FR_OK) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->misc.ptr, 0, bytes, ctx->stream));
-    fr_kout ko{};
-    ko.count = static_cast<unsigned long long *>(ctx->misc.ptr);
-    rc = profiled_launch(*ctx, cfg, c, bits, y0, y1, 0, FR_OUT_COUNT, ko, ctx->stream);
-    if (rc != FR_OK) return rc;
-    std::vector<unsigned long long> host(2 * FR_COUNT_SLOTS);
-    HIP_TRY(hipMemcpyAsync(host.data(), ctx->misc.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (uint32_t s = 0; s < FR_COUNT_SLOTS; s++) {
-        *passes += host[s];
-        *steps += host[FR_COUNT_SLOTS + s];
-    }
-    return FR_OK;
+    uint64_t *const sums[2] = {passes, steps};
+    return count_rows(sums, bla_rows(cfg, c, bits, y0, y1, 0, FR_OUT_COUNT));
 }
 
 int fr_debug_bla_table(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, int which,

@@ -368,6 +368,162 @@ int host_raw(double *z, size_t zb, uint32_t *iters, size_t ib, double *dz, uint3
     return FR_OK;
 }
 
+/* ---- the pieces the row calls are made of.  An entry point builds its Centre, runs its road's domain check and hands one
+ * of these the road's launch, a callable (a lambda: no allocation on the call path).  Each keeps the order of its checks and
+ * their texts: they are behaviour (tests/golden/deep_call_errors.json). ------------------------------------------------- */
+
+/* Rows [y0, y1) as one launch on `stream` between the profiling events (fr_set_profiling): launch(p, kname) gets the rows'
+ * parameters (it may go on to plan its loop in them) and names its kernel for fr_last_kernel_name. */
+template <class Launch>
+int profiled_rows(const fr_config *cfg, const Opts &o, uint32_t y0, uint32_t y1, unsigned channels, hipStream_t stream, Launch &&launch) {
+    fr_kparams p;
+    rows_params(cfg, o, y0, y1, channels, p);
+    int rc = prof_begin(stream);
+    if (rc != FR_OK) return rc;
+    const char *kname = "";
+    rc = launch(p, kname);
+    if (rc != FR_OK) return rc;
+    return prof_end(stream, kname);
+}
+
+/* The device-pointer form of a call: the primary context under the lifetime lock and the caller's stream; no ctx->mu, no
+ * scratch, no synchronisation.  body(ctx, stream). */
+template <class Body>
+int device_form(void *hip_stream, Body &&body) {
+    LifeShared ls;
+    Ctx *ctx;
+    const int rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    return body(*ctx, static_cast<hipStream_t>(hip_stream));
+}
+
+/* The four row calls of a road, after its domain check: RGB / RGBA and raw results (z: zw doubles per pixel), each into
+ * device memory on the caller's stream and into a host buffer.  launch(ctx, ko, stream) renders the rows into `ko`. */
+template <class Launch>
+int rgb_rows_device(const fr_config *cfg, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len, void *hip_stream,
+                    Launch &&launch) {
+    const size_t need = (size_t)channels * cfg->width * (size_t)(y1 - y0);
+    if (need == 0) return FR_OK;
+    if (!d_out) return fail(FR_ERR_INVALID_ARGUMENT, "d_out is NULL");
+    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*(y1-y0)");
+    if (channels == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "RGBA8 output must be 4-byte aligned");
+    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
+        fr_kout ko{};
+        ko.rgb = static_cast<uint8_t *>(d_out);
+        return launch(ctx, ko, stream);
+    });
+}
+
+template <class Launch>
+int rgb_rows_host(const fr_config *cfg, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len, Launch &&launch) {
+    const size_t need = (size_t)channels * cfg->width * (size_t)(y1 - y0);
+    if (need == 0) return FR_OK;
+    if (!out) return fail(FR_ERR_INVALID_ARGUMENT, "out is NULL");
+    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*(y1-y0)");
+    return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) {
+        fr_kout ko{};
+        ko.rgb = static_cast<uint8_t *>(d_out);
+        return launch(ctx, ko, stream);
+    });
+}
+
+template <class Launch>
+int raw_rows_device(const fr_config *cfg, uint32_t y0, uint32_t y1, void *d_z, void *d_iters, void *hip_stream, Launch &&launch) {
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    if (npx == 0 || (!d_z && !d_iters)) return FR_OK;
+    if (reinterpret_cast<uintptr_t>(d_z) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_z must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_iters) & 3u) return fail(FR_ERR_INVALID_ARGUMENT, "d_iters must be 4-byte aligned");
+    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
+        fr_kout ko{};
+        ko.z = static_cast<double *>(d_z);
+        ko.iters = static_cast<uint32_t *>(d_iters);
+        return launch(ctx, ko, stream);
+    });
+}
+
+template <class Launch>
+int raw_rows_host(const fr_config *cfg, uint32_t y0, uint32_t y1, double *z, uint32_t *iters, unsigned zw, Launch &&launch) {
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    if (npx == 0 || (!z && !iters)) return FR_OK;
+    return host_raw(z, npx * zw * sizeof(double), iters, npx * sizeof(uint32_t), nullptr, nullptr, false,
+                    [&](Ctx &ctx, double *d_z, uint32_t *d_iters, double *, uint32_t *, hipStream_t stream) {
+                        fr_kout ko{};
+                        ko.z = d_z;
+                        ko.iters = d_iters;
+                        return launch(ctx, ko, stream);
+                    });
+}
+
+/* MODE COUNT read back: launch(ctx, ko, stream) adds into GROUPS x FR_COUNT_SLOTS zeroed partial sums at ko.count (ctx->misc,
+ * on ctx->stream under ctx->mu); group g's slots are then added to *sums[g]. */
+template <size_t GROUPS, class Launch>
+int count_rows(uint64_t *const (&sums)[GROUPS], Launch &&launch) {
+    LifeShared ls;
+    Ctx *ctx;
+    int rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    constexpr size_t bytes = sizeof(unsigned long long) * GROUPS * FR_COUNT_SLOTS;
+    rc = ctx->reserve(ctx->misc, bytes);
+    if (rc != FR_OK) return rc;
+    HIP_TRY(hipMemsetAsync(ctx->misc.ptr, 0, bytes, ctx->stream));
+    fr_kout ko{};
+    ko.count = static_cast<unsigned long long *>(ctx->misc.ptr);
+    rc = launch(*ctx, ko, ctx->stream);
+    if (rc != FR_OK) return rc;
+    unsigned long long host[GROUPS * FR_COUNT_SLOTS];
+    HIP_TRY(hipMemcpyAsync(host, ctx->misc.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (size_t g = 0; g < GROUPS; g++)
+        for (uint32_t s = 0; s < FR_COUNT_SLOTS; s++) *sums[g] += host[g * FR_COUNT_SLOTS + s];
+    return FR_OK;
+}
+
+/* The resumable state of a perturbation road — z, iters, the offset d (PT: dz, SCALED PT: w) and m — after the road's
+ * domain check.  `from` = nullptr: the state render, else the extension from *from.  check_state is what is left of the
+ * calls' domain (include/fractal_hip.h), before any device work; its texts name the road and the offset.  *work = false: a
+ * legal call with nothing to do (no rows; for the extension also M == N or an algorithm without orbits).  (Internal linkage:
+ * the library's dynamic symbols stay what they were.)
+ * launch(ctx, d_z, d_iters, d_d, d_m, stream): host_raw's; the host form keeps z and d in the context's z scratch, iters and
+ * m in its iters scratch, and uploads them first for an extension. */
+static inline int check_state(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, const void *z, const void *iters,
+                              const void *d, const void *m, const char *road, const char *d_name, bool *work) {
+    *work = false;
+    if (from && cfg->iterations < *from)
+        return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from a stored state");
+    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
+    if (!z || !iters || !d || !m)
+        return fail(FR_ERR_INVALID_ARGUMENT, std::string("NULL array: the ") + road + " state is z, iters, " + d_name + " and m, all four");
+    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(d) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u) ||
+        (reinterpret_cast<uintptr_t>(m) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, std::string("z and ") + d_name + " must be 8-byte aligned, iters and m 4-byte aligned");
+    *work = !from || (cfg->iterations != *from && (cfg->algo == FR_ALGO_MANDELBROT || cfg->algo == FR_ALGO_JULIA));
+    return FR_OK;
+}
+
+template <class Launch>
+int state_device(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z, void *d_iters, void *d_d, void *d_m,
+                 void *hip_stream, const char *road, const char *d_name, Launch &&launch) {
+    bool work;
+    const int rc = check_state(cfg, y0, y1, from, d_z, d_iters, d_d, d_m, road, d_name, &work);
+    if (rc != FR_OK || !work) return rc;
+    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
+        return launch(ctx, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters), static_cast<double *>(d_d),
+                      static_cast<uint32_t *>(d_m), stream);
+    });
+}
+
+template <class Launch>
+int state_host(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, double *z, uint32_t *iters, double *d, uint32_t *m,
+               const char *road, const char *d_name, Launch &&launch) {
+    bool work;
+    const int rc = check_state(cfg, y0, y1, from, z, iters, d, m, road, d_name, &work);
+    if (rc != FR_OK || !work) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), d, m, from != nullptr, launch);
+}
+
 /* multi-device teardown hook, called by fr_shutdown / fr_init_devices with the exclusive lock held */
 void multi_shutdown_locked();
 

@@ -29,11 +29,6 @@ namespace {
 
 #include "fr_colour.h"
 
-constexpr int kDdWaves = 4;             /* 256-thread workgroups */
-constexpr int kDdTileW = 8, kDdTileH = 8; /* one wave = 8 x 8 pixels */
-constexpr int kDdWavesX = 2, kDdWavesY = 2;
-constexpr int kDdBlockW = kDdTileW * kDdWavesX, kDdBlockH = kDdTileH * kDdWavesY; /* 16 x 16 pixels per workgroup */
-
 struct dd {
     double hi, lo;
 };
@@ -111,37 +106,37 @@ __device__ __forceinline__ dd start_dd(double coord, double max, double offset, 
 }
 
 template <int MODE>
-__global__ __launch_bounds__(64 * kDdWaves) void escape_dd_kernel(const fr_kparams p, const fr_kout out, const double lo_re,
-                                                                 const double lo_im, const uint32_t with_lo) {
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_dd_kernel(const fr_kparams p, const fr_kout out, const double lo_re,
+                                                                    const double lo_im, const uint32_t with_lo) {
     __shared__ double s_tab[FR_LOG2_N * 3];
-    __shared__ dd s_re[kDdBlockW];
-    __shared__ dd s_im[kDdBlockH];
+    __shared__ dd s_re[kDeepBlockW];
+    __shared__ dd s_im[kDeepBlockH];
 
     const uint32_t tid = threadIdx.x;
-    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDdBlockW - 1) / kDdBlockW);
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
     const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
-    const uint32_t col0 = bx * kDdBlockW, row0 = by * kDdBlockH;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
 
     if (MODE == FR_OUT_RGB) {
         const double *gt = &g_log2_tab[0][0];
-        for (uint32_t k = tid; k < FR_LOG2_N * 3; k += 64 * kDdWaves) s_tab[k] = gt[k];
+        for (uint32_t k = tid; k < FR_LOG2_N * 3; k += 64 * kDeepWaves) s_tab[k] = gt[k];
     }
-    if (tid < kDdBlockW + kDdBlockH) {
+    if (tid < kDeepBlockW + kDeepBlockH) {
         const double width = (double)p.width, height = (double)p.height;
-        if (tid < kDdBlockW) {
+        if (tid < kDeepBlockW) {
             const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
             s_re[tid] = start_dd((double)x, height, (width / height) / 2.0, p.pos_re, lo_re, p.scale_re);
         } else {
-            const uint32_t r = row0 + (tid - kDdBlockW);
+            const uint32_t r = row0 + (tid - kDeepBlockW);
             const uint64_t y = (uint64_t)p.y_first + (uint64_t)(r / p.block_rows) * p.y_stride + r % p.block_rows;
-            s_im[tid - kDdBlockW] = start_dd((double)y, height, 0.5, p.pos_im, lo_im, p.scale_im);
+            s_im[tid - kDeepBlockW] = start_dd((double)y, height, 0.5, p.pos_im, lo_im, p.scale_im);
         }
     }
     __syncthreads();
 
     const uint32_t wave = tid >> 6, lane = tid & 63;
-    const uint32_t lx = (wave % kDdWavesX) * kDdTileW + lane % kDdTileW;
-    const uint32_t ly = (wave / kDdWavesX) * kDdTileH + lane / kDdTileW;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
     const uint32_t cx = col0 + lx, r = row0 + ly;
     const bool valid = cx < p.ncols && r < p.nrows;
     const bool escape_algo = p.algo == 0 /* Mandelbrot */ || p.algo == 2 /* Julia */;
@@ -208,18 +203,18 @@ __global__ __launch_bounds__(64 * kDdWaves) void escape_dd_kernel(const fr_kpara
  * it on for M - N more with the c the render uses (start_dd of the pixel, or julia_set).  escape_dd_kernel's shape: 4
  * waves, 16 x 16 pixels.  `iters` is read first; a workgroup with no pixel at N ends there, having written nothing, and a
  * finished pixel's z is neither loaded nor stored. */
-__global__ __launch_bounds__(64 * kDdWaves) void escape_extend_dd_kernel(const fr_kparams p, double *z, uint32_t *iters,
-                                                                        const uint32_t from, const double lo_re, const double lo_im) {
-    __shared__ dd s_re[kDdBlockW];
-    __shared__ dd s_im[kDdBlockH];
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_extend_dd_kernel(const fr_kparams p, double *z, uint32_t *iters,
+                                                                           const uint32_t from, const double lo_re, const double lo_im) {
+    __shared__ dd s_re[kDeepBlockW];
+    __shared__ dd s_im[kDeepBlockH];
 
     const uint32_t tid = threadIdx.x;
-    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDdBlockW - 1) / kDdBlockW);
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
     const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
-    const uint32_t col0 = bx * kDdBlockW, row0 = by * kDdBlockH;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
     const uint32_t wave = tid >> 6, lane = tid & 63;
-    const uint32_t lx = (wave % kDdWavesX) * kDdTileW + lane % kDdTileW;
-    const uint32_t ly = (wave / kDdWavesX) * kDdTileH + lane / kDdTileW;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
     const uint32_t cx = col0 + lx, r = row0 + ly;
     const bool valid = cx < p.ncols && r < p.nrows;
     const uint64_t k = (uint64_t)r * p.ncols + cx;
@@ -230,15 +225,15 @@ __global__ __launch_bounds__(64 * kDdWaves) void escape_extend_dd_kernel(const f
 
     const bool julia = p.algo == 2;
     if (!julia) { /* uniform: c = the pixel's start, staged as escape_dd_kernel stages it */
-        if (tid < kDdBlockW + kDdBlockH) {
+        if (tid < kDeepBlockW + kDeepBlockH) {
             const double width = (double)p.width, height = (double)p.height;
-            if (tid < kDdBlockW) {
+            if (tid < kDeepBlockW) {
                 const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
                 s_re[tid] = start_dd((double)x, height, (width / height) / 2.0, p.pos_re, lo_re, p.scale_re);
             } else {
-                const uint32_t rr = row0 + (tid - kDdBlockW);
+                const uint32_t rr = row0 + (tid - kDeepBlockW);
                 const uint64_t y = (uint64_t)p.y_first + (uint64_t)(rr / p.block_rows) * p.y_stride + rr % p.block_rows;
-                s_im[tid - kDdBlockW] = start_dd((double)y, height, 0.5, p.pos_im, lo_im, p.scale_im);
+                s_im[tid - kDeepBlockW] = start_dd((double)y, height, 0.5, p.pos_im, lo_im, p.scale_im);
             }
         }
         __syncthreads();
@@ -267,10 +262,10 @@ hipError_t fr_launch_escape_extend_dd(const fr_kparams &p, double pos_lo_re, dou
     if (kernel_name) *kernel_name = "escape_extend_dd_kernel";
     if (p.ncols == 0 || p.nrows == 0) return hipSuccess;
     if (p.iterations < from_iterations || (p.algo != 0 && p.algo != 2)) return hipErrorInvalidValue;
-    const uint64_t tiles = (((uint64_t)p.ncols + kDdBlockW - 1) / kDdBlockW) * (((uint64_t)p.nrows + kDdBlockH - 1) / kDdBlockH);
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    escape_extend_dd_kernel<<<dim3((uint32_t)tiles), dim3(64 * kDdWaves), 0, stream>>>(p, z, iters, from_iterations, pos_lo_re,
-                                                                                     pos_lo_im);
+    dim3 grid, block;
+    const hipError_t e = fr_deep_grid(p, grid, block);
+    if (e != hipSuccess) return e;
+    escape_extend_dd_kernel<<<grid, block, 0, stream>>>(p, z, iters, from_iterations, pos_lo_re, pos_lo_im);
     return hipGetLastError();
 }
 
@@ -278,9 +273,9 @@ hipError_t fr_launch_escape_dd(const fr_kparams &p, double pos_lo_re, double pos
                                bool with_lo, hipStream_t stream, const char **kernel_name) {
     if (kernel_name) *kernel_name = "escape_dd_kernel";
     if (p.ncols == 0 || p.nrows == 0) return hipSuccess;
-    const uint64_t tiles = (((uint64_t)p.ncols + kDdBlockW - 1) / kDdBlockW) * (((uint64_t)p.nrows + kDdBlockH - 1) / kDdBlockH);
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const dim3 grid((uint32_t)tiles), block(64 * kDdWaves);
+    dim3 grid, block;
+    const hipError_t e = fr_deep_grid(p, grid, block);
+    if (e != hipSuccess) return e;
     const uint32_t wl = with_lo ? 1u : 0u;
     if (mode == FR_OUT_RGB)
         escape_dd_kernel<FR_OUT_RGB><<<grid, block, 0, stream>>>(p, out, pos_lo_re, pos_lo_im, wl);

@@ -129,6 +129,13 @@ enum fr_out_mode {
 /* MODE COUNT accumulates into this many uint64 partial sums (fr_kout::count points at them) */
 constexpr uint32_t FR_COUNT_SLOTS = 512;
 
+/* The workgroup of every deep kernel (fr_dd.hip, fr_pt.hip, fr_bla.hip, fr_scaled.hip): 4 waves, each one 8 x 8 tile, 2 x 2 of
+ * them, one workgroup per 16 x 16 pixels of the launch's local grid. */
+constexpr int kDeepWaves = 4;                 /* 256-thread workgroups */
+constexpr int kDeepTileW = 8, kDeepTileH = 8; /* one wave = 8 x 8 pixels */
+constexpr int kDeepWavesX = 2, kDeepWavesY = 2;
+constexpr int kDeepBlockW = kDeepTileW * kDeepWavesX, kDeepBlockH = kDeepTileH * kDeepWavesY; /* 16 x 16 pixels per workgroup */
+
 struct fr_kout {
     uint8_t *rgb;
     double *z;
@@ -139,6 +146,15 @@ struct fr_kout {
      * phase (open | refill << 32, loop | retire << 32, finish), 7 unused */
     unsigned long long *trace;
 };
+
+/* the launch geometry of a deep kernel over p's local grid; refuses a grid whose workgroup index would not fit the kernels' */
+inline hipError_t fr_deep_grid(const fr_kparams &p, dim3 &grid, dim3 &block) {
+    const uint64_t tiles = (((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW) * (((uint64_t)p.nrows + kDeepBlockH - 1) / kDeepBlockH);
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    grid = dim3((uint32_t)tiles);
+    block = dim3(64 * kDeepWaves);
+    return hipSuccess;
+}
 
 /* tile = kernel-variant selector (see fr_set_tile in include/fractal_hip.h); 0 = default.
  * *kernel_name (may be NULL) receives a static string naming the kernel that was launched. */

@@ -30,6 +30,9 @@
  *
  * The entry points that only PT has live here beside their launches, at the end of the file: the state render and its
  * extension, and every fr_*_pt_wide call (WIDE PT: the same launches with a Centre that holds a wide centre; fr_ctx.h).
+ * Each builds its Centre and checks PT's domain; the state calls then hand pt_state_rows, their launch, to the state road
+ * of fr_ctx.h (state_device, state_host), the others go to the row calls' bodies in fr_api.hip.  The workgroup's geometry and
+ * the launches' grid are the deep kernels' (fr_kernels.h: kDeep*, fr_deep_grid).
  */
 #include <cmath>
 #include <cstring>
@@ -43,11 +46,6 @@
 namespace {
 
 #include "fr_colour.h"
-
-constexpr int kPtWaves = 4;               /* 256-thread workgroups */
-constexpr int kPtTileW = 8, kPtTileH = 8; /* one wave = 8 x 8 pixels */
-constexpr int kPtWavesX = 2, kPtWavesY = 2;
-constexpr int kPtBlockW = kPtTileW * kPtWavesX, kPtBlockH = kPtTileH * kPtWavesY; /* 16 x 16 pixels per workgroup */
 
 /* ---- device: the pixel loop (include/fractal_hip.h, fr_precision: PT), operation for operation ------------------- */
 
@@ -99,40 +97,40 @@ __device__ __forceinline__ uint32_t orbit_pt(uint32_t iterations, double off_re,
 }
 
 template <int MODE, bool JULIA>
-__global__ __launch_bounds__(64 * kPtWaves) void escape_pt_kernel(const fr_kparams p, const fr_kout out,
-                                                                 const double2 *__restrict__ x_orbit,
-                                                                 const double2 *__restrict__ k_orbit, const uint32_t x_last,
-                                                                 const uint32_t k_last) {
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_pt_kernel(const fr_kparams p, const fr_kout out,
+                                                                    const double2 *__restrict__ x_orbit,
+                                                                    const double2 *__restrict__ k_orbit, const uint32_t x_last,
+                                                                    const uint32_t k_last) {
     __shared__ double s_tab[FR_LOG2_N * 3];
-    __shared__ double s_re[kPtBlockW];
-    __shared__ double s_im[kPtBlockH];
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
 
     const uint32_t tid = threadIdx.x;
-    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kPtBlockW - 1) / kPtBlockW);
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
     const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
-    const uint32_t col0 = bx * kPtBlockW, row0 = by * kPtBlockH;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
 
     if (MODE == FR_OUT_RGB) {
         const double *gt = &g_log2_tab[0][0];
-        for (uint32_t k = tid; k < FR_LOG2_N * 3; k += 64 * kPtWaves) s_tab[k] = gt[k];
+        for (uint32_t k = tid; k < FR_LOG2_N * 3; k += 64 * kDeepWaves) s_tab[k] = gt[k];
     }
-    if (tid < kPtBlockW + kPtBlockH) {
+    if (tid < kDeepBlockW + kDeepBlockH) {
         /* off: coord_to_space (calc/src/lib.rs:181-197) without the final `+ pos`, DD's off */
         const double width = (double)p.width, height = (double)p.height;
-        if (tid < kPtBlockW) {
+        if (tid < kDeepBlockW) {
             const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
             s_re[tid] = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
         } else {
-            const uint32_t r = row0 + (tid - kPtBlockW);
+            const uint32_t r = row0 + (tid - kDeepBlockW);
             const uint64_t y = (uint64_t)p.y_first + (uint64_t)(r / p.block_rows) * p.y_stride + r % p.block_rows;
-            s_im[tid - kPtBlockW] = (((double)y / height) - 0.5) / p.scale_im;
+            s_im[tid - kDeepBlockW] = (((double)y / height) - 0.5) / p.scale_im;
         }
     }
     __syncthreads();
 
     const uint32_t wave = tid >> 6, lane = tid & 63;
-    const uint32_t lx = (wave % kPtWavesX) * kPtTileW + lane % kPtTileW;
-    const uint32_t ly = (wave / kPtWavesX) * kPtTileH + lane / kPtTileW;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
     const uint32_t cx = col0 + lx, r = row0 + ly;
     const bool valid = cx < p.ncols && r < p.nrows;
     const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0; /* the host picks JULIA from the algorithm */
@@ -185,9 +183,9 @@ __global__ __launch_bounds__(64 * kPtWaves) void escape_pt_kernel(const fr_kpara
 template <bool JULIA>
 hipError_t launch(const fr_kparams &p, int mode, const fr_kout &out, const double2 *x_orbit, const double2 *k_orbit,
                   uint32_t x_last, uint32_t k_last, hipStream_t stream) {
-    const uint64_t tiles = (((uint64_t)p.ncols + kPtBlockW - 1) / kPtBlockW) * (((uint64_t)p.nrows + kPtBlockH - 1) / kPtBlockH);
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const dim3 grid((uint32_t)tiles), block(64 * kPtWaves);
+    dim3 grid, block;
+    const hipError_t e = fr_deep_grid(p, grid, block);
+    if (e != hipSuccess) return e;
     if (mode == FR_OUT_RGB)
         escape_pt_kernel<FR_OUT_RGB, JULIA><<<grid, block, 0, stream>>>(p, out, x_orbit, k_orbit, x_last, k_last);
     else if (mode == FR_OUT_ESCAPE)
@@ -267,15 +265,15 @@ constexpr uint32_t kPtOnK = 0x80000000u; /* bit 31 of the stored m: the pixel fo
 /* 16 column and 16 row offsets of the workgroup's pixels into LDS (escape_pt_kernel's staging); the caller synchronises */
 __device__ __forceinline__ void stage_offsets(const fr_kparams &p, uint32_t tid, uint32_t col0, uint32_t row0, double *s_re,
                                               double *s_im) {
-    if (tid < kPtBlockW + kPtBlockH) {
+    if (tid < kDeepBlockW + kDeepBlockH) {
         const double width = (double)p.width, height = (double)p.height;
-        if (tid < kPtBlockW) {
+        if (tid < kDeepBlockW) {
             const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
             s_re[tid] = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
         } else {
-            const uint32_t r = row0 + (tid - kPtBlockW);
+            const uint32_t r = row0 + (tid - kDeepBlockW);
             const uint64_t y = (uint64_t)p.y_first + (uint64_t)(r / p.block_rows) * p.y_stride + r % p.block_rows;
-            s_im[tid - kPtBlockW] = (((double)y / height) - 0.5) / p.scale_im;
+            s_im[tid - kDeepBlockW] = (((double)y / height) - 0.5) / p.scale_im;
         }
     }
 }
@@ -283,25 +281,25 @@ __device__ __forceinline__ void stage_offsets(const fr_kparams &p, uint32_t tid,
 /* escape_pt_kernel<FR_OUT_ESCAPE>'s shape with the state rule, storing the whole state: z and dz as re, im per pixel, iters,
  * m (bit 31: on K).  `ended`: bit 0 = X, bit 1 = K is ended by escape.  An algorithm without orbits writes zeros. */
 template <bool JULIA>
-__global__ __launch_bounds__(64 * kPtWaves) void escape_pt_state_kernel(const fr_kparams p, double *__restrict__ z,
-                                                                       uint32_t *__restrict__ iters, double *__restrict__ dz,
-                                                                       uint32_t *__restrict__ mm,
-                                                                       const double2 *__restrict__ x_orbit,
-                                                                       const double2 *__restrict__ k_orbit, const uint32_t x_last,
-                                                                       const uint32_t k_last, const uint32_t ended) {
-    __shared__ double s_re[kPtBlockW];
-    __shared__ double s_im[kPtBlockH];
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_pt_state_kernel(const fr_kparams p, double *__restrict__ z,
+                                                                          uint32_t *__restrict__ iters, double *__restrict__ dz,
+                                                                          uint32_t *__restrict__ mm,
+                                                                          const double2 *__restrict__ x_orbit,
+                                                                          const double2 *__restrict__ k_orbit, const uint32_t x_last,
+                                                                          const uint32_t k_last, const uint32_t ended) {
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
 
     const uint32_t tid = threadIdx.x;
-    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kPtBlockW - 1) / kPtBlockW);
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
     const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
-    const uint32_t col0 = bx * kPtBlockW, row0 = by * kPtBlockH;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
     stage_offsets(p, tid, col0, row0, s_re, s_im);
     __syncthreads();
 
     const uint32_t wave = tid >> 6, lane = tid & 63;
-    const uint32_t lx = (wave % kPtWavesX) * kPtTileW + lane % kPtTileW;
-    const uint32_t ly = (wave / kPtWavesX) * kPtTileH + lane / kPtTileW;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
     const uint32_t cx = col0 + lx, r = row0 + ly;
     if (cx >= p.ncols || r >= p.nrows) return;
     const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0; /* the host picks JULIA from the algorithm */
@@ -332,21 +330,21 @@ __global__ __launch_bounds__(64 * kPtWaves) void escape_pt_state_kernel(const fr
  * first and a workgroup with no pixel at `from` ends there, having written nothing; a finished pixel's z, dz and m are
  * neither loaded nor stored.  The orbits are those of the new cap. */
 template <bool JULIA>
-__global__ __launch_bounds__(64 * kPtWaves) void escape_extend_pt_kernel(const fr_kparams p, double *z, uint32_t *iters, double *dz,
-                                                                        uint32_t *mm, const uint32_t from,
-                                                                        const double2 *__restrict__ x_orbit,
-                                                                        const double2 *__restrict__ k_orbit, const uint32_t x_last,
-                                                                        const uint32_t k_last, const uint32_t ended) {
-    __shared__ double s_re[kPtBlockW];
-    __shared__ double s_im[kPtBlockH];
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_extend_pt_kernel(const fr_kparams p, double *z, uint32_t *iters, double *dz,
+                                                                           uint32_t *mm, const uint32_t from,
+                                                                           const double2 *__restrict__ x_orbit,
+                                                                           const double2 *__restrict__ k_orbit, const uint32_t x_last,
+                                                                           const uint32_t k_last, const uint32_t ended) {
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
 
     const uint32_t tid = threadIdx.x;
-    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kPtBlockW - 1) / kPtBlockW);
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
     const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
-    const uint32_t col0 = bx * kPtBlockW, row0 = by * kPtBlockH;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
     const uint32_t wave = tid >> 6, lane = tid & 63;
-    const uint32_t lx = (wave % kPtWavesX) * kPtTileW + lane % kPtTileW;
-    const uint32_t ly = (wave / kPtWavesX) * kPtTileH + lane / kPtTileW;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
     const uint32_t cx = col0 + lx, r = row0 + ly;
     const bool valid = cx < p.ncols && r < p.nrows;
     const uint64_t k = (uint64_t)r * p.ncols + cx;
@@ -588,9 +586,9 @@ int orbit_for(Ctx &ctx, const fr_config *cfg, const Centre &centre, std::shared_
 template <bool JULIA>
 hipError_t launch_state(const fr_kparams &p, uint32_t from, bool extend, double *z, uint32_t *iters, double *dz, uint32_t *m,
                         const PtOrbit *o, hipStream_t stream) {
-    const uint64_t tiles = (((uint64_t)p.ncols + kPtBlockW - 1) / kPtBlockW) * (((uint64_t)p.nrows + kPtBlockH - 1) / kPtBlockH);
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const dim3 grid((uint32_t)tiles), block(64 * kPtWaves);
+    dim3 grid, block;
+    const hipError_t e = fr_deep_grid(p, grid, block);
+    if (e != hipSuccess) return e;
     const double2 *x = o ? o->dev : nullptr, *k = o ? (JULIA ? o->dev + o->k_offset : o->dev) : nullptr;
     const uint32_t x_last = o ? o->x_last : 0u, k_last = o ? o->k_last : 0u, ended = o ? o->ended() : 0u;
     if (extend)
@@ -679,63 +677,34 @@ static int launch_pt_extend(Ctx &ctx, const fr_config *cfg, const Centre &c, con
 
 /* ---- resumable perturbation: FR_PRECISION_PT rows with their state, and that state continued to a higher cap ------- */
 
-/* The domain of the calls (include/fractal_hip.h), checked before any device work: `from` = nullptr for the state render.
- * *work = false: a legal call with nothing to do (no rows; for the extension also M == N or an algorithm without orbits). */
-static int check_pt_state(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, const void *z,
-                          const void *iters, const void *dz, const void *m, bool *work) {
-    *work = false;
-    int rc = check_rows(cfg, y0, y1);
-    if (rc == FR_OK) rc = c.check(cfg, FR_PRECISION_PT);
-    if (rc != FR_OK) return rc;
-    if (from && cfg->iterations < *from)
-        return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from a stored state");
-    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
-    if (!z || !iters || !dz || !m) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the PT state is z, iters, dz and m, all four");
-    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(dz) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u) ||
-        (reinterpret_cast<uintptr_t>(m) & 3u))
-        return fail(FR_ERR_INVALID_ARGUMENT, "z and dz must be 8-byte aligned, iters and m 4-byte aligned");
-    *work = !from || (cfg->iterations != *from && (cfg->algo == FR_ALGO_MANDELBROT || cfg->algo == FR_ALGO_JULIA));
-    return FR_OK;
+/* The launch of the state road (fr_ctx.h: state_device, state_host).  from == nullptr: the state render; else the extension
+ * from *from.  Into the arrays it is given, between the profiling events. */
+static auto pt_state_rows(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from) {
+    return [=](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_dz, uint32_t *d_m, hipStream_t stream) {
+        return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) {
+            return from ? launch_pt_extend(ctx, cfg, c, p, *from, d_z, d_iters, d_dz, d_m, stream, &kname)
+                        : launch_pt_state(ctx, cfg, c, p, d_z, d_iters, d_dz, d_m, stream, &kname);
+        });
+    };
 }
 
-/* from == nullptr: the state render; else the extension from *from.  On the caller's stream, into the caller's arrays. */
-static int pt_state_launch(Ctx &ctx, const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, double *d_z,
-                           uint32_t *d_iters, double *d_dz, uint32_t *d_m, hipStream_t stream) {
-    fr_kparams p;
-    rows_params(cfg, default_opts(), y0, y1, 0, p);
-    int rc = prof_begin(stream);
-    if (rc != FR_OK) return rc;
-    const char *kname = "";
-    rc = from ? launch_pt_extend(ctx, cfg, c, p, *from, d_z, d_iters, d_dz, d_m, stream, &kname)
-              : launch_pt_state(ctx, cfg, c, p, d_z, d_iters, d_dz, d_m, stream, &kname);
-    if (rc != FR_OK) return rc;
-    return prof_end(stream, kname);
+static int check_pt_rows(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1) {
+    const int rc = check_rows(cfg, y0, y1);
+    return rc == FR_OK ? c.check(cfg, FR_PRECISION_PT) : rc;
 }
 
 static int pt_state_device(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z, void *d_iters,
                            void *d_dz, void *d_m, void *hip_stream) {
-    bool work;
-    int rc = check_pt_state(cfg, c, y0, y1, from, d_z, d_iters, d_dz, d_m, &work);
-    if (rc != FR_OK || !work) return rc;
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
+    const int rc = check_pt_rows(cfg, c, y0, y1);
     if (rc != FR_OK) return rc;
-    return pt_state_launch(*ctx, cfg, c, y0, y1, from, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
-                           static_cast<double *>(d_dz), static_cast<uint32_t *>(d_m), static_cast<hipStream_t>(hip_stream));
+    return state_device(cfg, y0, y1, from, d_z, d_iters, d_dz, d_m, hip_stream, "PT", "dz", pt_state_rows(cfg, c, y0, y1, from));
 }
 
-/* the host forms: z and dz share the context's z scratch, iters and m its iters scratch */
 static int pt_state_host(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, double *z,
                          uint32_t *iters, double *dz, uint32_t *m) {
-    bool work;
-    const int rc = check_pt_state(cfg, c, y0, y1, from, z, iters, dz, m, &work);
-    if (rc != FR_OK || !work) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), dz, m, from != nullptr,
-                    [&](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_dz, uint32_t *d_m, hipStream_t stream) {
-                        return pt_state_launch(ctx, cfg, c, y0, y1, from, d_z, d_iters, d_dz, d_m, stream);
-                    });
+    const int rc = check_pt_rows(cfg, c, y0, y1);
+    if (rc != FR_OK) return rc;
+    return state_host(cfg, y0, y1, from, z, iters, dz, m, "PT", "dz", pt_state_rows(cfg, c, y0, y1, from));
 }
 
 /* WIDE PT: a NULL centre must not fall through to the dd road */

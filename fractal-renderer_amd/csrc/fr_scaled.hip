@@ -26,6 +26,11 @@
  * fr_pt.hip's cache continued from their integer tails.  They are to orbit_pt_scaled what fr_pt.hip's escape_pt_state_kernel
  * and escape_extend_pt_kernel are to orbit_pt, in their shape; escape_pt_scaled_kernel and orbit_pt_scaled are SCALED PT's and
  * stay as they are.  The table form has no state (BLA-PT's reason: i + 2^k <= iterations).
+ *
+ * The calls, at the end of the file: each builds its Centre (scaled: the wide centre is required), runs check_scaled and hands
+ * scaled_rows — the profiled launch of its rows — to the row-call body of its form in fr_ctx.h, as fr_bla.hip's do; the state
+ * calls hand scaled_state_rows to fr_ctx.h's state road (state_device, state_host), as fr_pt.hip's do.  The workgroup's
+ * geometry and the launches' grid are the deep kernels' (fr_kernels.h: kDeep*, fr_deep_grid).
  */
 #include <cmath>
 #include <cstring>
@@ -40,11 +45,6 @@
 namespace {
 
 #include "fr_colour.h"
-
-constexpr int kWaves = 4;               /* 256-thread workgroups */
-constexpr int kTileW = 8, kTileH = 8;   /* one wave = 8 x 8 pixels */
-constexpr int kWavesX = 2, kWavesY = 2;
-constexpr int kBlockW = kTileW * kWavesX, kBlockH = kTileH * kWavesY; /* 16 x 16 pixels per workgroup */
 
 constexpr double kBig = 0x1p500; /* max(|w.re|, |w.im|) >= kBig: w is "big" and the comparisons scale w down, not z up */
 
@@ -192,15 +192,15 @@ constexpr uint32_t kOnK = 0x80000000u; /* bit 31 of the stored m: the pixel foll
 /* 16 column and 16 row values of woff for the workgroup's pixels into LDS (scaled_body's staging: p.scale_re and p.scale_im
  * hold sre and sim); the caller synchronises */
 __device__ __forceinline__ void stage_woff(const fr_kparams &p, uint32_t tid, uint32_t col0, uint32_t row0, double *s_re, double *s_im) {
-    if (tid < kBlockW + kBlockH) {
+    if (tid < kDeepBlockW + kDeepBlockH) {
         const double width = (double)p.width, height = (double)p.height;
-        if (tid < kBlockW) {
+        if (tid < kDeepBlockW) {
             const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
             s_re[tid] = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
         } else {
-            const uint32_t r = row0 + (tid - kBlockW);
+            const uint32_t r = row0 + (tid - kDeepBlockW);
             const uint64_t y = (uint64_t)p.y_first + (uint64_t)(r / p.block_rows) * p.y_stride + r % p.block_rows;
-            s_im[tid - kBlockW] = (((double)y / height) - 0.5) / p.scale_im;
+            s_im[tid - kDeepBlockW] = (((double)y / height) - 0.5) / p.scale_im;
         }
     }
 }
@@ -208,23 +208,23 @@ __device__ __forceinline__ void stage_woff(const fr_kparams &p, uint32_t tid, ui
 /* escape_pt_scaled_kernel<FR_OUT_ESCAPE>'s shape with the state rule, storing the whole state: z and w as re, im per pixel,
  * iters, m (bit 31: on K).  `ended`: bit 0 = X, bit 1 = K is ended by escape.  An algorithm without orbits writes zeros. */
 template <bool JULIA>
-__global__ __launch_bounds__(64 * kWaves) void escape_pt_scaled_state_kernel(const fr_kparams p, double *__restrict__ z,
-                                                                            uint32_t *__restrict__ iters, double *__restrict__ w,
-                                                                            uint32_t *__restrict__ mm, const ScaledDev t,
-                                                                            const uint32_t ended) {
-    __shared__ double s_re[kBlockW];
-    __shared__ double s_im[kBlockH];
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_pt_scaled_state_kernel(const fr_kparams p, double *__restrict__ z,
+                                                                                 uint32_t *__restrict__ iters, double *__restrict__ w,
+                                                                                 uint32_t *__restrict__ mm, const ScaledDev t,
+                                                                                 const uint32_t ended) {
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
 
     const uint32_t tid = threadIdx.x;
-    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kBlockW - 1) / kBlockW);
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
     const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
-    const uint32_t col0 = bx * kBlockW, row0 = by * kBlockH;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
     stage_woff(p, tid, col0, row0, s_re, s_im);
     __syncthreads();
 
     const uint32_t wave = tid >> 6, lane = tid & 63;
-    const uint32_t lx = (wave % kWavesX) * kTileW + lane % kTileW;
-    const uint32_t ly = (wave / kWavesX) * kTileH + lane / kTileW;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
     const uint32_t cx = col0 + lx, r = row0 + ly;
     if (cx >= p.ncols || r >= p.nrows) return;
     const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0; /* the host picks JULIA from the algorithm */
@@ -255,19 +255,19 @@ __global__ __launch_bounds__(64 * kWaves) void escape_pt_scaled_state_kernel(con
  * first and a workgroup with no pixel at `from` ends there, having written nothing; a finished pixel's z, w and m are
  * neither loaded nor stored.  The orbits are those of the new cap. */
 template <bool JULIA>
-__global__ __launch_bounds__(64 * kWaves) void escape_extend_pt_scaled_kernel(const fr_kparams p, double *z, uint32_t *iters, double *w,
-                                                                             uint32_t *mm, const uint32_t from, const ScaledDev t,
-                                                                             const uint32_t ended) {
-    __shared__ double s_re[kBlockW];
-    __shared__ double s_im[kBlockH];
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_extend_pt_scaled_kernel(const fr_kparams p, double *z, uint32_t *iters, double *w,
+                                                                                  uint32_t *mm, const uint32_t from, const ScaledDev t,
+                                                                                  const uint32_t ended) {
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
 
     const uint32_t tid = threadIdx.x;
-    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kBlockW - 1) / kBlockW);
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
     const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
-    const uint32_t col0 = bx * kBlockW, row0 = by * kBlockH;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
     const uint32_t wave = tid >> 6, lane = tid & 63;
-    const uint32_t lx = (wave % kWavesX) * kTileW + lane % kTileW;
-    const uint32_t ly = (wave / kWavesX) * kTileH + lane / kTileW;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
     const uint32_t cx = col0 + lx, r = row0 + ly;
     const bool valid = cx < p.ncols && r < p.nrows;
     const uint64_t k = (uint64_t)r * p.ncols + cx;
@@ -402,35 +402,35 @@ __device__ __forceinline__ uint32_t orbit_bla_scaled(uint32_t iterations, double
 template <int MODE, bool JULIA, bool BLA>
 __device__ __forceinline__ void scaled_body(const fr_kparams &p, const fr_kout &out, const ScaledDev &t) {
     __shared__ double s_tab[FR_LOG2_N * 3];
-    __shared__ double s_re[kBlockW];
-    __shared__ double s_im[kBlockH];
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
 
     const uint32_t tid = threadIdx.x;
-    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kBlockW - 1) / kBlockW);
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
     const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
-    const uint32_t col0 = bx * kBlockW, row0 = by * kBlockH;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
 
     if (MODE == FR_OUT_RGB) {
         const double *gt = &g_log2_tab[0][0];
-        for (uint32_t k = tid; k < FR_LOG2_N * 3; k += 64 * kWaves) s_tab[k] = gt[k];
+        for (uint32_t k = tid; k < FR_LOG2_N * 3; k += 64 * kDeepWaves) s_tab[k] = gt[k];
     }
-    if (tid < kBlockW + kBlockH) {
+    if (tid < kDeepBlockW + kDeepBlockH) {
         /* woff: PT's off with the scaled divisors — p.scale_re and p.scale_im hold sre and sim */
         const double width = (double)p.width, height = (double)p.height;
-        if (tid < kBlockW) {
+        if (tid < kDeepBlockW) {
             const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
             s_re[tid] = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
         } else {
-            const uint32_t r = row0 + (tid - kBlockW);
+            const uint32_t r = row0 + (tid - kDeepBlockW);
             const uint64_t y = (uint64_t)p.y_first + (uint64_t)(r / p.block_rows) * p.y_stride + r % p.block_rows;
-            s_im[tid - kBlockW] = (((double)y / height) - 0.5) / p.scale_im;
+            s_im[tid - kDeepBlockW] = (((double)y / height) - 0.5) / p.scale_im;
         }
     }
     __syncthreads();
 
     const uint32_t wave = tid >> 6, lane = tid & 63;
-    const uint32_t lx = (wave % kWavesX) * kTileW + lane % kTileW;
-    const uint32_t ly = (wave / kWavesX) * kTileH + lane / kTileW;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
     const uint32_t cx = col0 + lx, r = row0 + ly;
     const bool valid = cx < p.ncols && r < p.nrows;
     const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0; /* the host picks JULIA from the algorithm */
@@ -494,20 +494,20 @@ __device__ __forceinline__ void scaled_body(const fr_kparams &p, const fr_kout &
 }
 
 template <int MODE, bool JULIA>
-__global__ __launch_bounds__(64 * kWaves) void escape_pt_scaled_kernel(const fr_kparams p, const fr_kout out, const ScaledDev t) {
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_pt_scaled_kernel(const fr_kparams p, const fr_kout out, const ScaledDev t) {
     scaled_body<MODE, JULIA, false>(p, out, t);
 }
 
 template <int MODE, bool JULIA>
-__global__ __launch_bounds__(64 * kWaves) void escape_bla_scaled_kernel(const fr_kparams p, const fr_kout out, const ScaledDev t) {
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_bla_scaled_kernel(const fr_kparams p, const fr_kout out, const ScaledDev t) {
     scaled_body<MODE, JULIA, true>(p, out, t);
 }
 
 template <bool JULIA, bool BLA>
 hipError_t launch(const fr_kparams &p, int mode, const fr_kout &out, const ScaledDev &t, hipStream_t stream) {
-    const uint64_t tiles = (((uint64_t)p.ncols + kBlockW - 1) / kBlockW) * (((uint64_t)p.nrows + kBlockH - 1) / kBlockH);
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const dim3 grid((uint32_t)tiles), block(64 * kWaves);
+    dim3 grid, block;
+    const hipError_t e = fr_deep_grid(p, grid, block);
+    if (e != hipSuccess) return e;
     if constexpr (BLA) {
         if (mode == FR_OUT_RGB)
             escape_bla_scaled_kernel<FR_OUT_RGB, JULIA><<<grid, block, 0, stream>>>(p, out, t);
@@ -535,9 +535,9 @@ hipError_t launch(bool julia, bool bla, const fr_kparams &p, int mode, const fr_
 template <bool JULIA>
 hipError_t launch_state(const fr_kparams &p, uint32_t from, bool extend, double *z, uint32_t *iters, double *w, uint32_t *m,
                         const ScaledDev &t, uint32_t ended, hipStream_t stream) {
-    const uint64_t tiles = (((uint64_t)p.ncols + kBlockW - 1) / kBlockW) * (((uint64_t)p.nrows + kBlockH - 1) / kBlockH);
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const dim3 grid((uint32_t)tiles), block(64 * kWaves);
+    dim3 grid, block;
+    const hipError_t e = fr_deep_grid(p, grid, block);
+    if (e != hipSuccess) return e;
     if (extend)
         escape_extend_pt_scaled_kernel<JULIA><<<grid, block, 0, stream>>>(p, z, iters, w, m, from, t, ended);
     else
@@ -549,8 +549,6 @@ hipError_t launch_state(const fr_kparams &p, uint32_t from, bool extend, double 
 
 namespace fr {
 namespace {
-
-const char *kernel_name(int bits) { return bits < 0 ? "escape_pt_scaled_kernel" : "escape_bla_scaled_kernel"; }
 
 /* `p` holds the view's scale; the kernels get a copy with the scaled divisors.  bits < 0: no table. */
 int launch_scaled(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_kparams &p, int mode, const fr_kout &out,
@@ -605,100 +603,73 @@ int check_scaled(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, 
     return FR_OK;
 }
 
-/* rows [y0, y1) on `stream` between the profiling events (fr_set_profiling), named for fr_last_kernel_name; the colour
- * constants alone: no loop plan, no kernel choice, no view sample */
-int profiled_launch(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, unsigned channels, int mode,
-                    const fr_kout &out, hipStream_t stream) {
-    fr_kparams p;
-    rows_params(cfg, default_opts(), y0, y1, channels, p);
-    int rc = prof_begin(stream);
-    if (rc == FR_OK) rc = launch_scaled(ctx, cfg, c, bits, p, mode, out, stream);
-    if (rc != FR_OK) return rc;
-    return prof_end(stream, kernel_name(bits));
+/* The launch every row call below hands to its helper (fr_ctx.h): rows [y0, y1) in `mode` on `stream` between the profiling
+ * events; the colour constants alone: no loop plan, no kernel choice, no view sample */
+auto scaled_rows(const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, unsigned channels, int mode) {
+    return [=](Ctx &ctx, const fr_kout &out, hipStream_t stream) {
+        return profiled_rows(cfg, default_opts(), y0, y1, channels, stream, [&](fr_kparams &p, const char *&kname) {
+            kname = bits < 0 ? "escape_pt_scaled_kernel" : "escape_bla_scaled_kernel";
+            return launch_scaled(ctx, cfg, c, bits, p, mode, out, stream);
+        });
+    };
 }
 
 /* ---- RESUMABLE SCALED PT: the plain loop's rows with their state, and that state continued to a higher cap -------------- */
 
-/* The domain of the four calls (include/fractal_hip.h), checked before any device work: `from` = nullptr for the state
- * render.  *work = false: a legal call with nothing to do (no rows; for the extension also M == N or an algorithm without
- * orbits). */
-int check_scaled_state(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, const void *z,
-                       const void *iters, const void *w, const void *m, bool *work) {
-    *work = false;
-    int bits = -1; /* the calls are the plain loop's */
-    const int rc = check_scaled(cfg, c, bits, y0, y1);
-    if (rc != FR_OK) return rc;
-    if (from && cfg->iterations < *from)
-        return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from a stored state");
-    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
-    if (!z || !iters || !w || !m) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the SCALED PT state is z, iters, w and m, all four");
-    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(w) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u) ||
-        (reinterpret_cast<uintptr_t>(m) & 3u))
-        return fail(FR_ERR_INVALID_ARGUMENT, "z and w must be 8-byte aligned, iters and m 4-byte aligned");
-    *work = !from || (cfg->iterations != *from && (cfg->algo == FR_ALGO_MANDELBROT || cfg->algo == FR_ALGO_JULIA));
-    return FR_OK;
+/* The launch of the state road (fr_ctx.h: state_device, state_host).  from == nullptr: the state render; else the extension
+ * from *from, on the orbits of cfg's cap, which pt_orbit_view's cache continues from those of the old one.  Into the arrays it
+ * is given, between the profiling events. */
+auto scaled_state_rows(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from) {
+    return [=](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_w, uint32_t *d_m, hipStream_t stream) {
+        return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) -> int {
+            kname = from ? "escape_extend_pt_scaled_kernel" : "escape_pt_scaled_state_kernel";
+            const bool julia = cfg->algo == 2, extend = from != nullptr;
+            if (cfg->algo != 0 && !julia) { /* no escape-time algorithm: zeros in all four arrays (the extension never gets here) */
+                HIP_TRY(launch_state<false>(p, 0, false, d_z, d_iters, d_w, d_m, ScaledDev{}, 0, stream));
+                return FR_OK;
+            }
+            const ScaledConsts k = scaled_consts(cfg);
+            p.scale_re = k.sre;
+            p.scale_im = k.sim;
+            std::shared_ptr<PtOrbit> orbit;
+            PtOrbitView v;
+            const int rc = pt_orbit_view(ctx, cfg, c, orbit, v);
+            if (rc != FR_OK) return rc;
+            ScaledDev t{};
+            t.x_orbit = v.x;
+            t.k_orbit = v.k;
+            t.x_last = v.x_last;
+            t.k_last = v.k_last;
+            t.S = k.S;
+            t.Sinv = k.Sinv;
+            const uint32_t n = extend ? *from : 0u;
+            HIP_TRY(julia ? launch_state<true>(p, n, extend, d_z, d_iters, d_w, d_m, t, v.ended, stream)
+                          : launch_state<false>(p, n, extend, d_z, d_iters, d_w, d_m, t, v.ended, stream));
+            return FR_OK;
+        });
+    };
 }
 
-/* from == nullptr: the state render; else the extension from *from, on the orbits of cfg's cap, which pt_orbit_view's cache
- * continues from those of the old one.  On the caller's stream, into the caller's arrays, between the profiling events. */
-int scaled_state_launch(Ctx &ctx, const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, double *d_z,
-                        uint32_t *d_iters, double *d_w, uint32_t *d_m, hipStream_t stream) {
-    fr_kparams p;
-    rows_params(cfg, default_opts(), y0, y1, 0, p);
-    int rc = prof_begin(stream);
-    if (rc != FR_OK) return rc;
-    const char *kname = from ? "escape_extend_pt_scaled_kernel" : "escape_pt_scaled_state_kernel";
-    const bool julia = cfg->algo == 2, extend = from != nullptr;
-    if (cfg->algo != 0 && !julia) { /* no escape-time algorithm: zeros in all four arrays (the extension never gets here) */
-        HIP_TRY(launch_state<false>(p, 0, false, d_z, d_iters, d_w, d_m, ScaledDev{}, 0, stream));
-        return prof_end(stream, kname);
-    }
-    const ScaledConsts k = scaled_consts(cfg);
-    p.scale_re = k.sre;
-    p.scale_im = k.sim;
-    std::shared_ptr<PtOrbit> orbit;
-    PtOrbitView v;
-    rc = pt_orbit_view(ctx, cfg, c, orbit, v);
-    if (rc != FR_OK) return rc;
-    ScaledDev t{};
-    t.x_orbit = v.x;
-    t.k_orbit = v.k;
-    t.x_last = v.x_last;
-    t.k_last = v.k_last;
-    t.S = k.S;
-    t.Sinv = k.Sinv;
-    const uint32_t n = extend ? *from : 0u;
-    HIP_TRY(julia ? launch_state<true>(p, n, extend, d_z, d_iters, d_w, d_m, t, v.ended, stream)
-                  : launch_state<false>(p, n, extend, d_z, d_iters, d_w, d_m, t, v.ended, stream));
-    return prof_end(stream, kname);
+/* the state calls are the plain loop's: SCALED PT's domain with bits = -1 */
+int check_scaled_plain(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1) {
+    int bits = -1;
+    return check_scaled(cfg, c, bits, y0, y1);
 }
 
 int scaled_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z,
                         void *d_iters, void *d_w, void *d_m, void *hip_stream) {
     const Centre c{nullptr, centre, true};
-    bool work;
-    int rc = check_scaled_state(cfg, c, y0, y1, from, d_z, d_iters, d_w, d_m, &work);
-    if (rc != FR_OK || !work) return rc;
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
+    const int rc = check_scaled_plain(cfg, c, y0, y1);
     if (rc != FR_OK) return rc;
-    return scaled_state_launch(*ctx, cfg, c, y0, y1, from, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
-                               static_cast<double *>(d_w), static_cast<uint32_t *>(d_m), static_cast<hipStream_t>(hip_stream));
+    return state_device(cfg, y0, y1, from, d_z, d_iters, d_w, d_m, hip_stream, "SCALED PT", "w", scaled_state_rows(cfg, c, y0, y1, from));
 }
 
-/* the host forms: z and w share the context's z scratch, iters and m its iters scratch (pt_state_host's road) */
 int scaled_state_host(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, const uint32_t *from, double *z,
                       uint32_t *iters, double *w, uint32_t *m) {
     const Centre c{nullptr, centre, true};
-    bool work;
-    const int rc = check_scaled_state(cfg, c, y0, y1, from, z, iters, w, m, &work);
-    if (rc != FR_OK || !work) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), w, m, from != nullptr,
-                    [&](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_w, uint32_t *d_m, hipStream_t stream) {
-                        return scaled_state_launch(ctx, cfg, c, y0, y1, from, d_z, d_iters, d_w, d_m, stream);
-                    });
+    const int rc = check_scaled_plain(cfg, c, y0, y1);
+    if (rc != FR_OK) return rc;
+    return state_host(cfg, y0, y1, from, z, iters, w, m, "SCALED PT", "w", scaled_state_rows(cfg, c, y0, y1, from));
 }
 
 }  // namespace
@@ -712,19 +683,7 @@ int fr_render_rows_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *
     int rc = check_channels(channels);
     if (rc == FR_OK) rc = check_scaled(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
-    const size_t need = (size_t)channels * cfg->width * (size_t)(y1 - y0);
-    if (need == 0) return FR_OK;
-    if (!d_out) return fail(FR_ERR_INVALID_ARGUMENT, "d_out is NULL");
-    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*(y1-y0)");
-    if (channels == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u))
-        return fail(FR_ERR_INVALID_ARGUMENT, "RGBA8 output must be 4-byte aligned");
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    fr_kout ko{};
-    ko.rgb = static_cast<uint8_t *>(d_out);
-    return profiled_launch(*ctx, cfg, c, bits, y0, y1, (unsigned)channels, FR_OUT_RGB, ko, static_cast<hipStream_t>(hip_stream));
+    return rgb_rows_device(cfg, y0, y1, channels, d_out, out_len, hip_stream, scaled_rows(cfg, c, bits, y0, y1, (unsigned)channels, FR_OUT_RGB));
 }
 
 int fr_render_rows_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, int channels,
@@ -733,81 +692,35 @@ int fr_render_rows_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre,
     int rc = check_channels(channels);
     if (rc == FR_OK) rc = check_scaled(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
-    const size_t need = (size_t)channels * cfg->width * (size_t)(y1 - y0);
-    if (need == 0) return FR_OK;
-    if (!out) return fail(FR_ERR_INVALID_ARGUMENT, "out is NULL");
-    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*(y1-y0)");
-    return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) {
-        fr_kout ko{};
-        ko.rgb = static_cast<uint8_t *>(d_out);
-        return profiled_launch(ctx, cfg, c, bits, y0, y1, (unsigned)channels, FR_OUT_RGB, ko, stream);
-    });
+    return rgb_rows_host(cfg, y0, y1, channels, out, out_len, scaled_rows(cfg, c, bits, y0, y1, (unsigned)channels, FR_OUT_RGB));
 }
 
 int fr_escape_rows_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, void *d_z,
                                     void *d_iters, void *hip_stream) {
     const Centre c{nullptr, centre, true};
-    int rc = check_scaled(cfg, c, bits, y0, y1);
+    const int rc = check_scaled(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    if (npx == 0 || (!d_z && !d_iters)) return FR_OK;
-    if (reinterpret_cast<uintptr_t>(d_z) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_z must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_iters) & 3u) return fail(FR_ERR_INVALID_ARGUMENT, "d_iters must be 4-byte aligned");
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    fr_kout ko{};
-    ko.z = static_cast<double *>(d_z);
-    ko.iters = static_cast<uint32_t *>(d_iters);
-    return profiled_launch(*ctx, cfg, c, bits, y0, y1, 0, FR_OUT_ESCAPE, ko, static_cast<hipStream_t>(hip_stream));
+    return raw_rows_device(cfg, y0, y1, d_z, d_iters, hip_stream, scaled_rows(cfg, c, bits, y0, y1, 0, FR_OUT_ESCAPE));
 }
 
 int fr_escape_rows_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, double *z,
                              uint32_t *iters) {
     const Centre c{nullptr, centre, true};
-    int rc = check_scaled(cfg, c, bits, y0, y1);
+    const int rc = check_scaled(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    if (npx == 0 || (!z && !iters)) return FR_OK;
-    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), nullptr, nullptr, false,
-                    [&](Ctx &ctx, double *d_z, uint32_t *d_iters, double *, uint32_t *, hipStream_t stream) {
-                        fr_kout ko{};
-                        ko.z = d_z;
-                        ko.iters = d_iters;
-                        return profiled_launch(ctx, cfg, c, bits, y0, y1, 0, FR_OUT_ESCAPE, ko, stream);
-                    });
+    return raw_rows_host(cfg, y0, y1, z, iters, 2, scaled_rows(cfg, c, bits, y0, y1, 0, FR_OUT_ESCAPE));
 }
 
 int fr_debug_pt_scaled_count(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, uint64_t *passes,
                              uint64_t *steps) {
     const Centre c{nullptr, centre, true};
-    int rc = check_scaled(cfg, c, bits, y0, y1);
+    const int rc = check_scaled(cfg, c, bits, y0, y1);
     if (rc != FR_OK) return rc;
     if (!passes || !steps) return fail(FR_ERR_INVALID_ARGUMENT, "passes or steps is NULL");
     *passes = *steps = 0;
     if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    const size_t bytes = sizeof(unsigned long long) * 2 * FR_COUNT_SLOTS;
-    rc = ctx->reserve(ctx->misc, bytes);
-    if (rc != FR_OK) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->misc.ptr, 0, bytes, ctx->stream));
-    fr_kout ko{};
-    ko.count = static_cast<unsigned long long *>(ctx->misc.ptr);
-    rc = profiled_launch(*ctx, cfg, c, bits, y0, y1, 0, FR_OUT_COUNT, ko, ctx->stream);
-    if (rc != FR_OK) return rc;
-    std::vector<unsigned long long> host(2 * FR_COUNT_SLOTS);
-    HIP_TRY(hipMemcpyAsync(host.data(), ctx->misc.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (uint32_t s = 0; s < FR_COUNT_SLOTS; s++) {
-        *passes += host[s];
-        *steps += host[FR_COUNT_SLOTS + s];
-    }
-    return FR_OK;
+    uint64_t *const sums[2] = {passes, steps};
+    return count_rows(sums, scaled_rows(cfg, c, bits, y0, y1, 0, FR_OUT_COUNT));
 }
 
 int fr_debug_bla_table_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, int which, uint32_t level, double *out,

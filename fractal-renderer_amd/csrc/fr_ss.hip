@@ -338,20 +338,16 @@ int fr_render_rows_ss_device(const fr_config *cfg, int precision, const fr_imagi
             return fail(FR_ERR_BUFFER_TOO_SMALL, "work_len < min_bytes of fr_ss_workspace_bytes");
         if (!d_work) return fail(FR_ERR_INVALID_ARGUMENT, "d_work is NULL");
     }
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (supersample == 1) { /* the plain render, byte for byte */
-        if (precision == FR_PRECISION_DD || precision == FR_PRECISION_PT)
-            return render_deep_device(*ctx, precision, cfg, Centre{pos_lo, nullptr}, o, y0, y1, (unsigned)channels, d_out, stream);
-        fr_kparams p;
-        rows_params(cfg, o, y0, y1, (unsigned)channels, p);
-        return render_device(*ctx, cfg, p, precision, o, d_out, stream);
-    }
-    return render_ss_device(*ctx, pl, precision, pos_lo, supersample, y0, (unsigned)channels, d_out, d_work, work_len,
-                            stream, o);
+    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
+        if (supersample == 1) { /* the plain render, byte for byte */
+            if (precision == FR_PRECISION_DD || precision == FR_PRECISION_PT)
+                return render_deep_device(ctx, precision, cfg, Centre{pos_lo, nullptr}, o, y0, y1, (unsigned)channels, d_out, stream);
+            fr_kparams p;
+            rows_params(cfg, o, y0, y1, (unsigned)channels, p);
+            return render_device(ctx, cfg, p, precision, o, d_out, stream);
+        }
+        return render_ss_device(ctx, pl, precision, pos_lo, supersample, y0, (unsigned)channels, d_out, d_work, work_len, stream, o);
+    });
 }
 
 int fr_render_rows_ss(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t supersample, uint32_t y0,

@@ -1,6 +1,6 @@
 """The table behind tests/test_deep_call_errors_cpu.py and tools/record_deep_call_errors.py: every deep entry point of the C
-ABI (DD, PT, PT state, PT extend, their wide variants, BLA-PT and its debug hooks, supersampling with pos_lo; host and
-device forms) and the invalid calls each must refuse BEFORE any device work, with a code and a message.
+ABI (DD, PT, PT state, PT extend, their wide variants, BLA-PT and its debug hooks, SCALED PT with its state, its extension
+and its debug hooks, supersampling with pos_lo; host and device forms) and the invalid calls each must refuse BEFORE any device work, with a code and a message.
 
 An entry is a C function and the order of its arguments, written as keys of one argument dict; a case edits that dict and
 applies to every entry whose signature has the keys it edits.  calls(native) yields (id, function name, ctypes arguments,
@@ -49,6 +49,17 @@ ENTRIES.update({
     "fr_render_rows_ss[pt]": ("fr_render_rows_ss", "cfg prec lo s y0 y1 ch out out_len opts", {"prec": 3, "s": 2}),
     "fr_render_rows_ss_device[pt]": (
         "fr_render_rows_ss_device", "cfg prec lo s y0 y1 ch out out_len work work_len stream opts", {"prec": 3, "s": 2}),
+    # SCALED PT: the centre is required and there is no pos_lo; the rows and the hooks take bits, the state calls do not
+    "fr_render_rows_pt_scaled": ("fr_render_rows_pt_scaled", "cfg wide bits y0 y1 ch out out_len", {}),
+    "fr_render_rows_pt_scaled_device": ("fr_render_rows_pt_scaled_device", "cfg wide bits y0 y1 ch out out_len stream", {}),
+    "fr_escape_rows_pt_scaled": ("fr_escape_rows_pt_scaled", "cfg wide bits y0 y1 z it", {}),
+    "fr_escape_rows_pt_scaled_device": ("fr_escape_rows_pt_scaled_device", "cfg wide bits y0 y1 z it stream", {}),
+    "fr_debug_pt_scaled_count": ("fr_debug_pt_scaled_count", "cfg wide bits y0 y1 passes steps", {}),
+    "fr_debug_bla_table_scaled": ("fr_debug_bla_table_scaled", "cfg wide bits which level table cap len", {}),
+    "fr_escape_rows_pt_scaled_state": ("fr_escape_rows_pt_scaled_state", STATE_HOST.format(where="wide"), {}),
+    "fr_escape_rows_pt_scaled_state_device": ("fr_escape_rows_pt_scaled_state_device", STATE_HOST.format(where="wide") + " stream", {}),
+    "fr_escape_extend_pt_scaled": ("fr_escape_extend_pt_scaled", EXTEND_HOST.format(where="wide"), {}),
+    "fr_escape_extend_pt_scaled_device": ("fr_escape_extend_pt_scaled_device", EXTEND_HOST.format(where="wide") + " stream", {}),
 })
 
 
@@ -62,6 +73,10 @@ def is_dd(entry):
 
 def is_bla(entry):
     return "bla" in entry
+
+
+def is_scaled(entry):
+    return "scaled" in entry
 
 
 class Call:
@@ -169,6 +184,19 @@ def bits_54(c):
     c.a["bits"] = 54
 
 
+def no_table(c):
+    """bits = -1: SCALED PT's plain loop; no answer where the call is about a table, and BLA-PT has no such value"""
+    if not c.has("bits"):
+        return False
+    c.a["bits"] = -1
+
+
+def bits_minus_1(c):
+    if is_scaled(c.entry) and not c.has("table"):  # legal for SCALED PT's rows and count: the pairs with no_table below pin that
+        return False
+    return no_table(c)
+
+
 def from_above_iterations(c):
     if not c.has("from"):
         return False
@@ -226,7 +254,8 @@ CASES = [y0_above_y1, y1_above_height, channels_2, limit_not_finite, pos_lo_not_
          both(channels_2, y0_above_y1), both(y0_above_y1, limit_not_finite), both(limit_not_finite, iterations_above_pt_max),
          both(iterations_above_pt_max, from_above_iterations), both(wide_centre_null, channels_2), both(bits_54, pos_lo_with_centre),
          both(pos_lo_not_normalised, bits_23), both(null_output, y1_above_height), both(from_above_iterations, null_output),
-         short_and_misaligned]
+         short_and_misaligned, bits_minus_1, both(no_table, null_output), both(no_table, misaligned_pointer),
+         both(wide_centre_null, bits_54), both(bits_23, null_output)]
 
 
 def calls(native):

@@ -4,7 +4,8 @@ test_gpu_pt.py, test_gpu_pt_state.py, test_gpu_pt_wide.py and test_gpu_bla.py, w
   - rows [5, 12) alone are rows 5 .. 11 of the whole call (the row grid of a launch);
   - with fr_set_profiling(1) every road reports a time and its own kernel, in both forms.
 Roads: DD and PT renders (RGB and RGBA), the PT state, the PT extension 150 -> 300, BLA-PT renders and escape rows; PT and
-BLA-PT with the centre as pos_lo and as the WideCentre of exactly the same value.
+BLA-PT with the centre as pos_lo and as the WideCentre of exactly the same value.  SCALED PT on the wide views: renders and
+escape rows with bits = -1 (the plain loop, scaled-pt-*) and bits = 0 (the table, scaled-bla-*), its state and its extension.
 Views: 33 x 17 at 300 iterations — ragged against the 16 x 16 pixels of a workgroup on both axes, more than one workgroup per
 axis — Mandelbrot on the Misiurewicz point and Julia on the repelling fixed point of tests/pt_wide_model.py (the centres of
 test_gpu_bla.py), at 2^84 with the centre split into pos + pos_lo, and Mandelbrot at 2^300 on the 6-word centre (wide only).
@@ -99,13 +100,31 @@ def _view(fr, name):
 
 KERNEL = {"dd-rgb": "escape_dd_kernel", "dd-rgba": "escape_dd_kernel", "pt-rgb": "escape_pt_kernel", "pt-rgba": "escape_pt_kernel",
           "pt-state": "escape_pt_state_kernel", "pt-extend": "escape_extend_pt_kernel", "bla-rgb": "escape_bla_kernel",
-          "bla-rgba": "escape_bla_kernel", "bla-escape": "escape_bla_kernel"}
+          "bla-rgba": "escape_bla_kernel", "bla-escape": "escape_bla_kernel",
+          "scaled-pt-rgb": "escape_pt_scaled_kernel", "scaled-pt-rgba": "escape_pt_scaled_kernel",
+          "scaled-pt-escape": "escape_pt_scaled_kernel", "scaled-bla-rgb": "escape_bla_scaled_kernel",
+          "scaled-bla-rgba": "escape_bla_scaled_kernel", "scaled-bla-escape": "escape_bla_scaled_kernel",
+          "scaled-state": "escape_pt_scaled_state_kernel", "scaled-extend": "escape_extend_pt_scaled_kernel"}
 ROADS = tuple(KERNEL)
-DTYPES = (np.float64, np.uint32, np.float64, np.uint32)  # z, iters, dz, m
+DTYPES = (np.float64, np.uint32, np.float64, np.uint32)  # z, iters, dz (SCALED PT: w), m
+
+
+def scaled(road):
+    return road.startswith("scaled")
+
+
+def applies(v, road):
+    """DD takes no wide centre, SCALED PT nothing else; v: a view's name"""
+    return not (road.startswith("dd") and not v.endswith("-lo")) and not (scaled(road) and v.endswith("-lo"))
+
+
+def state_road(road):
+    """the state road whose result an extension continues and must reproduce"""
+    return "scaled-state" if scaled(road) else "pt-state"
 
 
 def cases():
-    return [(v, r) for v in VIEWS for r in ROADS if not (r.startswith("dd") and not v.endswith("-lo"))]
+    return [(v, r) for v in VIEWS for r in ROADS if applies(v, r)]
 
 
 def raw_shapes(rows, n):
@@ -113,7 +132,7 @@ def raw_shapes(rows, n):
 
 
 def run(lib, torch, v, road, form, y0, y1, start=None):
-    """`start`: the state at 150 of rows [y0, y1) that pt-extend continues"""
+    """`start`: the state at 150 of rows [y0, y1) that pt-extend / scaled-extend continues"""
     rows, device = y1 - y0, form == "device"
     w = "_wide" if v.wide else ""
     if road.endswith(("rgb", "rgba")):
@@ -126,13 +145,15 @@ def run(lib, torch, v, road, form, y0, y1, start=None):
             check(getattr(lib, "fr_render_rows_dd" + suffix)(C.byref(v.cfg), v.where(), *tail))
         elif road.startswith("pt"):
             check(getattr(lib, "fr_render_rows_pt" + w + suffix)(C.byref(v.cfg), v.where(), *tail))
+        elif scaled(road):
+            check(getattr(lib, "fr_render_rows_pt_scaled" + suffix)(C.byref(v.cfg), C.byref(v.centre), -1 if "-pt-" in road else 0, *tail))
         else:
             check(getattr(lib, "fr_render_rows_pt_bla" + suffix)(C.byref(v.cfg), *v.both(), 0, *tail))
         if device:
             torch.cuda.synchronize()
             buf = buf.cpu().numpy()
         return (buf.reshape(rows, W_, ch),)
-    n_arrays = 2 if road == "bla-escape" else 4
+    n_arrays = 2 if road.endswith("escape") else 4
     shapes = raw_shapes(rows, n_arrays)
     host = [np.zeros(s, dtype=d) if start is None else np.array(start[k], dtype=d, order="C") for k, (s, d) in enumerate(zip(shapes, DTYPES))]
     if device:
@@ -143,10 +164,16 @@ def run(lib, torch, v, road, form, y0, y1, start=None):
     suffix = "_device" if device else ""
     if road == "bla-escape":
         check(getattr(lib, "fr_escape_rows_pt_bla" + suffix)(C.byref(v.cfg), *v.both(), 0, y0, y1, *ptrs))
+    elif road.endswith("escape"):
+        check(getattr(lib, "fr_escape_rows_pt_scaled" + suffix)(C.byref(v.cfg), C.byref(v.centre), -1 if "-pt-" in road else 0, y0, y1, *ptrs))
     elif road == "pt-state":
         check(getattr(lib, "fr_escape_rows_pt%s_state%s" % (w, suffix))(C.byref(v.cfg), v.where(), y0, y1, *ptrs))
-    else:
+    elif road == "pt-extend":
         check(getattr(lib, "fr_escape_extend_pt%s%s" % (w, suffix))(C.byref(v.cfg), v.where(), y0, y1, LOW_CAP, *ptrs))
+    elif road == "scaled-state":
+        check(getattr(lib, "fr_escape_rows_pt_scaled_state" + suffix)(C.byref(v.cfg), C.byref(v.centre), y0, y1, *ptrs))
+    else:
+        check(getattr(lib, "fr_escape_extend_pt_scaled" + suffix)(C.byref(v.cfg), C.byref(v.centre), y0, y1, LOW_CAP, *ptrs))
     if device:
         torch.cuda.synchronize()
         host = [t.cpu().numpy().view(d).reshape(s) for t, s, d in zip(dev, shapes, DTYPES)]
@@ -154,11 +181,14 @@ def run(lib, torch, v, road, form, y0, y1, start=None):
 
 
 @functools.lru_cache(maxsize=None)
-def _state_at_150(lib, v):
-    """the host form's state at the low cap, whole image: what the extensions start from"""
+def _state_at_150(lib, v, road):
+    """the host form's state at the low cap, whole image: what the extension `road` starts from"""
     host = [np.zeros(s, dtype=d) for s, d in zip(raw_shapes(H_, 4), DTYPES)]
-    name = "fr_escape_rows_pt%s_state" % ("_wide" if v.wide else "")
-    check(getattr(lib, name)(C.byref(v.low), v.where(), 0, H_, *(a.ctypes.data for a in host)))
+    if scaled(road):
+        check(lib.fr_escape_rows_pt_scaled_state(C.byref(v.low), C.byref(v.centre), 0, H_, *(a.ctypes.data for a in host)))
+    else:
+        name = "fr_escape_rows_pt%s_state" % ("_wide" if v.wide else "")
+        check(getattr(lib, name)(C.byref(v.low), v.where(), 0, H_, *(a.ctypes.data for a in host)))
     for a in host:
         a.setflags(write=False)
     return tuple(host)
@@ -167,7 +197,7 @@ def _state_at_150(lib, v):
 @functools.lru_cache(maxsize=None)
 def _whole(lib, torch, v, road, form):
     """the whole image by one call, computed once per (view, road, form) and never written to"""
-    out = run(lib, torch, v, road, form, 0, H_, _state_at_150(lib, v) if road == "pt-extend" else None)
+    out = run(lib, torch, v, road, form, 0, H_, _state_at_150(lib, v, road) if road.endswith("extend") else None)
     for a in out:
         a.setflags(write=False)
     return out
@@ -198,13 +228,13 @@ def test_host_form_and_device_form_write_the_same(fr, lib, torch, name, road):
         assert road.endswith("rgb") or (host[0][..., 3] == 255).all()
     else:
         assert len(np.unique(host[1])) > 5 and host[1].max() <= CAP
-    if road == "pt-extend":  # it moved the pixels still running at 150 and nothing else; what it gives is the state at 300
-        low = _state_at_150(lib, v)
+    if road.endswith("extend"):  # it moved the pixels still running at 150 and nothing else; what it gives is the state at 300
+        low = _state_at_150(lib, v, road)
         running = low[1] == LOW_CAP
         assert running.any() == (not name.startswith("M-") or name == "M-2^300")
         assert same(tuple(a[~running] for a in host), tuple(a[~running] for a in low))
         assert not running.any() or not np.array_equal(host[2][running], low[2][running])
-        assert same(host, _whole(lib, torch, v, "pt-state", "host"))
+        assert same(host, _whole(lib, torch, v, state_road(road), "host"))
 
 
 @pytest.mark.parametrize("form", ["host", "device"])
@@ -212,7 +242,7 @@ def test_host_form_and_device_form_write_the_same(fr, lib, torch, name, road):
 def test_rows_5_to_12_alone_are_those_rows_of_the_whole(fr, lib, torch, name, road, form):
     v = _view(fr, name)
     y0, y1 = SUB
-    start = tuple(a[y0:y1] for a in _state_at_150(lib, v)) if road == "pt-extend" else None
+    start = tuple(a[y0:y1] for a in _state_at_150(lib, v, road)) if road.endswith("extend") else None
     piece = run(lib, torch, v, road, form, y0, y1, start)
     assert same(piece, tuple(a[y0:y1] for a in _whole(lib, torch, v, road, form))), "%s, %s, %s form" % (name, road, form)
 
@@ -229,12 +259,12 @@ def test_profiling_reports_each_roads_kernel_in_both_forms(fr, lib, torch, name)
 
     try:
         for road in ROADS:
-            if road.startswith("dd") and v.wide:
+            if not applies(name, road):
                 continue
             for form in ("host", "device"):
                 check(lib.fr_set_profiling(0))  # forgets the last kernel: a road that records nothing has nothing to report
                 check(lib.fr_set_profiling(1))
-                got = run(lib, torch, v, road, form, 0, H_, _state_at_150(lib, v) if road == "pt-extend" else None)
+                got = run(lib, torch, v, road, form, 0, H_, _state_at_150(lib, v, road) if road.endswith("extend") else None)
                 kname, ms = last()
                 assert kname == KERNEL[road] and ms > 0.0, "%s, %s form: %r, %r ms" % (road, form, kname, ms)
                 assert same(got, _whole(lib, torch, v, road, form)), "%s, %s form: profiling changed the result" % (road, form)
