@@ -34,6 +34,7 @@ __all__ = [
     "escape_rows_pt_state", "extend_rows_pt", "escape_rows_pt_state_device", "extend_rows_pt_device", "pt_orbit_cache",
     "WideCentre", "reference_orbit_wide",
     "bla_table", "bla_count", "bla_cache", "BLA_DEFAULT_BITS",
+    "get_image_ss_pt", "colour_rows_ss_device", "colour_image_ss",
 ]
 
 
@@ -377,6 +378,46 @@ def box_filter(image, s, channels=3):
     return out
 
 
+def _ss_pt_road(pos_lo, centre, bla, scaled):
+    """get_image_ss_pt's keywords -> (road, bits) by _deep_call's rules; ValueError before any C call"""
+    if bla is not None:
+        bits = int(bla)
+        if bits != 0 and not 24 <= bits <= 53:
+            raise ValueError("bla= is None (off), 0 (%d bits) or 24 .. 53" % BLA_DEFAULT_BITS)
+    if centre is not None and pos_lo is not None:
+        raise ValueError("centre= and pos_lo= exclude each other")
+    if scaled:
+        if centre is None:
+            raise ValueError("scaled= needs centre= (a WideCentre); it takes no pos_lo=")
+        return _native.FR_PT_ROAD_SCALED, -1 if bla is None else bits
+    if bla is not None:
+        return _native.FR_PT_ROAD_BLA, bits
+    return _native.FR_PT_ROAD_PLAIN, 0
+
+
+def get_image_ss_pt(config, supersample, pos_lo=None, centre=None, bla=None, scaled=False, y0=0, y1=None, channels=3, out=None):
+    """Anti-aliased deep renders (fr_render_rows_ss_pt; include/fractal_hip.h, "supersampled rendering on the deep roads"):
+    rows [y0, y1) of the Precision.PT image with supersample x supersample samples per pixel, box-filtered on the device, as
+    uint8 [y1-y0, width, channels].  pos_lo, centre, bla and scaled select the road as they do in get_image_rows: plain PT
+    (pos_lo or neither), WIDE PT (centre), BLA-PT (bla = 0 or 24 .. 53, with pos_lo or centre or neither), SCALED PT
+    (scaled=True, needs centre; combines with bla).  supersample = 1 is the road's plain render."""
+    s = int(supersample)
+    if not 1 <= s <= SS_MAX:
+        raise ValueError("supersample is 1 .. %d" % SS_MAX)
+    if int(channels) not in (3, 4):
+        raise ValueError("channels is 3 or 4")
+    road, bits = _ss_pt_road(pos_lo, centre, bla, scaled)
+    y0, y1 = _rows(config, y0, y1)
+    if out is None:
+        out = np.empty((max(y1 - y0, 0), config.width, int(channels)), dtype=np.uint8)
+    lo = None if pos_lo is None else Imaginary(*(float(v) for v in pos_lo))
+    st = None if centre is None else centre.c_struct()
+    _native.check(_native.load().fr_render_rows_ss_pt(C.byref(config), None if lo is None else C.byref(lo),
+                                                      None if st is None else C.byref(st), road, bits, s, y0, y1, int(channels),
+                                                      out.ctypes.data, out.nbytes))
+    return out
+
+
 def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None, pos_lo=None, supersample=1, centre=None,
                    bla=None, scaled=False):
     """Rows [y0, y1) of get_image — the unit of the reference's rayon loop (src/lib.rs:256-264).
@@ -385,7 +426,8 @@ def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None,
     supersample = s > 1: s x s samples per pixel, box-filtered on the device (include/fractal_hip.h, "supersampled
     rendering"); only the [y1-y0, width] result leaves the device.
     centre (Precision.PT only, exclusive with pos_lo): a WideCentre in place of (config.pos, pos_lo) for views past a scale
-    of 10^30 (include/fractal_hip.h, "WIDE PT"); supersample does not take it yet.
+    of 10^30 (include/fractal_hip.h, "WIDE PT").  supersample combines with neither centre, bla nor scaled here:
+    anti-aliased deep renders on those roads are get_image_ss_pt's.
     bla (Precision.PT only, with pos_lo or centre or neither): None = plain PT; 0 or 24 .. 53 = BLA-PT at that many bits
     (0: BLA_DEFAULT_BITS), PT with iterations skipped in bulk — an approximation, defined in include/fractal_hip.h, "BLA-PT".
     scaled=True (needs centre=; combines with bla=; no pos_lo, supersample or opts): SCALED PT, the pixel loop that carries
@@ -637,6 +679,43 @@ def colour_rows_device(config, z_ptr, iters_ptr, n, out_ptr, channels=3, z_width
     n = int(n)
     _native.check(_native.load().fr_colour_rows_device(C.byref(config), z_ptr or None, int(z_width), iters_ptr or None, n,
                                                        int(channels), out_ptr or None, int(channels) * n, _stream(stream)))
+
+
+def colour_rows_ss_device(config, z_ptr, iters_ptr, width, rows, supersample, out_ptr, channels=3, z_width=2, stream=None):
+    """fr_colour_rows_ss_device: colour map + box filter in one kernel over a KEPT anti-aliased view — the stored results of
+    supersample * rows rows of supersample * width samples in DEVICE memory (what the escape_rows*_device calls write for the
+    config with width and height times supersample) — into channels * width * rows bytes at out_ptr, asynchronously on
+    `stream`.  The bytes are colour_rows_device's followed by the box filter's; no RGB workspace in between."""
+    width, rows, s = int(width), int(rows), int(supersample)
+    if not 1 <= s <= SS_MAX:
+        raise ValueError("supersample is 1 .. %d" % SS_MAX)
+    if int(z_width) not in (2, 4):
+        raise ValueError("z_width is 2 or 4")
+    if int(channels) not in (3, 4):
+        raise ValueError("channels is 3 or 4")
+    _native.check(_native.load().fr_colour_rows_ss_device(C.byref(config), z_ptr or None, int(z_width), iters_ptr or None, width, rows,
+                                                          s, int(channels), out_ptr or None, int(channels) * width * rows,
+                                                          _stream(stream)))
+
+
+def colour_image_ss(config, z, iters, supersample, channels=3):
+    """fr_colour_ss_rgb8 over numpy arrays: z float64 [s*rows, s*width, 2] (or [..., 4]: DD with its low parts, coloured on
+    the hi parts) and iters uint32 [s*rows, s*width] -> uint8 [rows, width, channels], each pixel the box-filtered colours
+    of its s x s samples: box_filter(colour_image(config, z, iters), s), byte for byte."""
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    iters = np.ascontiguousarray(iters, dtype=np.uint32)
+    s = int(supersample)
+    if not 1 <= s <= SS_MAX:
+        raise ValueError("supersample is 1 .. %d" % SS_MAX)
+    if int(channels) not in (3, 4):
+        raise ValueError("channels is 3 or 4")
+    if z.ndim != 3 or z.shape[:2] != iters.shape or z.shape[2] not in (2, 4) or iters.shape[0] % s or iters.shape[1] % s:
+        raise ValueError("z must be [s*rows, s*width, 2 or 4] and iters [s*rows, s*width]")
+    rows, width = iters.shape[0] // s, iters.shape[1] // s
+    out = np.empty((rows, width, int(channels)), dtype=np.uint8)
+    _native.check(_native.load().fr_colour_ss_rgb8(C.byref(config), z.ctypes.data, z.shape[2], iters.ctypes.data, width, rows, s,
+                                                   int(channels), out.ctypes.data, out.nbytes))
+    return out
 
 
 def colour_image(config, z, iters):

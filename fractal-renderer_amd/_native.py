@@ -116,6 +116,7 @@ class fr_wide_centre(C.Structure):
 
 FR_WIDE_MAX_WORDS = 16
 FR_BLA_DEFAULT_BITS = 40
+FR_PT_ROAD_PLAIN, FR_PT_ROAD_BLA, FR_PT_ROAD_SCALED = 0, 1, 2  # fr_pt_road
 _OPTS = C.POINTER(fr_render_opts)
 _WIDE = C.POINTER(fr_wide_centre)
 
@@ -350,6 +351,26 @@ PROTOTYPES = {
     "fr_escape_extend_pt_scaled": (
         C.c_int,
         [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "fr_render_rows_ss_pt_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+         C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "fr_render_rows_ss_pt": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+         C.c_void_p, C.c_size_t],
+    ),
+    "fr_colour_rows_ss_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
+         C.c_size_t, C.c_void_p],
+    ),
+    "fr_colour_ss_rgb8": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
+         C.c_size_t],
     ),
     "fr_colour_rows_device": (
         C.c_int,

@@ -14,6 +14,7 @@
 // in include/fractal_hip.h, "BLA-PT"; BITS is 24 .. 53, default 40);
 // --scaled beside --perturbation (SCALED PT: the pixel loop that carries its offsets scaled by the view's exponent, so scales
 // past 2^440 render, up to just under 2^952; it combines with --bla — include/fractal_hip.h, "SCALED PT");
+// --supersample N (N x N samples per pixel, box-filtered on the device; with --perturbation, --bla and --scaled too);
 // for -a fern: --threads N (the rayon thread count being stood in for; default: this machine's hardware
 // threads, what rayon would use) and --seed N (default: from the OS, as the reference seeds from entropy).
 // Not handled here (by design): --gui, --open.
@@ -133,8 +134,8 @@ int main(int argc, char **argv) {
     else die("invalid algorithm name");
     if (algo == Algo::Julia && (!julia_re || !julia_im)) die("--julia-real and --julia-imaginary are required with -a julia");
     if ((scale_x || scale_y) && scale != "0.4") die("--scale conflicts with --scale-x/--scale-y");
-    if (perturbation && (f32 || supersample_s || devices || algo == Algo::BarnsleyFern))
-        die("--perturbation does not combine with --f32, --supersample, --devices or -a fern");
+    if (perturbation && (f32 || devices || algo == Algo::BarnsleyFern))
+        die("--perturbation does not combine with --f32, --devices or -a fern");
     if (bla && !perturbation) die("--bla needs --perturbation");
     if (scaled && !perturbation) die("--scaled needs --perturbation");
 
@@ -198,7 +199,11 @@ int main(int argc, char **argv) {
         } else if (perturbation) {
             // the centre keeps every digit of -x / -y; cfg.pos (their f64 roundings) is not read
             const WideCentre centre = WideCentre::from_decimal(pos_x_s, pos_y, WideCentre::words_for_scale(cfg.scale.re, cfg.scale.im));
-            if (scaled) image = get_image(cfg, centre.c(), Scaled{bla ? bla_bits : -1});
+            if (supersample_s) { // anti-aliased: the same road, N x N samples per pixel
+                const uint32_t ss = to_u32(*supersample_s, "--supersample");
+                if (scaled) image = get_image(cfg, centre.c(), Scaled{bla ? bla_bits : -1}, ss);
+                else image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}, ss) : get_image(cfg, centre.c(), ss);
+            } else if (scaled) image = get_image(cfg, centre.c(), Scaled{bla ? bla_bits : -1});
             else image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}) : get_image(cfg, centre.c());
         } else {
             const int precision = f32 ? FR_PRECISION_F32 : FR_PRECISION_F64;

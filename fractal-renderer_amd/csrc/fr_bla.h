@@ -74,6 +74,17 @@ int bla_table_for(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, boo
 int bla_debug_table(const fr_config *cfg, const Centre &c, int bits, bool scaled, int which, uint32_t level, double *out, size_t cap,
                     uint32_t *len);
 
+/* For the supersampled form of the roads (fr_ss.hip: fr_render_rows_ss_pt), which renders the rows of cfg_s band by band:
+ * bla_check / scaled_check — the domain checks the roads' own calls run (the file-local check_bla / check_scaled), bits
+ * resolved in place — and bla_render_rows / scaled_render_rows — the roads' row launch (the file-local bla_rows / scaled_rows)
+ * in MODE RGB, called: rows [y0, y1) into out.rgb on `stream` between the profiling events (fr_bla.hip, fr_scaled.hip). */
+int bla_check(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1);
+int bla_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, unsigned channels,
+                    const fr_kout &out, hipStream_t stream);
+int scaled_check(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1);
+int scaled_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, unsigned channels,
+                       const fr_kout &out, hipStream_t stream);
+
 }  // namespace fr
 
 #endif

@@ -458,6 +458,14 @@ auto bla_rows(const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint
 }
 
 }  // namespace
+
+/* the road's check and RGB row launch for the supersampled form (fr_ss.hip), which bands the rows itself */
+int bla_check(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1) { return check_bla(cfg, c, bits, y0, y1); }
+int bla_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, unsigned channels,
+                    const fr_kout &out, hipStream_t stream) {
+    return bla_rows(cfg, c, bits, y0, y1, channels, FR_OUT_RGB)(ctx, out, stream);
+}
+
 }  // namespace fr
 
 using namespace fr;

@@ -233,6 +233,13 @@ hipError_t fr_launch_colour_rows(const fr_kparams &p, const double *z, uint32_t 
 hipError_t fr_launch_box_filter(const void *src, uint32_t width, uint64_t rows, uint32_t s, uint32_t bpp, void *dst,
                                 hipStream_t stream);
 
+/* Colour map + box filter over the stored results of the s times larger image (fr_ss.hip: colour_filter_kernel<s>): z
+ * (z_width 2 or 4 doubles per sample, colour on the hi parts) and iters hold s * rows rows of s * width samples; dst as
+ * fr_launch_box_filter's.  The same bytes as fr_launch_colour_rows followed by fr_launch_box_filter; s = 1 is the former.
+ * 64-bit element offsets.  Device arrays. */
+hipError_t fr_launch_colour_filter(const fr_kparams &p, const double *z, uint32_t z_width, const uint32_t *iters, uint32_t width,
+                                   uint64_t rows, uint32_t s, uint32_t bpp, void *dst, hipStream_t stream);
+
 /* n independent orbits, device arrays (re, im interleaved) */
 hipError_t fr_launch_recursive_batch(uint32_t iterations, const double *start, const double *c, size_t n,
                                      double limit, int precision, double *out_pos, uint32_t *out_iters,

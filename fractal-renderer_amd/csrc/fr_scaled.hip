@@ -673,6 +673,14 @@ int scaled_state_host(const fr_config *cfg, const fr_wide_centre *centre, uint32
 }
 
 }  // namespace
+
+/* the road's check and RGB row launch for the supersampled form (fr_ss.hip), which bands the rows itself */
+int scaled_check(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1) { return check_scaled(cfg, c, bits, y0, y1); }
+int scaled_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, unsigned channels,
+                       const fr_kout &out, hipStream_t stream) {
+    return scaled_rows(cfg, c, bits, y0, y1, channels, FR_OUT_RGB)(ctx, out, stream);
+}
+
 }  // namespace fr
 
 using namespace fr;

@@ -9,6 +9,10 @@
  *     the caller lends, each filtered into its place, all on the caller's stream), fr_render_rows_ss (the same into a
  *     host buffer, through context scratch), fr_box_filter_rgb8(_device) (the filter alone).
  * The render kernels are not touched: a band is an ordinary row-range render of the large image.
+ *   - the same on the deep roads (WIDE PT, BLA-PT, SCALED PT): fr_render_rows_ss_pt(_device), the band loop above with the
+ *     road's own row launch in place of the precision's;
+ *   - colour_filter_kernel / fr_launch_colour_filter and fr_colour_rows_ss_device / fr_colour_ss_rgb8: a KEPT anti-aliased
+ *     view — (z, iters) of cfg_s in device memory — coloured and filtered in one kernel, no RGB workspace in between.
  *
  * Kernel shape (memory-bound: it reads 3*s*s bytes and writes 3 or 4 per output pixel; DESIGN.md, "Supersampling"):
  *   - a workgroup of 256 lanes produces a tile of 256 output pixels x `ro` output rows (ro = 4, 2, 1 for s <= 2, 3, >= 4:
@@ -25,11 +29,15 @@
  *     < 4 tail bytes;
  *   - 64-bit byte offsets throughout (a source may exceed 4 GiB); plain vector loads and stores only.
  */
-#include "fr_ctx.h"
+#include "fr_bla.h" /* fr_ctx.h, and the BLA-PT / SCALED PT row launches */
 
 #include <algorithm>
 
+#include "fr_math.h"
+
 namespace {
+
+#include "fr_colour.h" /* the colour map of the renders: colour_filter_kernel's bytes are its bytes */
 
 constexpr uint32_t kSsThreads = 256;                     /* lanes = output pixels per tile row */
 constexpr uint32_t kSsOutPitch = 3 * kSsThreads + 16;    /* LDS bytes per staged RGB output row (3 spare + padding) */
@@ -158,6 +166,191 @@ __global__ __launch_bounds__(kSsThreads) void box_filter_kernel(const ss_params 
     }
 }
 
+
+/* ---- colour_filter_kernel: colour map + box filter over the stored results of cfg_s --------------------------------
+ *
+ * out = fr_box_filter_rgb8(fr_colour_rows(z, iters)) without the 3 * s * s bytes per output pixel in between.  Memory-bound:
+ * 20 B (z_width 2) or 36 B (z_width 4; the low parts are skipped, not read) per sample in, 3 or 4 B per output pixel out.
+ *   - a workgroup of 256 lanes owns a tile of kCfTileW = 64 output pixels x ro output rows (ro = 4, 2, 1 for s <= 4, <= 6,
+ *     <= 8: one wave per output row), i.e. 64 s x s ro samples; it takes cf_tiles_per_group(s) tiles, a grid's width apart,
+ *     so that the 3 KB log2 table — staged only when the colour map reads it — is paid once per >= 4096 samples;
+ *   - phase 1: one sample per lane, four in flight: consecutive lanes load consecutive samples of a source row (16 B of z
+ *     as two 8-byte loads — d_z is 8-byte aligned — and 4 B of iters each; a wave never straddles two rows), colour them
+ *     with colour_of — the renders' own map — and park
+ *     the packed r | g << 8 | b << 16 in LDS at [source row][sample]: 4 s s ro 64 bytes, 16 KiB at s = 4 and 8, 18 at 6;
+ *   - phase 2, after one barrier: lane l of wave w sums the s x s block of output pixel (l, w): r and b together in the
+ *     halves of one register, g in another; the LDS reads are 16 / 8 / 4 bytes wide for s % 4 == 0 / even / odd s (a lane's
+ *     s samples of a row are contiguous and aligned to their own size).  + floor(s s / 2), then the division of
+ *     box_filter_kernel: __umulhi(2 n, ceil(2^31 / (s s)));
+ *   - RGBA leaves as one dword per lane; RGB through box_filter_kernel's staging: bytes to LDS at the destination row's
+ *     address modulo 4, then aligned dwords (lanes 0 .. 47 of the row's wave) plus < 4 head and < 4 tail bytes (lanes 48 .. 53);
+ *   - s is a template parameter (2 .. 8; s = 1 is colour_rows_kernel): every index above is a shift or a constant multiply;
+ *   - 64-bit element offsets (a kept 3840 x 2160 view at s = 4 is 2.6 GB of z); plain vector loads and stores only. */
+constexpr uint32_t kCfTileW = 64;                    /* output pixels per tile row: one wave */
+constexpr uint32_t kCfThreads = 256;
+constexpr uint32_t kCfOutPitch = 3 * kCfTileW + 16;  /* LDS bytes per staged RGB output row (3 spare + padding; a multiple of 4) */
+__host__ __device__ constexpr uint32_t cf_tile_rows(uint32_t s) { return s <= 4 ? 4u : s <= 6 ? 2u : 1u; }
+/* tiles per workgroup: at least 4096 samples behind one staging of the table */
+constexpr uint32_t cf_tiles_per_group(uint32_t s) {
+    const uint32_t per_tile = kCfTileW * s * s * cf_tile_rows(s);
+    return (4096u + per_tile - 1u) / per_tile;
+}
+
+struct cf_params {
+    const double *z;
+    const uint32_t *iters;
+    uint8_t *dst;
+    uint64_t pitch;       /* s * width: samples per source row */
+    uint32_t width, rows; /* of the output */
+    uint32_t tiles_x, n_tiles;
+    uint32_t zw, bpp;     /* doubles of z per sample (2 or 4); 3 or 4 */
+};
+
+/* kernel arguments re-read where the colour map needs them (fr_kernels.hip: FR_COLD_PARAMS; `p` is argument 0) */
+typedef const __attribute__((address_space(4))) fr_kparams *CfKArgs;
+
+struct cf_sample {
+    double re, im;
+    uint32_t iters;
+    uint32_t at; /* the sample's LDS word, ~0u = none */
+};
+
+/* sample `idx` of the tile's flattened (source row, column) grid: loaded when it lies inside the image */
+template <uint32_t S>
+__device__ __forceinline__ cf_sample cf_load(uint32_t idx, uint32_t nsx, uint32_t nsy, const cf_params &q, uint64_t k00) {
+    constexpr uint32_t SW = kCfTileW * S, N = SW * S * cf_tile_rows(S);
+    cf_sample v{0.0, 0.0, 0u, ~0u};
+    const uint32_t k = idx / SW, c = idx - k * SW;
+    if (idx < N && k < nsy && c < nsx) {
+        const uint64_t g = k00 + (uint64_t)k * q.pitch + c;
+        if (q.zw == 2u) { /* uniform */
+            v.re = q.z[2u * g];
+            v.im = q.z[2u * g + 1u];
+        } else {
+            v.re = q.z[4u * g];
+            v.im = q.z[4u * g + 2u];
+        }
+        v.iters = q.iters[g];
+        v.at = idx;
+    }
+    return v;
+}
+
+__device__ __forceinline__ void cf_colour(const cf_sample &v, const double *s_tab, uint32_t *s_px) {
+    if (v.at == ~0u) return;
+    uint8_t rgb[3] = {0, 0, 0};
+    CfKArgs kp = (CfKArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp)); /* opaque: the ~40 constants are loaded here, not held across the kernel */
+    const ColourConsts cc = make_colour_consts(*kp);
+    colour_of(cc, v.re * v.re + v.im * v.im, v.iters, s_tab, nullptr, rgb); /* pos.squared_distance(), :214 */
+    s_px[v.at] = (uint32_t)rgb[0] | ((uint32_t)rgb[1] << 8) | ((uint32_t)rgb[2] << 16);
+}
+
+template <uint32_t S>
+__global__ __launch_bounds__(kCfThreads) void colour_filter_kernel(const fr_kparams p, const cf_params q) {
+    constexpr uint32_t RO = cf_tile_rows(S), SW = kCfTileW * S, N = SW * S * RO;
+    constexpr uint32_t HALF = S * S / 2u, MAGIC = (uint32_t)(((1ull << 31) + S * S - 1u) / (S * S));
+    __shared__ double s_tab[FR_LOG2_N * 3];
+    __shared__ __attribute__((aligned(16))) uint32_t s_px[N];
+    __shared__ uint32_t s_out_words[RO * kCfOutPitch / 4u];
+    uint8_t *const s_out = reinterpret_cast<uint8_t *>(s_out_words);
+    const uint32_t tid = threadIdx.x;
+    const bool escape_algo = p.algo == 0 || p.algo == 2;
+    if (escape_algo && p.smooth) { /* uniform */
+        const double *gt = &g_log2_tab[0][0];
+        for (uint32_t k = tid; k < FR_LOG2_N * 3; k += kCfThreads) s_tab[k] = gt[k];
+    }
+    const uint32_t w = tid >> 6, l = tid & 63u; /* phase 2 and 3: output row of the tile, output pixel of the row */
+    for (uint32_t tile = blockIdx.x; tile < q.n_tiles; tile += gridDim.x) {
+        const uint32_t ty = tile / q.tiles_x, tx = tile - ty * q.tiles_x;
+        const uint32_t x0 = tx * kCfTileW, r0 = ty * RO;
+        const uint32_t nx = min(kCfTileW, q.width - x0), nr = min(RO, q.rows - r0);
+        __syncthreads(); /* the table is staged; the previous tile's rows have left s_out */
+
+        /* ---- phase 1: samples -> colours -> LDS ---- */
+        if (escape_algo) {
+            const uint64_t k00 = (uint64_t)r0 * S * q.pitch + (uint64_t)x0 * S;
+            const uint32_t nsx = nx * S, nsy = nr * S;
+            for (uint32_t base = 0; base < N; base += 4u * kCfThreads) {
+                const cf_sample v0 = cf_load<S>(base + tid, nsx, nsy, q, k00);
+                const cf_sample v1 = cf_load<S>(base + kCfThreads + tid, nsx, nsy, q, k00);
+                const cf_sample v2 = cf_load<S>(base + 2u * kCfThreads + tid, nsx, nsy, q, k00);
+                const cf_sample v3 = cf_load<S>(base + 3u * kCfThreads + tid, nsx, nsy, q, k00);
+                cf_colour(v0, s_tab, s_px);
+                cf_colour(v1, s_tab, s_px);
+                cf_colour(v2, s_tab, s_px);
+                cf_colour(v3, s_tab, s_px);
+            }
+        }
+        __syncthreads();
+
+        /* ---- phase 2: one output pixel per lane ---- */
+        const bool live = w < nr && l < nx;
+        uint8_t *drow = q.dst + ((uint64_t)(r0 + (w < nr ? w : 0u)) * q.width + x0) * q.bpp; /* the wave's output row */
+        const uint32_t dmis = q.bpp == 4u ? 0u : (uint32_t)(uintptr_t)drow & 3u;
+        if (live) {
+            uint32_t rb = HALF | HALF << 16, gg = HALF; /* r and b in the halves of one word: a sum is at most 64 * 255 + 32 */
+            if (escape_algo) {
+                for (uint32_t j = 0; j < S; j++) {
+                    const uint32_t *row = s_px + (w * S + j) * SW + l * S;
+                    if constexpr (S % 4u == 0u) {
+                        for (uint32_t i = 0; i < S; i += 4u) {
+                            const uint4 v = *reinterpret_cast<const uint4 *>(row + i);
+                            rb += (v.x & 0x00FF00FFu) + (v.y & 0x00FF00FFu) + (v.z & 0x00FF00FFu) + (v.w & 0x00FF00FFu);
+                            gg += (v.x >> 8 & 0xFFu) + (v.y >> 8 & 0xFFu) + (v.z >> 8 & 0xFFu) + (v.w >> 8 & 0xFFu);
+                        }
+                    } else if constexpr (S % 2u == 0u) {
+                        for (uint32_t i = 0; i < S; i += 2u) {
+                            const uint2 v = *reinterpret_cast<const uint2 *>(row + i);
+                            rb += (v.x & 0x00FF00FFu) + (v.y & 0x00FF00FFu);
+                            gg += (v.x >> 8 & 0xFFu) + (v.y >> 8 & 0xFFu);
+                        }
+                    } else {
+                        for (uint32_t i = 0; i < S; i++) {
+                            const uint32_t v = row[i];
+                            rb += v & 0x00FF00FFu;
+                            gg += v >> 8 & 0xFFu;
+                        }
+                    }
+                }
+            }
+            const uint32_t cr = __umulhi(2u * (rb & 0xFFFFu), MAGIC), cg = __umulhi(2u * gg, MAGIC), cb = __umulhi(2u * (rb >> 16), MAGIC);
+            if (q.bpp == 4u) {
+                reinterpret_cast<uint32_t *>(drow)[l] = cr | cg << 8 | cb << 16 | 0xFF000000u;
+            } else {
+                uint8_t *o = s_out + w * kCfOutPitch + dmis + 3u * l;
+                o[0] = (uint8_t)cr;
+                o[1] = (uint8_t)cg;
+                o[2] = (uint8_t)cb;
+            }
+        }
+        if (q.bpp == 4u) continue; /* uniform */
+        __syncthreads();
+
+        /* ---- phase 3 (RGB): wave w's staged row -> aligned dwords + head and tail bytes ---- */
+        if (w < nr) {
+            const uint32_t obytes = 3u * nx;
+            const uint32_t head = min(obytes, (4u - dmis) & 3u);
+            const uint32_t body = (obytes - head) / 4u, tail = (obytes - head) & 3u; /* body <= 48 */
+            const uint8_t *o = s_out + w * kCfOutPitch + dmis; /* o + head is 4-byte aligned */
+            if (l < body) {
+                reinterpret_cast<uint32_t *>(drow + head)[l] = reinterpret_cast<const uint32_t *>(o + head)[l];
+            } else if (l >= 48u) { /* 48 .. 53: lanes no body dword ever uses */
+                const uint32_t b = l - 48u;
+                if (b < head) drow[b] = o[b];
+                else if (b >= 3u && b - 3u < tail) drow[obytes - tail + b - 3u] = o[obytes - tail + b - 3u];
+            }
+        }
+    }
+}
+
+template <uint32_t S>
+hipError_t cf_launch(const fr_kparams &p, const cf_params &q, hipStream_t stream) {
+    const uint32_t groups = (q.n_tiles + cf_tiles_per_group(S) - 1u) / cf_tiles_per_group(S);
+    colour_filter_kernel<S><<<dim3(groups), dim3(kCfThreads), 0, stream>>>(p, q);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t fr_launch_box_filter(const void *src, uint32_t width, uint64_t rows, uint32_t s, uint32_t bpp, void *dst,
@@ -185,6 +378,43 @@ hipError_t fr_launch_box_filter(const void *src, uint32_t width, uint64_t rows, 
         const uint64_t tiles = (uint64_t)p.tiles_x * ((n + p.ro - 1) / p.ro);
         box_filter_kernel<<<dim3((uint32_t)tiles), dim3(kSsThreads), lds_bytes, stream>>>(p);
         const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t fr_launch_colour_filter(const fr_kparams &p, const double *z, uint32_t z_width, const uint32_t *iters, uint32_t width,
+                                   uint64_t rows, uint32_t s, uint32_t bpp, void *dst, hipStream_t stream) {
+    if (width == 0 || rows == 0) return hipSuccess;
+    if (s < 1 || s > FR_SS_MAX || (bpp != 3 && bpp != 4) || (z_width != 2 && z_width != 4)) return hipErrorInvalidValue;
+    if (s == 1) return fr_launch_colour_rows(p, z, z_width, iters, (size_t)width * rows, bpp, dst, stream); /* nothing to filter */
+    cf_params q;
+    q.pitch = (uint64_t)s * width;
+    q.width = width;
+    q.tiles_x = (uint32_t)(((uint64_t)width + kCfTileW - 1) / kCfTileW);
+    q.zw = z_width;
+    q.bpp = bpp;
+    const uint32_t ro = cf_tile_rows(s);
+    /* launches of at most 2^30 tiles (whole tile rows) */
+    const uint64_t rows_per_launch = std::max<uint64_t>(1, (1ull << 30) / q.tiles_x) * ro;
+    for (uint64_t ra = 0; ra < rows; ra += rows_per_launch) {
+        const uint64_t n = std::min(rows - ra, rows_per_launch);
+        const uint64_t first = ra * s * q.pitch; /* the launch's first sample */
+        q.z = z + first * z_width;
+        q.iters = iters + first;
+        q.dst = static_cast<uint8_t *>(dst) + ra * width * bpp;
+        q.rows = (uint32_t)n;
+        q.n_tiles = (uint32_t)(q.tiles_x * ((n + ro - 1) / ro));
+        hipError_t e;
+        switch (s) {
+        case 2: e = cf_launch<2>(p, q, stream); break;
+        case 3: e = cf_launch<3>(p, q, stream); break;
+        case 4: e = cf_launch<4>(p, q, stream); break;
+        case 5: e = cf_launch<5>(p, q, stream); break;
+        case 6: e = cf_launch<6>(p, q, stream); break;
+        case 7: e = cf_launch<7>(p, q, stream); break;
+        default: e = cf_launch<8>(p, q, stream); break;
+        }
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -241,19 +471,17 @@ uint64_t ss_band_rows(const SsPlan &pl, uint32_t s, size_t work_len) {
     return (b + unit - 1) / unit * unit;
 }
 
-/* Rows [y0, y1) supersampled into device memory on `stream`; arguments already checked, s >= 2, the range and the
- * width not empty.  No host synchronisation beyond what a plain device-pointer render of cfg_s has. */
-int render_ss_device(Ctx &ctx, const SsPlan &pl, int precision, const fr_imaginary *pos_lo, uint32_t s, uint32_t y0,
-                     unsigned bpp, void *d_out, void *d_work, size_t work_len, hipStream_t stream, const Opts &o) {
-    const fr_config *cs = &pl.cfg_s;
-    const uint32_t width = cs->width / s;
-    const bool deep = precision == FR_PRECISION_DD || precision == FR_PRECISION_PT;
-    const uint64_t band = ss_band_rows(pl, s, work_len);
+/* Rows [y0, y1) supersampled into device memory on `stream`: the band loop of every supersampled render.  band(ctx, ya, yb,
+ * ko, stream) is the launch of source rows [ya, yb) of cfg_s as packed r,g,b into ko.rgb — a road's row launch (fr_bla.hip:
+ * bla_rows; DESIGN.md, "3.17") with the band's rows — between the profiling events; pending_sample: a view sample to post
+ * behind the last band (-1 none).  Arguments already checked, s >= 2, the range and the width not empty.  No host
+ * synchronisation beyond what the band's launch has. */
+template <class Band>
+int render_ss_bands(Ctx &ctx, const SsPlan &pl, uint32_t s, uint32_t y0, unsigned bpp, void *d_out, void *d_work, size_t work_len,
+                    hipStream_t stream, int pending_sample, Band &&band) {
+    const uint32_t width = pl.cfg_s.width / s;
+    const uint64_t rows = ss_band_rows(pl, s, work_len);
     const uint32_t Y0 = s * y0, Y1 = (uint32_t)(Y0 + pl.src_rows);
-    Opts ob = o;
-    if (!deep) decide_kernel(ctx, cs, precision, Y0, Y1, ob, stream, true); /* ONE choice for every band, as the host path's bands */
-    const int pending_sample = ob.pending_sample;
-    ob.pending_sample = -1;
     /* profiling: the span of the whole call — the first band records the start (and the render kernel's name), the
      * later bands record nothing, the end goes behind the last filter */
     Profiling &pr = profiling();
@@ -262,16 +490,12 @@ int render_ss_device(Ctx &ctx, const SsPlan &pl, int precision, const fr_imagina
         bool was;
         ~ProfGuard() { pr.enabled = was; }
     } prof_guard{pr, pr.enabled};
+    fr_kout ko{};
+    ko.rgb = static_cast<uint8_t *>(d_work);
     int rc = FR_OK;
-    for (uint64_t ya = Y0; ya < Y1 && rc == FR_OK; ya += band) {
-        const uint32_t yb = (uint32_t)std::min<uint64_t>(ya + band, Y1);
-        if (deep) {
-            rc = render_deep_device(ctx, precision, cs, Centre{pos_lo, nullptr}, o, (uint32_t)ya, yb, 3, d_work, stream);
-        } else {
-            fr_kparams p;
-            rows_params(cs, ob, (uint32_t)ya, yb, 3, p);
-            rc = render_device(ctx, cs, p, precision, ob, d_work, stream);
-        }
+    for (uint64_t ya = Y0; ya < Y1 && rc == FR_OK; ya += rows) {
+        const uint32_t yb = (uint32_t)std::min<uint64_t>(ya + rows, Y1);
+        rc = band(ctx, (uint32_t)ya, yb, ko, stream);
         if (rc != FR_OK) break;
         pr.enabled = false;
         uint8_t *dst = static_cast<uint8_t *>(d_out) + (uint64_t)(((uint32_t)ya - Y0) / s) * width * bpp;
@@ -281,6 +505,25 @@ int render_ss_device(Ctx &ctx, const SsPlan &pl, int precision, const fr_imagina
     ctx.post_sample(pending_sample, stream); /* behind the last band */
     if (rc == FR_OK && prof_guard.was && pr.have) HIP_TRY(hipEventRecord(pr.e1, stream));
     return rc;
+}
+
+/* the bands of fr_render_rows_ss(_device): the precision's own row render */
+int render_ss_device(Ctx &ctx, const SsPlan &pl, int precision, const fr_imaginary *pos_lo, uint32_t s, uint32_t y0,
+                     unsigned bpp, void *d_out, void *d_work, size_t work_len, hipStream_t stream, const Opts &o) {
+    const fr_config *cs = &pl.cfg_s;
+    const bool deep = precision == FR_PRECISION_DD || precision == FR_PRECISION_PT;
+    Opts ob = o;
+    if (!deep) /* ONE choice for every band, as the host path's bands */
+        decide_kernel(ctx, cs, precision, s * y0, (uint32_t)(s * y0 + pl.src_rows), ob, stream, true);
+    const int pending_sample = ob.pending_sample;
+    ob.pending_sample = -1;
+    return render_ss_bands(ctx, pl, s, y0, bpp, d_out, d_work, work_len, stream, pending_sample,
+                           [&](Ctx &c, uint32_t ya, uint32_t yb, const fr_kout &ko, hipStream_t st) {
+                               if (deep) return render_deep_device(c, precision, cs, Centre{pos_lo, nullptr}, o, ya, yb, 3, ko.rgb, st);
+                               fr_kparams p;
+                               rows_params(cs, ob, ya, yb, 3, p);
+                               return render_device(c, cs, p, precision, ob, ko.rgb, st);
+                           });
 }
 
 /* everything fr_render_rows_ss(_device) check before any device work; fills pl and o */
@@ -301,6 +544,70 @@ int box_filter_check(uint32_t width, uint32_t rows, uint32_t s, int channels) {
     if ((uint64_t)width * s > 0xFFFFFFFFull || (uint64_t)rows * s > 0xFFFFFFFFull)
         return fail(FR_ERR_INVALID_ARGUMENT, "supersample * width and supersample * rows must fit in 32 bits");
     return check_channels(channels);
+}
+
+/* ---- the deep roads, supersampled (include/fractal_hip.h, "supersampled rendering on the deep roads") ------------------- */
+
+/* what fr_render_rows_ss_pt(_device) have checked: the plan, the road's centre and its resolved bits */
+struct SsRoad {
+    SsPlan pl;
+    Centre c;
+    int road, bits;
+    Opts o; /* PLAIN: render_deep_device's */
+    /* rows [ya, yb) of `cfg` (cfg_s for a band, the caller's cfg for s = 1) on the road */
+    int rows(Ctx &ctx, const fr_config *cfg, uint32_t ya, uint32_t yb, unsigned channels, const fr_kout &ko, hipStream_t stream) const {
+        if (road == FR_PT_ROAD_BLA) return bla_render_rows(ctx, cfg, c, bits, ya, yb, channels, ko, stream);
+        if (road == FR_PT_ROAD_SCALED) return scaled_render_rows(ctx, cfg, c, bits, ya, yb, channels, ko, stream);
+        return render_deep_device(ctx, FR_PRECISION_PT, cfg, c, o, ya, yb, channels, ko.rgb, stream);
+    }
+};
+
+/* everything fr_render_rows_ss_pt(_device) check before any device work: the sizes, then the road's own domain on cfg_s */
+int ss_road_check(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits, uint32_t s,
+                  uint32_t y0, uint32_t y1, int channels, SsRoad &r) {
+    int rc = ss_plan(cfg, s, y0, y1, r.pl);
+    if (rc == FR_OK) rc = check_channels(channels);
+    if (rc != FR_OK) return rc;
+    const fr_config *cs = &r.pl.cfg_s;
+    const uint32_t Y0 = s * y0, Y1 = (uint32_t)(Y0 + r.pl.src_rows);
+    r.road = road;
+    r.bits = bits;
+    switch (road) {
+    case FR_PT_ROAD_PLAIN:
+        if (bits != 0) return fail(FR_ERR_INVALID_ARGUMENT, "bits must be 0 with FR_PT_ROAD_PLAIN: the plain loop has no table");
+        if (centre && pos_lo) return fail(FR_ERR_INVALID_ARGUMENT, "pos_lo must be NULL when a wide centre is given");
+        r.c = Centre{pos_lo, centre};
+        rc = r.c.check(cs, FR_PRECISION_PT);
+        if (rc == FR_OK) rc = resolve_opts(nullptr, r.o);
+        return rc;
+    case FR_PT_ROAD_BLA:
+        r.c = Centre{pos_lo, centre};
+        return bla_check(cs, r.c, r.bits, Y0, Y1);
+    case FR_PT_ROAD_SCALED:
+        if (pos_lo) return fail(FR_ERR_INVALID_ARGUMENT, "SCALED PT: pos_lo must be NULL, the centre is the wide centre");
+        r.c = Centre{nullptr, centre, true};
+        return scaled_check(cs, r.c, r.bits, Y0, Y1);
+    default:
+        return fail(FR_ERR_INVALID_ARGUMENT, "road must be FR_PT_ROAD_PLAIN (0), FR_PT_ROAD_BLA (1) or FR_PT_ROAD_SCALED (2)");
+    }
+}
+
+/* rows [y0, y1) of cfg on the road into ko.rgb: s = 1 the road's plain render, byte for byte; else its bands of cfg_s through
+ * the workspace, each filtered into place */
+int ss_road_rows(Ctx &ctx, const SsRoad &r, const fr_config *cfg, uint32_t s, uint32_t y0, uint32_t y1, unsigned bpp, const fr_kout &ko,
+                 void *d_work, size_t work_len, hipStream_t stream) {
+    if (s == 1) return r.rows(ctx, cfg, y0, y1, bpp, ko, stream);
+    return render_ss_bands(ctx, r.pl, s, y0, bpp, ko.rgb, d_work, work_len, stream, -1,
+                           [&](Ctx &c, uint32_t ya, uint32_t yb, const fr_kout &band, hipStream_t st) {
+                               return r.rows(c, &r.pl.cfg_s, ya, yb, 3, band, st);
+                           });
+}
+
+/* the domain of fr_colour_rows_ss_device / fr_colour_ss_rgb8 short of the buffers */
+int colour_ss_check(const fr_config *cfg, int z_width, uint32_t width, uint32_t rows, uint32_t s, int channels) {
+    if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (z_width != 2 && z_width != 4) return fail(FR_ERR_INVALID_ARGUMENT, "z_width must be 2 (re, im) or 4 (re.hi, re.lo, im.hi, im.lo)");
+    return box_filter_check(width, rows, s, channels);
 }
 
 }  // namespace
@@ -408,6 +715,85 @@ int fr_box_filter_rgb8(const uint8_t *src, uint32_t width, uint32_t rows, uint32
     if (rc != FR_OK) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->ss_work.ptr, src, src_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(fr_launch_box_filter(ctx->ss_work.ptr, width, rows, supersample, (uint32_t)channels, ctx->rgb.ptr, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FR_OK;
+}
+
+int fr_render_rows_ss_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                                uint32_t supersample, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len,
+                                void *d_work, size_t work_len, void *hip_stream) {
+    SsRoad r;
+    const int rc = ss_road_check(cfg, pos_lo, centre, road, bits, supersample, y0, y1, channels, r);
+    if (rc != FR_OK) return rc;
+    if (supersample > 1 && (size_t)cfg->width * (size_t)(y1 - y0) != 0) { /* the workspace, then rgb_rows_device's buffer rules */
+        if (work_len < r.pl.min_bytes) return fail(FR_ERR_BUFFER_TOO_SMALL, "work_len < min_bytes of fr_ss_workspace_bytes");
+        if (!d_work) return fail(FR_ERR_INVALID_ARGUMENT, "d_work is NULL");
+    }
+    return rgb_rows_device(cfg, y0, y1, channels, d_out, out_len, hip_stream, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
+        return ss_road_rows(ctx, r, cfg, supersample, y0, y1, (unsigned)channels, ko, d_work, work_len, stream);
+    });
+}
+
+int fr_render_rows_ss_pt(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                         uint32_t supersample, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len) {
+    SsRoad r;
+    const int rc = ss_road_check(cfg, pos_lo, centre, road, bits, supersample, y0, y1, channels, r);
+    if (rc != FR_OK) return rc;
+    const size_t work_len = supersample > 1 ? std::max(r.pl.min_bytes, std::min(r.pl.best_bytes, kSsHostWorkCap)) : 0;
+    return rgb_rows_host(cfg, y0, y1, channels, out, out_len, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
+        int rc = ctx.reserve(ctx.ss_work, work_len);
+        if (rc != FR_OK) return rc;
+        rc = ss_road_rows(ctx, r, cfg, supersample, y0, y1, (unsigned)channels, ko, ctx.ss_work.ptr, work_len, stream);
+        if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
+        return rc;
+    });
+}
+
+int fr_colour_rows_ss_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, uint32_t width, uint32_t rows,
+                             uint32_t supersample, int channels, void *d_out, size_t out_len, void *hip_stream) {
+    const int rc = colour_ss_check(cfg, z_width, width, rows, supersample, channels);
+    if (rc != FR_OK) return rc;
+    const size_t need = (size_t)channels * width * (size_t)rows;
+    if (need == 0) return FR_OK;
+    if (!d_z || !d_iters || !d_out) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array (d_z, d_iters, d_out)");
+    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*rows");
+    if ((reinterpret_cast<uintptr_t>(d_z) & 7u) || (reinterpret_cast<uintptr_t>(d_iters) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "d_z must be 8-byte aligned and d_iters 4-byte aligned");
+    if (channels == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "RGBA8 output (d_out) must be 4-byte aligned");
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    HIP_TRY(fr_launch_colour_filter(p, static_cast<const double *>(d_z), (uint32_t)z_width, static_cast<const uint32_t *>(d_iters), width,
+                                    rows, supersample, (uint32_t)channels, d_out, static_cast<hipStream_t>(hip_stream)));
+    return FR_OK;
+}
+
+int fr_colour_ss_rgb8(const fr_config *cfg, const double *z, int z_width, const uint32_t *iters, uint32_t width, uint32_t rows,
+                      uint32_t supersample, int channels, uint8_t *out, size_t out_len) {
+    int rc = colour_ss_check(cfg, z_width, width, rows, supersample, channels);
+    if (rc != FR_OK) return rc;
+    const size_t need = (size_t)channels * width * (size_t)rows;
+    if (need == 0) return FR_OK;
+    if (!z || !iters || !out) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array (z, iters, out)");
+    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*rows");
+    const size_t n = (size_t)supersample * width * ((size_t)supersample * rows);
+    const size_t zb = n * (size_t)z_width * sizeof(double), ib = n * sizeof(uint32_t);
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = ctx->reserve(ctx->z, zb);
+    if (rc == FR_OK) rc = ctx->reserve(ctx->iters, ib);
+    if (rc == FR_OK) rc = ctx->reserve(ctx->rgb, need);
+    if (rc != FR_OK) return rc;
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    HIP_TRY(hipMemcpyAsync(ctx->z.ptr, z, zb, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->iters.ptr, iters, ib, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(fr_launch_colour_filter(p, static_cast<const double *>(ctx->z.ptr), (uint32_t)z_width, static_cast<const uint32_t *>(ctx->iters.ptr),
+                                    width, rows, supersample, (uint32_t)channels, ctx->rgb.ptr, ctx->stream));
     HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FR_OK;

@@ -278,5 +278,37 @@ inline void extend_pt_rows_device(const Config &config, const fr_wide_centre &ce
     check(fr_escape_extend_pt_scaled_device(&config, &centre, 0, config.height, from_iterations, d_z, d_iters, d_w, d_m, hip_stream));
 }
 
+
+// ---- anti-aliased deep views (include/fractal_hip.h, "supersampled rendering on the deep roads") ------------------------------
+// get_image on a deep road with supersample x supersample samples per pixel, box-filtered on the device: the forms above with a
+// supersample factor behind them (1 .. FR_SS_MAX; 1 is the form without it, byte for byte).  One GPU.
+inline std::vector<RGB> get_image_ss_pt(const Config &config, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                                        uint32_t supersample) {
+    std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
+    check(fr_render_rows_ss_pt(&config, pos_lo, centre, road, bits, supersample, 0, config.height, 3,
+                               reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB)));
+    return image;
+}
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, uint32_t supersample) {
+    return get_image_ss_pt(config, nullptr, &centre, FR_PT_ROAD_PLAIN, 0, supersample);
+}
+inline std::vector<RGB> get_image(const Config &config, Bla bla, const fr_imaginary *pos_lo, uint32_t supersample) {
+    return get_image_ss_pt(config, pos_lo, nullptr, FR_PT_ROAD_BLA, bla.bits, supersample);
+}
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Bla bla, uint32_t supersample) {
+    return get_image_ss_pt(config, nullptr, &centre, FR_PT_ROAD_BLA, bla.bits, supersample);
+}
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Scaled scaled, uint32_t supersample) {
+    return get_image_ss_pt(config, nullptr, &centre, FR_PT_ROAD_SCALED, scaled.bits, supersample);
+}
+// A kept anti-aliased view is a kept view of the config with width and height times supersample: the escape / state / extend
+// wrappers above on that config, and this to colour it — colour map and box filter in one kernel, no RGB workspace.
+// channels 3 (r,g,b) or 4 (r,g,b,255; d_out 4-byte aligned); config is the OUTPUT's (width x height).
+inline void colour_rows_ss_device(const Config &config, const void *d_z, const void *d_iters, uint32_t supersample, void *d_out,
+                                  int channels = 4, void *hip_stream = nullptr, int z_width = 2) {
+    check(fr_colour_rows_ss_device(&config, d_z, z_width, d_iters, config.width, config.height, supersample, channels, d_out,
+                                   static_cast<size_t>(channels) * config.width * config.height, hip_stream));
+}
+
 }  // namespace fractal
 #endif

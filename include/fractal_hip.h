@@ -196,8 +196,8 @@ typedef struct fr_config {
  * the squares of the rebase test, |dz|^2 of an off that is 2^-53 of the pixel spacing, leave f64's normal range, and a scaled
  * pixel loop is not part of this definition; and F >= e + 64, where max(|scale.re|, |scale.im|) = f 2^e with 0.5 <= f < 1:
  * the orbit carries 64 guard bits beyond the pixel spacing.  A centre too coarse for its scale is the caller's mistake and
- * is refused, not rendered as a flat image.  One device; supersampling, block-cyclic and multi-device renders do not take
- * a wide centre.
+ * is refused, not rendered as a flat image.  One device; block-cyclic and multi-device renders do not take a wide centre, nor does
+ * fr_render_rows_ss: supersampling with a wide centre is fr_render_rows_ss_pt(_device).
  *
  * BLA-PT (the fr_*_pt_bla calls below): PT with bilinear-approximation skips.  While a pixel's offset dz from the reference
  * orbit is far smaller than the orbit itself, the step dz' = (2 X_m + dz) dz + dc is linear in (dz, dc) to below f64 rounding,
@@ -251,7 +251,8 @@ typedef struct fr_config {
  * Domain: PT's, or WIDE PT's with a centre; bits 0 (= FR_BLA_DEFAULT_BITS) or 24 .. 53; iterations <= FR_PT_MAX_ITERATIONS,
  * which bounds the tables: on the device an orbit's table holds fewer than `last` entries of 40 B (Mandelbrot) or 24 B (Julia,
  * two orbits), beside the orbit's own 16 B per entry — at most 640 MiB (768 MiB for Julia's two) at the cap.  One device;
- * supersampling, block-cyclic and multi-device renders do not take BLA-PT, nor do the resumable-state and extend calls: the
+ * block-cyclic and multi-device renders do not take BLA-PT (supersampling does, through fr_render_rows_ss_pt(_device) with
+ * FR_PT_ROAD_BLA, not through fr_render_rows_ss), nor do the resumable-state and extend calls: the
  * condition i + 2^k <= iterations makes a run at cap N no prefix of the run at cap M, so there is no state to continue, and
  * fr_escape_extend(_device) and fr_escape_extend_pt(_device) have no BLA form.
  *
@@ -305,8 +306,9 @@ typedef struct fr_config {
  * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): WIDE PT's, with a centre REQUIRED, and with
  * these changes: limit <= 2^20 (the default, 65536, is inside); min(|scale.re|, |scale.im|) >= 2^-32 max(|scale.re|,
  * |scale.im|); no 2^440 rule — what bounds the scale is F >= e + 64 with n <= 16, so e <= 952 and |scale| < 2^952; bits = -1
- * (no table: the plain scaled loop), 0 (= FR_BLA_DEFAULT_BITS) or 24 .. 53.  One device.  OUT OF SCOPE: supersampling,
- * block-cyclic and multi-device renders do not take SCALED PT.  Its plain loop (bits = -1) has a resumable state and an extend
+ * (no table: the plain scaled loop), 0 (= FR_BLA_DEFAULT_BITS) or 24 .. 53.  One device.  OUT OF SCOPE: block-cyclic and
+ * multi-device renders do not take SCALED PT; supersampling takes it through fr_render_rows_ss_pt(_device) with
+ * FR_PT_ROAD_SCALED, not through fr_render_rows_ss.  Its plain loop (bits = -1) has a resumable state and an extend
  * form, RESUMABLE SCALED PT below; its table form (bits >= 0) has neither, for BLA-PT's reason: the condition
  * i + 2^k <= iterations makes a run at cap N no prefix of the run at cap M.  A state written by the fr_*_pt_wide_state calls is
  * no input of the scaled extension: it holds dz where the scaled state holds w.
@@ -861,6 +863,60 @@ int fr_escape_rows_pt_scaled_state(const fr_config *cfg, const fr_wide_centre *c
                                    uint32_t *iters, double *w, uint32_t *m);
 int fr_escape_extend_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, uint32_t from_iterations,
                                double *z, uint32_t *iters, double *w, uint32_t *m);
+
+/* ---- supersampled rendering on the deep roads: WIDE PT, BLA-PT, SCALED PT --------------------------------------- */
+
+/* fr_render_rows_ss(_device) above take (precision, pos_lo) only; these two take the deep roads' own arguments.  DEFINITION,
+ * for supersample = s, 1 <= s <= FR_SS_MAX — the "supersampled rendering" block's, word for word, with H per road:
+ *   cfg_s = cfg with width * s and height * s, every other field unchanged;
+ *   H     = the image of cfg_s on the road:
+ *             FR_PT_ROAD_PLAIN, centre == NULL   the bytes of fr_render_rows_pt(cfg_s, pos_lo, ...) — this case equals
+ *                                                fr_render_rows_ss with FR_PRECISION_PT, byte for byte; pos_lo optional,
+ *                                                bits must be 0;
+ *             FR_PT_ROAD_PLAIN, centre != NULL   fr_render_rows_pt_wide(cfg_s, centre, ...); pos_lo must be NULL, bits 0;
+ *             FR_PT_ROAD_BLA                     fr_render_rows_pt_bla(cfg_s, pos_lo, centre, bits, ...); pos_lo / centre as
+ *                                                BLA-PT takes them, bits 0 or 24 .. 53;
+ *             FR_PT_ROAD_SCALED                  fr_render_rows_pt_scaled(cfg_s, centre, bits, ...); centre required, pos_lo
+ *                                                NULL, bits -1, 0 or 24 .. 53;
+ *   out(X, Y, c) = (sum over j < s, i < s of H(s*X + i, s*Y + j, c) + floor(s*s / 2)) / (s*s)
+ *           in integer arithmetic, truncating (the sums fit in 16 bits); with 4 channels alpha is 255.
+ * s = 1 is the road's plain render, byte for byte.  Algo::BarnsleyFern stays black.
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): s in 1 .. FR_SS_MAX; s * width and s * height
+ * fit in 32 bits; road in 0 .. 2; channels 3 or 4; the road's own domain ON cfg_s, checked by the code its plain calls run —
+ * D and Dw are taken over the whole image of cfg_s, as the definition of H says, and the F >= e + 64 rule reads cfg's scale,
+ * which cfg_s shares.
+ * Buffers: exactly fr_render_rows_ss(_device)'s — fr_ss_workspace_bytes serves these calls too (it depends on cfg, s and the
+ * rows only); work_len under *min_bytes or a short out_len give FR_ERR_BUFFER_TOO_SMALL; RGBA output is 4-byte aligned;
+ * d_work NULL / 0 for s = 1; y0 == y1 is a no-op without a device.
+ * The device form is asynchronous on `hip_stream`, allocates nothing and takes no lock beyond what the road's plain device
+ * call takes (the orbit / table cache): the orbit — and for BLA and SCALED-with-table the table — is computed and uploaded by
+ * the first band and served to the others (the caches are keyed by the view, not by the rows).  The host form uses the
+ * context's scratch (workspace at most 256 MiB) and one device-to-host copy of the small image.  With profiling on,
+ * fr_last_kernel_name reports the road's kernel and fr_last_kernel_ms the span from the first band's kernel to the last
+ * filter. */
+typedef enum fr_pt_road { FR_PT_ROAD_PLAIN = 0, FR_PT_ROAD_BLA = 1, FR_PT_ROAD_SCALED = 2 } fr_pt_road;
+int fr_render_rows_ss_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                                uint32_t supersample, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len,
+                                void *d_work, size_t work_len, void *hip_stream);
+int fr_render_rows_ss_pt(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                         uint32_t supersample, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len);
+
+/* A KEPT anti-aliased view is a kept view of cfg_s: (z, iters) of the s times larger image in DEVICE memory, written by any
+ * fr_escape_rows*_device call for cfg_s on any road and kept current by the extend calls.  This colours and filters it in ONE
+ * kernel, with no RGB workspace (the two-call composition needs 3 * s * s bytes per output pixel).  DEFINITION: the arrays
+ * hold s * rows rows of s * width samples, k = Y * (s * width) + X; then
+ *   out = fr_box_filter_rgb8(fr_colour_rows(cfg, z, z_width, iters, n = s*s * width * rows), width, rows, s, channels),
+ * byte for byte.  cfg contributes only what the colour map reads (iterations, stable_limit, exposure, inside, smooth, the
+ * colours, algo); an algorithm without orbits gives black; s = 1 is fr_colour_rows_device.
+ * Domain: z_width 2 or 4 (colour on the hi parts); channels 3 or 4 (RGBA output 4-byte aligned); s in 1 .. FR_SS_MAX with
+ * s * width and s * rows in 32 bits; d_z 8-byte aligned, d_iters 4-byte aligned; out_len >= channels * width * rows
+ * (FR_ERR_BUFFER_TOO_SMALL); an empty output (width or rows 0) is a no-op without a device.  The device form is asynchronous
+ * on `hip_stream`, allocates nothing and takes no lock.  fr_colour_ss_rgb8: the same over HOST arrays (upload to context
+ * scratch, launch, download, synchronise, as fr_colour_rgb8 does). */
+int fr_colour_rows_ss_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, uint32_t width, uint32_t rows,
+                             uint32_t supersample, int channels, void *d_out, size_t out_len, void *hip_stream);
+int fr_colour_ss_rgb8(const fr_config *cfg, const double *z, int z_width, const uint32_t *iters, uint32_t width, uint32_t rows,
+                      uint32_t supersample, int channels, uint8_t *out, size_t out_len);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 
