@@ -35,6 +35,7 @@ __all__ = [
     "WideCentre", "reference_orbit_wide",
     "bla_table", "bla_count", "bla_cache", "BLA_DEFAULT_BITS",
     "get_image_ss_pt", "colour_rows_ss_device", "colour_image_ss",
+    "ViewStats", "view_stats", "view_stats_device", "stats_percentile", "auto_exposure", "get_image_auto",
 ]
 
 
@@ -732,6 +733,76 @@ def colour_image(config, z, iters):
                                       out.nbytes)
     )
     return out
+
+
+class ViewStats(_native.fr_view_stats):
+    """fr_view_stats (include/fractal_hip.h, "statistics of a kept view"): n, stable, capped, escaped, sum_iters, min_iters,
+    max_iters, shift, and hist, the 1024 bins of the escape indices of the escaped pixels."""
+
+    def histogram(self):
+        """hist as a numpy uint64 [1024] (a copy)"""
+        return np.frombuffer(self.hist, dtype=np.uint64).copy()
+
+    @classmethod
+    def from_bytes(cls, raw):
+        """the record a device buffer held, e.g. the 8248 bytes view_stats_device wrote"""
+        return cls.from_buffer_copy(bytes(raw))
+
+
+def view_stats(config, z, iters):
+    """fr_view_stats over numpy arrays: z float64 [..., 2] (or [..., 4]: DD with its low parts, read on the hi parts) and
+    iters uint32 [...] -> ViewStats, reduced on the device; 8 KB come back.  Only config.iterations and config.stable_limit
+    are read."""
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    iters = np.ascontiguousarray(iters, dtype=np.uint32)
+    if z.ndim < 1 or z.shape[:-1] != iters.shape or z.shape[-1] not in (2, 4):
+        raise ValueError("z must be [..., 2 or 4] and iters [...]")
+    st = ViewStats()
+    _native.check(_native.load().fr_view_stats(C.byref(config), z.ctypes.data if iters.size else None, z.shape[-1],
+                                               iters.ctypes.data if iters.size else None, iters.size, C.byref(st)))
+    return st
+
+
+def view_stats_device(config, z_ptr, iters_ptr, n, stats_ptr, z_width=2, stream=None):
+    """fr_view_stats_device: the statistics of n stored results in DEVICE memory into the 8248 bytes at stats_ptr (device
+    memory, 8-byte aligned, overwritten whatever they held), asynchronously on `stream`; ViewStats.from_bytes reads them once
+    they are on the host."""
+    _native.check(_native.load().fr_view_stats_device(C.byref(config), z_ptr or None, int(z_width), iters_ptr or None, int(n),
+                                                      stats_ptr or None, _stream(stream)))
+
+
+def stats_percentile(stats, p):
+    """fr_stats_percentile (host only): the escape index at quantile p in [0, 1] of the escaped pixels; 0 when none escaped"""
+    out = C.c_uint32(0)
+    _native.check(_native.load().fr_stats_percentile(C.byref(stats), float(p), C.byref(out)))
+    return out.value
+
+
+def auto_exposure(config, stats, percentile=0.99):
+    """fr_auto_exposure (host only): the exposure at which an escaped pixel at that percentile of the escape indices gets the
+    full primary colour, config.iterations / max(percentile index, 1); config.exposure when no pixel escaped.  0.99 is a
+    presentation default — a lone pixel beside a minibrot should not darken the frame; 1.0 takes the maximum."""
+    out = C.c_double(0.0)
+    _native.check(_native.load().fr_auto_exposure(C.byref(config), C.byref(stats), float(percentile), C.byref(out)))
+    return out.value
+
+
+def get_image_auto(config, percentile=0.99, precision=Precision.F64, pos_lo=None, centre=None, bla=None, scaled=False, supersample=1):
+    """get_image at the exposure the view's own escape indices call for: (uint8 [height, width, 3], exposure).  escape_rows
+    on the road the keywords select (of the supersample times larger config when supersample > 1), view_stats over the
+    result, auto_exposure, then colour_image / colour_image_ss with config's clone carrying that exposure: the reference's
+    colour map, byte for byte the render of that clone.  config itself is left alone."""
+    s = int(supersample)
+    if not 1 <= s <= SS_MAX:
+        raise ValueError("supersample is 1 .. %d" % SS_MAX)
+    big = config.clone()
+    big.width, big.height = config.width * s, config.height * s
+    z, it = escape_rows(big, precision=precision, pos_lo=pos_lo, centre=centre, bla=bla, scaled=scaled)
+    exposure = auto_exposure(config, view_stats(big, z, it), percentile)
+    shown = config.clone()
+    shown.exposure = exposure
+    image = colour_image(shown, z, it) if s == 1 else colour_image_ss(shown, z, it, s)
+    return image, exposure
 
 
 def count_iterations(config, y0=0, y1=None, sx=1, sy=1, precision=Precision.F64):

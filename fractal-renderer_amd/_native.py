@@ -114,6 +114,26 @@ class fr_wide_centre(C.Structure):
     _fields_ = [("n_words", C.c_uint32), ("re", C.POINTER(C.c_uint64)), ("im", C.POINTER(C.c_uint64))]
 
 
+FR_STATS_BINS = 1024
+
+
+class fr_view_stats(C.Structure):
+    """include/fractal_hip.h fr_view_stats: the escape-index statistics of a kept view (sizeof == 8248)."""
+
+    _fields_ = [
+        ("n", C.c_uint64),
+        ("stable", C.c_uint64),
+        ("capped", C.c_uint64),
+        ("escaped", C.c_uint64),
+        ("sum_iters", C.c_uint64),
+        ("min_iters", C.c_uint32),
+        ("max_iters", C.c_uint32),
+        ("shift", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("hist", C.c_uint64 * FR_STATS_BINS),
+    ]
+
+
 FR_WIDE_MAX_WORDS = 16
 FR_BLA_DEFAULT_BITS = 40
 FR_PT_ROAD_PLAIN, FR_PT_ROAD_BLA, FR_PT_ROAD_SCALED = 0, 1, 2  # fr_pt_road
@@ -376,6 +396,11 @@ PROTOTYPES = {
         C.c_int,
         [C.POINTER(fr_config), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],
     ),
+    "fr_view_stats_device": (
+        C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "fr_view_stats": (C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(fr_view_stats)]),
+    "fr_stats_percentile": (C.c_int, [C.POINTER(fr_view_stats), C.c_double, C.POINTER(C.c_uint32)]),
+    "fr_auto_exposure": (C.c_int, [C.POINTER(fr_config), C.POINTER(fr_view_stats), C.c_double, C.POINTER(C.c_double)]),
     "fr_count_iterations": (
         C.c_int,
         [C.POINTER(fr_config), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),

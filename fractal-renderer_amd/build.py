@@ -16,8 +16,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libfractal_hip.so")
 ID_PATH = LIB_PATH + ".id"
-# the files that hold the escape-time kernels: tools that want their ISA compile these
-KERNEL_SOURCES = ["fr_kernels.hip", "fr_bla.hip", "fr_scaled.hip"]
+# the files that hold the escape-time kernels and the view statistics: tools that want their ISA compile these
+KERNEL_SOURCES = ["fr_kernels.hip", "fr_bla.hip", "fr_scaled.hip", "fr_stats.hip"]
 SOURCES = KERNEL_SOURCES + ["fr_dispatch.hip", "fr_api.hip", "fr_host.hip", "fr_multi.hip", "fr_fern.hip",
                             "fr_dd.hip", "fr_pt.hip", "fr_wide.hip", "fr_ss.hip"]
 DEPS = SOURCES + ["fr_kernels.h", "fr_launch.h", "fr_ctx.h", "fr_wide.h", "fr_bla.h", "fr_math.h", "fr_colour.h", "fr_log2_table.inc",

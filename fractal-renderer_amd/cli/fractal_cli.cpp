@@ -15,6 +15,11 @@
 // --scaled beside --perturbation (SCALED PT: the pixel loop that carries its offsets scaled by the view's exponent, so scales
 // past 2^440 render, up to just under 2^952; it combines with --bla — include/fractal_hip.h, "SCALED PT");
 // --supersample N (N x N samples per pixel, box-filtered on the device; with --perturbation, --bla and --scaled too);
+// --auto-exposure [P] (the exposure is chosen from the view's own escape indices: the one at which an escaped pixel at
+// percentile P of them, default 0.99, gets the full primary colour — include/fractal_hip.h, "statistics of a kept view"; a
+// following number within [0, 1] written with a '.' or an exponent is P (0.5, 1.0 — a bare 0 or 1 is a <width>), or write
+// --auto-exposure=P; every single-device road above, not with -e, more than
+// one device or -a fern; the chosen exposure is printed unless --quiet);
 // for -a fern: --threads N (the rayon thread count being stood in for; default: this machine's hardware
 // threads, what rayon would use) and --seed N (default: from the OS, as the reference seeds from entropy).
 // Not handled here (by design): --gui, --open.
@@ -75,6 +80,8 @@ int main(int argc, char **argv) {
     std::optional<std::string> iterations, pos_x, scale_x, scale_y, primary, secondary, julia_re, julia_im, devices, threads_s,
         seed_s, supersample_s;
     bool disable_inside = false, unsmooth = false, f32 = false, quiet = false, perturbation = false, bla = false, scaled = false;
+    bool exposure_given = false, auto_exposure_on = false;
+    double auto_p = 0.99;
     int bla_bits = 0;
     std::vector<std::string> positionals;
 
@@ -92,7 +99,26 @@ int main(int argc, char **argv) {
         else if (a == "--scale-x") scale_x = value(i, "--scale-x");
         else if (a == "--scale-y") scale_y = value(i, "--scale-y");
         else if (a == "-s" || a == "--scale") scale = value(i, "-s");
-        else if (a == "-e" || a == "--exposure") exposure = value(i, "-e");
+        else if (a == "-e" || a == "--exposure") {
+            exposure = value(i, "-e");
+            exposure_given = true;
+        }
+        else if (a == "--auto-exposure") { // a following 0.5 or 1.0 is the percentile; a bare integer is a <width>
+            auto_exposure_on = true;
+            if (i + 1 < argc && std::strpbrk(argv[i + 1], ".eE")) {
+                char *end = nullptr;
+                const double v = std::strtod(argv[i + 1], &end);
+                if (end != argv[i + 1] && *end == '\0' && v >= 0.0 && v <= 1.0) {
+                    auto_p = v;
+                    i++;
+                }
+            }
+        }
+        else if (a.rfind("--auto-exposure=", 0) == 0) {
+            auto_exposure_on = true;
+            auto_p = to_f64(a.substr(16), "--auto-exposure");
+            if (!(auto_p >= 0.0 && auto_p <= 1.0)) die("--auto-exposure takes a percentile within [0, 1]");
+        }
         else if (a == "--primary-color") primary = value(i, "--primary-color");
         else if (a == "--secondary-color") secondary = value(i, "--secondary-color");
         else if (a == "-d" || a == "--disable-inside") disable_inside = true;
@@ -138,6 +164,10 @@ int main(int argc, char **argv) {
         die("--perturbation does not combine with --f32, --devices or -a fern");
     if (bla && !perturbation) die("--bla needs --perturbation");
     if (scaled && !perturbation) die("--scaled needs --perturbation");
+    if (auto_exposure_on && exposure_given) die("--auto-exposure chooses the exposure: it does not combine with -e / --exposure");
+    if (auto_exposure_on && algo == Algo::BarnsleyFern) die("--auto-exposure does not apply to -a fern: the fern has no escape indices");
+    if (auto_exposure_on && devices && devices->find(',') != std::string::npos)
+        die("--auto-exposure runs on one device: the statistics cover one array, not the pieces of --devices");
 
     // src/lib.rs:207-226
     Config cfg = Config::make(algo);
@@ -196,6 +226,22 @@ int main(int argc, char **argv) {
                 seed = (static_cast<uint64_t>(rd()) << 32) | rd();
             }
             image = get_image_fern(cfg, threads, seed);
+        } else if (auto_exposure_on) {
+            // the road's escape indices, their statistics on the device, then the colour map at the exposure they call for
+            const uint32_t ss = supersample_s ? to_u32(*supersample_s, "--supersample") : 1;
+            double chosen = 0.0;
+            if (perturbation) {
+                const WideCentre centre = WideCentre::from_decimal(pos_x_s, pos_y, WideCentre::words_for_scale(cfg.scale.re, cfg.scale.im));
+                const fr_wide_centre wc = centre.c();
+                image = get_image_auto(cfg, ss, auto_p, &chosen, [&](const Config &big, double *z, uint32_t *iters) {
+                    if (scaled) check(fr_escape_rows_pt_scaled(&big, &wc, bla ? bla_bits : -1, 0, big.height, z, iters));
+                    else if (bla) check(fr_escape_rows_pt_bla(&big, nullptr, &wc, bla_bits, 0, big.height, z, iters));
+                    else check(fr_escape_rows_pt_wide(&big, &wc, 0, big.height, z, iters));
+                });
+            } else {
+                image = get_image_auto(cfg, f32 ? FR_PRECISION_F32 : FR_PRECISION_F64, auto_p, ss, &chosen);
+            }
+            if (!quiet) std::printf("auto-exposure %.17g (percentile %g of the escape indices)\n", chosen, auto_p);
         } else if (perturbation) {
             // the centre keeps every digit of -x / -y; cfg.pos (their f64 roundings) is not read
             const WideCentre centre = WideCentre::from_decimal(pos_x_s, pos_y, WideCentre::words_for_scale(cfg.scale.re, cfg.scale.im));

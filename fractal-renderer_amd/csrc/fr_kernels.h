@@ -240,6 +240,13 @@ hipError_t fr_launch_box_filter(const void *src, uint32_t width, uint64_t rows, 
 hipError_t fr_launch_colour_filter(const fr_kparams &p, const double *z, uint32_t z_width, const uint32_t *iters, uint32_t width,
                                    uint64_t rows, uint32_t s, uint32_t bpp, void *dst, hipStream_t stream);
 
+/* Escape-index statistics of n stored results (fr_stats.hip: view_stats_range_kernel, view_stats_hist_kernel): the
+ * fr_view_stats record of include/fractal_hip.h into the sizeof(struct fr_view_stats) bytes at `stats` (device, 8-byte aligned),
+ * whatever they held: a memset and two launches on `stream`, no host read between them.  z_width 2 or 4 (the hi parts are
+ * read), n <= 2^40; n == 0 queues the memset alone.  Device arrays. */
+hipError_t fr_launch_view_stats(const double *z, uint32_t z_width, const uint32_t *iters, size_t n, double stable_limit,
+                                uint32_t iterations, void *stats, hipStream_t stream);
+
 /* n independent orbits, device arrays (re, im interleaved) */
 hipError_t fr_launch_recursive_batch(uint32_t iterations, const double *start, const double *c, size_t n,
                                      double limit, int precision, double *out_pos, uint32_t *out_iters,

@@ -310,5 +310,65 @@ inline void colour_rows_ss_device(const Config &config, const void *d_z, const v
                                    static_cast<size_t>(channels) * config.width * config.height, hip_stream));
 }
 
+// ---- auto-exposure (include/fractal_hip.h, "statistics of a kept view") ------------------------------------------------------
+// The exposure a view's own escape indices call for: its (z, iters) reduced on the device to the 8 KB fr_view_stats record,
+// a percentile of the escaped pixels' indices taken from it on the host, and the exposure that gives a pixel there the full
+// primary colour.  The image stays the reference's colour map at that exposure.  (The record is `struct fr_view_stats`: the
+// C call that fills it bears the same name.)
+using ViewStats = struct fr_view_stats;
+// over host vectors as fr_escape_rows & co fill them: z_width doubles per pixel (4: DD with its low parts, read on the hi parts)
+inline ViewStats view_stats(const Config &config, const std::vector<double> &z, const std::vector<uint32_t> &iters, int z_width = 2) {
+    if (z_width < 1 || z.size() != static_cast<size_t>(z_width) * iters.size())
+        throw Error(FR_ERR_INVALID_ARGUMENT, "view_stats: z needs z_width doubles per entry of iters");
+    ViewStats out;
+    check(fr_view_stats(&config, z.data(), z_width, iters.data(), iters.size(), &out));
+    return out;
+}
+// device arrays into a device record (sizeof(ViewStats) bytes, 8-byte aligned), asynchronous on hip_stream: once per new view
+// or cap of a kept view; the GUI then copies the record back and recolours with auto_exposure's answer
+inline void view_stats_device(const Config &config, const void *d_z, const void *d_iters, size_t n, void *d_stats,
+                              void *hip_stream = nullptr, int z_width = 2) {
+    check(fr_view_stats_device(&config, d_z, z_width, d_iters, n, d_stats, hip_stream));
+}
+inline uint32_t stats_percentile(const ViewStats &stats, double p) {
+    uint32_t out = 0;
+    check(fr_stats_percentile(&stats, p, &out));
+    return out;
+}
+// 0.99 is a presentation default: a lone pixel beside a minibrot should not darken the frame; 1.0 takes the maximum
+inline double auto_exposure(const Config &config, const ViewStats &stats, double percentile = 0.99) {
+    double out = 0.0;
+    check(fr_auto_exposure(&config, &stats, percentile, &out));
+    return out;
+}
+// get_image at that exposure, on any single-device road: escape(cfg_s, z, iters) fills 2 doubles and one index per pixel of
+// cfg_s = config with width and height times supersample (fr_escape_rows, fr_escape_rows_pt_wide, ...); the result is the
+// road's render (supersampled render) of config with `exposure` set to *exposure_out, byte for byte.
+template <class Escape>
+std::vector<RGB> get_image_auto(const Config &config, uint32_t supersample, double percentile, double *exposure_out, Escape &&escape) {
+    if (supersample < 1 || supersample > FR_SS_MAX) throw Error(FR_ERR_INVALID_ARGUMENT, "get_image_auto: supersample is 1 .. FR_SS_MAX");
+    Config big = config;
+    big.width *= supersample;
+    big.height *= supersample;
+    const size_t n = static_cast<size_t>(big.width) * big.height;
+    std::vector<double> z(2 * n);
+    std::vector<uint32_t> iters(n);
+    escape(big, z.data(), iters.data());
+    Config shown = config;
+    shown.exposure = auto_exposure(config, view_stats(big, z, iters), percentile);
+    if (exposure_out) *exposure_out = shown.exposure;
+    std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
+    check(fr_colour_ss_rgb8(&shown, z.data(), 2, iters.data(), config.width, config.height, supersample, 3,
+                            reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB)));
+    return image;
+}
+// ... in the arithmetic of `precision` (FR_PRECISION_F64, FR_PRECISION_F32; the deep precisions with pos_lo = 0)
+inline std::vector<RGB> get_image_auto(const Config &config, int precision = FR_PRECISION_F64, double percentile = 0.99,
+                                       uint32_t supersample = 1, double *exposure_out = nullptr) {
+    return get_image_auto(config, supersample, percentile, exposure_out, [&](const Config &big, double *z, uint32_t *iters) {
+        check(fr_escape_rows(&big, precision, 0, big.height, z, iters));
+    });
+}
+
 }  // namespace fractal
 #endif

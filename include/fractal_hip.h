@@ -687,6 +687,69 @@ int fr_escape_extend(const fr_config *cfg, int precision, const fr_imaginary *po
 int fr_colour_rows_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, size_t n, int channels,
                           void *d_out, size_t out_len, void *hip_stream);
 
+/* ---- statistics of a kept view: where its pixels escape, and the exposure that shows it ---------------- */
+
+/* The colour map is primary * (iters [+ 1 - nu]) / iterations * exposure (calc/src/lib.rs:228) with `exposure` a constant of
+ * the Config that suits the default view at 50 iterations; a deep view needs a cap in the thousands while its pixels escape
+ * in a narrow band far below it, and comes out nearly flat.  The reference leaves that to a person at the GUI's exposure
+ * control (src/gui.rs:183-203).  These calls reduce a kept view's (z, iters) ON THE DEVICE to a small record — 8 KB cross
+ * PCIe, not 20 bytes per pixel — from which two host helpers take a percentile of the escape indices and the exposure that
+ * maps it to the full primary colour; the image is then fr_colour_rows_device's at that exposure, the reference's own colour
+ * map byte for byte.  DEFINITION, for pixel k of n:
+ *   re, im = the f64 position the colour map reads: z[2k], z[2k+1] for z_width 2; the hi parts z[4k], z[4k+2] for z_width 4;
+ *   dist   = re*re + im*im: two f64 multiplications and one addition, nothing fused (what the colour map forms);
+ *   it = iters[k], N = cfg->iterations.
+ *   Classes — the colour map's own branches (calc/src/lib.rs:216):
+ *     S (stable)  !(dist > cfg->stable_limit); a NaN dist lands here, as it does in the colour map;
+ *     C (capped)  dist > stable_limit and it >= N: exhaustion; foreign values above N count here too;
+ *     E (escaped) dist > stable_limit and it < N.
+ *   min_iters, max_iters, sum_iters are taken over E; shift is the smallest s >= 0 with (max_iters - min_iters) >> s <
+ *   FR_STATS_BINS; hist[b] is the number of pixels of E with (it - min_iters) >> shift == b.
+ * Every field is an integer function of the input: the result is bit-exact and independent of launch shape and atomic
+ * order.  Only cfg->iterations and cfg->stable_limit are read; algo, precision and the road that produced the arrays do not
+ * matter.  One call covers one array: records of row pieces are not merged, and multi-device / block-cyclic views are out
+ * of scope. */
+/* The record is a struct TAG, not a typedef: the call that fills it bears the same name, and in C a typedef and a function
+ * cannot share one.  Write `struct fr_view_stats` (in C++ too, where the function hides the bare name). */
+#define FR_STATS_BINS 1024
+struct fr_view_stats { /* sizeof == 8248 */
+    uint64_t n;         /* pixels examined */
+    uint64_t stable;    /* class S */
+    uint64_t capped;    /* class C */
+    uint64_t escaped;   /* class E;  n == stable + capped + escaped */
+    uint64_t sum_iters; /* sum of iters over class E, modulo 2^64 */
+    uint32_t min_iters; /* over class E; 0 when escaped == 0 */
+    uint32_t max_iters; /* over class E; 0 when escaped == 0 */
+    uint32_t shift;     /* a bin is 2^shift escape indices wide; 0 when escaped == 0 */
+    uint32_t reserved;  /* 0 */
+    uint64_t hist[FR_STATS_BINS];
+};
+
+/* Device arrays, asynchronous on hip_stream; d_stats: device memory, sizeof(struct fr_view_stats) bytes, 8-byte aligned.  The
+ * call overwrites *d_stats whatever it held (no precondition), allocates nothing, takes no lock, is re-entrant.  n == 0 is
+ * legal: an all-zero record with n = 0 (still queued on the stream: d_stats is device memory).
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): non-NULL pointers (the arrays may be NULL
+ * only when n == 0); z_width 2 or 4; d_z 8-byte, d_iters 4-byte, d_stats 8-byte aligned; n <= 2^40; stable_limit not NaN. */
+int fr_view_stats_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, size_t n, void *d_stats,
+                         void *hip_stream);
+/* the same over HOST arrays into a host record (context scratch: upload, launch, one small download, synchronise — as
+ * fr_colour_rgb8 does); n == 0 needs no device */
+int fr_view_stats(const fr_config *cfg, const double *z, int z_width, const uint32_t *iters, size_t n,
+                  struct fr_view_stats *out);
+/* Host only, no device.  The escape index at quantile p of class E: escaped == 0 gives 0; otherwise
+ * k = ceil(p * (double)escaped) — one f64 multiplication — clamped to [1, escaped], b = the smallest bin whose cumulative
+ * count reaches k, and the result is min(max_iters, min_iters + ((b + 1) << shift) - 1) computed in 64 bits: the bin's last
+ * index, exact when shift == 0.
+ * Domain: non-NULL pointers; p finite in [0, 1]; a self-consistent record (shift < 32, min_iters <= max_iters, and a
+ * histogram that reaches k). */
+int fr_stats_percentile(const struct fr_view_stats *s, double p, uint32_t *iters_out);
+/* Host only, no device.  escaped == 0 gives cfg->exposure; otherwise q = max(fr_stats_percentile(s, p), 1) and
+ * exposure = (double)cfg->iterations / (double)q, one f64 division: an escaped pixel at the p-quantile then has
+ * iters / iterations * exposure at (or one rounding under) 1 and gets the full primary colour.  With `smooth` the 1 - nu
+ * term shifts every pixel by the same 2 to 3 indices; that is accepted, the definition is on the escape index.
+ * Domain: fr_stats_percentile's, and cfg not NULL. */
+int fr_auto_exposure(const fr_config *cfg, const struct fr_view_stats *s, double p, double *exposure_out);
+
 /* ---- resumable perturbation: a deep view's cap raised in place ----------------------------------------- */
 
 /* A GUI keeps a PT view as (z, iters, dz, m) in DEVICE memory — 40 bytes per pixel — and answers an iterations change with
