@@ -36,6 +36,8 @@ __all__ = [
     "bla_table", "bla_count", "bla_cache", "BLA_DEFAULT_BITS",
     "get_image_ss_pt", "colour_rows_ss_device", "colour_image_ss",
     "ViewStats", "view_stats", "view_stats_device", "stats_percentile", "auto_exposure", "get_image_auto",
+    "escape_rows_de", "distance_rows", "colour_image_de", "get_image_de", "escape_rows_de_device", "distance_rows_device",
+    "colour_de_rows_device",
 ]
 
 
@@ -803,6 +805,89 @@ def get_image_auto(config, percentile=0.99, precision=Precision.F64, pos_lo=None
     shown.exposure = exposure
     image = colour_image(shown, z, it) if s == 1 else colour_image_ss(shown, z, it, s)
     return image, exposure
+
+
+def _de_call(precision, pos_lo, centre, device):
+    """the DE render the keywords select, in its host or device form: (function, leading arguments behind the config, keep-alive)"""
+    suffix = "_device" if device else ""
+    lib = _native.load()
+    if centre is not None:
+        family, pre, keep = _deep_call(precision, pos_lo, centre)  # its checks: Precision.PT, no pos_lo
+        return getattr(lib, "fr_escape_rows_de_pt_wide" + suffix), pre, keep
+    lo, keep = _lo(pos_lo)
+    return getattr(lib, "fr_escape_rows_de" + suffix), (int(precision), lo), keep
+
+
+def escape_rows_de(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, centre=None):
+    """fr_escape_rows_de / fr_escape_rows_de_pt_wide: rows [y0, y1) with the orbit's derivative (include/fractal_hip.h, "DE"):
+    (z float64 [rows, width, 2], iters uint32 [rows, width], der float64 [rows, width, 2]).  z and iters are the road's own,
+    bit for bit; der is the derivative of the returned position (d/dc for Mandelbrot, d/dz0 for Julia).  precision is
+    Precision.F64 or Precision.PT (pos_lo= or centre=, a WideCentre, as escape_rows takes them); everything else is refused."""
+    y0, y1 = _rows(config, y0, y1)
+    fn, pre, _keep = _de_call(precision, pos_lo, centre, False)
+    z = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
+    it = np.empty((y1 - y0, config.width), dtype=np.uint32)
+    der = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
+    _native.check(fn(C.byref(config), *pre, y0, y1, z.ctypes.data, it.ctypes.data, der.ctypes.data))
+    return z, it, der
+
+
+def escape_rows_de_device(config, z_ptr, iters_ptr, der_ptr, y0=0, y1=None, precision=Precision.F64, pos_lo=None, centre=None,
+                          stream=None):
+    """fr_escape_rows_de_device / fr_escape_rows_de_pt_wide_device: the same into DEVICE arrays (raw pointers as ints, all three
+    required), asynchronously on `stream`: the 36 bytes per pixel a GUI keeps to vary thickness without an orbit."""
+    y0, y1 = _rows(config, y0, y1)
+    fn, pre, _keep = _de_call(precision, pos_lo, centre, True)
+    _native.check(fn(C.byref(config), *pre, y0, y1, z_ptr or None, iters_ptr or None, der_ptr or None, _stream(stream)))
+
+
+def _de_arrays(z, iters, der):
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    iters = np.ascontiguousarray(iters, dtype=np.uint32)
+    der = np.ascontiguousarray(der, dtype=np.float64)
+    if z.shape[:-1] != iters.shape or z.shape[-1] != 2 or der.shape != z.shape:
+        raise ValueError("z and der must be [..., 2] and iters [...]")
+    return z, iters, der
+
+
+def distance_rows(config, z, iters, der):
+    """fr_distance_rows over numpy arrays: the exterior distance estimate |z| ln|z| / |z'| in PIXELS, float64 [...]; 0 for a
+    capped pixel and where the derivative overflowed, +inf where it is 0.  Only height, scale and iterations are read."""
+    z, iters, der = _de_arrays(z, iters, der)
+    out = np.empty(iters.shape, dtype=np.float64)
+    _native.check(_native.load().fr_distance_rows(C.byref(config), z.ctypes.data, iters.ctypes.data, der.ctypes.data, iters.size,
+                                                  out.ctypes.data))
+    return out
+
+
+def distance_rows_device(config, z_ptr, iters_ptr, der_ptr, n, out_ptr, stream=None):
+    """fr_distance_rows_device: D of n stored results in DEVICE memory into n float64 at out_ptr, asynchronously on `stream`"""
+    _native.check(_native.load().fr_distance_rows_device(C.byref(config), z_ptr or None, iters_ptr or None, der_ptr or None, int(n),
+                                                         out_ptr or None, _stream(stream)))
+
+
+def colour_image_de(config, z, iters, der, thickness):
+    """fr_colour_de_rgb8 over numpy arrays -> uint8 [..., 3]: colour_image's bytes, and where an escaped pixel lies closer than
+    `thickness` pixels to the set every byte times distance / thickness, truncated.  thickness 0 is colour_image."""
+    z, iters, der = _de_arrays(z, iters, der)
+    out = np.empty(iters.shape + (3,), dtype=np.uint8)
+    _native.check(_native.load().fr_colour_de_rgb8(C.byref(config), z.ctypes.data, iters.ctypes.data, der.ctypes.data, iters.size,
+                                                   float(thickness), out.ctypes.data, out.nbytes))
+    return out
+
+
+def colour_de_rows_device(config, z_ptr, iters_ptr, der_ptr, n, thickness, out_ptr, channels=3, stream=None):
+    """fr_colour_de_rows_device: the shaded colour map over n stored results in DEVICE memory into channels * n bytes at out_ptr
+    (3: r,g,b at any alignment; 4: r,g,b,255, 4-byte aligned), asynchronously on `stream`."""
+    _native.check(_native.load().fr_colour_de_rows_device(C.byref(config), z_ptr or None, iters_ptr or None, der_ptr or None, int(n),
+                                                          float(thickness), int(channels), out_ptr or None, _stream(stream)))
+
+
+def get_image_de(config, thickness=1.0, precision=Precision.F64, pos_lo=None, centre=None):
+    """get_image with distance shading: uint8 [height, width, 3].  escape_rows_de on the road the keywords select, then
+    colour_image_de: filaments thinner than a pixel stay visible as dark lines `thickness` pixels wide."""
+    z, it, der = escape_rows_de(config, precision=precision, pos_lo=pos_lo, centre=centre)
+    return colour_image_de(config, z, it, der, thickness)
 
 
 def count_iterations(config, y0=0, y1=None, sx=1, sy=1, precision=Precision.F64):

@@ -401,6 +401,25 @@ PROTOTYPES = {
     "fr_view_stats": (C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(fr_view_stats)]),
     "fr_stats_percentile": (C.c_int, [C.POINTER(fr_view_stats), C.c_double, C.POINTER(C.c_uint32)]),
     "fr_auto_exposure": (C.c_int, [C.POINTER(fr_config), C.POINTER(fr_view_stats), C.c_double, C.POINTER(C.c_double)]),
+    "fr_escape_rows_de_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_int, C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "fr_escape_rows_de": (
+        C.c_int, [C.POINTER(fr_config), C.c_int, C.POINTER(Imaginary), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fr_escape_rows_de_pt_wide_device": (
+        C.c_int, [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fr_escape_rows_de_pt_wide": (
+        C.c_int, [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fr_distance_rows_device": (
+        C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "fr_distance_rows": (C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fr_colour_de_rows_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p, C.c_void_p],
+    ),
+    "fr_colour_de_rgb8": (
+        C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_size_t]),
     "fr_count_iterations": (
         C.c_int,
         [C.POINTER(fr_config), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),

@@ -20,6 +20,9 @@
 // following number within [0, 1] written with a '.' or an exponent is P (0.5, 1.0 — a bare 0 or 1 is a <width>), or write
 // --auto-exposure=P; every single-device road above, not with -e, more than
 // one device or -a fern; the chosen exposure is printed unless --quiet);
+// --distance-shade T (distance estimation: an escaped pixel closer than T pixels to the set is darkened by distance / T, so
+// filaments thinner than a pixel stay visible — include/fractal_hip.h, "DE"; the F64 road, or --perturbation; not with --bla,
+// --scaled, --supersample above 1, --f32, --devices, --auto-exposure or -a fern);
 // for -a fern: --threads N (the rayon thread count being stood in for; default: this machine's hardware
 // threads, what rayon would use) and --seed N (default: from the OS, as the reference seeds from entropy).
 // Not handled here (by design): --gui, --open.
@@ -81,6 +84,7 @@ int main(int argc, char **argv) {
         seed_s, supersample_s;
     bool disable_inside = false, unsmooth = false, f32 = false, quiet = false, perturbation = false, bla = false, scaled = false;
     bool exposure_given = false, auto_exposure_on = false;
+    std::optional<std::string> distance_shade;
     double auto_p = 0.99;
     int bla_bits = 0;
     std::vector<std::string> positionals;
@@ -119,6 +123,7 @@ int main(int argc, char **argv) {
             auto_p = to_f64(a.substr(16), "--auto-exposure");
             if (!(auto_p >= 0.0 && auto_p <= 1.0)) die("--auto-exposure takes a percentile within [0, 1]");
         }
+        else if (a == "--distance-shade") distance_shade = value(i, "--distance-shade");
         else if (a == "--primary-color") primary = value(i, "--primary-color");
         else if (a == "--secondary-color") secondary = value(i, "--secondary-color");
         else if (a == "-d" || a == "--disable-inside") disable_inside = true;
@@ -168,6 +173,16 @@ int main(int argc, char **argv) {
     if (auto_exposure_on && algo == Algo::BarnsleyFern) die("--auto-exposure does not apply to -a fern: the fern has no escape indices");
     if (auto_exposure_on && devices && devices->find(',') != std::string::npos)
         die("--auto-exposure runs on one device: the statistics cover one array, not the pieces of --devices");
+    if (distance_shade) {
+        const uint32_t ss = supersample_s ? to_u32(*supersample_s, "--supersample") : 1;
+        if (bla) die("--distance-shade does not combine with --bla: a skipped block has no per-step derivative");
+        if (scaled) die("--distance-shade does not combine with --scaled: distance estimation is not defined on SCALED PT");
+        if (ss > 1) die("--distance-shade does not combine with --supersample above 1");
+        if (f32) die("--distance-shade does not combine with --f32: distance estimation is defined on the f64 road and on --perturbation");
+        if (devices) die("--distance-shade does not combine with --devices: distance estimation runs on one device");
+        if (auto_exposure_on) die("--distance-shade does not combine with --auto-exposure");
+        if (algo == Algo::BarnsleyFern) die("--distance-shade does not apply to -a fern: the fern has no orbit derivative");
+    }
 
     // src/lib.rs:207-226
     Config cfg = Config::make(algo);
@@ -226,6 +241,14 @@ int main(int argc, char **argv) {
                 seed = (static_cast<uint64_t>(rd()) << 32) | rd();
             }
             image = get_image_fern(cfg, threads, seed);
+        } else if (distance_shade) {
+            const double thickness = to_f64(*distance_shade, "--distance-shade");
+            if (perturbation) {
+                const WideCentre centre = WideCentre::from_decimal(pos_x_s, pos_y, WideCentre::words_for_scale(cfg.scale.re, cfg.scale.im));
+                image = get_image_de(cfg, centre.c(), thickness);
+            } else {
+                image = get_image_de(cfg, thickness);
+            }
         } else if (auto_exposure_on) {
             // the road's escape indices, their statistics on the device, then the colour map at the exposure they call for
             const uint32_t ss = supersample_s ? to_u32(*supersample_s, "--supersample") : 1;

@@ -370,5 +370,41 @@ inline std::vector<RGB> get_image_auto(const Config &config, int precision = FR_
     });
 }
 
+// ---- distance estimation (include/fractal_hip.h, "DE") ------------------------------------------------------------------------
+// get_image with distance shading: the road's escape results WITH the orbit's derivative, then the colour map with every byte
+// of an escaped pixel closer than `thickness` pixels to the set scaled by distance / thickness — filaments thinner than a
+// pixel stay visible.  escape(config, z, iters, der) fills 2 + 2 doubles and one index per pixel (fr_escape_rows_de,
+// fr_escape_rows_de_pt_wide).  thickness 0 is get_image's bytes.
+template <class Escape>
+std::vector<RGB> get_image_de(const Config &config, double thickness, Escape &&escape) {
+    const size_t n = static_cast<size_t>(config.width) * config.height;
+    std::vector<double> z(2 * n), der(2 * n);
+    std::vector<uint32_t> iters(n);
+    escape(config, z.data(), iters.data(), der.data());
+    std::vector<RGB> image(n);
+    check(fr_colour_de_rgb8(&config, z.data(), iters.data(), der.data(), n, thickness, reinterpret_cast<uint8_t *>(image.data()),
+                            image.size() * sizeof(RGB)));
+    return image;
+}
+// ... on the F64 road, or on PT with a dd centre (precision FR_PRECISION_PT; pos_lo may be null)
+inline std::vector<RGB> get_image_de(const Config &config, double thickness = 1.0, int precision = FR_PRECISION_F64,
+                                     const fr_imaginary *pos_lo = nullptr) {
+    return get_image_de(config, thickness, [&](const Config &c, double *z, uint32_t *iters, double *der) {
+        check(fr_escape_rows_de(&c, precision, pos_lo, 0, c.height, z, iters, der));
+    });
+}
+// ... on PT with a wide centre
+inline std::vector<RGB> get_image_de(const Config &config, const fr_wide_centre &centre, double thickness = 1.0) {
+    return get_image_de(config, thickness, [&](const Config &c, double *z, uint32_t *iters, double *der) {
+        check(fr_escape_rows_de_pt_wide(&c, &centre, 0, c.height, z, iters, der));
+    });
+}
+// a kept view's recolour at another thickness, device arrays, asynchronous on hip_stream: no orbit is run
+inline void colour_de_rows_device(const Config &config, const void *d_z, const void *d_iters, const void *d_der, double thickness,
+                                  void *d_out, int channels = 4, void *hip_stream = nullptr) {
+    const size_t n = static_cast<size_t>(config.width) * config.height;
+    check(fr_colour_de_rows_device(&config, d_z, d_iters, d_der, n, thickness, channels, d_out, hip_stream));
+}
+
 }  // namespace fractal
 #endif

@@ -336,6 +336,42 @@ typedef struct fr_config {
  * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): SCALED PT's, with the centre REQUIRED; there
  * is no bits argument, the calls are the plain loop's; for the extension M >= N (M == N is a legal no-op that needs no
  * device, as y0 == y1 is); all four arrays, z and w 8-byte aligned, iters and m 4-byte aligned (y0 == y1 needs none). */
+/*
+ * DE (distance estimation; the fr_escape_rows_de, fr_distance_rows and fr_colour_de calls below): the orbit's derivative
+ * carried beside the escape loop, the exterior distance estimate derived from it, and the colour map shaded by that distance.
+ * DE is defined on two roads: FR_PRECISION_F64, and FR_PRECISION_PT with a dd centre (pos, pos_lo) or a wide centre (WIDE PT).
+ * Every operation below is ONE correctly rounded f64 operation; fma is fused and nothing else is; sqrt is IEEE; log2 is the
+ * software log2 the colour map uses (fr_log2 of csrc/fr_math.h).
+ *   Derivative.  b0 = 1 for Mandelbrot (d/dc), 0 for Julia (d/dz0).  The derivative d accompanies `previous` and starts as
+ *   (1, 0).  In step i the road's own step forms `next` from previous = z — F64: recursive(), calc/src/lib.rs:245-257, with
+ *   its operation order; PT: PT's step on (X, m, z, dz) above, word for word, rebases included — and beside it, from the same z
+ *   (the f64 position before the step; in PT the z the loop already holds):
+ *     t  = (z.re + z.re, z.im + z.im)
+ *     nd = (fma(t.re, d.re, fma(-t.im, d.im, b0)), fma(t.re, d.im, t.im * d.re))
+ *   Escape returns (next, i, nd); otherwise d = nd; exhaustion returns (previous, iterations, d): `der` is always the
+ *   derivative of the returned position, and iterations = 0 returns (start, 0, (1, 0)).  d may become +-inf or NaN: that is
+ *   the IEEE result of this sequence and part of the definition (a NaN's sign and payload are not specified).  z and iters
+ *   are the road's own, bit for bit (fr_escape_rows_device, fr_escape_rows_pt, fr_escape_rows_pt_wide).  An algorithm without
+ *   orbits writes zeros into all three arrays.
+ *   Distance, in pixels, per pixel:
+ *     if iters == iterations: D = 0
+ *     else n2  = z.re*z.re + z.im*z.im;  dn2 = d.re*d.re + d.im*d.im
+ *          num = (sqrt(n2) * log2(n2)) * 0x1.62e42fefa39efp-2                            [|z| ln|z|]
+ *          D   = (num / sqrt(dn2)) * ((double)height * min(|scale.re|, |scale.im|))      [the last factor: one product]
+ *          if !(D > 0) D = 0            [NaN and negatives; +inf stays: d == 0, nothing is near]
+ *   This is b = |z| ln|z| / |z'|; close to the set the true distance lies in (b/2, 2b).  dn2 = +inf (|d| >= 2^512, or d
+ *   itself inf / NaN) gives D = 0, which inside the domain below happens only to pixels far below one pixel from the set,
+ *   where 0 is what should be drawn (DESIGN.md 3.20 carries the bound: b < height * min|scale| * 2^-465 pixels there).
+ *   Shading.  fr_colour_de_rows applies the colour map exactly as fr_colour_rows_device does; then, for a pixel with
+ *   iters < iterations, thickness > 0 and s = D / thickness < 1, every colour byte becomes (uint8_t)((double)byte * s),
+ *   truncated.  Alpha stays 255.  Capped pixels are never shaded: their inside colour is the reference's.  thickness == 0
+ *   gives fr_colour_rows_device's bytes exactly.
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): the road's own domain; limit <= 2^20;
+ * thickness finite and in [0, 2^20]; F64 takes no pos_lo; PT with a wide centre keeps WIDE PT's |scale| <= 2^440.
+ * Out of scope, refused by name: FR_PRECISION_F32, FR_PRECISION_DD, BLA-PT (a skipped block has no per-step derivative here)
+ * and SCALED PT; block-cyclic and multi-device renders; supersampling; fr_pixel; raising a DE view's cap in place — AFTER
+ * fr_escape_extend* ON (z, iters), A der ARRAY IS STALE: it is the derivative at the old cap's position, and no call
+ * continues it.  Render the view again with fr_escape_rows_de at the new cap. */
 #define FR_BLA_DEFAULT_BITS 40
 #define FR_PT_MAX_ITERATIONS (1u << 24)
 #define FR_WIDE_MAX_WORDS 16
@@ -980,6 +1016,39 @@ int fr_colour_rows_ss_device(const fr_config *cfg, const void *d_z, int z_width,
                              uint32_t supersample, int channels, void *d_out, size_t out_len, void *hip_stream);
 int fr_colour_ss_rgb8(const fr_config *cfg, const double *z, int z_width, const uint32_t *iters, uint32_t width, uint32_t rows,
                       uint32_t supersample, int channels, uint8_t *out, size_t out_len);
+
+/* ---- distance estimation: the orbit's derivative, the distance in pixels, distance-shaded colour ----------- */
+
+/* DE (defined at fr_precision above).  A kept view gains one array: der, 2 doubles per pixel beside (z, iters) — 36 bytes per
+ * pixel in all.  Thickness, like exposure, is then a recolour: fr_colour_de_rows_device over the kept arrays, no orbit.
+ * The _device forms are asynchronous on hip_stream, allocate nothing and take no lock beyond what the road's render takes
+ * (PT: the context's orbit cache, which they share with the PT calls: no second orbit is computed).
+ *
+ * Rows [y0, y1) of the view with their derivatives: z and der 2 doubles per pixel (8-byte aligned), iters uint32 (4-byte
+ * aligned), k = (y - y0) * width + x.  All three arrays are required; y0 == y1 is a no-op that needs no device.  precision:
+ * FR_PRECISION_F64 (pos_lo must be NULL) or FR_PRECISION_PT (pos_lo NULL = (0, 0)).  With profiling on, fr_last_kernel_name
+ * reports escape_de_kernel / escape_pt_de_kernel. */
+int fr_escape_rows_de_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, void *d_z,
+                             void *d_iters, void *d_der, void *hip_stream);
+int fr_escape_rows_de(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z,
+                      uint32_t *iters, double *der);
+/* the same on PT with a wide centre (WIDE PT's domain; centre required) */
+int fr_escape_rows_de_pt_wide_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, void *d_z,
+                                     void *d_iters, void *d_der, void *hip_stream);
+int fr_escape_rows_de_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z,
+                              uint32_t *iters, double *der);
+/* D of n stored results, one double per pixel (8-byte aligned).  Reads only height, scale and iterations from cfg.  n <= 2^40;
+ * n == 0 needs no device. */
+int fr_distance_rows_device(const fr_config *cfg, const void *d_z, const void *d_iters, const void *d_der, size_t n, void *d_out,
+                            void *hip_stream);
+int fr_distance_rows(const fr_config *cfg, const double *z, const uint32_t *iters, const double *der, size_t n, double *out);
+/* The colour map with distance shading over n stored results: channels 3 (r,g,b at any alignment) or 4 (r,g,b,255; d_out
+ * 4-byte aligned), channels * n bytes.  thickness in pixels, finite, in [0, 2^20]; 0 = fr_colour_rows_device's bytes. */
+int fr_colour_de_rows_device(const fr_config *cfg, const void *d_z, const void *d_iters, const void *d_der, size_t n,
+                             double thickness, int channels, void *d_out, void *hip_stream);
+/* the same over HOST arrays into packed r,g,b (upload, colour, download, synchronise: as fr_colour_rgb8) */
+int fr_colour_de_rgb8(const fr_config *cfg, const double *z, const uint32_t *iters, const double *der, size_t n, double thickness,
+                      uint8_t *out, size_t out_len);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 
