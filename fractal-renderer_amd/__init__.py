@@ -38,6 +38,8 @@ __all__ = [
     "ViewStats", "view_stats", "view_stats_device", "stats_percentile", "auto_exposure", "get_image_auto",
     "escape_rows_de", "distance_rows", "colour_image_de", "get_image_de", "escape_rows_de_device", "distance_rows_device",
     "colour_de_rows_device",
+    "extend_rows_de", "extend_rows_de_device", "escape_rows_de_pt_state", "escape_rows_de_pt_state_device", "extend_rows_de_pt",
+    "extend_rows_de_pt_device",
 ]
 
 
@@ -839,6 +841,95 @@ def escape_rows_de_device(config, z_ptr, iters_ptr, der_ptr, y0=0, y1=None, prec
     y0, y1 = _rows(config, y0, y1)
     fn, pre, _keep = _de_call(precision, pos_lo, centre, True)
     _native.check(fn(C.byref(config), *pre, y0, y1, z_ptr or None, iters_ptr or None, der_ptr or None, _stream(stream)))
+
+
+def _de_state_call(name, pos_lo, centre, device):
+    """a PT call of RESUMABLE DE in its host or device form: (function, pos_lo pointer, centre pointer, keep-alive).  pos_lo= and
+    centre= are exclusive, as everywhere (ValueError)."""
+    fn = getattr(_native.load(), name + ("_device" if device else ""))
+    if centre is not None:
+        _family, pre, keep = _deep_call(Precision.PT, pos_lo, centre)  # its checks: no pos_lo beside a centre
+        return fn, None, pre[0], keep
+    lo, keep = _lo(pos_lo)
+    return fn, lo, None, keep
+
+
+def _de_state_arrays(config, y0, y1, z, iters, dz, m, der):
+    shape = (max(y1 - y0, 0), config.width)
+    z, dz, der = (np.array(a, dtype=np.float64, order="C") for a in (z, dz, der))
+    iters, m = np.array(iters, dtype=np.uint32, order="C"), np.array(m, dtype=np.uint32, order="C")
+    if any(a.shape != shape + (2,) for a in (z, dz, der)) or iters.shape != shape or m.shape != shape:
+        raise ValueError("z, dz and der must be [rows, width, 2], iters and m [rows, width] for rows [y0, y1)")
+    return z, iters, dz, m, der
+
+
+def extend_rows_de(config, z, iters, der, from_iterations, precision=Precision.F64, y0=0, y1=None):
+    """fr_escape_extend_de over numpy arrays: (z, iters, der) as escape_rows_de returned them on the F64 road at the cap
+    `from_iterations` -> the same triple at config.iterations, bit for bit what escape_rows_de gives there (copies; the arguments
+    are left alone).  Precision.PT is refused: its state has five arrays (escape_rows_de_pt_state, extend_rows_de_pt)."""
+    y0, y1 = _rows(config, y0, y1)
+    shape = (max(y1 - y0, 0), config.width)
+    z, der = np.array(z, dtype=np.float64, order="C"), np.array(der, dtype=np.float64, order="C")
+    iters = np.array(iters, dtype=np.uint32, order="C")
+    if z.shape != shape + (2,) or der.shape != shape + (2,) or iters.shape != shape:
+        raise ValueError("z and der must be [rows, width, 2] and iters [rows, width] for rows [y0, y1)")
+    _native.check(_native.load().fr_escape_extend_de(C.byref(config), int(precision), y0, y1, int(from_iterations), z.ctypes.data,
+                                                     iters.ctypes.data, der.ctypes.data))
+    return z, iters, der
+
+
+def extend_rows_de_device(config, z_ptr, iters_ptr, der_ptr, from_iterations, precision=Precision.F64, y0=0, y1=None, stream=None):
+    """fr_escape_extend_de_device: raise the cap of the F64 road's stored (z, iters, der) of rows [y0, y1) from `from_iterations`
+    to config.iterations IN PLACE, asynchronously on `stream` (raw device pointers as ints)."""
+    y0, y1 = _rows(config, y0, y1)
+    _native.check(_native.load().fr_escape_extend_de_device(C.byref(config), int(precision), y0, y1, int(from_iterations), z_ptr or None,
+                                                            iters_ptr or None, der_ptr or None, _stream(stream)))
+
+
+def escape_rows_de_pt_state(config, pos_lo=None, centre=None, y0=0, y1=None):
+    """fr_escape_rows_de_pt_state: rows [y0, y1) in Precision.PT with their resumable DE state (include/fractal_hip.h, "RESUMABLE
+    DE"): (z float64 [rows, width, 2], iters uint32 [rows, width], dz float64 [rows, width, 2], m uint32 [rows, width], der
+    float64 [rows, width, 2]).  z, iters, der are escape_rows_de's, dz and m escape_rows_pt_state's.  pos_lo= or centre= (a
+    WideCentre), not both."""
+    y0, y1 = _rows(config, y0, y1)
+    fn, lo, wide, _keep = _de_state_call("fr_escape_rows_de_pt_state", pos_lo, centre, False)
+    shape = (max(y1 - y0, 0), config.width)
+    z, dz, der = (np.empty(shape + (2,), dtype=np.float64) for _ in range(3))
+    it, m = np.empty(shape, dtype=np.uint32), np.empty(shape, dtype=np.uint32)
+    _native.check(fn(C.byref(config), lo, wide, y0, y1, z.ctypes.data, it.ctypes.data, dz.ctypes.data, m.ctypes.data, der.ctypes.data))
+    return z, it, dz, m, der
+
+
+def escape_rows_de_pt_state_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, der_ptr, pos_lo=None, centre=None, y0=0, y1=None,
+                                   stream=None):
+    """fr_escape_rows_de_pt_state_device: the same into DEVICE arrays (raw pointers as ints, all five required), asynchronously on
+    `stream`: the 56 bytes per pixel a GUI keeps to vary thickness AND the cap without rendering again."""
+    y0, y1 = _rows(config, y0, y1)
+    fn, lo, wide, _keep = _de_state_call("fr_escape_rows_de_pt_state", pos_lo, centre, True)
+    _native.check(fn(C.byref(config), lo, wide, y0, y1, z_ptr or None, iters_ptr or None, dz_ptr or None, m_ptr or None, der_ptr or None,
+                     _stream(stream)))
+
+
+def extend_rows_de_pt(config, z, iters, dz, m, der, from_iterations, pos_lo=None, centre=None, y0=0, y1=None):
+    """fr_escape_extend_de_pt over numpy arrays: the state escape_rows_de_pt_state returned at the cap `from_iterations` -> the
+    state at config.iterations (copies; the arguments are left alone).  The arrays must be that view's; the library cannot check
+    it."""
+    y0, y1 = _rows(config, y0, y1)
+    z, iters, dz, m, der = _de_state_arrays(config, y0, y1, z, iters, dz, m, der)
+    fn, lo, wide, _keep = _de_state_call("fr_escape_extend_de_pt", pos_lo, centre, False)
+    _native.check(fn(C.byref(config), lo, wide, y0, y1, int(from_iterations), z.ctypes.data, iters.ctypes.data, dz.ctypes.data,
+                     m.ctypes.data, der.ctypes.data))
+    return z, iters, dz, m, der
+
+
+def extend_rows_de_pt_device(config, z_ptr, iters_ptr, dz_ptr, m_ptr, der_ptr, from_iterations, pos_lo=None, centre=None, y0=0,
+                             y1=None, stream=None):
+    """fr_escape_extend_de_pt_device: raise the cap of the stored DE state of rows [y0, y1) from `from_iterations` to
+    config.iterations IN PLACE, asynchronously on `stream`; the view's reference orbit is continued, not recomputed."""
+    y0, y1 = _rows(config, y0, y1)
+    fn, lo, wide, _keep = _de_state_call("fr_escape_extend_de_pt", pos_lo, centre, True)
+    _native.check(fn(C.byref(config), lo, wide, y0, y1, int(from_iterations), z_ptr or None, iters_ptr or None, dz_ptr or None,
+                     m_ptr or None, der_ptr or None, _stream(stream)))
 
 
 def _de_arrays(z, iters, der):

@@ -411,6 +411,30 @@ PROTOTYPES = {
         C.c_int, [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fr_escape_rows_de_pt_wide": (
         C.c_int, [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fr_escape_extend_de_device": (
+        C.c_int, [C.POINTER(fr_config), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fr_escape_extend_de": (
+        C.c_int, [C.POINTER(fr_config), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fr_escape_rows_de_pt_state_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p],
+    ),
+    "fr_escape_rows_de_pt_state": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p],
+    ),
+    "fr_escape_extend_de_pt_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "fr_escape_extend_de_pt": (
+        C.c_int,
+        [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p],
+    ),
     "fr_distance_rows_device": (
         C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "fr_distance_rows": (C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -2,6 +2,8 @@
  * fr_de.hip — distance estimation (include/fractal_hip.h, "DE"): the orbit's derivative carried beside the escape loop on the
  * F64 road and on PT (dd or wide centre), the exterior distance estimate b = |z| ln|z| / |z'| in pixels, and the colour map
  * with distance shading.  tests/de_model.c restates all of it; tests/test_gpu_de.py compares the two bit for bit.
+ * RESUMABLE DE (include/fractal_hip.h): the same derivative kept as state, so that a DE view's cap is raised in place;
+ * tests/de_state_model.c restates it and tests/test_gpu_de_extend.py compares the two bit for bit.
  *
  * Every operation of the definition is one correctly rounded f64 operation (the build has -ffp-contract=off; fma only where
  * the definition says fma), so the derivative, overflow to inf and NaN included, is the same on every conforming machine.
@@ -15,10 +17,16 @@
  *   escape_pt_de_kernel<JULIA>  PT's loop as fr_pt.hip's orbit_pt states it — same operations, same rebases, the load of
  *                               X_{m+2} issued a step ahead — with d beside it, from the z the loop holds.  The orbits are the
  *                               context's (fr_ctx.h: pt_orbit_view): a dd and a wide centre differ only there.
+ *   escape_extend_de_kernel<JULIA>     RESUMABLE DE on the F64 road: escape_de_kernel's step continued in place from the stored
+ *                               (z, der) of the pixels whose iters is the old cap, c staged as the render stages it.
+ *   escape_pt_de_state_kernel<JULIA>   escape_pt_de_kernel with RESUMABLE PT's rebase rule, storing (z, iters, dz, m, der);
+ *   escape_extend_pt_de_kernel<JULIA>  continues that state in place on the orbits of the new cap.  Both run orbit_pt_de_state,
+ *                               the one copy of the state step with the derivative.  The two extend kernels read iters first and
+ *                               a workgroup with no pixel at the old cap ends before it stages or loads anything.
  *   distance_rows_kernel        (z, iters, der) -> D, one double per pixel; the log2 table in LDS.
  *   colour_de_rows_kernel       fr_colour.h's colour_of, the renders' own map, then the shading: every byte times
  *                               s = D / thickness where s < 1.  RGBA leaves as one dword, RGB as three bytes at any alignment.
- * No kernel here uses scratch (profiles/de_inner_loop_isa.txt).
+ * No kernel here uses scratch (profiles/de_inner_loop_isa.txt, profiles/de_state_inner_loop_isa.txt).
  */
 #include <cmath>
 #include <memory>
@@ -185,6 +193,205 @@ __global__ __launch_bounds__(kDeThreads) void escape_pt_de_kernel(const fr_kpara
     de_store(p, l, z, iters, der, zr, zi, i, dr, di);
 }
 
+/* ---- RESUMABLE DE (include/fractal_hip.h): a DE view's cap raised in place ------------------------------------------------------ */
+
+/* The F64 road.  Exhaustion stored (previous, N, d) and c is a function of the pixel, so the loop goes on from i = from.  `iters`
+ * is read first; a workgroup with no pixel at `from` ends there (escape_extend_pt_kernel's early-out), and a finished pixel's z
+ * and der are neither loaded nor stored.  The host launches it only for an escape-time algorithm and from < p.iterations. */
+template <bool JULIA>
+__global__ __launch_bounds__(kDeThreads) void escape_extend_de_kernel(const fr_kparams p, double *z, uint32_t *iters, double *der,
+                                                                      const uint32_t from) {
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
+    const uint32_t tid = threadIdx.x;
+    const DeLane l = de_lane(p, tid);
+    const uint64_t k = (uint64_t)l.r * p.ncols + l.cx;
+    uint32_t done = 0;
+    if (l.valid) done = iters[k];
+    const bool running = l.valid && done == from;
+    if (!__syncthreads_or(running ? 1 : 0)) return; /* whole workgroup (uniform) */
+    if (!JULIA) { /* c = the pixel's coordinate, staged as the render stages it; Julia's c is the constant */
+        de_stage<false>(p, tid, l.col0, l.row0, s_re, s_im);
+        __syncthreads();
+    }
+    if (!running) return;
+    const double cre = JULIA ? p.julia_re : s_re[l.lx], cim = JULIA ? p.julia_im : s_im[l.ly];
+    const double b0 = JULIA ? 0.0 : 1.0;
+    const double squared = p.limit * p.limit;
+    const uint32_t iterations = p.iterations;
+    double re = z[2 * k], im = z[2 * k + 1], dr = der[2 * k], di = der[2 * k + 1];
+    uint32_t i = from;
+    for (; i < iterations; i++) { /* escape_de_kernel's step */
+        const double tr = re + re, ti = im + im;
+        const double nre = (re * re - im * im) + cre;
+        const double nim = tr * im + cim;
+        const double ndr = __builtin_fma(tr, dr, __builtin_fma(-ti, di, b0));
+        const double ndi = __builtin_fma(tr, di, ti * dr);
+        re = nre, im = nim, dr = ndr, di = ndi;
+        if (nre * nre + nim * nim > squared) break;
+    }
+    de_store(p, l, z, iters, der, re, im, i, dr, di); /* i == iterations on exhaustion: the new cap */
+}
+
+/* PT.  A pixel's state between steps is RESUMABLE PT's (z, dz, m, onK; fr_pt.hip: orbit_pt_state) with the derivative d beside
+ * it.  orbit_pt_de_state runs `steps` steps from it — escape_pt_de_kernel's operations with the state rule's rebase condition:
+ * dist < |dz|^2, or m == last of an orbit ENDED BY ESCAPE (x_end / k_end: that last index, or ~0 for an orbit cut by the cap,
+ * which m never equals) — and leaves the state after the last step in `s`; on escape that is (next, 0, 0, nd).  Returns the
+ * steps completed before the escape (`steps`: none).  x_last / k_last only clamp the loads. */
+struct PtDeState {
+    double zr, zi, dzr, dzi, dr, di;
+    uint32_t m;
+    bool on_k;
+};
+
+constexpr uint32_t kDeOnK = 0x80000000u; /* bit 31 of the stored m: the pixel follows K (fr_pt.hip: kPtOnK) */
+
+template <bool JULIA>
+__device__ __forceinline__ uint32_t orbit_pt_de_state(uint32_t steps, double dcr, double dci, const double2 *x_orbit,
+                                                      const double2 *k_orbit, uint32_t x_last, uint32_t k_last, uint32_t x_end,
+                                                      uint32_t k_end, double squared, PtDeState &s) {
+    const bool on_k = JULIA && s.on_k;
+    const double2 *X = on_k ? k_orbit : x_orbit;
+    uint32_t last = on_k ? k_last : x_last, end = on_k ? k_end : x_end;
+    uint32_t m = s.m;
+    bool k_now = on_k;
+    const double b0 = JULIA ? 0.0 : 1.0;
+    double dzr = s.dzr, dzi = s.dzi, zr = s.zr, zi = s.zi, dr = s.dr, di = s.di;
+    double2 Z = X[min(m, last)], N = X[min(m + 1u, last)]; /* m < last at the top of every step */
+    const double2 K1 = k_orbit[1];                         /* the entry after a rebase; K_0 = R_0 = 0 */
+    uint32_t i = 0;
+    for (; i < steps; i++) {
+        const double2 P = X[min(m + 2u, last)]; /* X_{m+2}: next step's X_{m+1} if it does not rebase */
+        const double tr = Z.x + zr, ti = Z.y + zi;
+        const double ur = zr + zr, ui = zi + zi; /* the derivative's t: from the z before the step */
+        const double ndr = __builtin_fma(tr, dzr, __builtin_fma(-ti, dzi, dcr));
+        const double ndi = __builtin_fma(tr, dzi, __builtin_fma(ti, dzr, dci));
+        const double ner = __builtin_fma(ur, dr, __builtin_fma(-ui, di, b0));
+        const double nei = __builtin_fma(ur, di, ui * dr);
+        m++;
+        zr = N.x + ndr;
+        zi = N.y + ndi;
+        dzr = ndr;
+        dzi = ndi;
+        dr = ner;
+        di = nei;
+        const double dist = zr * zr + zi * zi;
+        if (dist > squared) break; /* this lane leaves EXEC; the wave goes on while any lane is left */
+        if (dist < dzr * dzr + dzi * dzi || m == end) {
+            dzr = zr;
+            dzi = zi;
+            m = 0;
+            if (JULIA) {
+                X = k_orbit;
+                last = k_last;
+                end = k_end;
+                k_now = true;
+            }
+            Z = make_double2(0.0, 0.0);
+            N = K1;
+        } else {
+            Z = N;
+            N = P;
+        }
+    }
+    const bool escaped = i < steps;
+    s.zr = zr;
+    s.zi = zi;
+    s.dzr = escaped ? 0.0 : dzr;
+    s.dzi = escaped ? 0.0 : dzi;
+    s.dr = dr;
+    s.di = di;
+    s.m = escaped ? 0u : m;
+    s.on_k = !escaped && k_now;
+    return i;
+}
+
+__device__ __forceinline__ void de_state_store(uint64_t k, double *z, uint32_t *iters, double *dz, uint32_t *mm, double *der,
+                                               const PtDeState &s, uint32_t it) {
+    z[2 * k] = s.zr;
+    z[2 * k + 1] = s.zi;
+    iters[k] = it;
+    dz[2 * k] = s.dzr;
+    dz[2 * k + 1] = s.dzi;
+    mm[k] = s.m | (s.on_k ? kDeOnK : 0u);
+    der[2 * k] = s.dr;
+    der[2 * k + 1] = s.di;
+}
+
+/* escape_pt_state_kernel's shape with the derivative: the whole state, 56 bytes per pixel.  `ended`: bit 0 = X, bit 1 = K is
+ * ended by escape.  An algorithm without orbits writes zeros into all five arrays. */
+template <bool JULIA>
+__global__ __launch_bounds__(kDeThreads) void escape_pt_de_state_kernel(const fr_kparams p, double *__restrict__ z,
+                                                                        uint32_t *__restrict__ iters, double *__restrict__ dz,
+                                                                        uint32_t *__restrict__ mm, double *__restrict__ der,
+                                                                        const double2 *__restrict__ x_orbit,
+                                                                        const double2 *__restrict__ k_orbit, const uint32_t x_last,
+                                                                        const uint32_t k_last, const uint32_t ended) {
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
+    const uint32_t tid = threadIdx.x;
+    const DeLane l = de_lane(p, tid);
+    de_stage<true>(p, tid, l.col0, l.row0, s_re, s_im);
+    __syncthreads();
+    if (!l.valid) return;
+    const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0;
+    PtDeState s{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0u, false};
+    uint32_t it = 0;
+    if (escape_algo) {
+        const double off_re = s_re[l.lx], off_im = s_im[l.ly];
+        s.m = JULIA ? 0u : 1u;
+        s.dzr = off_re;
+        s.dzi = off_im;
+        const double2 X0 = x_orbit[min(s.m, x_last)];
+        s.zr = X0.x + s.dzr;
+        s.zi = X0.y + s.dzi;
+        s.dr = 1.0;
+        it = orbit_pt_de_state<JULIA>(p.iterations, JULIA ? 0.0 : off_re, JULIA ? 0.0 : off_im, x_orbit, k_orbit, x_last, k_last,
+                                      (ended & 1u) ? x_last : ~0u, (ended & 2u) ? k_last : ~0u, p.limit * p.limit, s);
+    }
+    de_state_store((uint64_t)l.r * p.ncols + l.cx, z, iters, dz, mm, der, s, it);
+}
+
+/* escape_extend_pt_kernel's shape with the derivative: the stored state continued from cap `from` to p.iterations in place, on
+ * the orbits of the new cap.  `iters` is read first and a workgroup with no pixel at `from` ends there, having written nothing;
+ * a finished pixel's z, dz, m and der are neither loaded nor stored. */
+template <bool JULIA>
+__global__ __launch_bounds__(kDeThreads) void escape_extend_pt_de_kernel(const fr_kparams p, double *z, uint32_t *iters, double *dz,
+                                                                         uint32_t *mm, double *der, const uint32_t from,
+                                                                         const double2 *__restrict__ x_orbit,
+                                                                         const double2 *__restrict__ k_orbit, const uint32_t x_last,
+                                                                         const uint32_t k_last, const uint32_t ended) {
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
+    const uint32_t tid = threadIdx.x;
+    const DeLane l = de_lane(p, tid);
+    const uint64_t k = (uint64_t)l.r * p.ncols + l.cx;
+    uint32_t done = 0;
+    if (l.valid) done = iters[k];
+    const bool running = l.valid && done == from;
+    if (!__syncthreads_or(running ? 1 : 0)) return; /* whole workgroup (uniform) */
+    if (!JULIA) { /* dc = the pixel's offset, staged as the render stages it; Julia's dc is 0 */
+        de_stage<true>(p, tid, l.col0, l.row0, s_re, s_im);
+        __syncthreads();
+    }
+    if (!running) return;
+    const uint32_t word = mm[k];
+    PtDeState s;
+    s.zr = z[2 * k];
+    s.zi = z[2 * k + 1];
+    s.dzr = dz[2 * k];
+    s.dzi = dz[2 * k + 1];
+    s.dr = der[2 * k];
+    s.di = der[2 * k + 1];
+    s.on_k = JULIA && (word & kDeOnK) != 0;
+    /* m < last of the orbit followed in every state this view produces; the clamp keeps foreign data inside the orbit */
+    s.m = min(word & ~kDeOnK, (s.on_k ? k_last : x_last) - 1u);
+    const uint32_t it = orbit_pt_de_state<JULIA>(p.iterations - from, JULIA ? 0.0 : s_re[l.lx], JULIA ? 0.0 : s_im[l.ly], x_orbit, k_orbit,
+                                                 x_last, k_last, (ended & 1u) ? x_last : ~0u, (ended & 2u) ? k_last : ~0u,
+                                                 p.limit * p.limit, s);
+    de_state_store(k, z, iters, dz, mm, der, s, from + it); /* it == M - N on exhaustion: the new cap */
+}
+
 /* ---- distance and shaded colour over stored results ------------------------------------------------------------------------- */
 
 /* D of the definition; `pixels` = (double)height * min(|scale.re|, |scale.im|), formed by the host */
@@ -276,8 +483,9 @@ namespace {
 
 const char *const kDeScope =
     "distance estimation is defined for FR_PRECISION_F64 and FR_PRECISION_PT (dd or wide centre) on one device; FR_PRECISION_F32, "
-    "FR_PRECISION_DD, BLA-PT, SCALED PT, block-cyclic and multi-device renders, supersampling, fr_pixel and raising a DE view's cap in "
-    "place are out of scope";
+    "FR_PRECISION_DD, BLA-PT, SCALED PT, block-cyclic and multi-device renders, supersampling and fr_pixel are out of scope, and so is "
+    "raising a DE view's cap with fr_escape_extend* on (z, iters) alone: fr_escape_extend_de(_device) (F64) and "
+    "fr_escape_extend_de_pt(_device) (PT) continue the derivative with them";
 
 /* the launch of rows [y0, y1) with their derivatives; arguments already checked */
 int de_launch(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const fr_kparams &p, double *d_z, uint32_t *d_iters,
@@ -365,6 +573,158 @@ int de_rows_host(const fr_config *cfg, int precision, const Centre &c, bool wide
     return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), der, nullptr, false, de_rows(cfg, precision, c, y0, y1));
 }
 
+/* ---- RESUMABLE DE: the state render of PT and the two extensions ------------------------------------------------------------ */
+
+/* The arrays of a RESUMABLE DE call and what is left of its domain after the road's (check_state's order and its M < N text,
+ * fr_ctx.h).  pt: the five arrays of the PT state, else the F64 road's three.  `from` = nullptr: the state render.  *work = false:
+ * a legal call with nothing to do (no rows; for an extension also M == N or an algorithm without orbits). */
+int de_state_check(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, bool pt, const void *z, const void *iters,
+                   const void *dz, const void *m, const void *der, bool *work) {
+    *work = false;
+    if (from && cfg->iterations < *from)
+        return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from a stored state");
+    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
+    if (pt) {
+        if (!z || !iters || !dz || !m || !der)
+            return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the DE state of PT is z, iters, dz, m and der, all five");
+        if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(dz) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) ||
+            (reinterpret_cast<uintptr_t>(iters) & 3u) || (reinterpret_cast<uintptr_t>(m) & 3u))
+            return fail(FR_ERR_INVALID_ARGUMENT, "z, dz and der must be 8-byte aligned, iters and m 4-byte aligned");
+    } else {
+        if (!z || !iters || !der) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the extension of a DE view needs z, iters and der, all three");
+        if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u))
+            return fail(FR_ERR_INVALID_ARGUMENT, "z and der must be 8-byte aligned, iters 4-byte aligned");
+    }
+    *work = !from || (cfg->iterations != *from && (cfg->algo == FR_ALGO_MANDELBROT || cfg->algo == FR_ALGO_JULIA));
+    return FR_OK;
+}
+
+/* the domain of the F64 extension short of its arrays */
+int de_extend_f64_check(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1) {
+    const int rc = check_rows(cfg, y0, y1);
+    if (rc != FR_OK) return rc;
+    if (precision == FR_PRECISION_PT)
+        return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_PT: a DE view's PT state is (z, iters, dz, m, der), not the three arrays of "
+                                             "fr_escape_rows_de; fr_escape_rows_de_pt_state(_device) stores that state and "
+                                             "fr_escape_extend_de_pt(_device) continues it");
+    if (precision != FR_PRECISION_F64) return fail(FR_ERR_INVALID_ARGUMENT, kDeScope);
+    if (!(cfg->limit <= 0x1p20))
+        return fail(FR_ERR_INVALID_ARGUMENT, "distance estimation: limit must be <= 2^20 (the bound that keeps the derivative's overflow "
+                                             "below one pixel rests on it)");
+    return FR_OK;
+}
+
+/* the domain of the PT state calls short of their arrays: PT's with a dd centre, WIDE PT's with a wide one, and DE's limit */
+int de_pt_state_domain(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1) {
+    int rc = check_rows(cfg, y0, y1);
+    if (rc != FR_OK) return rc;
+    if (c.wide && c.pos_lo) return fail(FR_ERR_INVALID_ARGUMENT, "distance estimation: pos_lo must be NULL when a wide centre is given");
+    rc = c.check(cfg, FR_PRECISION_PT);
+    if (rc != FR_OK) return rc;
+    if (!(cfg->limit <= 0x1p20))
+        return fail(FR_ERR_INVALID_ARGUMENT, "distance estimation: limit must be <= 2^20 (the bound that keeps the derivative's overflow "
+                                             "below one pixel rests on it)");
+    return FR_OK;
+}
+
+/* the F64 extension of rows [y0, y1) between the profiling events; arguments already checked, there is work */
+int de_extend_f64_rows(const fr_config *cfg, uint32_t y0, uint32_t y1, uint32_t from, double *d_z, uint32_t *d_iters, double *d_der,
+                       hipStream_t stream) {
+    return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) -> int {
+        kname = "escape_extend_de_kernel";
+        if (p.ncols == 0 || p.nrows == 0 || p.iterations <= from) return FR_OK;
+        dim3 grid, block;
+        HIP_TRY(fr_deep_grid(p, grid, block));
+        if (cfg->algo == FR_ALGO_JULIA)
+            escape_extend_de_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, from);
+        else
+            escape_extend_de_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, from);
+        HIP_TRY(hipGetLastError());
+        return FR_OK;
+    });
+}
+
+/* the PT state render (from == nullptr) or its extension from *from, on the context's orbits of cfg's cap, which the cache
+ * continues from those of a lower cap of the same view (fr_pt.hip: orbit_for) */
+int de_pt_state_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, double *d_z,
+                     uint32_t *d_iters, double *d_dz, uint32_t *d_m, double *d_der, hipStream_t stream) {
+    return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) -> int {
+        kname = from ? "escape_extend_pt_de_kernel" : "escape_pt_de_state_kernel";
+        const bool julia = cfg->algo == FR_ALGO_JULIA;
+        const bool orbits = julia || cfg->algo == FR_ALGO_MANDELBROT;
+        if (p.ncols == 0 || p.nrows == 0 || (from && (!orbits || p.iterations <= *from))) return FR_OK;
+        dim3 grid, block;
+        HIP_TRY(fr_deep_grid(p, grid, block));
+        std::shared_ptr<PtOrbit> keep; /* alive until the launch is enqueued */
+        PtOrbitView v;
+        if (orbits) {
+            const int rc = pt_orbit_view(ctx, cfg, c, keep, v);
+            if (rc != FR_OK) return rc;
+        }
+        if (from) {
+            if (julia)
+                escape_extend_pt_de_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_dz, d_m, d_der, *from, v.x, v.k, v.x_last,
+                                                                             v.k_last, v.ended);
+            else
+                escape_extend_pt_de_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_dz, d_m, d_der, *from, v.x, v.k, v.x_last,
+                                                                              v.k_last, v.ended);
+        } else if (julia) {
+            escape_pt_de_state_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_dz, d_m, d_der, v.x, v.k, v.x_last, v.k_last, v.ended);
+        } else {
+            escape_pt_de_state_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_dz, d_m, d_der, v.x, v.k, v.x_last, v.k_last, v.ended);
+        }
+        HIP_TRY(hipGetLastError());
+        return FR_OK;
+    });
+}
+
+int de_pt_state_device(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z, void *d_iters,
+                       void *d_dz, void *d_m, void *d_der, void *hip_stream) {
+    int rc = de_pt_state_domain(cfg, c, y0, y1);
+    if (rc != FR_OK) return rc;
+    bool work;
+    rc = de_state_check(cfg, y0, y1, from, true, d_z, d_iters, d_dz, d_m, d_der, &work);
+    if (rc != FR_OK || !work) return rc;
+    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
+        return de_pt_state_rows(ctx, cfg, c, y0, y1, from, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
+                                static_cast<double *>(d_dz), static_cast<uint32_t *>(d_m), static_cast<double *>(d_der), stream);
+    });
+}
+
+/* The host form of the five arrays, done here as fr_distance_rows does its own (host_raw carries four): z, dz and der in the
+ * context's z scratch, iters and m in its iters scratch; an extension uploads them first. */
+int de_pt_state_host(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, double *z, uint32_t *iters,
+                     double *dz, uint32_t *m, double *der) {
+    int rc = de_pt_state_domain(cfg, c, y0, y1);
+    if (rc != FR_OK) return rc;
+    bool work;
+    rc = de_state_check(cfg, y0, y1, from, true, z, iters, dz, m, der, &work);
+    if (rc != FR_OK || !work) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0), zb = npx * 2 * sizeof(double), ib = npx * sizeof(uint32_t);
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = ctx->reserve(ctx->z, 3 * zb);
+    if (rc == FR_OK) rc = ctx->reserve(ctx->iters, 2 * ib);
+    if (rc != FR_OK) return rc;
+    char *const dd = static_cast<char *>(ctx->z.ptr), *const du = static_cast<char *>(ctx->iters.ptr);
+    const struct {
+        void *host, *dev;
+        size_t bytes;
+    } arrays[5] = {{z, dd, zb}, {iters, du, ib}, {dz, dd + zb, zb}, {m, du + ib, ib}, {der, dd + 2 * zb, zb}};
+    if (from)
+        for (const auto &a : arrays) HIP_TRY(hipMemcpyAsync(a.dev, a.host, a.bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = de_pt_state_rows(*ctx, cfg, c, y0, y1, from, static_cast<double *>(arrays[0].dev), static_cast<uint32_t *>(arrays[1].dev),
+                          static_cast<double *>(arrays[2].dev), static_cast<uint32_t *>(arrays[3].dev), static_cast<double *>(arrays[4].dev),
+                          ctx->stream);
+    if (rc != FR_OK) return rc;
+    for (const auto &a : arrays) HIP_TRY(hipMemcpyAsync(a.host, a.dev, a.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FR_OK;
+}
+
 /* the domain of the calls over stored results, short of their output */
 int de_stored_check(const fr_config *cfg, const void *z, const void *iters, const void *der, size_t n) {
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
@@ -419,6 +779,57 @@ int fr_escape_rows_de_pt_wide_device(const fr_config *cfg, const fr_wide_centre 
 int fr_escape_rows_de_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z, uint32_t *iters,
                               double *der) {
     return de_rows_host(cfg, FR_PRECISION_PT, Centre{nullptr, centre}, true, y0, y1, z, iters, der);
+}
+
+/* ---- RESUMABLE DE (include/fractal_hip.h) ---- */
+
+int fr_escape_extend_de_device(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint32_t from_iterations, void *d_z,
+                               void *d_iters, void *d_der, void *hip_stream) {
+    int rc = de_extend_f64_check(cfg, precision, y0, y1);
+    if (rc != FR_OK) return rc;
+    bool work;
+    rc = de_state_check(cfg, y0, y1, &from_iterations, false, d_z, d_iters, nullptr, nullptr, d_der, &work);
+    if (rc != FR_OK || !work) return rc;
+    return device_form(hip_stream, [&](Ctx &, hipStream_t stream) {
+        return de_extend_f64_rows(cfg, y0, y1, from_iterations, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
+                                  static_cast<double *>(d_der), stream);
+    });
+}
+
+int fr_escape_extend_de(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint32_t from_iterations, double *z, uint32_t *iters,
+                        double *der) {
+    int rc = de_extend_f64_check(cfg, precision, y0, y1);
+    if (rc != FR_OK) return rc;
+    bool work;
+    rc = de_state_check(cfg, y0, y1, &from_iterations, false, z, iters, nullptr, nullptr, der, &work);
+    if (rc != FR_OK || !work) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    /* z and der share the context's z scratch, as in fr_escape_rows_de; uploaded first, as fr_escape_extend does */
+    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), der, nullptr, true,
+                    [&](Ctx &, double *d_z, uint32_t *d_iters, double *d_der, uint32_t *, hipStream_t stream) {
+                        return de_extend_f64_rows(cfg, y0, y1, from_iterations, d_z, d_iters, d_der, stream);
+                    });
+}
+
+int fr_escape_rows_de_pt_state_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, uint32_t y0,
+                                      uint32_t y1, void *d_z, void *d_iters, void *d_dz, void *d_m, void *d_der, void *hip_stream) {
+    return de_pt_state_device(cfg, Centre{pos_lo, centre}, y0, y1, nullptr, d_z, d_iters, d_dz, d_m, d_der, hip_stream);
+}
+
+int fr_escape_rows_de_pt_state(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
+                               double *z, uint32_t *iters, double *dz, uint32_t *m, double *der) {
+    return de_pt_state_host(cfg, Centre{pos_lo, centre}, y0, y1, nullptr, z, iters, dz, m, der);
+}
+
+int fr_escape_extend_de_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
+                                  uint32_t from_iterations, void *d_z, void *d_iters, void *d_dz, void *d_m, void *d_der,
+                                  void *hip_stream) {
+    return de_pt_state_device(cfg, Centre{pos_lo, centre}, y0, y1, &from_iterations, d_z, d_iters, d_dz, d_m, d_der, hip_stream);
+}
+
+int fr_escape_extend_de_pt(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
+                           uint32_t from_iterations, double *z, uint32_t *iters, double *dz, uint32_t *m, double *der) {
+    return de_pt_state_host(cfg, Centre{pos_lo, centre}, y0, y1, &from_iterations, z, iters, dz, m, der);
 }
 
 int fr_distance_rows_device(const fr_config *cfg, const void *d_z, const void *d_iters, const void *d_der, size_t n, void *d_out,

@@ -369,9 +369,36 @@ typedef struct fr_config {
  * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): the road's own domain; limit <= 2^20;
  * thickness finite and in [0, 2^20]; F64 takes no pos_lo; PT with a wide centre keeps WIDE PT's |scale| <= 2^440.
  * Out of scope, refused by name: FR_PRECISION_F32, FR_PRECISION_DD, BLA-PT (a skipped block has no per-step derivative here)
- * and SCALED PT; block-cyclic and multi-device renders; supersampling; fr_pixel; raising a DE view's cap in place — AFTER
- * fr_escape_extend* ON (z, iters), A der ARRAY IS STALE: it is the derivative at the old cap's position, and no call
- * continues it.  Render the view again with fr_escape_rows_de at the new cap. */
+ * and SCALED PT; block-cyclic and multi-device renders; supersampling; fr_pixel.  AFTER fr_escape_extend* ON (z, iters) ALONE,
+ * A der ARRAY IS STALE: it is the derivative at the old cap's position, and those calls do not know of it.  The calls that
+ * continue all arrays are fr_escape_extend_de(_device) on the F64 road and fr_escape_extend_de_pt(_device) on PT (RESUMABLE DE
+ * below); a PT view whose cap will be raised is rendered with fr_escape_rows_de_pt_state, not fr_escape_rows_de. */
+/*
+ * RESUMABLE DE (fr_escape_extend_de, fr_escape_rows_de_pt_state, fr_escape_extend_de_pt below): the state that lets a DE view's
+ * cap be raised in place, derivative included.  The derivative is part of the loop's state like everything else.
+ *   F64.  The stored (z, iters, der) of fr_escape_rows_de IS the resumable state: exhaustion returns (previous, iterations, d),
+ *   and c is a function of the pixel, recomputed by the render's own coordinate code.  Continuing a pixel with iters == N for
+ *   M - N steps of DE's F64 step from (previous, d) is the loop at cap M, bit for bit in all three arrays.
+ *   PT (dd or wide centre).  The resumable state of a pixel after N steps is (z, dz, m, onK, d), stored as (z, iters, dz, m,
+ *   der), 56 bytes per pixel, in RESUMABLE PT's form (bit 31 of m: a Julia pixel on K).  It is RESUMABLE PT's state run — PT's
+ *   step sequence with the rebase rule "dist < |dz|^2, or m == last of an orbit ENDED BY ESCAPE" — with DE's derivative beside
+ *   it: in every step, from the z before the step,
+ *     t  = (z.re + z.re, z.im + z.im)
+ *     nd = (fma(t.re, d.re, fma(-t.im, d.im, b0)), fma(t.re, d.im, t.im * d.re)),     d0 = (1, 0).
+ *   Escape stores (next, i, dz = (0, 0), m = 0, nd); exhaustion stores (z, N, dz, m | onK << 31, d).  N = 0 stores RESUMABLE PT's
+ *   initial state with der = (1, 0).  An algorithm without orbits writes zeros into all five arrays.
+ *   CLAIM 1: for every N, z, iters and der of the PT state run equal fr_escape_rows_de's (PT) bit for bit, and dz and m equal
+ *   fr_escape_rows_pt_state's.
+ *   Why: the derivative reads only z.  RESUMABLE PT's claim says the z sequence of the state run is PT's; the one cap-dependent
+ *   rebase, which the state rule leaves out, changes (dz, m) and never z.
+ *   CLAIM 2: continuing the state from N for M - N steps on the orbits of cap M gives the state run at cap M, bit for bit in
+ *   all five arrays (a NaN in der is any NaN, as in DE).
+ *   Why: RESUMABLE PT's argument for (z, iters, dz, m), plus "d is a function of the z sequence": d after step i is determined
+ *   by d0 and z_0 .. z_i, which a state run to N and a state run to M share up to N.
+ * Domain: DE's, unchanged (limit <= 2^20; PT's domain with a dd centre, WIDE PT's |scale| <= 2^440 with a wide one); M >= N.
+ * The overflow bound of DE is about the step that is returned and does not depend on where a run was
+ * interrupted: a continued derivative takes the same values, overflow included, as the uninterrupted one.
+ * DE on BLA-PT and SCALED PT stays out of scope, and so their states are not resumable with a derivative either. */
 #define FR_BLA_DEFAULT_BITS 40
 #define FR_PT_MAX_ITERATIONS (1u << 24)
 #define FR_WIDE_MAX_WORDS 16
@@ -1037,6 +1064,50 @@ int fr_escape_rows_de_pt_wide_device(const fr_config *cfg, const fr_wide_centre 
                                      void *d_iters, void *d_der, void *hip_stream);
 int fr_escape_rows_de_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z,
                               uint32_t *iters, double *der);
+/* RESUMABLE DE (defined at fr_precision above): a kept DE view answers an iterations change in place, derivative included.
+ *
+ * The F64 road: raise the cap of the (z, iters, der) that fr_escape_rows_de(_device) wrote, N = from_iterations -> M =
+ * cfg->iterations, cfg_N = cfg with iterations = N:
+ *   Precondition: the arrays hold what fr_escape_rows_de_device(cfg_N, FR_PRECISION_F64, NULL, y0, y1, ...) writes.
+ *   Result: after the call they hold what the same call writes for cfg, bit for bit in all three arrays (z and iters are then
+ *   also fr_escape_rows_device's at M).
+ *   A pixel with iters[k] != N is finished: only that word is read; its z and der are neither loaded nor written.  Values of
+ *   iters[k] above N are foreign data and are left alone like finished pixels.
+ * The library CANNOT check the precondition, and the call is not idempotent (in arrays that already hold cap M, iters[k] == N
+ * means "escaped at step N").  Domain (else FR_ERR_INVALID_ARGUMENT, before any device work): precision FR_PRECISION_F64 —
+ * FR_PRECISION_PT is refused with a message that names fr_escape_extend_de_pt, everything else with DE's scope message; limit
+ * <= 2^20; M >= N — M == N is a legal no-op that needs no device, as y0 == y1 is; all three arrays, z and der 8-byte aligned,
+ * iters 4-byte aligned (y0 == y1 needs none).  An algorithm without orbits: nothing is done.  The _device form is asynchronous
+ * on hip_stream, allocates nothing and takes no lock; the host form uploads, launches, downloads and synchronises as
+ * fr_escape_extend does.  With profiling on, fr_last_kernel_name reports escape_extend_de_kernel. */
+int fr_escape_extend_de_device(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint32_t from_iterations, void *d_z,
+                               void *d_iters, void *d_der, void *hip_stream);
+int fr_escape_extend_de(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint32_t from_iterations, double *z,
+                        uint32_t *iters, double *der);
+/* PT.  One road for both centres, as the fr_*_pt_bla calls take them: `centre` non-NULL selects WIDE PT's orbits and domain
+ * (pos_lo must then be NULL and cfg->pos is not read), otherwise the centre is PT's (cfg->pos, pos_lo), pos_lo NULL = (0, 0).
+ * fr_escape_rows_de_pt_state(_device): rows [y0, y1) with their DE state: z, dz, der 2 doubles per pixel (8-byte aligned),
+ * iters, m one uint32 (4-byte aligned), all five required (y0 == y1 needs none and no device), k = (y - y0) * width + x.
+ * z, iters, der are fr_escape_rows_de's (PT), dz and m fr_escape_rows_pt_state's, bit for bit.
+ * fr_escape_extend_de_pt(_device): raise the cap of that state IN PLACE, N = from_iterations -> M = cfg->iterations, with
+ * fr_escape_extend_pt's contract: the precondition (the arrays hold the state render of cfg_N) cannot be checked — arrays from
+ * another view or cap are continued as if they were this one's, an index m beyond the orbit is brought inside it, nothing
+ * more; the call is not idempotent; a pixel with iters[k] != N has only that word read and nothing of it loaded or written,
+ * values above N included; M == N and y0 == y1 are no-ops that need no device; M < N is refused; an algorithm without orbits:
+ * nothing is done.  Every refusal happens before any device work.
+ * The calls use the context's orbit cache: a DE state render, a DE render and a PT render of one view share one orbit, and an
+ * extension continues the orbit of the lower cap instead of recomputing it (fr_debug_pt_orbit_cache shows it).  The _device
+ * forms allocate nothing.  With profiling on, fr_last_kernel_name reports escape_pt_de_state_kernel /
+ * escape_extend_pt_de_kernel. */
+int fr_escape_rows_de_pt_state_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, uint32_t y0,
+                                      uint32_t y1, void *d_z, void *d_iters, void *d_dz, void *d_m, void *d_der, void *hip_stream);
+int fr_escape_rows_de_pt_state(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
+                               double *z, uint32_t *iters, double *dz, uint32_t *m, double *der);
+int fr_escape_extend_de_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, uint32_t y0,
+                                  uint32_t y1, uint32_t from_iterations, void *d_z, void *d_iters, void *d_dz, void *d_m, void *d_der,
+                                  void *hip_stream);
+int fr_escape_extend_de_pt(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
+                           uint32_t from_iterations, double *z, uint32_t *iters, double *dz, uint32_t *m, double *der);
 /* D of n stored results, one double per pixel (8-byte aligned).  Reads only height, scale and iterations from cfg.  n <= 2^40;
  * n == 0 needs no device. */
 int fr_distance_rows_device(const fr_config *cfg, const void *d_z, const void *d_iters, const void *d_der, size_t n, void *d_out,
