@@ -809,10 +809,15 @@ def get_image_auto(config, percentile=0.99, precision=Precision.F64, pos_lo=None
     return image, exposure
 
 
-def _de_call(precision, pos_lo, centre, device):
+def _de_call(precision, pos_lo, centre, device, bla=None, opts=None):
     """the DE render the keywords select, in its host or device form: (function, leading arguments behind the config, keep-alive)"""
     suffix = "_device" if device else ""
     lib = _native.load()
+    if bla is not None:  # DE ON BLA-PT; _deep_call's checks: Precision.PT, no opts, the bits, no pos_lo beside a centre
+        _family, pre, keep = _deep_call(precision, pos_lo, centre, bla=bla, opts=opts)
+        return getattr(lib, "fr_escape_rows_de_pt_bla" + suffix), pre, keep
+    if opts is not None:
+        raise ValueError("opts= goes with bla= only, which refuses it: a DE render has one kernel per road")
     if centre is not None:
         family, pre, keep = _deep_call(precision, pos_lo, centre)  # its checks: Precision.PT, no pos_lo
         return getattr(lib, "fr_escape_rows_de_pt_wide" + suffix), pre, keep
@@ -820,13 +825,15 @@ def _de_call(precision, pos_lo, centre, device):
     return getattr(lib, "fr_escape_rows_de" + suffix), (int(precision), lo), keep
 
 
-def escape_rows_de(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, centre=None):
+def escape_rows_de(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, centre=None, bla=None, opts=None):
     """fr_escape_rows_de / fr_escape_rows_de_pt_wide: rows [y0, y1) with the orbit's derivative (include/fractal_hip.h, "DE"):
     (z float64 [rows, width, 2], iters uint32 [rows, width], der float64 [rows, width, 2]).  z and iters are the road's own,
     bit for bit; der is the derivative of the returned position (d/dc for Mandelbrot, d/dz0 for Julia).  precision is
-    Precision.F64 or Precision.PT (pos_lo= or centre=, a WideCentre, as escape_rows takes them); everything else is refused."""
+    Precision.F64 or Precision.PT (pos_lo= or centre=, a WideCentre, as escape_rows takes them); everything else is refused.
+    bla= (None: off; 0: the default bits; 24 .. 53; needs Precision.PT and takes no opts, as bla= does elsewhere): DE ON BLA-PT,
+    fr_escape_rows_de_pt_bla — z and iters are escape_rows(..., bla=)'s bit for bit, der goes through the table's skips."""
     y0, y1 = _rows(config, y0, y1)
-    fn, pre, _keep = _de_call(precision, pos_lo, centre, False)
+    fn, pre, _keep = _de_call(precision, pos_lo, centre, False, bla, opts)
     z = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
     it = np.empty((y1 - y0, config.width), dtype=np.uint32)
     der = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
@@ -835,11 +842,12 @@ def escape_rows_de(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, 
 
 
 def escape_rows_de_device(config, z_ptr, iters_ptr, der_ptr, y0=0, y1=None, precision=Precision.F64, pos_lo=None, centre=None,
-                          stream=None):
-    """fr_escape_rows_de_device / fr_escape_rows_de_pt_wide_device: the same into DEVICE arrays (raw pointers as ints, all three
-    required), asynchronously on `stream`: the 36 bytes per pixel a GUI keeps to vary thickness without an orbit."""
+                          stream=None, bla=None, opts=None):
+    """fr_escape_rows_de_device / fr_escape_rows_de_pt_wide_device / fr_escape_rows_de_pt_bla_device (bla=, as escape_rows_de takes
+    it): the same into DEVICE arrays (raw pointers as ints, all three required), asynchronously on `stream`: the 36 bytes per
+    pixel a GUI keeps to vary thickness without an orbit."""
     y0, y1 = _rows(config, y0, y1)
-    fn, pre, _keep = _de_call(precision, pos_lo, centre, True)
+    fn, pre, _keep = _de_call(precision, pos_lo, centre, True, bla, opts)
     _native.check(fn(C.byref(config), *pre, y0, y1, z_ptr or None, iters_ptr or None, der_ptr or None, _stream(stream)))
 
 
@@ -974,10 +982,10 @@ def colour_de_rows_device(config, z_ptr, iters_ptr, der_ptr, n, thickness, out_p
                                                           float(thickness), int(channels), out_ptr or None, _stream(stream)))
 
 
-def get_image_de(config, thickness=1.0, precision=Precision.F64, pos_lo=None, centre=None):
-    """get_image with distance shading: uint8 [height, width, 3].  escape_rows_de on the road the keywords select, then
-    colour_image_de: filaments thinner than a pixel stay visible as dark lines `thickness` pixels wide."""
-    z, it, der = escape_rows_de(config, precision=precision, pos_lo=pos_lo, centre=centre)
+def get_image_de(config, thickness=1.0, precision=Precision.F64, pos_lo=None, centre=None, bla=None, opts=None):
+    """get_image with distance shading: uint8 [height, width, 3].  escape_rows_de on the road the keywords select (bla=: DE ON
+    BLA-PT), then colour_image_de: filaments thinner than a pixel stay visible as dark lines `thickness` pixels wide."""
+    z, it, der = escape_rows_de(config, precision=precision, pos_lo=pos_lo, centre=centre, bla=bla, opts=opts)
     return colour_image_de(config, z, it, der, thickness)
 
 

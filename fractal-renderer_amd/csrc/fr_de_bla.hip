@@ -1,0 +1,288 @@
+/*
+ * fr_de_bla.hip — DE ON BLA-PT (include/fractal_hip.h, "DE ON BLA-PT"): BLA-PT's pixel loop (fr_bla.hip: orbit_bla) with the
+ * orbit's derivative d carried beside it, through the plain steps as DE carries it (fr_de.hip) and through the table's skips:
+ * a skip over 2^K steps is d' = A d + B with the entry's own coefficients, since the table's merge A = Ay Ax, B = Ay Bx + By is
+ * the recurrence of d' = 2 X d + b0 over the block.  tests/de_bla_model.c restates the definition; tests/test_gpu_de_bla.py
+ * compares the two bit for bit.
+ *
+ * Nothing is added to the table and none is rebuilt: orbits and tables are the context's (fr_bla.h: bla_table_for), so a BLA-PT
+ * call and a DE call of the same view and bits share one table.
+ *
+ * escape_bla_de_kernel<JULIA>: escape_bla_kernel's escape mode — a workgroup of 4 waves renders 16 x 16 pixels, each wave one
+ * 8 x 8 tile, `off` staged in LDS, the level search by bisection over r2, 64-bit output offsets — writing z, iters and der.
+ * One pass:
+ *   - the search, the load of (A, B) behind the branch and the step of dz are orbit_bla's, operation for operation: the
+ *     derivative only reads, so z and iters are fr_escape_rows_pt_bla's bit for bit;
+ *   - ONE arithmetic path for the derivative of both kinds of lanes: nd = (fma(g.re, d.re, fma(-g.im, d.im, b.re)),
+ *     fma(g.re, d.im, fma(g.im, d.re, b.im))), where a lane that skips takes g = A and b = B (Julia: b = (+0, +0), its table
+ *     stores no B) and a lane that steps takes g = z + z and b = (b0, -0).  fma(x, y, -0) is x * y in every bit — the sum of a
+ *     product and -0 is the product, and -0 + -0 = -0 keeps a zero product's sign — so the plain lane's imaginary part is the
+ *     definition's fma(t.re, d.im, t.im * d.re), and on a view where no pass skips all three arrays are fr_escape_rows_de's (PT).
+ * The registers, the occupancy and the inner loop: profiles/de_bla_inner_loop_isa.txt.
+ *
+ * The calls, at the end of the file: BLA-PT's domain check (fr_bla.h: bla_check), DE's limit and arrays, then the profiled
+ * launch through the row-call bodies of fr_ctx.h (device_form, host_raw, profiled_rows).
+ */
+#include <cmath>
+#include <memory>
+
+#include "fr_bla.h"
+#include "fr_ctx.h"
+#include "fr_math.h"
+#include "fr_wide.h"
+
+namespace {
+
+/* the orbits and their tables as the kernel sees them (fr_bla.hip's BlaDev); Mandelbrot: the k fields repeat the x fields */
+struct DeBlaDev {
+    const double2 *x_orbit, *k_orbit;
+    const double *x_r2, *k_r2;     /* r2 of the levels >= 1 */
+    const double *x_coef, *k_coef; /* Mandelbrot: A.re, A.im, B.re, B.im per entry; Julia: A.re, A.im */
+    uint32_t x_last, k_last;
+    uint32_t x_n0, k_n0; /* entries of level 0: last - 1, or 0 for an empty table */
+};
+
+/* The pixel loop of "DE ON BLA-PT": orbit_bla (fr_bla.hip) with d = (er, ei) beside it.  Returns the escape index (or
+ * `iterations`), the final z in (out_re, out_im) and the derivative in (out_dr, out_di): the returned step's on escape, the
+ * last one's on exhaustion, (1, 0) for a cap of 0. */
+template <bool JULIA>
+__device__ __forceinline__ uint32_t orbit_bla_de(uint32_t iterations, double off_re, double off_im, const DeBlaDev &t, double squared,
+                                                 double &out_re, double &out_im, double &out_dr, double &out_di) {
+    const double2 *X = t.x_orbit;
+    const double *R2 = t.x_r2, *CF = t.x_coef;
+    uint32_t last = t.x_last, n0 = t.x_n0;
+    uint32_t m = JULIA ? 0u : 1u;
+    double dzr = off_re, dzi = off_im;
+    const double dcr = JULIA ? 0.0 : off_re, dci = JULIA ? 0.0 : off_im;
+    const double b0 = JULIA ? 0.0 : 1.0;
+    double2 Z = X[m]; /* X_m of the orbit followed */
+    double zr = Z.x + dzr, zi = Z.y + dzi;
+    double er = 1.0, ei = 0.0; /* d0 = (1, 0) */
+    uint32_t i = 0, result = iterations;
+    while (i < iterations) {
+        /* 1. the level: the largest k in 1 .. kc whose radius holds dz (orbit_bla's search) */
+        const double d2 = dzr * dzr + dzi * dzi;
+        const uint32_t j = m - 1u;
+        uint32_t K = 0;
+        if (m >= 1u && j < n0) {
+            uint32_t kc = j ? (uint32_t)__builtin_ctz(j) : 31u;          /* j % 2^k == 0 */
+            kc = min(kc, 31u - (uint32_t)__builtin_clz(n0 - j));         /* (j >> k) < n_k, that is j + 2^k <= n0 */
+            kc = min(kc, 31u - (uint32_t)__builtin_clz(iterations - i)); /* i + 2^k <= iterations */
+            uint32_t lo = 0, hi = kc;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi + 1u) >> 1;
+                if (d2 < R2[bla_level_offset(n0, mid) + (j >> mid)])
+                    lo = mid;
+                else
+                    hi = mid - 1u;
+            }
+            K = lo;
+        }
+        /* 2. the step dz' = A dz + c and the derivative's d' = g d + b */
+        double ar, ai, cr = dcr, ci = dci;
+        double gr, gi, br = b0, bi = -0.0; /* a plain step: fma(g.im, d.re, -0) is g.im * d.re, the definition's product */
+        uint32_t step = 1u;
+        if (K) {
+            const uint32_t e = bla_level_offset(n0, K) + (j >> K);
+            if (JULIA) { /* B dc is +0 = dc for every finite B; the derivative's b is (+0, +0) by definition */
+                const double2 A = reinterpret_cast<const double2 *>(CF)[e];
+                ar = A.x, ai = A.y;
+                br = 0.0, bi = 0.0;
+            } else {
+                const double4 AB = reinterpret_cast<const double4 *>(CF)[e];
+                ar = AB.x, ai = AB.y;
+                cr = __builtin_fma(AB.z, dcr, -(AB.w * dci));
+                ci = __builtin_fma(AB.z, dci, AB.w * dcr);
+                br = AB.z, bi = AB.w;
+            }
+            gr = ar, gi = ai;
+            step = 1u << K;
+        } else {
+            ar = Z.x + zr, ai = Z.y + zi; /* t = X_m + z */
+            gr = zr + zr, gi = zi + zi;   /* the derivative's t: from the z before the step */
+        }
+        const double ndr = __builtin_fma(ar, dzr, __builtin_fma(-ai, dzi, cr));
+        const double ndi = __builtin_fma(ar, dzi, __builtin_fma(ai, dzr, ci));
+        const double ner = __builtin_fma(gr, er, __builtin_fma(-gi, ei, br));
+        const double nei = __builtin_fma(gr, ei, __builtin_fma(gi, er, bi));
+        m += step;
+        i += step;
+        const double2 N = X[min(m, last)]; /* m <= last: 1 + ((j >> K) + 1) 2^K <= 1 + n0 */
+        zr = N.x + ndr;
+        zi = N.y + ndi;
+        dzr = ndr;
+        dzi = ndi;
+        er = ner; /* escape returns nd; otherwise d = nd */
+        ei = nei;
+        /* 3. the tests, PT's; a rebase never touches d */
+        const double dist = zr * zr + zi * zi;
+        if (dist > squared) { /* this lane leaves EXEC; the wave goes on while any lane is left */
+            result = i - 1u;
+            break;
+        }
+        if (dist < dzr * dzr + dzi * dzi || m == last) {
+            dzr = zr;
+            dzi = zi;
+            m = 0;
+            if (JULIA) {
+                X = t.k_orbit;
+                R2 = t.k_r2;
+                CF = t.k_coef;
+                last = t.k_last;
+                n0 = t.k_n0;
+            }
+            Z = make_double2(0.0, 0.0); /* K_0 = R_0 = 0 */
+        } else {
+            Z = N;
+        }
+    }
+    out_re = zr;
+    out_im = zi;
+    out_dr = er;
+    out_di = ei;
+    return result;
+}
+
+template <bool JULIA>
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_bla_de_kernel(const fr_kparams p, double *__restrict__ z,
+                                                                        uint32_t *__restrict__ iters, double *__restrict__ der,
+                                                                        const DeBlaDev t) {
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
+    const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
+
+    if (tid < kDeepBlockW + kDeepBlockH) {
+        /* off: coord_to_space (calc/src/lib.rs:181-197) without the final `+ pos`, PT's off */
+        const double width = (double)p.width, height = (double)p.height;
+        if (tid < kDeepBlockW) {
+            const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
+            s_re[tid] = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
+        } else {
+            const uint32_t r = row0 + (tid - kDeepBlockW);
+            const uint64_t y = (uint64_t)p.y_first + (uint64_t)(r / p.block_rows) * p.y_stride + r % p.block_rows;
+            s_im[tid - kDeepBlockW] = (((double)y / height) - 0.5) / p.scale_im;
+        }
+    }
+    __syncthreads();
+
+    const uint32_t wave = tid >> 6, lane = tid & 63;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
+    const uint32_t cx = col0 + lx, r = row0 + ly;
+    if (!(cx < p.ncols && r < p.nrows)) return;
+    const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0; /* the host picks JULIA from the algorithm */
+
+    double zr = 0.0, zi = 0.0, dr = 0.0, di = 0.0; /* an algorithm without orbits writes zeros */
+    uint32_t it = 0;
+    if (escape_algo) {
+        const double squared = p.limit * p.limit; /* calc/src/lib.rs:246 */
+        it = orbit_bla_de<JULIA>(p.iterations, s_re[lx], s_im[ly], t, squared, zr, zi, dr, di);
+    }
+    const uint64_t k = (uint64_t)r * p.ncols + cx;
+    z[2 * k] = zr;
+    z[2 * k + 1] = zi;
+    iters[k] = it;
+    der[2 * k] = dr;
+    der[2 * k + 1] = di;
+}
+
+}  // namespace
+
+using namespace fr;
+
+namespace {
+
+/* the launch of rows with their derivatives on the context's orbits and tables; arguments already checked */
+int launch_bla_de(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_kparams &p, double *d_z, uint32_t *d_iters,
+                  double *d_der, hipStream_t stream) {
+    if (p.ncols == 0 || p.nrows == 0) return FR_OK;
+    dim3 grid, block;
+    HIP_TRY(fr_deep_grid(p, grid, block));
+    const bool julia = cfg->algo == FR_ALGO_JULIA;
+    if (cfg->algo != FR_ALGO_MANDELBROT && !julia) { /* no escape-time algorithm: zeros, and no orbit is asked for */
+        escape_bla_de_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, DeBlaDev{});
+        HIP_TRY(hipGetLastError());
+        return FR_OK;
+    }
+    std::shared_ptr<PtOrbit> orbit; /* alive until the launch is enqueued, like the table */
+    std::shared_ptr<BlaTable> table;
+    PtOrbitView v;
+    const int rc = bla_table_for(ctx, cfg, c, bits, false, orbit, v, table);
+    if (rc != FR_OK) return rc;
+    const BlaTableDev &d = table->view;
+    DeBlaDev t{};
+    t.x_r2 = d.x_rad, t.k_r2 = d.k_rad;
+    t.x_coef = d.x_coef, t.k_coef = d.k_coef;
+    t.x_n0 = d.x_n0, t.k_n0 = d.k_n0;
+    t.x_orbit = v.x;
+    t.k_orbit = v.k;
+    t.x_last = v.x_last;
+    t.k_last = v.k_last;
+    if (julia)
+        escape_bla_de_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, t);
+    else
+        escape_bla_de_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, t);
+    HIP_TRY(hipGetLastError());
+    return FR_OK;
+}
+
+/* BLA-PT's domain (bits resolved in place), DE's limit, then the arrays; *work = false: no rows, nothing to do and no device
+ * needed */
+int check_bla_de(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1, const void *z, const void *iters,
+                 const void *der, bool *work) {
+    *work = false;
+    const int rc = bla_check(cfg, c, bits, y0, y1);
+    if (rc != FR_OK) return rc;
+    if (!(cfg->limit <= 0x1p20))
+        return fail(FR_ERR_INVALID_ARGUMENT, "distance estimation: limit must be <= 2^20 (the bound that keeps the derivative's overflow "
+                                             "below one pixel rests on it)");
+    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
+    if (!z || !iters || !der) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: a DE render writes z, iters and der, all three");
+    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "z and der must be 8-byte aligned, iters 4-byte aligned");
+    *work = true;
+    return FR_OK;
+}
+
+/* rows [y0, y1) as one launch between the profiling events: host_raw's callable, with der where it carries dz */
+auto bla_de_rows(const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1) {
+    return [=](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_der, uint32_t *, hipStream_t stream) {
+        return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) {
+            kname = "escape_bla_de_kernel";
+            return launch_bla_de(ctx, cfg, c, bits, p, d_z, d_iters, d_der, stream);
+        });
+    };
+}
+
+}  // namespace
+
+extern "C" {
+
+int fr_escape_rows_de_pt_bla_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
+                                    uint32_t y1, void *d_z, void *d_iters, void *d_der, void *hip_stream) {
+    const Centre c{pos_lo, centre};
+    bool work;
+    const int rc = check_bla_de(cfg, c, bits, y0, y1, d_z, d_iters, d_der, &work);
+    if (rc != FR_OK || !work) return rc;
+    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
+        return bla_de_rows(cfg, c, bits, y0, y1)(ctx, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
+                                                 static_cast<double *>(d_der), nullptr, stream);
+    });
+}
+
+int fr_escape_rows_de_pt_bla(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
+                             uint32_t y1, double *z, uint32_t *iters, double *der) {
+    const Centre c{pos_lo, centre};
+    bool work;
+    const int rc = check_bla_de(cfg, c, bits, y0, y1, z, iters, der, &work);
+    if (rc != FR_OK || !work) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    /* z and der share the context's z scratch, as in fr_escape_rows_de */
+    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), der, nullptr, false, bla_de_rows(cfg, c, bits, y0, y1));
+}
+
+} /* extern "C" */

@@ -399,6 +399,14 @@ inline std::vector<RGB> get_image_de(const Config &config, const fr_wide_centre 
         check(fr_escape_rows_de_pt_wide(&c, &centre, 0, c.height, z, iters, der));
     });
 }
+// ... on BLA-PT (include/fractal_hip.h, "DE ON BLA-PT"): the derivative goes through the table's skips; a dd centre
+// (config.pos, pos_lo; pos_lo may be null) or a wide centre, never both
+inline std::vector<RGB> get_image_de(const Config &config, Bla bla, double thickness = 1.0, const fr_imaginary *pos_lo = nullptr,
+                                     const fr_wide_centre *centre = nullptr) {
+    return get_image_de(config, thickness, [&](const Config &c, double *z, uint32_t *iters, double *der) {
+        check(fr_escape_rows_de_pt_bla(&c, pos_lo, centre, bla.bits, 0, c.height, z, iters, der));
+    });
+}
 // a kept view's recolour at another thickness, device arrays, asynchronous on hip_stream: no orbit is run
 inline void colour_de_rows_device(const Config &config, const void *d_z, const void *d_iters, const void *d_der, double thickness,
                                   void *d_out, int channels = 4, void *hip_stream = nullptr) {

@@ -368,8 +368,8 @@ typedef struct fr_config {
  *   gives fr_colour_rows_device's bytes exactly.
  * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): the road's own domain; limit <= 2^20;
  * thickness finite and in [0, 2^20]; F64 takes no pos_lo; PT with a wide centre keeps WIDE PT's |scale| <= 2^440.
- * Out of scope, refused by name: FR_PRECISION_F32, FR_PRECISION_DD, BLA-PT (a skipped block has no per-step derivative here)
- * and SCALED PT; block-cyclic and multi-device renders; supersampling; fr_pixel.  AFTER fr_escape_extend* ON (z, iters) ALONE,
+ * Out of scope of these calls, refused by name: FR_PRECISION_F32, FR_PRECISION_DD, BLA-PT (these calls know no table: DE ON BLA-PT
+ * below has calls of its own) and SCALED PT; block-cyclic and multi-device renders; supersampling; fr_pixel.  AFTER fr_escape_extend* ON (z, iters) ALONE,
  * A der ARRAY IS STALE: it is the derivative at the old cap's position, and those calls do not know of it.  The calls that
  * continue all arrays are fr_escape_extend_de(_device) on the F64 road and fr_escape_extend_de_pt(_device) on PT (RESUMABLE DE
  * below); a PT view whose cap will be raised is rendered with fr_escape_rows_de_pt_state, not fr_escape_rows_de. */
@@ -398,7 +398,40 @@ typedef struct fr_config {
  * Domain: DE's, unchanged (limit <= 2^20; PT's domain with a dd centre, WIDE PT's |scale| <= 2^440 with a wide one); M >= N.
  * The overflow bound of DE is about the step that is returned and does not depend on where a run was
  * interrupted: a continued derivative takes the same values, overflow included, as the uninterrupted one.
- * DE on BLA-PT and SCALED PT stays out of scope, and so their states are not resumable with a derivative either. */
+ * DE on SCALED PT stays out of scope; DE ON BLA-PT (below) has no state: neither is resumable with a derivative. */
+/*
+ * DE ON BLA-PT (fr_escape_rows_de_pt_bla(_device) below): the derivative carried through the table's skips.  It is BLA-PT's
+ * definition above word for word, with a dd centre (pos, pos_lo) or a wide centre (WIDE PT's domain) — the orbits, the table with
+ * D, bits and b0, the level search, the plain step, the skip, the escape test, the rebase rule, and (z, i - 1) on escape after
+ * a skip — with the derivative d carried beside it, d0 = (1, 0).  Every operation is ONE correctly rounded f64 operation; fma
+ * is fused and nothing else is.  In one pass of BLA-PT's loop:
+ *   Plain step (no level K found): DE's step, from the z before the step:
+ *     t  = (z.re + z.re, z.im + z.im)
+ *     nd = (fma(t.re, d.re, fma(-t.im, d.im, b0)), fma(t.re, d.im, t.im * d.re))
+ *   Skip with the entry (A, B) of level K: b = B for Mandelbrot; b = (+0, +0) for Julia (its device table stores no B, and
+ *   b0 = 0 there);
+ *     nd.re = fma(A.re, d.re, fma(-A.im, d.im, b.re))
+ *     nd.im = fma(A.re, d.im, fma( A.im, d.re, b.im))
+ *   Escape returns (z, i - 1, nd); otherwise d = nd; exhaustion returns (z, iterations, d).  A rebase never touches d.
+ *   iterations = 0 returns (start, 0, (1, 0)).  An algorithm without orbits writes zeros into all three arrays.  d may become
+ *   +-inf or NaN: that is the IEEE result of this sequence and part of the definition, as in DE (a NaN is any NaN).
+ *   Why the skip is the derivative: over a block of 2^K steps d' = prod(2 z_k) d + b0 sum(...), and the table's level-0 entry
+ *   A = 2 X_m, B = (b0, 0) with its merge A = Ay Ax, B = Ay Bx + By is that recurrence with X_k in place of z_k.  A skip is
+ *   applied only while |dz| < r = eps |2X|, so every factor is off by a relative |dz_k| / |X_k| < 2 eps.  No table data is
+ *   added and no table is rebuilt: the calls share the context's table with the fr_*_pt_bla calls of the same view and bits.
+ *   CLAIM 1: z and iters are fr_escape_rows_pt_bla's, bit for bit: the derivative only reads.
+ *   CLAIM 2: on a view where no pass skips, all three arrays are fr_escape_rows_de's (FR_PRECISION_PT), bit for bit.
+ *   DE's overflow bound is about the returned step's derivative and carries over unchanged.  BLA-PT's invariant
+ *   keeps A finite where r2 > 0; its stated footnote case gives a non-finite d, hence D = 0.
+ *   The distance and the shading are DE's own, unchanged: fr_distance_rows(_device) and fr_colour_de_rows_device /
+ *   fr_colour_de_rgb8 run over this call's (z, iters, der).  Measured accuracy against DE on plain PT: DESIGN.md 3.22.
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): BLA-PT's, dd or wide centre (with a wide
+ * centre |scale| <= 2^440); DE's limit <= 2^20; bits 0 (FR_BLA_DEFAULT_BITS) or 24 .. 53; all three arrays, z and der 8-byte
+ * aligned, iters 4-byte aligned; y0 == y1 is a no-op that needs no device and no array.
+ * Out of scope: SCALED PT (past 2^440 the derivative itself leaves the range in which dn2 = |d|^2 is finite: that road needs a
+ * scaled derivative and an overflow argument of its own); a resumable state or an extend form (BLA-PT has none: i + 2^k <=
+ * iterations makes a run at cap N no prefix of the run at cap M); supersampling; multi-device and block-cyclic renders; the
+ * command line (--distance-shade with --bla stays refused). */
 #define FR_BLA_DEFAULT_BITS 40
 #define FR_PT_MAX_ITERATIONS (1u << 24)
 #define FR_WIDE_MAX_WORDS 16
@@ -1064,6 +1097,15 @@ int fr_escape_rows_de_pt_wide_device(const fr_config *cfg, const fr_wide_centre 
                                      void *d_iters, void *d_der, void *hip_stream);
 int fr_escape_rows_de_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z,
                               uint32_t *iters, double *der);
+/* DE ON BLA-PT (defined at fr_precision above): rows [y0, y1) with their derivatives on the BLA-PT road; the centre convention
+ * is the fr_*_pt_bla calls' (a dd centre (cfg->pos, pos_lo), pos_lo NULL = (0, 0), or a wide centre, never both); bits as there.
+ * The arrays are fr_escape_rows_de's: all three required, y0 == y1 a no-op that needs no device.  Orbits and tables are the
+ * context's caches, shared with the PT and BLA-PT calls (fr_debug_bla_cache shows a table served).  With profiling on,
+ * fr_last_kernel_name reports escape_bla_de_kernel. */
+int fr_escape_rows_de_pt_bla_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
+                                    uint32_t y1, void *d_z, void *d_iters, void *d_der, void *hip_stream);
+int fr_escape_rows_de_pt_bla(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
+                             uint32_t y1, double *z, uint32_t *iters, double *der);
 /* RESUMABLE DE (defined at fr_precision above): a kept DE view answers an iterations change in place, derivative included.
  *
  * The F64 road: raise the cap of the (z, iters, der) that fr_escape_rows_de(_device) wrote, N = from_iterations -> M =
