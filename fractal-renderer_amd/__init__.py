@@ -40,6 +40,7 @@ __all__ = [
     "colour_de_rows_device",
     "extend_rows_de", "extend_rows_de_device", "escape_rows_de_pt_state", "escape_rows_de_pt_state_device", "extend_rows_de_pt",
     "extend_rows_de_pt_device",
+    "ss_de_workspace_bytes", "colour_image_de_ss", "colour_de_rows_ss_device",
 ]
 
 
@@ -982,11 +983,81 @@ def colour_de_rows_device(config, z_ptr, iters_ptr, der_ptr, n, thickness, out_p
                                                           float(thickness), int(channels), out_ptr or None, _stream(stream)))
 
 
-def get_image_de(config, thickness=1.0, precision=Precision.F64, pos_lo=None, centre=None, bla=None, opts=None):
+def get_image_de(config, thickness=1.0, precision=Precision.F64, pos_lo=None, centre=None, bla=None, opts=None, supersample=1, y0=0,
+                 y1=None, channels=3):
     """get_image with distance shading: uint8 [height, width, 3].  escape_rows_de on the road the keywords select (bla=: DE ON
-    BLA-PT), then colour_image_de: filaments thinner than a pixel stay visible as dark lines `thickness` pixels wide."""
-    z, it, der = escape_rows_de(config, precision=precision, pos_lo=pos_lo, centre=centre, bla=bla, opts=opts)
-    return colour_image_de(config, z, it, der, thickness)
+    BLA-PT), then colour_image_de: filaments thinner than a pixel stay visible as dark lines `thickness` pixels wide.
+    supersample = s > 1, a row range y0= / y1= or channels=4: fr_render_rows_ss_de (include/fractal_hip.h, "SUPERSAMPLED DE") —
+    rows [y0, y1) with s x s samples per pixel, each shaded with the thickness thickness * s in sample pixels (the line stays
+    `thickness` OUTPUT pixels wide) and box-filtered on the device, uint8 [y1-y0, width, channels]; the s times larger DE arrays
+    exist only a band at a time.  supersample = 1 gives the bytes of the call without it."""
+    s = int(supersample)
+    if not 1 <= s <= SS_MAX:
+        raise ValueError("supersample is 1 .. %d" % SS_MAX)
+    if int(channels) not in (3, 4):
+        raise ValueError("channels is 3 or 4")
+    if s == 1 and y0 == 0 and y1 is None and int(channels) == 3:
+        z, it, der = escape_rows_de(config, precision=precision, pos_lo=pos_lo, centre=centre, bla=bla, opts=opts)
+        return colour_image_de(config, z, it, der, thickness)
+    if opts is not None:
+        raise ValueError("a DE render takes no opts: it has one kernel per road")
+    road, bits = _ss_pt_road(pos_lo, centre, bla, False)
+    if (centre is not None or bla is not None) and int(precision) != Precision.PT:
+        raise ValueError("centre= and bla= need precision=Precision.PT")
+    y0, y1 = _rows(config, y0, y1)
+    out = np.empty((max(y1 - y0, 0), config.width, int(channels)), dtype=np.uint8)
+    lo = None if pos_lo is None else Imaginary(*(float(v) for v in pos_lo))
+    st = None if centre is None else centre.c_struct()
+    _native.check(_native.load().fr_render_rows_ss_de(C.byref(config), int(precision), None if lo is None else C.byref(lo),
+                                                      None if st is None else C.byref(st), road, bits, float(thickness), s, y0, y1,
+                                                      int(channels), out.ctypes.data, out.nbytes))
+    return out
+
+
+def ss_de_workspace_bytes(config, supersample, y0=0, y1=None):
+    """fr_ss_de_workspace_bytes: (min_bytes, best_bytes) of the device workspace fr_render_rows_ss_de_device wants for rows
+    [y0, y1) — one band of 8 * supersample source rows at 36 bytes per sample, and the whole range (at most 1 GiB).  Unlike
+    ss_workspace_bytes, supersample = 1 needs one too."""
+    y1 = config.height if y1 is None else y1
+    mn, best = C.c_size_t(0), C.c_size_t(0)
+    _native.check(_native.load().fr_ss_de_workspace_bytes(C.byref(config), int(supersample), y0, y1, C.byref(mn), C.byref(best)))
+    return mn.value, best.value
+
+
+def colour_image_de_ss(config, z, iters, der, supersample, thickness, channels=3):
+    """fr_colour_de_ss_rgb8 over numpy arrays: z, der float64 [s*rows, s*width, 2] and iters uint32 [s*rows, s*width] — a DE
+    render of the config with width and height times s — -> uint8 [rows, width, channels]: box_filter(colour_image_de(config_s,
+    z, iters, der, thickness * s), s), byte for byte.  config is the OUTPUT image's: config.height is the whole image's height
+    (the arrays may hold fewer rows), thickness is in output pixels."""
+    z, iters, der = _de_arrays(z, iters, der)
+    s = int(supersample)
+    if not 1 <= s <= SS_MAX:
+        raise ValueError("supersample is 1 .. %d" % SS_MAX)
+    if int(channels) not in (3, 4):
+        raise ValueError("channels is 3 or 4")
+    if iters.ndim != 2 or iters.shape[0] % s or iters.shape[1] % s:
+        raise ValueError("z and der must be [s*rows, s*width, 2] and iters [s*rows, s*width]")
+    rows, width = iters.shape[0] // s, iters.shape[1] // s
+    out = np.empty((rows, width, int(channels)), dtype=np.uint8)
+    _native.check(_native.load().fr_colour_de_ss_rgb8(C.byref(config), z.ctypes.data, iters.ctypes.data, der.ctypes.data, width, rows, s,
+                                                      float(thickness), int(channels), out.ctypes.data, out.nbytes))
+    return out
+
+
+def colour_de_rows_ss_device(config, z_ptr, iters_ptr, der_ptr, width, rows, supersample, thickness, out_ptr, channels=3, stream=None):
+    """fr_colour_de_rows_ss_device: colour map + distance shade + box filter in one kernel over a KEPT anti-aliased DE view — the
+    (z, iters, der) of supersample * rows rows of supersample * width samples in DEVICE memory (what escape_rows_de_device
+    writes for the config with width and height times supersample) — into channels * width * rows bytes at out_ptr,
+    asynchronously on `stream`.  config is the output image's (config.height the whole image's height); thickness in output
+    pixels.  Thickness and exposure are a recolour: no orbit, no RGB image of the large view."""
+    width, rows, s = int(width), int(rows), int(supersample)
+    if not 1 <= s <= SS_MAX:
+        raise ValueError("supersample is 1 .. %d" % SS_MAX)
+    if int(channels) not in (3, 4):
+        raise ValueError("channels is 3 or 4")
+    _native.check(_native.load().fr_colour_de_rows_ss_device(C.byref(config), z_ptr or None, iters_ptr or None, der_ptr or None, width,
+                                                             rows, s, float(thickness), int(channels), out_ptr or None,
+                                                             int(channels) * width * rows, _stream(stream)))
 
 
 def count_iterations(config, y0=0, y1=None, sx=1, sy=1, precision=Precision.F64):

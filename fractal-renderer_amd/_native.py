@@ -451,6 +451,28 @@ PROTOTYPES = {
     ),
     "fr_colour_de_rgb8": (
         C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_size_t]),
+    "fr_colour_de_rows_ss_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_void_p,
+         C.c_size_t, C.c_void_p],
+    ),
+    "fr_colour_de_ss_rgb8": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_void_p,
+         C.c_size_t],
+    ),
+    "fr_ss_de_workspace_bytes": (
+        C.c_int, [C.POINTER(fr_config), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "fr_render_rows_ss_de_device": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_int, C.POINTER(Imaginary), _WIDE, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32,
+         C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "fr_render_rows_ss_de": (
+        C.c_int,
+        [C.POINTER(fr_config), C.c_int, C.POINTER(Imaginary), _WIDE, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32,
+         C.c_int, C.c_void_p, C.c_size_t],
+    ),
     "fr_count_iterations": (
         C.c_int,
         [C.POINTER(fr_config), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),

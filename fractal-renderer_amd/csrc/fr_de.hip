@@ -32,15 +32,16 @@
 #include <memory>
 
 #include "fr_ctx.h"
+#include "fr_de.h"
 #include "fr_math.h"
 #include "fr_wide.h"
 
 namespace {
 
 #include "fr_colour.h"
+#include "fr_de_shade.h" /* kHalfLn2, de_distance */
 
 constexpr uint32_t kDeThreads = 64 * kDeepWaves;
-constexpr double kHalfLn2 = 0x1.62e42fefa39efp-2; /* ln 2 / 2: |z| ln|z| = sqrt(n2) * log2(n2) * (ln 2 / 2) */
 
 /* the workgroup's 16 x 16 pixels: this lane's local column and row (fr_kernels.h: kDeep*) */
 struct DeLane {
@@ -394,16 +395,6 @@ __global__ __launch_bounds__(kDeThreads) void escape_extend_pt_de_kernel(const f
 
 /* ---- distance and shaded colour over stored results ------------------------------------------------------------------------- */
 
-/* D of the definition; `pixels` = (double)height * min(|scale.re|, |scale.im|), formed by the host */
-__device__ __forceinline__ double de_distance(double zr, double zi, double dr, double di, uint32_t it, uint32_t iterations, double pixels,
-                                              const double *lds_tab) {
-    if (it == iterations) return 0.0;
-    const double n2 = zr * zr + zi * zi, dn2 = dr * dr + di * di;
-    const double num = (__builtin_sqrt(n2) * fr_log2_tab(n2, lds_tab)) * kHalfLn2;
-    const double D = (num / __builtin_sqrt(dn2)) * pixels;
-    return D > 0.0 ? D : 0.0; /* NaN and negatives give 0; +inf stays */
-}
-
 __device__ __forceinline__ void de_stage_table(double *s_tab) {
     const double *gt = &g_log2_tab[0][0];
     for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kDeThreads) s_tab[k] = gt[k];
@@ -483,7 +474,8 @@ namespace {
 
 const char *const kDeScope =
     "distance estimation is defined for FR_PRECISION_F64 and FR_PRECISION_PT (dd or wide centre) on one device; FR_PRECISION_F32, "
-    "FR_PRECISION_DD, BLA-PT, SCALED PT, block-cyclic and multi-device renders, supersampling and fr_pixel are out of scope, and so is "
+    "FR_PRECISION_DD, BLA-PT, SCALED PT, block-cyclic and multi-device renders and fr_pixel are out of scope (BLA-PT has "
+    "fr_escape_rows_de_pt_bla, supersampling fr_render_rows_ss_de), and so is "
     "raising a DE view's cap with fr_escape_extend* on (z, iters) alone: fr_escape_extend_de(_device) (F64) and "
     "fr_escape_extend_de_pt(_device) (PT) continue the derivative with them";
 
@@ -752,12 +744,33 @@ hipError_t launch_colour_de(const fr_config *cfg, const double *z, const uint32_
                             uint32_t channels, void *out, hipStream_t stream) {
     fr_kparams p;
     fill_params(cfg, default_opts(), p);
-    colour_de_rows_kernel<<<dim3(de_blocks(n)), dim3(kDeThreads), 0, stream>>>(p, z, iters, der, n, de_pixels(cfg), thickness, channels,
+    return fr_launch_colour_de_rows(p, z, iters, der, n, de_pixels(cfg), thickness, channels, out, stream);
+}
+
+} /* namespace */
+
+hipError_t fr_launch_colour_de_rows(const fr_kparams &p, const double *z, const uint32_t *iters, const double *der, size_t n, double pixels,
+                                    double thickness, uint32_t channels, void *out, hipStream_t stream) {
+    colour_de_rows_kernel<<<dim3(de_blocks(n)), dim3(kDeThreads), 0, stream>>>(p, z, iters, der, n, pixels, thickness, channels,
                                                                               static_cast<uint8_t *>(out));
     return hipGetLastError();
 }
 
-} /* namespace */
+/* for the supersampled DE roads (fr_de.h): the domain check and the row launch of the calls above, called */
+namespace fr {
+
+int de_domain(const fr_config *cfg, int precision, const Centre &c, bool wide_call, uint32_t y0, uint32_t y1) {
+    alignas(8) static const char arrays[8] = {}; /* stands for the three arrays: the caller's are its workspace's, checked there */
+    bool work;
+    return de_check(cfg, precision, c, wide_call, y0, y1, arrays, arrays, arrays, &work);
+}
+
+int de_render_rows(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, uint32_t y0, uint32_t y1, double *d_z, uint32_t *d_iters,
+                   double *d_der, hipStream_t stream) {
+    return de_rows(cfg, precision, c, y0, y1)(ctx, d_z, d_iters, d_der, nullptr, stream);
+}
+
+}  // namespace fr
 
 extern "C" {
 

@@ -28,6 +28,7 @@
 
 #include "fr_bla.h"
 #include "fr_ctx.h"
+#include "fr_de.h"
 #include "fr_math.h"
 #include "fr_wide.h"
 
@@ -259,6 +260,22 @@ auto bla_de_rows(const fr_config *cfg, const Centre &c, int bits, uint32_t y0, u
 }
 
 }  // namespace
+
+/* for the supersampled DE roads (fr_de.h): the domain check and the row launch of the calls below, called */
+namespace fr {
+
+int bla_de_domain(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1) {
+    alignas(8) static const char arrays[8] = {}; /* stands for the three arrays: the caller's are its workspace's, checked there */
+    bool work;
+    return check_bla_de(cfg, c, bits, y0, y1, arrays, arrays, arrays, &work);
+}
+
+int bla_de_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, double *d_z, uint32_t *d_iters,
+                       double *d_der, hipStream_t stream) {
+    return bla_de_rows(cfg, c, bits, y0, y1)(ctx, d_z, d_iters, d_der, nullptr, stream);
+}
+
+}  // namespace fr
 
 extern "C" {
 

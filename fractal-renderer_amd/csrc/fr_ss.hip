@@ -30,6 +30,7 @@
  *   - 64-bit byte offsets throughout (a source may exceed 4 GiB); plain vector loads and stores only.
  */
 #include "fr_bla.h" /* fr_ctx.h, and the BLA-PT / SCALED PT row launches */
+#include "fr_ss.h"
 
 #include <algorithm>
 
@@ -421,20 +422,9 @@ hipError_t fr_launch_colour_filter(const fr_kparams &p, const double *z, uint32_
 }
 
 namespace fr {
-namespace {
 
-constexpr size_t kSsBestCap = (size_t)1 << 30;     /* fr_ss_workspace_bytes' best_bytes */
-constexpr size_t kSsHostWorkCap = (size_t)256 << 20; /* the host road's workspace: the context keeps it */
-
-struct SsPlan {
-    fr_config cfg_s;      /* cfg with width * s, height * s */
-    uint64_t src_rows;    /* s * (y1 - y0) */
-    uint64_t row_bytes;   /* 3 * s * width: one source row */
-    size_t min_bytes, best_bytes;
-};
-
-/* the part of the domain that needs no precision: cfg, s, the sizes, the rows */
-int ss_plan(const fr_config *cfg, uint32_t s, uint32_t y0, uint32_t y1, SsPlan &pl) {
+/* the part of the domain that needs no precision: cfg, s, the sizes, the rows (fr_ss.h) */
+int ss_plan(const fr_config *cfg, uint32_t s, uint32_t y0, uint32_t y1, SsPlan &pl, uint32_t sample_bytes) {
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
     if (s < 1 || s > FR_SS_MAX) return fail(FR_ERR_INVALID_ARGUMENT, "supersample must be 1 .. FR_SS_MAX (8)");
     if ((uint64_t)cfg->width * s > 0xFFFFFFFFull)
@@ -447,8 +437,8 @@ int ss_plan(const fr_config *cfg, uint32_t s, uint32_t y0, uint32_t y1, SsPlan &
     pl.cfg_s.width = cfg->width * s;
     pl.cfg_s.height = cfg->height * s;
     pl.src_rows = (uint64_t)s * (y1 - y0);
-    pl.row_bytes = (uint64_t)3u * s * cfg->width;
-    if (s == 1) {
+    pl.row_bytes = (uint64_t)sample_bytes * s * cfg->width;
+    if (s == 1 && sample_bytes == 3u) {
         pl.min_bytes = pl.best_bytes = 0;
         return FR_OK;
     }
@@ -470,6 +460,8 @@ uint64_t ss_band_rows(const SsPlan &pl, uint32_t s, size_t work_len) {
     const uint64_t b = (pl.src_rows + nb - 1) / nb;
     return (b + unit - 1) / unit * unit;
 }
+
+namespace {
 
 /* Rows [y0, y1) supersampled into device memory on `stream`: the band loop of every supersampled render.  band(ctx, ya, yb,
  * ko, stream) is the launch of source rows [ya, yb) of cfg_s as packed r,g,b into ko.rgb — a road's row launch (fr_bla.hip:

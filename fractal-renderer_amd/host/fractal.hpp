@@ -386,15 +386,28 @@ std::vector<RGB> get_image_de(const Config &config, double thickness, Escape &&e
                             image.size() * sizeof(RGB)));
     return image;
 }
+// Anti-aliased (include/fractal_hip.h, "SUPERSAMPLED DE"): supersample x supersample samples per pixel, each shaded with the
+// thickness thickness * supersample in sample pixels — the line stays `thickness` output pixels wide — and box-filtered on the
+// device; the larger DE arrays exist only a band at a time.  road FR_PT_ROAD_PLAIN or FR_PT_ROAD_BLA.  The overloads below take
+// it as their last argument; 1 is the form without it, byte for byte.
+inline std::vector<RGB> get_image_ss_de(const Config &config, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
+                                        int road, int bits, double thickness, uint32_t supersample) {
+    std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
+    check(fr_render_rows_ss_de(&config, precision, pos_lo, centre, road, bits, thickness, supersample, 0, config.height, 3,
+                               reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB)));
+    return image;
+}
 // ... on the F64 road, or on PT with a dd centre (precision FR_PRECISION_PT; pos_lo may be null)
 inline std::vector<RGB> get_image_de(const Config &config, double thickness = 1.0, int precision = FR_PRECISION_F64,
-                                     const fr_imaginary *pos_lo = nullptr) {
+                                     const fr_imaginary *pos_lo = nullptr, uint32_t supersample = 1) {
+    if (supersample != 1) return get_image_ss_de(config, precision, pos_lo, nullptr, FR_PT_ROAD_PLAIN, 0, thickness, supersample);
     return get_image_de(config, thickness, [&](const Config &c, double *z, uint32_t *iters, double *der) {
         check(fr_escape_rows_de(&c, precision, pos_lo, 0, c.height, z, iters, der));
     });
 }
 // ... on PT with a wide centre
-inline std::vector<RGB> get_image_de(const Config &config, const fr_wide_centre &centre, double thickness = 1.0) {
+inline std::vector<RGB> get_image_de(const Config &config, const fr_wide_centre &centre, double thickness = 1.0, uint32_t supersample = 1) {
+    if (supersample != 1) return get_image_ss_de(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_PLAIN, 0, thickness, supersample);
     return get_image_de(config, thickness, [&](const Config &c, double *z, uint32_t *iters, double *der) {
         check(fr_escape_rows_de_pt_wide(&c, &centre, 0, c.height, z, iters, der));
     });
@@ -402,7 +415,8 @@ inline std::vector<RGB> get_image_de(const Config &config, const fr_wide_centre 
 // ... on BLA-PT (include/fractal_hip.h, "DE ON BLA-PT"): the derivative goes through the table's skips; a dd centre
 // (config.pos, pos_lo; pos_lo may be null) or a wide centre, never both
 inline std::vector<RGB> get_image_de(const Config &config, Bla bla, double thickness = 1.0, const fr_imaginary *pos_lo = nullptr,
-                                     const fr_wide_centre *centre = nullptr) {
+                                     const fr_wide_centre *centre = nullptr, uint32_t supersample = 1) {
+    if (supersample != 1) return get_image_ss_de(config, FR_PRECISION_PT, pos_lo, centre, FR_PT_ROAD_BLA, bla.bits, thickness, supersample);
     return get_image_de(config, thickness, [&](const Config &c, double *z, uint32_t *iters, double *der) {
         check(fr_escape_rows_de_pt_bla(&c, pos_lo, centre, bla.bits, 0, c.height, z, iters, der));
     });
@@ -412,6 +426,13 @@ inline void colour_de_rows_device(const Config &config, const void *d_z, const v
                                   void *d_out, int channels = 4, void *hip_stream = nullptr) {
     const size_t n = static_cast<size_t>(config.width) * config.height;
     check(fr_colour_de_rows_device(&config, d_z, d_iters, d_der, n, thickness, channels, d_out, hip_stream));
+}
+// A kept anti-aliased DE view is a kept DE view of the config with width and height times supersample (36 * supersample^2 bytes
+// per output pixel): this colours, shades and box-filters it in one kernel.  config is the OUTPUT's; thickness in output pixels.
+inline void colour_de_rows_ss_device(const Config &config, const void *d_z, const void *d_iters, const void *d_der, uint32_t supersample,
+                                     double thickness, void *d_out, int channels = 4, void *hip_stream = nullptr) {
+    check(fr_colour_de_rows_ss_device(&config, d_z, d_iters, d_der, config.width, config.height, supersample, thickness, channels, d_out,
+                                      static_cast<size_t>(channels) * config.width * config.height, hip_stream));
 }
 
 }  // namespace fractal

@@ -369,7 +369,8 @@ typedef struct fr_config {
  * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): the road's own domain; limit <= 2^20;
  * thickness finite and in [0, 2^20]; F64 takes no pos_lo; PT with a wide centre keeps WIDE PT's |scale| <= 2^440.
  * Out of scope of these calls, refused by name: FR_PRECISION_F32, FR_PRECISION_DD, BLA-PT (these calls know no table: DE ON BLA-PT
- * below has calls of its own) and SCALED PT; block-cyclic and multi-device renders; supersampling; fr_pixel.  AFTER fr_escape_extend* ON (z, iters) ALONE,
+ * below has calls of its own) and SCALED PT; block-cyclic and multi-device renders; fr_pixel.  Supersampling is SUPERSAMPLED DE
+ * below (fr_render_rows_ss_de, fr_colour_de_rows_ss_device), not these calls.  AFTER fr_escape_extend* ON (z, iters) ALONE,
  * A der ARRAY IS STALE: it is the derivative at the old cap's position, and those calls do not know of it.  The calls that
  * continue all arrays are fr_escape_extend_de(_device) on the F64 road and fr_escape_extend_de_pt(_device) on PT (RESUMABLE DE
  * below); a PT view whose cap will be raised is rendered with fr_escape_rows_de_pt_state, not fr_escape_rows_de. */
@@ -430,8 +431,35 @@ typedef struct fr_config {
  * aligned, iters 4-byte aligned; y0 == y1 is a no-op that needs no device and no array.
  * Out of scope: SCALED PT (past 2^440 the derivative itself leaves the range in which dn2 = |d|^2 is finite: that road needs a
  * scaled derivative and an overflow argument of its own); a resumable state or an extend form (BLA-PT has none: i + 2^k <=
- * iterations makes a run at cap N no prefix of the run at cap M); supersampling; multi-device and block-cyclic renders; the
- * command line (--distance-shade with --bla stays refused). */
+ * iterations makes a run at cap N no prefix of the run at cap M); multi-device and block-cyclic renders; the command line
+ * (--distance-shade with --bla stays refused).  Supersampling is SUPERSAMPLED DE below, with FR_PT_ROAD_BLA. */
+/*
+ * SUPERSAMPLED DE (fr_render_rows_ss_de, fr_colour_de_rows_ss_device below): distance estimation and supersampling at once —
+ * filaments thinner than a pixel stay visible AND the borders are anti-aliased.  DEFINITION, for supersample = s,
+ * 1 <= s <= FR_SS_MAX, and a thickness T in OUTPUT pixels:
+ *   cfg_s = cfg with width * s and height * s, every other field unchanged;
+ *   (z, iters, der) = the road's DE render of cfg_s, bit for bit what the existing call writes:
+ *             FR_PRECISION_F64                       fr_escape_rows_de(cfg_s, FR_PRECISION_F64, NULL, ...);
+ *             FR_PRECISION_PT, FR_PT_ROAD_PLAIN      fr_escape_rows_de(cfg_s, FR_PRECISION_PT, pos_lo, ...), or with a wide
+ *                                                    centre fr_escape_rows_de_pt_wide(cfg_s, centre, ...);
+ *             FR_PRECISION_PT, FR_PT_ROAD_BLA        fr_escape_rows_de_pt_bla(cfg_s, pos_lo, centre, bits, ...); its D is taken
+ *                                                    over the whole image of cfg_s, as the supersampled deep roads define;
+ *   Ts    = T * (double)s, one f64 product;
+ *   H     = the bytes of fr_colour_de_rows_device(cfg_s, z, iters, der, n, Ts, 3): the distance is in SAMPLE pixels — its last
+ *           factor is (double)(s * height) * min(|scale.re|, |scale.im|) — and so is Ts, hence the line stays T output pixels
+ *           wide whatever s is;
+ *   out(X, Y, c) = (sum over j < s, i < s of H(s*X + i, s*Y + j, c) + floor(s*s / 2)) / (s*s)
+ *           in integer arithmetic, truncating; with 4 channels alpha is 255: the box filter of "supersampled rendering".
+ * s = 1 is the road's DE render followed by fr_colour_de_rows_device(cfg, ..., T, channels), byte for byte.  T = 0 gives the
+ * bytes of the unshaded supersampled render of the same road (fr_render_rows_ss / fr_render_rows_ss_pt).  An algorithm without
+ * orbits gives black.
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): s in 1 .. FR_SS_MAX; s * width and s * height
+ * fit in 32 bits; the road's own DE domain ON cfg_s, checked by the code the plain calls run; T finite with 0 <= T * s <= 2^20
+ * (Ts is then inside fr_colour_de_rows_device's own domain: the definition is literally a composition of existing calls);
+ * channels 3 or 4.  Refused by name: FR_PRECISION_F32 and FR_PRECISION_DD (DE's scope message), FR_PT_ROAD_SCALED (DE on SCALED
+ * PT stays out of scope).  One device.  The command line stays as it is: --distance-shade beside --supersample above 1 or
+ * --bla is refused there.
+ */
 #define FR_BLA_DEFAULT_BITS 40
 #define FR_PT_MAX_ITERATIONS (1u << 24)
 #define FR_WIDE_MAX_WORDS 16
@@ -1162,6 +1190,53 @@ int fr_colour_de_rows_device(const fr_config *cfg, const void *d_z, const void *
 /* the same over HOST arrays into packed r,g,b (upload, colour, download, synchronise: as fr_colour_rgb8) */
 int fr_colour_de_rgb8(const fr_config *cfg, const double *z, const uint32_t *iters, const double *der, size_t n, double thickness,
                       uint8_t *out, size_t out_len);
+
+/* SUPERSAMPLED DE (defined at fr_precision above).
+ *
+ * A KEPT anti-aliased DE view is a kept DE view of cfg_s: (z, iters, der) of the s times larger image in DEVICE memory, s * rows
+ * rows of s * width samples, k = Y * (s * width) + X, 36 * s * s bytes per output pixel, written by any fr_escape_rows_de*_device
+ * call for cfg_s.  fr_colour_de_rows_ss_device colours, shades and filters it in ONE kernel (colour_de_filter_kernel), with no
+ * RGB image of cfg_s in between: thickness and exposure are a recolour.  DEFINITION:
+ *   out = fr_box_filter_rgb8(fr_colour_de_rows(cfg_s, z, iters, der, n = s*s * width * rows, thickness * s), width, rows, s, channels),
+ * byte for byte.  cfg is the OUTPUT image's config: cfg->height is the whole image's height (`rows` may be fewer: a row range of
+ * the view), `width` the output width; cfg contributes what the colour map reads plus height, scale and iterations.  s = 1 is
+ * fr_colour_de_rows_device.  An algorithm without orbits gives black.
+ * Domain: s in 1 .. FR_SS_MAX with s * width, s * rows and s * cfg->height in 32 bits; thickness finite, 0 <= thickness * s <=
+ * 2^20; channels 3 or 4 (RGBA output 4-byte aligned); d_z and d_der 8-byte aligned, d_iters 4-byte aligned; out_len >= channels *
+ * width * rows (FR_ERR_BUFFER_TOO_SMALL); an empty output (width or rows 0) is a no-op without a device.  The device form is
+ * asynchronous on `hip_stream`, allocates nothing and takes no lock.  fr_colour_de_ss_rgb8: the same over HOST arrays (upload to
+ * context scratch, launch, download, synchronise, as fr_colour_de_rgb8 does). */
+int fr_colour_de_rows_ss_device(const fr_config *cfg, const void *d_z, const void *d_iters, const void *d_der, uint32_t width,
+                                uint32_t rows, uint32_t supersample, double thickness, int channels, void *d_out, size_t out_len,
+                                void *hip_stream);
+int fr_colour_de_ss_rgb8(const fr_config *cfg, const double *z, const uint32_t *iters, const double *der, uint32_t width, uint32_t rows,
+                         uint32_t supersample, double thickness, int channels, uint8_t *out, size_t out_len);
+/* Workspace of fr_render_rows_ss_de_device for rows [y0, y1): rows [s*y0, s*y1) of cfg_s are rendered in bands by
+ * fr_ss_workspace_bytes' rule at 36 bytes per sample (36 * s * width bytes a source row): *min_bytes = one band of 8 * s source
+ * rows (or all the rows if there are fewer), *best_bytes = the whole range, at most 1 GiB (never under *min_bytes); any length
+ * from *min_bytes up is accepted and used, Bmax, nb and B as there.  Unlike the RGB road, s = 1 needs a workspace too: the arrays
+ * must live somewhere.  LAYOUT: a band of n samples lies at d_work as z (16 n bytes) | der (16 n) | iters (4 n), each array as
+ * the DE calls write it; d_work must be 8-byte aligned.  Either pointer may be NULL.  No device needed. */
+int fr_ss_de_workspace_bytes(const fr_config *cfg, uint32_t supersample, uint32_t y0, uint32_t y1, size_t *min_bytes,
+                             size_t *best_bytes);
+/* Rows [y0, y1) of the SUPERSAMPLED DE image as r,g,b (channels 3) or r,g,b,255 (channels 4; d_out 4-byte aligned) into DEVICE
+ * memory, asynchronously on `hip_stream`: band by band, the road's DE row launch into the workspace, then the fused kernel into
+ * the band's place in d_out; the image of cfg_s never exists whole (a 3840 x 2160 frame at s = 4 would be 4.8 GB of arrays).
+ * precision: FR_PRECISION_F64 (road FR_PT_ROAD_PLAIN, pos_lo NULL, centre NULL, bits 0) or FR_PRECISION_PT (road
+ * FR_PT_ROAD_PLAIN with bits 0, or FR_PT_ROAD_BLA with bits 0 or 24 .. 53; pos_lo or centre or neither, never both;
+ * FR_PT_ROAD_SCALED is refused by name).  The caller lends d_work (work_len bytes, 8-byte aligned) until the work queued on the
+ * stream has finished; work_len under *min_bytes or a short out_len give FR_ERR_BUFFER_TOO_SMALL; y0 == y1 is a no-op without a
+ * device.  The library allocates nothing and takes no lock beyond what the road's plain device call takes (the orbit / table
+ * cache): the orbit — and for BLA the table — is computed and uploaded by the first band and served to the others
+ * (fr_debug_pt_orbit_cache, fr_debug_bla_cache).  With profiling on, fr_last_kernel_name reports the road's DE kernel and
+ * fr_last_kernel_ms the span from the first band's kernel to the last filter. */
+int fr_render_rows_ss_de_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
+                                int bits, double thickness, uint32_t supersample, uint32_t y0, uint32_t y1, int channels, void *d_out,
+                                size_t out_len, void *d_work, size_t work_len, void *hip_stream);
+/* The same into a HOST buffer of at least channels*width*(y1-y0) bytes: the workspace (at most 256 MiB) and the result live in
+ * the context's scratch; the small image leaves the device in one copy. */
+int fr_render_rows_ss_de(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                         double thickness, uint32_t supersample, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 
