@@ -41,6 +41,7 @@ __all__ = [
     "extend_rows_de", "extend_rows_de_device", "escape_rows_de_pt_state", "escape_rows_de_pt_state_device", "extend_rows_de_pt",
     "extend_rows_de_pt_device",
     "ss_de_workspace_bytes", "colour_image_de_ss", "colour_de_rows_ss_device",
+    "de_scaled_view",
 ]
 
 
@@ -810,10 +811,13 @@ def get_image_auto(config, percentile=0.99, precision=Precision.F64, pos_lo=None
     return image, exposure
 
 
-def _de_call(precision, pos_lo, centre, device, bla=None, opts=None):
+def _de_call(precision, pos_lo, centre, device, bla=None, opts=None, scaled=False):
     """the DE render the keywords select, in its host or device form: (function, leading arguments behind the config, keep-alive)"""
     suffix = "_device" if device else ""
     lib = _native.load()
+    if scaled:  # DE ON SCALED PT; _deep_call's checks: centre=, Precision.PT, no pos_lo, no opts, the bits of bla=
+        _family, pre, keep = _deep_call(precision, pos_lo, centre, bla=bla, opts=opts, scaled=True)
+        return getattr(lib, "fr_escape_rows_de_pt_scaled" + suffix), pre, keep
     if bla is not None:  # DE ON BLA-PT; _deep_call's checks: Precision.PT, no opts, the bits, no pos_lo beside a centre
         _family, pre, keep = _deep_call(precision, pos_lo, centre, bla=bla, opts=opts)
         return getattr(lib, "fr_escape_rows_de_pt_bla" + suffix), pre, keep
@@ -826,15 +830,18 @@ def _de_call(precision, pos_lo, centre, device, bla=None, opts=None):
     return getattr(lib, "fr_escape_rows_de" + suffix), (int(precision), lo), keep
 
 
-def escape_rows_de(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, centre=None, bla=None, opts=None):
+def escape_rows_de(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, centre=None, bla=None, opts=None, scaled=False):
     """fr_escape_rows_de / fr_escape_rows_de_pt_wide: rows [y0, y1) with the orbit's derivative (include/fractal_hip.h, "DE"):
     (z float64 [rows, width, 2], iters uint32 [rows, width], der float64 [rows, width, 2]).  z and iters are the road's own,
     bit for bit; der is the derivative of the returned position (d/dc for Mandelbrot, d/dz0 for Julia).  precision is
     Precision.F64 or Precision.PT (pos_lo= or centre=, a WideCentre, as escape_rows takes them); everything else is refused.
     bla= (None: off; 0: the default bits; 24 .. 53; needs Precision.PT and takes no opts, as bla= does elsewhere): DE ON BLA-PT,
-    fr_escape_rows_de_pt_bla — z and iters are escape_rows(..., bla=)'s bit for bit, der goes through the table's skips."""
+    fr_escape_rows_de_pt_bla — z and iters are escape_rows(..., bla=)'s bit for bit, der goes through the table's skips.
+    scaled=True (needs centre= and Precision.PT; combines with bla=; no pos_lo, no opts): DE ON SCALED PT,
+    fr_escape_rows_de_pt_scaled, for views past 2^440 — der then holds the SCALED derivative u = d 2^-e, and the distance and the
+    shading are taken on de_scaled_view(config)."""
     y0, y1 = _rows(config, y0, y1)
-    fn, pre, _keep = _de_call(precision, pos_lo, centre, False, bla, opts)
+    fn, pre, _keep = _de_call(precision, pos_lo, centre, False, bla, opts, scaled)
     z = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
     it = np.empty((y1 - y0, config.width), dtype=np.uint32)
     der = np.empty((y1 - y0, config.width, 2), dtype=np.float64)
@@ -843,12 +850,12 @@ def escape_rows_de(config, y0=0, y1=None, precision=Precision.F64, pos_lo=None, 
 
 
 def escape_rows_de_device(config, z_ptr, iters_ptr, der_ptr, y0=0, y1=None, precision=Precision.F64, pos_lo=None, centre=None,
-                          stream=None, bla=None, opts=None):
+                          stream=None, bla=None, opts=None, scaled=False):
     """fr_escape_rows_de_device / fr_escape_rows_de_pt_wide_device / fr_escape_rows_de_pt_bla_device (bla=, as escape_rows_de takes
-    it): the same into DEVICE arrays (raw pointers as ints, all three required), asynchronously on `stream`: the 36 bytes per
-    pixel a GUI keeps to vary thickness without an orbit."""
+    it) / fr_escape_rows_de_pt_scaled_device (scaled=True, as there): the same into DEVICE arrays (raw pointers as ints, all three
+    required), asynchronously on `stream`: the 36 bytes per pixel a GUI keeps to vary thickness without an orbit."""
     y0, y1 = _rows(config, y0, y1)
-    fn, pre, _keep = _de_call(precision, pos_lo, centre, True, bla, opts)
+    fn, pre, _keep = _de_call(precision, pos_lo, centre, True, bla, opts, scaled)
     _native.check(fn(C.byref(config), *pre, y0, y1, z_ptr or None, iters_ptr or None, der_ptr or None, _stream(stream)))
 
 
@@ -983,19 +990,35 @@ def colour_de_rows_device(config, z_ptr, iters_ptr, der_ptr, n, thickness, out_p
                                                           float(thickness), int(channels), out_ptr or None, _stream(stream)))
 
 
+def de_scaled_view(config):
+    """fr_de_scaled_view: the scaled view cfg_v of DE ON SCALED PT, a copy of `config` with scale = (sre, sim) = scale 2^-e; the
+    distance and the shading of escape_rows_de(..., scaled=True)'s arrays are distance_rows / colour_image_de on it.  Host only."""
+    view = Config.from_buffer_copy(bytes(config))
+    _native.check(_native.load().fr_de_scaled_view(C.byref(config), C.byref(view)))
+    return view
+
+
 def get_image_de(config, thickness=1.0, precision=Precision.F64, pos_lo=None, centre=None, bla=None, opts=None, supersample=1, y0=0,
-                 y1=None, channels=3):
+                 y1=None, channels=3, scaled=False):
     """get_image with distance shading: uint8 [height, width, 3].  escape_rows_de on the road the keywords select (bla=: DE ON
     BLA-PT), then colour_image_de: filaments thinner than a pixel stay visible as dark lines `thickness` pixels wide.
     supersample = s > 1, a row range y0= / y1= or channels=4: fr_render_rows_ss_de (include/fractal_hip.h, "SUPERSAMPLED DE") —
     rows [y0, y1) with s x s samples per pixel, each shaded with the thickness thickness * s in sample pixels (the line stays
     `thickness` OUTPUT pixels wide) and box-filtered on the device, uint8 [y1-y0, width, channels]; the s times larger DE arrays
-    exist only a band at a time.  supersample = 1 gives the bytes of the call without it."""
+    exist only a band at a time.  supersample = 1 gives the bytes of the call without it.
+    scaled=True (needs centre=; combines with bla=): DE ON SCALED PT — escape_rows_de(..., scaled=True), then colour_image_de on
+    de_scaled_view(config); the whole image at one sample per pixel and 3 channels only."""
     s = int(supersample)
     if not 1 <= s <= SS_MAX:
         raise ValueError("supersample is 1 .. %d" % SS_MAX)
     if int(channels) not in (3, 4):
         raise ValueError("channels is 3 or 4")
+    if scaled:
+        if s != 1 or y0 != 0 or y1 is not None or int(channels) != 3:
+            raise ValueError("scaled=True: supersample > 1, a row range and channels=4 are out of scope of DE ON SCALED PT "
+                             "(fr_render_rows_ss_de refuses FR_PT_ROAD_SCALED)")
+        z, it, der = escape_rows_de(config, precision=precision, pos_lo=pos_lo, centre=centre, bla=bla, opts=opts, scaled=True)
+        return colour_image_de(de_scaled_view(config), z, it, der, thickness)
     if s == 1 and y0 == 0 and y1 is None and int(channels) == 3:
         z, it, der = escape_rows_de(config, precision=precision, pos_lo=pos_lo, centre=centre, bla=bla, opts=opts)
         return colour_image_de(config, z, it, der, thickness)

@@ -418,6 +418,11 @@ PROTOTYPES = {
     ),
     "fr_escape_rows_de_pt_bla": (
         C.c_int, [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fr_escape_rows_de_pt_scaled_device": (
+        C.c_int, [C.POINTER(fr_config), _WIDE, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fr_escape_rows_de_pt_scaled": (
+        C.c_int, [C.POINTER(fr_config), _WIDE, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fr_de_scaled_view": (C.c_int, [C.POINTER(fr_config), C.POINTER(fr_config)]),
     "fr_escape_extend_de_device": (
         C.c_int, [C.POINTER(fr_config), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fr_escape_extend_de": (

@@ -1,0 +1,371 @@
+/*
+ * fr_de_scaled.hip — DE ON SCALED PT (include/fractal_hip.h, "DE ON SCALED PT"): SCALED PT's pixel loops (fr_scaled.hip:
+ * orbit_pt_scaled, orbit_bla_scaled) with a SCALED derivative u = d 2^-e carried beside them, e the exponent of the view's scale.
+ * Past a scale of 2^440 the derivative d itself is of the order 2^e at a pixel near the set, so dn2 = |d|^2 leaves f64 from
+ * e = 512; u stays where d stays at a scale of 1.  The recurrence is linear in d, so scaling it scales only the constant term:
+ * u' = 2 z u + b0 2^-e through a plain step and u' = A u + B 2^-e through a skip.  tests/de_scaled_model.c restates the
+ * definition; tests/test_gpu_de_scaled.py compares the two bit for bit.
+ *
+ * Host part: nothing of its own.  Orbits and tables are the context's (fr_scaled.h: scaled_dev_fill), so a fr_*_pt_scaled call
+ * and a DE call of the same view and bits share them.  The distance and the shading are DE's own kernels, run on the scaled view
+ * that fr_de_scaled_view writes: no distance or colour kernel is added.
+ *
+ * Device part: escape_pt_scaled_de_kernel<JULIA> (bits = -1) and escape_bla_scaled_de_kernel<JULIA>, the escape mode of
+ * escape_pt_scaled_kernel and escape_bla_scaled_kernel in their shape — a workgroup of 4 waves renders 16 x 16 pixels, each wave
+ * one 8 x 8 tile, woff staged in LDS, the level search by bisection over R, a skip's loads behind the branch, 64-bit output
+ * offsets, plain vector loads and stores — writing z, iters and der.  The step of w, the search and the tests are the siblings'
+ * operation for operation: the derivative only reads, so z and iters are fr_escape_rows_pt_scaled's bit for bit.  The table form
+ * keeps escape_bla_de_kernel's ONE arithmetic path for the derivative: nu = (fma(g.re, u.re, fma(-g.im, u.im, b.re)),
+ * fma(g.re, u.im, fma(g.im, u.re, b.im))), where a lane that skips takes g = A and b = B Sinv (Julia: (+0, +0)) and a lane that
+ * steps takes g = z + z and b = (bs0, -0); fma(x, y, -0) is x * y in every bit, so the stepping lane's imaginary part is the
+ * definition's fma(t.re, u.im, t.im * u.re).  The registers, the occupancy and the inner loop:
+ * profiles/de_scaled_inner_loop_isa.txt.
+ *
+ * The calls, at the end of the file: SCALED PT's domain check (fr_bla.h: scaled_check), DE's arrays, then the profiled launch
+ * through the row-call bodies of fr_ctx.h (device_form, host_raw, profiled_rows).
+ */
+#include <cmath>
+#include <memory>
+
+#include "fr_bla.h"
+#include "fr_ctx.h"
+#include "fr_math.h"
+#include "fr_scaled.h"
+#include "fr_wide.h"
+
+namespace {
+
+/* ---- device: the plain scaled loop with the scaled derivative (bits = -1) ------------------------------------------------ */
+
+/* orbit_pt_scaled (fr_scaled.hip) with u = (ur, ui) beside it.  Returns the escape index (or `iterations`), the final z in
+ * (out_re, out_im) and the scaled derivative in (out_ur, out_ui): the returned step's on escape, the last one's on exhaustion,
+ * (Sinv, 0) for a cap of 0. */
+template <bool JULIA>
+__device__ __forceinline__ uint32_t orbit_pt_scaled_de(uint32_t iterations, double woff_re, double woff_im, const ScaledDev &t,
+                                                       double squared, double &out_re, double &out_im, double &out_ur, double &out_ui) {
+    const double S = t.S, Sinv = t.Sinv;
+    const double2 *X = t.x_orbit;
+    uint32_t last = t.x_last;
+    uint32_t m = JULIA ? 0u : 1u;
+    double wr = woff_re, wi = woff_im;
+    const double wcr = JULIA ? 0.0 : woff_re, wci = JULIA ? 0.0 : woff_im;
+    const double bs0 = JULIA ? 0.0 : Sinv;
+    double2 Z = X[m], N = X[min(m + 1u, last)]; /* m <= last - 1 at the top of every step (a cap of 0 takes none) */
+    const double2 K1 = t.k_orbit[1];            /* the entry after a rebase; K_0 = R_0 = 0 */
+    double zr = __builtin_fma(wr, Sinv, Z.x), zi = __builtin_fma(wi, Sinv, Z.y);
+    double ur = Sinv, ui = 0.0; /* u0 = (Sinv, 0) */
+    uint32_t i = 0;
+    for (; i < iterations; i++) {
+        const double2 P = X[min(m + 2u, last)]; /* X_{m+2}: next step's X_{m+1} if it does not rebase */
+        const double tr = Z.x + zr, ti = Z.y + zi;
+        const double gr = zr + zr, gi = zi + zi; /* the derivative's t: from the z before the step */
+        const double nwr = __builtin_fma(tr, wr, __builtin_fma(-ti, wi, wcr));
+        const double nwi = __builtin_fma(tr, wi, __builtin_fma(ti, wr, wci));
+        const double nur = __builtin_fma(gr, ur, __builtin_fma(-gi, ui, bs0));
+        const double nui = __builtin_fma(gr, ui, gi * ur);
+        m++;
+        zr = __builtin_fma(nwr, Sinv, N.x);
+        zi = __builtin_fma(nwi, Sinv, N.y);
+        wr = nwr;
+        wi = nwi;
+        ur = nur; /* escape returns nu; otherwise u = nu */
+        ui = nui;
+        const double dist = zr * zr + zi * zi;
+        if (dist > squared) break; /* this lane leaves EXEC; the wave goes on while any lane is left */
+        if (rebase_test(zr, zi, wr, wi, S, Sinv) || m == last) { /* a rebase never touches u */
+            wr = zr * S;
+            wi = zi * S;
+            m = 0;
+            if (JULIA) {
+                X = t.k_orbit;
+                last = t.k_last;
+            }
+            Z = make_double2(0.0, 0.0);
+            N = K1;
+        } else {
+            Z = N;
+            N = P;
+        }
+    }
+    out_re = zr;
+    out_im = zi;
+    out_ur = ur;
+    out_ui = ui;
+    return i;
+}
+
+/* ---- device: the scaled loop with table skips and the scaled derivative (bits >= 0) ------------------------------------------ */
+
+/* orbit_bla_scaled (fr_scaled.hip) with u beside it, as orbit_bla_de (fr_de_bla.hip) carries d beside orbit_bla */
+template <bool JULIA>
+__device__ __forceinline__ uint32_t orbit_bla_scaled_de(uint32_t iterations, double woff_re, double woff_im, const ScaledDev &t,
+                                                        double squared, double &out_re, double &out_im, double &out_ur, double &out_ui) {
+    const double S = t.S, Sinv = t.Sinv;
+    const double2 *X = t.x_orbit;
+    const double *R = t.x_R, *CF = t.x_coef;
+    uint32_t last = t.x_last, n0 = t.x_n0;
+    uint32_t m = JULIA ? 0u : 1u;
+    double wr = woff_re, wi = woff_im;
+    const double wcr = JULIA ? 0.0 : woff_re, wci = JULIA ? 0.0 : woff_im;
+    const double bs0 = JULIA ? 0.0 : Sinv;
+    double2 Z = X[m]; /* X_m of the orbit followed */
+    double zr = __builtin_fma(wr, Sinv, Z.x), zi = __builtin_fma(wi, Sinv, Z.y);
+    double ur = Sinv, ui = 0.0; /* u0 = (Sinv, 0) */
+    uint32_t i = 0, result = iterations;
+    while (i < iterations) {
+        /* 1. the level: the largest k in 1 .. kc with (w f)^2 < (R f)^2 (orbit_bla_scaled's search) */
+        const uint32_t j = m - 1u;
+        uint32_t K = 0;
+        if (m >= 1u && j < n0) {
+            const double f = is_big(wr, wi) ? Sinv : 1.0;
+            const double ar = wr * f, ai = wi * f;
+            const double d2 = ar * ar + ai * ai;
+            uint32_t kc = j ? (uint32_t)__builtin_ctz(j) : 31u;          /* j % 2^k == 0 */
+            kc = min(kc, 31u - (uint32_t)__builtin_clz(n0 - j));         /* (j >> k) < n_k, that is j + 2^k <= n0 */
+            kc = min(kc, 31u - (uint32_t)__builtin_clz(iterations - i)); /* i + 2^k <= iterations */
+            uint32_t lo = 0, hi = kc;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi + 1u) >> 1;
+                const double Rf = R[bla_level_offset(n0, mid) + (j >> mid)] * f;
+                if (d2 < Rf * Rf)
+                    lo = mid;
+                else
+                    hi = mid - 1u;
+            }
+            K = lo;
+        }
+        /* 2. the step w' = A w + c and the derivative's u' = g u + b — one arithmetic path each, only the loads behind the branch */
+        double ar, ai, cr = wcr, ci = wci;
+        double gr, gi, br = bs0, bi = -0.0; /* a plain step: fma(g.im, u.re, -0) is g.im * u.re, the definition's product */
+        uint32_t step = 1u;
+        if (K) {
+            const uint32_t e = bla_level_offset(n0, K) + (j >> K);
+            if (JULIA) { /* B wc is +0 = wc for every finite B; the derivative's b is (+0, +0) by definition */
+                const double2 A = reinterpret_cast<const double2 *>(CF)[e];
+                ar = A.x, ai = A.y;
+                br = 0.0, bi = 0.0;
+            } else {
+                const double4 AB = reinterpret_cast<const double4 *>(CF)[e];
+                ar = AB.x, ai = AB.y;
+                cr = __builtin_fma(AB.z, wcr, -(AB.w * wci));
+                ci = __builtin_fma(AB.z, wci, AB.w * wcr);
+                br = AB.z * Sinv, bi = AB.w * Sinv;
+            }
+            gr = ar, gi = ai;
+            step = 1u << K;
+        } else {
+            ar = Z.x + zr, ai = Z.y + zi; /* t = X_m + z */
+            gr = zr + zr, gi = zi + zi;   /* the derivative's t: from the z before the step */
+        }
+        const double nwr = __builtin_fma(ar, wr, __builtin_fma(-ai, wi, cr));
+        const double nwi = __builtin_fma(ar, wi, __builtin_fma(ai, wr, ci));
+        const double nur = __builtin_fma(gr, ur, __builtin_fma(-gi, ui, br));
+        const double nui = __builtin_fma(gr, ui, __builtin_fma(gi, ur, bi));
+        m += step;
+        i += step;
+        const double2 N = X[min(m, last)]; /* m <= last: 1 + ((j >> K) + 1) 2^K <= 1 + n0 */
+        zr = __builtin_fma(nwr, Sinv, N.x);
+        zi = __builtin_fma(nwi, Sinv, N.y);
+        wr = nwr;
+        wi = nwi;
+        ur = nur; /* escape returns nu; otherwise u = nu */
+        ui = nui;
+        /* 3. the tests, the plain scaled loop's; a rebase never touches u */
+        const double dist = zr * zr + zi * zi;
+        if (dist > squared) { /* this lane leaves EXEC; the wave goes on while any lane is left */
+            result = i - 1u;
+            break;
+        }
+        if (rebase_test(zr, zi, wr, wi, S, Sinv) || m == last) {
+            wr = zr * S;
+            wi = zi * S;
+            m = 0;
+            if (JULIA) {
+                X = t.k_orbit;
+                R = t.k_R;
+                CF = t.k_coef;
+                last = t.k_last;
+                n0 = t.k_n0;
+            }
+            Z = make_double2(0.0, 0.0); /* K_0 = R_0 = 0 */
+        } else {
+            Z = N;
+        }
+    }
+    out_re = zr;
+    out_im = zi;
+    out_ur = ur;
+    out_ui = ui;
+    return result;
+}
+
+/* ---- device: the kernels: one body, the loop chosen by BLA ----------------------------------------------------------------- */
+
+template <bool JULIA, bool BLA>
+__device__ __forceinline__ void scaled_de_body(const fr_kparams &p, double *__restrict__ z, uint32_t *__restrict__ iters,
+                                               double *__restrict__ der, const ScaledDev &t) {
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
+    const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
+    stage_woff(p, tid, col0, row0, s_re, s_im);
+    __syncthreads();
+
+    const uint32_t wave = tid >> 6, lane = tid & 63;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
+    const uint32_t cx = col0 + lx, r = row0 + ly;
+    if (!(cx < p.ncols && r < p.nrows)) return;
+    const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0; /* the host picks JULIA from the algorithm */
+
+    double zr = 0.0, zi = 0.0, ur = 0.0, ui = 0.0; /* an algorithm without orbits writes zeros */
+    uint32_t it = 0;
+    if (escape_algo) {
+        const double squared = p.limit * p.limit; /* calc/src/lib.rs:246 */
+        if constexpr (BLA)
+            it = orbit_bla_scaled_de<JULIA>(p.iterations, s_re[lx], s_im[ly], t, squared, zr, zi, ur, ui);
+        else
+            it = orbit_pt_scaled_de<JULIA>(p.iterations, s_re[lx], s_im[ly], t, squared, zr, zi, ur, ui);
+    }
+    const uint64_t k = (uint64_t)r * p.ncols + cx;
+    z[2 * k] = zr;
+    z[2 * k + 1] = zi;
+    iters[k] = it;
+    der[2 * k] = ur;
+    der[2 * k + 1] = ui;
+}
+
+template <bool JULIA>
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_pt_scaled_de_kernel(const fr_kparams p, double *__restrict__ z,
+                                                                              uint32_t *__restrict__ iters, double *__restrict__ der,
+                                                                              const ScaledDev t) {
+    scaled_de_body<JULIA, false>(p, z, iters, der, t);
+}
+
+template <bool JULIA>
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_bla_scaled_de_kernel(const fr_kparams p, double *__restrict__ z,
+                                                                               uint32_t *__restrict__ iters, double *__restrict__ der,
+                                                                               const ScaledDev t) {
+    scaled_de_body<JULIA, true>(p, z, iters, der, t);
+}
+
+hipError_t launch(bool julia, bool bla, const fr_kparams &p, double *z, uint32_t *iters, double *der, const ScaledDev &t,
+                  hipStream_t stream) {
+    dim3 grid, block;
+    const hipError_t e = fr_deep_grid(p, grid, block);
+    if (e != hipSuccess) return e;
+    if (bla) {
+        if (julia)
+            escape_bla_scaled_de_kernel<true><<<grid, block, 0, stream>>>(p, z, iters, der, t);
+        else
+            escape_bla_scaled_de_kernel<false><<<grid, block, 0, stream>>>(p, z, iters, der, t);
+    } else {
+        if (julia)
+            escape_pt_scaled_de_kernel<true><<<grid, block, 0, stream>>>(p, z, iters, der, t);
+        else
+            escape_pt_scaled_de_kernel<false><<<grid, block, 0, stream>>>(p, z, iters, der, t);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
+using namespace fr;
+
+namespace {
+
+/* the launch of rows with their scaled derivatives on the context's orbits and tables; `p` holds the view's scale, the kernels
+ * get a copy with the scaled divisors.  bits < 0: no table.  Arguments already checked. */
+int launch_scaled_de(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_kparams &p, double *d_z, uint32_t *d_iters,
+                     double *d_der, hipStream_t stream) {
+    if (p.ncols == 0 || p.nrows == 0) return FR_OK;
+    const bool julia = cfg->algo == FR_ALGO_JULIA, bla = bits >= 0;
+    if (cfg->algo != FR_ALGO_MANDELBROT && !julia) { /* no escape-time algorithm: zeros, and no orbit is asked for */
+        HIP_TRY(launch(false, bla, p, d_z, d_iters, d_der, ScaledDev{}, stream));
+        return FR_OK;
+    }
+    const ScaledConsts k = scaled_consts(cfg);
+    fr_kparams ps = p;
+    ps.scale_re = k.sre;
+    ps.scale_im = k.sim;
+    std::shared_ptr<PtOrbit> orbit; /* alive until the launch is enqueued, like the table */
+    std::shared_ptr<BlaTable> table;
+    ScaledDev t;
+    const int rc = scaled_dev_fill(ctx, cfg, c, bits, k, orbit, table, t);
+    if (rc != FR_OK) return rc;
+    HIP_TRY(launch(julia, bla, ps, d_z, d_iters, d_der, t, stream));
+    return FR_OK;
+}
+
+/* SCALED PT's domain (bits resolved in place; its limit <= 2^20 is DE's too), then the arrays; *work = false: no rows, nothing
+ * to do and no device needed */
+int check_scaled_de(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1, const void *z, const void *iters,
+                    const void *der, bool *work) {
+    *work = false;
+    const int rc = scaled_check(cfg, c, bits, y0, y1);
+    if (rc != FR_OK) return rc;
+    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
+    if (!z || !iters || !der) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: a DE render writes z, iters and der, all three");
+    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "z and der must be 8-byte aligned, iters 4-byte aligned");
+    *work = true;
+    return FR_OK;
+}
+
+/* rows [y0, y1) as one launch between the profiling events: host_raw's callable, with der where it carries dz */
+auto scaled_de_rows(const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1) {
+    return [=](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_der, uint32_t *, hipStream_t stream) {
+        return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) {
+            kname = bits < 0 ? "escape_pt_scaled_de_kernel" : "escape_bla_scaled_de_kernel";
+            return launch_scaled_de(ctx, cfg, c, bits, p, d_z, d_iters, d_der, stream);
+        });
+    };
+}
+
+}  // namespace
+
+extern "C" {
+
+int fr_escape_rows_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, void *d_z,
+                                       void *d_iters, void *d_der, void *hip_stream) {
+    const Centre c{nullptr, centre, true};
+    bool work;
+    const int rc = check_scaled_de(cfg, c, bits, y0, y1, d_z, d_iters, d_der, &work);
+    if (rc != FR_OK || !work) return rc;
+    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
+        return scaled_de_rows(cfg, c, bits, y0, y1)(ctx, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
+                                                    static_cast<double *>(d_der), nullptr, stream);
+    });
+}
+
+int fr_escape_rows_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, double *z,
+                                uint32_t *iters, double *der) {
+    const Centre c{nullptr, centre, true};
+    bool work;
+    const int rc = check_scaled_de(cfg, c, bits, y0, y1, z, iters, der, &work);
+    if (rc != FR_OK || !work) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
+    /* z and der share the context's z scratch, as in fr_escape_rows_de */
+    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), der, nullptr, false, scaled_de_rows(cfg, c, bits, y0, y1));
+}
+
+int fr_de_scaled_view(const fr_config *cfg, fr_config *view) {
+    if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
+    if (!view) return fail(FR_ERR_INVALID_ARGUMENT, "view is NULL");
+    /* SCALED PT's rules about the scale (fr_wide.hip: check_pt_wide), which are what the constants of a view rest on */
+    const double sre = std::fabs(cfg->scale.re), sim = std::fabs(cfg->scale.im);
+    if (!std::isfinite(sre) || !std::isfinite(sim)) return fail(FR_ERR_INVALID_ARGUMENT, "SCALED PT: the scale of the view must be finite");
+    if (sre < 0x1p-64 || sim < 0x1p-64) return fail(FR_ERR_INVALID_ARGUMENT, "SCALED PT: |scale| must be >= 2^-64 on both axes");
+    if ((sre < sim ? sre : sim) < 0x1p-32 * (sre > sim ? sre : sim))
+        return fail(FR_ERR_INVALID_ARGUMENT, "SCALED PT: min |scale| must be >= 2^-32 max |scale| over the two axes");
+    const ScaledConsts k = scaled_consts(cfg);
+    if (view != cfg) *view = *cfg;
+    view->scale.re = k.sre;
+    view->scale.im = k.sim;
+    return FR_OK;
+}
+
+} /* extern "C" */

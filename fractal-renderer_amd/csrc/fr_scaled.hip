@@ -27,6 +27,9 @@
  * and escape_extend_pt_kernel are to orbit_pt, in their shape; escape_pt_scaled_kernel and orbit_pt_scaled are SCALED PT's and
  * stay as they are.  The table form has no state (BLA-PT's reason: i + 2^k <= iterations).
  *
+ * What the kernels here share with those of DE ON SCALED PT (fr_de_scaled.hip) lives in fr_scaled.h, one copy: ScaledDev and its
+ * fill from the context's caches, kBig, is_big, rebase_test and stage_woff.
+ *
  * The calls, at the end of the file: each builds its Centre (scaled: the wide centre is required), runs check_scaled and hands
  * scaled_rows — the profiled launch of its rows — to the row-call body of its form in fr_ctx.h, as fr_bla.hip's do; the state
  * calls hand scaled_state_rows to fr_ctx.h's state road (state_device, state_host), as fr_pt.hip's do.  The workgroup's
@@ -40,37 +43,12 @@
 #include "fr_bla.h"
 #include "fr_ctx.h"
 #include "fr_math.h"
+#include "fr_scaled.h"
 #include "fr_wide.h"
 
 namespace {
 
 #include "fr_colour.h"
-
-constexpr double kBig = 0x1p500; /* max(|w.re|, |w.im|) >= kBig: w is "big" and the comparisons scale w down, not z up */
-
-/* the orbits, the tables (escape_bla_scaled_kernel only) and the scale as the kernels see them; Mandelbrot: the k fields
- * repeat the x fields */
-struct ScaledDev {
-    const double2 *x_orbit, *k_orbit;
-    const double *x_R, *k_R;       /* R of the levels >= 1 */
-    const double *x_coef, *k_coef; /* Mandelbrot: A.re, A.im, B.re, B.im per entry; Julia: A.re, A.im */
-    uint32_t x_last, k_last;
-    uint32_t x_n0, k_n0; /* entries of level 0: last - 1, or 0 for an empty table */
-    double S, Sinv;      /* 2^e, 2^-e */
-};
-
-__device__ __forceinline__ bool is_big(double wr, double wi) {
-    const double a = __builtin_fabs(wr), b = __builtin_fabs(wi);
-    return (a > b ? a : b) >= kBig;
-}
-
-/* the rebase test of the definition on one arithmetic path: (z fl)^2 < (w fr)^2 with the factors selected by `big` */
-__device__ __forceinline__ bool rebase_test(double zr, double zi, double wr, double wi, double S, double Sinv) {
-    const bool big = is_big(wr, wi);
-    const double fl = big ? 1.0 : S, fr = big ? Sinv : 1.0;
-    const double lr = zr * fl, li = zi * fl, rr = wr * fr, ri = wi * fr;
-    return lr * lr + li * li < rr * rr + ri * ri;
-}
 
 /* ---- device: the plain scaled loop (include/fractal_hip.h, "SCALED PT", bits = -1), operation for operation -------------- */
 
@@ -188,22 +166,6 @@ __device__ __forceinline__ uint32_t orbit_pt_scaled_state(uint32_t steps, double
 }
 
 constexpr uint32_t kOnK = 0x80000000u; /* bit 31 of the stored m: the pixel follows K */
-
-/* 16 column and 16 row values of woff for the workgroup's pixels into LDS (scaled_body's staging: p.scale_re and p.scale_im
- * hold sre and sim); the caller synchronises */
-__device__ __forceinline__ void stage_woff(const fr_kparams &p, uint32_t tid, uint32_t col0, uint32_t row0, double *s_re, double *s_im) {
-    if (tid < kDeepBlockW + kDeepBlockH) {
-        const double width = (double)p.width, height = (double)p.height;
-        if (tid < kDeepBlockW) {
-            const uint64_t x = (uint64_t)p.x_first + (uint64_t)(col0 + tid) * p.x_stride;
-            s_re[tid] = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
-        } else {
-            const uint32_t r = row0 + (tid - kDeepBlockW);
-            const uint64_t y = (uint64_t)p.y_first + (uint64_t)(r / p.block_rows) * p.y_stride + r % p.block_rows;
-            s_im[tid - kDeepBlockW] = (((double)y / height) - 0.5) / p.scale_im;
-        }
-    }
-}
 
 /* escape_pt_scaled_kernel<FR_OUT_ESCAPE>'s shape with the state rule, storing the whole state: z and w as re, im per pixel,
  * iters, m (bit 31: on K).  `ended`: bit 0 = X, bit 1 = K is ended by escape.  An algorithm without orbits writes zeros. */
@@ -565,25 +527,9 @@ int launch_scaled(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, con
     ps.scale_im = k.sim;
     std::shared_ptr<PtOrbit> orbit;
     std::shared_ptr<BlaTable> table;
-    PtOrbitView v;
-    ScaledDev t{};
-    if (bla) {
-        const int rc = bla_table_for(ctx, cfg, c, bits, true, orbit, v, table);
-        if (rc != FR_OK) return rc;
-        const BlaTableDev &d = table->view;
-        t.x_R = d.x_rad, t.k_R = d.k_rad;
-        t.x_coef = d.x_coef, t.k_coef = d.k_coef;
-        t.x_n0 = d.x_n0, t.k_n0 = d.k_n0;
-    } else {
-        const int rc = pt_orbit_view(ctx, cfg, c, orbit, v);
-        if (rc != FR_OK) return rc;
-    }
-    t.x_orbit = v.x;
-    t.k_orbit = v.k;
-    t.x_last = v.x_last;
-    t.k_last = v.k_last;
-    t.S = k.S;
-    t.Sinv = k.Sinv;
+    ScaledDev t;
+    const int rc = scaled_dev_fill(ctx, cfg, c, bits, k, orbit, table, t);
+    if (rc != FR_OK) return rc;
     HIP_TRY(launch(julia, bla, ps, mode, out, t, stream));
     return FR_OK;
 }

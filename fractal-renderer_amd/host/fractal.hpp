@@ -421,6 +421,20 @@ inline std::vector<RGB> get_image_de(const Config &config, Bla bla, double thick
         check(fr_escape_rows_de_pt_bla(&c, pos_lo, centre, bla.bits, 0, c.height, z, iters, der));
     });
 }
+// ... past a scale of 2^440, on SCALED PT (include/fractal_hip.h, "DE ON SCALED PT"): der holds the scaled derivative u = d 2^-e,
+// and the shading is DE's own on the scaled view that fr_de_scaled_view writes.  One sample per pixel.
+inline std::vector<RGB> get_image_de(const Config &config, Scaled scaled, const fr_wide_centre &centre, double thickness = 1.0) {
+    const size_t n = static_cast<size_t>(config.width) * config.height;
+    std::vector<double> z(2 * n), der(2 * n);
+    std::vector<uint32_t> iters(n);
+    check(fr_escape_rows_de_pt_scaled(&config, &centre, scaled.bits, 0, config.height, z.data(), iters.data(), der.data()));
+    Config view = config;
+    check(fr_de_scaled_view(&config, &view));
+    std::vector<RGB> image(n);
+    check(fr_colour_de_rgb8(&view, z.data(), iters.data(), der.data(), n, thickness, reinterpret_cast<uint8_t *>(image.data()),
+                            image.size() * sizeof(RGB)));
+    return image;
+}
 // a kept view's recolour at another thickness, device arrays, asynchronous on hip_stream: no orbit is run
 inline void colour_de_rows_device(const Config &config, const void *d_z, const void *d_iters, const void *d_der, double thickness,
                                   void *d_out, int channels = 4, void *hip_stream = nullptr) {

@@ -434,6 +434,50 @@ typedef struct fr_config {
  * iterations makes a run at cap N no prefix of the run at cap M); multi-device and block-cyclic renders; the command line
  * (--distance-shade with --bla stays refused).  Supersampling is SUPERSAMPLED DE below, with FR_PT_ROAD_BLA. */
 /*
+ * DE ON SCALED PT (fr_escape_rows_de_pt_scaled(_device) and fr_de_scaled_view below): distance estimation past a scale of 2^440,
+ * with its own calls; the DE calls above and SUPERSAMPLED DE below keep refusing SCALED PT.  At a pixel D pixels from the set
+ * |d| is about |z| ln|z| * height * |scale| / D, of the order 2^e and above, so dn2 = |d|^2 leaves f64 from e = 512.  The
+ * road carries a SCALED derivative u = d 2^-e instead, as it carries w = dz 2^e for the offset.
+ * It is SCALED PT's definition above word for word, in both forms (bits = -1, the plain scaled loop, and bits >= 0, the table) —
+ * the orbits, S, Sinv, sre, sim and woff; the pixel state, the step and the BIG / not-BIG rebase test; the table with R and Dw,
+ * the level search, the skip and the escape test — and beside it runs the scaled derivative u.  Every operation is ONE correctly
+ * rounded f64 operation; fma is fused and nothing else is.
+ *   u0 = (Sinv, 0).  bs0 = Sinv for Mandelbrot and 0 for Julia.
+ *   Plain step, from the z the loop holds before the step:
+ *     t  = (z.re + z.re, z.im + z.im)
+ *     nu = (fma(t.re, u.re, fma(-t.im, u.im, bs0)), fma(t.re, u.im, t.im * u.re))
+ *   Skip with the entry (A, B) of level K: b = (B.re * Sinv, B.im * Sinv) for Mandelbrot, one multiplication each;
+ *   b = (+0, +0) for Julia;
+ *     nu = (fma(A.re, u.re, fma(-A.im, u.im, b.re)), fma(A.re, u.im, fma(A.im, u.re, b.im)))
+ *   Escape returns (z, index, nu), the index being i in the plain loop and i - 1 after a pass of the table form; otherwise
+ *   u = nu.  Exhaustion returns (z, iterations, u).  A rebase never touches u.  iterations = 0 returns (start, 0, (Sinv, 0)).
+ *   An algorithm without orbits writes zeros.  u may become +-inf or NaN, as in DE (a NaN is any NaN).  The stored der array
+ *   holds u: the derivative with respect to the view's SCALED coordinate.
+ *   THE SCALED VIEW: cfg_v is cfg with scale = (sre, sim) = (scale.re * Sinv, scale.im * Sinv), both products exact, every other
+ *   field unchanged (fr_de_scaled_view writes it).  The distance and the shading are DE's own calls, run on cfg_v:
+ *   fr_distance_rows(_device), fr_colour_de_rows_device, fr_colour_de_rgb8, and fr_colour_de_rows_ss_device for a kept view.  Of
+ *   the view they read only height, scale, iterations and the colour fields, so
+ *     D = (num / sqrt(u.re*u.re + u.im*u.im)) * ((double)height * min(|sre|, |sim|))
+ *   — d = u 2^e and scale = (sre, sim) 2^e: the factor 2^e cancels in D.  No distance or colour kernel is added or changed.
+ *   CLAIM 1: z and iters are fr_escape_rows_pt_scaled's for the same bits, bit for bit: the derivative only reads.
+ *   CLAIM 2: in the common domain (WIDE PT's: |scale| <= 2^440, limit <= 2^20), and where no intermediate of either run is
+ *   subnormal or overflows, u = d 2^-e exactly, d from fr_escape_rows_de_pt_wide for bits = -1 or from fr_escape_rows_de_pt_bla
+ *   with the wide centre for bits >= 0 (the latter with SCALED PT's own caveat about a pixel with |w| < 2^-53), and D on cfg_v
+ *   equals D of DE on cfg, bit for bit.  The reason: (q 2^e) (p 2^-e) rounds as q p does — every product in the u chain is the
+ *   product of the d chain times 2^-e, bs0 = b0 2^-e and B Sinv = B 2^-e are exact, and in D the scale's 2^e cancels the same way.
+ *   CLAIM 3, the range (DESIGN.md 3.24 writes the argument out).  Overflow: un2 = u.re*u.re + u.im*u.im = +inf needs a component
+ *   of u near 2^512, which gives D = 0 where the true distance is below about height * 2^-465 pixels: DE's bound carried over,
+ *   since pixels_v = height * min(|sre|, |sim|) <= height.  Underflow: un2 underflows only for |u| < 2^-511; then D exceeds every
+ *   admissible thickness (<= 2^20) or is +inf, such a pixel is never shaded and never should be, and ITS REPORTED DISTANCE IS
+ *   NOT ACCURATE THERE.  Components: a single component of u may go subnormal beside a large one (|component of d| < 2^(e-1022));
+ *   its square is below 2^-2044 of the other's and does not move un2, hence not D.
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): SCALED PT's, with the centre REQUIRED; its
+ * limit <= 2^20 is DE's too; bits -1, 0 (FR_BLA_DEFAULT_BITS) or 24 .. 53; all three arrays, z and der 8-byte aligned, iters
+ * 4-byte aligned; y0 == y1 is a no-op that needs no device and no array.
+ * Out of scope: a resumable state or an extend form for scaled DE; supersampling (fr_render_rows_ss_de keeps refusing
+ * FR_PT_ROAD_SCALED; a kept scaled view is filtered by fr_colour_de_rows_ss_device on cfg_v); the command line; the Rust shim;
+ * multi-device and block-cyclic renders. */
+/*
  * SUPERSAMPLED DE (fr_render_rows_ss_de, fr_colour_de_rows_ss_device below): distance estimation and supersampling at once —
  * filaments thinner than a pixel stay visible AND the borders are anti-aliased.  DEFINITION, for supersample = s,
  * 1 <= s <= FR_SS_MAX, and a thickness T in OUTPUT pixels:
@@ -1134,6 +1178,22 @@ int fr_escape_rows_de_pt_bla_device(const fr_config *cfg, const fr_imaginary *po
                                     uint32_t y1, void *d_z, void *d_iters, void *d_der, void *hip_stream);
 int fr_escape_rows_de_pt_bla(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
                              uint32_t y1, double *z, uint32_t *iters, double *der);
+/* DE ON SCALED PT (defined at fr_precision above): rows [y0, y1) with their SCALED derivatives u = d 2^-e on the SCALED PT road;
+ * centre (required) and bits (-1: the plain scaled loop, 0 or 24 .. 53: the table) as the fr_*_pt_scaled calls take them.  The
+ * arrays are fr_escape_rows_de's: all three required, y0 == y1 a no-op that needs no device.  z and iters are
+ * fr_escape_rows_pt_scaled's bit for bit.  Orbits and tables are the context's caches, shared with the fr_*_pt_scaled calls of
+ * the same view and bits (fr_debug_bla_cache shows a table served).  With profiling on, fr_last_kernel_name reports
+ * escape_pt_scaled_de_kernel / escape_bla_scaled_de_kernel. */
+int fr_escape_rows_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, void *d_z,
+                                       void *d_iters, void *d_der, void *hip_stream);
+int fr_escape_rows_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, double *z,
+                                uint32_t *iters, double *der);
+/* The scaled view cfg_v of DE ON SCALED PT: *view = *cfg with scale = (scale.re * Sinv, scale.im * Sinv), both exact.  The
+ * distance and the shading of a scaled DE render are DE's own calls run on it (fr_distance_rows(_device),
+ * fr_colour_de_rows_device, fr_colour_de_rgb8, fr_colour_de_rows_ss_device).  Host only; `view` may alias `cfg`.  Refuses what
+ * SCALED PT's rules about the scale refuse: a NULL argument, a scale that is not finite, |scale| < 2^-64 on an axis, min |scale| <
+ * 2^-32 max |scale|. */
+int fr_de_scaled_view(const fr_config *cfg, fr_config *view);
 /* RESUMABLE DE (defined at fr_precision above): a kept DE view answers an iterations change in place, derivative included.
  *
  * The F64 road: raise the cap of the (z, iters, der) that fr_escape_rows_de(_device) wrote, N = from_iterations -> M =
