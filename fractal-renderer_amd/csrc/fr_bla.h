@@ -35,6 +35,7 @@ struct BlaTableDev {
 struct BlaTable {
     std::weak_ptr<PtOrbit> orbit; /* identity of the orbits the tables were built from; holds no device memory alive */
     double D = 0.0;               /* D, or Dw of a scaled table */
+    double S = 1.0;               /* S = 2^e of a scaled table (eps and every stored R are proportional to it); BLA-PT: 1 */
     int bits = 0;
     bool scaled = false; /* SCALED PT's table: R in place of r2 */
     void *dev = nullptr;

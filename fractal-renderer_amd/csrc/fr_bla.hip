@@ -6,9 +6,10 @@
  *
  * Host part: the table of an orbit, built from its stored f64 entries alone (the orbit comes from fr_pt.hip's cache, dd or
  * wide), with -ffp-contract=off and std::fma exactly where the definition has fma; uploaded once and kept per context
- * (Ctx::bla_table, under Ctx::pt_mu), keyed by the orbit's identity, D and bits.  SCALED PT's table (fr_scaled.hip) is the
+ * (Ctx::bla_table, under Ctx::pt_mu), keyed by the orbit's identity, D, S and bits.  SCALED PT's table (fr_scaled.hip) is the
  * same build with eps S for eps, Dw for D and the scaled radius R stored where BLA-PT stores r2; it shares the slot, with its
- * kind in the key (fr_bla.h).
+ * kind in the key (fr_bla.h).  S = 2^e is a key field of its own (BLA-PT: 1): two views whose scales differ by a power of two
+ * share the orbit, (sre, sim) and with them Dw bit for bit, and every R of one is 2^k times the other's.
  *
  * Device layout of one orbit's table: the levels k >= 1 one after another (level 0 only builds the levels above it and never
  * leaves the host); level k starts at entry bla_level_offset(n0, k), a closed form, so the kernel needs no offset array.  r2
@@ -339,7 +340,8 @@ double image_D(const fr_config *cfg) {
 
 namespace fr {
 
-/* fr_bla.h: one slot per context for both kinds of table, keyed by the orbit, D (or Dw), bits and the kind */
+/* fr_bla.h: one slot per context for both kinds of table, keyed by the orbit, D (or Dw), S (1 for BLA-PT), bits and the kind:
+ * everything build_table reads */
 int bla_table_for(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, bool scaled, std::shared_ptr<PtOrbit> &orbit,
                   PtOrbitView &v, std::shared_ptr<BlaTable> &out) {
     const int rc = pt_orbit_view(ctx, cfg, c, orbit, v);
@@ -354,8 +356,8 @@ int bla_table_for(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, boo
     const double D = image_D(&image);
     std::lock_guard<std::mutex> lk(ctx.pt_mu);
     const std::shared_ptr<BlaTable> cached = ctx.bla_table;
-    if (cached && cached->orbit.lock() == orbit && memcmp(&cached->D, &D, sizeof D) == 0 && cached->bits == bits &&
-        cached->scaled == scaled) {
+    if (cached && cached->orbit.lock() == orbit && memcmp(&cached->D, &D, sizeof D) == 0 && memcmp(&cached->S, &S, sizeof S) == 0 &&
+        cached->bits == bits && cached->scaled == scaled) {
         cached->built = false;
         out = cached;
         return FR_OK;
@@ -382,6 +384,7 @@ int bla_table_for(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, boo
     auto t = std::make_shared<BlaTable>();
     t->orbit = orbit;
     t->D = D;
+    t->S = S;
     t->bits = bits;
     t->scaled = scaled;
     t->x_levels = tx.levels();

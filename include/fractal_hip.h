@@ -1041,7 +1041,8 @@ int fr_debug_bla_cache(uint32_t out[4]);
 /* The SCALED PT calls (fr_precision above, "SCALED PT").  `centre` is required; cfg->pos is not read.  bits: -1 = no table
  * (the plain scaled loop, WIDE PT's counterpart), 0 = FR_BLA_DEFAULT_BITS, else 24 .. 53 (BLA-PT's counterpart).  y0 == y1 and
  * argument errors need no device.  The orbit is the one the fr_*_pt_wide calls cache (either road serves the other); the
- * table is built, uploaded and kept per context as BLA-PT's is, in the same slot, keyed by the orbit, Dw, bits and its kind.
+ * table is built, uploaded and kept per context as BLA-PT's is, in the same slot, keyed by the orbit, Dw, S, bits and its kind
+ * (S = 2^e on its own: a scale 2^k times another's has the same orbit and Dw, and every radius 2^k times as large).
  * fr_render_rows_pt_scaled(_device): the buffers, channels, alignment and asynchrony of fr_render_rows_pt_wide(_device).
  * fr_escape_rows_pt_scaled(_device): as fr_escape_rows_pt_bla(_device); fr_colour_rgb8 / fr_colour_rows_device over the
  * results reproduces the render.  With profiling on, fr_last_kernel_name reports escape_pt_scaled_kernel (bits = -1) or

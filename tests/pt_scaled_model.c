@@ -277,3 +277,39 @@ int ptsm_rows(const ptsm_view *v, const double *x, uint32_t x_last, const double
     free(sk);
     return good;
 }
+
+/* ptsm_rows with a FOREIGN table: the tables are built with tv's Dw and S, everything else — the pixel loop's constants, the
+ * offsets, the cap, the limit, the orbits — is v's.  What a kernel computes that is handed the tables of another view on the
+ * same orbits (tests/test_table_cache_cpu.py).  tv = v: ptsm_rows, bit for bit.  bits >= 0. */
+int ptsm_rows_table_of(const ptsm_view *v, const ptsm_view *tv, const double *x, uint32_t x_last, const double *k, uint32_t k_last,
+                       int bits, uint32_t y0, uint32_t y1, double *z2, uint32_t *iters, uint32_t *passes, uint32_t *rebases) {
+    const ptsm_consts c = consts(v);
+    const double Dw = ptsm_Dw(tv), S = consts(tv).S, b0 = v->julia ? 0.0 : 1.0;
+    ptsm_table tx, tk;
+    tx.levels = tk.levels = 0;
+    ptsm_entry *sx = NULL, *sk = NULL;
+    if (bits < 0) return 0;
+    sx = malloc((size_t)(ptsm_table_entries(x_last) + 1) * sizeof(ptsm_entry));
+    if (!sx) return 0;
+    build(x, x_last, Dw, S, b0, bits, &tx, sx);
+    followed ox = {x, x_last, &tx}, ok = ox;
+    if (v->julia) {
+        sk = malloc((size_t)(ptsm_table_entries(k_last) + 1) * sizeof(ptsm_entry));
+        if (!sk) {
+            free(sx);
+            return 0;
+        }
+        build(k, k_last, Dw, S, b0, bits, &tk, sk);
+        ok.x = k, ok.last = k_last, ok.t = &tk;
+    }
+    int good = 1;
+    for (uint32_t y = y0; y < y1; y++)
+        for (uint32_t xx = 0; xx < v->width; xx++) {
+            const uint64_t p = (uint64_t)(y - y0) * v->width + xx;
+            iters[p] = pixel(v, &c, &ox, &ok, xx, y, &z2[2 * p], &z2[2 * p + 1], &passes[p], &rebases[p]);
+            if (iters[p] == 0xFFFFFFFFu) good = 0;
+        }
+    free(sx);
+    free(sk);
+    return good;
+}

@@ -52,6 +52,8 @@ def lib():
     L.ptsm_rows.restype = C.c_int
     L.ptsm_rows.argtypes = [C.POINTER(_View), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ptsm_rows_table_of.restype = C.c_int
+    L.ptsm_rows_table_of.argtypes = [C.POINTER(_View), C.POINTER(_View)] + L.ptsm_rows.argtypes[1:]
     _lib = L
     return L
 
@@ -102,6 +104,24 @@ def escape_rows(cfg, x_orbit, k_orbit=None, bits=NO_TABLE, y0=0, y1=None):
     it, passes, reb = (np.empty(shape, dtype=np.uint32) for _ in range(3))
     ok = lib().ptsm_rows(C.byref(v), x_orbit.ctypes.data, len(x_orbit) - 1, k_orbit.ctypes.data, len(k_orbit) - 1, bits, y0, y1,
                          z.ctypes.data, it.ctypes.data, passes.ctypes.data, reb.ctypes.data)
+    assert ok, "pt_scaled_model: out of memory, or a step went past the end of an orbit"
+    return z, it, passes, reb
+
+
+def escape_rows_table_of(cfg, table_cfg, x_orbit, k_orbit=None, bits=40, y0=0, y1=None):
+    """escape_rows with a FOREIGN table: the tables are built with table_cfg's Dw and S, everything else is cfg's — what a
+    kernel computes that is handed another view's tables on the same orbits.  table_cfg = cfg: escape_rows, bit for bit."""
+    assert bits >= 0
+    y1 = cfg.height if y1 is None else y1
+    x_orbit = _orbit(x_orbit)
+    k_orbit = x_orbit if k_orbit is None else _orbit(k_orbit)
+    assert (cfg.algo == 2) == (k_orbit is not x_orbit)
+    v, tv = _view(cfg), _view(table_cfg)
+    shape = (y1 - y0, cfg.width)
+    z = np.empty(shape + (2,), dtype=np.float64)
+    it, passes, reb = (np.empty(shape, dtype=np.uint32) for _ in range(3))
+    ok = lib().ptsm_rows_table_of(C.byref(v), C.byref(tv), x_orbit.ctypes.data, len(x_orbit) - 1, k_orbit.ctypes.data,
+                                  len(k_orbit) - 1, bits, y0, y1, z.ctypes.data, it.ctypes.data, passes.ctypes.data, reb.ctypes.data)
     assert ok, "pt_scaled_model: out of memory, or a step went past the end of an orbit"
     return z, it, passes, reb
 
