@@ -76,7 +76,8 @@ def assert_same(got, want, what):
 
 
 class Road:
-    """the calls of one view: its config, and its centre (wide) or pos_lo (dd) kept alive beside it"""
+    """the calls of one view: its config, and its centre (wide) or pos_lo (dd) kept alive beside it.  `name` is one of
+    deep_truth.VIEWS, or a Spec, a record of tests/deep_random_views.py or a deep_truth.View in its place."""
 
     def __init__(self, fr, native, lib, name, cap=None):
         self.lib, self.v = lib, T.view(name)
