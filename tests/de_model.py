@@ -22,6 +22,7 @@ import pt_model as PTM
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "de_model.c")
 ORACLE = os.path.join(os.path.dirname(HERE), "oracle")
+THREADS = max(1, min(16, os.cpu_count() or 1))  # for the oracle's colour map, whose own default is a thread per processor
 
 _lib = None
 
@@ -119,7 +120,7 @@ def base_colours(cfg, z, it):
     mode = O.lib().fro_get_log2_mode()
     O.set_log2_mode(O.LOG2_SOFT)
     try:
-        return O.colour_rows(ocfg, z, it)
+        return O.colour_rows(ocfg, z, it, THREADS)
     finally:
         O.set_log2_mode(mode)
 
