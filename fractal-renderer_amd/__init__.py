@@ -42,6 +42,7 @@ __all__ = [
     "extend_rows_de_pt_device",
     "ss_de_workspace_bytes", "colour_image_de_ss", "colour_de_rows_ss_device",
     "de_scaled_view",
+    "escape_rows_de_pt_scaled_state", "extend_rows_de_pt_scaled", "get_image_de_scaled_ss",
 ]
 
 
@@ -1016,7 +1017,7 @@ def get_image_de(config, thickness=1.0, precision=Precision.F64, pos_lo=None, ce
     if scaled:
         if s != 1 or y0 != 0 or y1 is not None or int(channels) != 3:
             raise ValueError("scaled=True: supersample > 1, a row range and channels=4 are out of scope of DE ON SCALED PT "
-                             "(fr_render_rows_ss_de refuses FR_PT_ROAD_SCALED)")
+                             "(fr_render_rows_ss_de refuses FR_PT_ROAD_SCALED); get_image_de_scaled_ss renders them")
         z, it, der = escape_rows_de(config, precision=precision, pos_lo=pos_lo, centre=centre, bla=bla, opts=opts, scaled=True)
         return colour_image_de(de_scaled_view(config), z, it, der, thickness)
     if s == 1 and y0 == 0 and y1 is None and int(channels) == 3:
@@ -1034,6 +1035,58 @@ def get_image_de(config, thickness=1.0, precision=Precision.F64, pos_lo=None, ce
     _native.check(_native.load().fr_render_rows_ss_de(C.byref(config), int(precision), None if lo is None else C.byref(lo),
                                                       None if st is None else C.byref(st), road, bits, float(thickness), s, y0, y1,
                                                       int(channels), out.ctypes.data, out.nbytes))
+    return out
+
+
+def _scaled_centre(centre):
+    if centre is None:
+        raise ValueError("the scaled calls need centre= (a WideCentre)")
+    return centre.c_struct()
+
+
+def escape_rows_de_pt_scaled_state(config, centre, y0=0, y1=None):
+    """fr_escape_rows_de_pt_scaled_state: rows [y0, y1) on SCALED PT's plain loop with their resumable DE state
+    (include/fractal_hip.h, "RESUMABLE SCALED DE"): (z float64 [rows, width, 2], iters uint32 [rows, width], w float64 [rows,
+    width, 2], m uint32 [rows, width], der float64 [rows, width, 2] holding u = d 2^-e).  z, iters, der are
+    escape_rows_de(..., scaled=True)'s, w and m escape_rows_pt_state(..., scaled=True)'s.  centre: a WideCentre, required."""
+    st = _scaled_centre(centre)
+    y0, y1 = _rows(config, y0, y1)
+    shape = (max(y1 - y0, 0), config.width)
+    z, w, der = (np.empty(shape + (2,), dtype=np.float64) for _ in range(3))
+    it, m = np.empty(shape, dtype=np.uint32), np.empty(shape, dtype=np.uint32)
+    _native.check(_native.load().fr_escape_rows_de_pt_scaled_state(C.byref(config), C.byref(st), y0, y1, z.ctypes.data, it.ctypes.data,
+                                                                   w.ctypes.data, m.ctypes.data, der.ctypes.data))
+    return z, it, w, m, der
+
+
+def extend_rows_de_pt_scaled(config, z, iters, w, m, der, from_iterations, centre, y0=0, y1=None):
+    """fr_escape_extend_de_pt_scaled over numpy arrays: the state escape_rows_de_pt_scaled_state returned at the cap
+    `from_iterations` -> the state at config.iterations (copies; the arguments are left alone).  The arrays must be that view's;
+    the library cannot check it."""
+    st = _scaled_centre(centre)
+    y0, y1 = _rows(config, y0, y1)
+    z, iters, w, m, der = _de_state_arrays(config, y0, y1, z, iters, w, m, der)
+    _native.check(_native.load().fr_escape_extend_de_pt_scaled(C.byref(config), C.byref(st), y0, y1, int(from_iterations), z.ctypes.data,
+                                                               iters.ctypes.data, w.ctypes.data, m.ctypes.data, der.ctypes.data))
+    return z, iters, w, m, der
+
+
+def get_image_de_scaled_ss(config, thickness, centre, supersample, bla=None, y0=0, y1=None, channels=3):
+    """fr_render_rows_ss_de_pt_scaled (include/fractal_hip.h, "SUPERSAMPLED SCALED DE"): rows [y0, y1) of the distance-shaded image
+    past a scale of 2^440 with supersample x supersample samples per pixel — escape_rows_de(..., scaled=True) on the s times larger
+    image a band at a time, shaded on its scaled view with thickness * s in sample pixels and box-filtered on the device — as uint8
+    [y1-y0, width, channels].  centre: a WideCentre, required; bla: None (the plain scaled loop), 0 or 24 .. 53."""
+    s = int(supersample)
+    if not 1 <= s <= SS_MAX:
+        raise ValueError("supersample is 1 .. %d" % SS_MAX)
+    if int(channels) not in (3, 4):
+        raise ValueError("channels is 3 or 4")
+    _road, bits = _ss_pt_road(None, centre, bla, True)
+    st = centre.c_struct()
+    y0, y1 = _rows(config, y0, y1)
+    out = np.empty((max(y1 - y0, 0), config.width, int(channels)), dtype=np.uint8)
+    _native.check(_native.load().fr_render_rows_ss_de_pt_scaled(C.byref(config), C.byref(st), bits, float(thickness), s, y0, y1,
+                                                                int(channels), out.ctypes.data, out.nbytes))
     return out
 
 

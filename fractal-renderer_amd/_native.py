@@ -447,6 +447,21 @@ PROTOTYPES = {
         [C.POINTER(fr_config), C.POINTER(Imaginary), _WIDE, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
          C.c_void_p, C.c_void_p],
     ),
+    "fr_escape_rows_de_pt_scaled_state_device": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "fr_escape_rows_de_pt_scaled_state": (
+        C.c_int, [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fr_escape_extend_de_pt_scaled_device": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p],
+    ),
+    "fr_escape_extend_de_pt_scaled": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
     "fr_distance_rows_device": (
         C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "fr_distance_rows": (C.c_int, [C.POINTER(fr_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -477,6 +492,15 @@ PROTOTYPES = {
         C.c_int,
         [C.POINTER(fr_config), C.c_int, C.POINTER(Imaginary), _WIDE, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32,
          C.c_int, C.c_void_p, C.c_size_t],
+    ),
+    "fr_render_rows_ss_de_pt_scaled_device": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t,
+         C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "fr_render_rows_ss_de_pt_scaled": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t],
     ),
     "fr_count_iterations": (
         C.c_int,

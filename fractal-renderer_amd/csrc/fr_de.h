@@ -2,7 +2,8 @@
  * fr_de.h — internal: what the supersampled DE roads (fr_ss_de.hip) take from the DE roads, as fr_bla.h lends BLA-PT's row
  * launch to fr_ss.hip.  Each pair is the domain check the road's own calls run (the file-local de_check / check_bla_de, short of
  * the arrays) and the road's row launch (the file-local de_rows / bla_de_rows), called: rows [y0, y1) of cfg with their
- * derivatives into device arrays on `stream`, between the profiling events.
+ * derivatives into device arrays on `stream`, between the profiling events.  And what RESUMABLE SCALED DE (fr_de_scaled.hip) takes
+ * from RESUMABLE DE (fr_de.hip): the host and device plumbing of a DE state's five arrays, one copy.
  */
 #ifndef FR_DE_H
 #define FR_DE_H
@@ -19,6 +20,27 @@ int de_render_rows(Ctx &ctx, const fr_config *cfg, int precision, const Centre &
 int bla_de_domain(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1);
 int bla_de_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, double *d_z, uint32_t *d_iters,
                        double *d_der, hipStream_t stream);
+
+/* DE ON SCALED PT (fr_de_scaled.hip) for SUPERSAMPLED SCALED DE; bits resolved in place, the centre required */
+int scaled_de_domain(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1);
+int scaled_de_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, double *d_z,
+                          uint32_t *d_iters, double *d_der, hipStream_t stream);
+
+/* The five arrays of a DE state — z, iters, the offset d (PT: dz, SCALED PT: w), m and der — after the road's domain check: the
+ * one copy of what fr_escape_rows_de_pt_state / fr_escape_extend_de_pt and their scaled counterparts (fr_de_scaled.hip) do with
+ * them (fr_de.hip).  `from` = nullptr: the state render, else the extension from *from.  Both forms check what is left of the
+ * calls' domain (the lower cap, NULL and misaligned arrays: texts that name `road` and `d_name`) and return FR_OK without a
+ * device where there is nothing to do; the device form then runs `rows` on the caller's stream, the host form keeps z, d and der
+ * in the context's z scratch and iters and m in its iters scratch, uploads them first for an extension, and synchronises.  `rows`
+ * is a plain function with its arguments behind `self`: nothing is allocated on the call path. */
+struct DeStateRows {
+    int (*fn)(const void *self, Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_d, uint32_t *d_m, double *d_der, hipStream_t stream);
+    const void *self;
+};
+int de_state_device(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z, void *d_iters, void *d_d, void *d_m,
+                    void *d_der, void *hip_stream, const char *road, const char *d_name, const DeStateRows &rows);
+int de_state_host(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, double *z, uint32_t *iters, double *d, uint32_t *m,
+                  double *der, const char *road, const char *d_name, const DeStateRows &rows);
 
 }  // namespace fr
 

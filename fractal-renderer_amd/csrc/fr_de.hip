@@ -568,20 +568,21 @@ int de_rows_host(const fr_config *cfg, int precision, const Centre &c, bool wide
 /* ---- RESUMABLE DE: the state render of PT and the two extensions ------------------------------------------------------------ */
 
 /* The arrays of a RESUMABLE DE call and what is left of its domain after the road's (check_state's order and its M < N text,
- * fr_ctx.h).  pt: the five arrays of the PT state, else the F64 road's three.  `from` = nullptr: the state render.  *work = false:
+ * fr_ctx.h).  pt: the five arrays of a perturbation road's state (`road` and `d_name` name it and its offset in the texts: PT and
+ * dz, SCALED PT and w), else the F64 road's three.  `from` = nullptr: the state render.  *work = false:
  * a legal call with nothing to do (no rows; for an extension also M == N or an algorithm without orbits). */
 int de_state_check(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, bool pt, const void *z, const void *iters,
-                   const void *dz, const void *m, const void *der, bool *work) {
+                   const void *dz, const void *m, const void *der, bool *work, const char *road = "PT", const char *d_name = "dz") {
     *work = false;
     if (from && cfg->iterations < *from)
         return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from a stored state");
     if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
     if (pt) {
         if (!z || !iters || !dz || !m || !der)
-            return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the DE state of PT is z, iters, dz, m and der, all five");
+            return fail(FR_ERR_INVALID_ARGUMENT, std::string("NULL array: the DE state of ") + road + " is z, iters, " + d_name + ", m and der, all five");
         if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(dz) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) ||
             (reinterpret_cast<uintptr_t>(iters) & 3u) || (reinterpret_cast<uintptr_t>(m) & 3u))
-            return fail(FR_ERR_INVALID_ARGUMENT, "z, dz and der must be 8-byte aligned, iters and m 4-byte aligned");
+            return fail(FR_ERR_INVALID_ARGUMENT, std::string("z, ") + d_name + " and der must be 8-byte aligned, iters and m 4-byte aligned");
     } else {
         if (!z || !iters || !der) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the extension of a DE view needs z, iters and der, all three");
         if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u))
@@ -670,51 +671,32 @@ int de_pt_state_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, uint32_t y
     });
 }
 
+/* de_pt_state_rows behind fr_de.h's DeStateRows */
+struct PtStateCall {
+    const fr_config *cfg;
+    const Centre *c;
+    uint32_t y0, y1;
+    const uint32_t *from;
+    static int run(const void *self, Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_dz, uint32_t *d_m, double *d_der, hipStream_t stream) {
+        const PtStateCall &a = *static_cast<const PtStateCall *>(self);
+        return de_pt_state_rows(ctx, a.cfg, *a.c, a.y0, a.y1, a.from, d_z, d_iters, d_dz, d_m, d_der, stream);
+    }
+};
+
 int de_pt_state_device(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z, void *d_iters,
                        void *d_dz, void *d_m, void *d_der, void *hip_stream) {
-    int rc = de_pt_state_domain(cfg, c, y0, y1);
+    const int rc = de_pt_state_domain(cfg, c, y0, y1);
     if (rc != FR_OK) return rc;
-    bool work;
-    rc = de_state_check(cfg, y0, y1, from, true, d_z, d_iters, d_dz, d_m, d_der, &work);
-    if (rc != FR_OK || !work) return rc;
-    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
-        return de_pt_state_rows(ctx, cfg, c, y0, y1, from, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
-                                static_cast<double *>(d_dz), static_cast<uint32_t *>(d_m), static_cast<double *>(d_der), stream);
-    });
+    const PtStateCall call{cfg, &c, y0, y1, from};
+    return de_state_device(cfg, y0, y1, from, d_z, d_iters, d_dz, d_m, d_der, hip_stream, "PT", "dz", DeStateRows{PtStateCall::run, &call});
 }
 
-/* The host form of the five arrays, done here as fr_distance_rows does its own (host_raw carries four): z, dz and der in the
- * context's z scratch, iters and m in its iters scratch; an extension uploads them first. */
 int de_pt_state_host(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, double *z, uint32_t *iters,
                      double *dz, uint32_t *m, double *der) {
-    int rc = de_pt_state_domain(cfg, c, y0, y1);
+    const int rc = de_pt_state_domain(cfg, c, y0, y1);
     if (rc != FR_OK) return rc;
-    bool work;
-    rc = de_state_check(cfg, y0, y1, from, true, z, iters, dz, m, der, &work);
-    if (rc != FR_OK || !work) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0), zb = npx * 2 * sizeof(double), ib = npx * sizeof(uint32_t);
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    rc = ctx->reserve(ctx->z, 3 * zb);
-    if (rc == FR_OK) rc = ctx->reserve(ctx->iters, 2 * ib);
-    if (rc != FR_OK) return rc;
-    char *const dd = static_cast<char *>(ctx->z.ptr), *const du = static_cast<char *>(ctx->iters.ptr);
-    const struct {
-        void *host, *dev;
-        size_t bytes;
-    } arrays[5] = {{z, dd, zb}, {iters, du, ib}, {dz, dd + zb, zb}, {m, du + ib, ib}, {der, dd + 2 * zb, zb}};
-    if (from)
-        for (const auto &a : arrays) HIP_TRY(hipMemcpyAsync(a.dev, a.host, a.bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = de_pt_state_rows(*ctx, cfg, c, y0, y1, from, static_cast<double *>(arrays[0].dev), static_cast<uint32_t *>(arrays[1].dev),
-                          static_cast<double *>(arrays[2].dev), static_cast<uint32_t *>(arrays[3].dev), static_cast<double *>(arrays[4].dev),
-                          ctx->stream);
-    if (rc != FR_OK) return rc;
-    for (const auto &a : arrays) HIP_TRY(hipMemcpyAsync(a.host, a.dev, a.bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FR_OK;
+    const PtStateCall call{cfg, &c, y0, y1, from};
+    return de_state_host(cfg, y0, y1, from, z, iters, dz, m, der, "PT", "dz", DeStateRows{PtStateCall::run, &call});
 }
 
 /* the domain of the calls over stored results, short of their output */
@@ -768,6 +750,48 @@ int de_domain(const fr_config *cfg, int precision, const Centre &c, bool wide_ca
 int de_render_rows(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, uint32_t y0, uint32_t y1, double *d_z, uint32_t *d_iters,
                    double *d_der, hipStream_t stream) {
     return de_rows(cfg, precision, c, y0, y1)(ctx, d_z, d_iters, d_der, nullptr, stream);
+}
+
+int de_state_device(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z, void *d_iters, void *d_d, void *d_m,
+                    void *d_der, void *hip_stream, const char *road, const char *d_name, const DeStateRows &rows) {
+    bool work;
+    const int rc = de_state_check(cfg, y0, y1, from, true, d_z, d_iters, d_d, d_m, d_der, &work, road, d_name);
+    if (rc != FR_OK || !work) return rc;
+    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
+        return rows.fn(rows.self, ctx, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters), static_cast<double *>(d_d),
+                       static_cast<uint32_t *>(d_m), static_cast<double *>(d_der), stream);
+    });
+}
+
+/* The host form of the five arrays, done here as fr_distance_rows does its own (host_raw carries four): z, d and der in the
+ * context's z scratch, iters and m in its iters scratch; an extension uploads them first. */
+int de_state_host(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, double *z, uint32_t *iters, double *d, uint32_t *m,
+                  double *der, const char *road, const char *d_name, const DeStateRows &rows) {
+    bool work;
+    int rc = de_state_check(cfg, y0, y1, from, true, z, iters, d, m, der, &work, road, d_name);
+    if (rc != FR_OK || !work) return rc;
+    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0), zb = npx * 2 * sizeof(double), ib = npx * sizeof(uint32_t);
+    LifeShared ls;
+    Ctx *ctx;
+    rc = primary(&ctx);
+    if (rc != FR_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = ctx->reserve(ctx->z, 3 * zb);
+    if (rc == FR_OK) rc = ctx->reserve(ctx->iters, 2 * ib);
+    if (rc != FR_OK) return rc;
+    char *const dd = static_cast<char *>(ctx->z.ptr), *const du = static_cast<char *>(ctx->iters.ptr);
+    const struct {
+        void *host, *dev;
+        size_t bytes;
+    } arrays[5] = {{z, dd, zb}, {iters, du, ib}, {d, dd + zb, zb}, {m, du + ib, ib}, {der, dd + 2 * zb, zb}};
+    if (from)
+        for (const auto &a : arrays) HIP_TRY(hipMemcpyAsync(a.dev, a.host, a.bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = rows.fn(rows.self, *ctx, static_cast<double *>(arrays[0].dev), static_cast<uint32_t *>(arrays[1].dev),
+                 static_cast<double *>(arrays[2].dev), static_cast<uint32_t *>(arrays[3].dev), static_cast<double *>(arrays[4].dev), ctx->stream);
+    if (rc != FR_OK) return rc;
+    for (const auto &a : arrays) HIP_TRY(hipMemcpyAsync(a.host, a.dev, a.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FR_OK;
 }
 
 }  // namespace fr

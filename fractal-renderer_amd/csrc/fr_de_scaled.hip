@@ -21,14 +21,26 @@
  * definition's fma(t.re, u.im, t.im * u.re).  The registers, the occupancy and the inner loop:
  * profiles/de_scaled_inner_loop_isa.txt.
  *
+ * RESUMABLE SCALED DE (include/fractal_hip.h, "RESUMABLE SCALED DE"; tests/de_scaled_state_model.c restates it;
+ * tests/test_gpu_de_scaled_state.py compares the two bit for bit): escape_pt_scaled_de_state_kernel<JULIA> is the plain loop's DE
+ * render with RESUMABLE SCALED PT's state rule — no rebase at the end of an orbit that the cap cut — and stores the whole state
+ * (z, iters, w, m, der); escape_extend_pt_scaled_de_kernel<JULIA> continues such a state to a higher cap in place, on orbits that
+ * fr_pt.hip's cache continued from their integer tails.  They are fr_scaled.hip's escape_pt_scaled_state_kernel and
+ * escape_extend_pt_scaled_kernel in their shape, with (ur, ui) carried as orbit_pt_scaled_de carries them; both run
+ * orbit_pt_scaled_de_state, the one copy of the state step with the derivative.  escape_pt_scaled_de_kernel and orbit_pt_scaled_de
+ * stay as they are.  The table form has no state (BLA-PT's reason: i + 2^k <= iterations).  Registers and occupancy: DESIGN.md 3.27.
+ *
  * The calls, at the end of the file: SCALED PT's domain check (fr_bla.h: scaled_check), DE's arrays, then the profiled launch
- * through the row-call bodies of fr_ctx.h (device_form, host_raw, profiled_rows).
+ * through the row-call bodies of fr_ctx.h (device_form, host_raw, profiled_rows); the state calls hand their launch to RESUMABLE
+ * DE's five-array road (fr_de.h: de_state_device, de_state_host).  scaled_de_domain and scaled_de_render_rows lend the DE render
+ * to SUPERSAMPLED SCALED DE (fr_ss_de.hip).
  */
 #include <cmath>
 #include <memory>
 
 #include "fr_bla.h"
 #include "fr_ctx.h"
+#include "fr_de.h"
 #include "fr_math.h"
 #include "fr_scaled.h"
 #include "fr_wide.h"
@@ -271,6 +283,194 @@ hipError_t launch(bool julia, bool bla, const fr_kparams &p, double *z, uint32_t
     return hipGetLastError();
 }
 
+/* ---- device: the resumable state of the plain scaled loop with the scaled derivative (include/fractal_hip.h, "RESUMABLE SCALED
+ * DE") ------------------------------------------------------------------------------------------------------------------------- */
+
+/* A pixel's state between steps: RESUMABLE SCALED PT's (z, w, m, onK) with u beside it.  orbit_pt_scaled_de_state is
+ * orbit_pt_scaled_state (fr_scaled.hip) with (ur, ui) carried as orbit_pt_scaled_de carries them: `steps` steps of the plain
+ * scaled loop from the state with the state rule's rebase condition — the scaled rebase test, or m == last of an orbit that is
+ * ENDED BY ESCAPE (x_end / k_end: that last index, or ~0 for an orbit cut by the cap, which m never equals) — and the state
+ * after the last step left in `s`; on escape that is (z, 0, 0) with nu kept.  Returns the steps completed before the escape
+ * (`steps`: none).  t.x_last / t.k_last only clamp the loads. */
+struct ScaledDeState {
+    double zr, zi, wr, wi, ur, ui;
+    uint32_t m;
+    bool on_k;
+};
+
+template <bool JULIA>
+__device__ __forceinline__ uint32_t orbit_pt_scaled_de_state(uint32_t steps, double wcr, double wci, const ScaledDev &t, uint32_t x_end,
+                                                             uint32_t k_end, double squared, ScaledDeState &s) {
+    const double S = t.S, Sinv = t.Sinv;
+    const bool on_k = JULIA && s.on_k;
+    const double2 *X = on_k ? t.k_orbit : t.x_orbit;
+    uint32_t last = on_k ? t.k_last : t.x_last, end = on_k ? k_end : x_end;
+    uint32_t m = s.m;
+    bool k_now = on_k;
+    const double bs0 = JULIA ? 0.0 : Sinv;
+    double wr = s.wr, wi = s.wi, zr = s.zr, zi = s.zi, ur = s.ur, ui = s.ui;
+    double2 Z = X[min(m, last)], N = X[min(m + 1u, last)]; /* m < last at the top of every step */
+    const double2 K1 = t.k_orbit[1];                       /* the entry after a rebase; K_0 = R_0 = 0 */
+    uint32_t i = 0;
+    for (; i < steps; i++) {
+        const double2 P = X[min(m + 2u, last)]; /* X_{m+2}: next step's X_{m+1} if it does not rebase */
+        const double tr = Z.x + zr, ti = Z.y + zi;
+        const double gr = zr + zr, gi = zi + zi; /* the derivative's t: from the z before the step */
+        const double nwr = __builtin_fma(tr, wr, __builtin_fma(-ti, wi, wcr));
+        const double nwi = __builtin_fma(tr, wi, __builtin_fma(ti, wr, wci));
+        const double nur = __builtin_fma(gr, ur, __builtin_fma(-gi, ui, bs0));
+        const double nui = __builtin_fma(gr, ui, gi * ur);
+        m++;
+        zr = __builtin_fma(nwr, Sinv, N.x);
+        zi = __builtin_fma(nwi, Sinv, N.y);
+        wr = nwr;
+        wi = nwi;
+        ur = nur; /* escape keeps nu; otherwise u = nu */
+        ui = nui;
+        const double dist = zr * zr + zi * zi;
+        if (dist > squared) break; /* this lane leaves EXEC; the wave goes on while any lane is left */
+        if (rebase_test(zr, zi, wr, wi, S, Sinv) || m == end) { /* a rebase never touches u */
+            wr = zr * S;
+            wi = zi * S;
+            m = 0;
+            if (JULIA) {
+                X = t.k_orbit;
+                last = t.k_last;
+                end = k_end;
+                k_now = true;
+            }
+            Z = make_double2(0.0, 0.0);
+            N = K1;
+        } else {
+            Z = N;
+            N = P;
+        }
+    }
+    const bool escaped = i < steps; /* (z, 0, 0) for an escaped lane, nu kept */
+    s.zr = zr;
+    s.zi = zi;
+    s.wr = escaped ? 0.0 : wr;
+    s.wi = escaped ? 0.0 : wi;
+    s.ur = ur;
+    s.ui = ui;
+    s.m = escaped ? 0u : m;
+    s.on_k = !escaped && k_now;
+    return i;
+}
+
+__device__ __forceinline__ void scaled_de_state_store(uint64_t k, double *z, uint32_t *iters, double *w, uint32_t *mm, double *der,
+                                                      const ScaledDeState &s, uint32_t it) {
+    z[2 * k] = s.zr;
+    z[2 * k + 1] = s.zi;
+    iters[k] = it;
+    w[2 * k] = s.wr;
+    w[2 * k + 1] = s.wi;
+    mm[k] = s.m | (s.on_k ? kOnK : 0u);
+    der[2 * k] = s.ur;
+    der[2 * k + 1] = s.ui;
+}
+
+/* escape_pt_scaled_state_kernel's shape (fr_scaled.hip) with the derivative: the whole state, 56 bytes per pixel, five stores.
+ * `ended`: bit 0 = X, bit 1 = K is ended by escape.  An algorithm without orbits writes zeros into all five arrays. */
+template <bool JULIA>
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_pt_scaled_de_state_kernel(const fr_kparams p, double *__restrict__ z,
+                                                                                    uint32_t *__restrict__ iters, double *__restrict__ w,
+                                                                                    uint32_t *__restrict__ mm, double *__restrict__ der,
+                                                                                    const ScaledDev t, const uint32_t ended) {
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
+    const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
+    stage_woff(p, tid, col0, row0, s_re, s_im);
+    __syncthreads();
+
+    const uint32_t wave = tid >> 6, lane = tid & 63;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
+    const uint32_t cx = col0 + lx, r = row0 + ly;
+    if (cx >= p.ncols || r >= p.nrows) return;
+    const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0; /* the host picks JULIA from the algorithm */
+
+    ScaledDeState s{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0u, false};
+    uint32_t it = 0;
+    if (escape_algo) {
+        const double woff_re = s_re[lx], woff_im = s_im[ly];
+        s.m = JULIA ? 0u : 1u;
+        s.wr = woff_re;
+        s.wi = woff_im;
+        const double2 X0 = t.x_orbit[min(s.m, t.x_last)];
+        s.zr = __builtin_fma(s.wr, t.Sinv, X0.x);
+        s.zi = __builtin_fma(s.wi, t.Sinv, X0.y);
+        s.ur = t.Sinv; /* u0 = (Sinv, 0) */
+        it = orbit_pt_scaled_de_state<JULIA>(p.iterations, JULIA ? 0.0 : woff_re, JULIA ? 0.0 : woff_im, t, (ended & 1u) ? t.x_last : ~0u,
+                                             (ended & 2u) ? t.k_last : ~0u, p.limit * p.limit, s);
+    }
+    scaled_de_state_store((uint64_t)r * p.ncols + cx, z, iters, w, mm, der, s, it);
+}
+
+/* escape_extend_pt_scaled_kernel's shape (fr_scaled.hip) with the derivative: the stored state continued from cap `from` to
+ * p.iterations in place, on the orbits of the new cap.  `iters` is read first and a workgroup with no pixel at `from` ends there,
+ * having written nothing; a finished pixel's z, w, m and der are neither loaded nor stored. */
+template <bool JULIA>
+__global__ __launch_bounds__(64 * kDeepWaves) void escape_extend_pt_scaled_de_kernel(const fr_kparams p, double *z, uint32_t *iters, double *w,
+                                                                                     uint32_t *mm, double *der, const uint32_t from,
+                                                                                     const ScaledDev t, const uint32_t ended) {
+    __shared__ double s_re[kDeepBlockW];
+    __shared__ double s_im[kDeepBlockH];
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t tiles_x = (uint32_t)(((uint64_t)p.ncols + kDeepBlockW - 1) / kDeepBlockW);
+    const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+    const uint32_t col0 = bx * kDeepBlockW, row0 = by * kDeepBlockH;
+    const uint32_t wave = tid >> 6, lane = tid & 63;
+    const uint32_t lx = (wave % kDeepWavesX) * kDeepTileW + lane % kDeepTileW;
+    const uint32_t ly = (wave / kDeepWavesX) * kDeepTileH + lane / kDeepTileW;
+    const uint32_t cx = col0 + lx, r = row0 + ly;
+    const bool valid = cx < p.ncols && r < p.nrows;
+    const uint64_t k = (uint64_t)r * p.ncols + cx;
+    uint32_t done = 0;
+    if (valid) done = iters[k];
+    const bool running = valid && done == from;
+    if (!__syncthreads_or(running ? 1 : 0)) return; /* whole workgroup (uniform) */
+
+    if (!JULIA) { /* wc = the pixel's woff, staged as the render stages it; Julia's wc is 0 */
+        stage_woff(p, tid, col0, row0, s_re, s_im);
+        __syncthreads();
+    }
+    if (!running) return;
+    const uint32_t word = mm[k];
+    ScaledDeState s;
+    s.zr = z[2 * k];
+    s.zi = z[2 * k + 1];
+    s.wr = w[2 * k];
+    s.wi = w[2 * k + 1];
+    s.ur = der[2 * k];
+    s.ui = der[2 * k + 1];
+    s.on_k = JULIA && (word & kOnK) != 0;
+    /* m < last of the orbit followed in every state this view produces; the clamp keeps foreign data inside the orbit */
+    s.m = min(word & ~kOnK, (s.on_k ? t.k_last : t.x_last) - 1u);
+    const uint32_t it = orbit_pt_scaled_de_state<JULIA>(p.iterations - from, JULIA ? 0.0 : s_re[lx], JULIA ? 0.0 : s_im[ly], t,
+                                                        (ended & 1u) ? t.x_last : ~0u, (ended & 2u) ? t.k_last : ~0u, p.limit * p.limit, s);
+    scaled_de_state_store(k, z, iters, w, mm, der, s, from + it); /* it == M - N on exhaustion: the new cap */
+}
+
+/* the state render, or — extend — the extension from `from` */
+template <bool JULIA>
+hipError_t launch_state(const fr_kparams &p, uint32_t from, bool extend, double *z, uint32_t *iters, double *w, uint32_t *m, double *der,
+                        const ScaledDev &t, uint32_t ended, hipStream_t stream) {
+    dim3 grid, block;
+    const hipError_t e = fr_deep_grid(p, grid, block);
+    if (e != hipSuccess) return e;
+    if (extend)
+        escape_extend_pt_scaled_de_kernel<JULIA><<<grid, block, 0, stream>>>(p, z, iters, w, m, der, from, t, ended);
+    else
+        escape_pt_scaled_de_state_kernel<JULIA><<<grid, block, 0, stream>>>(p, z, iters, w, m, der, t, ended);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 using namespace fr;
@@ -325,9 +525,116 @@ auto scaled_de_rows(const fr_config *cfg, const Centre &c, int bits, uint32_t y0
     };
 }
 
+/* ---- RESUMABLE SCALED DE: the plain loop's rows with their DE state, and that state continued to a higher cap ---------------- */
+
+/* The state render (from == nullptr) or its extension from *from between the profiling events, on the context's orbits of
+ * cfg's cap, which pt_orbit_view's cache continues from those of a lower cap of the same view and shares with every other scaled
+ * or wide call of it.  fr_de.h's DeStateRows: `run` with the call's arguments behind `self`. */
+struct ScaledDeStateCall {
+    const fr_config *cfg;
+    const Centre *c;
+    uint32_t y0, y1;
+    const uint32_t *from;
+    static int run(const void *self, Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_w, uint32_t *d_m, double *d_der, hipStream_t stream) {
+        const ScaledDeStateCall &a = *static_cast<const ScaledDeStateCall *>(self);
+        const fr_config *cfg = a.cfg;
+        return profiled_rows(cfg, default_opts(), a.y0, a.y1, 0, stream, [&](fr_kparams &p, const char *&kname) -> int {
+            kname = a.from ? "escape_extend_pt_scaled_de_kernel" : "escape_pt_scaled_de_state_kernel";
+            const bool julia = cfg->algo == FR_ALGO_JULIA, extend = a.from != nullptr;
+            if (p.ncols == 0 || p.nrows == 0) return FR_OK;
+            if (cfg->algo != FR_ALGO_MANDELBROT && !julia) { /* no escape-time algorithm: zeros in all five arrays (the extension never gets here) */
+                HIP_TRY(launch_state<false>(p, 0, false, d_z, d_iters, d_w, d_m, d_der, ScaledDev{}, 0, stream));
+                return FR_OK;
+            }
+            const ScaledConsts k = scaled_consts(cfg);
+            p.scale_re = k.sre;
+            p.scale_im = k.sim;
+            std::shared_ptr<PtOrbit> orbit; /* alive until the launch is enqueued */
+            PtOrbitView v;
+            const int rc = pt_orbit_view(ctx, cfg, *a.c, orbit, v);
+            if (rc != FR_OK) return rc;
+            ScaledDev t{};
+            t.x_orbit = v.x;
+            t.k_orbit = v.k;
+            t.x_last = v.x_last;
+            t.k_last = v.k_last;
+            t.S = k.S;
+            t.Sinv = k.Sinv;
+            const uint32_t n = extend ? *a.from : 0u;
+            HIP_TRY(julia ? launch_state<true>(p, n, extend, d_z, d_iters, d_w, d_m, d_der, t, v.ended, stream)
+                          : launch_state<false>(p, n, extend, d_z, d_iters, d_w, d_m, d_der, t, v.ended, stream));
+            return FR_OK;
+        });
+    }
+};
+
+/* the state calls are the plain loop's: SCALED PT's domain with bits = -1 and the centre required */
+int scaled_de_state_domain(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1) {
+    int bits = -1;
+    return scaled_check(cfg, c, bits, y0, y1);
+}
+
+int scaled_de_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z,
+                           void *d_iters, void *d_w, void *d_m, void *d_der, void *hip_stream) {
+    const Centre c{nullptr, centre, true};
+    const int rc = scaled_de_state_domain(cfg, c, y0, y1);
+    if (rc != FR_OK) return rc;
+    const ScaledDeStateCall call{cfg, &c, y0, y1, from};
+    return de_state_device(cfg, y0, y1, from, d_z, d_iters, d_w, d_m, d_der, hip_stream, "SCALED PT", "w",
+                           DeStateRows{ScaledDeStateCall::run, &call});
+}
+
+int scaled_de_state_host(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, const uint32_t *from, double *z,
+                         uint32_t *iters, double *w, uint32_t *m, double *der) {
+    const Centre c{nullptr, centre, true};
+    const int rc = scaled_de_state_domain(cfg, c, y0, y1);
+    if (rc != FR_OK) return rc;
+    const ScaledDeStateCall call{cfg, &c, y0, y1, from};
+    return de_state_host(cfg, y0, y1, from, z, iters, w, m, der, "SCALED PT", "w", DeStateRows{ScaledDeStateCall::run, &call});
+}
+
 }  // namespace
 
+/* for SUPERSAMPLED SCALED DE (fr_de.h): the domain check and the row launch of the calls below, called */
+namespace fr {
+
+int scaled_de_domain(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1) {
+    alignas(8) static const char arrays[8] = {}; /* stands for the three arrays: the caller's are its workspace's, checked there */
+    bool work;
+    return check_scaled_de(cfg, c, bits, y0, y1, arrays, arrays, arrays, &work);
+}
+
+int scaled_de_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, double *d_z,
+                          uint32_t *d_iters, double *d_der, hipStream_t stream) {
+    return scaled_de_rows(cfg, c, bits, y0, y1)(ctx, d_z, d_iters, d_der, nullptr, stream);
+}
+
+}  // namespace fr
+
 extern "C" {
+
+/* ---- the calls of RESUMABLE SCALED DE (the plain loop's: no bits) -------------------------------------------------------------- */
+
+int fr_escape_rows_de_pt_scaled_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, void *d_z,
+                                             void *d_iters, void *d_w, void *d_m, void *d_der, void *hip_stream) {
+    return scaled_de_state_device(cfg, centre, y0, y1, nullptr, d_z, d_iters, d_w, d_m, d_der, hip_stream);
+}
+
+int fr_escape_rows_de_pt_scaled_state(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z,
+                                      uint32_t *iters, double *w, uint32_t *m, double *der) {
+    return scaled_de_state_host(cfg, centre, y0, y1, nullptr, z, iters, w, m, der);
+}
+
+int fr_escape_extend_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
+                                         uint32_t from_iterations, void *d_z, void *d_iters, void *d_w, void *d_m, void *d_der,
+                                         void *hip_stream) {
+    return scaled_de_state_device(cfg, centre, y0, y1, &from_iterations, d_z, d_iters, d_w, d_m, d_der, hip_stream);
+}
+
+int fr_escape_extend_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, uint32_t from_iterations,
+                                  double *z, uint32_t *iters, double *w, uint32_t *m, double *der) {
+    return scaled_de_state_host(cfg, centre, y0, y1, &from_iterations, z, iters, w, m, der);
+}
 
 int fr_escape_rows_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, void *d_z,
                                        void *d_iters, void *d_der, void *hip_stream) {

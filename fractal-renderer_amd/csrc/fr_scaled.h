@@ -1,8 +1,8 @@
 /*
- * fr_scaled.h — internal: what the scaled kernels of fr_scaled.hip (SCALED PT) and fr_de_scaled.hip (DE ON SCALED PT) share, one
- * copy of each: the orbits, tables and scale as a kernel sees them (ScaledDev) with their fill from the context's caches, the
- * BIG threshold, the rebase test on one arithmetic path and the staging of woff.  Everything here has internal linkage: each of
- * the two translation units compiles its own copy into its own kernels.
+ * fr_scaled.h — internal: what the scaled kernels of fr_scaled.hip (SCALED PT) and fr_de_scaled.hip (DE ON SCALED PT, RESUMABLE
+ * SCALED DE) share, one copy of each: the orbits, tables and scale as a kernel sees them (ScaledDev) with their fill from the
+ * context's caches, the BIG threshold, the on-K bit of a stored state's m, the rebase test on one arithmetic path and the staging
+ * of woff.  Everything here has internal linkage: each of the two translation units compiles its own copy into its own kernels.
  */
 #ifndef FR_SCALED_H
 #define FR_SCALED_H
@@ -15,6 +15,7 @@
 namespace {
 
 constexpr double kBig = 0x1p500; /* max(|w.re|, |w.im|) >= kBig: w is "big" and the comparisons scale w down, not z up */
+constexpr uint32_t kOnK = 0x80000000u; /* bit 31 of a stored state's m: the pixel follows K (RESUMABLE SCALED PT, RESUMABLE SCALED DE) */
 
 /* the orbits, the tables (escape_bla_scaled_kernel only) and the scale as the kernels see them; Mandelbrot: the k fields
  * repeat the x fields */

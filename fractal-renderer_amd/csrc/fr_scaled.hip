@@ -28,7 +28,7 @@
  * stay as they are.  The table form has no state (BLA-PT's reason: i + 2^k <= iterations).
  *
  * What the kernels here share with those of DE ON SCALED PT (fr_de_scaled.hip) lives in fr_scaled.h, one copy: ScaledDev and its
- * fill from the context's caches, kBig, is_big, rebase_test and stage_woff.
+ * fill from the context's caches, kBig, kOnK, is_big, rebase_test and stage_woff.
  *
  * The calls, at the end of the file: each builds its Centre (scaled: the wide centre is required), runs check_scaled and hands
  * scaled_rows — the profiled launch of its rows — to the row-call body of its form in fr_ctx.h, as fr_bla.hip's do; the state
@@ -164,8 +164,6 @@ __device__ __forceinline__ uint32_t orbit_pt_scaled_state(uint32_t steps, double
     s.on_k = !escaped && k_now;
     return i;
 }
-
-constexpr uint32_t kOnK = 0x80000000u; /* bit 31 of the stored m: the pixel follows K */
 
 /* escape_pt_scaled_kernel<FR_OUT_ESCAPE>'s shape with the state rule, storing the whole state: z and w as re, im per pixel,
  * iters, m (bit 31: on K).  `ended`: bit 0 = X, bit 1 = K is ended by escape.  An algorithm without orbits writes zeros. */

@@ -7,7 +7,9 @@
  *   - the entry points: fr_colour_de_rows_ss_device / fr_colour_de_ss_rgb8 (a KEPT anti-aliased DE view recoloured),
  *     fr_ss_de_workspace_bytes, fr_render_rows_ss_de_device (bands of source rows rendered into a workspace the caller lends — the
  *     road's own DE row launch, fr_de.h — each shaded and filtered into its place, all on the caller's stream) and
- *     fr_render_rows_ss_de (the same into a host buffer, through context scratch).
+ *     fr_render_rows_ss_de (the same into a host buffer, through context scratch), and SUPERSAMPLED SCALED DE's
+ *     fr_render_rows_ss_de_pt_scaled(_device): the same band loop and the same fused kernel with DE ON SCALED PT's row launch
+ *     (fr_de.h: scaled_de_render_rows) and the scaled view's pixels.
  * The render kernels are not touched: a band is an ordinary row-range DE render of the large image.
  *
  * Kernel shape: colour_filter_kernel<S>'s (fr_ss.hip), which it differs from in phase 1 only.  Memory-bound:
@@ -27,6 +29,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "fr_bla.h" /* scaled_consts */
 #include "fr_ctx.h"
 #include "fr_de.h"
 #include "fr_math.h"
@@ -313,6 +316,7 @@ struct SsDeRoad {
     double ts, pixels;
     /* source rows [ya, yb) of cfg_s with their derivatives on the road */
     int rows(Ctx &ctx, uint32_t ya, uint32_t yb, double *d_z, uint32_t *d_iters, double *d_der, hipStream_t stream) const {
+        if (road == FR_PT_ROAD_SCALED) return scaled_de_render_rows(ctx, &pl.cfg_s, c, bits, ya, yb, d_z, d_iters, d_der, stream);
         if (road == FR_PT_ROAD_BLA) return bla_de_render_rows(ctx, &pl.cfg_s, c, bits, ya, yb, d_z, d_iters, d_der, stream);
         return de_render_rows(ctx, &pl.cfg_s, precision, c, ya, yb, d_z, d_iters, d_der, stream);
     }
@@ -348,6 +352,27 @@ int ss_de_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo,
         return fail(FR_ERR_INVALID_ARGUMENT, "bits must be 0 with FR_PT_ROAD_PLAIN: the plain loop has no table");
     /* F64 and plain PT; every other precision meets DE's scope message here */
     return de_domain(cs, precision, r.c, precision == FR_PRECISION_PT && centre != nullptr, Y0, Y1);
+}
+
+/* SUPERSAMPLED SCALED DE: everything fr_render_rows_ss_de_pt_scaled(_device) check before any device work — the sizes, the
+ * thickness, then DE ON SCALED PT's domain on cfg_s, by the code its plain calls run.  The road's arm of SsDeRoad: rows() is
+ * fr_escape_rows_de_pt_scaled's launch and `pixels` the last factor of D on the scaled view of cfg_s. */
+int ss_de_scaled_check(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t s, uint32_t y0, uint32_t y1,
+                       int channels, SsDeRoad &r) {
+    int rc = ss_plan(cfg, s, y0, y1, r.pl, kDeSampleBytes);
+    if (rc == FR_OK) rc = check_channels(channels);
+    if (rc == FR_OK) rc = ss_de_thickness(thickness, s, r.ts);
+    if (rc != FR_OK) return rc;
+    const uint32_t Y0 = s * y0, Y1 = (uint32_t)(Y0 + r.pl.src_rows);
+    r.precision = FR_PRECISION_PT;
+    r.road = FR_PT_ROAD_SCALED;
+    r.bits = bits;
+    r.c = Centre{nullptr, centre, true};
+    rc = scaled_de_domain(&r.pl.cfg_s, r.c, r.bits, Y0, Y1);
+    if (rc != FR_OK) return rc;
+    const ScaledConsts k = scaled_consts(cfg); /* cfg_s shares cfg's scale */
+    r.pixels = (double)(s * cfg->height) * std::fmin(std::fabs(k.sre), std::fabs(k.sim));
+    return FR_OK;
 }
 
 /* The band loop: render_ss_bands' (fr_ss.hip) with the DE arrays in the workspace and the fused kernel behind each band.  A band
@@ -468,6 +493,39 @@ int fr_render_rows_ss_de_device(const fr_config *cfg, int precision, const fr_im
     }
     return rgb_rows_device(cfg, y0, y1, channels, d_out, out_len, hip_stream, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
         return render_ss_de_bands(ctx, r, supersample, y0, (unsigned)channels, ko.rgb, d_work, work_len, stream);
+    });
+}
+
+/* ---- SUPERSAMPLED SCALED DE: the two calls above on the scaled road, which fr_render_rows_ss_de keeps refusing ---------------- */
+
+int fr_render_rows_ss_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness,
+                                          uint32_t supersample, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len,
+                                          void *d_work, size_t work_len, void *hip_stream) {
+    SsDeRoad r;
+    const int rc = ss_de_scaled_check(cfg, centre, bits, thickness, supersample, y0, y1, channels, r);
+    if (rc != FR_OK) return rc;
+    if ((size_t)cfg->width * (size_t)(y1 - y0) != 0) { /* the workspace, then rgb_rows_device's buffer rules */
+        if (work_len < r.pl.min_bytes) return fail(FR_ERR_BUFFER_TOO_SMALL, "work_len < min_bytes of fr_ss_de_workspace_bytes");
+        if (!d_work) return fail(FR_ERR_INVALID_ARGUMENT, "d_work is NULL");
+        if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_work must be 8-byte aligned (z and der lie in it)");
+    }
+    return rgb_rows_device(cfg, y0, y1, channels, d_out, out_len, hip_stream, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
+        return render_ss_de_bands(ctx, r, supersample, y0, (unsigned)channels, ko.rgb, d_work, work_len, stream);
+    });
+}
+
+int fr_render_rows_ss_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t supersample,
+                                   uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len) {
+    SsDeRoad r;
+    const int rc = ss_de_scaled_check(cfg, centre, bits, thickness, supersample, y0, y1, channels, r);
+    if (rc != FR_OK) return rc;
+    const size_t work_len = std::max(r.pl.min_bytes, std::min(r.pl.best_bytes, kSsHostWorkCap));
+    return rgb_rows_host(cfg, y0, y1, channels, out, out_len, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
+        int rc = ctx.reserve(ctx.ss_work, work_len);
+        if (rc != FR_OK) return rc;
+        rc = render_ss_de_bands(ctx, r, supersample, y0, (unsigned)channels, ko.rgb, ctx.ss_work.ptr, work_len, stream);
+        if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
+        return rc;
     });
 }
 

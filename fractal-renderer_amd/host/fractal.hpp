@@ -435,6 +435,34 @@ inline std::vector<RGB> get_image_de(const Config &config, Scaled scaled, const 
                             image.size() * sizeof(RGB)));
     return image;
 }
+// ... anti-aliased (include/fractal_hip.h, "SUPERSAMPLED SCALED DE"): supersample x supersample samples per pixel, each shaded on
+// the scaled view with thickness * supersample in sample pixels, box-filtered on the device; supersample = 1 is the call above.
+inline std::vector<RGB> get_image_de(const Config &config, Scaled scaled, const fr_wide_centre &centre, double thickness,
+                                     uint32_t supersample) {
+    std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
+    check(fr_render_rows_ss_de_pt_scaled(&config, &centre, scaled.bits, thickness, supersample, 0, config.height, 3,
+                                         reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB)));
+    return image;
+}
+// the same into device memory through a workspace the caller lends (fr_ss_de_workspace_bytes), asynchronous on hip_stream
+inline void get_image_de_device(const Config &config, Scaled scaled, const fr_wide_centre &centre, double thickness, uint32_t supersample,
+                                void *d_out, void *d_work, size_t work_len, int channels = 4, void *hip_stream = nullptr) {
+    check(fr_render_rows_ss_de_pt_scaled_device(&config, &centre, scaled.bits, thickness, supersample, 0, config.height, channels, d_out,
+                                                static_cast<size_t>(channels) * config.width * config.height, d_work, work_len, hip_stream));
+}
+// A DE view past 2^440 kept on the device is (z, iters, w, m, der), 56 bytes per pixel ("RESUMABLE SCALED DE"): the state render and
+// the extension that raises its cap in place, scaled derivative included.  The plain loop's (scaled.bits must be -1: the table
+// form has no state).  Recolour with colour_de_rows_device / colour_de_rows_ss_device on the view fr_de_scaled_view writes.
+inline void de_state_rows_device(const Config &config, const fr_wide_centre &centre, Scaled scaled, void *d_z, void *d_iters, void *d_w,
+                                 void *d_m, void *d_der, void *hip_stream = nullptr) {
+    if (scaled.bits != -1) throw std::invalid_argument("SCALED PT: only the plain loop (bits = -1) has a resumable state");
+    check(fr_escape_rows_de_pt_scaled_state_device(&config, &centre, 0, config.height, d_z, d_iters, d_w, d_m, d_der, hip_stream));
+}
+inline void extend_de_rows_device(const Config &config, const fr_wide_centre &centre, Scaled scaled, uint32_t from_iterations, void *d_z,
+                                  void *d_iters, void *d_w, void *d_m, void *d_der, void *hip_stream = nullptr) {
+    if (scaled.bits != -1) throw std::invalid_argument("SCALED PT: only the plain loop (bits = -1) has a resumable state");
+    check(fr_escape_extend_de_pt_scaled_device(&config, &centre, 0, config.height, from_iterations, d_z, d_iters, d_w, d_m, d_der, hip_stream));
+}
 // a kept view's recolour at another thickness, device arrays, asynchronous on hip_stream: no orbit is run
 inline void colour_de_rows_device(const Config &config, const void *d_z, const void *d_iters, const void *d_der, double thickness,
                                   void *d_out, int channels = 4, void *hip_stream = nullptr) {

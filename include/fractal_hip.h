@@ -399,7 +399,8 @@ typedef struct fr_config {
  * Domain: DE's, unchanged (limit <= 2^20; PT's domain with a dd centre, WIDE PT's |scale| <= 2^440 with a wide one); M >= N.
  * The overflow bound of DE is about the step that is returned and does not depend on where a run was
  * interrupted: a continued derivative takes the same values, overflow included, as the uninterrupted one.
- * DE on SCALED PT stays out of scope; DE ON BLA-PT (below) has no state: neither is resumable with a derivative. */
+ * DE on SCALED PT stays out of scope; DE ON BLA-PT (below) has no state: neither is resumable with a derivative.  That is the
+ * scope of THESE calls; RESUMABLE SCALED DE below has calls of its own for the plain scaled loop. */
 /*
  * DE ON BLA-PT (fr_escape_rows_de_pt_bla(_device) below): the derivative carried through the table's skips.  It is BLA-PT's
  * definition above word for word, with a dd centre (pos, pos_lo) or a wide centre (WIDE PT's domain) — the orbits, the table with
@@ -476,7 +477,42 @@ typedef struct fr_config {
  * 4-byte aligned; y0 == y1 is a no-op that needs no device and no array.
  * Out of scope: a resumable state or an extend form for scaled DE; supersampling (fr_render_rows_ss_de keeps refusing
  * FR_PT_ROAD_SCALED; a kept scaled view is filtered by fr_colour_de_rows_ss_device on cfg_v); the command line; the Rust shim;
- * multi-device and block-cyclic renders. */
+ * multi-device and block-cyclic renders.  The first two are out of scope of THESE calls; RESUMABLE SCALED DE and SUPERSAMPLED
+ * SCALED DE below have calls of their own. */
+/*
+ * RESUMABLE SCALED DE (fr_escape_rows_de_pt_scaled_state, fr_escape_extend_de_pt_scaled below): the state that lets a DE view past
+ * a scale of 2^440 have its cap raised in place, scaled derivative included.  The state of a pixel after N steps is
+ * (z, w, m, onK, u).  It is RESUMABLE SCALED PT's state run, word for word — the plain scaled loop, bits = -1; the rebase rule
+ * "the scaled rebase test, or m == last of an orbit ENDED BY ESCAPE"; both forms of the test, BIG and not BIG — with DE ON SCALED
+ * PT's plain-step derivative beside it: u0 = (Sinv, 0), bs0 = Sinv for Mandelbrot and 0 for Julia, and in every step, from the
+ * z the loop holds before the step,
+ *     t  = (z.re + z.re, z.im + z.im)
+ *     nu = (fma(t.re, u.re, fma(-t.im, u.im, bs0)), fma(t.re, u.im, t.im * u.re)).
+ * A rebase never touches u.  Every operation is ONE correctly rounded f64 operation; fma is fused and nothing else is.
+ *   Stored form, 56 bytes per pixel: the arrays (z, iters, w, m, der) in RESUMABLE SCALED PT's layout (w holds the SCALED offset,
+ *   bit 31 of m: a Julia pixel on K) with der = u, 2 doubles, beside them.  Escape stores (next, i, w = (0, 0), m = 0, nu);
+ *   exhaustion stores (z, N, w, m | onK << 31, u).  N = 0 stores RESUMABLE SCALED PT's initial state with der = (Sinv, 0).  An
+ *   algorithm without orbits writes zeros into all five arrays.
+ *   CLAIM 1: for every N, z, iters and der equal fr_escape_rows_de_pt_scaled's with bits = -1, and w and m equal
+ *   fr_escape_rows_pt_scaled_state's, bit for bit.
+ *   Why: u reads only z.  RESUMABLE SCALED PT's claim 1 says the z sequence of the state run is SCALED PT's; the one
+ *   cap-dependent rebase, which the state rule leaves out, changes (w, m) and never z, hence never u.  (z, iters, w, m) are
+ *   computed by RESUMABLE SCALED PT's operations, which u does not enter.
+ *   CLAIM 2: continuing the state from N for M - N steps on the orbits of cap M gives the state run at cap M, bit for bit in all
+ *   five arrays (a NaN in der is any NaN, as in DE).
+ *   Why: RESUMABLE SCALED PT's claim 2 for (z, iters, w, m), plus "u is a function of the z sequence": u after step i is
+ *   determined by u0 and z_0 .. z_i, which a state run to N and a state run to M share up to N.
+ *   CLAIM 3: in WIDE PT's domain with limit <= 2^20, where no intermediate of either run is subnormal or overflows, z, iters
+ *   and m equal fr_escape_rows_de_pt_state's with the wide centre, w = dz 2^e, and der 2^e is its der, all exactly.
+ *   Why: RESUMABLE SCALED PT's claim 3 for (z, iters, w, m) and DE ON SCALED PT's claim 2 for u: multiplication by a power of two
+ *   commutes with every rounding, and u reads only z, which is the same in both runs.
+ *   The range argument of DE ON SCALED PT (its CLAIM 3) is about the returned step's u and does not depend on
+ *   where a run was interrupted: a continued u takes the same values, overflow and underflow included, as the uninterrupted one.
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): SCALED PT's, with the centre REQUIRED (DE's
+ * limit <= 2^20 is already SCALED PT's); there is no bits argument, the calls are the plain loop's; for the extension M >= N
+ * (M == N is a legal no-op that needs no device, as y0 == y1 is); all five arrays non-NULL, z, w and der 8-byte aligned, iters
+ * and m 4-byte aligned (y0 == y1 needs none).  The table form (bits >= 0) has no state, for BLA-PT's reason: the condition
+ * i + 2^k <= iterations makes a run at cap N no prefix of the run at cap M. */
 /*
  * SUPERSAMPLED DE (fr_render_rows_ss_de, fr_colour_de_rows_ss_device below): distance estimation and supersampling at once —
  * filaments thinner than a pixel stay visible AND the borders are anti-aliased.  DEFINITION, for supersample = s,
@@ -502,7 +538,31 @@ typedef struct fr_config {
  * (Ts is then inside fr_colour_de_rows_device's own domain: the definition is literally a composition of existing calls);
  * channels 3 or 4.  Refused by name: FR_PRECISION_F32 and FR_PRECISION_DD (DE's scope message), FR_PT_ROAD_SCALED (DE on SCALED
  * PT stays out of scope).  One device.  The command line stays as it is: --distance-shade beside --supersample above 1 or
- * --bla is refused there.
+ * --bla is refused there.  FR_PT_ROAD_SCALED is out of scope of THESE calls; SUPERSAMPLED SCALED DE below has calls of its own.
+ */
+/*
+ * SUPERSAMPLED SCALED DE (fr_render_rows_ss_de_pt_scaled(_device) below): SUPERSAMPLED DE past a scale of 2^440, on DE ON SCALED
+ * PT's road, with its own calls; fr_render_rows_ss_de keeps refusing FR_PT_ROAD_SCALED.  DEFINITION, for supersample = s,
+ * 1 <= s <= FR_SS_MAX, and a thickness T in OUTPUT pixels:
+ *   cfg_s  = cfg with width * s and height * s, every other field unchanged;
+ *   (z, iters, u) = fr_escape_rows_de_pt_scaled(cfg_s, centre, bits, ...), bit for bit; bits is -1, 0 or 24 .. 53; its Dw is
+ *            taken over the whole image of cfg_s, as the supersampled deep roads define;
+ *   cfg_sv = fr_de_scaled_view(cfg_s): cfg_s with scale = (sre, sim);
+ *   Ts     = T * (double)s, one f64 product;
+ *   H      = the bytes of fr_colour_de_rows_device(cfg_sv, z, iters, u, n, Ts, 3): the distance is in SAMPLE pixels, its last
+ *            factor (double)(s * height) * min(|sre|, |sim|), one product;
+ *   out    = SUPERSAMPLED DE's integer box filter of H:
+ *            out(X, Y, c) = (sum over j < s, i < s of H(s*X + i, s*Y + j, c) + floor(s*s / 2)) / (s*s), truncating; with 4
+ *            channels alpha is 255.
+ * s = 1 is fr_escape_rows_de_pt_scaled followed by fr_colour_de_rows_device(cfg_v, ..., T, channels), byte for byte.  T = 0 gives
+ * the bytes of fr_render_rows_ss_pt(..., FR_PT_ROAD_SCALED, bits, s).  An algorithm without orbits gives black.  A KEPT
+ * anti-aliased scaled view — (z, iters, w, m, u) of cfg_s, written by fr_escape_rows_de_pt_scaled_state_device and kept current
+ * by fr_escape_extend_de_pt_scaled_device — recoloured by fr_colour_de_rows_ss_device on cfg_v gives the same bytes as this
+ * render with bits = -1 at the view's cap.
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message, before any device work): s in 1 .. FR_SS_MAX; s * width and s * height
+ * fit in 32 bits; DE ON SCALED PT's domain ON cfg_s, checked by the code the plain calls run (centre required; bits -1, 0 or
+ * 24 .. 53); T finite with 0 <= T * s <= 2^20; channels 3 or 4; the buffer and workspace rules of fr_render_rows_ss_de_device
+ * (fr_ss_de_workspace_bytes plans the workspace, 36 bytes per sample).  No colour or filter kernel is added or changed.
  */
 #define FR_BLA_DEFAULT_BITS 40
 #define FR_PT_MAX_ITERATIONS (1u << 24)
@@ -1239,6 +1299,31 @@ int fr_escape_extend_de_pt_device(const fr_config *cfg, const fr_imaginary *pos_
                                   void *hip_stream);
 int fr_escape_extend_de_pt(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
                            uint32_t from_iterations, double *z, uint32_t *iters, double *dz, uint32_t *m, double *der);
+/* RESUMABLE SCALED DE (defined at fr_precision above): a GUI keeps a DE view past 2^440 as (z, iters, w, m, der) in DEVICE memory
+ * — 56 bytes per pixel — and answers an iterations change with fr_escape_extend_de_pt_scaled_device; the distance and the shading
+ * are DE's calls over (z, iters, der) on the scaled view (fr_de_scaled_view).  The calls are the plain scaled loop's and take no
+ * bits; `centre` is required.  Each is the counterpart of the fr_*_de_pt_state / fr_escape_extend_de_pt call it is named after,
+ * with d_w / w where that one has d_dz / dz: the same buffers, alignment and asynchrony on `hip_stream`, nothing allocated by the
+ * _device forms, and fr_escape_extend_pt_scaled's contract for the extension — the precondition (the arrays hold the state
+ * render of cfg_N) cannot be checked; arrays from another view or cap are continued as if they were this one's, an index m beyond
+ * the orbit is brought inside it, nothing more; the call is not idempotent; a pixel with iters[k] != N has only that word read
+ * and nothing of it loaded or written, values above N included; M == N and y0 == y1 are no-ops that need no device; M < N is
+ * refused; an algorithm without orbits: the render writes zeros into all five arrays, the extension does nothing.  Every refusal
+ * happens before any device work.  z, iters and der are fr_escape_rows_de_pt_scaled's with bits = -1, w and m
+ * fr_escape_rows_pt_scaled_state's, bit for bit.
+ * The orbit is the shared slot's: a scaled DE state call serves and is served by every other scaled or wide call of the view, and
+ * an extension computes only the missing orbit entries (fr_debug_pt_orbit_cache shows it).  The host forms go through the
+ * context's scratch: upload (extension), launch, download, synchronise.  With profiling on, fr_last_kernel_name reports
+ * escape_pt_scaled_de_state_kernel / escape_extend_pt_scaled_de_kernel. */
+int fr_escape_rows_de_pt_scaled_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, void *d_z,
+                                             void *d_iters, void *d_w, void *d_m, void *d_der, void *hip_stream);
+int fr_escape_rows_de_pt_scaled_state(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z,
+                                      uint32_t *iters, double *w, uint32_t *m, double *der);
+int fr_escape_extend_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1,
+                                         uint32_t from_iterations, void *d_z, void *d_iters, void *d_w, void *d_m, void *d_der,
+                                         void *hip_stream);
+int fr_escape_extend_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, uint32_t from_iterations,
+                                  double *z, uint32_t *iters, double *w, uint32_t *m, double *der);
 /* D of n stored results, one double per pixel (8-byte aligned).  Reads only height, scale and iterations from cfg.  n <= 2^40;
  * n == 0 needs no device. */
 int fr_distance_rows_device(const fr_config *cfg, const void *d_z, const void *d_iters, const void *d_der, size_t n, void *d_out,
@@ -1298,6 +1383,17 @@ int fr_render_rows_ss_de_device(const fr_config *cfg, int precision, const fr_im
  * the context's scratch; the small image leaves the device in one copy. */
 int fr_render_rows_ss_de(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
                          double thickness, uint32_t supersample, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len);
+/* SUPERSAMPLED SCALED DE (defined at fr_precision above): fr_render_rows_ss_de(_device) on DE ON SCALED PT's road.  `centre` is
+ * required; bits: -1 = the plain scaled loop, 0 = FR_BLA_DEFAULT_BITS, else 24 .. 53.  Buffers, workspace (fr_ss_de_workspace_bytes,
+ * 36 bytes per sample, its layout), alignment, asynchrony and error codes are fr_render_rows_ss_de_device's; the orbit — and
+ * with a table the table — is computed and uploaded by the first band and served to the others.  With profiling on,
+ * fr_last_kernel_name reports escape_pt_scaled_de_kernel / escape_bla_scaled_de_kernel and fr_last_kernel_ms the span from the first
+ * band's kernel to the last filter.  The host form uses the context's scratch (workspace at most 256 MiB). */
+int fr_render_rows_ss_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness,
+                                          uint32_t supersample, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len,
+                                          void *d_work, size_t work_len, void *hip_stream);
+int fr_render_rows_ss_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t supersample,
+                                   uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 
