@@ -43,6 +43,7 @@ __all__ = [
     "ss_de_workspace_bytes", "colour_image_de_ss", "colour_de_rows_ss_device",
     "de_scaled_view",
     "escape_rows_de_pt_scaled_state", "extend_rows_de_pt_scaled", "get_image_de_scaled_ss",
+    "get_image_ss_adaptive", "ss_adaptive_workspace_bytes",
 ]
 
 
@@ -1098,6 +1099,59 @@ def ss_de_workspace_bytes(config, supersample, y0=0, y1=None):
     mn, best = C.c_size_t(0), C.c_size_t(0)
     _native.check(_native.load().fr_ss_de_workspace_bytes(C.byref(config), int(supersample), y0, y1, C.byref(mn), C.byref(best)))
     return mn.value, best.value
+
+
+def _adaptive_road(precision, pos_lo, centre, bla, scaled):
+    """The road arguments of the adaptive calls — (pos_lo pointer, centre pointer, road, bits) and what keeps their memory
+    alive — from the keywords, resolved through _deep_call: its families are the roads"""
+    if int(precision) not in (Precision.F64, Precision.PT):
+        raise ValueError("adaptive supersampling takes precision=Precision.F64 or Precision.PT")
+    family, pre, keep = _deep_call(precision, pos_lo, centre, bla, scaled=scaled)
+    if int(precision) != Precision.PT and family != "plain":
+        raise ValueError("pos_lo= needs precision=Precision.PT")
+    if family == "scaled":
+        return (None, pre[0], _native.FR_PT_ROAD_SCALED, pre[1]), keep
+    if family == "bla":
+        return (pre[0], pre[1], _native.FR_PT_ROAD_BLA, pre[2]), keep
+    if family == "wide":
+        return (None, pre[0], _native.FR_PT_ROAD_PLAIN, 0), keep
+    if family == "lo":
+        return (pre[0], None, _native.FR_PT_ROAD_PLAIN, 0), keep
+    return (None, None, _native.FR_PT_ROAD_PLAIN, 0), keep
+
+
+def ss_adaptive_workspace_bytes(config, supersample, y0=0, y1=None):
+    """fr_ss_adaptive_workspace_bytes: the bytes of device workspace fr_render_rows_ss_adaptive_device wants for rows [y0, y1) —
+    the probe colours of the rows and their two neighbours, the edge list and two counters; one size, no banding."""
+    y1 = config.height if y1 is None else y1
+    n = C.c_size_t(0)
+    _native.check(_native.load().fr_ss_adaptive_workspace_bytes(C.byref(config), int(supersample), y0, y1, C.byref(n)))
+    return n.value
+
+
+def get_image_ss_adaptive(config, supersample, threshold=8, precision=Precision.F64, pos_lo=None, centre=None, bla=None, scaled=False,
+                          y0=0, y1=None, channels=3, out=None):
+    """Adaptive supersampling (fr_render_rows_ss_adaptive; include/fractal_hip.h, "ADAPTIVE SUPERSAMPLING"): rows [y0, y1) with
+    supersample x supersample samples only at EDGE pixels — those whose probe sample differs from a neighbour's by more than
+    `threshold` (0 .. 255; -1: every pixel, the bytes of the supersampled render; 255: none, the probe image) in some channel —
+    and the probe sample everywhere else.  Returns (image uint8 [y1-y0, width, channels], refined: the number of edge pixels).
+    precision is Precision.F64 or Precision.PT; pos_lo, centre, bla and scaled select the deep road as in get_image_rows.  A
+    non-edge pixel's interior samples are never looked at: get_image_de is the tool for features thinner than a pixel."""
+    s = int(supersample)
+    if not 1 <= s <= SS_MAX:
+        raise ValueError("supersample is 1 .. %d" % SS_MAX)
+    if not -1 <= int(threshold) <= 255:
+        raise ValueError("threshold is -1 .. 255")
+    if int(channels) not in (3, 4):
+        raise ValueError("channels is 3 or 4")
+    (lo, ptr, road, bits), _keep = _adaptive_road(precision, pos_lo, centre, bla, scaled)
+    y0, y1 = _rows(config, y0, y1)
+    if out is None:
+        out = np.empty((max(y1 - y0, 0), config.width, int(channels)), dtype=np.uint8)
+    refined = C.c_uint64(0)
+    _native.check(_native.load().fr_render_rows_ss_adaptive(C.byref(config), int(precision), lo, ptr, road, bits, s, int(threshold), y0, y1,
+                                                            int(channels), out.ctypes.data, out.nbytes, C.byref(refined)))
+    return out, refined.value
 
 
 def colour_image_de_ss(config, z, iters, der, supersample, thickness, channels=3):

@@ -15,6 +15,11 @@
 // --scaled beside --perturbation (SCALED PT: the pixel loop that carries its offsets scaled by the view's exponent, so scales
 // past 2^440 render, up to just under 2^952; it combines with --bla — include/fractal_hip.h, "SCALED PT");
 // --supersample N (N x N samples per pixel, box-filtered on the device; with --perturbation, --bla and --scaled too);
+// --adaptive or --adaptive=T beside --supersample (adaptive supersampling: all N x N samples only at edge pixels, those whose
+// probe sample differs from a neighbour's by more than T, 0 .. 255, default 8, in some channel; -1 refines every pixel — written
+// with '=': a bare number after --adaptive is <width>; include/fractal_hip.h, "ADAPTIVE SUPERSAMPLING"; with --perturbation, --bla
+// and --scaled too, not with --distance-shade, --auto-exposure, --f32, --devices or -a fern; the refined share is printed unless
+// --quiet);
 // --auto-exposure [P] (the exposure is chosen from the view's own escape indices: the one at which an escaped pixel at
 // percentile P of them, default 0.99, gets the full primary colour — include/fractal_hip.h, "statistics of a kept view"; a
 // following number within [0, 1] written with a '.' or an exponent is P (0.5, 1.0 — a bare 0 or 1 is a <width>), or write
@@ -85,6 +90,8 @@ int main(int argc, char **argv) {
     bool disable_inside = false, unsmooth = false, f32 = false, quiet = false, perturbation = false, bla = false, scaled = false;
     bool exposure_given = false, auto_exposure_on = false;
     std::optional<std::string> distance_shade;
+    bool adaptive = false;
+    int adaptive_t = 8;
     double auto_p = 0.99;
     int bla_bits = 0;
     std::vector<std::string> positionals;
@@ -142,6 +149,14 @@ int main(int argc, char **argv) {
             bla_bits = static_cast<int>(to_u32(a.substr(6), "--bla"));
             if (bla_bits < 24 || bla_bits > 53) die("--bla takes 24 .. 53 bits");
         }
+        else if (a == "--adaptive") adaptive = true; // adaptive supersampling at the default threshold
+        else if (a.rfind("--adaptive=", 0) == 0) { // ... or at -1 .. 255 (written with '=': a bare number after --adaptive is <width>)
+            adaptive = true;
+            char *end = nullptr;
+            const long v = std::strtol(a.c_str() + 11, &end, 10);
+            if (end == a.c_str() + 11 || *end != '\0' || v < -1 || v > 255) die("--adaptive takes a threshold of -1 .. 255");
+            adaptive_t = static_cast<int>(v);
+        }
         else if (a == "--supersample") supersample_s = value(i, "--supersample"); // N x N samples per pixel, box-filtered on the device
         else if (a == "--devices") devices = value(i, "--devices");
         else if (a == "--threads") threads_s = value(i, "--threads");
@@ -173,6 +188,14 @@ int main(int argc, char **argv) {
     if (auto_exposure_on && algo == Algo::BarnsleyFern) die("--auto-exposure does not apply to -a fern: the fern has no escape indices");
     if (auto_exposure_on && devices && devices->find(',') != std::string::npos)
         die("--auto-exposure runs on one device: the statistics cover one array, not the pieces of --devices");
+    if (adaptive) {
+        if (!supersample_s) die("--adaptive needs --supersample: it chooses where the N x N samples are taken");
+        if (distance_shade) die("--adaptive does not combine with --distance-shade");
+        if (auto_exposure_on) die("--adaptive does not combine with --auto-exposure");
+        if (f32) die("--adaptive does not combine with --f32: adaptive supersampling is defined on the f64 road and on --perturbation");
+        if (devices) die("--adaptive does not combine with --devices: adaptive supersampling runs on one device");
+        if (algo == Algo::BarnsleyFern) die("--adaptive does not apply to -a fern");
+    }
     if (distance_shade) {
         const uint32_t ss = supersample_s ? to_u32(*supersample_s, "--supersample") : 1;
         if (bla) die("--distance-shade does not combine with --bla: a skipped block has no per-step derivative");
@@ -227,6 +250,7 @@ int main(int argc, char **argv) {
             use_devices(list);
         }
         std::vector<RGB> image;
+        uint64_t refined = 0; // --adaptive: the number of edge pixels
         const auto t0 = std::chrono::steady_clock::now();
         if (algo == Algo::BarnsleyFern) {
             uint32_t threads = threads_s ? to_u32(*threads_s, "--threads") : std::thread::hardware_concurrency();
@@ -268,7 +292,12 @@ int main(int argc, char **argv) {
         } else if (perturbation) {
             // the centre keeps every digit of -x / -y; cfg.pos (their f64 roundings) is not read
             const WideCentre centre = WideCentre::from_decimal(pos_x_s, pos_y, WideCentre::words_for_scale(cfg.scale.re, cfg.scale.im));
-            if (supersample_s) { // anti-aliased: the same road, N x N samples per pixel
+            if (adaptive) { // anti-aliased where the image has edges
+                const uint32_t ss = to_u32(*supersample_s, "--supersample");
+                const Adaptive ad{adaptive_t, &refined};
+                if (scaled) image = get_image(cfg, centre.c(), Scaled{bla ? bla_bits : -1}, ss, ad);
+                else image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}, ss, ad) : get_image(cfg, centre.c(), ss, ad);
+            } else if (supersample_s) { // anti-aliased: the same road, N x N samples per pixel
                 const uint32_t ss = to_u32(*supersample_s, "--supersample");
                 if (scaled) image = get_image(cfg, centre.c(), Scaled{bla ? bla_bits : -1}, ss);
                 else image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}, ss) : get_image(cfg, centre.c(), ss);
@@ -276,7 +305,8 @@ int main(int argc, char **argv) {
             else image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}) : get_image(cfg, centre.c());
         } else {
             const int precision = f32 ? FR_PRECISION_F32 : FR_PRECISION_F64;
-            image = supersample_s ? get_image(cfg, precision, to_u32(*supersample_s, "--supersample")) : get_image(cfg, precision);
+            if (adaptive) image = get_image(cfg, precision, to_u32(*supersample_s, "--supersample"), Adaptive{adaptive_t, &refined});
+            else image = supersample_s ? get_image(cfg, precision, to_u32(*supersample_s, "--supersample")) : get_image(cfg, precision);
         }
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         const std::string path = filename + ".ppm";  // the reference appends ".avif" (src/lib.rs:192-195)
@@ -285,6 +315,11 @@ int main(int argc, char **argv) {
         std::fprintf(f, "P6\n%u %u\n255\n", cfg.width, cfg.height);
         std::fwrite(image.data(), 3, image.size(), f);
         std::fclose(f);
+        if (adaptive && !quiet) {
+            const uint64_t npx = static_cast<uint64_t>(cfg.width) * cfg.height;
+            std::printf("refined %llu of %llu pixels (%.1f%%) at threshold %d\n", static_cast<unsigned long long>(refined),
+                        static_cast<unsigned long long>(npx), npx ? 100.0 * static_cast<double>(refined) / static_cast<double>(npx) : 0.0, adaptive_t);
+        }
         if (!quiet) std::printf("rendered %ux%u in %.2f ms -> %s\n", cfg.width, cfg.height, ms, path.c_str());
     } catch (const Error &e) {
         std::fprintf(stderr, "fractal_hip error %d: %s\n", e.code(), e.what());

@@ -31,6 +31,10 @@
  *     wave no longer share m, so PT's one-step-ahead load of X_{m+2} has nothing to aim at and is not carried over: the
  *     latency is covered by the other waves of the CU (the kernel runs at 8 waves per SIMD).
  *
+ * ADAPTIVE SUPERSAMPLING (include/fractal_hip.h; fr_ss_adaptive.hip): ss_refine_bla_kernel<JULIA>, persistent waves that run
+ * orbit_bla on the s x s samples of the listed edge pixels (fr_ss_list.h: the claim loop); bla_render_map, the RGB launch over
+ * the probe's strided map, and bla_ss_refine, the refine launch.
+ *
  * The calls, at the end of the file: each builds its Centre, runs check_bla and hands bla_rows — the profiled launch of its
  * rows — to the row-call body of its form in fr_ctx.h (rgb_rows_device, rgb_rows_host, raw_rows_device, raw_rows_host,
  * count_rows).  The workgroup's geometry and the launch's grid are the deep kernels' (fr_kernels.h: kDeep*, fr_deep_grid).
@@ -43,6 +47,7 @@
 #include "fr_bla.h"
 #include "fr_ctx.h"
 #include "fr_math.h"
+#include "fr_ss_list.h"
 #include "fr_wide.h"
 
 namespace {
@@ -251,6 +256,31 @@ hipError_t launch(const fr_kparams &p, int mode, const fr_kout &out, const BlaDe
     return hipGetLastError();
 }
 
+/* ---- device: ADAPTIVE SUPERSAMPLING's refine pass (include/fractal_hip.h; fr_ss_list.h: the claim loop) ---------------- */
+
+/* ss_refine_pt_kernel (fr_pt.hip) with orbit_bla: `off` by escape_bla_kernel's formula on cfg_s (`p`), the table `t` built with
+ * D over the whole image of cfg_s */
+template <bool JULIA>
+__global__ __launch_bounds__(kSsRefineThreads) void ss_refine_bla_kernel(const fr_kparams p, const fr_ss_refine a, const BlaDev t) {
+    __shared__ double s_tab[FR_LOG2_N * 3];
+    const double *gt = &g_log2_tab[0][0];
+    for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    __syncthreads();
+    const double width = (double)p.width, height = (double)p.height;
+    const double squared = p.limit * p.limit;
+    ss_refine_loop(a, [&](uint64_t x, uint64_t y) {
+        const double off_re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
+        const double off_im = (((double)y / height) - 0.5) / p.scale_im;
+        double zr, zi;
+        uint32_t passes;
+        const uint32_t iters = orbit_bla<JULIA>(p.iterations, off_re, off_im, t, squared, zr, zi, passes);
+        uint8_t rgb[3] = {0, 0, 0};
+        const ColourConsts cc = make_colour_consts(p);
+        colour_pixel<double>(cc, zr, zi, zr * zr, zi * zi, iters, s_tab, nullptr, rgb);
+        return (uint32_t)rgb[0] | ((uint32_t)rgb[1] << 8) | ((uint32_t)rgb[2] << 16);
+    });
+}
+
 /* ---- host: the table of one orbit (include/fractal_hip.h, "BLA-PT": table) ------------------------------------------ */
 
 /* levels >= 1 in the device layout; level 0 is a function of one orbit entry and is recomputed where it is asked for */
@@ -410,6 +440,25 @@ int bla_table_for(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, boo
 
 namespace {
 
+/* the view's orbits and tables from the context's caches as the kernels take them; the caller keeps `orbit` and `table` alive
+ * until its launch has been enqueued */
+int bla_dev_fill(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, std::shared_ptr<PtOrbit> &orbit, std::shared_ptr<BlaTable> &table,
+                 BlaDev &t) {
+    PtOrbitView v;
+    const int rc = bla_table_for(ctx, cfg, c, bits, false, orbit, v, table);
+    if (rc != FR_OK) return rc;
+    const BlaTableDev &d = table->view;
+    t = BlaDev{};
+    t.x_r2 = d.x_rad, t.k_r2 = d.k_rad;
+    t.x_coef = d.x_coef, t.k_coef = d.k_coef;
+    t.x_n0 = d.x_n0, t.k_n0 = d.k_n0;
+    t.x_orbit = v.x;
+    t.k_orbit = v.k;
+    t.x_last = v.x_last;
+    t.k_last = v.k_last;
+    return FR_OK;
+}
+
 int launch_bla(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_kparams &p, int mode, const fr_kout &out,
                hipStream_t stream) {
     if (p.ncols == 0 || p.nrows == 0) return FR_OK;
@@ -420,18 +469,9 @@ int launch_bla(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const 
     }
     std::shared_ptr<PtOrbit> orbit;
     std::shared_ptr<BlaTable> table;
-    PtOrbitView v;
-    const int rc = bla_table_for(ctx, cfg, c, bits, false, orbit, v, table);
+    BlaDev t;
+    const int rc = bla_dev_fill(ctx, cfg, c, bits, orbit, table, t);
     if (rc != FR_OK) return rc;
-    const BlaTableDev &d = table->view;
-    BlaDev t{};
-    t.x_r2 = d.x_rad, t.k_r2 = d.k_rad;
-    t.x_coef = d.x_coef, t.k_coef = d.k_coef;
-    t.x_n0 = d.x_n0, t.k_n0 = d.k_n0;
-    t.x_orbit = v.x;
-    t.k_orbit = v.k;
-    t.x_last = v.x_last;
-    t.k_last = v.k_last;
     HIP_TRY(julia ? launch<true>(p, mode, out, t, stream) : launch<false>(p, mode, out, t, stream));
     return FR_OK;
 }
@@ -467,6 +507,30 @@ int bla_check(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uin
 int bla_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, unsigned channels,
                     const fr_kout &out, hipStream_t stream) {
     return bla_rows(cfg, c, bits, y0, y1, channels, FR_OUT_RGB)(ctx, out, stream);
+}
+
+/* fr_ss_list.h: ADAPTIVE SUPERSAMPLING on BLA-PT — the probe (the road's RGB kernel over the strided map) and the refine pass */
+int bla_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_map &map, const fr_kout &out, hipStream_t stream) {
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    map.apply(p);
+    return launch_bla(ctx, cfg, c, bits, p, FR_OUT_RGB, out, stream);
+}
+
+int bla_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, uint32_t groups, hipStream_t stream) {
+    std::shared_ptr<PtOrbit> orbit;
+    std::shared_ptr<BlaTable> table;
+    BlaDev t;
+    const int rc = bla_dev_fill(ctx, cfg, c, bits, orbit, table, t);
+    if (rc != FR_OK) return rc;
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    if (cfg->algo == 2)
+        ss_refine_bla_kernel<true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, t);
+    else
+        ss_refine_bla_kernel<false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, t);
+    HIP_TRY(hipGetLastError());
+    return FR_OK;
 }
 
 }  // namespace fr

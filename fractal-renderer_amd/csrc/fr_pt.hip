@@ -28,6 +28,9 @@
  * the host continued from their dd tails instead of recomputing them (orbit_for).  escape_pt_kernel and orbit_pt are the
  * PT definition's and stay as they are.
  *
+ * ADAPTIVE SUPERSAMPLING (include/fractal_hip.h; fr_ss_adaptive.hip): ss_refine_pt_kernel<JULIA>, persistent waves that run
+ * orbit_pt on the s x s samples of the listed edge pixels (fr_ss_list.h: the claim loop), and pt_ss_refine, its launch.
+ *
  * The entry points that only PT has live here beside their launches, at the end of the file: the state render and its
  * extension, and every fr_*_pt_wide call (WIDE PT: the same launches with a Centre that holds a wide centre; fr_ctx.h).
  * Each builds its Centre and checks PT's domain; the state calls then hand pt_state_rows, their launch, to the state road
@@ -41,6 +44,7 @@
 
 #include "fr_ctx.h"
 #include "fr_math.h"
+#include "fr_ss_list.h"
 #include "fr_wide.h"
 
 namespace {
@@ -193,6 +197,34 @@ hipError_t launch(const fr_kparams &p, int mode, const fr_kout &out, const doubl
     else
         escape_pt_kernel<FR_OUT_COUNT, JULIA><<<grid, block, 0, stream>>>(p, out, x_orbit, k_orbit, x_last, k_last);
     return hipGetLastError();
+}
+
+/* ---- device: ADAPTIVE SUPERSAMPLING's refine pass (include/fractal_hip.h; fr_ss_list.h: the claim loop) --------------- */
+
+/* Persistent waves over the edge list of an adaptive render of cfg_s (`p` holds cfg_s): each lane computes its sample's `off`
+ * by escape_pt_kernel's formula — the same operations on the same (x, y), hence the same bits — runs orbit_pt and colours
+ * the f64 z as the render does.  The log2 table is staged before the loop, which holds no barrier. */
+template <bool JULIA>
+__global__ __launch_bounds__(kSsRefineThreads) void ss_refine_pt_kernel(const fr_kparams p, const fr_ss_refine a,
+                                                                        const double2 *__restrict__ x_orbit,
+                                                                        const double2 *__restrict__ k_orbit, const uint32_t x_last,
+                                                                        const uint32_t k_last) {
+    __shared__ double s_tab[FR_LOG2_N * 3];
+    const double *gt = &g_log2_tab[0][0];
+    for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    __syncthreads();
+    const double width = (double)p.width, height = (double)p.height;
+    const double squared = p.limit * p.limit;
+    ss_refine_loop(a, [&](uint64_t x, uint64_t y) {
+        const double off_re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
+        const double off_im = (((double)y / height) - 0.5) / p.scale_im;
+        double zr, zi;
+        const uint32_t iters = orbit_pt<JULIA>(p.iterations, off_re, off_im, x_orbit, k_orbit, x_last, k_last, squared, zr, zi);
+        uint8_t rgb[3] = {0, 0, 0};
+        const ColourConsts cc = make_colour_consts(p);
+        colour_pixel<double>(cc, zr, zi, zr * zr, zi * zi, iters, s_tab, nullptr, rgb);
+        return (uint32_t)rgb[0] | ((uint32_t)rgb[1] << 8) | ((uint32_t)rgb[2] << 16);
+    });
 }
 
 /* ---- device: the resumable state (include/fractal_hip.h, "resumable perturbation") --------------------------------- */
@@ -638,6 +670,21 @@ int launch_pt(Ctx &ctx, const fr_config *cfg, const Centre &c, const fr_kparams 
     } else {
         HIP_TRY(launch<false>(p, mode, out, o->dev, o->dev, o->x_last, o->x_last, stream));
     }
+    return FR_OK;
+}
+
+/* fr_ss_list.h: the refine pass of an adaptive render on plain PT (dd or wide centre), on the orbits the probe made */
+int pt_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, const fr_ss_refine &a, uint32_t groups, hipStream_t stream) {
+    std::shared_ptr<PtOrbit> o;
+    const int rc = orbit_for(ctx, cfg, c, o);
+    if (rc != FR_OK) return rc;
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    if (cfg->algo == 2)
+        ss_refine_pt_kernel<true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, o->dev + o->k_offset, o->x_last, o->k_last);
+    else
+        ss_refine_pt_kernel<false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, o->dev, o->x_last, o->x_last);
+    HIP_TRY(hipGetLastError());
     return FR_OK;
 }
 

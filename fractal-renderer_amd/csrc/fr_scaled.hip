@@ -27,6 +27,10 @@
  * and escape_extend_pt_kernel are to orbit_pt, in their shape; escape_pt_scaled_kernel and orbit_pt_scaled are SCALED PT's and
  * stay as they are.  The table form has no state (BLA-PT's reason: i + 2^k <= iterations).
  *
+ * ADAPTIVE SUPERSAMPLING (include/fractal_hip.h; fr_ss_adaptive.hip): ss_refine_scaled_kernel<JULIA, BLA>, persistent waves that
+ * run orbit_pt_scaled / orbit_bla_scaled on the s x s samples of the listed edge pixels (fr_ss_list.h: the claim loop);
+ * scaled_render_map, the RGB launch over the probe's strided map, and scaled_ss_refine, the refine launch.
+ *
  * What the kernels here share with those of DE ON SCALED PT (fr_de_scaled.hip) lives in fr_scaled.h, one copy: ScaledDev and its
  * fill from the context's caches, kBig, kOnK, is_big, rebase_test and stage_woff.
  *
@@ -44,6 +48,7 @@
 #include "fr_ctx.h"
 #include "fr_math.h"
 #include "fr_scaled.h"
+#include "fr_ss_list.h"
 #include "fr_wide.h"
 
 namespace {
@@ -491,6 +496,36 @@ hipError_t launch(bool julia, bool bla, const fr_kparams &p, int mode, const fr_
     return julia ? launch<true, false>(p, mode, out, t, stream) : launch<false, false>(p, mode, out, t, stream);
 }
 
+/* ---- device: ADAPTIVE SUPERSAMPLING's refine pass (include/fractal_hip.h; fr_ss_list.h: the claim loop) ---------------- */
+
+/* ss_refine_pt_kernel (fr_pt.hip) with the scaled loops: `woff` by scaled_body's formula on cfg_s (`p` holds cfg_s with the
+ * scaled divisors sre, sim), the loop chosen by BLA, the table built with Dw over the whole image of cfg_s */
+template <bool JULIA, bool BLA>
+__global__ __launch_bounds__(kSsRefineThreads) void ss_refine_scaled_kernel(const fr_kparams p, const fr_ss_refine a, const ScaledDev t) {
+    __shared__ double s_tab[FR_LOG2_N * 3];
+    const double *gt = &g_log2_tab[0][0];
+    for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    __syncthreads();
+    const double width = (double)p.width, height = (double)p.height;
+    const double squared = p.limit * p.limit;
+    ss_refine_loop(a, [&](uint64_t x, uint64_t y) {
+        const double woff_re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
+        const double woff_im = (((double)y / height) - 0.5) / p.scale_im;
+        double zr, zi;
+        uint32_t iters;
+        if constexpr (BLA) {
+            uint32_t passes;
+            iters = orbit_bla_scaled<JULIA>(p.iterations, woff_re, woff_im, t, squared, zr, zi, passes);
+        } else {
+            iters = orbit_pt_scaled<JULIA>(p.iterations, woff_re, woff_im, t, squared, zr, zi);
+        }
+        uint8_t rgb[3] = {0, 0, 0};
+        const ColourConsts cc = make_colour_consts(p);
+        colour_pixel<double>(cc, zr, zi, zr * zr, zi * zi, iters, s_tab, nullptr, rgb);
+        return (uint32_t)rgb[0] | ((uint32_t)rgb[1] << 8) | ((uint32_t)rgb[2] << 16);
+    });
+}
+
 /* the state render, or — extend — the extension from `from` */
 template <bool JULIA>
 hipError_t launch_state(const fr_kparams &p, uint32_t from, bool extend, double *z, uint32_t *iters, double *w, uint32_t *m,
@@ -623,6 +658,38 @@ int scaled_check(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, 
 int scaled_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, unsigned channels,
                        const fr_kout &out, hipStream_t stream) {
     return scaled_rows(cfg, c, bits, y0, y1, channels, FR_OUT_RGB)(ctx, out, stream);
+}
+
+/* fr_ss_list.h: ADAPTIVE SUPERSAMPLING on SCALED PT — the probe (the road's RGB kernel over the strided map) and the refine pass */
+int scaled_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_map &map, const fr_kout &out, hipStream_t stream) {
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    map.apply(p);
+    return launch_scaled(ctx, cfg, c, bits, p, FR_OUT_RGB, out, stream);
+}
+
+int scaled_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, uint32_t groups, hipStream_t stream) {
+    const ScaledConsts k = scaled_consts(cfg);
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    p.scale_re = k.sre;
+    p.scale_im = k.sim;
+    std::shared_ptr<PtOrbit> orbit;
+    std::shared_ptr<BlaTable> table;
+    ScaledDev t;
+    const int rc = scaled_dev_fill(ctx, cfg, c, bits, k, orbit, table, t);
+    if (rc != FR_OK) return rc;
+    const dim3 grid(groups), block(kSsRefineThreads);
+    const bool julia = cfg->algo == 2;
+    if (bits >= 0) {
+        if (julia) ss_refine_scaled_kernel<true, true><<<grid, block, 0, stream>>>(p, a, t);
+        else ss_refine_scaled_kernel<false, true><<<grid, block, 0, stream>>>(p, a, t);
+    } else {
+        if (julia) ss_refine_scaled_kernel<true, false><<<grid, block, 0, stream>>>(p, a, t);
+        else ss_refine_scaled_kernel<false, false><<<grid, block, 0, stream>>>(p, a, t);
+    }
+    HIP_TRY(hipGetLastError());
+    return FR_OK;
 }
 
 }  // namespace fr

@@ -301,6 +301,37 @@ inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &ce
 inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Scaled scaled, uint32_t supersample) {
     return get_image_ss_pt(config, nullptr, &centre, FR_PT_ROAD_SCALED, scaled.bits, supersample);
 }
+// ---- adaptive supersampling (include/fractal_hip.h, "ADAPTIVE SUPERSAMPLING") --------------------------------------------------
+// The supersampled forms above with an Adaptive behind them: all supersample x supersample samples only at EDGE pixels — those
+// whose probe sample differs from a neighbour's by more than `threshold` (0 .. 255; -1: every pixel, the supersampled render's
+// bytes; 255: none) in some channel — and the probe sample everywhere else.  *refined (may be null) receives the number of edge
+// pixels.  The F64 road and every FR_PRECISION_PT road; one GPU.
+struct Adaptive {
+    int threshold = 8;
+    uint64_t *refined = nullptr;
+};
+inline std::vector<RGB> get_image_ss_adaptive(const Config &config, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
+                                              int road, int bits, uint32_t supersample, Adaptive adaptive) {
+    std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
+    check(fr_render_rows_ss_adaptive(&config, precision, pos_lo, centre, road, bits, supersample, adaptive.threshold, 0, config.height, 3,
+                                     reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB), adaptive.refined));
+    return image;
+}
+inline std::vector<RGB> get_image(const Config &config, int precision, uint32_t supersample, Adaptive adaptive) {
+    return get_image_ss_adaptive(config, precision, nullptr, nullptr, FR_PT_ROAD_PLAIN, 0, supersample, adaptive);
+}
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, uint32_t supersample, Adaptive adaptive) {
+    return get_image_ss_adaptive(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_PLAIN, 0, supersample, adaptive);
+}
+inline std::vector<RGB> get_image(const Config &config, Bla bla, const fr_imaginary *pos_lo, uint32_t supersample, Adaptive adaptive) {
+    return get_image_ss_adaptive(config, FR_PRECISION_PT, pos_lo, nullptr, FR_PT_ROAD_BLA, bla.bits, supersample, adaptive);
+}
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Bla bla, uint32_t supersample, Adaptive adaptive) {
+    return get_image_ss_adaptive(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_BLA, bla.bits, supersample, adaptive);
+}
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Scaled scaled, uint32_t supersample, Adaptive adaptive) {
+    return get_image_ss_adaptive(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_SCALED, scaled.bits, supersample, adaptive);
+}
 // A kept anti-aliased view is a kept view of the config with width and height times supersample: the escape / state / extend
 // wrappers above on that config, and this to colour it — colour map and box filter in one kernel, no RGB workspace.
 // channels 3 (r,g,b) or 4 (r,g,b,255; d_out 4-byte aligned); config is the OUTPUT's (width x height).

@@ -1395,6 +1395,59 @@ int fr_render_rows_ss_de_pt_scaled_device(const fr_config *cfg, const fr_wide_ce
 int fr_render_rows_ss_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t supersample,
                                    uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len);
 
+/* ---- adaptive supersampling: all s*s samples only at edge pixels ----------------------------------------------------- */
+
+/* ADAPTIVE SUPERSAMPLING (fr_render_rows_ss_adaptive(_device) below).  Supersampling renders s*s samples of every output
+ * pixel; most pixels lie in smooth regions, where one sample is the filtered average to within a grey level.  DEFINITION, for
+ * supersample = s, 1 <= s <= FR_SS_MAX, and an integer threshold t, -1 <= t <= 255:
+ *   cfg_s  = cfg with width * s and height * s, every other field unchanged;
+ *   H      = the bytes of the road's plain render of cfg_s.  The roads are those of fr_render_rows_ss_de_device's argument rule
+ *            plus FR_PT_ROAD_SCALED: FR_PRECISION_F64 (road PLAIN, no pos_lo, no centre, bits 0); FR_PRECISION_PT with
+ *            FR_PT_ROAD_PLAIN (pos_lo, a wide centre or neither; bits 0), FR_PT_ROAD_BLA (pos_lo / centre as BLA-PT takes them,
+ *            bits 0 or 24 .. 53) or FR_PT_ROAD_SCALED (centre required, pos_lo NULL, bits -1, 0 or 24 .. 53).  BLA-PT's D and
+ *            SCALED PT's Dw are taken over the whole image of cfg_s, as the supersampled deep roads define;
+ *   p      = floor(s / 2); the PROBE of output pixel (X, Y) is P(X, Y, c) = H(s*X + p, s*Y + p, c);
+ *   F(X, Y, c) = (sum over j < s, i < s of H(s*X + i, s*Y + j, c) + floor(s*s / 2)) / (s*s), integer and truncating: the box
+ *            filter of "supersampled rendering";
+ *   edge(X, Y) holds when t < 0, and when a neighbour (X', Y') != (X, Y) exists with |X' - X| <= 1 and |Y' - Y| <= 1,
+ *            0 <= X' < width and 0 <= Y' < height OF THE IMAGE (not of the call's rows), and a channel c with
+ *            |P(X, Y, c) - P(X', Y', c)| > t;
+ *   out(X, Y, c) = edge(X, Y) ? F(X, Y, c) : P(X, Y, c); with 4 channels alpha is 255;
+ *   refined = the number of edge pixels in rows [y0, y1).
+ * An algorithm without orbits gives black and refined = 0.  Consequences: t = -1 gives the bytes of fr_render_rows_ss /
+ * fr_render_rows_ss_pt; t = 255 gives the probe image; s = 1 is the road's plain render for every t; any split of [0, height)
+ * into row pieces gives the whole image's bytes and the same total refined.
+ * A non-edge pixel's interior samples are NEVER LOOKED AT: a feature smaller than a pixel inside a flat neighbourhood is
+ * missed.  Distance shading (SUPERSAMPLED DE) is the tool for that.
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message that names the argument, before any device work): s in 1 .. FR_SS_MAX;
+ * s * width and s * height fit in 32 bits; threshold in -1 .. 255; channels 3 or 4; the road's own domain ON cfg_s with the
+ * argument rules above; width * (y1 - y0) < 2^32; d_work and a non-NULL d_refined 8-byte aligned; RGBA output 4-byte aligned.
+ * FR_PRECISION_F32 and FR_PRECISION_DD are refused by name.  A work_len under the workspace size or a short out_len give
+ * FR_ERR_BUFFER_TOO_SMALL.  y0 == y1 is a no-op that needs no device and no buffer.
+ * Workspace: ONE size per row range, no banding — a caller with less memory calls by row pieces, which the definition makes
+ * exact.  It holds the probe colours of rows [ya, yb) = [max(y0 - 1, 0), min(y1 + 1, height)), 3 bytes each, rounded up to 8
+ * bytes; a uint32 list of at most width * (y1 - y0) pixel indices, rounded up to 8 bytes; and two 64-bit counters, the count
+ * and the claim cursor, which every call zeroes on the stream:
+ *   bytes = ceil8(3 * width * (yb - ya)) + ceil8(4 * width * (y1 - y0)) + 16        (0 for an empty range or width 0).
+ * The device form is asynchronous on `hip_stream`: no host synchronisation (the PT roads: apart from computing and uploading
+ * the view's orbit and table when the context does not hold them yet, as their plain device calls do), no allocation, and
+ * re-entrant as fr_render_rows_ss_device is; d_refined (device memory, may be NULL) receives the count as a uint64 behind the
+ * last kernel.  The F64 road makes one kernel choice for the call, by name and size: it takes no view sample.  The host form
+ * uses the context's scratch; above the host roads' 256 MiB workspace cap it splits the range into row pieces itself.  With
+ * profiling on, fr_last_kernel_name reports the last kernel of the call (ss_refine_*_kernel, or ss_mark_kernel when nothing is
+ * refined) and fr_last_kernel_ms the span of the whole call. */
+int fr_ss_adaptive_workspace_bytes(const fr_config *cfg, uint32_t supersample, uint32_t y0, uint32_t y1, size_t *bytes);
+int fr_render_rows_ss_adaptive_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
+                                      int bits, uint32_t supersample, int threshold, uint32_t y0, uint32_t y1, int channels, void *d_out,
+                                      size_t out_len, void *d_work, size_t work_len, void *d_refined /* uint64 on the device, may be NULL */,
+                                      void *hip_stream);
+int fr_render_rows_ss_adaptive(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                               uint32_t supersample, int threshold, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len,
+                               uint64_t *refined /* may be NULL */);
+/* Test hook: the refine kernels' grid in workgroups of 4 waves; 0 = the default (it fills the device, capped by the most work
+ * the rows can hold).  The output does not depend on it. */
+int fr_debug_ss_adaptive_grid(uint32_t workgroups);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* Exact sum of EXECUTED loop iterations over the pixels (x, y) with x % sx == 0, y % sy == 0 of
