@@ -8,7 +8,8 @@ Python-integer orbits; every assertion message carries the view (config bytes, n
     the first view of a seed;
   - fr_debug_reference_orbit_wide against the integers' orbit, its end by escape included;
   - RGB and RGBA renders of each road against the oracle's soft-log2 colour map over the model's arrays, with drawn colour fields;
-  - WIDE PT's and SCALED PT's state at a drawn cap N and at min(cap, 1), and its extension to the cap, in all four arrays;
+  - WIDE PT's and SCALED PT's state at a drawn cap N, at min(cap, 1) and at the view's band split (tests/deep_ss_views.py), and its
+    extension to the cap, in all four arrays;
   - DE: fr_escape_rows_de_pt_wide, fr_escape_rows_de_pt_bla and the wide DE state with its extension inside 2^440;
     fr_escape_rows_de_pt_scaled without and with a table everywhere, then fr_distance_rows_device and fr_colour_de_rows_device on
     fr_de_scaled_view's config with a drawn thickness;
@@ -29,6 +30,7 @@ import de_model as D
 import de_scaled_model as M
 import de_state_model as DS
 import deep_random_views as G
+import deep_ss_views as V
 import pt_model as P
 import pt_scaled_model as S
 import pt_scaled_state_model as R
@@ -220,11 +222,17 @@ def drawn_splits(rng, cap):
     return sorted({int(rng.integers(0, cap)) if cap > 0 else 0, min(cap, 1)})
 
 
+def with_band_split(splits, v):
+    """the splits and the view's band split N of tests/deep_ss_views.py (the median escaped index + 1): where a view has one, pixels
+    finished before N stand beside pixels escaping after it on a third of the views, which a drawn split almost never gives"""
+    return sorted(set(splits) | ({v.split} if v.split is not None else set()))
+
+
 @pytest.mark.parametrize("seed", G.SEEDS)
 def test_random_views_state_and_extension(fr, native, lib, torch, seed):
     rng = np.random.default_rng([G.BASE_SEED + seed, 1])
-    for c in cases_of(fr, native, lib, seed):
-        check_states(c, torch, drawn_splits(rng, c.g.cap))
+    for k, c in enumerate(cases_of(fr, native, lib, seed)):
+        check_states(c, torch, with_band_split(drawn_splits(rng, c.g.cap), V.all_of(seed)[k]))
 
 
 # ---- distance estimation -------------------------------------------------------------------------------------------------------------
@@ -284,8 +292,9 @@ def check_de(c, torch, splits, thickness):
 @pytest.mark.parametrize("seed", G.SEEDS)
 def test_random_views_distance_estimation(fr, native, lib, torch, seed):
     rng = np.random.default_rng([G.BASE_SEED + seed, 2])
-    for c in cases_of(fr, native, lib, seed):
-        check_de(c, torch, drawn_splits(rng, c.g.cap), THICKNESSES[int(rng.integers(len(THICKNESSES)))])
+    for k, c in enumerate(cases_of(fr, native, lib, seed)):
+        splits = with_band_split(drawn_splits(rng, c.g.cap), V.all_of(seed)[k])
+        check_de(c, torch, splits, THICKNESSES[int(rng.integers(len(THICKNESSES)))])
 
 
 # ---- a row piece ---------------------------------------------------------------------------------------------------------------------
@@ -318,7 +327,7 @@ def test_random_views_row_pieces(fr, native, lib, torch, seed):
 @pytest.mark.parametrize("name", list(G.EDGES))
 def test_edge_views(fr, native, lib, torch, name):
     c = case(fr, native, lib, name)
-    splits = sorted({c.g.cap // 3, min(c.g.cap, 1)})
+    splits = with_band_split({c.g.cap // 3, min(c.g.cap, 1)}, V.edge(name))
     check_escape_rows(c, torch, host=True)
     check_orbit(c)
     check_renders(c)
