@@ -44,6 +44,7 @@ __all__ = [
     "de_scaled_view",
     "escape_rows_de_pt_scaled_state", "extend_rows_de_pt_scaled", "get_image_de_scaled_ss",
     "get_image_ss_adaptive", "ss_adaptive_workspace_bytes",
+    "get_image_de_adaptive", "ss_adaptive_de_workspace_bytes",
 ]
 
 
@@ -1151,6 +1152,44 @@ def get_image_ss_adaptive(config, supersample, threshold=8, precision=Precision.
     refined = C.c_uint64(0)
     _native.check(_native.load().fr_render_rows_ss_adaptive(C.byref(config), int(precision), lo, ptr, road, bits, s, int(threshold), y0, y1,
                                                             int(channels), out.ctypes.data, out.nbytes, C.byref(refined)))
+    return out, refined.value
+
+
+def ss_adaptive_de_workspace_bytes(config, supersample, y0=0, y1=None):
+    """fr_ss_adaptive_de_workspace_bytes: the bytes of device workspace fr_render_rows_ss_adaptive_de_device wants for rows
+    [y0, y1) — the probe's z, der, iters and colours of the rows and their two neighbours, the edge list and two counters; one
+    size, no banding."""
+    y1 = config.height if y1 is None else y1
+    n = C.c_size_t(0)
+    _native.check(_native.load().fr_ss_adaptive_de_workspace_bytes(C.byref(config), int(supersample), y0, y1, C.byref(n)))
+    return n.value
+
+
+def get_image_de_adaptive(config, thickness=1.0, supersample=2, threshold=8, reach=2.0, precision=Precision.F64, pos_lo=None, centre=None,
+                          bla=None, y0=0, y1=None, channels=3, out=None):
+    """Adaptive anti-aliased distance estimation (fr_render_rows_ss_adaptive_de; include/fractal_hip.h, "ADAPTIVE SUPERSAMPLED
+    DE"): rows [y0, y1) of the distance-shaded image with supersample x supersample samples only at EDGE pixels — those whose
+    shaded probe sample differs from a neighbour's by more than `threshold` in some channel (-1: every pixel, the bytes of
+    get_image_de(..., supersample=s), which is the faster call for them) and those whose probe lies closer to the set than
+    `reach` output pixels by its own distance estimate (0: the colour rule alone) — and the probe sample everywhere else.
+    Returns (image uint8 [y1-y0, width, channels], refined: the number of edge pixels).  thickness is in output pixels.
+    precision is Precision.F64 or Precision.PT; pos_lo, centre and bla select the deep road as in get_image_ss_adaptive; the
+    scaled road is not offered."""
+    s = int(supersample)
+    if not 1 <= s <= SS_MAX:
+        raise ValueError("supersample is 1 .. %d" % SS_MAX)
+    if not -1 <= int(threshold) <= 255:
+        raise ValueError("threshold is -1 .. 255")
+    if int(channels) not in (3, 4):
+        raise ValueError("channels is 3 or 4")
+    (lo, ptr, road, bits), _keep = _adaptive_road(precision, pos_lo, centre, bla, False)
+    y0, y1 = _rows(config, y0, y1)
+    if out is None:
+        out = np.empty((max(y1 - y0, 0), config.width, int(channels)), dtype=np.uint8)
+    refined = C.c_uint64(0)
+    _native.check(_native.load().fr_render_rows_ss_adaptive_de(C.byref(config), int(precision), lo, ptr, road, bits, float(thickness), s,
+                                                               int(threshold), float(reach), y0, y1, int(channels), out.ctypes.data,
+                                                               out.nbytes, C.byref(refined)))
     return out, refined.value
 
 

@@ -18,14 +18,14 @@ LIB_PATH = os.path.join(PKG_DIR, "libfractal_hip.so")
 ID_PATH = LIB_PATH + ".id"
 # the files that hold the escape-time kernels, the view statistics and the distance estimate: tools that want their ISA compile these
 KERNEL_SOURCES = ["fr_kernels.hip", "fr_bla.hip", "fr_scaled.hip", "fr_stats.hip", "fr_de.hip", "fr_de_bla.hip", "fr_ss_de.hip",
-                  "fr_de_scaled.hip", "fr_ss_adaptive.hip"]
-# fr_de.hip and, behind it, fr_de_bla.hip, fr_ss_de.hip, fr_de_scaled.hip and fr_ss_adaptive.hip are compiled and linked LAST: the
+                  "fr_de_scaled.hip", "fr_ss_adaptive.hip", "fr_ss_adaptive_de.hip"]
+# fr_de.hip and, behind it, fr_de_bla.hip, fr_ss_de.hip, fr_de_scaled.hip, fr_ss_adaptive.hip and fr_ss_adaptive_de.hip are compiled and linked LAST: the
 # translation units before them keep the order and the places they had without them
-_LAST = ["fr_de.hip", "fr_de_bla.hip", "fr_ss_de.hip", "fr_de_scaled.hip", "fr_ss_adaptive.hip"]
+_LAST = ["fr_de.hip", "fr_de_bla.hip", "fr_ss_de.hip", "fr_de_scaled.hip", "fr_ss_adaptive.hip", "fr_ss_adaptive_de.hip"]
 SOURCES = [s for s in KERNEL_SOURCES if s not in _LAST] + ["fr_dispatch.hip", "fr_api.hip", "fr_host.hip", "fr_multi.hip",
                                                            "fr_fern.hip", "fr_dd.hip", "fr_pt.hip", "fr_wide.hip", "fr_ss.hip"] + _LAST
 DEPS = SOURCES + ["fr_kernels.h", "fr_launch.h", "fr_ctx.h", "fr_wide.h", "fr_bla.h", "fr_math.h", "fr_colour.h", "fr_log2_table.inc",
-                  "fr_de.h", "fr_de_shade.h", "fr_ss.h", "fr_scaled.h", "fr_ss_list.h",
+                  "fr_de.h", "fr_de_shade.h", "fr_ss.h", "fr_scaled.h", "fr_ss_list.h", "fr_ss_de_sample.h",
                   os.path.join("..", "..", "include", "fractal_hip.h")]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",

@@ -23,6 +23,10 @@
  *   escape_extend_pt_de_kernel<JULIA>  continues that state in place on the orbits of the new cap.  Both run orbit_pt_de_state,
  *                               the one copy of the state step with the derivative.  The two extend kernels read iters first and
  *                               a workgroup with no pixel at the old cap ends before it stages or loads anything.
+ *   ss_refine_de_f64_kernel<JULIA>, ss_refine_de_pt_kernel<JULIA>   ADAPTIVE SUPERSAMPLED DE's refine pass (fr_ss_adaptive_de.hip;
+ *                               fr_ss_list.h: the claim loop): persistent waves run escape_de_kernel's loop / orbit_pt_de (the
+ *                               one copy of escape_pt_de_kernel's loop) on the s x s samples of the listed edge pixels and
+ *                               colour and shade each as colour_de_rows_kernel does (fr_ss_de_sample.h).
  *   distance_rows_kernel        (z, iters, der) -> D, one double per pixel; the log2 table in LDS.
  *   colour_de_rows_kernel       fr_colour.h's colour_of, the renders' own map, then the shading: every byte times
  *                               s = D / thickness where s < 1.  RGBA leaves as one dword, RGB as three bytes at any alignment.
@@ -34,12 +38,14 @@
 #include "fr_ctx.h"
 #include "fr_de.h"
 #include "fr_math.h"
+#include "fr_ss_list.h"
 #include "fr_wide.h"
 
 namespace {
 
 #include "fr_colour.h"
 #include "fr_de_shade.h" /* kHalfLn2, de_distance */
+#include "fr_ss_de_sample.h" /* ss_de_sample_colour */
 
 constexpr uint32_t kDeThreads = 64 * kDeepWaves;
 
@@ -128,6 +134,59 @@ __global__ __launch_bounds__(kDeThreads) void escape_de_kernel(const fr_kparams 
 
 /* ---- PT (include/fractal_hip.h, fr_precision: PT; fr_pt.hip: orbit_pt) with d beside it ------------------------------------- */
 
+/* escape_pt_de_kernel's pixel: PT's loop as orbit_pt states it with d beside it, from `off`.  Returns the escape index (or
+ * `iterations`), leaves the final z in (zr, zi) and the derivative in (dr, di). */
+template <bool JULIA>
+__device__ __forceinline__ uint32_t orbit_pt_de(uint32_t iterations, double off_re, double off_im, const double2 *__restrict__ x_orbit,
+                                                const double2 *__restrict__ k_orbit, uint32_t x_last, uint32_t k_last, double squared,
+                                                double &zr, double &zi, double &dr, double &di) {
+    const double b0 = JULIA ? 0.0 : 1.0;
+    const double2 *X = x_orbit;
+    uint32_t last = x_last;
+    uint32_t m = JULIA ? 0u : 1u;
+    double dzr = off_re, dzi = off_im;
+    const double dcr = JULIA ? 0.0 : off_re, dci = JULIA ? 0.0 : off_im;
+    /* m <= last - 1 at the top of every step: X_{m+1} exists; the clamp is for a cap of 0, where R has two entries */
+    double2 Z = X[m], N = X[min(m + 1u, last)];
+    const double2 K1 = k_orbit[1];  /* the entry after a rebase; K_0 = R_0 = 0 */
+    zr = Z.x + dzr, zi = Z.y + dzi;
+    dr = 1.0, di = 0.0;
+    uint32_t i = 0;
+    for (; i < iterations; i++) {
+        const double2 P = X[min(m + 2u, last)]; /* X_{m+2}: next step's X_{m+1} if it does not rebase */
+        const double tr = Z.x + zr, ti = Z.y + zi;
+        const double ur = zr + zr, ui = zi + zi; /* the derivative's t: from the z before the step */
+        const double ndr = __builtin_fma(tr, dzr, __builtin_fma(-ti, dzi, dcr));
+        const double ndi = __builtin_fma(tr, dzi, __builtin_fma(ti, dzr, dci));
+        const double ner = __builtin_fma(ur, dr, __builtin_fma(-ui, di, b0));
+        const double nei = __builtin_fma(ur, di, ui * dr);
+        m++;
+        zr = N.x + ndr;
+        zi = N.y + ndi;
+        dzr = ndr;
+        dzi = ndi;
+        dr = ner;
+        di = nei;
+        const double dist = zr * zr + zi * zi;
+        if (dist > squared) break;
+        if (dist < dzr * dzr + dzi * dzi || m == last) {
+            dzr = zr;
+            dzi = zi;
+            m = 0;
+            if (JULIA) {
+                X = k_orbit;
+                last = k_last;
+            }
+            Z = make_double2(0.0, 0.0);
+            N = K1;
+        } else {
+            Z = N;
+            N = P;
+        }
+    }
+    return i;
+}
+
 template <bool JULIA>
 __global__ __launch_bounds__(kDeThreads) void escape_pt_de_kernel(const fr_kparams p, double *__restrict__ z, uint32_t *__restrict__ iters,
                                                                   double *__restrict__ der, const double2 *__restrict__ x_orbit,
@@ -143,55 +202,66 @@ __global__ __launch_bounds__(kDeThreads) void escape_pt_de_kernel(const fr_kpara
     const bool escape_algo = JULIA ? p.algo == 2 : p.algo == 0;
     double zr = 0.0, zi = 0.0, dr = 0.0, di = 0.0;
     uint32_t i = 0;
-    if (escape_algo) {
-        const double off_re = s_re[l.lx], off_im = s_im[l.ly];
-        const double squared = p.limit * p.limit;
-        const uint32_t iterations = p.iterations;
-        const double b0 = JULIA ? 0.0 : 1.0;
-        const double2 *X = x_orbit;
-        uint32_t last = x_last;
-        uint32_t m = JULIA ? 0u : 1u;
-        double dzr = off_re, dzi = off_im;
-        const double dcr = JULIA ? 0.0 : off_re, dci = JULIA ? 0.0 : off_im;
-        /* m <= last - 1 at the top of every step: X_{m+1} exists; the clamp is for a cap of 0, where R has two entries */
-        double2 Z = X[m], N = X[min(m + 1u, last)];
-        const double2 K1 = k_orbit[1];  /* the entry after a rebase; K_0 = R_0 = 0 */
-        zr = Z.x + dzr, zi = Z.y + dzi;
-        dr = 1.0;
-        for (; i < iterations; i++) {
-            const double2 P = X[min(m + 2u, last)]; /* X_{m+2}: next step's X_{m+1} if it does not rebase */
-            const double tr = Z.x + zr, ti = Z.y + zi;
-            const double ur = zr + zr, ui = zi + zi; /* the derivative's t: from the z before the step */
-            const double ndr = __builtin_fma(tr, dzr, __builtin_fma(-ti, dzi, dcr));
-            const double ndi = __builtin_fma(tr, dzi, __builtin_fma(ti, dzr, dci));
-            const double ner = __builtin_fma(ur, dr, __builtin_fma(-ui, di, b0));
-            const double nei = __builtin_fma(ur, di, ui * dr);
-            m++;
-            zr = N.x + ndr;
-            zi = N.y + ndi;
-            dzr = ndr;
-            dzi = ndi;
-            dr = ner;
-            di = nei;
-            const double dist = zr * zr + zi * zi;
-            if (dist > squared) break;
-            if (dist < dzr * dzr + dzi * dzi || m == last) {
-                dzr = zr;
-                dzi = zi;
-                m = 0;
-                if (JULIA) {
-                    X = k_orbit;
-                    last = k_last;
-                }
-                Z = make_double2(0.0, 0.0);
-                N = K1;
-            } else {
-                Z = N;
-                N = P;
-            }
-        }
-    }
+    if (escape_algo)
+        i = orbit_pt_de<JULIA>(p.iterations, s_re[l.lx], s_im[l.ly], x_orbit, k_orbit, x_last, k_last, p.limit * p.limit, zr, zi, dr, di);
     de_store(p, l, z, iters, der, zr, zi, i, dr, di);
+}
+
+/* ---- ADAPTIVE SUPERSAMPLED DE's refine pass (include/fractal_hip.h; fr_ss_list.h: the claim loop) ----------------------------- */
+
+/* Persistent waves over the edge list of an adaptive DE render of cfg_s (`p` holds cfg_s).  The F64 road: each lane computes its
+ * sample's c by coord_to_space on cfg_s — escape_de_kernel's de_stage operations on the same (x, y), hence the same bits — runs
+ * escape_de_kernel's loop and colours and shades the sample as colour_de_rows_kernel does (fr_ss_de_sample.h).  The log2 table is
+ * staged before the loop, which holds no barrier. */
+template <bool JULIA>
+__global__ __launch_bounds__(kSsRefineThreads) void ss_refine_de_f64_kernel(const fr_kparams p, const fr_ss_refine a,
+                                                                            const fr_ss_de_shade sh) {
+    __shared__ double s_tab[FR_LOG2_N * 3];
+    const double *gt = &g_log2_tab[0][0];
+    for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    __syncthreads();
+    const double width = (double)p.width, height = (double)p.height;
+    const double squared = p.limit * p.limit; /* :246 */
+    const uint32_t iterations = p.iterations;
+    ss_refine_loop(a, [&](uint64_t x, uint64_t y) {
+        double re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re + p.pos_re; /* de_stage<false> */
+        double im = (((double)y / height) - 0.5) / p.scale_im + p.pos_im;
+        const double cre = JULIA ? p.julia_re : re, cim = JULIA ? p.julia_im : im;
+        const double b0 = JULIA ? 0.0 : 1.0;
+        double dr = 1.0, di = 0.0;
+        uint32_t i = 0;
+        for (; i < iterations; i++) { /* escape_de_kernel's step */
+            const double tr = re + re, ti = im + im;
+            const double nre = (re * re - im * im) + cre;
+            const double nim = tr * im + cim;
+            const double ndr = __builtin_fma(tr, dr, __builtin_fma(-ti, di, b0));
+            const double ndi = __builtin_fma(tr, di, ti * dr);
+            re = nre, im = nim, dr = ndr, di = ndi;
+            if (nre * nre + nim * nim > squared) break;
+        }
+        return ss_de_sample_colour(p, re, im, dr, di, i, sh.pixels, sh.thickness, s_tab);
+    });
+}
+
+/* PT: `off` by de_stage<true>'s formula on cfg_s, then orbit_pt_de on the context's orbits */
+template <bool JULIA>
+__global__ __launch_bounds__(kSsRefineThreads) void ss_refine_de_pt_kernel(const fr_kparams p, const fr_ss_refine a, const fr_ss_de_shade sh,
+                                                                           const double2 *__restrict__ x_orbit,
+                                                                           const double2 *__restrict__ k_orbit, const uint32_t x_last,
+                                                                           const uint32_t k_last) {
+    __shared__ double s_tab[FR_LOG2_N * 3];
+    const double *gt = &g_log2_tab[0][0];
+    for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    __syncthreads();
+    const double width = (double)p.width, height = (double)p.height;
+    const double squared = p.limit * p.limit;
+    ss_refine_loop(a, [&](uint64_t x, uint64_t y) {
+        const double off_re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
+        const double off_im = (((double)y / height) - 0.5) / p.scale_im;
+        double zr, zi, dr, di;
+        const uint32_t it = orbit_pt_de<JULIA>(p.iterations, off_re, off_im, x_orbit, k_orbit, x_last, k_last, squared, zr, zi, dr, di);
+        return ss_de_sample_colour(p, zr, zi, dr, di, it, sh.pixels, sh.thickness, s_tab);
+    });
 }
 
 /* ---- RESUMABLE DE (include/fractal_hip.h): a DE view's cap raised in place ------------------------------------------------------ */
@@ -750,6 +820,41 @@ int de_domain(const fr_config *cfg, int precision, const Centre &c, bool wide_ca
 int de_render_rows(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, uint32_t y0, uint32_t y1, double *d_z, uint32_t *d_iters,
                    double *d_der, hipStream_t stream) {
     return de_rows(cfg, precision, c, y0, y1)(ctx, d_z, d_iters, d_der, nullptr, stream);
+}
+
+/* fr_ss_list.h: ADAPTIVE SUPERSAMPLED DE on the F64 road and PT — the probe (the road's DE kernel over the strided map) and the
+ * refine pass on the orbits the probe made */
+int de_render_map(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const fr_ss_map &map, double *d_z, uint32_t *d_iters,
+                  double *d_der, hipStream_t stream) {
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    map.apply(p);
+    const char *kname;
+    return de_launch(ctx, cfg, precision, c, p, d_z, d_iters, d_der, stream, kname);
+}
+
+int de_ss_refine(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const fr_ss_refine &a, const fr_ss_de_shade &sh,
+                 uint32_t groups, hipStream_t stream) {
+    const bool julia = cfg->algo == FR_ALGO_JULIA;
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    const dim3 grid(groups), block(kSsRefineThreads);
+    if (precision == FR_PRECISION_PT) {
+        std::shared_ptr<PtOrbit> keep; /* alive until the launch is enqueued */
+        PtOrbitView v;
+        const int rc = pt_orbit_view(ctx, cfg, c, keep, v);
+        if (rc != FR_OK) return rc;
+        if (julia)
+            ss_refine_de_pt_kernel<true><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
+        else
+            ss_refine_de_pt_kernel<false><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
+    } else if (julia) {
+        ss_refine_de_f64_kernel<true><<<grid, block, 0, stream>>>(p, a, sh);
+    } else {
+        ss_refine_de_f64_kernel<false><<<grid, block, 0, stream>>>(p, a, sh);
+    }
+    HIP_TRY(hipGetLastError());
+    return FR_OK;
 }
 
 int de_state_device(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z, void *d_iters, void *d_d, void *d_m,

@@ -20,6 +20,9 @@
  *     definition's fma(t.re, d.im, t.im * d.re), and on a view where no pass skips all three arrays are fr_escape_rows_de's (PT).
  * The registers, the occupancy and the inner loop: profiles/de_bla_inner_loop_isa.txt.
  *
+ * ss_refine_de_bla_kernel<JULIA>: ADAPTIVE SUPERSAMPLED DE's refine pass on this road (fr_ss_adaptive_de.hip; fr_ss_list.h: the
+ * claim loop) — orbit_bla_de on the s x s samples of the listed edge pixels, each coloured and shaded through fr_ss_de_sample.h.
+ *
  * The calls, at the end of the file: BLA-PT's domain check (fr_bla.h: bla_check), DE's limit and arrays, then the profiled
  * launch through the row-call bodies of fr_ctx.h (device_form, host_raw, profiled_rows).
  */
@@ -30,9 +33,14 @@
 #include "fr_ctx.h"
 #include "fr_de.h"
 #include "fr_math.h"
+#include "fr_ss_list.h"
 #include "fr_wide.h"
 
 namespace {
+
+#include "fr_colour.h"
+#include "fr_de_shade.h"
+#include "fr_ss_de_sample.h" /* ss_de_sample_colour */
 
 /* the orbits and their tables as the kernel sees them (fr_bla.hip's BlaDev); Mandelbrot: the k fields repeat the x fields */
 struct DeBlaDev {
@@ -191,11 +199,50 @@ __global__ __launch_bounds__(64 * kDeepWaves) void escape_bla_de_kernel(const fr
     der[2 * k + 1] = di;
 }
 
+/* ADAPTIVE SUPERSAMPLED DE's refine pass (include/fractal_hip.h; fr_ss_list.h: the claim loop; fr_de.hip: ss_refine_de_pt_kernel)
+ * with orbit_bla_de: `off` by escape_bla_de_kernel's formula on cfg_s (`p`), the table `t` built with D over the whole image of
+ * cfg_s */
+template <bool JULIA>
+__global__ __launch_bounds__(kSsRefineThreads) void ss_refine_de_bla_kernel(const fr_kparams p, const fr_ss_refine a, const fr_ss_de_shade sh,
+                                                                            const DeBlaDev t) {
+    __shared__ double s_tab[FR_LOG2_N * 3];
+    const double *gt = &g_log2_tab[0][0];
+    for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    __syncthreads();
+    const double width = (double)p.width, height = (double)p.height;
+    const double squared = p.limit * p.limit;
+    ss_refine_loop(a, [&](uint64_t x, uint64_t y) {
+        const double off_re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
+        const double off_im = (((double)y / height) - 0.5) / p.scale_im;
+        double zr, zi, dr, di;
+        const uint32_t it = orbit_bla_de<JULIA>(p.iterations, off_re, off_im, t, squared, zr, zi, dr, di);
+        return ss_de_sample_colour(p, zr, zi, dr, di, it, sh.pixels, sh.thickness, s_tab);
+    });
+}
+
 }  // namespace
 
 using namespace fr;
 
 namespace {
+
+/* the orbits and the table of an escape-time view as the kernels take them, from the context's caches */
+int de_bla_dev_fill(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, std::shared_ptr<PtOrbit> &orbit,
+                    std::shared_ptr<BlaTable> &table, DeBlaDev &t) {
+    PtOrbitView v;
+    const int rc = bla_table_for(ctx, cfg, c, bits, false, orbit, v, table);
+    if (rc != FR_OK) return rc;
+    const BlaTableDev &d = table->view;
+    t = DeBlaDev{};
+    t.x_r2 = d.x_rad, t.k_r2 = d.k_rad;
+    t.x_coef = d.x_coef, t.k_coef = d.k_coef;
+    t.x_n0 = d.x_n0, t.k_n0 = d.k_n0;
+    t.x_orbit = v.x;
+    t.k_orbit = v.k;
+    t.x_last = v.x_last;
+    t.k_last = v.k_last;
+    return FR_OK;
+}
 
 /* the launch of rows with their derivatives on the context's orbits and tables; arguments already checked */
 int launch_bla_de(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_kparams &p, double *d_z, uint32_t *d_iters,
@@ -211,18 +258,9 @@ int launch_bla_de(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, con
     }
     std::shared_ptr<PtOrbit> orbit; /* alive until the launch is enqueued, like the table */
     std::shared_ptr<BlaTable> table;
-    PtOrbitView v;
-    const int rc = bla_table_for(ctx, cfg, c, bits, false, orbit, v, table);
+    DeBlaDev t;
+    const int rc = de_bla_dev_fill(ctx, cfg, c, bits, orbit, table, t);
     if (rc != FR_OK) return rc;
-    const BlaTableDev &d = table->view;
-    DeBlaDev t{};
-    t.x_r2 = d.x_rad, t.k_r2 = d.k_rad;
-    t.x_coef = d.x_coef, t.k_coef = d.k_coef;
-    t.x_n0 = d.x_n0, t.k_n0 = d.k_n0;
-    t.x_orbit = v.x;
-    t.k_orbit = v.k;
-    t.x_last = v.x_last;
-    t.k_last = v.k_last;
     if (julia)
         escape_bla_de_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, t);
     else
@@ -273,6 +311,32 @@ int bla_de_domain(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0,
 int bla_de_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, double *d_z, uint32_t *d_iters,
                        double *d_der, hipStream_t stream) {
     return bla_de_rows(cfg, c, bits, y0, y1)(ctx, d_z, d_iters, d_der, nullptr, stream);
+}
+
+/* fr_ss_list.h: ADAPTIVE SUPERSAMPLED DE on BLA-PT — the probe (the road's DE kernel over the strided map) and the refine pass */
+int bla_de_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_map &map, double *d_z, uint32_t *d_iters,
+                      double *d_der, hipStream_t stream) {
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    map.apply(p);
+    return launch_bla_de(ctx, cfg, c, bits, p, d_z, d_iters, d_der, stream);
+}
+
+int bla_de_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, const fr_ss_de_shade &sh,
+                     uint32_t groups, hipStream_t stream) {
+    std::shared_ptr<PtOrbit> orbit; /* alive until the launch is enqueued, like the table */
+    std::shared_ptr<BlaTable> table;
+    DeBlaDev t;
+    const int rc = de_bla_dev_fill(ctx, cfg, c, bits, orbit, table, t);
+    if (rc != FR_OK) return rc;
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    if (cfg->algo == FR_ALGO_JULIA)
+        ss_refine_de_bla_kernel<true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
+    else
+        ss_refine_de_bla_kernel<false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
+    HIP_TRY(hipGetLastError());
+    return FR_OK;
 }
 
 }  // namespace fr

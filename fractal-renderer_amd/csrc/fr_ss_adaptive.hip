@@ -32,11 +32,6 @@ namespace {
 
 #include "fr_colour.h"
 
-constexpr uint32_t kMarkW = 32, kMarkH = 8;           /* the tile: one lane per output pixel, a wave = two tile rows */
-constexpr uint32_t kMarkThreads = kMarkW * kMarkH;
-constexpr uint32_t kMarkPitch = kMarkW + 2, kMarkHalo = kMarkPitch * (kMarkH + 2);
-constexpr uint32_t kMarkOutside = 0xFFFFFFFFu;        /* a halo position outside the image */
-
 struct ssm_params {
     const uint8_t *probe;          /* probe colours of image rows [ya, yb), packed r,g,b */
     uint8_t *out;                  /* rows [y0, y0 + rows) of the output */
@@ -50,68 +45,24 @@ struct ssm_params {
     int tau;                       /* -1: every pixel is an edge; 255: none is */
 };
 
-__device__ __forceinline__ bool ssm_differs(uint32_t c, uint32_t n, int tau) {
-    if (n == kMarkOutside) return false;
-    const int dr = (int)(c & 0xFFu) - (int)(n & 0xFFu), dg = (int)(c >> 8 & 0xFFu) - (int)(n >> 8 & 0xFFu),
-              db = (int)(c >> 16 & 0xFFu) - (int)(n >> 16 & 0xFFu);
-    return abs(dr) > tau || abs(dg) > tau || abs(db) > tau;
-}
-
 __global__ __launch_bounds__(kMarkThreads) void ss_mark_kernel(const ssm_params q) {
     __shared__ uint32_t s_p[kMarkHalo];
     const uint32_t tid = threadIdx.x;
     const uint32_t ty = blockIdx.x / q.tiles_x, tx = blockIdx.x - ty * q.tiles_x;
     const uint32_t X0 = tx * kMarkW, R0 = ty * kMarkH;
-    for (uint32_t k = tid; k < kMarkHalo; k += kMarkThreads) {
-        const uint32_t hr = k / kMarkPitch, hc = k - hr * kMarkPitch;
-        const int64_t X = (int64_t)X0 + hc - 1, Y = (int64_t)q.y0 + R0 + hr - 1; /* image coordinates */
-        uint32_t v = kMarkOutside;
-        if (X >= 0 && X < (int64_t)q.width && Y >= (int64_t)q.ya && Y < (int64_t)q.yb) {
-            const uint8_t *c = q.probe + ((uint64_t)(Y - q.ya) * q.width + (uint64_t)X) * 3u;
-            v = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16);
-        }
-        s_p[k] = v;
-    }
+    ss_mark_stage(s_p, q.probe, q.width, q.ya, q.yb, q.y0, X0, R0, tid);
     __syncthreads();
 
     const uint32_t lx = tid % kMarkW, ly = tid / kMarkW;
     const uint32_t X = X0 + lx, row = R0 + ly;
     const bool valid = X < q.width && row < q.rows;
     const uint32_t *at = s_p + (ly + 1u) * kMarkPitch + lx + 1u;
-    const uint32_t c = at[0];
     bool edge = false;
     if (valid) {
-        if (q.tau < 0) {
-            edge = true;
-        } else {
-            edge = ssm_differs(c, at[-(int)kMarkPitch - 1], q.tau) || ssm_differs(c, at[-(int)kMarkPitch], q.tau) ||
-                   ssm_differs(c, at[-(int)kMarkPitch + 1], q.tau) || ssm_differs(c, at[-1], q.tau) || ssm_differs(c, at[1], q.tau) ||
-                   ssm_differs(c, at[kMarkPitch - 1u], q.tau) || ssm_differs(c, at[kMarkPitch], q.tau) ||
-                   ssm_differs(c, at[kMarkPitch + 1u], q.tau);
-        }
-        const uint64_t px = (uint64_t)row * q.width + X;
-        if (q.bpp == 4u) {
-            reinterpret_cast<uint32_t *>(q.out)[px] = c | 0xFF000000u;
-        } else {
-            uint8_t *o = q.out + 3ull * px;
-            o[0] = (uint8_t)c;
-            o[1] = (uint8_t)(c >> 8);
-            o[2] = (uint8_t)(c >> 16);
-        }
+        edge = q.tau < 0 || ss_mark_neighbours(at, q.tau);
+        ss_mark_write(q.out, q.bpp, (uint64_t)row * q.width + X, at[0]);
     }
-    /* the wave's edge pixels: one ballot, one atomic (every lane of the wave is here) */
-    const unsigned long long mask = __ballot(edge);
-    if (mask == 0ull) return; /* wave-uniform */
-    const uint32_t lane = tid & 63u;
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(q.counters, (unsigned long long)__builtin_popcountll(mask));
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
-    base = ((unsigned long long)hi << 32) | lo;
-    if (edge) {
-        const uint32_t rank = (uint32_t)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
-        q.list[base + rank] = row * q.width + X; /* < 2^32: the domain */
-    }
+    ss_mark_append(edge, row * q.width + X, q.list, q.counters, tid);
 }
 
 /* The F64 road's refine pass (fr_ss_list.h: ss_refine_loop; fr_pt.hip: ss_refine_pt_kernel): each lane computes its sample's c
@@ -151,9 +102,36 @@ std::atomic<uint32_t> g_refine_groups{0}; /* fr_debug_ss_adaptive_grid: 0 = the 
 }  // namespace
 
 namespace fr {
-namespace {
 
 constexpr uint32_t kRefineGroupsDefault = 256 * 8; /* 256 CUs x 8 workgroups of 4 waves: every wave slot of the device */
+
+/* fr_ss_list.h: the edge list as a refine kernel takes it, and the refine grid */
+fr_ss_refine ss_refine_args(uint8_t *out, const uint32_t *list, unsigned long long *counters, uint32_t width, uint32_t y0, uint32_t s,
+                            uint32_t bpp) {
+    fr_ss_refine a;
+    a.out = out;
+    a.list = list;
+    a.counters = counters;
+    a.width = width;
+    a.y0 = y0;
+    a.s = s;
+    a.s2 = s * s;
+    a.ppw = 64u / a.s2;
+    a.bpp = bpp;
+    a.half = a.s2 / 2u;
+    a.magic = (uint32_t)(((1ull << 31) + a.s2 - 1u) / a.s2);
+    return a;
+}
+
+uint32_t ss_refine_groups(const fr_ss_refine &a, uint32_t rows) {
+    /* the most work the rows can hold: every pixel an edge, ppw entries a claim, 4 waves a workgroup */
+    const uint64_t claims = ((uint64_t)a.width * rows + a.ppw - 1) / a.ppw;
+    const uint64_t cap = (claims + kSsRefineThreads / 64u - 1) / (kSsRefineThreads / 64u);
+    const uint32_t groups = g_refine_groups.load();
+    return groups ? groups : (uint32_t)std::min<uint64_t>(kRefineGroupsDefault, cap);
+}
+
+namespace {
 
 /* what the adaptive calls have checked: the plan of cfg_s, the road with its centre and resolved bits */
 struct SsaRoad {
@@ -293,23 +271,8 @@ int ssa_render(Ctx &ctx, const SsaRoad &r, const fr_config *cfg, uint32_t s, uin
     /* 3. F over the probe bytes of the listed pixels; s = 1: F = P already; a threshold of 255: the list is empty */
     const char *kname = "ss_mark_kernel";
     if (s > 1 && escape_algo && r.tau < 255) {
-        fr_ss_refine a;
-        a.out = q.out;
-        a.list = list;
-        a.counters = counters;
-        a.width = cfg->width;
-        a.y0 = y0;
-        a.s = s;
-        a.s2 = s * s;
-        a.ppw = 64u / a.s2;
-        a.bpp = bpp;
-        a.half = a.s2 / 2u;
-        a.magic = (uint32_t)(((1ull << 31) + a.s2 - 1u) / a.s2);
-        /* the most work the rows can hold: every pixel an edge, ppw entries a claim, 4 waves a workgroup */
-        const uint64_t claims = ((uint64_t)cfg->width * q.rows + a.ppw - 1) / a.ppw;
-        const uint64_t cap = (claims + kSsRefineThreads / 64u - 1) / (kSsRefineThreads / 64u);
-        uint32_t groups = g_refine_groups.load();
-        if (groups == 0) groups = (uint32_t)std::min<uint64_t>(kRefineGroupsDefault, cap);
+        const fr_ss_refine a = ss_refine_args(q.out, list, counters, cfg->width, y0, s, bpp);
+        const uint32_t groups = ss_refine_groups(a, q.rows);
         if (r.precision == FR_PRECISION_F64) {
             fr_kparams p;
             fill_params(cs, default_opts(), p);

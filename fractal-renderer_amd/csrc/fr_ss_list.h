@@ -1,8 +1,9 @@
 /*
  * fr_ss_list.h — internal: what the pieces of ADAPTIVE SUPERSAMPLING (include/fractal_hip.h) share — the strided pixel map of
- * the probe pass, the edge list as a refine kernel sees it, the claim loop of the persistent refine waves, and the road
+ * the probe pass, the mark pass's tile and its pieces, the edge list as a refine kernel sees it, the claim loop of the persistent refine waves, and the road
  * launches that fr_ss_adaptive.hip calls.  The refine kernels themselves sit beside their road's loop (fr_pt.hip, fr_bla.hip,
- * fr_scaled.hip; the F64 road's in fr_ss_adaptive.hip).  The device code here has internal linkage: each translation unit
+ * fr_scaled.hip; the F64 road's in fr_ss_adaptive.hip) — and ADAPTIVE SUPERSAMPLED DE's (fr_ss_adaptive_de.hip) beside their road's
+ * DE loop (fr_de.hip, fr_de_bla.hip).  The device code here has internal linkage: each translation unit
  * compiles its own copy into its own kernels.
  */
 #ifndef FR_SS_LIST_H
@@ -44,7 +45,82 @@ struct fr_ss_refine {
 
 constexpr uint32_t kSsRefineThreads = 256; /* 4 waves; a wave claims on its own, the workgroup only shares the log2 table */
 
+/* The thickness and the pixels of the distance shade as a DE refine kernel takes them (ADAPTIVE SUPERSAMPLED DE): Ts = T * s in
+ * sample pixels and (double)(s * height) * min(|scale.re|, |scale.im|), what colour_de_rows_kernel is handed for cfg_s. */
+struct fr_ss_de_shade {
+    double pixels, thickness;
+};
+
+/* The mark pass's tile (ss_mark_kernel, ss_mark_de_kernel): one lane per output pixel, a wave = two tile rows, a one-pixel halo
+ * around it in LDS as packed r | g << 8 | b << 16. */
+constexpr uint32_t kMarkW = 32, kMarkH = 8;
+constexpr uint32_t kMarkThreads = kMarkW * kMarkH;
+constexpr uint32_t kMarkPitch = kMarkW + 2, kMarkHalo = kMarkPitch * (kMarkH + 2);
+constexpr uint32_t kMarkOutside = 0xFFFFFFFFu; /* a halo position outside the image */
+
 namespace {
+
+/* ---- the mark pass's shared pieces ---- */
+
+/* the probe colours of the tile at (X0, y0 + R0) with its halo into s_p; rows outside [ya, yb) and columns outside the width are
+ * outside the IMAGE.  `probe` holds rows [ya, yb) as packed r,g,b.  The caller synchronises. */
+__device__ __forceinline__ void ss_mark_stage(uint32_t *s_p, const uint8_t *probe, uint32_t width, uint32_t ya, uint32_t yb, uint32_t y0,
+                                              uint32_t X0, uint32_t R0, uint32_t tid) {
+    for (uint32_t k = tid; k < kMarkHalo; k += kMarkThreads) {
+        const uint32_t hr = k / kMarkPitch, hc = k - hr * kMarkPitch;
+        const int64_t X = (int64_t)X0 + hc - 1, Y = (int64_t)y0 + R0 + hr - 1; /* image coordinates */
+        uint32_t v = kMarkOutside;
+        if (X >= 0 && X < (int64_t)width && Y >= (int64_t)ya && Y < (int64_t)yb) {
+            const uint8_t *c = probe + ((uint64_t)(Y - ya) * width + (uint64_t)X) * 3u;
+            v = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16);
+        }
+        s_p[k] = v;
+    }
+}
+
+__device__ __forceinline__ bool ss_mark_differs(uint32_t c, uint32_t n, int tau) {
+    if (n == kMarkOutside) return false;
+    const int dr = (int)(c & 0xFFu) - (int)(n & 0xFFu), dg = (int)(c >> 8 & 0xFFu) - (int)(n >> 8 & 0xFFu),
+              db = (int)(c >> 16 & 0xFFu) - (int)(n >> 16 & 0xFFu);
+    return abs(dr) > tau || abs(dg) > tau || abs(db) > tau;
+}
+
+/* the neighbour rule at `at`, the lane's own word in the staged tile: some of the 8 neighbours inside the image differs */
+__device__ __forceinline__ bool ss_mark_neighbours(const uint32_t *at, int tau) {
+    const uint32_t c = at[0];
+    return ss_mark_differs(c, at[-(int)kMarkPitch - 1], tau) || ss_mark_differs(c, at[-(int)kMarkPitch], tau) ||
+           ss_mark_differs(c, at[-(int)kMarkPitch + 1], tau) || ss_mark_differs(c, at[-1], tau) || ss_mark_differs(c, at[1], tau) ||
+           ss_mark_differs(c, at[kMarkPitch - 1u], tau) || ss_mark_differs(c, at[kMarkPitch], tau) ||
+           ss_mark_differs(c, at[kMarkPitch + 1u], tau);
+}
+
+/* P of pixel `px` (row * width + X, rows from y0) into the output */
+__device__ __forceinline__ void ss_mark_write(uint8_t *out, uint32_t bpp, uint64_t px, uint32_t c) {
+    if (bpp == 4u) {
+        reinterpret_cast<uint32_t *>(out)[px] = c | 0xFF000000u;
+    } else {
+        uint8_t *o = out + 3ull * px;
+        o[0] = (uint8_t)c;
+        o[1] = (uint8_t)(c >> 8);
+        o[2] = (uint8_t)(c >> 16);
+    }
+}
+
+/* the wave's edge pixels onto the list: one ballot, one atomic (every lane of the wave is here) */
+__device__ __forceinline__ void ss_mark_append(bool edge, uint32_t idx, uint32_t *list, unsigned long long *counters, uint32_t tid) {
+    const unsigned long long mask = __ballot(edge);
+    if (mask == 0ull) return; /* wave-uniform */
+    const uint32_t lane = tid & 63u;
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(counters, (unsigned long long)__builtin_popcountll(mask));
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
+    base = ((unsigned long long)hi << 32) | lo;
+    if (edge) {
+        const uint32_t rank = (uint32_t)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
+        list[base + rank] = idx; /* < 2^32: the domain */
+    }
+}
 
 /* The claim loop of one persistent wave.  Called by every lane of the wave, converged, AFTER the workgroup's last barrier: the
  * loop runs a different number of times per wave and holds none.  Each pass claims ppw entries with one atomic on the cursor
@@ -111,6 +187,27 @@ int bla_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, co
 int bla_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, uint32_t groups, hipStream_t stream);
 int scaled_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_map &map, const fr_kout &out, hipStream_t stream);
 int scaled_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, uint32_t groups, hipStream_t stream);
+
+/* What the two adaptive calls share on the host (fr_ss_adaptive.hip).  ss_refine_args: the edge list of `rows` rows from y0 of
+ * a width-wide output as a refine kernel takes it.  ss_refine_groups: the refine grid in workgroups — fr_debug_ss_adaptive_grid's
+ * when one is set, else every wave slot of the device, capped by the most work the rows can hold (every pixel an edge, ppw
+ * entries a claim, 4 waves a workgroup). */
+fr_ss_refine ss_refine_args(uint8_t *out, const uint32_t *list, unsigned long long *counters, uint32_t width, uint32_t y0, uint32_t s,
+                            uint32_t bpp);
+uint32_t ss_refine_groups(const fr_ss_refine &a, uint32_t rows);
+
+/* ADAPTIVE SUPERSAMPLED DE's road launches (fr_ss_adaptive_de.hip calls them) on cfg_s (`cfg` below), arguments already checked.
+ * *_de_render_map: the road's existing DE kernel over the probe's map — the siblings of de_render_rows / bla_de_render_rows
+ * (fr_de.h), which build their grid from (y0, y1); no profiling events.  *_de_ss_refine: `groups` workgroups of the road's DE
+ * refine kernel, for an escape-time algorithm; the orbit and the table are the context's, made by the probe. */
+int de_render_map(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const fr_ss_map &map, double *d_z, uint32_t *d_iters,
+                  double *d_der, hipStream_t stream);
+int de_ss_refine(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const fr_ss_refine &a, const fr_ss_de_shade &sh,
+                 uint32_t groups, hipStream_t stream);
+int bla_de_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_map &map, double *d_z, uint32_t *d_iters,
+                      double *d_der, hipStream_t stream);
+int bla_de_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, const fr_ss_de_shade &sh,
+                     uint32_t groups, hipStream_t stream);
 
 }  // namespace fr
 

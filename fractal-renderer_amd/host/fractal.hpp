@@ -481,6 +481,40 @@ inline void get_image_de_device(const Config &config, Scaled scaled, const fr_wi
     check(fr_render_rows_ss_de_pt_scaled_device(&config, &centre, scaled.bits, thickness, supersample, 0, config.height, channels, d_out,
                                                 static_cast<size_t>(channels) * config.width * config.height, d_work, work_len, hip_stream));
 }
+// ---- adaptive anti-aliased distance estimation (include/fractal_hip.h, "ADAPTIVE SUPERSAMPLED DE") -----------------------------
+// get_image_de's supersampled forms with an AdaptiveDe behind them: the distance-shaded supersample x supersample samples only at
+// EDGE pixels — those whose shaded probe differs from a neighbour's by more than `threshold` in some channel (-1: every pixel, the
+// supersampled DE render's bytes, for which that form is faster) and those whose probe lies closer to the set than `reach` output
+// pixels by its own distance estimate (0: the colour rule alone) — and the probe sample everywhere else.  *refined (may be null)
+// receives the number of edge pixels.  The F64 road, PT with a dd or a wide centre, and BLA-PT; one GPU.
+struct AdaptiveDe {
+    int threshold = 8;
+    double reach = 2.0;
+    uint64_t *refined = nullptr;
+};
+inline std::vector<RGB> get_image_ss_adaptive_de(const Config &config, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
+                                                 int road, int bits, double thickness, uint32_t supersample, AdaptiveDe adaptive) {
+    std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
+    check(fr_render_rows_ss_adaptive_de(&config, precision, pos_lo, centre, road, bits, thickness, supersample, adaptive.threshold,
+                                        adaptive.reach, 0, config.height, 3, reinterpret_cast<uint8_t *>(image.data()),
+                                        image.size() * sizeof(RGB), adaptive.refined));
+    return image;
+}
+// ... on the F64 road, or on PT with a dd centre (precision FR_PRECISION_PT; pos_lo may be null)
+inline std::vector<RGB> get_image_de(const Config &config, double thickness, int precision, const fr_imaginary *pos_lo, uint32_t supersample,
+                                     AdaptiveDe adaptive) {
+    return get_image_ss_adaptive_de(config, precision, pos_lo, nullptr, FR_PT_ROAD_PLAIN, 0, thickness, supersample, adaptive);
+}
+// ... on PT with a wide centre
+inline std::vector<RGB> get_image_de(const Config &config, const fr_wide_centre &centre, double thickness, uint32_t supersample,
+                                     AdaptiveDe adaptive) {
+    return get_image_ss_adaptive_de(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_PLAIN, 0, thickness, supersample, adaptive);
+}
+// ... on BLA-PT: a dd centre (config.pos, pos_lo; pos_lo may be null) or a wide centre, never both
+inline std::vector<RGB> get_image_de(const Config &config, Bla bla, double thickness, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
+                                     uint32_t supersample, AdaptiveDe adaptive) {
+    return get_image_ss_adaptive_de(config, FR_PRECISION_PT, pos_lo, centre, FR_PT_ROAD_BLA, bla.bits, thickness, supersample, adaptive);
+}
 // A DE view past 2^440 kept on the device is (z, iters, w, m, der), 56 bytes per pixel ("RESUMABLE SCALED DE"): the state render and
 // the extension that raises its cap in place, scaled derivative included.  The plain loop's (scaled.bits must be -1: the table
 // form has no state).  Recolour with colour_de_rows_device / colour_de_rows_ss_device on the view fr_de_scaled_view writes.

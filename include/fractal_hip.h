@@ -1448,6 +1448,57 @@ int fr_render_rows_ss_adaptive(const fr_config *cfg, int precision, const fr_ima
  * the rows can hold).  The output does not depend on it. */
 int fr_debug_ss_adaptive_grid(uint32_t workgroups);
 
+/* ADAPTIVE SUPERSAMPLED DE (fr_render_rows_ss_adaptive_de(_device) below): ADAPTIVE SUPERSAMPLING and SUPERSAMPLED DE combined.
+ * The adaptive call never looks at a non-edge pixel's interior samples; with distance estimation the probe KNOWS what it did not
+ * sample: its exterior distance D says how far the set is, and a pixel whose probe is closer to the set than a caller-chosen
+ * reach is refined whatever its neighbours look like.  DEFINITION, for supersample = s, 1 <= s <= FR_SS_MAX, a thickness T in
+ * output pixels, an integer threshold t, -1 <= t <= 255, and a reach R in output pixels:
+ *   cfg_s, (z, iters, der), Ts = T * (double)s and H are exactly those of SUPERSAMPLED DE: the road's DE render of cfg_s,
+ *            coloured and shaded by fr_colour_de_rows_device(cfg_s, ..., Ts, 3);
+ *   Dist(x, y) = D of "DE" for sample (x, y) of cfg_s: fr_distance_rows on cfg_s, in sample pixels, with the last factor
+ *            (double)(s * height) * min(|scale.re|, |scale.im|);
+ *   Rs     = R * (double)s, one f64 product;
+ *   p      = floor(s / 2); the probe colour is P(X, Y, c) = H(s*X + p, s*Y + p, c), the probe distance Dp(X, Y) =
+ *            Dist(s*X + p, s*Y + p), the probe index ip(X, Y) = iters(s*X + p, s*Y + p);
+ *   F      = the integer box filter of "supersampled rendering", as in ADAPTIVE SUPERSAMPLING;
+ *   near(X, Y) holds when ip(X, Y) < iterations and Dp(X, Y) < Rs: a capped probe is never near; an escaped probe with D = 0 (an
+ *            overflowed derivative) is near whenever Rs > 0; R = 0 makes near false everywhere;
+ *   edge(X, Y) holds when t < 0, or when ADAPTIVE SUPERSAMPLING's neighbour rule on P holds (8 neighbours inside the IMAGE, some
+ *            channel differing by more than t), or when near(X, Y) holds;
+ *   out(X, Y, c) = edge(X, Y) ? F(X, Y, c) : P(X, Y, c); with 4 channels alpha is 255;
+ *   refined = the number of edge pixels in rows [y0, y1).
+ * An algorithm without orbits gives black and refined = 0.  Consequences: t = -1 gives the bytes of fr_render_rows_ss_de for
+ * every R (it is slower than that call: use that call); t = 255 with R = 0 gives the probe image; R = 0 is the colour rule on the
+ * shaded bytes; s = 1 is the road's DE render followed by fr_colour_de_rows_device(cfg, ..., T, channels) for every t and R;
+ * T = 0 with R = 0 gives fr_render_rows_ss_adaptive's bytes and count on the same road; any split of [0, height) into row pieces
+ * gives the whole image's bytes and the same total refined (near reads the pixel's own probe only).
+ * Roads: fr_render_rows_ss_de_device's argument rule — FR_PRECISION_F64 (road FR_PT_ROAD_PLAIN, pos_lo NULL, centre NULL, bits
+ * 0) or FR_PRECISION_PT (road FR_PT_ROAD_PLAIN with bits 0, or FR_PT_ROAD_BLA with bits 0 or 24 .. 53 and D over the whole image
+ * of cfg_s; pos_lo or centre or neither, never both); FR_PT_ROAD_SCALED is refused by name, as are FR_PRECISION_F32 and
+ * FR_PRECISION_DD.
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message that names the argument, before any device work): ADAPTIVE SUPERSAMPLING's
+ * and SUPERSAMPLED DE's, plus reach finite with 0 <= R * s <= 2^20 and thickness finite with 0 <= T * s <= 2^20.  A work_len under
+ * the workspace size or a short out_len give FR_ERR_BUFFER_TOO_SMALL.  y0 == y1 is a no-op that needs no device and no buffer.
+ * Workspace: ONE size per row range, no banding.  With [ya, yb) = [max(y0 - 1, 0), min(y1 + 1, height)) and n = width * (yb - ya)
+ * it holds, every array 8-byte aligned and in this order, the probe's z (16 n bytes), der (16 n), iters (ceil8(4 n)) and colours
+ * (ceil8(3 n)), the edge list (ceil8(4 * width * (y1 - y0))) and two 64-bit counters:
+ *   bytes = 32 n + ceil8(4 n) + ceil8(3 n) + ceil8(4 * width * (y1 - y0)) + 16        (0 for an empty range or width 0).
+ * The device form is asynchronous on `hip_stream`: no host synchronisation (the PT roads: apart from computing and uploading the
+ * view's orbit and table when the context does not hold them yet, as their plain device calls do), no allocation, re-entrant;
+ * d_refined (device memory, may be NULL) receives the count as a uint64 behind the last kernel.  The host form uses the
+ * context's scratch; above the host roads' 256 MiB workspace cap it splits the range into row pieces itself.  With profiling on,
+ * fr_last_kernel_name reports the last kernel of the call (ss_refine_de_f64_kernel, ss_refine_de_pt_kernel or
+ * ss_refine_de_bla_kernel, or ss_mark_de_kernel when no refine pass runs) and fr_last_kernel_ms the span of the whole call.
+ * fr_debug_ss_adaptive_grid sets the grid of these refine kernels too. */
+int fr_ss_adaptive_de_workspace_bytes(const fr_config *cfg, uint32_t supersample, uint32_t y0, uint32_t y1, size_t *bytes);
+int fr_render_rows_ss_adaptive_de_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
+                                         int road, int bits, double thickness, uint32_t supersample, int threshold, double reach,
+                                         uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len, void *d_work, size_t work_len,
+                                         void *d_refined /* uint64 on the device, may be NULL */, void *hip_stream);
+int fr_render_rows_ss_adaptive_de(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
+                                  int bits, double thickness, uint32_t supersample, int threshold, double reach, uint32_t y0, uint32_t y1,
+                                  int channels, uint8_t *out, size_t out_len, uint64_t *refined /* may be NULL */);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* Exact sum of EXECUTED loop iterations over the pixels (x, y) with x % sx == 0, y % sy == 0 of
