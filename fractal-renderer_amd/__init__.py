@@ -45,6 +45,7 @@ __all__ = [
     "escape_rows_de_pt_scaled_state", "extend_rows_de_pt_scaled", "get_image_de_scaled_ss",
     "get_image_ss_adaptive", "ss_adaptive_workspace_bytes",
     "get_image_de_adaptive", "ss_adaptive_de_workspace_bytes",
+    "ss_transfer_tables",
 ]
 
 
@@ -341,9 +342,27 @@ def device_name():
 SS_MAX = 8  # FR_SS_MAX
 
 
-def _render_rows(config, y0, y1, channels, out, precision, opts, pos_lo, supersample, centre, bla, scaled=False):
+def _check_transfer(transfer):
+    """A `transfer` that reaches no _tf call (supersample = 1 on a road without one) is still the library's to refuse: an empty
+    fr_box_filter_rgb8_tf, which needs no device.  Returns it as an int."""
+    t = int(transfer)
+    if t != 0:
+        _native.check(_native.load().fr_box_filter_rgb8_tf(None, 0, 0, 1, t, 3, None, 0))
+    return t
+
+
+def ss_transfer_tables():
+    """fr_ss_transfer_tables: the library's own (L, T) of LINEAR-LIGHT SUPERSAMPLING (include/fractal_hip.h) as uint16 arrays —
+    L[v], v = 0 .. 255, a byte as linear light, and T[k - 1], k = 1 .. 255, the least linear value that encodes to k.  No device."""
+    dec, thr = C.POINTER(C.c_uint16)(), C.POINTER(C.c_uint16)()
+    _native.check(_native.load().fr_ss_transfer_tables(C.byref(dec), C.byref(thr)))
+    return np.array(dec[:256], dtype=np.uint16), np.array(thr[:255], dtype=np.uint16)
+
+
+def _render_rows(config, y0, y1, channels, out, precision, opts, pos_lo, supersample, centre, bla, scaled=False, transfer=0):
     """rows [y0, y1) into `out` as `channels` bytes per pixel, by the C row render of the arguments' family"""
     lib, cfg = _native.load(), C.byref(config)
+    transfer = _check_transfer(transfer)
     family, pre, _keep = _deep_call(precision, pos_lo, centre, bla, supersample, opts, scaled)
     o = C.byref(opts) if opts is not None else None
     tail = (y0, y1, channels, out.ctypes.data, out.nbytes)
@@ -354,7 +373,7 @@ def _render_rows(config, y0, y1, channels, out, precision, opts, pos_lo, supersa
     elif family == "wide":
         rc = lib.fr_render_rows_pt_wide(cfg, *pre, *tail)
     elif family == "ss":  # s x s samples per pixel, box-filtered on the device
-        rc = lib.fr_render_rows_ss(cfg, int(precision), *pre, int(supersample), *tail, o)
+        rc = lib.fr_render_rows_ss_tf(cfg, int(precision), *pre, int(supersample), transfer, *tail, o)
     elif family == "lo":
         rc = _render_rows_lo(precision)(cfg, *pre, *tail)
     elif channels == 4:
@@ -374,17 +393,21 @@ def ss_workspace_bytes(config, supersample, y0=0, y1=None):
     return mn.value, best.value
 
 
-def box_filter(image, s, channels=3):
-    """The box filter of the supersampled renders alone (fr_box_filter_rgb8): image uint8 [s*rows, s*width, 3] ->
+def box_filter(image, s, channels=3, transfer=0):
+    """The box filter of the supersampled renders alone (fr_box_filter_rgb8_tf): image uint8 [s*rows, s*width, 3] ->
     uint8 [rows, width, channels], each byte (sum of its s x s block + s*s // 2) // (s*s); channels=4 adds alpha 255.
-    E.g. to re-filter a large render the caller already holds."""
+    E.g. to re-filter a large render the caller already holds.
+    transfer = 1 (FR_SS_TRANSFER_SRGB; include/fractal_hip.h, "LINEAR-LIGHT SUPERSAMPLING"): the samples are averaged as linear
+    light — decoded by the table L, summed, divided the same way, encoded by the thresholds T (ss_transfer_tables) — so a thin
+    bright line keeps its light; 0 is the byte average; the library refuses any other value."""
     image = np.ascontiguousarray(image, dtype=np.uint8)
     s = int(s)
     if image.ndim != 3 or image.shape[2] != 3 or s < 1 or image.shape[0] % s or image.shape[1] % s:
         raise ValueError("image must be uint8 [s*rows, s*width, 3]")
     rows, width = image.shape[0] // s, image.shape[1] // s
     out = np.empty((rows, width, channels), dtype=np.uint8)
-    _native.check(_native.load().fr_box_filter_rgb8(image.ctypes.data, width, rows, s, channels, out.ctypes.data, out.nbytes))
+    _native.check(_native.load().fr_box_filter_rgb8_tf(image.ctypes.data, width, rows, s, int(transfer), channels, out.ctypes.data,
+                                                       out.nbytes))
     return out
 
 
@@ -405,12 +428,13 @@ def _ss_pt_road(pos_lo, centre, bla, scaled):
     return _native.FR_PT_ROAD_PLAIN, 0
 
 
-def get_image_ss_pt(config, supersample, pos_lo=None, centre=None, bla=None, scaled=False, y0=0, y1=None, channels=3, out=None):
+def get_image_ss_pt(config, supersample, pos_lo=None, centre=None, bla=None, scaled=False, y0=0, y1=None, channels=3, out=None,
+                    transfer=0):
     """Anti-aliased deep renders (fr_render_rows_ss_pt; include/fractal_hip.h, "supersampled rendering on the deep roads"):
     rows [y0, y1) of the Precision.PT image with supersample x supersample samples per pixel, box-filtered on the device, as
     uint8 [y1-y0, width, channels].  pos_lo, centre, bla and scaled select the road as they do in get_image_rows: plain PT
     (pos_lo or neither), WIDE PT (centre), BLA-PT (bla = 0 or 24 .. 53, with pos_lo or centre or neither), SCALED PT
-    (scaled=True, needs centre; combines with bla).  supersample = 1 is the road's plain render."""
+    (scaled=True, needs centre; combines with bla).  supersample = 1 is the road's plain render. transfer: see box_filter."""
     s = int(supersample)
     if not 1 <= s <= SS_MAX:
         raise ValueError("supersample is 1 .. %d" % SS_MAX)
@@ -422,19 +446,19 @@ def get_image_ss_pt(config, supersample, pos_lo=None, centre=None, bla=None, sca
         out = np.empty((max(y1 - y0, 0), config.width, int(channels)), dtype=np.uint8)
     lo = None if pos_lo is None else Imaginary(*(float(v) for v in pos_lo))
     st = None if centre is None else centre.c_struct()
-    _native.check(_native.load().fr_render_rows_ss_pt(C.byref(config), None if lo is None else C.byref(lo),
-                                                      None if st is None else C.byref(st), road, bits, s, y0, y1, int(channels),
-                                                      out.ctypes.data, out.nbytes))
+    _native.check(_native.load().fr_render_rows_ss_pt_tf(C.byref(config), None if lo is None else C.byref(lo),
+                                                         None if st is None else C.byref(st), road, bits, s, int(transfer), y0, y1,
+                                                         int(channels), out.ctypes.data, out.nbytes))
     return out
 
 
 def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None, pos_lo=None, supersample=1, centre=None,
-                   bla=None, scaled=False):
+                   bla=None, scaled=False, transfer=0):
     """Rows [y0, y1) of get_image — the unit of the reference's rayon loop (src/lib.rs:256-264).
     Returns uint8 [y1-y0, width, 3].  pos_lo (Precision.DD or Precision.PT only): the low halves (re, im) of the view
     centre (split_dd), so that the centre is pos + pos_lo; None = (0, 0).
     supersample = s > 1: s x s samples per pixel, box-filtered on the device (include/fractal_hip.h, "supersampled
-    rendering"); only the [y1-y0, width] result leaves the device.
+    rendering"); only the [y1-y0, width] result leaves the device.  transfer (0 or 1): see box_filter.
     centre (Precision.PT only, exclusive with pos_lo): a WideCentre in place of (config.pos, pos_lo) for views past a scale
     of 10^30 (include/fractal_hip.h, "WIDE PT").  supersample combines with neither centre, bla nor scaled here:
     anti-aliased deep renders on those roads are get_image_ss_pt's.
@@ -445,19 +469,20 @@ def get_image_rows(config, y0, y1, precision=Precision.F64, out=None, opts=None,
     "SCALED PT"); inside WIDE PT's domain it gives the same bytes as the call without it."""
     if out is None:
         out = np.empty((max(int(y1) - int(y0), 0), config.width, 3), dtype=np.uint8)
-    return _render_rows(config, y0, y1, 3, out, precision, opts, pos_lo, supersample, centre, bla, scaled)
+    return _render_rows(config, y0, y1, 3, out, precision, opts, pos_lo, supersample, centre, bla, scaled, transfer)
 
 
-def get_image(config, precision=Precision.F64, pos_lo=None, supersample=1, centre=None, bla=None, scaled=False):
+def get_image(config, precision=Precision.F64, pos_lo=None, supersample=1, centre=None, bla=None, scaled=False, transfer=0):
     """get_image(&Config) -> Vec<RGB> (src/lib.rs:253-270): uint8 [height, width, 3], row-major,
     bytes r,g,b.  Algo.BarnsleyFern is outside this path (random IFS, src/lib.rs:271-319): the
     per-pixel function returns BLACK for it (calc/src/lib.rs:211) and so does this.
-    pos_lo: see get_image_rows (Precision.DD or Precision.PT only).  supersample, centre, bla, scaled: see get_image_rows."""
+    pos_lo: see get_image_rows (Precision.DD or Precision.PT only).  supersample, centre, bla, scaled, transfer: see
+    get_image_rows."""
     out = np.empty((config.height, config.width, 3), dtype=np.uint8)
-    if not scaled and bla is None and centre is None and supersample == 1 and pos_lo is None and int(precision) == Precision.F64:
+    if transfer == 0 and not scaled and bla is None and centre is None and supersample == 1 and pos_lo is None and int(precision) == Precision.F64:
         _native.check(_native.load().fr_render_rgb8(C.byref(config), out.ctypes.data, out.nbytes))
         return out
-    return _render_rows(config, 0, config.height, 3, out, precision, None, pos_lo, supersample, centre, bla, scaled)
+    return _render_rows(config, 0, config.height, 3, out, precision, None, pos_lo, supersample, centre, bla, scaled, transfer)
 
 
 def _dd_only(precision):
@@ -483,13 +508,14 @@ def get_image_fern(config, threads=1, seed=0, walkers=0):
     return out
 
 
-def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None, supersample=1, centre=None, bla=None, scaled=False):
+def get_image_rgba(config, precision=Precision.F64, out=None, pos_lo=None, supersample=1, centre=None, bla=None, scaled=False,
+                   transfer=0):
     """get_image as RGBA8 (alpha 255): uint8 [height, width, 4] — the GUI's upload format
     (src/gui.rs:71-72) produced on the device.  pos_lo: see get_image_rows (Precision.DD or Precision.PT only).
-    supersample, centre, bla, scaled: see get_image_rows."""
+    supersample, centre, bla, scaled, transfer: see get_image_rows."""
     if out is None:
         out = np.empty((config.height, config.width, 4), dtype=np.uint8)
-    return _render_rows(config, 0, config.height, 4, out, precision, None, pos_lo, supersample, centre, bla, scaled)
+    return _render_rows(config, 0, config.height, 4, out, precision, None, pos_lo, supersample, centre, bla, scaled, transfer)
 
 
 def get_recursive_pixel(config, x, y, precision=Precision.F64):
@@ -691,11 +717,11 @@ def colour_rows_device(config, z_ptr, iters_ptr, n, out_ptr, channels=3, z_width
                                                        int(channels), out_ptr or None, int(channels) * n, _stream(stream)))
 
 
-def colour_rows_ss_device(config, z_ptr, iters_ptr, width, rows, supersample, out_ptr, channels=3, z_width=2, stream=None):
+def colour_rows_ss_device(config, z_ptr, iters_ptr, width, rows, supersample, out_ptr, channels=3, z_width=2, stream=None, transfer=0):
     """fr_colour_rows_ss_device: colour map + box filter in one kernel over a KEPT anti-aliased view — the stored results of
     supersample * rows rows of supersample * width samples in DEVICE memory (what the escape_rows*_device calls write for the
     config with width and height times supersample) — into channels * width * rows bytes at out_ptr, asynchronously on
-    `stream`.  The bytes are colour_rows_device's followed by the box filter's; no RGB workspace in between."""
+    `stream`.  The bytes are colour_rows_device's followed by the box filter's; no RGB workspace in between. transfer: see box_filter."""
     width, rows, s = int(width), int(rows), int(supersample)
     if not 1 <= s <= SS_MAX:
         raise ValueError("supersample is 1 .. %d" % SS_MAX)
@@ -703,15 +729,15 @@ def colour_rows_ss_device(config, z_ptr, iters_ptr, width, rows, supersample, ou
         raise ValueError("z_width is 2 or 4")
     if int(channels) not in (3, 4):
         raise ValueError("channels is 3 or 4")
-    _native.check(_native.load().fr_colour_rows_ss_device(C.byref(config), z_ptr or None, int(z_width), iters_ptr or None, width, rows,
-                                                          s, int(channels), out_ptr or None, int(channels) * width * rows,
-                                                          _stream(stream)))
+    _native.check(_native.load().fr_colour_rows_ss_tf_device(C.byref(config), z_ptr or None, int(z_width), iters_ptr or None, width, rows,
+                                                             s, int(transfer), int(channels), out_ptr or None,
+                                                             int(channels) * width * rows, _stream(stream)))
 
 
-def colour_image_ss(config, z, iters, supersample, channels=3):
+def colour_image_ss(config, z, iters, supersample, channels=3, transfer=0):
     """fr_colour_ss_rgb8 over numpy arrays: z float64 [s*rows, s*width, 2] (or [..., 4]: DD with its low parts, coloured on
     the hi parts) and iters uint32 [s*rows, s*width] -> uint8 [rows, width, channels], each pixel the box-filtered colours
-    of its s x s samples: box_filter(colour_image(config, z, iters), s), byte for byte."""
+    of its s x s samples: box_filter(colour_image(config, z, iters), s, transfer=transfer), byte for byte. transfer: see box_filter."""
     z = np.ascontiguousarray(z, dtype=np.float64)
     iters = np.ascontiguousarray(iters, dtype=np.uint32)
     s = int(supersample)
@@ -723,8 +749,8 @@ def colour_image_ss(config, z, iters, supersample, channels=3):
         raise ValueError("z must be [s*rows, s*width, 2 or 4] and iters [s*rows, s*width]")
     rows, width = iters.shape[0] // s, iters.shape[1] // s
     out = np.empty((rows, width, int(channels)), dtype=np.uint8)
-    _native.check(_native.load().fr_colour_ss_rgb8(C.byref(config), z.ctypes.data, z.shape[2], iters.ctypes.data, width, rows, s,
-                                                   int(channels), out.ctypes.data, out.nbytes))
+    _native.check(_native.load().fr_colour_ss_rgb8_tf(C.byref(config), z.ctypes.data, z.shape[2], iters.ctypes.data, width, rows, s,
+                                                      int(transfer), int(channels), out.ctypes.data, out.nbytes))
     return out
 
 
@@ -796,11 +822,14 @@ def auto_exposure(config, stats, percentile=0.99):
     return out.value
 
 
-def get_image_auto(config, percentile=0.99, precision=Precision.F64, pos_lo=None, centre=None, bla=None, scaled=False, supersample=1):
+def get_image_auto(config, percentile=0.99, precision=Precision.F64, pos_lo=None, centre=None, bla=None, scaled=False, supersample=1,
+                   transfer=0):
     """get_image at the exposure the view's own escape indices call for: (uint8 [height, width, 3], exposure).  escape_rows
     on the road the keywords select (of the supersample times larger config when supersample > 1), view_stats over the
     result, auto_exposure, then colour_image / colour_image_ss with config's clone carrying that exposure: the reference's
-    colour map, byte for byte the render of that clone.  config itself is left alone."""
+    colour map, byte for byte the render of that clone.  config itself is left alone.  transfer: see box_filter (the
+    statistics are the samples', whichever way they are averaged)."""
+    transfer = _check_transfer(transfer)
     s = int(supersample)
     if not 1 <= s <= SS_MAX:
         raise ValueError("supersample is 1 .. %d" % SS_MAX)
@@ -810,7 +839,7 @@ def get_image_auto(config, percentile=0.99, precision=Precision.F64, pos_lo=None
     exposure = auto_exposure(config, view_stats(big, z, it), percentile)
     shown = config.clone()
     shown.exposure = exposure
-    image = colour_image(shown, z, it) if s == 1 else colour_image_ss(shown, z, it, s)
+    image = colour_image(shown, z, it) if s == 1 else colour_image_ss(shown, z, it, s, transfer=transfer)
     return image, exposure
 
 
@@ -1002,15 +1031,17 @@ def de_scaled_view(config):
 
 
 def get_image_de(config, thickness=1.0, precision=Precision.F64, pos_lo=None, centre=None, bla=None, opts=None, supersample=1, y0=0,
-                 y1=None, channels=3, scaled=False):
+                 y1=None, channels=3, scaled=False, transfer=0):
     """get_image with distance shading: uint8 [height, width, 3].  escape_rows_de on the road the keywords select (bla=: DE ON
     BLA-PT), then colour_image_de: filaments thinner than a pixel stay visible as dark lines `thickness` pixels wide.
     supersample = s > 1, a row range y0= / y1= or channels=4: fr_render_rows_ss_de (include/fractal_hip.h, "SUPERSAMPLED DE") —
     rows [y0, y1) with s x s samples per pixel, each shaded with the thickness thickness * s in sample pixels (the line stays
     `thickness` OUTPUT pixels wide) and box-filtered on the device, uint8 [y1-y0, width, channels]; the s times larger DE arrays
-    exist only a band at a time.  supersample = 1 gives the bytes of the call without it.
+    exist only a band at a time.  supersample = 1 gives the bytes of the call without it.  transfer: see box_filter; the
+    shade stays on the sample's bytes, before the filter.
     scaled=True (needs centre=; combines with bla=): DE ON SCALED PT — escape_rows_de(..., scaled=True), then colour_image_de on
     de_scaled_view(config); the whole image at one sample per pixel and 3 channels only."""
+    transfer = _check_transfer(transfer)
     s = int(supersample)
     if not 1 <= s <= SS_MAX:
         raise ValueError("supersample is 1 .. %d" % SS_MAX)
@@ -1034,9 +1065,9 @@ def get_image_de(config, thickness=1.0, precision=Precision.F64, pos_lo=None, ce
     out = np.empty((max(y1 - y0, 0), config.width, int(channels)), dtype=np.uint8)
     lo = None if pos_lo is None else Imaginary(*(float(v) for v in pos_lo))
     st = None if centre is None else centre.c_struct()
-    _native.check(_native.load().fr_render_rows_ss_de(C.byref(config), int(precision), None if lo is None else C.byref(lo),
-                                                      None if st is None else C.byref(st), road, bits, float(thickness), s, y0, y1,
-                                                      int(channels), out.ctypes.data, out.nbytes))
+    _native.check(_native.load().fr_render_rows_ss_de_tf(C.byref(config), int(precision), None if lo is None else C.byref(lo),
+                                                         None if st is None else C.byref(st), road, bits, float(thickness), s, transfer,
+                                                         y0, y1, int(channels), out.ctypes.data, out.nbytes))
     return out
 
 
@@ -1073,11 +1104,11 @@ def extend_rows_de_pt_scaled(config, z, iters, w, m, der, from_iterations, centr
     return z, iters, w, m, der
 
 
-def get_image_de_scaled_ss(config, thickness, centre, supersample, bla=None, y0=0, y1=None, channels=3):
+def get_image_de_scaled_ss(config, thickness, centre, supersample, bla=None, y0=0, y1=None, channels=3, transfer=0):
     """fr_render_rows_ss_de_pt_scaled (include/fractal_hip.h, "SUPERSAMPLED SCALED DE"): rows [y0, y1) of the distance-shaded image
     past a scale of 2^440 with supersample x supersample samples per pixel — escape_rows_de(..., scaled=True) on the s times larger
     image a band at a time, shaded on its scaled view with thickness * s in sample pixels and box-filtered on the device — as uint8
-    [y1-y0, width, channels].  centre: a WideCentre, required; bla: None (the plain scaled loop), 0 or 24 .. 53."""
+    [y1-y0, width, channels].  centre: a WideCentre, required; bla: None (the plain scaled loop), 0 or 24 .. 53. transfer: see box_filter."""
     s = int(supersample)
     if not 1 <= s <= SS_MAX:
         raise ValueError("supersample is 1 .. %d" % SS_MAX)
@@ -1087,8 +1118,8 @@ def get_image_de_scaled_ss(config, thickness, centre, supersample, bla=None, y0=
     st = centre.c_struct()
     y0, y1 = _rows(config, y0, y1)
     out = np.empty((max(y1 - y0, 0), config.width, int(channels)), dtype=np.uint8)
-    _native.check(_native.load().fr_render_rows_ss_de_pt_scaled(C.byref(config), C.byref(st), bits, float(thickness), s, y0, y1,
-                                                                int(channels), out.ctypes.data, out.nbytes))
+    _native.check(_native.load().fr_render_rows_ss_de_pt_scaled_tf(C.byref(config), C.byref(st), bits, float(thickness), s, int(transfer),
+                                                                   y0, y1, int(channels), out.ctypes.data, out.nbytes))
     return out
 
 
@@ -1131,13 +1162,14 @@ def ss_adaptive_workspace_bytes(config, supersample, y0=0, y1=None):
 
 
 def get_image_ss_adaptive(config, supersample, threshold=8, precision=Precision.F64, pos_lo=None, centre=None, bla=None, scaled=False,
-                          y0=0, y1=None, channels=3, out=None):
+                          y0=0, y1=None, channels=3, out=None, transfer=0):
     """Adaptive supersampling (fr_render_rows_ss_adaptive; include/fractal_hip.h, "ADAPTIVE SUPERSAMPLING"): rows [y0, y1) with
     supersample x supersample samples only at EDGE pixels — those whose probe sample differs from a neighbour's by more than
     `threshold` (0 .. 255; -1: every pixel, the bytes of the supersampled render; 255: none, the probe image) in some channel —
     and the probe sample everywhere else.  Returns (image uint8 [y1-y0, width, channels], refined: the number of edge pixels).
     precision is Precision.F64 or Precision.PT; pos_lo, centre, bla and scaled select the deep road as in get_image_rows.  A
-    non-edge pixel's interior samples are never looked at: get_image_de is the tool for features thinner than a pixel."""
+    non-edge pixel's interior samples are never looked at: get_image_de is the tool for features thinner than a pixel.
+    transfer: see box_filter; it changes the filter of the edge pixels only — the probe and the edge rule stay on the bytes."""
     s = int(supersample)
     if not 1 <= s <= SS_MAX:
         raise ValueError("supersample is 1 .. %d" % SS_MAX)
@@ -1150,8 +1182,9 @@ def get_image_ss_adaptive(config, supersample, threshold=8, precision=Precision.
     if out is None:
         out = np.empty((max(y1 - y0, 0), config.width, int(channels)), dtype=np.uint8)
     refined = C.c_uint64(0)
-    _native.check(_native.load().fr_render_rows_ss_adaptive(C.byref(config), int(precision), lo, ptr, road, bits, s, int(threshold), y0, y1,
-                                                            int(channels), out.ctypes.data, out.nbytes, C.byref(refined)))
+    _native.check(_native.load().fr_render_rows_ss_adaptive_tf(C.byref(config), int(precision), lo, ptr, road, bits, s, int(transfer),
+                                                               int(threshold), y0, y1, int(channels), out.ctypes.data, out.nbytes,
+                                                               C.byref(refined)))
     return out, refined.value
 
 
@@ -1166,7 +1199,7 @@ def ss_adaptive_de_workspace_bytes(config, supersample, y0=0, y1=None):
 
 
 def get_image_de_adaptive(config, thickness=1.0, supersample=2, threshold=8, reach=2.0, precision=Precision.F64, pos_lo=None, centre=None,
-                          bla=None, y0=0, y1=None, channels=3, out=None):
+                          bla=None, y0=0, y1=None, channels=3, out=None, transfer=0):
     """Adaptive anti-aliased distance estimation (fr_render_rows_ss_adaptive_de; include/fractal_hip.h, "ADAPTIVE SUPERSAMPLED
     DE"): rows [y0, y1) of the distance-shaded image with supersample x supersample samples only at EDGE pixels — those whose
     shaded probe sample differs from a neighbour's by more than `threshold` in some channel (-1: every pixel, the bytes of
@@ -1174,7 +1207,7 @@ def get_image_de_adaptive(config, thickness=1.0, supersample=2, threshold=8, rea
     `reach` output pixels by its own distance estimate (0: the colour rule alone) — and the probe sample everywhere else.
     Returns (image uint8 [y1-y0, width, channels], refined: the number of edge pixels).  thickness is in output pixels.
     precision is Precision.F64 or Precision.PT; pos_lo, centre and bla select the deep road as in get_image_ss_adaptive; the
-    scaled road is not offered."""
+    scaled road is not offered.  transfer: see get_image_ss_adaptive."""
     s = int(supersample)
     if not 1 <= s <= SS_MAX:
         raise ValueError("supersample is 1 .. %d" % SS_MAX)
@@ -1187,17 +1220,17 @@ def get_image_de_adaptive(config, thickness=1.0, supersample=2, threshold=8, rea
     if out is None:
         out = np.empty((max(y1 - y0, 0), config.width, int(channels)), dtype=np.uint8)
     refined = C.c_uint64(0)
-    _native.check(_native.load().fr_render_rows_ss_adaptive_de(C.byref(config), int(precision), lo, ptr, road, bits, float(thickness), s,
-                                                               int(threshold), float(reach), y0, y1, int(channels), out.ctypes.data,
-                                                               out.nbytes, C.byref(refined)))
+    _native.check(_native.load().fr_render_rows_ss_adaptive_de_tf(C.byref(config), int(precision), lo, ptr, road, bits, float(thickness), s,
+                                                                  int(transfer), int(threshold), float(reach), y0, y1, int(channels),
+                                                                  out.ctypes.data, out.nbytes, C.byref(refined)))
     return out, refined.value
 
 
-def colour_image_de_ss(config, z, iters, der, supersample, thickness, channels=3):
+def colour_image_de_ss(config, z, iters, der, supersample, thickness, channels=3, transfer=0):
     """fr_colour_de_ss_rgb8 over numpy arrays: z, der float64 [s*rows, s*width, 2] and iters uint32 [s*rows, s*width] — a DE
     render of the config with width and height times s — -> uint8 [rows, width, channels]: box_filter(colour_image_de(config_s,
     z, iters, der, thickness * s), s), byte for byte.  config is the OUTPUT image's: config.height is the whole image's height
-    (the arrays may hold fewer rows), thickness is in output pixels."""
+    (the arrays may hold fewer rows), thickness is in output pixels. transfer: see box_filter."""
     z, iters, der = _de_arrays(z, iters, der)
     s = int(supersample)
     if not 1 <= s <= SS_MAX:
@@ -1208,25 +1241,26 @@ def colour_image_de_ss(config, z, iters, der, supersample, thickness, channels=3
         raise ValueError("z and der must be [s*rows, s*width, 2] and iters [s*rows, s*width]")
     rows, width = iters.shape[0] // s, iters.shape[1] // s
     out = np.empty((rows, width, int(channels)), dtype=np.uint8)
-    _native.check(_native.load().fr_colour_de_ss_rgb8(C.byref(config), z.ctypes.data, iters.ctypes.data, der.ctypes.data, width, rows, s,
-                                                      float(thickness), int(channels), out.ctypes.data, out.nbytes))
+    _native.check(_native.load().fr_colour_de_ss_rgb8_tf(C.byref(config), z.ctypes.data, iters.ctypes.data, der.ctypes.data, width, rows, s,
+                                                         int(transfer), float(thickness), int(channels), out.ctypes.data, out.nbytes))
     return out
 
 
-def colour_de_rows_ss_device(config, z_ptr, iters_ptr, der_ptr, width, rows, supersample, thickness, out_ptr, channels=3, stream=None):
+def colour_de_rows_ss_device(config, z_ptr, iters_ptr, der_ptr, width, rows, supersample, thickness, out_ptr, channels=3, stream=None,
+                             transfer=0):
     """fr_colour_de_rows_ss_device: colour map + distance shade + box filter in one kernel over a KEPT anti-aliased DE view — the
     (z, iters, der) of supersample * rows rows of supersample * width samples in DEVICE memory (what escape_rows_de_device
     writes for the config with width and height times supersample) — into channels * width * rows bytes at out_ptr,
     asynchronously on `stream`.  config is the output image's (config.height the whole image's height); thickness in output
-    pixels.  Thickness and exposure are a recolour: no orbit, no RGB image of the large view."""
+    pixels.  Thickness and exposure are a recolour: no orbit, no RGB image of the large view. transfer: see box_filter."""
     width, rows, s = int(width), int(rows), int(supersample)
     if not 1 <= s <= SS_MAX:
         raise ValueError("supersample is 1 .. %d" % SS_MAX)
     if int(channels) not in (3, 4):
         raise ValueError("channels is 3 or 4")
-    _native.check(_native.load().fr_colour_de_rows_ss_device(C.byref(config), z_ptr or None, iters_ptr or None, der_ptr or None, width,
-                                                             rows, s, float(thickness), int(channels), out_ptr or None,
-                                                             int(channels) * width * rows, _stream(stream)))
+    _native.check(_native.load().fr_colour_de_rows_ss_tf_device(C.byref(config), z_ptr or None, iters_ptr or None, der_ptr or None, width,
+                                                                rows, s, int(transfer), float(thickness), int(channels), out_ptr or None,
+                                                                int(channels) * width * rows, _stream(stream)))
 
 
 def count_iterations(config, y0=0, y1=None, sx=1, sy=1, precision=Precision.F64):

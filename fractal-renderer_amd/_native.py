@@ -548,6 +548,31 @@ PROTOTYPES = {
     "fr_debug_set_two_pass_capacity": (C.c_int, [C.c_uint32]),
 }
 
+# LINEAR-LIGHT SUPERSAMPLING: every _tf call is its twin with `int transfer` behind `supersample`, whose index is given here
+_TF_TWINS = {
+    "fr_box_filter_rgb8": 3, "fr_box_filter_rgb8_device": 3,
+    "fr_render_rows_ss": 3, "fr_render_rows_ss_device": 3,
+    "fr_render_rows_ss_pt": 5, "fr_render_rows_ss_pt_device": 5,
+    "fr_colour_rows_ss_device": 6, "fr_colour_ss_rgb8": 6,
+    "fr_colour_de_rows_ss_device": 6, "fr_colour_de_ss_rgb8": 6,
+    "fr_render_rows_ss_de": 7, "fr_render_rows_ss_de_device": 7,
+    "fr_render_rows_ss_de_pt_scaled": 4, "fr_render_rows_ss_de_pt_scaled_device": 4,
+    "fr_render_rows_ss_adaptive": 6, "fr_render_rows_ss_adaptive_device": 6,
+    "fr_render_rows_ss_adaptive_de": 7, "fr_render_rows_ss_adaptive_de_device": 7,
+}
+
+
+def tf_name(twin):
+    """fr_x -> fr_x_tf, fr_x_device -> fr_x_tf_device."""
+    return twin[:-len("_device")] + "_tf_device" if twin.endswith("_device") else twin + "_tf"
+
+
+for _twin, _k in _TF_TWINS.items():
+    _res, _args = PROTOTYPES[_twin]
+    assert _args[_k] is C.c_uint32
+    PROTOTYPES[tf_name(_twin)] = (_res, _args[:_k + 1] + [C.c_int] + _args[_k + 1:])
+PROTOTYPES["fr_ss_transfer_tables"] = (C.c_int, [C.POINTER(C.POINTER(C.c_uint16)), C.POINTER(C.POINTER(C.c_uint16))])
+
 _lib = None
 
 

@@ -20,6 +20,9 @@
 // with '=': a bare number after --adaptive is <width>; include/fractal_hip.h, "ADAPTIVE SUPERSAMPLING"; with --perturbation, --bla
 // and --scaled too, not with --distance-shade, --auto-exposure, --f32, --devices or -a fern; the refined share is printed unless
 // --quiet);
+// --linear-light beside --supersample above 1 (the N x N samples are averaged as linear light — decoded from sRGB, averaged and
+// encoded again, exactly — so a thin bright line keeps its light; include/fractal_hip.h, "LINEAR-LIGHT SUPERSAMPLING"; with
+// --adaptive, --perturbation, --bla, --scaled and --auto-exposure too);
 // --auto-exposure [P] (the exposure is chosen from the view's own escape indices: the one at which an escaped pixel at
 // percentile P of them, default 0.99, gets the full primary colour — include/fractal_hip.h, "statistics of a kept view"; a
 // following number within [0, 1] written with a '.' or an exponent is P (0.5, 1.0 — a bare 0 or 1 is a <width>), or write
@@ -91,6 +94,7 @@ int main(int argc, char **argv) {
     bool exposure_given = false, auto_exposure_on = false;
     std::optional<std::string> distance_shade;
     bool adaptive = false;
+    bool linear_light = false;
     int adaptive_t = 8;
     double auto_p = 0.99;
     int bla_bits = 0;
@@ -157,6 +161,7 @@ int main(int argc, char **argv) {
             if (end == a.c_str() + 11 || *end != '\0' || v < -1 || v > 255) die("--adaptive takes a threshold of -1 .. 255");
             adaptive_t = static_cast<int>(v);
         }
+        else if (a == "--linear-light") linear_light = true; // the samples are averaged as linear light
         else if (a == "--supersample") supersample_s = value(i, "--supersample"); // N x N samples per pixel, box-filtered on the device
         else if (a == "--devices") devices = value(i, "--devices");
         else if (a == "--threads") threads_s = value(i, "--threads");
@@ -195,6 +200,11 @@ int main(int argc, char **argv) {
         if (f32) die("--adaptive does not combine with --f32: adaptive supersampling is defined on the f64 road and on --perturbation");
         if (devices) die("--adaptive does not combine with --devices: adaptive supersampling runs on one device");
         if (algo == Algo::BarnsleyFern) die("--adaptive does not apply to -a fern");
+    }
+    if (linear_light) {
+        if (!supersample_s || to_u32(*supersample_s, "--supersample") <= 1)
+            die("--linear-light needs --supersample above 1: it chooses how the N x N samples are averaged");
+        if (algo == Algo::BarnsleyFern) die("--linear-light does not apply to -a fern");
     }
     if (distance_shade) {
         const uint32_t ss = supersample_s ? to_u32(*supersample_s, "--supersample") : 1;
@@ -250,6 +260,7 @@ int main(int argc, char **argv) {
             use_devices(list);
         }
         std::vector<RGB> image;
+        const Transfer tf = linear_light ? Transfer::Srgb : Transfer::Bytes;
         uint64_t refined = 0; // --adaptive: the number of edge pixels
         const auto t0 = std::chrono::steady_clock::now();
         if (algo == Algo::BarnsleyFern) {
@@ -284,9 +295,9 @@ int main(int argc, char **argv) {
                     if (scaled) check(fr_escape_rows_pt_scaled(&big, &wc, bla ? bla_bits : -1, 0, big.height, z, iters));
                     else if (bla) check(fr_escape_rows_pt_bla(&big, nullptr, &wc, bla_bits, 0, big.height, z, iters));
                     else check(fr_escape_rows_pt_wide(&big, &wc, 0, big.height, z, iters));
-                });
+                }, tf);
             } else {
-                image = get_image_auto(cfg, f32 ? FR_PRECISION_F32 : FR_PRECISION_F64, auto_p, ss, &chosen);
+                image = get_image_auto(cfg, f32 ? FR_PRECISION_F32 : FR_PRECISION_F64, auto_p, ss, &chosen, tf);
             }
             if (!quiet) std::printf("auto-exposure %.17g (percentile %g of the escape indices)\n", chosen, auto_p);
         } else if (perturbation) {
@@ -295,18 +306,18 @@ int main(int argc, char **argv) {
             if (adaptive) { // anti-aliased where the image has edges
                 const uint32_t ss = to_u32(*supersample_s, "--supersample");
                 const Adaptive ad{adaptive_t, &refined};
-                if (scaled) image = get_image(cfg, centre.c(), Scaled{bla ? bla_bits : -1}, ss, ad);
-                else image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}, ss, ad) : get_image(cfg, centre.c(), ss, ad);
+                if (scaled) image = get_image(cfg, centre.c(), Scaled{bla ? bla_bits : -1}, ss, ad, tf);
+                else image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}, ss, ad, tf) : get_image(cfg, centre.c(), ss, ad, tf);
             } else if (supersample_s) { // anti-aliased: the same road, N x N samples per pixel
                 const uint32_t ss = to_u32(*supersample_s, "--supersample");
-                if (scaled) image = get_image(cfg, centre.c(), Scaled{bla ? bla_bits : -1}, ss);
-                else image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}, ss) : get_image(cfg, centre.c(), ss);
+                if (scaled) image = get_image(cfg, centre.c(), Scaled{bla ? bla_bits : -1}, ss, tf);
+                else image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}, ss, tf) : get_image(cfg, centre.c(), ss, tf);
             } else if (scaled) image = get_image(cfg, centre.c(), Scaled{bla ? bla_bits : -1});
             else image = bla ? get_image(cfg, centre.c(), Bla{bla_bits}) : get_image(cfg, centre.c());
         } else {
             const int precision = f32 ? FR_PRECISION_F32 : FR_PRECISION_F64;
-            if (adaptive) image = get_image(cfg, precision, to_u32(*supersample_s, "--supersample"), Adaptive{adaptive_t, &refined});
-            else image = supersample_s ? get_image(cfg, precision, to_u32(*supersample_s, "--supersample")) : get_image(cfg, precision);
+            if (adaptive) image = get_image(cfg, precision, to_u32(*supersample_s, "--supersample"), Adaptive{adaptive_t, &refined}, tf);
+            else image = supersample_s ? get_image(cfg, precision, to_u32(*supersample_s, "--supersample"), tf) : get_image(cfg, precision);
         }
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         const std::string path = filename + ".ppm";  // the reference appends ".avif" (src/lib.rs:192-195)

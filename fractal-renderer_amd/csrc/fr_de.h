@@ -55,6 +55,6 @@ hipError_t fr_launch_colour_de_rows(const fr_kparams &p, const double *z, const 
  * same bytes as fr_launch_colour_de_rows followed by fr_launch_box_filter; s = 1 is the former.  64-bit element offsets. */
 hipError_t fr_launch_colour_de_filter(const fr_kparams &p, const double *z, const uint32_t *iters, const double *der, uint32_t width,
                                       uint64_t rows, uint32_t s, double pixels, double thickness, uint32_t bpp, void *dst,
-                                      hipStream_t stream);
+                                      hipStream_t stream, int transfer = 0 /* fr_ss_transfer: LINEAR-LIGHT SUPERSAMPLING */);
 
 #endif

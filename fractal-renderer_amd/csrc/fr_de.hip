@@ -213,17 +213,18 @@ __global__ __launch_bounds__(kDeThreads) void escape_pt_de_kernel(const fr_kpara
  * sample's c by coord_to_space on cfg_s — escape_de_kernel's de_stage operations on the same (x, y), hence the same bits — runs
  * escape_de_kernel's loop and colours and shades the sample as colour_de_rows_kernel does (fr_ss_de_sample.h).  The log2 table is
  * staged before the loop, which holds no barrier. */
-template <bool JULIA>
+template <bool JULIA, bool LINEAR>
 __global__ __launch_bounds__(kSsRefineThreads) void ss_refine_de_f64_kernel(const fr_kparams p, const fr_ss_refine a,
                                                                             const fr_ss_de_shade sh) {
     __shared__ double s_tab[FR_LOG2_N * 3];
     const double *gt = &g_log2_tab[0][0];
     for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    const uint16_t *const s_lt = ss_refine_tables<LINEAR>(); /* LINEAR-LIGHT SUPERSAMPLING: staged with the log2 table */
     __syncthreads();
     const double width = (double)p.width, height = (double)p.height;
     const double squared = p.limit * p.limit; /* :246 */
     const uint32_t iterations = p.iterations;
-    ss_refine_loop(a, [&](uint64_t x, uint64_t y) {
+    ss_refine_loop<LINEAR>(a, s_lt, [&](uint64_t x, uint64_t y) {
         double re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re + p.pos_re; /* de_stage<false> */
         double im = (((double)y / height) - 0.5) / p.scale_im + p.pos_im;
         const double cre = JULIA ? p.julia_re : re, cim = JULIA ? p.julia_im : im;
@@ -244,7 +245,7 @@ __global__ __launch_bounds__(kSsRefineThreads) void ss_refine_de_f64_kernel(cons
 }
 
 /* PT: `off` by de_stage<true>'s formula on cfg_s, then orbit_pt_de on the context's orbits */
-template <bool JULIA>
+template <bool JULIA, bool LINEAR>
 __global__ __launch_bounds__(kSsRefineThreads) void ss_refine_de_pt_kernel(const fr_kparams p, const fr_ss_refine a, const fr_ss_de_shade sh,
                                                                            const double2 *__restrict__ x_orbit,
                                                                            const double2 *__restrict__ k_orbit, const uint32_t x_last,
@@ -252,10 +253,11 @@ __global__ __launch_bounds__(kSsRefineThreads) void ss_refine_de_pt_kernel(const
     __shared__ double s_tab[FR_LOG2_N * 3];
     const double *gt = &g_log2_tab[0][0];
     for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    const uint16_t *const s_lt = ss_refine_tables<LINEAR>(); /* LINEAR-LIGHT SUPERSAMPLING: staged with the log2 table */
     __syncthreads();
     const double width = (double)p.width, height = (double)p.height;
     const double squared = p.limit * p.limit;
-    ss_refine_loop(a, [&](uint64_t x, uint64_t y) {
+    ss_refine_loop<LINEAR>(a, s_lt, [&](uint64_t x, uint64_t y) {
         const double off_re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
         const double off_im = (((double)y / height) - 0.5) / p.scale_im;
         double zr, zi, dr, di;
@@ -844,14 +846,19 @@ int de_ss_refine(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c,
         PtOrbitView v;
         const int rc = pt_orbit_view(ctx, cfg, c, keep, v);
         if (rc != FR_OK) return rc;
-        if (julia)
-            ss_refine_de_pt_kernel<true><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
-        else
-            ss_refine_de_pt_kernel<false><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
+        if (julia) {
+            if (a.linear) ss_refine_de_pt_kernel<true, true><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
+            else ss_refine_de_pt_kernel<true, false><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
+        } else {
+            if (a.linear) ss_refine_de_pt_kernel<false, true><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
+            else ss_refine_de_pt_kernel<false, false><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
+        }
     } else if (julia) {
-        ss_refine_de_f64_kernel<true><<<grid, block, 0, stream>>>(p, a, sh);
+        if (a.linear) ss_refine_de_f64_kernel<true, true><<<grid, block, 0, stream>>>(p, a, sh);
+        else ss_refine_de_f64_kernel<true, false><<<grid, block, 0, stream>>>(p, a, sh);
     } else {
-        ss_refine_de_f64_kernel<false><<<grid, block, 0, stream>>>(p, a, sh);
+        if (a.linear) ss_refine_de_f64_kernel<false, true><<<grid, block, 0, stream>>>(p, a, sh);
+        else ss_refine_de_f64_kernel<false, false><<<grid, block, 0, stream>>>(p, a, sh);
     }
     HIP_TRY(hipGetLastError());
     return FR_OK;

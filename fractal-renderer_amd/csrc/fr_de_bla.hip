@@ -202,16 +202,17 @@ __global__ __launch_bounds__(64 * kDeepWaves) void escape_bla_de_kernel(const fr
 /* ADAPTIVE SUPERSAMPLED DE's refine pass (include/fractal_hip.h; fr_ss_list.h: the claim loop; fr_de.hip: ss_refine_de_pt_kernel)
  * with orbit_bla_de: `off` by escape_bla_de_kernel's formula on cfg_s (`p`), the table `t` built with D over the whole image of
  * cfg_s */
-template <bool JULIA>
+template <bool JULIA, bool LINEAR>
 __global__ __launch_bounds__(kSsRefineThreads) void ss_refine_de_bla_kernel(const fr_kparams p, const fr_ss_refine a, const fr_ss_de_shade sh,
                                                                             const DeBlaDev t) {
     __shared__ double s_tab[FR_LOG2_N * 3];
     const double *gt = &g_log2_tab[0][0];
     for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    const uint16_t *const s_lt = ss_refine_tables<LINEAR>(); /* LINEAR-LIGHT SUPERSAMPLING: staged with the log2 table */
     __syncthreads();
     const double width = (double)p.width, height = (double)p.height;
     const double squared = p.limit * p.limit;
-    ss_refine_loop(a, [&](uint64_t x, uint64_t y) {
+    ss_refine_loop<LINEAR>(a, s_lt, [&](uint64_t x, uint64_t y) {
         const double off_re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
         const double off_im = (((double)y / height) - 0.5) / p.scale_im;
         double zr, zi, dr, di;
@@ -331,10 +332,13 @@ int bla_de_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, 
     if (rc != FR_OK) return rc;
     fr_kparams p;
     fill_params(cfg, default_opts(), p);
-    if (cfg->algo == FR_ALGO_JULIA)
-        ss_refine_de_bla_kernel<true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
-    else
-        ss_refine_de_bla_kernel<false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
+    if (cfg->algo == FR_ALGO_JULIA) {
+        if (a.linear) ss_refine_de_bla_kernel<true, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
+        else ss_refine_de_bla_kernel<true, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
+    } else {
+        if (a.linear) ss_refine_de_bla_kernel<false, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
+        else ss_refine_de_bla_kernel<false, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
+    }
     HIP_TRY(hipGetLastError());
     return FR_OK;
 }

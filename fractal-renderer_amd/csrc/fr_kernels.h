@@ -231,14 +231,15 @@ hipError_t fr_launch_colour_rows(const fr_kparams &p, const double *z, uint32_t 
  * output byte = (sum of its s x s block + floor(s*s / 2)) / (s*s).  s = 1 .. FR_SS_MAX; any alignment otherwise;
  * 64-bit byte offsets.  Device arrays. */
 hipError_t fr_launch_box_filter(const void *src, uint32_t width, uint64_t rows, uint32_t s, uint32_t bpp, void *dst,
-                                hipStream_t stream);
+                                hipStream_t stream, int transfer = 0 /* fr_ss_transfer: LINEAR-LIGHT SUPERSAMPLING */);
 
 /* Colour map + box filter over the stored results of the s times larger image (fr_ss.hip: colour_filter_kernel<s>): z
  * (z_width 2 or 4 doubles per sample, colour on the hi parts) and iters hold s * rows rows of s * width samples; dst as
  * fr_launch_box_filter's.  The same bytes as fr_launch_colour_rows followed by fr_launch_box_filter; s = 1 is the former.
  * 64-bit element offsets.  Device arrays. */
 hipError_t fr_launch_colour_filter(const fr_kparams &p, const double *z, uint32_t z_width, const uint32_t *iters, uint32_t width,
-                                   uint64_t rows, uint32_t s, uint32_t bpp, void *dst, hipStream_t stream);
+                                   uint64_t rows, uint32_t s, uint32_t bpp, void *dst, hipStream_t stream,
+                                   int transfer = 0 /* fr_ss_transfer */);
 
 /* Escape-index statistics of n stored results (fr_stats.hip: view_stats_range_kernel, view_stats_hist_kernel): the
  * fr_view_stats record of include/fractal_hip.h into the sizeof(struct fr_view_stats) bytes at `stats` (device, 8-byte aligned),

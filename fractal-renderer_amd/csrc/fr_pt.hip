@@ -204,7 +204,7 @@ hipError_t launch(const fr_kparams &p, int mode, const fr_kout &out, const doubl
 /* Persistent waves over the edge list of an adaptive render of cfg_s (`p` holds cfg_s): each lane computes its sample's `off`
  * by escape_pt_kernel's formula — the same operations on the same (x, y), hence the same bits — runs orbit_pt and colours
  * the f64 z as the render does.  The log2 table is staged before the loop, which holds no barrier. */
-template <bool JULIA>
+template <bool JULIA, bool LINEAR>
 __global__ __launch_bounds__(kSsRefineThreads) void ss_refine_pt_kernel(const fr_kparams p, const fr_ss_refine a,
                                                                         const double2 *__restrict__ x_orbit,
                                                                         const double2 *__restrict__ k_orbit, const uint32_t x_last,
@@ -212,10 +212,11 @@ __global__ __launch_bounds__(kSsRefineThreads) void ss_refine_pt_kernel(const fr
     __shared__ double s_tab[FR_LOG2_N * 3];
     const double *gt = &g_log2_tab[0][0];
     for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    const uint16_t *const s_lt = ss_refine_tables<LINEAR>(); /* LINEAR-LIGHT SUPERSAMPLING: staged with the log2 table */
     __syncthreads();
     const double width = (double)p.width, height = (double)p.height;
     const double squared = p.limit * p.limit;
-    ss_refine_loop(a, [&](uint64_t x, uint64_t y) {
+    ss_refine_loop<LINEAR>(a, s_lt, [&](uint64_t x, uint64_t y) {
         const double off_re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
         const double off_im = (((double)y / height) - 0.5) / p.scale_im;
         double zr, zi;
@@ -680,10 +681,13 @@ int pt_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, const fr_ss_re
     if (rc != FR_OK) return rc;
     fr_kparams p;
     fill_params(cfg, default_opts(), p);
-    if (cfg->algo == 2)
-        ss_refine_pt_kernel<true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, o->dev + o->k_offset, o->x_last, o->k_last);
-    else
-        ss_refine_pt_kernel<false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, o->dev, o->x_last, o->x_last);
+    if (cfg->algo == 2) {
+        if (a.linear) ss_refine_pt_kernel<true, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, o->dev + o->k_offset, o->x_last, o->k_last);
+        else ss_refine_pt_kernel<true, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, o->dev + o->k_offset, o->x_last, o->k_last);
+    } else {
+        if (a.linear) ss_refine_pt_kernel<false, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, o->dev, o->x_last, o->x_last);
+        else ss_refine_pt_kernel<false, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, o->dev, o->x_last, o->x_last);
+    }
     HIP_TRY(hipGetLastError());
     return FR_OK;
 }

@@ -500,15 +500,16 @@ hipError_t launch(bool julia, bool bla, const fr_kparams &p, int mode, const fr_
 
 /* ss_refine_pt_kernel (fr_pt.hip) with the scaled loops: `woff` by scaled_body's formula on cfg_s (`p` holds cfg_s with the
  * scaled divisors sre, sim), the loop chosen by BLA, the table built with Dw over the whole image of cfg_s */
-template <bool JULIA, bool BLA>
+template <bool JULIA, bool BLA, bool LINEAR>
 __global__ __launch_bounds__(kSsRefineThreads) void ss_refine_scaled_kernel(const fr_kparams p, const fr_ss_refine a, const ScaledDev t) {
     __shared__ double s_tab[FR_LOG2_N * 3];
     const double *gt = &g_log2_tab[0][0];
     for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    const uint16_t *const s_lt = ss_refine_tables<LINEAR>(); /* LINEAR-LIGHT SUPERSAMPLING: staged with the log2 table */
     __syncthreads();
     const double width = (double)p.width, height = (double)p.height;
     const double squared = p.limit * p.limit;
-    ss_refine_loop(a, [&](uint64_t x, uint64_t y) {
+    ss_refine_loop<LINEAR>(a, s_lt, [&](uint64_t x, uint64_t y) {
         const double woff_re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
         const double woff_im = (((double)y / height) - 0.5) / p.scale_im;
         double zr, zi;
@@ -682,11 +683,21 @@ int scaled_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, 
     const dim3 grid(groups), block(kSsRefineThreads);
     const bool julia = cfg->algo == 2;
     if (bits >= 0) {
-        if (julia) ss_refine_scaled_kernel<true, true><<<grid, block, 0, stream>>>(p, a, t);
-        else ss_refine_scaled_kernel<false, true><<<grid, block, 0, stream>>>(p, a, t);
+        if (julia) {
+            if (a.linear) ss_refine_scaled_kernel<true, true, true><<<grid, block, 0, stream>>>(p, a, t);
+            else ss_refine_scaled_kernel<true, true, false><<<grid, block, 0, stream>>>(p, a, t);
+        } else {
+            if (a.linear) ss_refine_scaled_kernel<false, true, true><<<grid, block, 0, stream>>>(p, a, t);
+            else ss_refine_scaled_kernel<false, true, false><<<grid, block, 0, stream>>>(p, a, t);
+        }
     } else {
-        if (julia) ss_refine_scaled_kernel<true, false><<<grid, block, 0, stream>>>(p, a, t);
-        else ss_refine_scaled_kernel<false, false><<<grid, block, 0, stream>>>(p, a, t);
+        if (julia) {
+            if (a.linear) ss_refine_scaled_kernel<true, false, true><<<grid, block, 0, stream>>>(p, a, t);
+            else ss_refine_scaled_kernel<true, false, false><<<grid, block, 0, stream>>>(p, a, t);
+        } else {
+            if (a.linear) ss_refine_scaled_kernel<false, false, true><<<grid, block, 0, stream>>>(p, a, t);
+            else ss_refine_scaled_kernel<false, false, false><<<grid, block, 0, stream>>>(p, a, t);
+        }
     }
     HIP_TRY(hipGetLastError());
     return FR_OK;

@@ -25,6 +25,9 @@ struct SsPlan {
  * the DE arrays (z, der, iters), which s = 1 needs too. */
 int ss_plan(const fr_config *cfg, uint32_t s, uint32_t y0, uint32_t y1, SsPlan &pl, uint32_t sample_bytes = 3);
 
+/* LINEAR-LIGHT SUPERSAMPLING: the `transfer` argument of every _tf call, refused before anything else is looked at */
+int check_transfer(int transfer);
+
 /* Source rows per band for a workspace of work_len >= min_bytes: the largest multiple of 8 * s that fits (or all the
  * rows), then evened out — nb = ceil(rows / Bmax) bands of ceil(rows / nb) rows rounded up to 8 * s. */
 uint64_t ss_band_rows(const SsPlan &pl, uint32_t s, size_t work_len);

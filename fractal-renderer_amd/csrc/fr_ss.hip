@@ -14,6 +14,10 @@
  *   - colour_filter_kernel / fr_launch_colour_filter and fr_colour_rows_ss_device / fr_colour_ss_rgb8: a KEPT anti-aliased
  *     view — (z, iters) of cfg_s in device memory — coloured and filtered in one kernel, no RGB workspace in between.
  *
+ * LINEAR-LIGHT SUPERSAMPLING (include/fractal_hip.h): every entry point here is a one-line forward to its _tf form, which holds
+ * the body and takes `transfer`; FR_SS_TRANSFER_SRGB launches the LINEAR instance of the filter (fr_srgb.h: the two tables in
+ * 1 KiB of LDS, a decode where the byte is read, three 22-bit sums, the same division, an eight-step bisection to encode).
+ *
  * Kernel shape (memory-bound: it reads 3*s*s bytes and writes 3 or 4 per output pixel; DESIGN.md, "Supersampling"):
  *   - a workgroup of 256 lanes produces a tile of 256 output pixels x `ro` output rows (ro = 4, 2, 1 for s <= 2, 3, >= 4:
  *     12 .. 49 KiB of source per workgroup);
@@ -39,6 +43,7 @@
 namespace {
 
 #include "fr_colour.h" /* the colour map of the renders: colour_filter_kernel's bytes are its bytes */
+#include "fr_srgb.h"   /* LINEAR-LIGHT SUPERSAMPLING: the tables of the filters' LINEAR instances */
 
 constexpr uint32_t kSsThreads = 256;                     /* lanes = output pixels per tile row */
 constexpr uint32_t kSsOutPitch = 3 * kSsThreads + 16;    /* LDS bytes per staged RGB output row (3 spare + padding) */
@@ -73,9 +78,19 @@ __device__ inline uint32_t ss_load_chunk(uint32_t idx, uint32_t total, uint32_t 
     return k * in_pitch + mis + head + 16u * c;
 }
 
+/* LINEAR (LINEAR-LIGHT SUPERSAMPLING) differs in phase 2 only: the two tables sit in 1 KiB of LDS behind the staged output rows
+ * (staged before phase 1's barrier), a sample's byte is decoded as it is read, the three sums (22 bits) have a register each and
+ * the quotient of the same division is encoded by srgb_encode.  The byte instance is the kernel as it was. */
+template <bool LINEAR>
 __global__ __launch_bounds__(kSsThreads) void box_filter_kernel(const ss_params p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const uint32_t tid = threadIdx.x;
+    const uint16_t *s_lt = nullptr;
+    if constexpr (LINEAR) { /* behind the source rows and the output rows (both multiples of 16 bytes) */
+        uint16_t *t = reinterpret_cast<uint16_t *>(lds + p.ro * p.s * ss_in_pitch(p.s) + p.ro * kSsOutPitch);
+        srgb_stage(t, tid, kSsThreads);
+        s_lt = t;
+    }
     const uint32_t ty = blockIdx.x / p.tiles_x, tx = blockIdx.x - ty * p.tiles_x;
     const uint32_t x0 = tx * kSsThreads;
     const uint32_t nx = min(kSsThreads, p.width - x0); /* output pixels of this tile's rows */
@@ -129,13 +144,23 @@ __global__ __launch_bounds__(kSsThreads) void box_filter_kernel(const ss_params 
                 const uint32_t mis = (uint32_t)(uintptr_t)(seg0 + (uint64_t)k * p.src_pitch) & 15u;
                 const uint8_t *q = lds + k * in_pitch + mis + 3u * s * tid;
                 for (uint32_t i = 0; i < s; i++) {
-                    sum[0] += q[3u * i];
-                    sum[1] += q[3u * i + 1u];
-                    sum[2] += q[3u * i + 2u];
+                    if constexpr (LINEAR) {
+                        sum[0] += srgb_decode(s_lt, q[3u * i]);
+                        sum[1] += srgb_decode(s_lt, q[3u * i + 1u]);
+                        sum[2] += srgb_decode(s_lt, q[3u * i + 2u]);
+                    } else {
+                        sum[0] += q[3u * i];
+                        sum[1] += q[3u * i + 1u];
+                        sum[2] += q[3u * i + 2u];
+                    }
                 }
             }
-            const uint32_t cr = __umulhi(2u * sum[0], p.magic), cg = __umulhi(2u * sum[1], p.magic),
-                           cb = __umulhi(2u * sum[2], p.magic);
+            uint32_t cr = __umulhi(2u * sum[0], p.magic), cg = __umulhi(2u * sum[1], p.magic), cb = __umulhi(2u * sum[2], p.magic);
+            if constexpr (LINEAR) {
+                cr = srgb_encode(s_lt, cr);
+                cg = srgb_encode(s_lt, cg);
+                cb = srgb_encode(s_lt, cb);
+            }
             if (p.bpp == 4) {
                 reinterpret_cast<uint32_t *>(drow)[tid] = cr | cg << 8 | cb << 16 | 0xFF000000u;
             } else {
@@ -247,7 +272,10 @@ __device__ __forceinline__ void cf_colour(const cf_sample &v, const double *s_ta
     s_px[v.at] = (uint32_t)rgb[0] | ((uint32_t)rgb[1] << 8) | ((uint32_t)rgb[2] << 16);
 }
 
-template <uint32_t S>
+/* LINEAR (LINEAR-LIGHT SUPERSAMPLING) differs in phase 2 only: the two tables are staged beside the log2 table (1 KiB more LDS), a
+ * sample's three bytes are decoded as its word is read, the sums (22 bits) have a register each, and the quotients are encoded
+ * by srgb_encode.  The byte instances are the kernel as it was. */
+template <uint32_t S, bool LINEAR>
 __global__ __launch_bounds__(kCfThreads) void colour_filter_kernel(const fr_kparams p, const cf_params q) {
     constexpr uint32_t RO = cf_tile_rows(S), SW = kCfTileW * S, N = SW * S * RO;
     constexpr uint32_t HALF = S * S / 2u, MAGIC = (uint32_t)(((1ull << 31) + S * S - 1u) / (S * S));
@@ -260,6 +288,12 @@ __global__ __launch_bounds__(kCfThreads) void colour_filter_kernel(const fr_kpar
     if (escape_algo && p.smooth) { /* uniform */
         const double *gt = &g_log2_tab[0][0];
         for (uint32_t k = tid; k < FR_LOG2_N * 3; k += kCfThreads) s_tab[k] = gt[k];
+    }
+    const uint16_t *s_lt = nullptr;
+    if constexpr (LINEAR) {
+        __shared__ uint16_t s_srgb[kSrgbLdsWords];
+        srgb_stage(s_srgb, tid, kCfThreads);
+        s_lt = s_srgb;
     }
     const uint32_t w = tid >> 6, l = tid & 63u; /* phase 2 and 3: output row of the tile, output pixel of the row */
     for (uint32_t tile = blockIdx.x; tile < q.n_tiles; tile += gridDim.x) {
@@ -290,11 +324,19 @@ __global__ __launch_bounds__(kCfThreads) void colour_filter_kernel(const fr_kpar
         uint8_t *drow = q.dst + ((uint64_t)(r0 + (w < nr ? w : 0u)) * q.width + x0) * q.bpp; /* the wave's output row */
         const uint32_t dmis = q.bpp == 4u ? 0u : (uint32_t)(uintptr_t)drow & 3u;
         if (live) {
-            uint32_t rb = HALF | HALF << 16, gg = HALF; /* r and b in the halves of one word: a sum is at most 64 * 255 + 32 */
+            [[maybe_unused]] uint32_t rb = HALF | HALF << 16, gg = HALF; /* r and b in the halves of one word: a sum is at most 64 * 255 + 32 */
+            [[maybe_unused]] uint32_t lr = HALF, lg = HALF, lb = HALF;   /* LINEAR: a sum is at most 64 * 65535 + 32 */
             if (escape_algo) {
                 for (uint32_t j = 0; j < S; j++) {
                     const uint32_t *row = s_px + (w * S + j) * SW + l * S;
-                    if constexpr (S % 4u == 0u) {
+                    if constexpr (LINEAR) {
+                        for (uint32_t i = 0; i < S; i++) {
+                            const uint32_t v = row[i];
+                            lr += srgb_decode(s_lt, v & 0xFFu);
+                            lg += srgb_decode(s_lt, v >> 8 & 0xFFu);
+                            lb += srgb_decode(s_lt, v >> 16);
+                        }
+                    } else if constexpr (S % 4u == 0u) {
                         for (uint32_t i = 0; i < S; i += 4u) {
                             const uint4 v = *reinterpret_cast<const uint4 *>(row + i);
                             rb += (v.x & 0x00FF00FFu) + (v.y & 0x00FF00FFu) + (v.z & 0x00FF00FFu) + (v.w & 0x00FF00FFu);
@@ -315,7 +357,14 @@ __global__ __launch_bounds__(kCfThreads) void colour_filter_kernel(const fr_kpar
                     }
                 }
             }
-            const uint32_t cr = __umulhi(2u * (rb & 0xFFFFu), MAGIC), cg = __umulhi(2u * gg, MAGIC), cb = __umulhi(2u * (rb >> 16), MAGIC);
+            uint32_t cr, cg, cb;
+            if constexpr (LINEAR) {
+                cr = srgb_encode(s_lt, __umulhi(2u * lr, MAGIC));
+                cg = srgb_encode(s_lt, __umulhi(2u * lg, MAGIC));
+                cb = srgb_encode(s_lt, __umulhi(2u * lb, MAGIC));
+            } else {
+                cr = __umulhi(2u * (rb & 0xFFFFu), MAGIC), cg = __umulhi(2u * gg, MAGIC), cb = __umulhi(2u * (rb >> 16), MAGIC);
+            }
             if (q.bpp == 4u) {
                 reinterpret_cast<uint32_t *>(drow)[l] = cr | cg << 8 | cb << 16 | 0xFF000000u;
             } else {
@@ -346,18 +395,20 @@ __global__ __launch_bounds__(kCfThreads) void colour_filter_kernel(const fr_kpar
 }
 
 template <uint32_t S>
-hipError_t cf_launch(const fr_kparams &p, const cf_params &q, hipStream_t stream) {
+hipError_t cf_launch(const fr_kparams &p, const cf_params &q, bool linear, hipStream_t stream) {
     const uint32_t groups = (q.n_tiles + cf_tiles_per_group(S) - 1u) / cf_tiles_per_group(S);
-    colour_filter_kernel<S><<<dim3(groups), dim3(kCfThreads), 0, stream>>>(p, q);
+    if (linear) colour_filter_kernel<S, true><<<dim3(groups), dim3(kCfThreads), 0, stream>>>(p, q);
+    else colour_filter_kernel<S, false><<<dim3(groups), dim3(kCfThreads), 0, stream>>>(p, q);
     return hipGetLastError();
 }
 
 }  // namespace
 
 hipError_t fr_launch_box_filter(const void *src, uint32_t width, uint64_t rows, uint32_t s, uint32_t bpp, void *dst,
-                                hipStream_t stream) {
+                                hipStream_t stream, int transfer) {
     if (width == 0 || rows == 0) return hipSuccess;
     if (s < 1 || s > FR_SS_MAX || (bpp != 3 && bpp != 4)) return hipErrorInvalidValue;
+    const bool linear = transfer == FR_SS_TRANSFER_SRGB;
     ss_params p;
     p.src_pitch = (uint64_t)3u * s * width;
     p.width = width;
@@ -367,7 +418,9 @@ hipError_t fr_launch_box_filter(const void *src, uint32_t width, uint64_t rows, 
     p.bpp = bpp;
     p.half = s * s / 2u;
     p.magic = (uint32_t)(((1ull << 31) + s * s - 1u) / (s * s));
-    const size_t lds_bytes = (size_t)p.ro * s * ss_in_pitch(s) + (bpp == 3 ? (size_t)p.ro * kSsOutPitch : 0u);
+    /* LINEAR: the output rows' place is kept for either bpp and the two tables lie behind it (51 216 bytes at s = 8) */
+    const size_t lds_bytes = linear ? (size_t)p.ro * s * ss_in_pitch(s) + (size_t)p.ro * kSsOutPitch + kSrgbLdsWords * sizeof(uint16_t)
+                                    : (size_t)p.ro * s * ss_in_pitch(s) + (bpp == 3 ? (size_t)p.ro * kSsOutPitch : 0u);
     /* launches of at most 2^30 workgroups (whole tile rows) */
     const uint64_t rows_per_launch = std::max<uint64_t>(1, (1ull << 30) / p.tiles_x) * p.ro;
     for (uint64_t ra = 0; ra < rows; ra += rows_per_launch) {
@@ -377,7 +430,8 @@ hipError_t fr_launch_box_filter(const void *src, uint32_t width, uint64_t rows, 
         p.dst = static_cast<uint8_t *>(dst) + ra * width * bpp;
         p.rows = (uint32_t)n;
         const uint64_t tiles = (uint64_t)p.tiles_x * ((n + p.ro - 1) / p.ro);
-        box_filter_kernel<<<dim3((uint32_t)tiles), dim3(kSsThreads), lds_bytes, stream>>>(p);
+        if (linear) box_filter_kernel<true><<<dim3((uint32_t)tiles), dim3(kSsThreads), lds_bytes, stream>>>(p);
+        else box_filter_kernel<false><<<dim3((uint32_t)tiles), dim3(kSsThreads), lds_bytes, stream>>>(p);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -385,9 +439,10 @@ hipError_t fr_launch_box_filter(const void *src, uint32_t width, uint64_t rows, 
 }
 
 hipError_t fr_launch_colour_filter(const fr_kparams &p, const double *z, uint32_t z_width, const uint32_t *iters, uint32_t width,
-                                   uint64_t rows, uint32_t s, uint32_t bpp, void *dst, hipStream_t stream) {
+                                   uint64_t rows, uint32_t s, uint32_t bpp, void *dst, hipStream_t stream, int transfer) {
     if (width == 0 || rows == 0) return hipSuccess;
     if (s < 1 || s > FR_SS_MAX || (bpp != 3 && bpp != 4) || (z_width != 2 && z_width != 4)) return hipErrorInvalidValue;
+    const bool linear = transfer == FR_SS_TRANSFER_SRGB;
     if (s == 1) return fr_launch_colour_rows(p, z, z_width, iters, (size_t)width * rows, bpp, dst, stream); /* nothing to filter */
     cf_params q;
     q.pitch = (uint64_t)s * width;
@@ -408,13 +463,13 @@ hipError_t fr_launch_colour_filter(const fr_kparams &p, const double *z, uint32_
         q.n_tiles = (uint32_t)(q.tiles_x * ((n + ro - 1) / ro));
         hipError_t e;
         switch (s) {
-        case 2: e = cf_launch<2>(p, q, stream); break;
-        case 3: e = cf_launch<3>(p, q, stream); break;
-        case 4: e = cf_launch<4>(p, q, stream); break;
-        case 5: e = cf_launch<5>(p, q, stream); break;
-        case 6: e = cf_launch<6>(p, q, stream); break;
-        case 7: e = cf_launch<7>(p, q, stream); break;
-        default: e = cf_launch<8>(p, q, stream); break;
+        case 2: e = cf_launch<2>(p, q, linear, stream); break;
+        case 3: e = cf_launch<3>(p, q, linear, stream); break;
+        case 4: e = cf_launch<4>(p, q, linear, stream); break;
+        case 5: e = cf_launch<5>(p, q, linear, stream); break;
+        case 6: e = cf_launch<6>(p, q, linear, stream); break;
+        case 7: e = cf_launch<7>(p, q, linear, stream); break;
+        default: e = cf_launch<8>(p, q, linear, stream); break;
         }
         if (e != hipSuccess) return e;
     }
@@ -422,6 +477,12 @@ hipError_t fr_launch_colour_filter(const fr_kparams &p, const double *z, uint32_
 }
 
 namespace fr {
+
+int check_transfer(int transfer) {
+    if (transfer != FR_SS_TRANSFER_BYTES && transfer != FR_SS_TRANSFER_SRGB)
+        return fail(FR_ERR_INVALID_ARGUMENT, "transfer must be FR_SS_TRANSFER_BYTES (0) or FR_SS_TRANSFER_SRGB (1)");
+    return FR_OK;
+}
 
 /* the part of the domain that needs no precision: cfg, s, the sizes, the rows (fr_ss.h) */
 int ss_plan(const fr_config *cfg, uint32_t s, uint32_t y0, uint32_t y1, SsPlan &pl, uint32_t sample_bytes) {
@@ -469,7 +530,7 @@ namespace {
  * behind the last band (-1 none).  Arguments already checked, s >= 2, the range and the width not empty.  No host
  * synchronisation beyond what the band's launch has. */
 template <class Band>
-int render_ss_bands(Ctx &ctx, const SsPlan &pl, uint32_t s, uint32_t y0, unsigned bpp, void *d_out, void *d_work, size_t work_len,
+int render_ss_bands(Ctx &ctx, const SsPlan &pl, uint32_t s, int transfer, uint32_t y0, unsigned bpp, void *d_out, void *d_work, size_t work_len,
                     hipStream_t stream, int pending_sample, Band &&band) {
     const uint32_t width = pl.cfg_s.width / s;
     const uint64_t rows = ss_band_rows(pl, s, work_len);
@@ -491,7 +552,7 @@ int render_ss_bands(Ctx &ctx, const SsPlan &pl, uint32_t s, uint32_t y0, unsigne
         if (rc != FR_OK) break;
         pr.enabled = false;
         uint8_t *dst = static_cast<uint8_t *>(d_out) + (uint64_t)(((uint32_t)ya - Y0) / s) * width * bpp;
-        const hipError_t e = fr_launch_box_filter(d_work, width, (yb - (uint32_t)ya) / s, s, bpp, dst, stream);
+        const hipError_t e = fr_launch_box_filter(d_work, width, (yb - (uint32_t)ya) / s, s, bpp, dst, stream, transfer);
         if (e != hipSuccess) rc = fail_hip(e, "fr_launch_box_filter");
     }
     ctx.post_sample(pending_sample, stream); /* behind the last band */
@@ -500,7 +561,7 @@ int render_ss_bands(Ctx &ctx, const SsPlan &pl, uint32_t s, uint32_t y0, unsigne
 }
 
 /* the bands of fr_render_rows_ss(_device): the precision's own row render */
-int render_ss_device(Ctx &ctx, const SsPlan &pl, int precision, const fr_imaginary *pos_lo, uint32_t s, uint32_t y0,
+int render_ss_device(Ctx &ctx, const SsPlan &pl, int precision, const fr_imaginary *pos_lo, uint32_t s, int transfer, uint32_t y0,
                      unsigned bpp, void *d_out, void *d_work, size_t work_len, hipStream_t stream, const Opts &o) {
     const fr_config *cs = &pl.cfg_s;
     const bool deep = precision == FR_PRECISION_DD || precision == FR_PRECISION_PT;
@@ -509,7 +570,7 @@ int render_ss_device(Ctx &ctx, const SsPlan &pl, int precision, const fr_imagina
         decide_kernel(ctx, cs, precision, s * y0, (uint32_t)(s * y0 + pl.src_rows), ob, stream, true);
     const int pending_sample = ob.pending_sample;
     ob.pending_sample = -1;
-    return render_ss_bands(ctx, pl, s, y0, bpp, d_out, d_work, work_len, stream, pending_sample,
+    return render_ss_bands(ctx, pl, s, transfer, y0, bpp, d_out, d_work, work_len, stream, pending_sample,
                            [&](Ctx &c, uint32_t ya, uint32_t yb, const fr_kout &ko, hipStream_t st) {
                                if (deep) return render_deep_device(c, precision, cs, Centre{pos_lo, nullptr}, o, ya, yb, 3, ko.rgb, st);
                                fr_kparams p;
@@ -586,10 +647,10 @@ int ss_road_check(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wid
 
 /* rows [y0, y1) of cfg on the road into ko.rgb: s = 1 the road's plain render, byte for byte; else its bands of cfg_s through
  * the workspace, each filtered into place */
-int ss_road_rows(Ctx &ctx, const SsRoad &r, const fr_config *cfg, uint32_t s, uint32_t y0, uint32_t y1, unsigned bpp, const fr_kout &ko,
+int ss_road_rows(Ctx &ctx, const SsRoad &r, const fr_config *cfg, uint32_t s, int transfer, uint32_t y0, uint32_t y1, unsigned bpp, const fr_kout &ko,
                  void *d_work, size_t work_len, hipStream_t stream) {
     if (s == 1) return r.rows(ctx, cfg, y0, y1, bpp, ko, stream);
-    return render_ss_bands(ctx, r.pl, s, y0, bpp, ko.rgb, d_work, work_len, stream, -1,
+    return render_ss_bands(ctx, r.pl, s, transfer, y0, bpp, ko.rgb, d_work, work_len, stream, -1,
                            [&](Ctx &c, uint32_t ya, uint32_t yb, const fr_kout &band, hipStream_t st) {
                                return r.rows(c, &r.pl.cfg_s, ya, yb, 3, band, st);
                            });
@@ -609,6 +670,14 @@ using namespace fr;
 
 extern "C" {
 
+int fr_ss_transfer_tables(fr_ss_table *decode256, fr_ss_table *thresholds255) {
+    static const uint16_t decode[256] = FR_SRGB_DECODE_INIT;
+    static const uint16_t thresholds[255] = FR_SRGB_THRESHOLD_INIT;
+    if (decode256) *decode256 = decode;
+    if (thresholds255) *thresholds255 = thresholds;
+    return FR_OK;
+}
+
 int fr_ss_workspace_bytes(const fr_config *cfg, uint32_t supersample, uint32_t y0, uint32_t y1, size_t *min_bytes,
                           size_t *best_bytes) {
     SsPlan pl;
@@ -619,9 +688,10 @@ int fr_ss_workspace_bytes(const fr_config *cfg, uint32_t supersample, uint32_t y
     return FR_OK;
 }
 
-int fr_render_rows_ss_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t supersample,
+int fr_render_rows_ss_tf_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t supersample, int transfer,
                              uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len, void *d_work,
                              size_t work_len, void *hip_stream, const fr_render_opts *opts) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsPlan pl;
     Opts o;
     int rc = ss_check(cfg, precision, pos_lo, supersample, y0, y1, channels, opts, pl, o);
@@ -645,12 +715,19 @@ int fr_render_rows_ss_device(const fr_config *cfg, int precision, const fr_imagi
             rows_params(cfg, o, y0, y1, (unsigned)channels, p);
             return render_device(ctx, cfg, p, precision, o, d_out, stream);
         }
-        return render_ss_device(ctx, pl, precision, pos_lo, supersample, y0, (unsigned)channels, d_out, d_work, work_len, stream, o);
+        return render_ss_device(ctx, pl, precision, pos_lo, supersample, transfer, y0, (unsigned)channels, d_out, d_work, work_len, stream, o);
     });
 }
 
-int fr_render_rows_ss(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t supersample, uint32_t y0,
+int fr_render_rows_ss_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t supersample,
+                             uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len, void *d_work,
+                             size_t work_len, void *hip_stream, const fr_render_opts *opts) {
+    return fr_render_rows_ss_tf_device(cfg, precision, pos_lo, supersample, FR_SS_TRANSFER_BYTES, y0, y1, channels, d_out, out_len, d_work, work_len, hip_stream, opts);
+}
+
+int fr_render_rows_ss_tf(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t supersample, int transfer, uint32_t y0,
                       uint32_t y1, int channels, uint8_t *out, size_t out_len, const fr_render_opts *opts) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsPlan pl;
     Opts o;
     int rc = ss_check(cfg, precision, pos_lo, supersample, y0, y1, channels, opts, pl, o);
@@ -668,14 +745,20 @@ int fr_render_rows_ss(const fr_config *cfg, int precision, const fr_imaginary *p
     return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) {
         int rc = ctx.reserve(ctx.ss_work, work_len);
         if (rc != FR_OK) return rc;
-        rc = render_ss_device(ctx, pl, precision, pos_lo, supersample, y0, (unsigned)channels, d_out, ctx.ss_work.ptr, work_len, stream, o);
+        rc = render_ss_device(ctx, pl, precision, pos_lo, supersample, transfer, y0, (unsigned)channels, d_out, ctx.ss_work.ptr, work_len, stream, o);
         if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
         return rc;
     });
 }
 
-int fr_box_filter_rgb8_device(const void *d_src, uint32_t width, uint32_t rows, uint32_t supersample, int channels,
+int fr_render_rows_ss(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t supersample, uint32_t y0,
+                      uint32_t y1, int channels, uint8_t *out, size_t out_len, const fr_render_opts *opts) {
+    return fr_render_rows_ss_tf(cfg, precision, pos_lo, supersample, FR_SS_TRANSFER_BYTES, y0, y1, channels, out, out_len, opts);
+}
+
+int fr_box_filter_rgb8_tf_device(const void *d_src, uint32_t width, uint32_t rows, uint32_t supersample, int transfer, int channels,
                               void *d_out, size_t out_len, void *hip_stream) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     const int rc = box_filter_check(width, rows, supersample, channels);
     if (rc != FR_OK) return rc;
     const size_t need = (size_t)channels * width * (size_t)rows;
@@ -684,12 +767,18 @@ int fr_box_filter_rgb8_device(const void *d_src, uint32_t width, uint32_t rows, 
     if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*rows");
     if (channels == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u))
         return fail(FR_ERR_INVALID_ARGUMENT, "RGBA8 output (d_out) must be 4-byte aligned");
-    HIP_TRY(fr_launch_box_filter(d_src, width, rows, supersample, (uint32_t)channels, d_out, static_cast<hipStream_t>(hip_stream)));
+    HIP_TRY(fr_launch_box_filter(d_src, width, rows, supersample, (uint32_t)channels, d_out, static_cast<hipStream_t>(hip_stream), transfer));
     return FR_OK;
 }
 
-int fr_box_filter_rgb8(const uint8_t *src, uint32_t width, uint32_t rows, uint32_t supersample, int channels, uint8_t *out,
+int fr_box_filter_rgb8_device(const void *d_src, uint32_t width, uint32_t rows, uint32_t supersample, int channels,
+                              void *d_out, size_t out_len, void *hip_stream) {
+    return fr_box_filter_rgb8_tf_device(d_src, width, rows, supersample, FR_SS_TRANSFER_BYTES, channels, d_out, out_len, hip_stream);
+}
+
+int fr_box_filter_rgb8_tf(const uint8_t *src, uint32_t width, uint32_t rows, uint32_t supersample, int transfer, int channels, uint8_t *out,
                        size_t out_len) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     int rc = box_filter_check(width, rows, supersample, channels);
     if (rc != FR_OK) return rc;
     const size_t need = (size_t)channels * width * (size_t)rows;
@@ -706,15 +795,21 @@ int fr_box_filter_rgb8(const uint8_t *src, uint32_t width, uint32_t rows, uint32
     if (rc == FR_OK) rc = ctx->reserve(ctx->rgb, need);
     if (rc != FR_OK) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->ss_work.ptr, src, src_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(fr_launch_box_filter(ctx->ss_work.ptr, width, rows, supersample, (uint32_t)channels, ctx->rgb.ptr, ctx->stream));
+    HIP_TRY(fr_launch_box_filter(ctx->ss_work.ptr, width, rows, supersample, (uint32_t)channels, ctx->rgb.ptr, ctx->stream, transfer));
     HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FR_OK;
 }
 
-int fr_render_rows_ss_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
-                                uint32_t supersample, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len,
+int fr_box_filter_rgb8(const uint8_t *src, uint32_t width, uint32_t rows, uint32_t supersample, int channels, uint8_t *out,
+                       size_t out_len) {
+    return fr_box_filter_rgb8_tf(src, width, rows, supersample, FR_SS_TRANSFER_BYTES, channels, out, out_len);
+}
+
+int fr_render_rows_ss_pt_tf_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                                uint32_t supersample, int transfer, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len,
                                 void *d_work, size_t work_len, void *hip_stream) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsRoad r;
     const int rc = ss_road_check(cfg, pos_lo, centre, road, bits, supersample, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
@@ -723,12 +818,19 @@ int fr_render_rows_ss_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo
         if (!d_work) return fail(FR_ERR_INVALID_ARGUMENT, "d_work is NULL");
     }
     return rgb_rows_device(cfg, y0, y1, channels, d_out, out_len, hip_stream, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
-        return ss_road_rows(ctx, r, cfg, supersample, y0, y1, (unsigned)channels, ko, d_work, work_len, stream);
+        return ss_road_rows(ctx, r, cfg, supersample, transfer, y0, y1, (unsigned)channels, ko, d_work, work_len, stream);
     });
 }
 
-int fr_render_rows_ss_pt(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
-                         uint32_t supersample, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len) {
+int fr_render_rows_ss_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                                uint32_t supersample, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len,
+                                void *d_work, size_t work_len, void *hip_stream) {
+    return fr_render_rows_ss_pt_tf_device(cfg, pos_lo, centre, road, bits, supersample, FR_SS_TRANSFER_BYTES, y0, y1, channels, d_out, out_len, d_work, work_len, hip_stream);
+}
+
+int fr_render_rows_ss_pt_tf(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                         uint32_t supersample, int transfer, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsRoad r;
     const int rc = ss_road_check(cfg, pos_lo, centre, road, bits, supersample, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
@@ -736,14 +838,20 @@ int fr_render_rows_ss_pt(const fr_config *cfg, const fr_imaginary *pos_lo, const
     return rgb_rows_host(cfg, y0, y1, channels, out, out_len, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
         int rc = ctx.reserve(ctx.ss_work, work_len);
         if (rc != FR_OK) return rc;
-        rc = ss_road_rows(ctx, r, cfg, supersample, y0, y1, (unsigned)channels, ko, ctx.ss_work.ptr, work_len, stream);
+        rc = ss_road_rows(ctx, r, cfg, supersample, transfer, y0, y1, (unsigned)channels, ko, ctx.ss_work.ptr, work_len, stream);
         if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
         return rc;
     });
 }
 
-int fr_colour_rows_ss_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, uint32_t width, uint32_t rows,
-                             uint32_t supersample, int channels, void *d_out, size_t out_len, void *hip_stream) {
+int fr_render_rows_ss_pt(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                         uint32_t supersample, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len) {
+    return fr_render_rows_ss_pt_tf(cfg, pos_lo, centre, road, bits, supersample, FR_SS_TRANSFER_BYTES, y0, y1, channels, out, out_len);
+}
+
+int fr_colour_rows_ss_tf_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, uint32_t width, uint32_t rows,
+                             uint32_t supersample, int transfer, int channels, void *d_out, size_t out_len, void *hip_stream) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     const int rc = colour_ss_check(cfg, z_width, width, rows, supersample, channels);
     if (rc != FR_OK) return rc;
     const size_t need = (size_t)channels * width * (size_t)rows;
@@ -757,12 +865,18 @@ int fr_colour_rows_ss_device(const fr_config *cfg, const void *d_z, int z_width,
     fr_kparams p;
     fill_params(cfg, default_opts(), p);
     HIP_TRY(fr_launch_colour_filter(p, static_cast<const double *>(d_z), (uint32_t)z_width, static_cast<const uint32_t *>(d_iters), width,
-                                    rows, supersample, (uint32_t)channels, d_out, static_cast<hipStream_t>(hip_stream)));
+                                    rows, supersample, (uint32_t)channels, d_out, static_cast<hipStream_t>(hip_stream), transfer));
     return FR_OK;
 }
 
-int fr_colour_ss_rgb8(const fr_config *cfg, const double *z, int z_width, const uint32_t *iters, uint32_t width, uint32_t rows,
-                      uint32_t supersample, int channels, uint8_t *out, size_t out_len) {
+int fr_colour_rows_ss_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, uint32_t width, uint32_t rows,
+                             uint32_t supersample, int channels, void *d_out, size_t out_len, void *hip_stream) {
+    return fr_colour_rows_ss_tf_device(cfg, d_z, z_width, d_iters, width, rows, supersample, FR_SS_TRANSFER_BYTES, channels, d_out, out_len, hip_stream);
+}
+
+int fr_colour_ss_rgb8_tf(const fr_config *cfg, const double *z, int z_width, const uint32_t *iters, uint32_t width, uint32_t rows,
+                      uint32_t supersample, int transfer, int channels, uint8_t *out, size_t out_len) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     int rc = colour_ss_check(cfg, z_width, width, rows, supersample, channels);
     if (rc != FR_OK) return rc;
     const size_t need = (size_t)channels * width * (size_t)rows;
@@ -785,10 +899,15 @@ int fr_colour_ss_rgb8(const fr_config *cfg, const double *z, int z_width, const 
     HIP_TRY(hipMemcpyAsync(ctx->z.ptr, z, zb, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->iters.ptr, iters, ib, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(fr_launch_colour_filter(p, static_cast<const double *>(ctx->z.ptr), (uint32_t)z_width, static_cast<const uint32_t *>(ctx->iters.ptr),
-                                    width, rows, supersample, (uint32_t)channels, ctx->rgb.ptr, ctx->stream));
+                                    width, rows, supersample, (uint32_t)channels, ctx->rgb.ptr, ctx->stream, transfer));
     HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FR_OK;
+}
+
+int fr_colour_ss_rgb8(const fr_config *cfg, const double *z, int z_width, const uint32_t *iters, uint32_t width, uint32_t rows,
+                      uint32_t supersample, int channels, uint8_t *out, size_t out_len) {
+    return fr_colour_ss_rgb8_tf(cfg, z, z_width, iters, width, rows, supersample, FR_SS_TRANSFER_BYTES, channels, out, out_len);
 }
 
 } /* extern "C" */

@@ -69,16 +69,17 @@ __global__ __launch_bounds__(kMarkThreads) void ss_mark_kernel(const ssm_params 
  * by coord_to_space on cfg_s (`p`) — the render kernels' operations on the same (x, y), hence the same bits — and runs
  * recursive() (calc/src/lib.rs:245-257) as written, escape_de_kernel's loop (fr_de.hip) without the derivative; the build has
  * -ffp-contract=off. */
-template <bool JULIA>
+template <bool JULIA, bool LINEAR>
 __global__ __launch_bounds__(kSsRefineThreads) void ss_refine_f64_kernel(const fr_kparams p, const fr_ss_refine a) {
     __shared__ double s_tab[FR_LOG2_N * 3];
     const double *gt = &g_log2_tab[0][0];
     for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    const uint16_t *const s_lt = ss_refine_tables<LINEAR>(); /* LINEAR-LIGHT SUPERSAMPLING: staged with the log2 table */
     __syncthreads();
     const double width = (double)p.width, height = (double)p.height;
     const double squared = p.limit * p.limit; /* :246 */
     const uint32_t iterations = p.iterations;
-    ss_refine_loop(a, [&](uint64_t x, uint64_t y) {
+    ss_refine_loop<LINEAR>(a, s_lt, [&](uint64_t x, uint64_t y) {
         double re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re + p.pos_re; /* coord_to_space, :182-184 */
         double im = (((double)y / height) - 0.5) / p.scale_im + p.pos_im;
         const double cre = JULIA ? p.julia_re : re, cim = JULIA ? p.julia_im : im; /* :209-210 */
@@ -107,8 +108,9 @@ constexpr uint32_t kRefineGroupsDefault = 256 * 8; /* 256 CUs x 8 workgroups of 
 
 /* fr_ss_list.h: the edge list as a refine kernel takes it, and the refine grid */
 fr_ss_refine ss_refine_args(uint8_t *out, const uint32_t *list, unsigned long long *counters, uint32_t width, uint32_t y0, uint32_t s,
-                            uint32_t bpp) {
+                            uint32_t bpp, int transfer) {
     fr_ss_refine a;
+    a.linear = transfer == FR_SS_TRANSFER_SRGB;
     a.out = out;
     a.list = list;
     a.counters = counters;
@@ -209,7 +211,7 @@ int ssa_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, c
 /* Rows [y0, y1) of the adaptive render into d_out on `stream`: the three passes.  Arguments checked, the rows and the width not
  * empty, d_work holds ssa_layout's bytes.  No host synchronisation (PT roads: apart from computing and uploading the view's
  * orbit and table when the context does not hold them yet), no allocation; the count stays in the workspace's first counter. */
-int ssa_render(Ctx &ctx, const SsaRoad &r, const fr_config *cfg, uint32_t s, uint32_t y0, uint32_t y1, unsigned bpp, void *d_out, void *d_work,
+int ssa_render(Ctx &ctx, const SsaRoad &r, const fr_config *cfg, uint32_t s, int transfer, uint32_t y0, uint32_t y1, unsigned bpp, void *d_out, void *d_work,
                hipStream_t stream) {
     const fr_config *cs = &r.pl.cfg_s;
     const SsaLayout l = ssa_layout(cfg, y0, y1);
@@ -271,15 +273,18 @@ int ssa_render(Ctx &ctx, const SsaRoad &r, const fr_config *cfg, uint32_t s, uin
     /* 3. F over the probe bytes of the listed pixels; s = 1: F = P already; a threshold of 255: the list is empty */
     const char *kname = "ss_mark_kernel";
     if (s > 1 && escape_algo && r.tau < 255) {
-        const fr_ss_refine a = ss_refine_args(q.out, list, counters, cfg->width, y0, s, bpp);
+        const fr_ss_refine a = ss_refine_args(q.out, list, counters, cfg->width, y0, s, bpp, transfer);
         const uint32_t groups = ss_refine_groups(a, q.rows);
         if (r.precision == FR_PRECISION_F64) {
             fr_kparams p;
             fill_params(cs, default_opts(), p);
-            if (cfg->algo == FR_ALGO_JULIA)
-                ss_refine_f64_kernel<true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a);
-            else
-                ss_refine_f64_kernel<false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a);
+            if (cfg->algo == FR_ALGO_JULIA) {
+                if (a.linear) ss_refine_f64_kernel<true, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a);
+                else ss_refine_f64_kernel<true, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a);
+            } else {
+                if (a.linear) ss_refine_f64_kernel<false, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a);
+                else ss_refine_f64_kernel<false, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a);
+            }
             HIP_TRY(hipGetLastError());
             kname = "ss_refine_f64_kernel";
         } else if (r.road == FR_PT_ROAD_BLA) {
@@ -330,9 +335,10 @@ int fr_ss_adaptive_workspace_bytes(const fr_config *cfg, uint32_t supersample, u
     return FR_OK;
 }
 
-int fr_render_rows_ss_adaptive_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
-                                      int bits, uint32_t supersample, int threshold, uint32_t y0, uint32_t y1, int channels, void *d_out,
+int fr_render_rows_ss_adaptive_tf_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
+                                      int bits, uint32_t supersample, int transfer, int threshold, uint32_t y0, uint32_t y1, int channels, void *d_out,
                                       size_t out_len, void *d_work, size_t work_len, void *d_refined, void *hip_stream) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsaRoad r;
     int rc = ssa_check(cfg, precision, pos_lo, centre, road, bits, supersample, threshold, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
@@ -348,7 +354,7 @@ int fr_render_rows_ss_adaptive_device(const fr_config *cfg, int precision, const
     rc = ssa_check_buffers(cfg, y0, y1, channels, d_out, out_len, d_work, work_len, d_refined);
     if (rc != FR_OK) return rc;
     return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) -> int {
-        const int rc = ssa_render(ctx, r, cfg, supersample, y0, y1, (unsigned)channels, d_out, d_work, stream);
+        const int rc = ssa_render(ctx, r, cfg, supersample, transfer, y0, y1, (unsigned)channels, d_out, d_work, stream);
         if (rc != FR_OK || !d_refined) return rc;
         const char *count = static_cast<const char *>(d_work) + ssa_layout(cfg, y0, y1).counters_off;
         HIP_TRY(hipMemcpyAsync(d_refined, count, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
@@ -356,9 +362,16 @@ int fr_render_rows_ss_adaptive_device(const fr_config *cfg, int precision, const
     });
 }
 
-int fr_render_rows_ss_adaptive(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
-                               uint32_t supersample, int threshold, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len,
+int fr_render_rows_ss_adaptive_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
+                                      int bits, uint32_t supersample, int threshold, uint32_t y0, uint32_t y1, int channels, void *d_out,
+                                      size_t out_len, void *d_work, size_t work_len, void *d_refined, void *hip_stream) {
+    return fr_render_rows_ss_adaptive_tf_device(cfg, precision, pos_lo, centre, road, bits, supersample, FR_SS_TRANSFER_BYTES, threshold, y0, y1, channels, d_out, out_len, d_work, work_len, d_refined, hip_stream);
+}
+
+int fr_render_rows_ss_adaptive_tf(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                               uint32_t supersample, int transfer, int threshold, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len,
                                uint64_t *refined) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsaRoad r;
     const int rc = ssa_check(cfg, precision, pos_lo, centre, road, bits, supersample, threshold, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
@@ -380,7 +393,7 @@ int fr_render_rows_ss_adaptive(const fr_config *cfg, int precision, const fr_ima
             SsaRoad rp = r; /* the piece's plan: its source rows */
             rp.pl.src_rows = (uint64_t)supersample * (yb - ya);
             uint8_t *dst = ko.rgb + (uint64_t)(ya - y0) * cfg->width * (unsigned)channels;
-            rc = ssa_render(ctx, rp, cfg, supersample, ya, yb, (unsigned)channels, dst, ctx.ss_work.ptr, stream);
+            rc = ssa_render(ctx, rp, cfg, supersample, transfer, ya, yb, (unsigned)channels, dst, ctx.ss_work.ptr, stream);
             if (rc != FR_OK) break;
             const char *count = static_cast<const char *>(ctx.ss_work.ptr) + ssa_layout(cfg, ya, yb).counters_off;
             const hipError_t e = hipMemcpyAsync(&counts[k], count, sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
@@ -393,6 +406,12 @@ int fr_render_rows_ss_adaptive(const fr_config *cfg, int precision, const fr_ima
     if (refined)
         for (const uint64_t c : counts) *refined += c;
     return FR_OK;
+}
+
+int fr_render_rows_ss_adaptive(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                               uint32_t supersample, int threshold, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len,
+                               uint64_t *refined) {
+    return fr_render_rows_ss_adaptive_tf(cfg, precision, pos_lo, centre, road, bits, supersample, FR_SS_TRANSFER_BYTES, threshold, y0, y1, channels, out, out_len, refined);
 }
 
 int fr_debug_ss_adaptive_grid(uint32_t workgroups) {

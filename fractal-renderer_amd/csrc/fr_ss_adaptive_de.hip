@@ -179,7 +179,7 @@ int ssad_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, 
 /* Rows [y0, y1) of the adaptive DE render into d_out on `stream`: the four passes.  Arguments checked, the rows and the width not
  * empty, d_work holds ssad_layout's bytes.  No host synchronisation (PT roads: apart from computing and uploading the view's
  * orbit and table when the context does not hold them yet), no allocation; the count stays in the workspace's first counter. */
-int ssad_render(Ctx &ctx, const SsadRoad &r, const fr_config *cfg, uint32_t s, uint32_t y0, uint32_t y1, unsigned bpp, void *d_out,
+int ssad_render(Ctx &ctx, const SsadRoad &r, const fr_config *cfg, uint32_t s, int transfer, uint32_t y0, uint32_t y1, unsigned bpp, void *d_out,
                 void *d_work, hipStream_t stream) {
     const fr_config *cs = &r.pl.cfg_s;
     const SsadLayout l = ssad_layout(cfg, y0, y1);
@@ -237,7 +237,7 @@ int ssad_render(Ctx &ctx, const SsadRoad &r, const fr_config *cfg, uint32_t s, u
     /* 4. F over the probe bytes of the listed pixels; s = 1: F = P already; threshold 255 and reach 0: the list is empty */
     const char *kname = "ss_mark_de_kernel";
     if (s > 1 && escape_algo && (q.tau < 255 || q.rs > 0.0)) {
-        const fr_ss_refine a = ss_refine_args(q.out, list, counters, cfg->width, y0, s, bpp);
+        const fr_ss_refine a = ss_refine_args(q.out, list, counters, cfg->width, y0, s, bpp, transfer);
         const uint32_t groups = ss_refine_groups(a, q.rows);
         const fr_ss_de_shade sh{r.pixels, r.ts};
         if (r.road == FR_PT_ROAD_BLA) {
@@ -285,10 +285,11 @@ int fr_ss_adaptive_de_workspace_bytes(const fr_config *cfg, uint32_t supersample
     return FR_OK;
 }
 
-int fr_render_rows_ss_adaptive_de_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
-                                         int road, int bits, double thickness, uint32_t supersample, int threshold, double reach,
+int fr_render_rows_ss_adaptive_de_tf_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
+                                         int road, int bits, double thickness, uint32_t supersample, int transfer, int threshold, double reach,
                                          uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len, void *d_work, size_t work_len,
                                          void *d_refined, void *hip_stream) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsadRoad r;
     int rc = ssad_check(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, threshold, reach, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
@@ -304,7 +305,7 @@ int fr_render_rows_ss_adaptive_de_device(const fr_config *cfg, int precision, co
     rc = ssad_check_buffers(cfg, y0, y1, channels, d_out, out_len, d_work, work_len, d_refined);
     if (rc != FR_OK) return rc;
     return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) -> int {
-        const int rc = ssad_render(ctx, r, cfg, supersample, y0, y1, (unsigned)channels, d_out, d_work, stream);
+        const int rc = ssad_render(ctx, r, cfg, supersample, transfer, y0, y1, (unsigned)channels, d_out, d_work, stream);
         if (rc != FR_OK || !d_refined) return rc;
         const char *count = static_cast<const char *>(d_work) + ssad_layout(cfg, y0, y1).counters_off;
         HIP_TRY(hipMemcpyAsync(d_refined, count, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
@@ -312,9 +313,17 @@ int fr_render_rows_ss_adaptive_de_device(const fr_config *cfg, int precision, co
     });
 }
 
-int fr_render_rows_ss_adaptive_de(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
-                                  int bits, double thickness, uint32_t supersample, int threshold, double reach, uint32_t y0, uint32_t y1,
+int fr_render_rows_ss_adaptive_de_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
+                                         int road, int bits, double thickness, uint32_t supersample, int threshold, double reach,
+                                         uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len, void *d_work, size_t work_len,
+                                         void *d_refined, void *hip_stream) {
+    return fr_render_rows_ss_adaptive_de_tf_device(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, FR_SS_TRANSFER_BYTES, threshold, reach, y0, y1, channels, d_out, out_len, d_work, work_len, d_refined, hip_stream);
+}
+
+int fr_render_rows_ss_adaptive_de_tf(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
+                                  int bits, double thickness, uint32_t supersample, int transfer, int threshold, double reach, uint32_t y0, uint32_t y1,
                                   int channels, uint8_t *out, size_t out_len, uint64_t *refined) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsadRoad r;
     const int rc = ssad_check(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, threshold, reach, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
@@ -335,7 +344,7 @@ int fr_render_rows_ss_adaptive_de(const fr_config *cfg, int precision, const fr_
             SsadRoad rp = r; /* the piece's plan: its source rows */
             rp.pl.src_rows = (uint64_t)supersample * (yb - ya);
             uint8_t *dst = ko.rgb + (uint64_t)(ya - y0) * cfg->width * (unsigned)channels;
-            rc = ssad_render(ctx, rp, cfg, supersample, ya, yb, (unsigned)channels, dst, ctx.ss_work.ptr, stream);
+            rc = ssad_render(ctx, rp, cfg, supersample, transfer, ya, yb, (unsigned)channels, dst, ctx.ss_work.ptr, stream);
             if (rc != FR_OK) break;
             const char *count = static_cast<const char *>(ctx.ss_work.ptr) + ssad_layout(cfg, ya, yb).counters_off;
             const hipError_t e = hipMemcpyAsync(&counts[k], count, sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
@@ -348,6 +357,12 @@ int fr_render_rows_ss_adaptive_de(const fr_config *cfg, int precision, const fr_
     if (refined)
         for (const uint64_t c : counts) *refined += c;
     return FR_OK;
+}
+
+int fr_render_rows_ss_adaptive_de(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
+                                  int bits, double thickness, uint32_t supersample, int threshold, double reach, uint32_t y0, uint32_t y1,
+                                  int channels, uint8_t *out, size_t out_len, uint64_t *refined) {
+    return fr_render_rows_ss_adaptive_de_tf(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, FR_SS_TRANSFER_BYTES, threshold, reach, y0, y1, channels, out, out_len, refined);
 }
 
 } /* extern "C" */

@@ -39,6 +39,7 @@ namespace {
 
 #include "fr_colour.h"   /* the colour map of the renders */
 #include "fr_de_shade.h" /* de_distance */
+#include "fr_srgb.h"     /* LINEAR-LIGHT SUPERSAMPLING: the tables of the filter's LINEAR instances */
 
 /* The tile: colour_filter_kernel's (fr_ss.hip), restated.  That kernel keeps its own copy: routing both kernels through one
  * shared function changed colour_filter_kernel's instruction stream (tools/isa_digest.py), and this file leaves the device code
@@ -71,10 +72,12 @@ struct cfd_params {
 /* Phases 2 and 3 of one tile, called by all 256 lanes behind the barrier that ends phase 1.  s_px holds the tile's packed
  * r | g << 8 | b << 16 words at [source row][sample] (`have` false: an algorithm without orbits, every sum is 0); lane l of wave
  * w owns output pixel (x0 + l, r0 + w) of q.dst.  RGBA leaves as one dword per lane; RGB goes to s_out at the destination row's address
- * modulo 4 and, behind one barrier, out as aligned dwords (lanes 0 .. 47) plus < 4 head and < 4 tail bytes (lanes 48 .. 53). */
-template <uint32_t S>
-__device__ __forceinline__ void cf_filter_tile(const uint32_t *s_px, uint8_t *s_out, bool have, const cfd_params &q, uint32_t x0, uint32_t r0,
-                                               uint32_t nx, uint32_t nr, uint32_t w, uint32_t l) {
+ * modulo 4 and, behind one barrier, out as aligned dwords (lanes 0 .. 47) plus < 4 head and < 4 tail bytes (lanes 48 .. 53).
+ * LINEAR (LINEAR-LIGHT SUPERSAMPLING): s_lt is the workgroup's staged tables (fr_srgb.h); a sample's three bytes are decoded as
+ * its word is read, the sums (22 bits) have a register each, the quotients are encoded.  The byte form does not read s_lt. */
+template <uint32_t S, bool LINEAR>
+__device__ __forceinline__ void cf_filter_tile(const uint32_t *s_px, uint8_t *s_out, const uint16_t *s_lt, bool have, const cfd_params &q,
+                                               uint32_t x0, uint32_t r0, uint32_t nx, uint32_t nr, uint32_t w, uint32_t l) {
     constexpr uint32_t SW = kCfTileW * S;
     constexpr uint32_t HALF = S * S / 2u, MAGIC = (uint32_t)(((1ull << 31) + S * S - 1u) / (S * S));
     /* ---- phase 2: one output pixel per lane ---- */
@@ -82,11 +85,19 @@ __device__ __forceinline__ void cf_filter_tile(const uint32_t *s_px, uint8_t *s_
     uint8_t *drow = q.dst + ((uint64_t)(r0 + (w < nr ? w : 0u)) * q.width + x0) * q.bpp; /* the wave's output row */
     const uint32_t dmis = q.bpp == 4u ? 0u : (uint32_t)(uintptr_t)drow & 3u;
     if (live) {
-        uint32_t rb = HALF | HALF << 16, gg = HALF; /* r and b in the halves of one word: a sum is at most 64 * 255 + 32 */
+        [[maybe_unused]] uint32_t rb = HALF | HALF << 16, gg = HALF; /* r and b in the halves of one word: a sum is at most 64 * 255 + 32 */
+        [[maybe_unused]] uint32_t lr = HALF, lg = HALF, lb = HALF;   /* LINEAR: a sum is at most 64 * 65535 + 32 */
         if (have) {
             for (uint32_t j = 0; j < S; j++) {
                 const uint32_t *row = s_px + (w * S + j) * SW + l * S;
-                if constexpr (S % 4u == 0u) {
+                if constexpr (LINEAR) {
+                    for (uint32_t i = 0; i < S; i++) {
+                        const uint32_t v = row[i];
+                        lr += srgb_decode(s_lt, v & 0xFFu);
+                        lg += srgb_decode(s_lt, v >> 8 & 0xFFu);
+                        lb += srgb_decode(s_lt, v >> 16);
+                    }
+                } else if constexpr (S % 4u == 0u) {
                     for (uint32_t i = 0; i < S; i += 4u) {
                         const uint4 v = *reinterpret_cast<const uint4 *>(row + i);
                         rb += (v.x & 0x00FF00FFu) + (v.y & 0x00FF00FFu) + (v.z & 0x00FF00FFu) + (v.w & 0x00FF00FFu);
@@ -107,7 +118,14 @@ __device__ __forceinline__ void cf_filter_tile(const uint32_t *s_px, uint8_t *s_
                 }
             }
         }
-        const uint32_t cr = __umulhi(2u * (rb & 0xFFFFu), MAGIC), cg = __umulhi(2u * gg, MAGIC), cb = __umulhi(2u * (rb >> 16), MAGIC);
+        uint32_t cr, cg, cb;
+        if constexpr (LINEAR) {
+            cr = srgb_encode(s_lt, __umulhi(2u * lr, MAGIC));
+            cg = srgb_encode(s_lt, __umulhi(2u * lg, MAGIC));
+            cb = srgb_encode(s_lt, __umulhi(2u * lb, MAGIC));
+        } else {
+            cr = __umulhi(2u * (rb & 0xFFFFu), MAGIC), cg = __umulhi(2u * gg, MAGIC), cb = __umulhi(2u * (rb >> 16), MAGIC);
+        }
         if (q.bpp == 4u) {
             reinterpret_cast<uint32_t *>(drow)[l] = cr | cg << 8 | cb << 16 | 0xFF000000u;
         } else {
@@ -186,7 +204,7 @@ __device__ __forceinline__ void cfd_colour(const cfd_sample &v, uint32_t iterati
     s_px[v.at] = r | (g << 8) | (b << 16);
 }
 
-template <uint32_t S>
+template <uint32_t S, bool LINEAR>
 __global__ __launch_bounds__(kCfThreads) void colour_de_filter_kernel(const fr_kparams p, const cfd_params q) {
     constexpr uint32_t RO = cf_tile_rows(S), SW = kCfTileW * S, N = SW * S * RO;
     __shared__ double s_tab[FR_LOG2_N * 3];
@@ -198,6 +216,12 @@ __global__ __launch_bounds__(kCfThreads) void colour_de_filter_kernel(const fr_k
     if (escape_algo) { /* uniform; the distance reads the table whether the colour map does or not */
         const double *gt = &g_log2_tab[0][0];
         for (uint32_t k = tid; k < FR_LOG2_N * 3; k += kCfThreads) s_tab[k] = gt[k];
+    }
+    const uint16_t *s_lt = nullptr;
+    if constexpr (LINEAR) { /* 1 KiB beside the log2 table, before the first tile's barrier */
+        __shared__ uint16_t s_srgb[kSrgbLdsWords];
+        srgb_stage(s_srgb, tid, kCfThreads);
+        s_lt = s_srgb;
     }
     const uint32_t iterations = p.iterations;
     const uint32_t w = tid >> 6, l = tid & 63u; /* phase 2 and 3: output row of the tile, output pixel of the row */
@@ -225,14 +249,15 @@ __global__ __launch_bounds__(kCfThreads) void colour_de_filter_kernel(const fr_k
         __syncthreads();
 
         /* ---- phases 2 and 3: the s x s sums, the division, the way out ---- */
-        cf_filter_tile<S>(s_px, s_out, escape_algo, q, x0, r0, nx, nr, w, l);
+        cf_filter_tile<S, LINEAR>(s_px, s_out, s_lt, escape_algo, q, x0, r0, nx, nr, w, l);
     }
 }
 
 template <uint32_t S>
-hipError_t cfd_launch(const fr_kparams &p, const cfd_params &q, hipStream_t stream) {
+hipError_t cfd_launch(const fr_kparams &p, const cfd_params &q, bool linear, hipStream_t stream) {
     const uint32_t groups = (q.n_tiles + cf_tiles_per_group(S) - 1u) / cf_tiles_per_group(S);
-    colour_de_filter_kernel<S><<<dim3(groups), dim3(kCfThreads), 0, stream>>>(p, q);
+    if (linear) colour_de_filter_kernel<S, true><<<dim3(groups), dim3(kCfThreads), 0, stream>>>(p, q);
+    else colour_de_filter_kernel<S, false><<<dim3(groups), dim3(kCfThreads), 0, stream>>>(p, q);
     return hipGetLastError();
 }
 
@@ -240,9 +265,10 @@ hipError_t cfd_launch(const fr_kparams &p, const cfd_params &q, hipStream_t stre
 
 hipError_t fr_launch_colour_de_filter(const fr_kparams &p, const double *z, const uint32_t *iters, const double *der, uint32_t width,
                                       uint64_t rows, uint32_t s, double pixels, double thickness, uint32_t bpp, void *dst,
-                                      hipStream_t stream) {
+                                      hipStream_t stream, int transfer) {
     if (width == 0 || rows == 0) return hipSuccess;
     if (s < 1 || s > FR_SS_MAX || (bpp != 3 && bpp != 4)) return hipErrorInvalidValue;
+    const bool linear = transfer == FR_SS_TRANSFER_SRGB;
     if (s == 1) /* nothing to filter */
         return fr_launch_colour_de_rows(p, z, iters, der, (size_t)width * rows, pixels, thickness, bpp, dst, stream);
     cfd_params q;
@@ -266,13 +292,13 @@ hipError_t fr_launch_colour_de_filter(const fr_kparams &p, const double *z, cons
         q.n_tiles = (uint32_t)(q.tiles_x * ((n + ro - 1) / ro));
         hipError_t e;
         switch (s) {
-        case 2: e = cfd_launch<2>(p, q, stream); break;
-        case 3: e = cfd_launch<3>(p, q, stream); break;
-        case 4: e = cfd_launch<4>(p, q, stream); break;
-        case 5: e = cfd_launch<5>(p, q, stream); break;
-        case 6: e = cfd_launch<6>(p, q, stream); break;
-        case 7: e = cfd_launch<7>(p, q, stream); break;
-        default: e = cfd_launch<8>(p, q, stream); break;
+        case 2: e = cfd_launch<2>(p, q, linear, stream); break;
+        case 3: e = cfd_launch<3>(p, q, linear, stream); break;
+        case 4: e = cfd_launch<4>(p, q, linear, stream); break;
+        case 5: e = cfd_launch<5>(p, q, linear, stream); break;
+        case 6: e = cfd_launch<6>(p, q, linear, stream); break;
+        case 7: e = cfd_launch<7>(p, q, linear, stream); break;
+        default: e = cfd_launch<8>(p, q, linear, stream); break;
         }
         if (e != hipSuccess) return e;
     }
@@ -379,7 +405,7 @@ int ss_de_scaled_check(const fr_config *cfg, const fr_wide_centre *centre, int b
  * of n samples lies at d_work as z (16 n bytes) | der (16 n) | iters (4 n).  Profiling: the span of the whole call — the first
  * band records the start and the render kernel's name, the later bands record nothing, the end goes behind the last filter.
  * Arguments already checked, the range and the width not empty.  No host synchronisation beyond what the band's launch has. */
-int render_ss_de_bands(Ctx &ctx, const SsDeRoad &r, uint32_t s, uint32_t y0, unsigned bpp, void *d_out, void *d_work, size_t work_len,
+int render_ss_de_bands(Ctx &ctx, const SsDeRoad &r, uint32_t s, int transfer, uint32_t y0, unsigned bpp, void *d_out, void *d_work, size_t work_len,
                        hipStream_t stream) {
     const SsPlan &pl = r.pl;
     const uint32_t width = pl.cfg_s.width / s;
@@ -403,7 +429,7 @@ int render_ss_de_bands(Ctx &ctx, const SsDeRoad &r, uint32_t s, uint32_t y0, uns
         if (rc != FR_OK) break;
         pr.enabled = false;
         uint8_t *dst = static_cast<uint8_t *>(d_out) + (uint64_t)(((uint32_t)ya - Y0) / s) * width * bpp;
-        const hipError_t e = fr_launch_colour_de_filter(p, d_z, d_iters, d_der, width, (yb - (uint32_t)ya) / s, s, r.pixels, r.ts, bpp, dst, stream);
+        const hipError_t e = fr_launch_colour_de_filter(p, d_z, d_iters, d_der, width, (yb - (uint32_t)ya) / s, s, r.pixels, r.ts, bpp, dst, stream, transfer);
         if (e != hipSuccess) rc = fail_hip(e, "fr_launch_colour_de_filter");
     }
     if (rc == FR_OK && prof_guard.was && pr.have) HIP_TRY(hipEventRecord(pr.e1, stream));
@@ -417,8 +443,9 @@ using namespace fr;
 
 extern "C" {
 
-int fr_colour_de_rows_ss_device(const fr_config *cfg, const void *d_z, const void *d_iters, const void *d_der, uint32_t width, uint32_t rows,
-                                uint32_t supersample, double thickness, int channels, void *d_out, size_t out_len, void *hip_stream) {
+int fr_colour_de_rows_ss_tf_device(const fr_config *cfg, const void *d_z, const void *d_iters, const void *d_der, uint32_t width, uint32_t rows,
+                                uint32_t supersample, int transfer, double thickness, int channels, void *d_out, size_t out_len, void *hip_stream) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     double ts;
     const int rc = colour_de_ss_check(cfg, width, rows, supersample, thickness, channels, ts);
     if (rc != FR_OK) return rc;
@@ -434,12 +461,18 @@ int fr_colour_de_rows_ss_device(const fr_config *cfg, const void *d_z, const voi
     fill_params(cfg, default_opts(), p);
     HIP_TRY(fr_launch_colour_de_filter(p, static_cast<const double *>(d_z), static_cast<const uint32_t *>(d_iters),
                                        static_cast<const double *>(d_der), width, rows, supersample, ss_de_pixels(cfg, supersample), ts,
-                                       (uint32_t)channels, d_out, static_cast<hipStream_t>(hip_stream)));
+                                       (uint32_t)channels, d_out, static_cast<hipStream_t>(hip_stream), transfer));
     return FR_OK;
 }
 
-int fr_colour_de_ss_rgb8(const fr_config *cfg, const double *z, const uint32_t *iters, const double *der, uint32_t width, uint32_t rows,
-                         uint32_t supersample, double thickness, int channels, uint8_t *out, size_t out_len) {
+int fr_colour_de_rows_ss_device(const fr_config *cfg, const void *d_z, const void *d_iters, const void *d_der, uint32_t width, uint32_t rows,
+                                uint32_t supersample, double thickness, int channels, void *d_out, size_t out_len, void *hip_stream) {
+    return fr_colour_de_rows_ss_tf_device(cfg, d_z, d_iters, d_der, width, rows, supersample, FR_SS_TRANSFER_BYTES, thickness, channels, d_out, out_len, hip_stream);
+}
+
+int fr_colour_de_ss_rgb8_tf(const fr_config *cfg, const double *z, const uint32_t *iters, const double *der, uint32_t width, uint32_t rows,
+                         uint32_t supersample, int transfer, double thickness, int channels, uint8_t *out, size_t out_len) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     double ts;
     int rc = colour_de_ss_check(cfg, width, rows, supersample, thickness, channels, ts);
     if (rc != FR_OK) return rc;
@@ -465,10 +498,15 @@ int fr_colour_de_ss_rgb8(const fr_config *cfg, const double *z, const uint32_t *
     HIP_TRY(hipMemcpyAsync(d_der, der, zb, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->iters.ptr, iters, ib, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(fr_launch_colour_de_filter(p, d_z, static_cast<const uint32_t *>(ctx->iters.ptr), d_der, width, rows, supersample,
-                                       ss_de_pixels(cfg, supersample), ts, (uint32_t)channels, ctx->rgb.ptr, ctx->stream));
+                                       ss_de_pixels(cfg, supersample), ts, (uint32_t)channels, ctx->rgb.ptr, ctx->stream, transfer));
     HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FR_OK;
+}
+
+int fr_colour_de_ss_rgb8(const fr_config *cfg, const double *z, const uint32_t *iters, const double *der, uint32_t width, uint32_t rows,
+                         uint32_t supersample, double thickness, int channels, uint8_t *out, size_t out_len) {
+    return fr_colour_de_ss_rgb8_tf(cfg, z, iters, der, width, rows, supersample, FR_SS_TRANSFER_BYTES, thickness, channels, out, out_len);
 }
 
 int fr_ss_de_workspace_bytes(const fr_config *cfg, uint32_t supersample, uint32_t y0, uint32_t y1, size_t *min_bytes, size_t *best_bytes) {
@@ -480,9 +518,10 @@ int fr_ss_de_workspace_bytes(const fr_config *cfg, uint32_t supersample, uint32_
     return FR_OK;
 }
 
-int fr_render_rows_ss_de_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
-                                int bits, double thickness, uint32_t supersample, uint32_t y0, uint32_t y1, int channels, void *d_out,
+int fr_render_rows_ss_de_tf_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
+                                int bits, double thickness, uint32_t supersample, int transfer, uint32_t y0, uint32_t y1, int channels, void *d_out,
                                 size_t out_len, void *d_work, size_t work_len, void *hip_stream) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsDeRoad r;
     const int rc = ss_de_check(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
@@ -492,15 +531,22 @@ int fr_render_rows_ss_de_device(const fr_config *cfg, int precision, const fr_im
         if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_work must be 8-byte aligned (z and der lie in it)");
     }
     return rgb_rows_device(cfg, y0, y1, channels, d_out, out_len, hip_stream, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
-        return render_ss_de_bands(ctx, r, supersample, y0, (unsigned)channels, ko.rgb, d_work, work_len, stream);
+        return render_ss_de_bands(ctx, r, supersample, transfer, y0, (unsigned)channels, ko.rgb, d_work, work_len, stream);
     });
+}
+
+int fr_render_rows_ss_de_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
+                                int bits, double thickness, uint32_t supersample, uint32_t y0, uint32_t y1, int channels, void *d_out,
+                                size_t out_len, void *d_work, size_t work_len, void *hip_stream) {
+    return fr_render_rows_ss_de_tf_device(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, FR_SS_TRANSFER_BYTES, y0, y1, channels, d_out, out_len, d_work, work_len, hip_stream);
 }
 
 /* ---- SUPERSAMPLED SCALED DE: the two calls above on the scaled road, which fr_render_rows_ss_de keeps refusing ---------------- */
 
-int fr_render_rows_ss_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness,
-                                          uint32_t supersample, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len,
+int fr_render_rows_ss_de_pt_scaled_tf_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness,
+                                          uint32_t supersample, int transfer, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len,
                                           void *d_work, size_t work_len, void *hip_stream) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsDeRoad r;
     const int rc = ss_de_scaled_check(cfg, centre, bits, thickness, supersample, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
@@ -510,12 +556,19 @@ int fr_render_rows_ss_de_pt_scaled_device(const fr_config *cfg, const fr_wide_ce
         if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_work must be 8-byte aligned (z and der lie in it)");
     }
     return rgb_rows_device(cfg, y0, y1, channels, d_out, out_len, hip_stream, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
-        return render_ss_de_bands(ctx, r, supersample, y0, (unsigned)channels, ko.rgb, d_work, work_len, stream);
+        return render_ss_de_bands(ctx, r, supersample, transfer, y0, (unsigned)channels, ko.rgb, d_work, work_len, stream);
     });
 }
 
-int fr_render_rows_ss_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t supersample,
+int fr_render_rows_ss_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness,
+                                          uint32_t supersample, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len,
+                                          void *d_work, size_t work_len, void *hip_stream) {
+    return fr_render_rows_ss_de_pt_scaled_tf_device(cfg, centre, bits, thickness, supersample, FR_SS_TRANSFER_BYTES, y0, y1, channels, d_out, out_len, d_work, work_len, hip_stream);
+}
+
+int fr_render_rows_ss_de_pt_scaled_tf(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t supersample, int transfer,
                                    uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsDeRoad r;
     const int rc = ss_de_scaled_check(cfg, centre, bits, thickness, supersample, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
@@ -523,7 +576,28 @@ int fr_render_rows_ss_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *c
     return rgb_rows_host(cfg, y0, y1, channels, out, out_len, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
         int rc = ctx.reserve(ctx.ss_work, work_len);
         if (rc != FR_OK) return rc;
-        rc = render_ss_de_bands(ctx, r, supersample, y0, (unsigned)channels, ko.rgb, ctx.ss_work.ptr, work_len, stream);
+        rc = render_ss_de_bands(ctx, r, supersample, transfer, y0, (unsigned)channels, ko.rgb, ctx.ss_work.ptr, work_len, stream);
+        if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
+        return rc;
+    });
+}
+
+int fr_render_rows_ss_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t supersample,
+                                   uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len) {
+    return fr_render_rows_ss_de_pt_scaled_tf(cfg, centre, bits, thickness, supersample, FR_SS_TRANSFER_BYTES, y0, y1, channels, out, out_len);
+}
+
+int fr_render_rows_ss_de_tf(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                         double thickness, uint32_t supersample, int transfer, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
+    SsDeRoad r;
+    const int rc = ss_de_check(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, y0, y1, channels, r);
+    if (rc != FR_OK) return rc;
+    const size_t work_len = std::max(r.pl.min_bytes, std::min(r.pl.best_bytes, kSsHostWorkCap));
+    return rgb_rows_host(cfg, y0, y1, channels, out, out_len, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
+        int rc = ctx.reserve(ctx.ss_work, work_len);
+        if (rc != FR_OK) return rc;
+        rc = render_ss_de_bands(ctx, r, supersample, transfer, y0, (unsigned)channels, ko.rgb, ctx.ss_work.ptr, work_len, stream);
         if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
         return rc;
     });
@@ -531,17 +605,7 @@ int fr_render_rows_ss_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *c
 
 int fr_render_rows_ss_de(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
                          double thickness, uint32_t supersample, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len) {
-    SsDeRoad r;
-    const int rc = ss_de_check(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, y0, y1, channels, r);
-    if (rc != FR_OK) return rc;
-    const size_t work_len = std::max(r.pl.min_bytes, std::min(r.pl.best_bytes, kSsHostWorkCap));
-    return rgb_rows_host(cfg, y0, y1, channels, out, out_len, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
-        int rc = ctx.reserve(ctx.ss_work, work_len);
-        if (rc != FR_OK) return rc;
-        rc = render_ss_de_bands(ctx, r, supersample, y0, (unsigned)channels, ko.rgb, ctx.ss_work.ptr, work_len, stream);
-        if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
-        return rc;
-    });
+    return fr_render_rows_ss_de_tf(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, FR_SS_TRANSFER_BYTES, y0, y1, channels, out, out_len);
 }
 
 } /* extern "C" */

@@ -41,6 +41,7 @@ struct fr_ss_refine {
     uint32_t s, s2, ppw;           /* supersample; s * s; floor(64 / s2): entries a wave claims at a time */
     uint32_t bpp;                  /* 3 or 4 */
     uint32_t half, magic;          /* floor(s2 / 2); ceil(2^31 / s2): the box filter's division (fr_ss.hip) */
+    uint32_t linear;               /* LINEAR-LIGHT SUPERSAMPLING: the launch takes the kernel's LINEAR instance (the host reads it) */
 };
 
 constexpr uint32_t kSsRefineThreads = 256; /* 4 waves; a wave claims on its own, the workgroup only shares the log2 table */
@@ -59,6 +60,8 @@ constexpr uint32_t kMarkPitch = kMarkW + 2, kMarkHalo = kMarkPitch * (kMarkH + 2
 constexpr uint32_t kMarkOutside = 0xFFFFFFFFu; /* a halo position outside the image */
 
 namespace {
+
+#include "fr_srgb.h" /* LINEAR-LIGHT SUPERSAMPLING: the tables of the refine kernels' LINEAR instances */
 
 /* ---- the mark pass's shared pieces ---- */
 
@@ -122,16 +125,33 @@ __device__ __forceinline__ void ss_mark_append(bool edge, uint32_t idx, uint32_t
     }
 }
 
-/* The claim loop of one persistent wave.  Called by every lane of the wave, converged, AFTER the workgroup's last barrier: the
+/* The sRGB tables of a refine kernel's LINEAR instance in LDS (1 KiB), staged by the whole workgroup: call it before the barrier
+ * that follows the log2 table's staging.  The byte instance has none. */
+template <bool LINEAR>
+__device__ __forceinline__ const uint16_t *ss_refine_tables() {
+    if constexpr (LINEAR) {
+        __shared__ uint16_t s_lt[kSrgbLdsWords];
+        srgb_stage(s_lt, threadIdx.x, kSsRefineThreads);
+        return s_lt;
+    } else {
+        return nullptr;
+    }
+}
+
+/* The claim loop of one persistent wave. Called by every lane of the wave, converged, AFTER the workgroup's last barrier: the
  * loop runs a different number of times per wave and holds none.  Each pass claims ppw entries with one atomic on the cursor
  * (lane 0; the answer is made wave-uniform, so the exit is taken by the whole wave); lane l takes sample l % s2 of entry
  * l / s2 — (i, j) = (k % s, k / s) of output pixel (X, Y) — and sample(x, y) returns the packed r | g << 8 | b << 16 of sample
  * pixel (x, y) of cfg_s.  Lanes with no sample (at or past ppw * s2, or past the count: the list is read only below it) skip
  * the orbit with 0 and rejoin for the shuffles, which every lane of the wave executes: the s2 triples of an entry are summed
  * by each of its lanes out of its neighbours' registers (integers: the order does not matter), and the entry's first lane
- * writes F over the probe bytes. */
-template <class Sample>
-__device__ __forceinline__ void ss_refine_loop(const fr_ss_refine &a, Sample &&sample) {
+ * writes F over the probe bytes.
+ * LINEAR (LINEAR-LIGHT SUPERSAMPLING): s_lt is the workgroup's staged tables (fr_srgb.h: srgb_stage, before that last barrier).
+ * Each lane decodes its own sample before the shuffles — L[r] | L[g] << 16 in one register, L[b] in another, two shuffles a
+ * sample — the three sums (22 bits) have a register each, and the entry's first lane encodes the three quotients.  The byte
+ * form does not read s_lt. */
+template <bool LINEAR, class Sample>
+__device__ __forceinline__ void ss_refine_loop(const fr_ss_refine &a, const uint16_t *s_lt, Sample &&sample) {
     const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long count = a.counters[0];
     const uint32_t e = lane / a.s2, k = lane - e * a.s2;
@@ -151,8 +171,34 @@ __device__ __forceinline__ void ss_refine_loop(const fr_ss_refine &a, Sample &&s
             X = idx - row * a.width;
             packed = sample((uint64_t)a.s * X + i, (uint64_t)a.s * ((uint64_t)a.y0 + row) + j);
         }
-        uint32_t rb = a.half | a.half << 16, gg = a.half; /* r and b in the halves of one word: a sum is at most 64 * 255 + 32 */
         const uint32_t first = e * a.s2;
+        if constexpr (LINEAR) {
+            const uint32_t lrg = srgb_decode(s_lt, packed & 0xFFu) | srgb_decode(s_lt, packed >> 8 & 0xFFu) << 16;
+            const uint32_t lb = srgb_decode(s_lt, packed >> 16 & 0xFFu);
+            uint32_t sr = a.half, sg = a.half, sb = a.half; /* a sum is at most 64 * 65535 + 32 */
+            for (uint32_t t = 0; t < a.s2; t++) { /* uniform trip count; a source lane past 63 belongs to no entry */
+                const int from = (int)((first + t) & 63u);
+                const uint32_t v = (uint32_t)__shfl((int)lrg, from, 64);
+                sr += v & 0xFFFFu;
+                sg += v >> 16;
+                sb += (uint32_t)__shfl((int)lb, from, 64);
+            }
+            if (live && k == 0) {
+                const uint32_t cr = srgb_encode(s_lt, __umulhi(2u * sr, a.magic)), cg = srgb_encode(s_lt, __umulhi(2u * sg, a.magic)),
+                               cb = srgb_encode(s_lt, __umulhi(2u * sb, a.magic));
+                const uint64_t px = (uint64_t)row * a.width + X;
+                if (a.bpp == 4u) {
+                    reinterpret_cast<uint32_t *>(a.out)[px] = cr | cg << 8 | cb << 16 | 0xFF000000u;
+                } else {
+                    uint8_t *o = a.out + 3ull * px;
+                    o[0] = (uint8_t)cr;
+                    o[1] = (uint8_t)cg;
+                    o[2] = (uint8_t)cb;
+                }
+            }
+            continue;
+        }
+        uint32_t rb = a.half | a.half << 16, gg = a.half; /* r and b in the halves of one word: a sum is at most 64 * 255 + 32 */
         for (uint32_t t = 0; t < a.s2; t++) { /* uniform trip count; a source lane past 63 belongs to no entry */
             const uint32_t v = (uint32_t)__shfl((int)packed, (int)((first + t) & 63u), 64);
             rb += v & 0x00FF00FFu;
@@ -193,7 +239,7 @@ int scaled_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, 
  * when one is set, else every wave slot of the device, capped by the most work the rows can hold (every pixel an edge, ppw
  * entries a claim, 4 waves a workgroup). */
 fr_ss_refine ss_refine_args(uint8_t *out, const uint32_t *list, unsigned long long *counters, uint32_t width, uint32_t y0, uint32_t s,
-                            uint32_t bpp);
+                            uint32_t bpp, int transfer = 0);
 uint32_t ss_refine_groups(const fr_ss_refine &a, uint32_t rows);
 
 /* ADAPTIVE SUPERSAMPLED DE's road launches (fr_ss_adaptive_de.hip calls them) on cfg_s (`cfg` below), arguments already checked.

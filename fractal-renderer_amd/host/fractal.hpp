@@ -111,13 +111,18 @@ inline std::vector<RGB> get_image(const Config &config, int precision = FR_PRECI
     return image;
 }
 
+// In which space the s x s samples of a supersampled form are averaged (include/fractal_hip.h, "LINEAR-LIGHT SUPERSAMPLING"):
+// Bytes, the display-encoded values as they are, or Srgb, linear light — decoded, averaged, encoded again, exactly, in integers —
+// which keeps the light of a bright thread on a dark ground.  The last, defaulted argument of every supersampled form below.
+enum class Transfer : int { Bytes = FR_SS_TRANSFER_BYTES, Srgb = FR_SS_TRANSFER_SRGB };
+
 // get_image anti-aliased: supersample x supersample samples per pixel, box-filtered on the device (include/fractal_hip.h,
 // "supersampled rendering"; 1 <= supersample <= FR_SS_MAX).  Only the width x height result crosses PCIe.  One GPU,
 // whatever use_devices chose; supersample = 1 is get_image(config, precision) on that GPU, byte for byte.
-inline std::vector<RGB> get_image(const Config &config, int precision, uint32_t supersample) {
+inline std::vector<RGB> get_image(const Config &config, int precision, uint32_t supersample, Transfer transfer = Transfer::Bytes) {
     std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
-    check(fr_render_rows_ss(&config, precision, nullptr, supersample, 0, config.height, 3,
-                            reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB), nullptr));
+    check(fr_render_rows_ss_tf(&config, precision, nullptr, supersample, static_cast<int>(transfer), 0, config.height, 3,
+                               reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB), nullptr));
     return image;
 }
 
@@ -283,23 +288,23 @@ inline void extend_pt_rows_device(const Config &config, const fr_wide_centre &ce
 // get_image on a deep road with supersample x supersample samples per pixel, box-filtered on the device: the forms above with a
 // supersample factor behind them (1 .. FR_SS_MAX; 1 is the form without it, byte for byte).  One GPU.
 inline std::vector<RGB> get_image_ss_pt(const Config &config, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
-                                        uint32_t supersample) {
+                                        uint32_t supersample, Transfer transfer = Transfer::Bytes) {
     std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
-    check(fr_render_rows_ss_pt(&config, pos_lo, centre, road, bits, supersample, 0, config.height, 3,
-                               reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB)));
+    check(fr_render_rows_ss_pt_tf(&config, pos_lo, centre, road, bits, supersample, static_cast<int>(transfer), 0, config.height, 3,
+                                  reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB)));
     return image;
 }
-inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, uint32_t supersample) {
-    return get_image_ss_pt(config, nullptr, &centre, FR_PT_ROAD_PLAIN, 0, supersample);
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, uint32_t supersample, Transfer transfer = Transfer::Bytes) {
+    return get_image_ss_pt(config, nullptr, &centre, FR_PT_ROAD_PLAIN, 0, supersample, transfer);
 }
-inline std::vector<RGB> get_image(const Config &config, Bla bla, const fr_imaginary *pos_lo, uint32_t supersample) {
-    return get_image_ss_pt(config, pos_lo, nullptr, FR_PT_ROAD_BLA, bla.bits, supersample);
+inline std::vector<RGB> get_image(const Config &config, Bla bla, const fr_imaginary *pos_lo, uint32_t supersample, Transfer transfer = Transfer::Bytes) {
+    return get_image_ss_pt(config, pos_lo, nullptr, FR_PT_ROAD_BLA, bla.bits, supersample, transfer);
 }
-inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Bla bla, uint32_t supersample) {
-    return get_image_ss_pt(config, nullptr, &centre, FR_PT_ROAD_BLA, bla.bits, supersample);
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Bla bla, uint32_t supersample, Transfer transfer = Transfer::Bytes) {
+    return get_image_ss_pt(config, nullptr, &centre, FR_PT_ROAD_BLA, bla.bits, supersample, transfer);
 }
-inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Scaled scaled, uint32_t supersample) {
-    return get_image_ss_pt(config, nullptr, &centre, FR_PT_ROAD_SCALED, scaled.bits, supersample);
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Scaled scaled, uint32_t supersample, Transfer transfer = Transfer::Bytes) {
+    return get_image_ss_pt(config, nullptr, &centre, FR_PT_ROAD_SCALED, scaled.bits, supersample, transfer);
 }
 // ---- adaptive supersampling (include/fractal_hip.h, "ADAPTIVE SUPERSAMPLING") --------------------------------------------------
 // The supersampled forms above with an Adaptive behind them: all supersample x supersample samples only at EDGE pixels — those
@@ -311,34 +316,35 @@ struct Adaptive {
     uint64_t *refined = nullptr;
 };
 inline std::vector<RGB> get_image_ss_adaptive(const Config &config, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
-                                              int road, int bits, uint32_t supersample, Adaptive adaptive) {
+                                              int road, int bits, uint32_t supersample, Adaptive adaptive, Transfer transfer = Transfer::Bytes) {
     std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
-    check(fr_render_rows_ss_adaptive(&config, precision, pos_lo, centre, road, bits, supersample, adaptive.threshold, 0, config.height, 3,
-                                     reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB), adaptive.refined));
+    check(fr_render_rows_ss_adaptive_tf(&config, precision, pos_lo, centre, road, bits, supersample, static_cast<int>(transfer), adaptive.threshold, 0,
+                                        config.height, 3, reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB),
+                                        adaptive.refined));
     return image;
 }
-inline std::vector<RGB> get_image(const Config &config, int precision, uint32_t supersample, Adaptive adaptive) {
-    return get_image_ss_adaptive(config, precision, nullptr, nullptr, FR_PT_ROAD_PLAIN, 0, supersample, adaptive);
+inline std::vector<RGB> get_image(const Config &config, int precision, uint32_t supersample, Adaptive adaptive, Transfer transfer = Transfer::Bytes) {
+    return get_image_ss_adaptive(config, precision, nullptr, nullptr, FR_PT_ROAD_PLAIN, 0, supersample, adaptive, transfer);
 }
-inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, uint32_t supersample, Adaptive adaptive) {
-    return get_image_ss_adaptive(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_PLAIN, 0, supersample, adaptive);
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, uint32_t supersample, Adaptive adaptive, Transfer transfer = Transfer::Bytes) {
+    return get_image_ss_adaptive(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_PLAIN, 0, supersample, adaptive, transfer);
 }
-inline std::vector<RGB> get_image(const Config &config, Bla bla, const fr_imaginary *pos_lo, uint32_t supersample, Adaptive adaptive) {
-    return get_image_ss_adaptive(config, FR_PRECISION_PT, pos_lo, nullptr, FR_PT_ROAD_BLA, bla.bits, supersample, adaptive);
+inline std::vector<RGB> get_image(const Config &config, Bla bla, const fr_imaginary *pos_lo, uint32_t supersample, Adaptive adaptive, Transfer transfer = Transfer::Bytes) {
+    return get_image_ss_adaptive(config, FR_PRECISION_PT, pos_lo, nullptr, FR_PT_ROAD_BLA, bla.bits, supersample, adaptive, transfer);
 }
-inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Bla bla, uint32_t supersample, Adaptive adaptive) {
-    return get_image_ss_adaptive(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_BLA, bla.bits, supersample, adaptive);
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Bla bla, uint32_t supersample, Adaptive adaptive, Transfer transfer = Transfer::Bytes) {
+    return get_image_ss_adaptive(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_BLA, bla.bits, supersample, adaptive, transfer);
 }
-inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Scaled scaled, uint32_t supersample, Adaptive adaptive) {
-    return get_image_ss_adaptive(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_SCALED, scaled.bits, supersample, adaptive);
+inline std::vector<RGB> get_image(const Config &config, const fr_wide_centre &centre, Scaled scaled, uint32_t supersample, Adaptive adaptive, Transfer transfer = Transfer::Bytes) {
+    return get_image_ss_adaptive(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_SCALED, scaled.bits, supersample, adaptive, transfer);
 }
 // A kept anti-aliased view is a kept view of the config with width and height times supersample: the escape / state / extend
 // wrappers above on that config, and this to colour it — colour map and box filter in one kernel, no RGB workspace.
 // channels 3 (r,g,b) or 4 (r,g,b,255; d_out 4-byte aligned); config is the OUTPUT's (width x height).
 inline void colour_rows_ss_device(const Config &config, const void *d_z, const void *d_iters, uint32_t supersample, void *d_out,
-                                  int channels = 4, void *hip_stream = nullptr, int z_width = 2) {
-    check(fr_colour_rows_ss_device(&config, d_z, z_width, d_iters, config.width, config.height, supersample, channels, d_out,
-                                   static_cast<size_t>(channels) * config.width * config.height, hip_stream));
+                                  int channels = 4, void *hip_stream = nullptr, int z_width = 2, Transfer transfer = Transfer::Bytes) {
+    check(fr_colour_rows_ss_tf_device(&config, d_z, z_width, d_iters, config.width, config.height, supersample, static_cast<int>(transfer), channels,
+                                      d_out, static_cast<size_t>(channels) * config.width * config.height, hip_stream));
 }
 
 // ---- auto-exposure (include/fractal_hip.h, "statistics of a kept view") ------------------------------------------------------
@@ -376,7 +382,8 @@ inline double auto_exposure(const Config &config, const ViewStats &stats, double
 // cfg_s = config with width and height times supersample (fr_escape_rows, fr_escape_rows_pt_wide, ...); the result is the
 // road's render (supersampled render) of config with `exposure` set to *exposure_out, byte for byte.
 template <class Escape>
-std::vector<RGB> get_image_auto(const Config &config, uint32_t supersample, double percentile, double *exposure_out, Escape &&escape) {
+std::vector<RGB> get_image_auto(const Config &config, uint32_t supersample, double percentile, double *exposure_out, Escape &&escape,
+                                Transfer transfer = Transfer::Bytes) {
     if (supersample < 1 || supersample > FR_SS_MAX) throw Error(FR_ERR_INVALID_ARGUMENT, "get_image_auto: supersample is 1 .. FR_SS_MAX");
     Config big = config;
     big.width *= supersample;
@@ -389,16 +396,16 @@ std::vector<RGB> get_image_auto(const Config &config, uint32_t supersample, doub
     shown.exposure = auto_exposure(config, view_stats(big, z, iters), percentile);
     if (exposure_out) *exposure_out = shown.exposure;
     std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
-    check(fr_colour_ss_rgb8(&shown, z.data(), 2, iters.data(), config.width, config.height, supersample, 3,
-                            reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB)));
+    check(fr_colour_ss_rgb8_tf(&shown, z.data(), 2, iters.data(), config.width, config.height, supersample, static_cast<int>(transfer), 3,
+                               reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB)));
     return image;
 }
 // ... in the arithmetic of `precision` (FR_PRECISION_F64, FR_PRECISION_F32; the deep precisions with pos_lo = 0)
 inline std::vector<RGB> get_image_auto(const Config &config, int precision = FR_PRECISION_F64, double percentile = 0.99,
-                                       uint32_t supersample = 1, double *exposure_out = nullptr) {
+                                       uint32_t supersample = 1, double *exposure_out = nullptr, Transfer transfer = Transfer::Bytes) {
     return get_image_auto(config, supersample, percentile, exposure_out, [&](const Config &big, double *z, uint32_t *iters) {
         check(fr_escape_rows(&big, precision, 0, big.height, z, iters));
-    });
+    }, transfer);
 }
 
 // ---- distance estimation (include/fractal_hip.h, "DE") ------------------------------------------------------------------------
@@ -422,23 +429,24 @@ std::vector<RGB> get_image_de(const Config &config, double thickness, Escape &&e
 // device; the larger DE arrays exist only a band at a time.  road FR_PT_ROAD_PLAIN or FR_PT_ROAD_BLA.  The overloads below take
 // it as their last argument; 1 is the form without it, byte for byte.
 inline std::vector<RGB> get_image_ss_de(const Config &config, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
-                                        int road, int bits, double thickness, uint32_t supersample) {
+                                        int road, int bits, double thickness, uint32_t supersample, Transfer transfer = Transfer::Bytes) {
     std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
-    check(fr_render_rows_ss_de(&config, precision, pos_lo, centre, road, bits, thickness, supersample, 0, config.height, 3,
-                               reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB)));
+    check(fr_render_rows_ss_de_tf(&config, precision, pos_lo, centre, road, bits, thickness, supersample, static_cast<int>(transfer), 0, config.height, 3,
+                                  reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB)));
     return image;
 }
 // ... on the F64 road, or on PT with a dd centre (precision FR_PRECISION_PT; pos_lo may be null)
 inline std::vector<RGB> get_image_de(const Config &config, double thickness = 1.0, int precision = FR_PRECISION_F64,
-                                     const fr_imaginary *pos_lo = nullptr, uint32_t supersample = 1) {
-    if (supersample != 1) return get_image_ss_de(config, precision, pos_lo, nullptr, FR_PT_ROAD_PLAIN, 0, thickness, supersample);
+                                     const fr_imaginary *pos_lo = nullptr, uint32_t supersample = 1, Transfer transfer = Transfer::Bytes) {
+    if (supersample != 1) return get_image_ss_de(config, precision, pos_lo, nullptr, FR_PT_ROAD_PLAIN, 0, thickness, supersample, transfer);
     return get_image_de(config, thickness, [&](const Config &c, double *z, uint32_t *iters, double *der) {
         check(fr_escape_rows_de(&c, precision, pos_lo, 0, c.height, z, iters, der));
     });
 }
 // ... on PT with a wide centre
-inline std::vector<RGB> get_image_de(const Config &config, const fr_wide_centre &centre, double thickness = 1.0, uint32_t supersample = 1) {
-    if (supersample != 1) return get_image_ss_de(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_PLAIN, 0, thickness, supersample);
+inline std::vector<RGB> get_image_de(const Config &config, const fr_wide_centre &centre, double thickness = 1.0, uint32_t supersample = 1,
+                                     Transfer transfer = Transfer::Bytes) {
+    if (supersample != 1) return get_image_ss_de(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_PLAIN, 0, thickness, supersample, transfer);
     return get_image_de(config, thickness, [&](const Config &c, double *z, uint32_t *iters, double *der) {
         check(fr_escape_rows_de_pt_wide(&c, &centre, 0, c.height, z, iters, der));
     });
@@ -446,8 +454,9 @@ inline std::vector<RGB> get_image_de(const Config &config, const fr_wide_centre 
 // ... on BLA-PT (include/fractal_hip.h, "DE ON BLA-PT"): the derivative goes through the table's skips; a dd centre
 // (config.pos, pos_lo; pos_lo may be null) or a wide centre, never both
 inline std::vector<RGB> get_image_de(const Config &config, Bla bla, double thickness = 1.0, const fr_imaginary *pos_lo = nullptr,
-                                     const fr_wide_centre *centre = nullptr, uint32_t supersample = 1) {
-    if (supersample != 1) return get_image_ss_de(config, FR_PRECISION_PT, pos_lo, centre, FR_PT_ROAD_BLA, bla.bits, thickness, supersample);
+                                     const fr_wide_centre *centre = nullptr, uint32_t supersample = 1, Transfer transfer = Transfer::Bytes) {
+    if (supersample != 1)
+        return get_image_ss_de(config, FR_PRECISION_PT, pos_lo, centre, FR_PT_ROAD_BLA, bla.bits, thickness, supersample, transfer);
     return get_image_de(config, thickness, [&](const Config &c, double *z, uint32_t *iters, double *der) {
         check(fr_escape_rows_de_pt_bla(&c, pos_lo, centre, bla.bits, 0, c.height, z, iters, der));
     });
@@ -469,17 +478,18 @@ inline std::vector<RGB> get_image_de(const Config &config, Scaled scaled, const 
 // ... anti-aliased (include/fractal_hip.h, "SUPERSAMPLED SCALED DE"): supersample x supersample samples per pixel, each shaded on
 // the scaled view with thickness * supersample in sample pixels, box-filtered on the device; supersample = 1 is the call above.
 inline std::vector<RGB> get_image_de(const Config &config, Scaled scaled, const fr_wide_centre &centre, double thickness,
-                                     uint32_t supersample) {
+                                     uint32_t supersample, Transfer transfer = Transfer::Bytes) {
     std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
-    check(fr_render_rows_ss_de_pt_scaled(&config, &centre, scaled.bits, thickness, supersample, 0, config.height, 3,
-                                         reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB)));
+    check(fr_render_rows_ss_de_pt_scaled_tf(&config, &centre, scaled.bits, thickness, supersample, static_cast<int>(transfer), 0, config.height, 3,
+                                            reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB)));
     return image;
 }
 // the same into device memory through a workspace the caller lends (fr_ss_de_workspace_bytes), asynchronous on hip_stream
 inline void get_image_de_device(const Config &config, Scaled scaled, const fr_wide_centre &centre, double thickness, uint32_t supersample,
-                                void *d_out, void *d_work, size_t work_len, int channels = 4, void *hip_stream = nullptr) {
-    check(fr_render_rows_ss_de_pt_scaled_device(&config, &centre, scaled.bits, thickness, supersample, 0, config.height, channels, d_out,
-                                                static_cast<size_t>(channels) * config.width * config.height, d_work, work_len, hip_stream));
+                                void *d_out, void *d_work, size_t work_len, int channels = 4, void *hip_stream = nullptr, Transfer transfer = Transfer::Bytes) {
+    check(fr_render_rows_ss_de_pt_scaled_tf_device(&config, &centre, scaled.bits, thickness, supersample, static_cast<int>(transfer), 0, config.height,
+                                                   channels, d_out, static_cast<size_t>(channels) * config.width * config.height, d_work,
+                                                   work_len, hip_stream));
 }
 // ---- adaptive anti-aliased distance estimation (include/fractal_hip.h, "ADAPTIVE SUPERSAMPLED DE") -----------------------------
 // get_image_de's supersampled forms with an AdaptiveDe behind them: the distance-shaded supersample x supersample samples only at
@@ -493,27 +503,28 @@ struct AdaptiveDe {
     uint64_t *refined = nullptr;
 };
 inline std::vector<RGB> get_image_ss_adaptive_de(const Config &config, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
-                                                 int road, int bits, double thickness, uint32_t supersample, AdaptiveDe adaptive) {
+                                                 int road, int bits, double thickness, uint32_t supersample, AdaptiveDe adaptive,
+                                                 Transfer transfer = Transfer::Bytes) {
     std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
-    check(fr_render_rows_ss_adaptive_de(&config, precision, pos_lo, centre, road, bits, thickness, supersample, adaptive.threshold,
-                                        adaptive.reach, 0, config.height, 3, reinterpret_cast<uint8_t *>(image.data()),
-                                        image.size() * sizeof(RGB), adaptive.refined));
+    check(fr_render_rows_ss_adaptive_de_tf(&config, precision, pos_lo, centre, road, bits, thickness, supersample, static_cast<int>(transfer),
+                                           adaptive.threshold, adaptive.reach, 0, config.height, 3,
+                                           reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB), adaptive.refined));
     return image;
 }
 // ... on the F64 road, or on PT with a dd centre (precision FR_PRECISION_PT; pos_lo may be null)
 inline std::vector<RGB> get_image_de(const Config &config, double thickness, int precision, const fr_imaginary *pos_lo, uint32_t supersample,
-                                     AdaptiveDe adaptive) {
-    return get_image_ss_adaptive_de(config, precision, pos_lo, nullptr, FR_PT_ROAD_PLAIN, 0, thickness, supersample, adaptive);
+                                     AdaptiveDe adaptive, Transfer transfer = Transfer::Bytes) {
+    return get_image_ss_adaptive_de(config, precision, pos_lo, nullptr, FR_PT_ROAD_PLAIN, 0, thickness, supersample, adaptive, transfer);
 }
 // ... on PT with a wide centre
 inline std::vector<RGB> get_image_de(const Config &config, const fr_wide_centre &centre, double thickness, uint32_t supersample,
-                                     AdaptiveDe adaptive) {
-    return get_image_ss_adaptive_de(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_PLAIN, 0, thickness, supersample, adaptive);
+                                     AdaptiveDe adaptive, Transfer transfer = Transfer::Bytes) {
+    return get_image_ss_adaptive_de(config, FR_PRECISION_PT, nullptr, &centre, FR_PT_ROAD_PLAIN, 0, thickness, supersample, adaptive, transfer);
 }
 // ... on BLA-PT: a dd centre (config.pos, pos_lo; pos_lo may be null) or a wide centre, never both
 inline std::vector<RGB> get_image_de(const Config &config, Bla bla, double thickness, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
-                                     uint32_t supersample, AdaptiveDe adaptive) {
-    return get_image_ss_adaptive_de(config, FR_PRECISION_PT, pos_lo, centre, FR_PT_ROAD_BLA, bla.bits, thickness, supersample, adaptive);
+                                     uint32_t supersample, AdaptiveDe adaptive, Transfer transfer = Transfer::Bytes) {
+    return get_image_ss_adaptive_de(config, FR_PRECISION_PT, pos_lo, centre, FR_PT_ROAD_BLA, bla.bits, thickness, supersample, adaptive, transfer);
 }
 // A DE view past 2^440 kept on the device is (z, iters, w, m, der), 56 bytes per pixel ("RESUMABLE SCALED DE"): the state render and
 // the extension that raises its cap in place, scaled derivative included.  The plain loop's (scaled.bits must be -1: the table
@@ -537,9 +548,9 @@ inline void colour_de_rows_device(const Config &config, const void *d_z, const v
 // A kept anti-aliased DE view is a kept DE view of the config with width and height times supersample (36 * supersample^2 bytes
 // per output pixel): this colours, shades and box-filters it in one kernel.  config is the OUTPUT's; thickness in output pixels.
 inline void colour_de_rows_ss_device(const Config &config, const void *d_z, const void *d_iters, const void *d_der, uint32_t supersample,
-                                     double thickness, void *d_out, int channels = 4, void *hip_stream = nullptr) {
-    check(fr_colour_de_rows_ss_device(&config, d_z, d_iters, d_der, config.width, config.height, supersample, thickness, channels, d_out,
-                                      static_cast<size_t>(channels) * config.width * config.height, hip_stream));
+                                     double thickness, void *d_out, int channels = 4, void *hip_stream = nullptr, Transfer transfer = Transfer::Bytes) {
+    check(fr_colour_de_rows_ss_tf_device(&config, d_z, d_iters, d_der, config.width, config.height, supersample, static_cast<int>(transfer), thickness,
+                                         channels, d_out, static_cast<size_t>(channels) * config.width * config.height, hip_stream));
 }
 
 }  // namespace fractal

@@ -1499,6 +1499,96 @@ int fr_render_rows_ss_adaptive_de(const fr_config *cfg, int precision, const fr_
                                   int bits, double thickness, uint32_t supersample, int threshold, double reach, uint32_t y0, uint32_t y1,
                                   int channels, uint8_t *out, size_t out_len, uint64_t *refined /* may be NULL */);
 
+/* LINEAR-LIGHT SUPERSAMPLING (the _tf calls below).  Every supersampled call ends in the same reduction, the average of the s*s
+ * sample BYTES.  The bytes are display-encoded (sRGB) values, so that average is not an average of light: one white sample
+ * among black ones at s = 4 comes out at grey level 16 where the light's average is 71.  The _tf calls take a `transfer`
+ * argument that chooses in which space the samples are averaged; FR_SS_TRANSFER_BYTES is the byte average of every call above. */
+typedef enum fr_ss_transfer { FR_SS_TRANSFER_BYTES = 0, FR_SS_TRANSFER_SRGB = 1 } fr_ss_transfer;
+/* DEFINITION.  Let f be the sRGB decoding function of IEC 61966-2-1:
+ *   f(x) = x / 12.92 for x <= 0.04045,  f(x) = ((x + 0.055) / 1.055)^2.4 otherwise.
+ * Decode table    L[v], v = 0 .. 255, uint16:  L[v] = floor(65535 * f(v / 255) + 1/2).
+ * Threshold table T[k], k = 1 .. 255, uint16:  T[k] = ceil(65535 * f((k - 1/2) / 255)).
+ * Both are committed as a generated include, csrc/fr_srgb_table.inc, beside its generator csrc/gen_srgb_table.py (`decimal` at
+ * 100 digits).  No value is a tie: on the linear segment the argument is a rational that is never an integer or a half-integer,
+ * elsewhere it is irrational.  THE COMMITTED NUMBERS ARE THE DEFINITION; the formulas say where they come from.  To pin them:
+ *   L[0..4] = 0, 20, 40, 60, 80;  L[127] = 13909, L[128] = 14146;  L[254] = 64952, L[255] = 65535;
+ *   T[1..4] = 10, 30, 50, 70;  T[128] = 14028, T[255] = 65244;
+ *   SHA-256 of L as 256 little-endian uint16:      fdb7af3c01815a2118db8e50aac3c2304205ccc3f381f8976c588642c1aa60b6
+ *   SHA-256 of T[1..255] as 255 little-endian uint16: f419ad49e531756005e2997106d1ec956b5c2839e9456ce3cb3df413d133d59a
+ * Encode: E(m) for 0 <= m <= 65535 is the number of k in 1 .. 255 with m >= T[k].  Any search order gives the same value.
+ * The filter, for FR_SS_TRANSFER_SRGB, with H the s-times-larger image exactly as each existing call defines it:
+ *   n(X,Y,c)   = sum over j < s, i < s of L[ H(s*X+i, s*Y+j, c) ]          (at most 64 * 65535 < 2^22)
+ *   m(X,Y,c)   = (n + floor(s*s/2)) / (s*s)     integer, truncating        (at most 65535)
+ *   out(X,Y,c) = E(m)                           alpha stays 255 with 4 channels
+ * For FR_SS_TRANSFER_BYTES, out is the existing byte formula, and every _tf call equals its existing twin byte for byte (the
+ * twin IS the _tf call with FR_SS_TRANSFER_BYTES).  Any other transfer value is FR_ERR_INVALID_ARGUMENT with a message that
+ * names the argument, before any device work and before any other argument is looked at.
+ * Properties:
+ *   - E(L[v]) = v for every v (DESIGN.md 3.31 proves it from the tables: L is strictly increasing and no L[v] is closer than 9
+ *     to a threshold).  So s*s equal samples give that byte, and s = 1 is the plain render for either transfer;
+ *   - E is non-decreasing;
+ *   - adaptive forms: the probe P, the neighbour rule on P's bytes and the `near` rule are untouched; only F changes, to the
+ *     filter above.  A non-edge pixel shows P in both transfers, so a flat region is identical in both; any split into row
+ *     pieces still gives the whole image's bytes and the same `refined` count;
+ *   - distance shading stays where it is, on the sample's bytes before the filter: H is unchanged.
+ * The workspace of every call is unchanged: bands are still packed r,g,b (or the DE arrays), and fr_ss_workspace_bytes,
+ * fr_ss_de_workspace_bytes and the two adaptive workspace calls serve the _tf calls as they are.  Each _tf call has its twin's
+ * signature with `int transfer` behind `supersample`; domains, refusals and their messages, buffer rules, asynchrony and the
+ * profiling reports are the twin's. */
+int fr_box_filter_rgb8_tf(const uint8_t *src, uint32_t width, uint32_t rows, uint32_t supersample, int transfer, int channels, uint8_t *out,
+                          size_t out_len);
+int fr_box_filter_rgb8_tf_device(const void *d_src, uint32_t width, uint32_t rows, uint32_t supersample, int transfer, int channels,
+                                 void *d_out, size_t out_len, void *hip_stream);
+int fr_render_rows_ss_tf(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t supersample, int transfer, uint32_t y0,
+                         uint32_t y1, int channels, uint8_t *out, size_t out_len, const fr_render_opts *opts);
+int fr_render_rows_ss_tf_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t supersample, int transfer,
+                                uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len, void *d_work, size_t work_len,
+                                void *hip_stream, const fr_render_opts *opts);
+int fr_render_rows_ss_pt_tf(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                            uint32_t supersample, int transfer, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len);
+int fr_render_rows_ss_pt_tf_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                                   uint32_t supersample, int transfer, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len,
+                                   void *d_work, size_t work_len, void *hip_stream);
+int fr_colour_rows_ss_tf_device(const fr_config *cfg, const void *d_z, int z_width, const void *d_iters, uint32_t width, uint32_t rows,
+                                uint32_t supersample, int transfer, int channels, void *d_out, size_t out_len, void *hip_stream);
+int fr_colour_ss_rgb8_tf(const fr_config *cfg, const double *z, int z_width, const uint32_t *iters, uint32_t width, uint32_t rows,
+                         uint32_t supersample, int transfer, int channels, uint8_t *out, size_t out_len);
+int fr_colour_de_rows_ss_tf_device(const fr_config *cfg, const void *d_z, const void *d_iters, const void *d_der, uint32_t width,
+                                   uint32_t rows, uint32_t supersample, int transfer, double thickness, int channels, void *d_out,
+                                   size_t out_len, void *hip_stream);
+int fr_colour_de_ss_rgb8_tf(const fr_config *cfg, const double *z, const uint32_t *iters, const double *der, uint32_t width, uint32_t rows,
+                            uint32_t supersample, int transfer, double thickness, int channels, uint8_t *out, size_t out_len);
+int fr_render_rows_ss_de_tf(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+                            double thickness, uint32_t supersample, int transfer, uint32_t y0, uint32_t y1, int channels, uint8_t *out,
+                            size_t out_len);
+int fr_render_rows_ss_de_tf_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
+                                   int bits, double thickness, uint32_t supersample, int transfer, uint32_t y0, uint32_t y1, int channels,
+                                   void *d_out, size_t out_len, void *d_work, size_t work_len, void *hip_stream);
+int fr_render_rows_ss_de_pt_scaled_tf(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t supersample,
+                                      int transfer, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len);
+int fr_render_rows_ss_de_pt_scaled_tf_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness,
+                                             uint32_t supersample, int transfer, uint32_t y0, uint32_t y1, int channels, void *d_out,
+                                             size_t out_len, void *d_work, size_t work_len, void *hip_stream);
+int fr_render_rows_ss_adaptive_tf(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
+                                  int bits, uint32_t supersample, int transfer, int threshold, uint32_t y0, uint32_t y1, int channels,
+                                  uint8_t *out, size_t out_len, uint64_t *refined /* may be NULL */);
+int fr_render_rows_ss_adaptive_tf_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
+                                         int road, int bits, uint32_t supersample, int transfer, int threshold, uint32_t y0, uint32_t y1,
+                                         int channels, void *d_out, size_t out_len, void *d_work, size_t work_len,
+                                         void *d_refined /* uint64 on the device, may be NULL */, void *hip_stream);
+int fr_render_rows_ss_adaptive_de_tf(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
+                                     int bits, double thickness, uint32_t supersample, int transfer, int threshold, double reach, uint32_t y0,
+                                     uint32_t y1, int channels, uint8_t *out, size_t out_len, uint64_t *refined /* may be NULL */);
+int fr_render_rows_ss_adaptive_de_tf_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
+                                            int road, int bits, double thickness, uint32_t supersample, int transfer, int threshold,
+                                            double reach, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len, void *d_work,
+                                            size_t work_len, void *d_refined /* uint64 on the device, may be NULL */, void *hip_stream);
+/* Host only, no device needed: pointers into the library's own copy of L (256 entries) and of T[1 .. 255] (255 entries, T[k] at
+ * index k - 1), so a binding or a test reads the definition from the library itself.  Either argument may be NULL.  fr_ss_table
+ * is `const uint16_t *`: the call is int fr_ss_transfer_tables(const uint16_t **decode256, const uint16_t **thresholds255). */
+typedef const uint16_t *fr_ss_table;
+int fr_ss_transfer_tables(fr_ss_table *decode256, fr_ss_table *thresholds255);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* Exact sum of EXECUTED loop iterations over the pixels (x, y) with x % sx == 0, y % sy == 0 of
