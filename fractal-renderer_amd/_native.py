@@ -515,6 +515,7 @@ PROTOTYPES = {
          C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)],
     ),
     "fr_debug_ss_adaptive_grid": (C.c_int, [C.c_uint32]),
+    "fr_debug_ss_host_work_cap": (C.c_int, [C.c_size_t]),
     "fr_ss_adaptive_de_workspace_bytes": (
         C.c_int, [C.POINTER(fr_config), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
     "fr_render_rows_ss_adaptive_de_device": (

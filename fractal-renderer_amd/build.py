@@ -25,7 +25,7 @@ _LAST = ["fr_de.hip", "fr_de_bla.hip", "fr_ss_de.hip", "fr_de_scaled.hip", "fr_s
 SOURCES = [s for s in KERNEL_SOURCES if s not in _LAST] + ["fr_dispatch.hip", "fr_api.hip", "fr_host.hip", "fr_multi.hip",
                                                            "fr_fern.hip", "fr_dd.hip", "fr_pt.hip", "fr_wide.hip", "fr_ss.hip"] + _LAST
 DEPS = SOURCES + ["fr_kernels.h", "fr_launch.h", "fr_ctx.h", "fr_wide.h", "fr_bla.h", "fr_math.h", "fr_colour.h", "fr_log2_table.inc",
-                  "fr_de.h", "fr_de_shade.h", "fr_ss.h", "fr_scaled.h", "fr_ss_list.h", "fr_ss_de_sample.h", "fr_srgb.h", "fr_srgb_table.inc",
+                  "fr_de.h", "fr_de_shade.h", "fr_ss.h", "fr_scaled.h", "fr_ss_list.h", "fr_ss_adaptive.h", "fr_ss_de_sample.h", "fr_srgb.h", "fr_srgb_table.inc",
                   os.path.join("..", "..", "include", "fractal_hip.h")]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",

@@ -14,6 +14,10 @@
  *   - colour_filter_kernel / fr_launch_colour_filter and fr_colour_rows_ss_device / fr_colour_ss_rgb8: a KEPT anti-aliased
  *     view — (z, iters) of cfg_s in device memory — coloured and filtered in one kernel, no RGB workspace in between.
  *
+ * The host plumbing is fr_ss.h's ("3.32"): the band loop ss_bands under render_ss_bands, ss_rows_device / ss_rows_host
+ * behind fr_render_rows_ss_pt's checks and under fr_render_rows_ss's host form, host_rgb (fr_ctx.h) under the filter's and the
+ * recolour's host forms.  fr_render_rows_ss_device keeps its own buffer rules: it looks at the output before the workspace.
+ *
  * LINEAR-LIGHT SUPERSAMPLING (include/fractal_hip.h): every entry point here is a one-line forward to its _tf form, which holds
  * the body and takes `transfer`; FR_SS_TRANSFER_SRGB launches the LINEAR instance of the filter (fr_srgb.h: the two tables in
  * 1 KiB of LDS, a decode where the byte is read, three 22-bit sums, the same division, an eight-step bisection to encode).
@@ -37,6 +41,7 @@
 #include "fr_ss.h"
 
 #include <algorithm>
+#include <atomic>
 
 #include "fr_math.h"
 
@@ -478,6 +483,13 @@ hipError_t fr_launch_colour_filter(const fr_kparams &p, const double *z, uint32_
 
 namespace fr {
 
+static std::atomic<size_t> g_host_work_cap{0}; /* fr_debug_ss_host_work_cap: 0 = kSsHostWorkCap */
+
+size_t ss_host_work_cap() {
+    const size_t cap = g_host_work_cap.load();
+    return cap ? cap : kSsHostWorkCap;
+}
+
 int check_transfer(int transfer) {
     if (transfer != FR_SS_TRANSFER_BYTES && transfer != FR_SS_TRANSFER_SRGB)
         return fail(FR_ERR_INVALID_ARGUMENT, "transfer must be FR_SS_TRANSFER_BYTES (0) or FR_SS_TRANSFER_SRGB (1)");
@@ -524,40 +536,22 @@ uint64_t ss_band_rows(const SsPlan &pl, uint32_t s, size_t work_len) {
 
 namespace {
 
-/* Rows [y0, y1) supersampled into device memory on `stream`: the band loop of every supersampled render.  band(ctx, ya, yb,
- * ko, stream) is the launch of source rows [ya, yb) of cfg_s as packed r,g,b into ko.rgb — a road's row launch (fr_bla.hip:
- * bla_rows; DESIGN.md, "3.17") with the band's rows — between the profiling events; pending_sample: a view sample to post
- * behind the last band (-1 none).  Arguments already checked, s >= 2, the range and the width not empty.  No host
- * synchronisation beyond what the band's launch has. */
+/* The packed-RGB bands of fr_render_rows_ss and fr_render_rows_ss_pt: ss_bands (fr_ss.h) with the box filter behind each band.
+ * band(ctx, ya, yb, ko, stream) is the launch of source rows [ya, yb) of cfg_s as packed r,g,b into ko.rgb, the workspace;
+ * s >= 2. */
 template <class Band>
 int render_ss_bands(Ctx &ctx, const SsPlan &pl, uint32_t s, int transfer, uint32_t y0, unsigned bpp, void *d_out, void *d_work, size_t work_len,
                     hipStream_t stream, int pending_sample, Band &&band) {
     const uint32_t width = pl.cfg_s.width / s;
-    const uint64_t rows = ss_band_rows(pl, s, work_len);
-    const uint32_t Y0 = s * y0, Y1 = (uint32_t)(Y0 + pl.src_rows);
-    /* profiling: the span of the whole call — the first band records the start (and the render kernel's name), the
-     * later bands record nothing, the end goes behind the last filter */
-    Profiling &pr = profiling();
-    struct ProfGuard {
-        Profiling &pr;
-        bool was;
-        ~ProfGuard() { pr.enabled = was; }
-    } prof_guard{pr, pr.enabled};
     fr_kout ko{};
     ko.rgb = static_cast<uint8_t *>(d_work);
-    int rc = FR_OK;
-    for (uint64_t ya = Y0; ya < Y1 && rc == FR_OK; ya += rows) {
-        const uint32_t yb = (uint32_t)std::min<uint64_t>(ya + rows, Y1);
-        rc = band(ctx, (uint32_t)ya, yb, ko, stream);
-        if (rc != FR_OK) break;
-        pr.enabled = false;
-        uint8_t *dst = static_cast<uint8_t *>(d_out) + (uint64_t)(((uint32_t)ya - Y0) / s) * width * bpp;
-        const hipError_t e = fr_launch_box_filter(d_work, width, (yb - (uint32_t)ya) / s, s, bpp, dst, stream, transfer);
-        if (e != hipSuccess) rc = fail_hip(e, "fr_launch_box_filter");
-    }
-    ctx.post_sample(pending_sample, stream); /* behind the last band */
-    if (rc == FR_OK && prof_guard.was && pr.have) HIP_TRY(hipEventRecord(pr.e1, stream));
-    return rc;
+    return ss_bands(ctx, pl, s, y0, bpp, d_out, work_len, stream, pending_sample,
+                    [&](Ctx &c, uint32_t ya, uint32_t yb, uint8_t *dst, uint32_t out_rows, hipStream_t st) {
+                        const int rc = band(c, ya, yb, ko, st);
+                        if (rc != FR_OK) return rc;
+                        const hipError_t e = fr_launch_box_filter(d_work, width, out_rows, s, bpp, dst, st, transfer);
+                        return e == hipSuccess ? FR_OK : fail_hip(e, "fr_launch_box_filter");
+                    });
 }
 
 /* the bands of fr_render_rows_ss(_device): the precision's own row render */
@@ -678,6 +672,12 @@ int fr_ss_transfer_tables(fr_ss_table *decode256, fr_ss_table *thresholds255) {
     return FR_OK;
 }
 
+int fr_debug_ss_host_work_cap(size_t bytes) {
+    if (bytes & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "bytes must be 0 (the default cap of 256 MiB) or a multiple of 8");
+    g_host_work_cap.store(bytes);
+    return FR_OK;
+}
+
 int fr_ss_workspace_bytes(const fr_config *cfg, uint32_t supersample, uint32_t y0, uint32_t y1, size_t *min_bytes,
                           size_t *best_bytes) {
     SsPlan pl;
@@ -741,14 +741,10 @@ int fr_render_rows_ss_tf(const fr_config *cfg, int precision, const fr_imaginary
             return fr_host_render_rows_deep(cfg, precision, Centre{pos_lo, nullptr}, y0, y1, out, out_len, (unsigned)channels, opts);
         return fr_host_render_rows(cfg, precision, y0, y1, out, out_len, (unsigned)channels, opts);
     }
-    const size_t work_len = std::max(pl.min_bytes, std::min(pl.best_bytes, kSsHostWorkCap));
-    return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) {
-        int rc = ctx.reserve(ctx.ss_work, work_len);
-        if (rc != FR_OK) return rc;
-        rc = render_ss_device(ctx, pl, precision, pos_lo, supersample, transfer, y0, (unsigned)channels, d_out, ctx.ss_work.ptr, work_len, stream, o);
-        if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
-        return rc;
-    });
+    return ss_rows_host(cfg, ss_host_work_len(pl), y0, y1, channels, out, out_len,
+                        [&](Ctx &ctx, const fr_kout &ko, void *d_work, size_t work_len, hipStream_t stream) {
+                            return render_ss_device(ctx, pl, precision, pos_lo, supersample, transfer, y0, (unsigned)channels, ko.rgb, d_work, work_len, stream, o);
+                        });
 }
 
 int fr_render_rows_ss(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t supersample, uint32_t y0,
@@ -786,19 +782,13 @@ int fr_box_filter_rgb8_tf(const uint8_t *src, uint32_t width, uint32_t rows, uin
     if (!src || !out) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array (src, out)");
     if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*rows");
     const size_t src_bytes = (size_t)3u * supersample * width * ((size_t)supersample * rows);
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    rc = ctx->reserve(ctx->ss_work, src_bytes);
-    if (rc == FR_OK) rc = ctx->reserve(ctx->rgb, need);
-    if (rc != FR_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->ss_work.ptr, src, src_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(fr_launch_box_filter(ctx->ss_work.ptr, width, rows, supersample, (uint32_t)channels, ctx->rgb.ptr, ctx->stream, transfer));
-    HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FR_OK;
+    return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) -> int {
+        const int rc = ctx.reserve(ctx.ss_work, src_bytes);
+        if (rc != FR_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx.ss_work.ptr, src, src_bytes, hipMemcpyHostToDevice, stream));
+        HIP_TRY(fr_launch_box_filter(ctx.ss_work.ptr, width, rows, supersample, (uint32_t)channels, d_out, stream, transfer));
+        return FR_OK;
+    });
 }
 
 int fr_box_filter_rgb8(const uint8_t *src, uint32_t width, uint32_t rows, uint32_t supersample, int channels, uint8_t *out,
@@ -813,13 +803,10 @@ int fr_render_rows_ss_pt_tf_device(const fr_config *cfg, const fr_imaginary *pos
     SsRoad r;
     const int rc = ss_road_check(cfg, pos_lo, centre, road, bits, supersample, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
-    if (supersample > 1 && (size_t)cfg->width * (size_t)(y1 - y0) != 0) { /* the workspace, then rgb_rows_device's buffer rules */
-        if (work_len < r.pl.min_bytes) return fail(FR_ERR_BUFFER_TOO_SMALL, "work_len < min_bytes of fr_ss_workspace_bytes");
-        if (!d_work) return fail(FR_ERR_INVALID_ARGUMENT, "d_work is NULL");
-    }
-    return rgb_rows_device(cfg, y0, y1, channels, d_out, out_len, hip_stream, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
-        return ss_road_rows(ctx, r, cfg, supersample, transfer, y0, y1, (unsigned)channels, ko, d_work, work_len, stream);
-    });
+    return ss_rows_device(cfg, r.pl, "work_len < min_bytes of fr_ss_workspace_bytes", false, y0, y1, channels, d_out, out_len, d_work, work_len,
+                          hip_stream, [&](Ctx &ctx, const fr_kout &ko, void *work, size_t len, hipStream_t stream) {
+                              return ss_road_rows(ctx, r, cfg, supersample, transfer, y0, y1, (unsigned)channels, ko, work, len, stream);
+                          });
 }
 
 int fr_render_rows_ss_pt_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
@@ -834,14 +821,10 @@ int fr_render_rows_ss_pt_tf(const fr_config *cfg, const fr_imaginary *pos_lo, co
     SsRoad r;
     const int rc = ss_road_check(cfg, pos_lo, centre, road, bits, supersample, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
-    const size_t work_len = supersample > 1 ? std::max(r.pl.min_bytes, std::min(r.pl.best_bytes, kSsHostWorkCap)) : 0;
-    return rgb_rows_host(cfg, y0, y1, channels, out, out_len, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
-        int rc = ctx.reserve(ctx.ss_work, work_len);
-        if (rc != FR_OK) return rc;
-        rc = ss_road_rows(ctx, r, cfg, supersample, transfer, y0, y1, (unsigned)channels, ko, ctx.ss_work.ptr, work_len, stream);
-        if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
-        return rc;
-    });
+    return ss_rows_host(cfg, ss_host_work_len(r.pl), y0, y1, channels, out, out_len, /* s = 1: a plan of 0 bytes */
+                        [&](Ctx &ctx, const fr_kout &ko, void *work, size_t len, hipStream_t stream) {
+                            return ss_road_rows(ctx, r, cfg, supersample, transfer, y0, y1, (unsigned)channels, ko, work, len, stream);
+                        });
 }
 
 int fr_render_rows_ss_pt(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
@@ -885,24 +868,18 @@ int fr_colour_ss_rgb8_tf(const fr_config *cfg, const double *z, int z_width, con
     if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*rows");
     const size_t n = (size_t)supersample * width * ((size_t)supersample * rows);
     const size_t zb = n * (size_t)z_width * sizeof(double), ib = n * sizeof(uint32_t);
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    rc = ctx->reserve(ctx->z, zb);
-    if (rc == FR_OK) rc = ctx->reserve(ctx->iters, ib);
-    if (rc == FR_OK) rc = ctx->reserve(ctx->rgb, need);
-    if (rc != FR_OK) return rc;
-    fr_kparams p;
-    fill_params(cfg, default_opts(), p);
-    HIP_TRY(hipMemcpyAsync(ctx->z.ptr, z, zb, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->iters.ptr, iters, ib, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(fr_launch_colour_filter(p, static_cast<const double *>(ctx->z.ptr), (uint32_t)z_width, static_cast<const uint32_t *>(ctx->iters.ptr),
-                                    width, rows, supersample, (uint32_t)channels, ctx->rgb.ptr, ctx->stream, transfer));
-    HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FR_OK;
+    return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) -> int {
+        int rc = ctx.reserve(ctx.z, zb);
+        if (rc == FR_OK) rc = ctx.reserve(ctx.iters, ib);
+        if (rc != FR_OK) return rc;
+        fr_kparams p;
+        fill_params(cfg, default_opts(), p);
+        HIP_TRY(hipMemcpyAsync(ctx.z.ptr, z, zb, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(ctx.iters.ptr, iters, ib, hipMemcpyHostToDevice, stream));
+        HIP_TRY(fr_launch_colour_filter(p, static_cast<const double *>(ctx.z.ptr), (uint32_t)z_width, static_cast<const uint32_t *>(ctx.iters.ptr),
+                                        width, rows, supersample, (uint32_t)channels, d_out, stream, transfer));
+        return FR_OK;
+    });
 }
 
 int fr_colour_ss_rgb8(const fr_config *cfg, const double *z, int z_width, const uint32_t *iters, uint32_t width, uint32_t rows,

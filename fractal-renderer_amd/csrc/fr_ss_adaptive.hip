@@ -17,15 +17,15 @@
  *      device memory, which keeps the call asynchronous and balances the very uneven cost of edge pixels.
  * The entry points: fr_ss_adaptive_workspace_bytes, fr_render_rows_ss_adaptive_device, fr_render_rows_ss_adaptive (the same
  * into a host buffer through context scratch, by row pieces above the host workspace cap) and the test hook
- * fr_debug_ss_adaptive_grid.
+ * fr_debug_ss_adaptive_grid.  Each call is its domain check (ssa_check) and fr_ss_adaptive.h's skeleton around ssa_render; the
+ * workspace's layout is that header's too ("3.32").
  */
 #include <algorithm>
 #include <atomic>
-#include <vector>
 
 #include "fr_bla.h"
 #include "fr_math.h"
-#include "fr_ss.h"
+#include "fr_ss_adaptive.h"
 #include "fr_ss_list.h"
 
 namespace {
@@ -143,24 +143,6 @@ struct SsaRoad {
     int tau;
 };
 
-/* the workspace of rows [y0, y1) of cfg (not empty): the probe colours of rows [ya, yb), the list, the two counters */
-struct SsaLayout {
-    uint32_t ya, yb;
-    size_t list_off, counters_off, total;
-};
-
-SsaLayout ssa_layout(const fr_config *cfg, uint32_t y0, uint32_t y1) {
-    SsaLayout l;
-    l.ya = y0 > 0 ? y0 - 1 : 0;
-    l.yb = y1 < cfg->height ? y1 + 1 : cfg->height;
-    const uint64_t probe = (uint64_t)3u * cfg->width * (l.yb - l.ya);
-    const uint64_t list = (uint64_t)4u * cfg->width * (y1 - y0);
-    l.list_off = (size_t)((probe + 7u) & ~7ull);
-    l.counters_off = l.list_off + (size_t)((list + 7u) & ~7ull);
-    l.total = l.counters_off + 2 * sizeof(unsigned long long);
-    return l;
-}
-
 /* everything the adaptive calls check before any device work, short of the buffers: the sizes, the threshold, then the road's own
  * domain on cfg_s with fr_render_rows_ss_de_device's argument rule per precision and road, plus FR_PT_ROAD_SCALED */
 int ssa_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits, uint32_t s,
@@ -209,13 +191,13 @@ int ssa_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, c
 }
 
 /* Rows [y0, y1) of the adaptive render into d_out on `stream`: the three passes.  Arguments checked, the rows and the width not
- * empty, d_work holds ssa_layout's bytes.  No host synchronisation (PT roads: apart from computing and uploading the view's
+ * empty, d_work holds ss_adaptive_layout's bytes.  No host synchronisation (PT roads: apart from computing and uploading the view's
  * orbit and table when the context does not hold them yet), no allocation; the count stays in the workspace's first counter. */
 int ssa_render(Ctx &ctx, const SsaRoad &r, const fr_config *cfg, uint32_t s, int transfer, uint32_t y0, uint32_t y1, unsigned bpp, void *d_out, void *d_work,
                hipStream_t stream) {
     const fr_config *cs = &r.pl.cfg_s;
-    const SsaLayout l = ssa_layout(cfg, y0, y1);
-    uint8_t *const probe = static_cast<uint8_t *>(d_work);
+    const SsAdaptiveLayout l = ss_adaptive_layout(cfg, y0, y1, false);
+    uint8_t *const probe = static_cast<uint8_t *>(d_work) + l.colour_off; /* 0: no DE arrays in front */
     uint32_t *const list = reinterpret_cast<uint32_t *>(probe + l.list_off);
     unsigned long long *const counters = reinterpret_cast<unsigned long long *>(probe + l.counters_off);
     const bool escape_algo = cfg->algo == FR_ALGO_MANDELBROT || cfg->algo == FR_ALGO_JULIA;
@@ -302,23 +284,6 @@ int ssa_render(Ctx &ctx, const SsaRoad &r, const fr_config *cfg, uint32_t s, int
     return prof_end(stream, kname);
 }
 
-/* the buffer rules of the device form, after the domain */
-int ssa_check_buffers(const fr_config *cfg, uint32_t y0, uint32_t y1, int channels, const void *d_out, size_t out_len, const void *d_work,
-                      size_t work_len, const void *d_refined) {
-    const size_t need = (size_t)channels * cfg->width * (size_t)(y1 - y0);
-    if (!d_out) return fail(FR_ERR_INVALID_ARGUMENT, "d_out is NULL");
-    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*(y1-y0)");
-    if (channels == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u))
-        return fail(FR_ERR_INVALID_ARGUMENT, "RGBA8 output (d_out) must be 4-byte aligned");
-    if (work_len < ssa_layout(cfg, y0, y1).total)
-        return fail(FR_ERR_BUFFER_TOO_SMALL, "work_len < bytes of fr_ss_adaptive_workspace_bytes");
-    if (!d_work) return fail(FR_ERR_INVALID_ARGUMENT, "d_work is NULL");
-    if (reinterpret_cast<uintptr_t>(d_work) & 7u)
-        return fail(FR_ERR_INVALID_ARGUMENT, "d_work must be 8-byte aligned (the list and the counters lie in it)");
-    if (reinterpret_cast<uintptr_t>(d_refined) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_refined must be 8-byte aligned (a uint64)");
-    return FR_OK;
-}
-
 }  // namespace
 }  // namespace fr
 
@@ -327,12 +292,7 @@ using namespace fr;
 extern "C" {
 
 int fr_ss_adaptive_workspace_bytes(const fr_config *cfg, uint32_t supersample, uint32_t y0, uint32_t y1, size_t *bytes) {
-    SsPlan pl;
-    const int rc = ss_plan(cfg, supersample, y0, y1, pl);
-    if (rc != FR_OK) return rc;
-    if (!bytes) return fail(FR_ERR_INVALID_ARGUMENT, "bytes is NULL");
-    *bytes = (size_t)cfg->width * (size_t)(y1 - y0) == 0 ? 0 : ssa_layout(cfg, y0, y1).total;
-    return FR_OK;
+    return ss_adaptive_workspace_bytes(cfg, supersample, y0, y1, false, bytes);
 }
 
 int fr_render_rows_ss_adaptive_tf_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
@@ -340,26 +300,13 @@ int fr_render_rows_ss_adaptive_tf_device(const fr_config *cfg, int precision, co
                                       size_t out_len, void *d_work, size_t work_len, void *d_refined, void *hip_stream) {
     if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsaRoad r;
-    int rc = ssa_check(cfg, precision, pos_lo, centre, road, bits, supersample, threshold, y0, y1, channels, r);
+    const int rc = ssa_check(cfg, precision, pos_lo, centre, road, bits, supersample, threshold, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
-    if (y0 == y1) return FR_OK; /* a no-op: no device, no buffer */
-    if (reinterpret_cast<uintptr_t>(d_refined) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_refined must be 8-byte aligned (a uint64)");
-    if (cfg->width == 0) { /* no pixels: refined = 0 */
-        if (!d_refined) return FR_OK;
-        return device_form(hip_stream, [&](Ctx &, hipStream_t stream) -> int {
-            HIP_TRY(hipMemsetAsync(d_refined, 0, sizeof(uint64_t), stream));
-            return FR_OK;
-        });
-    }
-    rc = ssa_check_buffers(cfg, y0, y1, channels, d_out, out_len, d_work, work_len, d_refined);
-    if (rc != FR_OK) return rc;
-    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) -> int {
-        const int rc = ssa_render(ctx, r, cfg, supersample, transfer, y0, y1, (unsigned)channels, d_out, d_work, stream);
-        if (rc != FR_OK || !d_refined) return rc;
-        const char *count = static_cast<const char *>(d_work) + ssa_layout(cfg, y0, y1).counters_off;
-        HIP_TRY(hipMemcpyAsync(d_refined, count, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
-        return FR_OK;
-    });
+    return ss_adaptive_device(cfg, false, "work_len < bytes of fr_ss_adaptive_workspace_bytes",
+                              "d_work must be 8-byte aligned (the list and the counters lie in it)", y0, y1, channels, d_out, out_len, d_work, work_len,
+                              d_refined, hip_stream, [&](Ctx &ctx, uint32_t ya, uint32_t yb, void *dst, void *work, hipStream_t stream) {
+                                  return ssa_render(ctx, r, cfg, supersample, transfer, ya, yb, (unsigned)channels, dst, work, stream);
+                              });
 }
 
 int fr_render_rows_ss_adaptive_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
@@ -375,37 +322,10 @@ int fr_render_rows_ss_adaptive_tf(const fr_config *cfg, int precision, const fr_
     SsaRoad r;
     const int rc = ssa_check(cfg, precision, pos_lo, centre, road, bits, supersample, threshold, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
-    if (refined) *refined = 0;
-    if (y0 == y1 || cfg->width == 0) return FR_OK;
-    /* row pieces whose workspace stays under the host roads' cap (one row at least): the definition makes them exact */
-    const auto bound = [&](uint32_t n) { /* ssa_layout's total for n rows with a neighbour row on either side */
-        return (((uint64_t)3u * cfg->width * ((uint64_t)n + 2) + 7u) & ~7ull) + (((uint64_t)4u * cfg->width * n + 7u) & ~7ull) + 16u;
-    };
-    uint32_t piece = y1 - y0;
-    while (piece > 1 && bound(piece) > kSsHostWorkCap) piece = (piece + 1) / 2;
-    const size_t work_len = (size_t)bound(piece);
-    std::vector<uint64_t> counts(((size_t)(y1 - y0) + piece - 1) / piece, 0);
-    const int rc2 = rgb_rows_host(cfg, y0, y1, channels, out, out_len, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
-        int rc = ctx.reserve(ctx.ss_work, work_len);
-        size_t k = 0;
-        for (uint32_t ya = y0; ya < y1 && rc == FR_OK; ya += piece, k++) {
-            const uint32_t yb = (uint32_t)std::min<uint64_t>((uint64_t)ya + piece, y1);
-            SsaRoad rp = r; /* the piece's plan: its source rows */
-            rp.pl.src_rows = (uint64_t)supersample * (yb - ya);
-            uint8_t *dst = ko.rgb + (uint64_t)(ya - y0) * cfg->width * (unsigned)channels;
-            rc = ssa_render(ctx, rp, cfg, supersample, transfer, ya, yb, (unsigned)channels, dst, ctx.ss_work.ptr, stream);
-            if (rc != FR_OK) break;
-            const char *count = static_cast<const char *>(ctx.ss_work.ptr) + ssa_layout(cfg, ya, yb).counters_off;
-            const hipError_t e = hipMemcpyAsync(&counts[k], count, sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
-            if (e != hipSuccess) rc = fail_hip(e, "hipMemcpyAsync(refined)");
-        }
-        if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
-        return rc;
-    });
-    if (rc2 != FR_OK) return rc2;
-    if (refined)
-        for (const uint64_t c : counts) *refined += c;
-    return FR_OK;
+    return ss_adaptive_host(cfg, false, y0, y1, channels, out, out_len, refined,
+                            [&](Ctx &ctx, uint32_t ya, uint32_t yb, void *dst, void *work, hipStream_t stream) {
+                                return ssa_render(ctx, r, cfg, supersample, transfer, ya, yb, (unsigned)channels, dst, work, stream);
+                            });
 }
 
 int fr_render_rows_ss_adaptive(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,

@@ -16,16 +16,13 @@
  * `near` reads the pixel's own probe only, so a row piece needs the same one-row halo as the colour rule and no more.
  * The entry points: fr_ss_adaptive_de_workspace_bytes, fr_render_rows_ss_adaptive_de_device and fr_render_rows_ss_adaptive_de (the
  * same into a host buffer through context scratch, by row pieces above the host workspace cap).  fr_debug_ss_adaptive_grid
- * (fr_ss_adaptive.hip) sets the refine grid here too.
+ * (fr_ss_adaptive.hip) sets the refine grid here too.  Each call is its domain check (ssad_check) and fr_ss_adaptive.h's skeleton
+ * around ssad_render; the workspace's layout is that header's, with the DE arrays in front ("3.32").
  */
-#include <algorithm>
-#include <cmath>
-#include <vector>
-
 #include "fr_ctx.h"
 #include "fr_de.h"
 #include "fr_math.h"
-#include "fr_ss.h"
+#include "fr_ss_adaptive.h"
 #include "fr_ss_list.h"
 
 namespace {
@@ -100,36 +97,6 @@ struct SsadRoad {
     double ts, rs, pixels;
 };
 
-constexpr uint64_t ceil8(uint64_t v) { return (v + 7u) & ~7ull; }
-
-/* the workspace of rows [y0, y1) of cfg (not empty): the probe's z, der, iters and colours of rows [ya, yb), the list, the two
- * counters.  ssad_offsets takes the two row counts apart, so that the host form can bound a piece — at most a neighbour row on
- * either side — before it knows where the piece lies. */
-struct SsadLayout {
-    uint32_t ya, yb;
-    size_t der_off, iters_off, colour_off, list_off, counters_off, total;
-};
-
-SsadLayout ssad_offsets(uint32_t width, uint64_t probe_rows, uint64_t rows) {
-    SsadLayout l{};
-    const uint64_t n = (uint64_t)width * probe_rows;
-    l.der_off = (size_t)(16u * n);
-    l.iters_off = l.der_off + (size_t)(16u * n);
-    l.colour_off = l.iters_off + (size_t)ceil8(4u * n);
-    l.list_off = l.colour_off + (size_t)ceil8(3u * n);
-    l.counters_off = l.list_off + (size_t)ceil8((uint64_t)4u * width * rows);
-    l.total = l.counters_off + 2 * sizeof(unsigned long long);
-    return l;
-}
-
-SsadLayout ssad_layout(const fr_config *cfg, uint32_t y0, uint32_t y1) {
-    const uint32_t ya = y0 > 0 ? y0 - 1 : 0, yb = y1 < cfg->height ? y1 + 1 : cfg->height;
-    SsadLayout l = ssad_offsets(cfg->width, yb - ya, y1 - y0);
-    l.ya = ya;
-    l.yb = yb;
-    return l;
-}
-
 /* everything the calls check before any device work, short of the buffers: the sizes, the thickness, the reach, the threshold,
  * then fr_render_rows_ss_de_device's argument rule per precision and road with the road's own DE domain on cfg_s */
 int ssad_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
@@ -137,9 +104,8 @@ int ssad_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, 
     int rc = ss_plan(cfg, s, y0, y1, r.pl);
     if (rc == FR_OK) rc = check_channels(channels);
     if (rc != FR_OK) return rc;
-    r.ts = thickness * (double)s;
-    if (!(thickness >= 0.0 && r.ts <= 0x1p20))
-        return fail(FR_ERR_INVALID_ARGUMENT, "thickness must be finite with 0 <= thickness * supersample <= 2^20 (output pixels; 0 = no shading)");
+    rc = ss_de_thickness(thickness, s, r.ts);
+    if (rc != FR_OK) return rc;
     r.rs = reach * (double)s;
     if (!(reach >= 0.0 && r.rs <= 0x1p20))
         return fail(FR_ERR_INVALID_ARGUMENT, "reach must be finite with 0 <= reach * supersample <= 2^20 (output pixels; 0 = the colour rule alone)");
@@ -149,7 +115,7 @@ int ssad_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, 
         return fail(FR_ERR_INVALID_ARGUMENT, "width * (y1 - y0) must be below 2^32: the edge list holds 32-bit pixel indices; call by row pieces");
     const fr_config *cs = &r.pl.cfg_s;
     const uint32_t Y0 = s * y0, Y1 = (uint32_t)(Y0 + r.pl.src_rows);
-    r.pixels = (double)(s * cfg->height) * std::fmin(std::fabs(cfg->scale.re), std::fabs(cfg->scale.im));
+    r.pixels = ss_de_pixels(cfg, s);
     r.precision = precision;
     r.road = road;
     r.bits = bits;
@@ -177,12 +143,12 @@ int ssad_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, 
 }
 
 /* Rows [y0, y1) of the adaptive DE render into d_out on `stream`: the four passes.  Arguments checked, the rows and the width not
- * empty, d_work holds ssad_layout's bytes.  No host synchronisation (PT roads: apart from computing and uploading the view's
+ * empty, d_work holds ss_adaptive_layout's bytes.  No host synchronisation (PT roads: apart from computing and uploading the view's
  * orbit and table when the context does not hold them yet), no allocation; the count stays in the workspace's first counter. */
 int ssad_render(Ctx &ctx, const SsadRoad &r, const fr_config *cfg, uint32_t s, int transfer, uint32_t y0, uint32_t y1, unsigned bpp, void *d_out,
                 void *d_work, hipStream_t stream) {
     const fr_config *cs = &r.pl.cfg_s;
-    const SsadLayout l = ssad_layout(cfg, y0, y1);
+    const SsAdaptiveLayout l = ss_adaptive_layout(cfg, y0, y1, true);
     char *const base = static_cast<char *>(d_work);
     double *const d_z = reinterpret_cast<double *>(base), *const d_der = reinterpret_cast<double *>(base + l.der_off);
     uint32_t *const d_iters = reinterpret_cast<uint32_t *>(base + l.iters_off);
@@ -252,23 +218,6 @@ int ssad_render(Ctx &ctx, const SsadRoad &r, const fr_config *cfg, uint32_t s, i
     return prof_end(stream, kname);
 }
 
-/* the buffer rules of the device form, after the domain */
-int ssad_check_buffers(const fr_config *cfg, uint32_t y0, uint32_t y1, int channels, const void *d_out, size_t out_len, const void *d_work,
-                       size_t work_len, const void *d_refined) {
-    const size_t need = (size_t)channels * cfg->width * (size_t)(y1 - y0);
-    if (!d_out) return fail(FR_ERR_INVALID_ARGUMENT, "d_out is NULL");
-    if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*(y1-y0)");
-    if (channels == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u))
-        return fail(FR_ERR_INVALID_ARGUMENT, "RGBA8 output (d_out) must be 4-byte aligned");
-    if (work_len < ssad_layout(cfg, y0, y1).total)
-        return fail(FR_ERR_BUFFER_TOO_SMALL, "work_len < bytes of fr_ss_adaptive_de_workspace_bytes");
-    if (!d_work) return fail(FR_ERR_INVALID_ARGUMENT, "d_work is NULL");
-    if (reinterpret_cast<uintptr_t>(d_work) & 7u)
-        return fail(FR_ERR_INVALID_ARGUMENT, "d_work must be 8-byte aligned (z, der, the list and the counters lie in it)");
-    if (reinterpret_cast<uintptr_t>(d_refined) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_refined must be 8-byte aligned (a uint64)");
-    return FR_OK;
-}
-
 }  // namespace
 }  // namespace fr
 
@@ -277,12 +226,7 @@ using namespace fr;
 extern "C" {
 
 int fr_ss_adaptive_de_workspace_bytes(const fr_config *cfg, uint32_t supersample, uint32_t y0, uint32_t y1, size_t *bytes) {
-    SsPlan pl;
-    const int rc = ss_plan(cfg, supersample, y0, y1, pl);
-    if (rc != FR_OK) return rc;
-    if (!bytes) return fail(FR_ERR_INVALID_ARGUMENT, "bytes is NULL");
-    *bytes = (size_t)cfg->width * (size_t)(y1 - y0) == 0 ? 0 : ssad_layout(cfg, y0, y1).total;
-    return FR_OK;
+    return ss_adaptive_workspace_bytes(cfg, supersample, y0, y1, true, bytes);
 }
 
 int fr_render_rows_ss_adaptive_de_tf_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
@@ -291,26 +235,13 @@ int fr_render_rows_ss_adaptive_de_tf_device(const fr_config *cfg, int precision,
                                          void *d_refined, void *hip_stream) {
     if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
     SsadRoad r;
-    int rc = ssad_check(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, threshold, reach, y0, y1, channels, r);
+    const int rc = ssad_check(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, threshold, reach, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
-    if (y0 == y1) return FR_OK; /* a no-op: no device, no buffer */
-    if (reinterpret_cast<uintptr_t>(d_refined) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_refined must be 8-byte aligned (a uint64)");
-    if (cfg->width == 0) { /* no pixels: refined = 0 */
-        if (!d_refined) return FR_OK;
-        return device_form(hip_stream, [&](Ctx &, hipStream_t stream) -> int {
-            HIP_TRY(hipMemsetAsync(d_refined, 0, sizeof(uint64_t), stream));
-            return FR_OK;
-        });
-    }
-    rc = ssad_check_buffers(cfg, y0, y1, channels, d_out, out_len, d_work, work_len, d_refined);
-    if (rc != FR_OK) return rc;
-    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) -> int {
-        const int rc = ssad_render(ctx, r, cfg, supersample, transfer, y0, y1, (unsigned)channels, d_out, d_work, stream);
-        if (rc != FR_OK || !d_refined) return rc;
-        const char *count = static_cast<const char *>(d_work) + ssad_layout(cfg, y0, y1).counters_off;
-        HIP_TRY(hipMemcpyAsync(d_refined, count, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
-        return FR_OK;
-    });
+    return ss_adaptive_device(cfg, true, "work_len < bytes of fr_ss_adaptive_de_workspace_bytes",
+                              "d_work must be 8-byte aligned (z, der, the list and the counters lie in it)", y0, y1, channels, d_out, out_len, d_work,
+                              work_len, d_refined, hip_stream, [&](Ctx &ctx, uint32_t ya, uint32_t yb, void *dst, void *work, hipStream_t stream) {
+                                  return ssad_render(ctx, r, cfg, supersample, transfer, ya, yb, (unsigned)channels, dst, work, stream);
+                              });
 }
 
 int fr_render_rows_ss_adaptive_de_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
@@ -327,36 +258,10 @@ int fr_render_rows_ss_adaptive_de_tf(const fr_config *cfg, int precision, const 
     SsadRoad r;
     const int rc = ssad_check(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, threshold, reach, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
-    if (refined) *refined = 0;
-    if (y0 == y1 || cfg->width == 0) return FR_OK;
-    /* row pieces whose workspace stays under the host roads' cap (one row at least): the definition makes them exact; a piece of
-     * n rows has a neighbour row on either side at the most */
-    const auto bound = [&](uint32_t n) { return (uint64_t)ssad_offsets(cfg->width, (uint64_t)n + 2, n).total; };
-    uint32_t piece = y1 - y0;
-    while (piece > 1 && bound(piece) > kSsHostWorkCap) piece = (piece + 1) / 2;
-    const size_t work_len = (size_t)bound(piece);
-    std::vector<uint64_t> counts(((size_t)(y1 - y0) + piece - 1) / piece, 0);
-    const int rc2 = rgb_rows_host(cfg, y0, y1, channels, out, out_len, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
-        int rc = ctx.reserve(ctx.ss_work, work_len);
-        size_t k = 0;
-        for (uint32_t ya = y0; ya < y1 && rc == FR_OK; ya += piece, k++) {
-            const uint32_t yb = (uint32_t)std::min<uint64_t>((uint64_t)ya + piece, y1);
-            SsadRoad rp = r; /* the piece's plan: its source rows */
-            rp.pl.src_rows = (uint64_t)supersample * (yb - ya);
-            uint8_t *dst = ko.rgb + (uint64_t)(ya - y0) * cfg->width * (unsigned)channels;
-            rc = ssad_render(ctx, rp, cfg, supersample, transfer, ya, yb, (unsigned)channels, dst, ctx.ss_work.ptr, stream);
-            if (rc != FR_OK) break;
-            const char *count = static_cast<const char *>(ctx.ss_work.ptr) + ssad_layout(cfg, ya, yb).counters_off;
-            const hipError_t e = hipMemcpyAsync(&counts[k], count, sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
-            if (e != hipSuccess) rc = fail_hip(e, "hipMemcpyAsync(refined)");
-        }
-        if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
-        return rc;
-    });
-    if (rc2 != FR_OK) return rc2;
-    if (refined)
-        for (const uint64_t c : counts) *refined += c;
-    return FR_OK;
+    return ss_adaptive_host(cfg, true, y0, y1, channels, out, out_len, refined,
+                            [&](Ctx &ctx, uint32_t ya, uint32_t yb, void *dst, void *work, hipStream_t stream) {
+                                return ssad_render(ctx, r, cfg, supersample, transfer, ya, yb, (unsigned)channels, dst, work, stream);
+                            });
 }
 
 int fr_render_rows_ss_adaptive_de(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,

@@ -10,7 +10,9 @@
  *     fr_render_rows_ss_de (the same into a host buffer, through context scratch), and SUPERSAMPLED SCALED DE's
  *     fr_render_rows_ss_de_pt_scaled(_device): the same band loop and the same fused kernel with DE ON SCALED PT's row launch
  *     (fr_de.h: scaled_de_render_rows) and the scaled view's pixels.
- * The render kernels are not touched: a band is an ordinary row-range DE render of the large image.
+ * The render kernels are not touched: a band is an ordinary row-range DE render of the large image.  The band loop, the two
+ * halves of a banded call and the thickness and pixels of the shade are fr_ss.h's ("3.32"); the recolour's host form
+ * goes through host_rgb (fr_ctx.h).
  *
  * Kernel shape: colour_filter_kernel<S>'s (fr_ss.hip), which it differs from in phase 1 only.  Memory-bound:
  * 36 B per sample in, 3 or 4 B per output pixel out.
@@ -27,7 +29,6 @@
  *   - 64-bit element offsets (a kept 3840 x 2160 DE view at s = 4 is 4.8 GB); plain vector loads and stores only.
  */
 #include <algorithm>
-#include <cmath>
 
 #include "fr_bla.h" /* scaled_consts */
 #include "fr_ctx.h"
@@ -308,21 +309,6 @@ hipError_t fr_launch_colour_de_filter(const fr_kparams &p, const double *z, cons
 namespace fr {
 namespace {
 
-constexpr uint32_t kDeSampleBytes = 36; /* z 16 + der 16 + iters 4 */
-
-/* Ts = T * s, one product; the domain keeps it inside fr_colour_de_rows_device's own */
-int ss_de_thickness(double thickness, uint32_t s, double &ts) {
-    ts = thickness * (double)s;
-    if (!(thickness >= 0.0 && ts <= 0x1p20))
-        return fail(FR_ERR_INVALID_ARGUMENT, "thickness must be finite with 0 <= thickness * supersample <= 2^20 (output pixels; 0 = no shading)");
-    return FR_OK;
-}
-
-/* sample pixels per unit of the plane along the tighter axis: the last factor of D on cfg_s, one product */
-double ss_de_pixels(const fr_config *cfg, uint32_t s) {
-    return (double)(s * cfg->height) * std::fmin(std::fabs(cfg->scale.re), std::fabs(cfg->scale.im));
-}
-
 /* the domain of fr_colour_de_rows_ss_device / fr_colour_de_ss_rgb8 short of the buffers */
 int colour_de_ss_check(const fr_config *cfg, uint32_t width, uint32_t rows, uint32_t s, double thickness, int channels, double &ts) {
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
@@ -348,21 +334,28 @@ struct SsDeRoad {
     }
 };
 
+/* the head of both checks below: the sizes at 36 bytes per sample, the channels, the thickness; then the road as it was asked for */
+int ss_de_head(const fr_config *cfg, int precision, const Centre &c, int road, int bits, double thickness, uint32_t s, uint32_t y0, uint32_t y1,
+               int channels, SsDeRoad &r) {
+    int rc = ss_plan(cfg, s, y0, y1, r.pl, kDeSampleBytes);
+    if (rc == FR_OK) rc = check_channels(channels);
+    if (rc == FR_OK) rc = ss_de_thickness(thickness, s, r.ts);
+    r.precision = precision;
+    r.road = road;
+    r.bits = bits;
+    r.c = c;
+    return rc;
+}
+
 /* everything fr_render_rows_ss_de(_device) check before any device work: the sizes, the thickness, then the road's own DE
  * domain on cfg_s, by the code its plain calls run */
 int ss_de_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
                 double thickness, uint32_t s, uint32_t y0, uint32_t y1, int channels, SsDeRoad &r) {
-    int rc = ss_plan(cfg, s, y0, y1, r.pl, kDeSampleBytes);
-    if (rc == FR_OK) rc = check_channels(channels);
-    if (rc == FR_OK) rc = ss_de_thickness(thickness, s, r.ts);
+    const int rc = ss_de_head(cfg, precision, Centre{pos_lo, centre}, road, bits, thickness, s, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
     const fr_config *cs = &r.pl.cfg_s;
     const uint32_t Y0 = s * y0, Y1 = (uint32_t)(Y0 + r.pl.src_rows);
     r.pixels = ss_de_pixels(cfg, s);
-    r.precision = precision;
-    r.road = road;
-    r.bits = bits;
-    r.c = Centre{pos_lo, centre};
     if (road == FR_PT_ROAD_SCALED)
         return fail(FR_ERR_INVALID_ARGUMENT, "FR_PT_ROAD_SCALED: distance estimation on SCALED PT is out of scope; supersampled DE takes "
                                              "FR_PRECISION_F64, FR_PRECISION_PT (dd or wide centre) and BLA-PT");
@@ -385,55 +378,50 @@ int ss_de_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo,
  * fr_escape_rows_de_pt_scaled's launch and `pixels` the last factor of D on the scaled view of cfg_s. */
 int ss_de_scaled_check(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t s, uint32_t y0, uint32_t y1,
                        int channels, SsDeRoad &r) {
-    int rc = ss_plan(cfg, s, y0, y1, r.pl, kDeSampleBytes);
-    if (rc == FR_OK) rc = check_channels(channels);
-    if (rc == FR_OK) rc = ss_de_thickness(thickness, s, r.ts);
+    int rc = ss_de_head(cfg, FR_PRECISION_PT, Centre{nullptr, centre, true}, FR_PT_ROAD_SCALED, bits, thickness, s, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
     const uint32_t Y0 = s * y0, Y1 = (uint32_t)(Y0 + r.pl.src_rows);
-    r.precision = FR_PRECISION_PT;
-    r.road = FR_PT_ROAD_SCALED;
-    r.bits = bits;
-    r.c = Centre{nullptr, centre, true};
     rc = scaled_de_domain(&r.pl.cfg_s, r.c, r.bits, Y0, Y1);
     if (rc != FR_OK) return rc;
     const ScaledConsts k = scaled_consts(cfg); /* cfg_s shares cfg's scale */
-    r.pixels = (double)(s * cfg->height) * std::fmin(std::fabs(k.sre), std::fabs(k.sim));
+    r.pixels = ss_de_pixels(cfg, s, k.sre, k.sim);
     return FR_OK;
 }
 
-/* The band loop: render_ss_bands' (fr_ss.hip) with the DE arrays in the workspace and the fused kernel behind each band.  A band
- * of n samples lies at d_work as z (16 n bytes) | der (16 n) | iters (4 n).  Profiling: the span of the whole call — the first
- * band records the start and the render kernel's name, the later bands record nothing, the end goes behind the last filter.
- * Arguments already checked, the range and the width not empty.  No host synchronisation beyond what the band's launch has. */
+/* The bands: ss_bands (fr_ss.h) with the DE arrays in the workspace and the fused kernel behind each band.  A band of n samples
+ * lies at d_work as z (16 n bytes) | der (16 n) | iters (4 n). */
 int render_ss_de_bands(Ctx &ctx, const SsDeRoad &r, uint32_t s, int transfer, uint32_t y0, unsigned bpp, void *d_out, void *d_work, size_t work_len,
                        hipStream_t stream) {
-    const SsPlan &pl = r.pl;
-    const uint32_t width = pl.cfg_s.width / s;
-    const uint64_t rows = ss_band_rows(pl, s, work_len);
-    const uint32_t Y0 = s * y0, Y1 = (uint32_t)(Y0 + pl.src_rows);
-    Profiling &pr = profiling();
-    struct ProfGuard {
-        Profiling &pr;
-        bool was;
-        ~ProfGuard() { pr.enabled = was; }
-    } prof_guard{pr, pr.enabled};
+    const uint32_t width = r.pl.cfg_s.width / s;
     fr_kparams p;
-    fill_params(&pl.cfg_s, default_opts(), p);
-    int rc = FR_OK;
-    for (uint64_t ya = Y0; ya < Y1 && rc == FR_OK; ya += rows) {
-        const uint32_t yb = (uint32_t)std::min<uint64_t>(ya + rows, Y1);
-        const uint64_t n = (uint64_t)(yb - (uint32_t)ya) * pl.cfg_s.width;
-        double *const d_z = static_cast<double *>(d_work), *const d_der = d_z + 2 * n;
-        uint32_t *const d_iters = reinterpret_cast<uint32_t *>(d_der + 2 * n);
-        rc = r.rows(ctx, (uint32_t)ya, yb, d_z, d_iters, d_der, stream);
-        if (rc != FR_OK) break;
-        pr.enabled = false;
-        uint8_t *dst = static_cast<uint8_t *>(d_out) + (uint64_t)(((uint32_t)ya - Y0) / s) * width * bpp;
-        const hipError_t e = fr_launch_colour_de_filter(p, d_z, d_iters, d_der, width, (yb - (uint32_t)ya) / s, s, r.pixels, r.ts, bpp, dst, stream, transfer);
-        if (e != hipSuccess) rc = fail_hip(e, "fr_launch_colour_de_filter");
-    }
-    if (rc == FR_OK && prof_guard.was && pr.have) HIP_TRY(hipEventRecord(pr.e1, stream));
-    return rc;
+    fill_params(&r.pl.cfg_s, default_opts(), p);
+    return ss_bands(ctx, r.pl, s, y0, bpp, d_out, work_len, stream, -1,
+                    [&](Ctx &c, uint32_t ya, uint32_t yb, uint8_t *dst, uint32_t out_rows, hipStream_t st) {
+                        const uint64_t n = (uint64_t)(yb - ya) * r.pl.cfg_s.width;
+                        double *const d_z = static_cast<double *>(d_work), *const d_der = d_z + 2 * n;
+                        uint32_t *const d_iters = reinterpret_cast<uint32_t *>(d_der + 2 * n);
+                        const int rc = r.rows(c, ya, yb, d_z, d_iters, d_der, st);
+                        if (rc != FR_OK) return rc;
+                        const hipError_t e = fr_launch_colour_de_filter(p, d_z, d_iters, d_der, width, out_rows, s, r.pixels, r.ts, bpp, dst, st, transfer);
+                        return e == hipSuccess ? FR_OK : fail_hip(e, "fr_launch_colour_de_filter");
+                    });
+}
+
+/* the four banded entry points behind their checks (fr_ss.h: ss_rows_device, ss_rows_host) */
+int ss_de_rows_device(const fr_config *cfg, const SsDeRoad &r, uint32_t s, int transfer, uint32_t y0, uint32_t y1, int channels, void *d_out,
+                      size_t out_len, void *d_work, size_t work_len, void *hip_stream) {
+    return ss_rows_device(cfg, r.pl, "work_len < min_bytes of fr_ss_de_workspace_bytes", true, y0, y1, channels, d_out, out_len, d_work, work_len,
+                          hip_stream, [&](Ctx &ctx, const fr_kout &ko, void *work, size_t len, hipStream_t stream) {
+                              return render_ss_de_bands(ctx, r, s, transfer, y0, (unsigned)channels, ko.rgb, work, len, stream);
+                          });
+}
+
+int ss_de_rows_host(const fr_config *cfg, const SsDeRoad &r, uint32_t s, int transfer, uint32_t y0, uint32_t y1, int channels, uint8_t *out,
+                    size_t out_len) {
+    return ss_rows_host(cfg, ss_host_work_len(r.pl), y0, y1, channels, out, out_len,
+                        [&](Ctx &ctx, const fr_kout &ko, void *work, size_t len, hipStream_t stream) {
+                            return render_ss_de_bands(ctx, r, s, transfer, y0, (unsigned)channels, ko.rgb, work, len, stream);
+                        });
 }
 
 }  // namespace
@@ -482,26 +470,20 @@ int fr_colour_de_ss_rgb8_tf(const fr_config *cfg, const double *z, const uint32_
     if (out_len < need) return fail(FR_ERR_BUFFER_TOO_SMALL, "out_len < channels*width*rows");
     const size_t n = (size_t)supersample * width * ((size_t)supersample * rows);
     const size_t zb = n * 2 * sizeof(double), ib = n * sizeof(uint32_t);
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    rc = ctx->reserve(ctx->z, 2 * zb); /* z, then der */
-    if (rc == FR_OK) rc = ctx->reserve(ctx->iters, ib);
-    if (rc == FR_OK) rc = ctx->reserve(ctx->rgb, need);
-    if (rc != FR_OK) return rc;
-    double *const d_z = static_cast<double *>(ctx->z.ptr), *const d_der = d_z + 2 * n;
-    fr_kparams p;
-    fill_params(cfg, default_opts(), p);
-    HIP_TRY(hipMemcpyAsync(d_z, z, zb, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_der, der, zb, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->iters.ptr, iters, ib, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(fr_launch_colour_de_filter(p, d_z, static_cast<const uint32_t *>(ctx->iters.ptr), d_der, width, rows, supersample,
-                                       ss_de_pixels(cfg, supersample), ts, (uint32_t)channels, ctx->rgb.ptr, ctx->stream, transfer));
-    HIP_TRY(hipMemcpyAsync(out, ctx->rgb.ptr, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FR_OK;
+    return host_rgb(out, need, [&](Ctx &ctx, void *d_out, hipStream_t stream) -> int {
+        int rc = ctx.reserve(ctx.z, 2 * zb); /* z, then der */
+        if (rc == FR_OK) rc = ctx.reserve(ctx.iters, ib);
+        if (rc != FR_OK) return rc;
+        double *const d_z = static_cast<double *>(ctx.z.ptr), *const d_der = d_z + 2 * n;
+        fr_kparams p;
+        fill_params(cfg, default_opts(), p);
+        HIP_TRY(hipMemcpyAsync(d_z, z, zb, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_der, der, zb, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(ctx.iters.ptr, iters, ib, hipMemcpyHostToDevice, stream));
+        HIP_TRY(fr_launch_colour_de_filter(p, d_z, static_cast<const uint32_t *>(ctx.iters.ptr), d_der, width, rows, supersample,
+                                           ss_de_pixels(cfg, supersample), ts, (uint32_t)channels, d_out, stream, transfer));
+        return FR_OK;
+    });
 }
 
 int fr_colour_de_ss_rgb8(const fr_config *cfg, const double *z, const uint32_t *iters, const double *der, uint32_t width, uint32_t rows,
@@ -525,14 +507,7 @@ int fr_render_rows_ss_de_tf_device(const fr_config *cfg, int precision, const fr
     SsDeRoad r;
     const int rc = ss_de_check(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
-    if ((size_t)cfg->width * (size_t)(y1 - y0) != 0) { /* the workspace, then rgb_rows_device's buffer rules */
-        if (work_len < r.pl.min_bytes) return fail(FR_ERR_BUFFER_TOO_SMALL, "work_len < min_bytes of fr_ss_de_workspace_bytes");
-        if (!d_work) return fail(FR_ERR_INVALID_ARGUMENT, "d_work is NULL");
-        if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_work must be 8-byte aligned (z and der lie in it)");
-    }
-    return rgb_rows_device(cfg, y0, y1, channels, d_out, out_len, hip_stream, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
-        return render_ss_de_bands(ctx, r, supersample, transfer, y0, (unsigned)channels, ko.rgb, d_work, work_len, stream);
-    });
+    return ss_de_rows_device(cfg, r, supersample, transfer, y0, y1, channels, d_out, out_len, d_work, work_len, hip_stream);
 }
 
 int fr_render_rows_ss_de_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
@@ -550,14 +525,7 @@ int fr_render_rows_ss_de_pt_scaled_tf_device(const fr_config *cfg, const fr_wide
     SsDeRoad r;
     const int rc = ss_de_scaled_check(cfg, centre, bits, thickness, supersample, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
-    if ((size_t)cfg->width * (size_t)(y1 - y0) != 0) { /* the workspace, then rgb_rows_device's buffer rules */
-        if (work_len < r.pl.min_bytes) return fail(FR_ERR_BUFFER_TOO_SMALL, "work_len < min_bytes of fr_ss_de_workspace_bytes");
-        if (!d_work) return fail(FR_ERR_INVALID_ARGUMENT, "d_work is NULL");
-        if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail(FR_ERR_INVALID_ARGUMENT, "d_work must be 8-byte aligned (z and der lie in it)");
-    }
-    return rgb_rows_device(cfg, y0, y1, channels, d_out, out_len, hip_stream, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
-        return render_ss_de_bands(ctx, r, supersample, transfer, y0, (unsigned)channels, ko.rgb, d_work, work_len, stream);
-    });
+    return ss_de_rows_device(cfg, r, supersample, transfer, y0, y1, channels, d_out, out_len, d_work, work_len, hip_stream);
 }
 
 int fr_render_rows_ss_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness,
@@ -572,14 +540,7 @@ int fr_render_rows_ss_de_pt_scaled_tf(const fr_config *cfg, const fr_wide_centre
     SsDeRoad r;
     const int rc = ss_de_scaled_check(cfg, centre, bits, thickness, supersample, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
-    const size_t work_len = std::max(r.pl.min_bytes, std::min(r.pl.best_bytes, kSsHostWorkCap));
-    return rgb_rows_host(cfg, y0, y1, channels, out, out_len, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
-        int rc = ctx.reserve(ctx.ss_work, work_len);
-        if (rc != FR_OK) return rc;
-        rc = render_ss_de_bands(ctx, r, supersample, transfer, y0, (unsigned)channels, ko.rgb, ctx.ss_work.ptr, work_len, stream);
-        if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
-        return rc;
-    });
+    return ss_de_rows_host(cfg, r, supersample, transfer, y0, y1, channels, out, out_len);
 }
 
 int fr_render_rows_ss_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t supersample,
@@ -593,14 +554,7 @@ int fr_render_rows_ss_de_tf(const fr_config *cfg, int precision, const fr_imagin
     SsDeRoad r;
     const int rc = ss_de_check(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, y0, y1, channels, r);
     if (rc != FR_OK) return rc;
-    const size_t work_len = std::max(r.pl.min_bytes, std::min(r.pl.best_bytes, kSsHostWorkCap));
-    return rgb_rows_host(cfg, y0, y1, channels, out, out_len, [&](Ctx &ctx, const fr_kout &ko, hipStream_t stream) {
-        int rc = ctx.reserve(ctx.ss_work, work_len);
-        if (rc != FR_OK) return rc;
-        rc = render_ss_de_bands(ctx, r, supersample, transfer, y0, (unsigned)channels, ko.rgb, ctx.ss_work.ptr, work_len, stream);
-        if (rc != FR_OK) (void)hipStreamSynchronize(stream); /* the scratch is reused by the next call */
-        return rc;
-    });
+    return ss_de_rows_host(cfg, r, supersample, transfer, y0, y1, channels, out, out_len);
 }
 
 int fr_render_rows_ss_de(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,

@@ -1447,6 +1447,11 @@ int fr_render_rows_ss_adaptive(const fr_config *cfg, int precision, const fr_ima
 /* Test hook: the refine kernels' grid in workgroups of 4 waves; 0 = the default (it fills the device, capped by the most work
  * the rows can hold).  The output does not depend on it. */
 int fr_debug_ss_adaptive_grid(uint32_t workgroups);
+/* Test hook: the cap in bytes on the workspace that the host forms of the supersampled renders (fr_render_rows_ss, _ss_pt, _ss_de,
+ * _ss_de_pt_scaled, _ss_adaptive, _ss_adaptive_de) reserve in the context's scratch; 0 = the default 256 MiB, any other value
+ * must be a multiple of 8.  A banded call never goes below its min_bytes and an adaptive call never below one row a piece.  The
+ * output does not depend on it. */
+int fr_debug_ss_host_work_cap(size_t bytes);
 
 /* ADAPTIVE SUPERSAMPLED DE (fr_render_rows_ss_adaptive_de(_device) below): ADAPTIVE SUPERSAMPLING and SUPERSAMPLED DE combined.
  * The adaptive call never looks at a non-edge pixel's interior samples; with distance estimation the probe KNOWS what it did not

@@ -499,3 +499,39 @@ def test_production_sizes_under_a_64_mib_workspace(fr, lib, torch, name, width, 
         assert torch.equal(got[..., :3], want), (channels, int((got[..., :3] != want).sum()))
         if channels == 4:
             assert bool((got[..., 3] == 255).all())
+
+
+# ---- the host form's bands under a small workspace cap ---------------------------------------------------------------------
+
+HOOK_W, HOOK_H, HOOK_S, HOOK_Y0, HOOK_Y1 = 37, 21, 3, 2, 19
+
+
+def host_bands_are_the_device_forms(lib, bytes_per_sample, device, host):
+    """What the four banded host forms are tested for under fr_debug_ss_host_work_cap: a cap below min_bytes gives min_bytes —
+    one band of 8 * s source rows, three bands over the 17 rows — and the bytes of the device form over ONE band (best_bytes).
+    device(work_len) and host() render rows [HOOK_Y0, HOOK_Y1) of the 37 x 21 view at s = 3."""
+    row_bytes, rows = bytes_per_sample * HOOK_S * HOOK_W, HOOK_S * (HOOK_Y1 - HOOK_Y0)
+    mn, best = 8 * HOOK_S * row_bytes, rows * row_bytes
+    assert -(-rows // (8 * HOOK_S)) == 3 and best > mn
+    want = device(best)
+    assert want.any()
+    try:
+        check(lib.fr_debug_ss_host_work_cap(8))
+        got = host()
+    finally:
+        check(lib.fr_debug_ss_host_work_cap(0))
+    assert np.array_equal(got, want), int((got != want).sum())
+    return mn, best
+
+
+@pytest.mark.parametrize("channels", [3, 4])
+def test_host_form_under_a_cap_below_min_bytes_is_the_device_form(fr, lib, torch, channels):
+    cfg = fr.Config.from_buffer_copy(bytes(view_config("default", HOOK_W, HOOK_H)))
+
+    def host():
+        out = np.zeros((HOOK_Y1 - HOOK_Y0, HOOK_W, channels), dtype=np.uint8)
+        check(lib.fr_render_rows_ss(C.byref(cfg), F64, None, HOOK_S, HOOK_Y0, HOOK_Y1, channels, out.ctypes.data, out.nbytes, None))
+        return out
+
+    sizes = host_bands_are_the_device_forms(lib, 3, lambda n: ss_device(torch, lib, cfg, F64, HOOK_S, HOOK_Y0, HOOK_Y1, channels, n), host)
+    assert sizes == workspace(lib, cfg, HOOK_S, HOOK_Y0, HOOK_Y1)

@@ -403,3 +403,42 @@ def test_cli_adaptive(fr, native, lib, tmp_path):
     assert r.returncode == 2 and "--adaptive" in r.stderr and "--supersample" in r.stderr
     r = subprocess.run([exe, "--supersample", "2", "--adaptive", "--distance-shade", "1", "4", "4"], capture_output=True, text=True)
     assert r.returncode == 2 and "--adaptive" in r.stderr and "--distance-shade" in r.stderr
+
+
+# ---- the host form's row pieces ---------------------------------------------------------------------------------------------------
+
+HOOK_W, HOOK_H, HOOK_S, HOOK_Y0, HOOK_Y1 = 37, 21, 3, 2, 19
+HOOK_CHAIN = [17, 9, 5, 3, 2, 1]  # the piece sizes the host form can arrive at from 17 rows: it halves, rounding up
+
+
+def hook_caps(workspace_bytes):
+    """piece size -> the cap that forces it: the workspace of a piece of n rows with a neighbour row on either side, which the next
+    larger piece of the chain does not fit"""
+    caps = {}
+    for n in (5, 2, 1):  # 5 + 5 + 5 + 2, eight twos and a one, seventeen ones: the last piece is ragged in the first two
+        caps[n] = workspace_bytes(HOOK_W, HOOK_H, HOOK_Y0, HOOK_Y0 + n)
+        larger = HOOK_CHAIN[HOOK_CHAIN.index(n) - 1]
+        assert caps[n] % 8 == 0 and workspace_bytes(HOOK_W, HOOK_H, HOOK_Y0, HOOK_Y0 + larger) > caps[n]
+    return caps
+
+
+@pytest.mark.parametrize("channels", [3, 4])
+@pytest.mark.parametrize("road", ["f64", "pt"])
+def test_host_form_by_row_pieces_is_the_device_form(fr, native, lib, torch, road, channels):
+    """fr_debug_ss_host_work_cap forces the row-piece loop, which runs only above 256 MiB otherwise: pieces of 5, 2 and 1 rows
+    give the device form's bytes over the whole range and its count"""
+    if road == "f64":
+        cfg, kw, tau = f64_cfg(fr, "seahorse", HOOK_W, HOOK_H), dict(), 8
+    else:
+        d = Deep(fr, native, "J-2^300", HOOK_S, size=(HOOK_W, HOOK_H))
+        cfg, kw, tau = d.cfg, dict(precision=PT, centre=d.c, road=PLAIN, bits=0), 8
+    want, count = ad_device(torch, lib, cfg, HOOK_S, tau, HOOK_Y0, HOOK_Y1, channels, **kw)
+    assert 0 < count < HOOK_W * (HOOK_Y1 - HOOK_Y0), count
+    assert lib.fr_debug_ss_host_work_cap(12) == 1  # not a multiple of 8
+    try:
+        for n, cap in hook_caps(A.workspace_bytes).items():
+            check(lib.fr_debug_ss_host_work_cap(cap))
+            got, refined = ad_host(lib, cfg, HOOK_S, tau, HOOK_Y0, HOOK_Y1, channels, **kw)
+            assert np.array_equal(got, want) and refined == count, (n, cap, int((got != want).sum()), refined, count)
+    finally:
+        check(lib.fr_debug_ss_host_work_cap(0))

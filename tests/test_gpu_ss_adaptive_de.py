@@ -420,3 +420,26 @@ def test_cpp_overload_gives_the_c_calls_bytes(fr, lib, tmp_path):
     assert r.returncode == 0, r.stderr
     assert np.array_equal(np.fromfile(out, dtype=np.uint8).reshape(h, w, 3), want)
     assert r.stdout.split() == ["refined", str(count)]
+
+
+# ---- the host form's row pieces ---------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("channels", [3, 4])
+@pytest.mark.parametrize("view", ["default", "pt-wide"])
+def test_host_form_by_row_pieces_is_the_device_form(fr, lib, torch, view, channels):
+    """fr_debug_ss_host_work_cap forces the row-piece loop, which runs only above 256 MiB otherwise: pieces of 5, 2 and 1 rows
+    (test_gpu_ss_adaptive.py: hook_caps) give the device form's bytes over the whole range and its count"""
+    from test_gpu_ss_adaptive import HOOK_H, HOOK_S, HOOK_W, HOOK_Y0, HOOK_Y1, hook_caps
+
+    cfg, kw = VIEWS[view](fr, HOOK_W, HOOK_H)
+    tau, reach = DEEP.get(view, (16, 1.0))
+    want, count = ad_device(torch, lib, cfg, kw, HOOK_S, 1.5, tau, reach, HOOK_Y0, HOOK_Y1, channels)
+    assert 0 < count < HOOK_W * (HOOK_Y1 - HOOK_Y0), count
+    try:
+        for n, cap in hook_caps(M.workspace_bytes).items():
+            check(lib.fr_debug_ss_host_work_cap(cap))
+            got, refined = ad_host(lib, cfg, kw, HOOK_S, 1.5, tau, reach, HOOK_Y0, HOOK_Y1, channels)
+            assert np.array_equal(got, want) and refined == count, (n, cap, int((got != want).sum()), refined, count)
+    finally:
+        check(lib.fr_debug_ss_host_work_cap(0))

@@ -428,3 +428,15 @@ def test_an_algorithm_without_orbits_renders_black(fr, lib, torch):
         assert not render_device(torch, lib, cfg, {}, s, T, 0, H_OUT, 3, mn).any()
         rgba = render_device(torch, lib, cfg, {}, s, T, 0, H_OUT, 4, mn)
         assert not rgba[..., :3].any() and (rgba[..., 3] == 255).all()
+
+
+@pytest.mark.parametrize("channels", [3, 4])
+def test_host_form_under_a_cap_below_min_bytes_is_the_device_form(fr, lib, torch, channels):
+    """fr_render_rows_ss_de on the F64 road (test_gpu_ss.py: host_bands_are_the_device_forms)"""
+    from test_gpu_ss import HOOK_H, HOOK_S, HOOK_W, HOOK_Y0, HOOK_Y1, host_bands_are_the_device_forms
+
+    cfg = DE.default_view(fr.Config.new(), HOOK_W, HOOK_H)
+    sizes = host_bands_are_the_device_forms(
+        lib, 36, lambda n: render_device(torch, lib, cfg, {}, HOOK_S, T, HOOK_Y0, HOOK_Y1, channels, n),
+        lambda: render_host(lib, cfg, {}, HOOK_S, T, HOOK_Y0, HOOK_Y1, channels))
+    assert sizes == fr.ss_de_workspace_bytes(cfg, HOOK_S, HOOK_Y0, HOOK_Y1)

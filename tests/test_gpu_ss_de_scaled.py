@@ -272,3 +272,22 @@ def test_profiling_reports_the_roads_kernel(fr, native, lib, torch):
             assert name.value == kernel and ms.value > 0, (bits, name.value, ms.value)
     finally:
         check(lib.fr_set_profiling(0))
+
+
+@pytest.mark.parametrize("channels", [3, 4])
+def test_host_form_under_a_cap_below_min_bytes_is_the_device_form(fr, native, lib, torch, channels):
+    """fr_render_rows_ss_de_pt_scaled on its table road (test_gpu_ss.py: host_bands_are_the_device_forms)"""
+    from test_gpu_ss import HOOK_H, HOOK_S, HOOK_W, HOOK_Y0, HOOK_Y1, host_bands_are_the_device_forms
+
+    v = S.view(fr.Config.new, S.J_900[:3] + (HOOK_W, HOOK_H) + S.J_900[5:])
+    centre = v.centre(native)
+
+    def host():
+        out = np.zeros((HOOK_Y1 - HOOK_Y0, HOOK_W, channels), dtype=np.uint8)
+        check(lib.fr_render_rows_ss_de_pt_scaled(C.byref(v.cfg), C.byref(centre), 40, THICK, HOOK_S, HOOK_Y0, HOOK_Y1, channels,
+                                                 out.ctypes.data, out.nbytes))
+        return out
+
+    sizes = host_bands_are_the_device_forms(
+        lib, 36, lambda n: render_device(torch, lib, native, v, 40, HOOK_S, THICK, HOOK_Y0, HOOK_Y1, channels, n), host)
+    assert sizes == fr.ss_de_workspace_bytes(v.cfg, HOOK_S, HOOK_Y0, HOOK_Y1)

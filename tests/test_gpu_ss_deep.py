@@ -611,3 +611,15 @@ def test_a_kept_scaled_view_extended_and_recoloured_is_the_render_at_the_higher_
     want = ss_pt_host(lib, d.cfg, d.c, SCALED, -1, s, 0, d.cfg.height, 3)
     assert np.array_equal(got, want), int((got != want).sum())
     assert np.array_equal(want, np_filter(d.yardstick(lib, SCALED, -1), s)) and not np.array_equal(want, low_img)
+
+
+@pytest.mark.parametrize("channels", [3, 4])
+def test_host_form_under_a_cap_below_min_bytes_is_the_device_form(fr, native, lib, torch, channels):
+    """fr_render_rows_ss_pt on BLA-PT (test_gpu_ss.py: host_bands_are_the_device_forms)"""
+    from test_gpu_ss import HOOK_H, HOOK_S, HOOK_W, HOOK_Y0, HOOK_Y1, host_bands_are_the_device_forms
+
+    d = Deep(fr, native, "J-2^300", HOOK_S, size=(HOOK_W, HOOK_H))
+    sizes = host_bands_are_the_device_forms(
+        lib, 3, lambda n: ss_pt_device(torch, lib, d.cfg, d.c, BLA, 0, HOOK_S, HOOK_Y0, HOOK_Y1, channels, n),
+        lambda: ss_pt_host(lib, d.cfg, d.c, BLA, 0, HOOK_S, HOOK_Y0, HOOK_Y1, channels))
+    assert sizes == workspace(lib, d.cfg, HOOK_S, HOOK_Y0, HOOK_Y1)
