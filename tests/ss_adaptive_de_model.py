@@ -35,8 +35,10 @@ def near_only(cfg, z, it, der, s, T, tau, reach):
     return n & ~e
 
 
-def adaptive_de(cfg, z, it, der, s, T, tau, reach, y0=0, y1=None, channels=3):
-    """(out uint8 [y1-y0, width, channels], refined) of rows [y0, y1): the edge set is the whole image's, cut to the rows"""
+def adaptive_de(cfg, z, it, der, s, T, tau, reach, y0=0, y1=None, channels=3, filter=None, H=None):
+    """(out uint8 [y1-y0, width, channels], refined) of rows [y0, y1): the edge set is the whole image's, cut to the rows.
+    filter(H, s) -> uint8 [height, width, 3] is F; None is the byte filter ss_de_model.box, ss_linear_model.ss_filter with the
+    sRGB transfer gives LINEAR-LIGHT SUPERSAMPLING's.  H: shaded(cfg, z, it, der, s, T) where the caller has it already"""
     h, w = cfg.height, cfg.width
     y1 = h if y1 is None else y1
     if cfg.algo not in (0, 2):
@@ -44,10 +46,11 @@ def adaptive_de(cfg, z, it, der, s, T, tau, reach, y0=0, y1=None, channels=3):
         if channels == 4:
             out[..., 3] = 255
         return out, 0
-    H = shaded(cfg, z, it, der, s, T)
+    if H is None:
+        H = shaded(cfg, z, it, der, s, T)
     e = (A.edges(H, s, tau) | near(cfg, z, it, der, s, reach))[y0:y1]
     P = A.probe(H, s)[y0:y1]
-    F = SD.box(H, s)[y0:y1]
+    F = (SD.box if filter is None else filter)(H, s)[y0:y1]
     rgb = np.where(e[..., None], F, P)
     if channels == 4:
         out = np.full(rgb.shape[:2] + (4,), 255, dtype=np.uint8)

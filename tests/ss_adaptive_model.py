@@ -42,8 +42,10 @@ def edges(big, s, tau):
     return e
 
 
-def adaptive(big, s, tau, y0=0, y1=None, channels=3, escape_algo=True):
-    """(out uint8 [y1-y0, width, channels], refined) of rows [y0, y1): the edge set is the whole image's, cut to the rows"""
+def adaptive(big, s, tau, y0=0, y1=None, channels=3, escape_algo=True, filter=None):
+    """(out uint8 [y1-y0, width, channels], refined) of rows [y0, y1): the edge set is the whole image's, cut to the rows.
+    filter(big, s) -> uint8 [height, width, 3] is F; None is the byte filter np_filter, ss_linear_model.ss_filter with the sRGB
+    transfer gives LINEAR-LIGHT SUPERSAMPLING's"""
     h = big.shape[0] // s
     y1 = h if y1 is None else y1
     if not escape_algo:
@@ -53,7 +55,7 @@ def adaptive(big, s, tau, y0=0, y1=None, channels=3, escape_algo=True):
         return out, 0
     e = edges(big, s, tau)[y0:y1]
     P = probe(big, s)[y0:y1]
-    F = np_filter(big, s)[y0:y1]
+    F = (np_filter if filter is None else filter)(big, s)[y0:y1]
     rgb = np.where(e[..., None], F, P)
     if channels == 4:
         out = np.full(rgb.shape[:2] + (4,), 255, dtype=np.uint8)

@@ -3,7 +3,8 @@ the only caller of the RGB render kernels over a strided pixel map (x_stride = s
 fr_set_tile and fr_set_loop_mode; every other adaptive test runs with the defaults.
   a. every F64 record of tests/shallow_random_views.py (generated and edge, algo 1 included) through
      fr_render_rows_ss_adaptive_device at the record's own s, tile and loop_mode, at thresholds -1, 255 and the record's tau
-     (deep_ss_views.median_tau of the host model's image of cfg_s), with the refined count, and for the record's row piece.  H is
+     (deep_ss_views.median_tau of the host model's image of cfg_s), with the refined count, and for the record's row piece; at the
+     record's tau and at -1 also with transfer 1, against the model with F replaced by the sRGB filter.  H is
      the HOST MODEL's image: the oracle's F64 rows of cfg_s through its colour map with the software log2; the device's plain
      render of cfg_s under the same selectors is asserted to equal it before it is used.  tests/test_deep_ss_random_cpu.py holds the
      conditions on these records;
@@ -17,6 +18,7 @@ import pytest
 import deep_ss_views as V
 import oracle_lib as O
 import shallow_random_views as R
+import ss_adaptive_de_views as AV
 import ss_adaptive_model as A
 from test_gpu_shallow_random import Selectors
 from test_gpu_ss_adaptive import ad_device, check, f64_cfg, fr, lib, native, scaled_up, torch  # noqa: F401  (fixtures and helpers)
@@ -50,6 +52,11 @@ def adaptive_record(fr, lib, torch, rec):
             want, count = A.adaptive(big, s, t, escape_algo=orbits)
             got, n = ad_device(torch, lib, cfg, s, t)
             assert np.array_equal(got, want) and n == count, "threshold %d: %d pixels differ, refined %d, the model %d; %s" % (
+                t, int((got != want).any(axis=-1).sum()), n, count, what)
+        for t in dict.fromkeys((tau, -1)):  # the LINEAR instance of ss_refine_f64_kernel: F is the sRGB filter
+            want, count = A.adaptive(big, s, t, escape_algo=orbits, filter=AV.srgb_filter)
+            got, n = ad_device(torch, lib, cfg, s, t, transfer=1)
+            assert np.array_equal(got, want) and n == count, "threshold %d, transfer 1: %d pixels differ, refined %d, the model %d; %s" % (
                 t, int((got != want).any(axis=-1).sum()), n, count, what)
         y0, y1 = rec.split
         want, count = A.adaptive(big, s, tau, y0, y1, escape_algo=orbits)

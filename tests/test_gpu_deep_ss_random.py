@@ -9,7 +9,8 @@ table bits everywhere.
   a. the anchor: the road's existing plain render of cfg_s is soft_colours of the road's model on cfg_s;
   b. fr_render_rows_ss_pt_device, 3 and 4 channels, the drawn row piece and an empty piece, against the box filter of the model image;
   c. fr_render_rows_ss_adaptive_device at thresholds -1, 255, 0 and the view's tau against ss_adaptive_model.adaptive with the
-     refined count; the three-way split; RGBA; the grid forced to 1 and 2 workgroups and d_refined NULL on one view per seed; the
+     refined count, and fr_render_rows_ss_adaptive_tf_device with transfer 1 at the view's tau and at -1 against the same model
+     with F replaced by the sRGB filter; the three-way split; RGBA; the grid forced to 1 and 2 workgroups and d_refined NULL on one view per seed; the
      dd-centre views of test_gpu_deep_edges.random_config on PT PLAIN and BLA-PT with pos_lo at one drawn s;
   d. fr_render_rows_ss_de_device on WIDE PT and BLA-PT inside 2^440 and fr_render_rows_ss_de_pt_scaled_device everywhere, at the
      view's thickness, at 0 and for the row piece, against ss_de_model.colour over the DE models of cfg_s;
@@ -32,6 +33,7 @@ import deep_random_views as G
 import deep_ss_views as V
 import pt_model as P
 import pt_scaled_model as S
+import ss_adaptive_de_views as AV
 import ss_adaptive_model as A
 import ss_de_model as SS
 from test_gpu_de import Buf, Rows
@@ -148,13 +150,16 @@ def check_adaptive(c, torch, extras):
         kw = dict(precision=PT, centre=c.centre, road=road, bits=bits)
 
         def run(tau, what="", **more):
-            want, count = A.adaptive(big, s, tau, more.get("y0", 0), more.get("y1"), more.get("channels", 3))
+            want, count = A.adaptive(big, s, tau, more.get("y0", 0), more.get("y1"), more.get("channels", 3),
+                                     filter=AV.FILTERS[more.get("transfer") or 0])
             got, n = ad_device(torch, lib, c.cfg, s, tau, **more, **kw)
             assert np.array_equal(got, want) and n == count, "%s, threshold %d%s: %d pixels differ, refined %d, the model %d; %s" % (
                 name, tau, what, differ(got, want), n, count, c.what)
 
         for tau in dict.fromkeys((-1, 255, 0, v.tau)):
             run(tau)
+        for tau in dict.fromkeys((v.tau, -1)):  # the LINEAR instance of the road's refine kernel: F is the sRGB filter
+            run(tau, ", transfer 1", transfer=1)
         if v.three_way() is not None:
             for y0, y1 in v.three_way():  # each piece against its slice: the bytes concatenate to the whole, the counts sum
                 run(v.tau, ", rows [%d, %d)" % (y0, y1), y0=y0, y1=y1)

@@ -67,8 +67,9 @@ def check(rc):
 
 
 def ad_device(torch, lib, cfg, s, tau, y0=0, y1=None, channels=3, precision=F64, pos_lo=None, centre=None, road=PLAIN, bits=0,
-              want_refined=True):
-    """fr_render_rows_ss_adaptive_device into a guarded destination, with the SMALLEST workspace and a canary behind it"""
+              want_refined=True, transfer=None):
+    """fr_render_rows_ss_adaptive_device — with a transfer (0 included) fr_render_rows_ss_adaptive_tf_device — into a guarded
+    destination, with the SMALLEST workspace and a canary behind it"""
     y1 = cfg.height if y1 is None else y1
     dev = torch.device("cuda", 0)
     need = channels * cfg.width * (y1 - y0)
@@ -81,9 +82,12 @@ def ad_device(torch, lib, cfg, s, tau, y0=0, y1=None, channels=3, precision=F64,
     d_n = torch.full((3,), -1, dtype=torch.int64, device=dev)
     assert d_work.data_ptr() % 8 == 0
     torch.cuda.synchronize()
-    check(lib.fr_render_rows_ss_adaptive_device(C.byref(cfg), precision, pos_lo, centre, road, bits, s, tau, y0, y1, channels,
-                                                d_out.data_ptr() + GUARD, need, d_work.data_ptr(), work_len,
-                                                d_n.data_ptr() + 8 if want_refined else None, None))
+    tail = (tau, y0, y1, channels, d_out.data_ptr() + GUARD, need, d_work.data_ptr(), work_len, d_n.data_ptr() + 8 if want_refined else None,
+            None)
+    if transfer is not None:
+        check(lib.fr_render_rows_ss_adaptive_tf_device(C.byref(cfg), precision, pos_lo, centre, road, bits, s, transfer, *tail))
+    else:
+        check(lib.fr_render_rows_ss_adaptive_device(C.byref(cfg), precision, pos_lo, centre, road, bits, s, *tail))
     torch.cuda.synchronize()
     host = d_out.cpu().numpy()
     assert (host[:GUARD] == 0xA5).all() and (host[GUARD + need:] == 0xA5).all(), "wrote outside the destination"
@@ -94,13 +98,16 @@ def ad_device(torch, lib, cfg, s, tau, y0=0, y1=None, channels=3, precision=F64,
     return host[GUARD:GUARD + need].reshape(y1 - y0, cfg.width, channels), int(cnt[1])
 
 
-def ad_host(lib, cfg, s, tau, y0=0, y1=None, channels=3, precision=F64, pos_lo=None, centre=None, road=PLAIN, bits=0):
+def ad_host(lib, cfg, s, tau, y0=0, y1=None, channels=3, precision=F64, pos_lo=None, centre=None, road=PLAIN, bits=0, transfer=None):
     y1 = cfg.height if y1 is None else y1
     need = channels * cfg.width * (y1 - y0)
     host = np.full(GUARD + need + GUARD, 0xA5, dtype=np.uint8)
     n = C.c_uint64(12345)
-    check(lib.fr_render_rows_ss_adaptive(C.byref(cfg), precision, pos_lo, centre, road, bits, s, tau, y0, y1, channels,
-                                         host.ctypes.data + GUARD, need, C.byref(n)))
+    tail = (tau, y0, y1, channels, host.ctypes.data + GUARD, need, C.byref(n))
+    if transfer is not None:
+        check(lib.fr_render_rows_ss_adaptive_tf(C.byref(cfg), precision, pos_lo, centre, road, bits, s, transfer, *tail))
+    else:
+        check(lib.fr_render_rows_ss_adaptive(C.byref(cfg), precision, pos_lo, centre, road, bits, s, *tail))
     assert (host[:GUARD] == 0xA5).all() and (host[GUARD + need:] == 0xA5).all(), "wrote outside the destination"
     return host[GUARD:GUARD + need].reshape(y1 - y0, cfg.width, channels), n.value
 

@@ -58,17 +58,21 @@ def check(rc):
 
 
 def c_args(kw):
-    """(precision, pos_lo, centre, road, bits) of the C call for the Python keywords, and what keeps their memory alive"""
+    """(precision, pos_lo, centre, road, bits) of the C call for the Python keywords, and what keeps their memory alive; the
+    keyword `c_call` holds the five as the C call takes them, kept alive by the caller"""
     from fractal_renderer_amd import _native
 
+    if "c_call" in kw:
+        return tuple(kw["c_call"]), None
     lo = None if kw.get("pos_lo") is None else _native.Imaginary(*kw["pos_lo"])
     st = None if kw.get("centre") is None else kw["centre"].c_struct()
     road, bits = (BLA, int(kw["bla"])) if kw.get("bla") is not None else (PLAIN, 0)
     return (int(kw.get("precision", 0)), None if lo is None else C.byref(lo), None if st is None else C.byref(st), road, bits), (lo, st)
 
 
-def ad_device(torch, lib, cfg, kw, s, thickness, tau, reach, y0=0, y1=None, channels=3, want_refined=True):
-    """fr_render_rows_ss_adaptive_de_device into a guarded destination, with the SMALLEST workspace between two guards"""
+def ad_device(torch, lib, cfg, kw, s, thickness, tau, reach, y0=0, y1=None, channels=3, want_refined=True, transfer=None):
+    """fr_render_rows_ss_adaptive_de_device — with a transfer (0 included) fr_render_rows_ss_adaptive_de_tf_device — into a guarded
+    destination, with the SMALLEST workspace between two guards"""
     y1 = cfg.height if y1 is None else y1
     dev = torch.device("cuda", 0)
     pre, _keep = c_args(kw)
@@ -82,9 +86,12 @@ def ad_device(torch, lib, cfg, kw, s, thickness, tau, reach, y0=0, y1=None, chan
     d_n = torch.full((3,), -1, dtype=torch.int64, device=dev)
     assert d_work.data_ptr() % 8 == 0 and d_out.data_ptr() % 4 == 0
     torch.cuda.synchronize()
-    check(lib.fr_render_rows_ss_adaptive_de_device(C.byref(cfg), *pre, thickness, s, tau, reach, y0, y1, channels, d_out.data_ptr() + GUARD,
-                                                   need, d_work.data_ptr() + GUARD, work_len, d_n.data_ptr() + 8 if want_refined else None,
-                                                   None))
+    tail = (tau, reach, y0, y1, channels, d_out.data_ptr() + GUARD, need, d_work.data_ptr() + GUARD, work_len,
+            d_n.data_ptr() + 8 if want_refined else None, None)
+    if transfer is not None:
+        check(lib.fr_render_rows_ss_adaptive_de_tf_device(C.byref(cfg), *pre, thickness, s, transfer, *tail))
+    else:
+        check(lib.fr_render_rows_ss_adaptive_de_device(C.byref(cfg), *pre, thickness, s, *tail))
     torch.cuda.synchronize()
     host = d_out.cpu().numpy()
     assert (host[:GUARD] == 0xA5).all() and (host[GUARD + need:] == 0xA5).all(), "wrote outside the destination"
@@ -96,14 +103,17 @@ def ad_device(torch, lib, cfg, kw, s, thickness, tau, reach, y0=0, y1=None, chan
     return host[GUARD:GUARD + need].reshape(y1 - y0, cfg.width, channels), int(cnt[1])
 
 
-def ad_host(lib, cfg, kw, s, thickness, tau, reach, y0=0, y1=None, channels=3):
+def ad_host(lib, cfg, kw, s, thickness, tau, reach, y0=0, y1=None, channels=3, transfer=None):
     y1 = cfg.height if y1 is None else y1
     pre, _keep = c_args(kw)
     need = channels * cfg.width * (y1 - y0)
     host = np.full(GUARD + need + GUARD, 0xA5, dtype=np.uint8)
     n = C.c_uint64(12345)
-    check(lib.fr_render_rows_ss_adaptive_de(C.byref(cfg), *pre, thickness, s, tau, reach, y0, y1, channels, host.ctypes.data + GUARD, need,
-                                            C.byref(n)))
+    tail = (tau, reach, y0, y1, channels, host.ctypes.data + GUARD, need, C.byref(n))
+    if transfer is not None:
+        check(lib.fr_render_rows_ss_adaptive_de_tf(C.byref(cfg), *pre, thickness, s, transfer, *tail))
+    else:
+        check(lib.fr_render_rows_ss_adaptive_de(C.byref(cfg), *pre, thickness, s, *tail))
     assert (host[:GUARD] == 0xA5).all() and (host[GUARD + need:] == 0xA5).all(), "wrote outside the destination"
     return host[GUARD:GUARD + need].reshape(y1 - y0, cfg.width, channels), n.value
 
