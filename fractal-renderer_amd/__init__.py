@@ -44,7 +44,7 @@ __all__ = [
     "de_scaled_view",
     "escape_rows_de_pt_scaled_state", "extend_rows_de_pt_scaled", "get_image_de_scaled_ss",
     "get_image_ss_adaptive", "ss_adaptive_workspace_bytes",
-    "get_image_de_adaptive", "ss_adaptive_de_workspace_bytes",
+    "get_image_de_adaptive", "get_image_de_adaptive_scaled", "ss_adaptive_de_workspace_bytes",
     "ss_transfer_tables",
 ]
 
@@ -1223,6 +1223,33 @@ def get_image_de_adaptive(config, thickness=1.0, supersample=2, threshold=8, rea
     _native.check(_native.load().fr_render_rows_ss_adaptive_de_tf(C.byref(config), int(precision), lo, ptr, road, bits, float(thickness), s,
                                                                   int(transfer), int(threshold), float(reach), y0, y1, int(channels),
                                                                   out.ctypes.data, out.nbytes, C.byref(refined)))
+    return out, refined.value
+
+
+def get_image_de_adaptive_scaled(config, thickness, centre, supersample=2, threshold=8, reach=2.0, bla=None, y0=0, y1=None, channels=3,
+                                 out=None, transfer=0):
+    """Adaptive anti-aliased distance estimation past a scale of 2^440 (fr_render_rows_ss_adaptive_de_pt_scaled;
+    include/fractal_hip.h, "ADAPTIVE SUPERSAMPLED SCALED DE"): get_image_de_adaptive on SCALED PT's road, the probe and the samples
+    those of get_image_de_scaled_ss.  Returns (image uint8 [y1-y0, width, channels], refined: the number of edge pixels).
+    centre: a WideCentre, required; bla: None (the plain scaled loop), 0 or 24 .. 53; thickness and reach in output pixels;
+    threshold -1 gives the bytes of get_image_de_scaled_ss, which is the faster call for them.  transfer: see
+    get_image_ss_adaptive."""
+    s = int(supersample)
+    if not 1 <= s <= SS_MAX:
+        raise ValueError("supersample is 1 .. %d" % SS_MAX)
+    if not -1 <= int(threshold) <= 255:
+        raise ValueError("threshold is -1 .. 255")
+    if int(channels) not in (3, 4):
+        raise ValueError("channels is 3 or 4")
+    _road, bits = _ss_pt_road(None, centre, bla, True)
+    st = centre.c_struct()
+    y0, y1 = _rows(config, y0, y1)
+    if out is None:
+        out = np.empty((max(y1 - y0, 0), config.width, int(channels)), dtype=np.uint8)
+    refined = C.c_uint64(0)
+    _native.check(_native.load().fr_render_rows_ss_adaptive_de_pt_scaled_tf(C.byref(config), C.byref(st), bits, float(thickness), s,
+                                                                            int(transfer), int(threshold), float(reach), y0, y1,
+                                                                            int(channels), out.ctypes.data, out.nbytes, C.byref(refined)))
     return out, refined.value
 
 

@@ -528,6 +528,16 @@ PROTOTYPES = {
         [C.POINTER(fr_config), C.c_int, C.POINTER(Imaginary), _WIDE, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_int, C.c_double,
          C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)],
     ),
+    "fr_render_rows_ss_adaptive_de_pt_scaled_device": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_int, C.c_double, C.c_uint32, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_int,
+         C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p],
+    ),
+    "fr_render_rows_ss_adaptive_de_pt_scaled": (
+        C.c_int,
+        [C.POINTER(fr_config), _WIDE, C.c_int, C.c_double, C.c_uint32, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_int,
+         C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)],
+    ),
     "fr_count_iterations": (
         C.c_int,
         [C.POINTER(fr_config), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
@@ -572,6 +582,11 @@ for _twin, _k in _TF_TWINS.items():
     _res, _args = PROTOTYPES[_twin]
     assert _args[_k] is C.c_uint32
     PROTOTYPES[tf_name(_twin)] = (_res, _args[:_k + 1] + [C.c_int] + _args[_k + 1:])
+# ADAPTIVE SUPERSAMPLED SCALED DE's twins, by the same rule: `int transfer` behind `supersample` (argument 4)
+for _twin in ("fr_render_rows_ss_adaptive_de_pt_scaled", "fr_render_rows_ss_adaptive_de_pt_scaled_device"):
+    _res, _args = PROTOTYPES[_twin]
+    assert _args[4] is C.c_uint32
+    PROTOTYPES[tf_name(_twin)] = (_res, _args[:5] + [C.c_int] + _args[5:])
 PROTOTYPES["fr_ss_transfer_tables"] = (C.c_int, [C.POINTER(C.POINTER(C.c_uint16)), C.POINTER(C.POINTER(C.c_uint16))])
 
 _lib = None

@@ -34,6 +34,11 @@
  * through the row-call bodies of fr_ctx.h (device_form, host_raw, profiled_rows); the state calls hand their launch to RESUMABLE
  * DE's five-array road (fr_de.h: de_state_device, de_state_host).  scaled_de_domain and scaled_de_render_rows lend the DE render
  * to SUPERSAMPLED SCALED DE (fr_ss_de.hip).
+ *
+ * ADAPTIVE SUPERSAMPLED SCALED DE (include/fractal_hip.h; fr_ss_adaptive_de.hip): ss_refine_de_scaled_kernel<JULIA, BLA, LINEAR>,
+ * persistent waves that run orbit_pt_scaled_de / orbit_bla_scaled_de on the s x s samples of the listed pixels through fr_ss_list.h's
+ * claim loop, each sample coloured and shaded through fr_ss_de_sample.h; scaled_de_render_map, the DE launch over the probe's
+ * strided map, and scaled_de_ss_refine, the refine launch.  Registers and occupancy: DESIGN.md 3.34.
  */
 #include <cmath>
 #include <memory>
@@ -43,9 +48,14 @@
 #include "fr_de.h"
 #include "fr_math.h"
 #include "fr_scaled.h"
+#include "fr_ss_list.h"
 #include "fr_wide.h"
 
 namespace {
+
+#include "fr_colour.h"       /* the refine kernel's colour map and the log2 table */
+#include "fr_de_shade.h"     /* de_distance */
+#include "fr_ss_de_sample.h" /* ss_de_sample_colour */
 
 /* ---- device: the plain scaled loop with the scaled derivative (bits = -1) ------------------------------------------------ */
 
@@ -279,6 +289,48 @@ hipError_t launch(bool julia, bool bla, const fr_kparams &p, double *z, uint32_t
             escape_pt_scaled_de_kernel<true><<<grid, block, 0, stream>>>(p, z, iters, der, t);
         else
             escape_pt_scaled_de_kernel<false><<<grid, block, 0, stream>>>(p, z, iters, der, t);
+    }
+    return hipGetLastError();
+}
+
+/* ---- device: ADAPTIVE SUPERSAMPLED SCALED DE's refine pass (include/fractal_hip.h; fr_ss_list.h: the claim loop) --------------- */
+
+/* ss_refine_de_bla_kernel (fr_de_bla.hip) with the scaled DE loops: `woff` by stage_woff's formula on cfg_s (`p` holds cfg_s with
+ * the scaled divisors sre, sim, as ss_refine_scaled_kernel has them), the loop chosen by BLA, the table built with Dw over the
+ * whole image of cfg_s; sh.pixels is the scaled view's last factor of D, sh.thickness is Ts */
+template <bool JULIA, bool BLA, bool LINEAR>
+__global__ __launch_bounds__(kSsRefineThreads) void ss_refine_de_scaled_kernel(const fr_kparams p, const fr_ss_refine a,
+                                                                               const fr_ss_de_shade sh, const ScaledDev t) {
+    __shared__ double s_tab[FR_LOG2_N * 3];
+    const double *gt = &g_log2_tab[0][0];
+    for (uint32_t k = threadIdx.x; k < FR_LOG2_N * 3; k += kSsRefineThreads) s_tab[k] = gt[k];
+    const uint16_t *const s_lt = ss_refine_tables<LINEAR>(); /* LINEAR-LIGHT SUPERSAMPLING: staged with the log2 table */
+    __syncthreads();
+    const double width = (double)p.width, height = (double)p.height;
+    const double squared = p.limit * p.limit;
+    ss_refine_loop<LINEAR>(a, s_lt, [&](uint64_t x, uint64_t y) {
+        const double woff_re = (((double)x / height) - ((width / height) / 2.0)) / p.scale_re;
+        const double woff_im = (((double)y / height) - 0.5) / p.scale_im;
+        double zr, zi, ur, ui;
+        uint32_t it;
+        if constexpr (BLA)
+            it = orbit_bla_scaled_de<JULIA>(p.iterations, woff_re, woff_im, t, squared, zr, zi, ur, ui);
+        else
+            it = orbit_pt_scaled_de<JULIA>(p.iterations, woff_re, woff_im, t, squared, zr, zi, ur, ui);
+        return ss_de_sample_colour(p, zr, zi, ur, ui, it, sh.pixels, sh.thickness, s_tab);
+    });
+}
+
+template <bool JULIA>
+hipError_t launch_refine(bool bla, const fr_kparams &p, const fr_ss_refine &a, const fr_ss_de_shade &sh, const ScaledDev &t, uint32_t groups,
+                         hipStream_t stream) {
+    const dim3 grid(groups), block(kSsRefineThreads);
+    if (bla) {
+        if (a.linear) ss_refine_de_scaled_kernel<JULIA, true, true><<<grid, block, 0, stream>>>(p, a, sh, t);
+        else ss_refine_de_scaled_kernel<JULIA, true, false><<<grid, block, 0, stream>>>(p, a, sh, t);
+    } else {
+        if (a.linear) ss_refine_de_scaled_kernel<JULIA, false, true><<<grid, block, 0, stream>>>(p, a, sh, t);
+        else ss_refine_de_scaled_kernel<JULIA, false, false><<<grid, block, 0, stream>>>(p, a, sh, t);
     }
     return hipGetLastError();
 }
@@ -607,6 +659,32 @@ int scaled_de_domain(const fr_config *cfg, const Centre &c, int &bits, uint32_t 
 int scaled_de_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, double *d_z,
                           uint32_t *d_iters, double *d_der, hipStream_t stream) {
     return scaled_de_rows(cfg, c, bits, y0, y1)(ctx, d_z, d_iters, d_der, nullptr, stream);
+}
+
+/* fr_ss_list.h: ADAPTIVE SUPERSAMPLED SCALED DE — the probe (the road's DE kernel over the strided map) and the refine pass */
+int scaled_de_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_map &map, double *d_z, uint32_t *d_iters,
+                         double *d_der, hipStream_t stream) {
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    map.apply(p);
+    return launch_scaled_de(ctx, cfg, c, bits, p, d_z, d_iters, d_der, stream);
+}
+
+int scaled_de_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, const fr_ss_de_shade &sh,
+                        uint32_t groups, hipStream_t stream) {
+    const ScaledConsts k = scaled_consts(cfg);
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    p.scale_re = k.sre;
+    p.scale_im = k.sim;
+    std::shared_ptr<PtOrbit> orbit; /* alive until the launch is enqueued, like the table */
+    std::shared_ptr<BlaTable> table;
+    ScaledDev t;
+    const int rc = scaled_dev_fill(ctx, cfg, c, bits, k, orbit, table, t);
+    if (rc != FR_OK) return rc;
+    const bool julia = cfg->algo == FR_ALGO_JULIA;
+    HIP_TRY(julia ? launch_refine<true>(bits >= 0, p, a, sh, t, groups, stream) : launch_refine<false>(bits >= 0, p, a, sh, t, groups, stream));
+    return FR_OK;
 }
 
 }  // namespace fr

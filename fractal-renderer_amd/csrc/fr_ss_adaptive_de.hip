@@ -18,7 +18,13 @@
  * same into a host buffer through context scratch, by row pieces above the host workspace cap).  fr_debug_ss_adaptive_grid
  * (fr_ss_adaptive.hip) sets the refine grid here too.  Each call is its domain check (ssad_check) and fr_ss_adaptive.h's skeleton
  * around ssad_render; the workspace's layout is that header's, with the DE arrays in front ("3.32").
+ *
+ * ADAPTIVE SUPERSAMPLED SCALED DE (include/fractal_hip.h): fr_render_rows_ss_adaptive_de_pt_scaled and its three other spellings,
+ * the road that the calls above keep refusing.  Their own check (ssad_scaled_check: DE ON SCALED PT's domain on cfg_s, `pixels` from
+ * the scaled view) and the scaled arm of ssad_render's two switches — the probe is scaled_de_render_map, the refine pass
+ * ss_refine_de_scaled_kernel (fr_de_scaled.hip); passes 2 and 3 run unchanged, the scaled view enters through `pixels` alone.
  */
+#include "fr_bla.h" /* scaled_consts */
 #include "fr_ctx.h"
 #include "fr_de.h"
 #include "fr_math.h"
@@ -97,10 +103,9 @@ struct SsadRoad {
     double ts, rs, pixels;
 };
 
-/* everything the calls check before any device work, short of the buffers: the sizes, the thickness, the reach, the threshold,
- * then fr_render_rows_ss_de_device's argument rule per precision and road with the road's own DE domain on cfg_s */
-int ssad_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
-               double thickness, uint32_t s, int threshold, double reach, uint32_t y0, uint32_t y1, int channels, SsadRoad &r) {
+/* the head of both checks below: the sizes, the channels, the thickness, the reach, the threshold and the list's 32-bit indices */
+int ssad_head(const fr_config *cfg, double thickness, uint32_t s, int threshold, double reach, uint32_t y0, uint32_t y1, int channels,
+              SsadRoad &r) {
     int rc = ss_plan(cfg, s, y0, y1, r.pl);
     if (rc == FR_OK) rc = check_channels(channels);
     if (rc != FR_OK) return rc;
@@ -113,13 +118,22 @@ int ssad_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, 
         return fail(FR_ERR_INVALID_ARGUMENT, "threshold must be -1 (every pixel is refined) or 0 .. 255");
     if ((uint64_t)cfg->width * (y1 - y0) > 0xFFFFFFFFull)
         return fail(FR_ERR_INVALID_ARGUMENT, "width * (y1 - y0) must be below 2^32: the edge list holds 32-bit pixel indices; call by row pieces");
+    r.tau = threshold;
+    return FR_OK;
+}
+
+/* everything the calls check before any device work, short of the buffers: the sizes, the thickness, the reach, the threshold,
+ * then fr_render_rows_ss_de_device's argument rule per precision and road with the road's own DE domain on cfg_s */
+int ssad_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road, int bits,
+               double thickness, uint32_t s, int threshold, double reach, uint32_t y0, uint32_t y1, int channels, SsadRoad &r) {
+    const int rc = ssad_head(cfg, thickness, s, threshold, reach, y0, y1, channels, r);
+    if (rc != FR_OK) return rc;
     const fr_config *cs = &r.pl.cfg_s;
     const uint32_t Y0 = s * y0, Y1 = (uint32_t)(Y0 + r.pl.src_rows);
     r.pixels = ss_de_pixels(cfg, s);
     r.precision = precision;
     r.road = road;
     r.bits = bits;
-    r.tau = threshold;
     r.c = Centre{pos_lo, centre};
     if (road == FR_PT_ROAD_SCALED)
         return fail(FR_ERR_INVALID_ARGUMENT, "FR_PT_ROAD_SCALED: distance estimation on SCALED PT is out of scope; adaptive supersampled DE takes "
@@ -140,6 +154,25 @@ int ssad_check(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, 
     if (road == FR_PT_ROAD_BLA) return bla_de_domain(cs, r.c, r.bits, Y0, Y1);
     if (bits != 0) return fail(FR_ERR_INVALID_ARGUMENT, "bits must be 0 with FR_PT_ROAD_PLAIN: the plain loop has no table");
     return de_domain(cs, precision, r.c, precision == FR_PRECISION_PT && centre != nullptr, Y0, Y1);
+}
+
+/* ADAPTIVE SUPERSAMPLED SCALED DE: the sizes, the thickness, the reach and the threshold as ssad_check takes them, then DE ON SCALED
+ * PT's domain on cfg_s by the code its plain calls run, and `pixels` — the last factor of D on the scaled view of cfg_s — as
+ * ss_de_scaled_check (fr_ss_de.hip) computes it */
+int ssad_scaled_check(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t s, int threshold, double reach,
+                      uint32_t y0, uint32_t y1, int channels, SsadRoad &r) {
+    int rc = ssad_head(cfg, thickness, s, threshold, reach, y0, y1, channels, r);
+    if (rc != FR_OK) return rc;
+    r.precision = FR_PRECISION_PT;
+    r.road = FR_PT_ROAD_SCALED;
+    r.bits = bits;
+    r.c = Centre{nullptr, centre, true};
+    const uint32_t Y0 = s * y0, Y1 = (uint32_t)(Y0 + r.pl.src_rows);
+    rc = scaled_de_domain(&r.pl.cfg_s, r.c, r.bits, Y0, Y1);
+    if (rc != FR_OK) return rc;
+    const ScaledConsts k = scaled_consts(cfg); /* cfg_s shares cfg's scale */
+    r.pixels = ss_de_pixels(cfg, s, k.sre, k.sim);
+    return FR_OK;
 }
 
 /* Rows [y0, y1) of the adaptive DE render into d_out on `stream`: the four passes.  Arguments checked, the rows and the width not
@@ -164,7 +197,9 @@ int ssad_render(Ctx &ctx, const SsadRoad &r, const fr_config *cfg, uint32_t s, i
     /* 1. the DE probe */
     const uint32_t half = s / 2u;
     const fr_ss_map map{cfg->width, l.yb - l.ya, half, s, s * l.ya + half, s};
-    if (r.road == FR_PT_ROAD_BLA)
+    if (r.road == FR_PT_ROAD_SCALED)
+        rc = scaled_de_render_map(ctx, cs, r.c, r.bits, map, d_z, d_iters, d_der, stream);
+    else if (r.road == FR_PT_ROAD_BLA)
         rc = bla_de_render_map(ctx, cs, r.c, r.bits, map, d_z, d_iters, d_der, stream);
     else
         rc = de_render_map(ctx, cs, r.precision, r.c, map, d_z, d_iters, d_der, stream);
@@ -206,7 +241,10 @@ int ssad_render(Ctx &ctx, const SsadRoad &r, const fr_config *cfg, uint32_t s, i
         const fr_ss_refine a = ss_refine_args(q.out, list, counters, cfg->width, y0, s, bpp, transfer);
         const uint32_t groups = ss_refine_groups(a, q.rows);
         const fr_ss_de_shade sh{r.pixels, r.ts};
-        if (r.road == FR_PT_ROAD_BLA) {
+        if (r.road == FR_PT_ROAD_SCALED) {
+            rc = scaled_de_ss_refine(ctx, cs, r.c, r.bits, a, sh, groups, stream);
+            kname = "ss_refine_de_scaled_kernel";
+        } else if (r.road == FR_PT_ROAD_BLA) {
             rc = bla_de_ss_refine(ctx, cs, r.c, r.bits, a, sh, groups, stream);
             kname = "ss_refine_de_bla_kernel";
         } else {
@@ -268,6 +306,48 @@ int fr_render_rows_ss_adaptive_de(const fr_config *cfg, int precision, const fr_
                                   int bits, double thickness, uint32_t supersample, int threshold, double reach, uint32_t y0, uint32_t y1,
                                   int channels, uint8_t *out, size_t out_len, uint64_t *refined) {
     return fr_render_rows_ss_adaptive_de_tf(cfg, precision, pos_lo, centre, road, bits, thickness, supersample, FR_SS_TRANSFER_BYTES, threshold, reach, y0, y1, channels, out, out_len, refined);
+}
+
+/* ---- ADAPTIVE SUPERSAMPLED SCALED DE: the four calls above on the scaled road, which they keep refusing ------------------------- */
+
+int fr_render_rows_ss_adaptive_de_pt_scaled_tf_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness,
+                                                      uint32_t supersample, int transfer, int threshold, double reach, uint32_t y0, uint32_t y1,
+                                                      int channels, void *d_out, size_t out_len, void *d_work, size_t work_len, void *d_refined,
+                                                      void *hip_stream) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
+    SsadRoad r;
+    const int rc = ssad_scaled_check(cfg, centre, bits, thickness, supersample, threshold, reach, y0, y1, channels, r);
+    if (rc != FR_OK) return rc;
+    return ss_adaptive_device(cfg, true, "work_len < bytes of fr_ss_adaptive_de_workspace_bytes",
+                              "d_work must be 8-byte aligned (z, der, the list and the counters lie in it)", y0, y1, channels, d_out, out_len, d_work,
+                              work_len, d_refined, hip_stream, [&](Ctx &ctx, uint32_t ya, uint32_t yb, void *dst, void *work, hipStream_t stream) {
+                                  return ssad_render(ctx, r, cfg, supersample, transfer, ya, yb, (unsigned)channels, dst, work, stream);
+                              });
+}
+
+int fr_render_rows_ss_adaptive_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness,
+                                                   uint32_t supersample, int threshold, double reach, uint32_t y0, uint32_t y1, int channels,
+                                                   void *d_out, size_t out_len, void *d_work, size_t work_len, void *d_refined, void *hip_stream) {
+    return fr_render_rows_ss_adaptive_de_pt_scaled_tf_device(cfg, centre, bits, thickness, supersample, FR_SS_TRANSFER_BYTES, threshold, reach, y0, y1, channels, d_out, out_len, d_work, work_len, d_refined, hip_stream);
+}
+
+int fr_render_rows_ss_adaptive_de_pt_scaled_tf(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t supersample,
+                                               int transfer, int threshold, double reach, uint32_t y0, uint32_t y1, int channels, uint8_t *out,
+                                               size_t out_len, uint64_t *refined) {
+    if (const int trc = check_transfer(transfer); trc != FR_OK) return trc;
+    SsadRoad r;
+    const int rc = ssad_scaled_check(cfg, centre, bits, thickness, supersample, threshold, reach, y0, y1, channels, r);
+    if (rc != FR_OK) return rc;
+    return ss_adaptive_host(cfg, true, y0, y1, channels, out, out_len, refined,
+                            [&](Ctx &ctx, uint32_t ya, uint32_t yb, void *dst, void *work, hipStream_t stream) {
+                                return ssad_render(ctx, r, cfg, supersample, transfer, ya, yb, (unsigned)channels, dst, work, stream);
+                            });
+}
+
+int fr_render_rows_ss_adaptive_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t supersample,
+                                            int threshold, double reach, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len,
+                                            uint64_t *refined) {
+    return fr_render_rows_ss_adaptive_de_pt_scaled_tf(cfg, centre, bits, thickness, supersample, FR_SS_TRANSFER_BYTES, threshold, reach, y0, y1, channels, out, out_len, refined);
 }
 
 } /* extern "C" */

@@ -3,7 +3,7 @@
  * the probe pass, the mark pass's tile and its pieces, the edge list as a refine kernel sees it, the claim loop of the persistent refine waves, and the road
  * launches that fr_ss_adaptive.hip calls.  The refine kernels themselves sit beside their road's loop (fr_pt.hip, fr_bla.hip,
  * fr_scaled.hip; the F64 road's in fr_ss_adaptive.hip) — and ADAPTIVE SUPERSAMPLED DE's (fr_ss_adaptive_de.hip) beside their road's
- * DE loop (fr_de.hip, fr_de_bla.hip).  The device code here has internal linkage: each translation unit
+ * DE loop (fr_de.hip, fr_de_bla.hip, fr_de_scaled.hip).  The device code here has internal linkage: each translation unit
  * compiles its own copy into its own kernels.
  */
 #ifndef FR_SS_LIST_H
@@ -254,6 +254,12 @@ int bla_de_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits,
                       double *d_der, hipStream_t stream);
 int bla_de_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, const fr_ss_de_shade &sh,
                      uint32_t groups, hipStream_t stream);
+/* ADAPTIVE SUPERSAMPLED SCALED DE's (fr_de_scaled.hip): the sibling of scaled_de_render_rows (fr_de.h) over the probe's map, and
+ * ss_refine_de_scaled_kernel's launch; bits < 0: the plain scaled loop, no table.  sh.pixels is the scaled view's. */
+int scaled_de_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_map &map, double *d_z, uint32_t *d_iters,
+                         double *d_der, hipStream_t stream);
+int scaled_de_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, const fr_ss_de_shade &sh,
+                        uint32_t groups, hipStream_t stream);
 
 }  // namespace fr
 

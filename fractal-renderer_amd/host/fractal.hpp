@@ -526,6 +526,16 @@ inline std::vector<RGB> get_image_de(const Config &config, Bla bla, double thick
                                      uint32_t supersample, AdaptiveDe adaptive, Transfer transfer = Transfer::Bytes) {
     return get_image_ss_adaptive_de(config, FR_PRECISION_PT, pos_lo, centre, FR_PT_ROAD_BLA, bla.bits, thickness, supersample, adaptive, transfer);
 }
+// ... past a scale of 2^440, on SCALED PT (include/fractal_hip.h, "ADAPTIVE SUPERSAMPLED SCALED DE"): the probe and the samples are
+// those of the supersampled scaled form above, shaded on the scaled view
+inline std::vector<RGB> get_image_de(const Config &config, Scaled scaled, const fr_wide_centre &centre, double thickness, uint32_t supersample,
+                                     AdaptiveDe adaptive, Transfer transfer = Transfer::Bytes) {
+    std::vector<RGB> image(static_cast<size_t>(config.width) * config.height);
+    check(fr_render_rows_ss_adaptive_de_pt_scaled_tf(&config, &centre, scaled.bits, thickness, supersample, static_cast<int>(transfer),
+                                                     adaptive.threshold, adaptive.reach, 0, config.height, 3,
+                                                     reinterpret_cast<uint8_t *>(image.data()), image.size() * sizeof(RGB), adaptive.refined));
+    return image;
+}
 // A DE view past 2^440 kept on the device is (z, iters, w, m, der), 56 bytes per pixel ("RESUMABLE SCALED DE"): the state render and
 // the extension that raises its cap in place, scaled derivative included.  The plain loop's (scaled.bits must be -1: the table
 // form has no state).  Recolour with colour_de_rows_device / colour_de_rows_ss_device on the view fr_de_scaled_view writes.

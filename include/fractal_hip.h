@@ -563,6 +563,8 @@ typedef struct fr_config {
  * fit in 32 bits; DE ON SCALED PT's domain ON cfg_s, checked by the code the plain calls run (centre required; bits -1, 0 or
  * 24 .. 53); T finite with 0 <= T * s <= 2^20; channels 3 or 4; the buffer and workspace rules of fr_render_rows_ss_de_device
  * (fr_ss_de_workspace_bytes plans the workspace, 36 bytes per sample).  No colour or filter kernel is added or changed.
+ * Taking all s*s samples only at edge pixels and near the set is out of scope of THESE calls; ADAPTIVE SUPERSAMPLED SCALED DE below
+ * has calls of its own.
  */
 #define FR_BLA_DEFAULT_BITS 40
 #define FR_PT_MAX_ITERATIONS (1u << 24)
@@ -1494,7 +1496,8 @@ int fr_debug_ss_host_work_cap(size_t bytes);
  * context's scratch; above the host roads' 256 MiB workspace cap it splits the range into row pieces itself.  With profiling on,
  * fr_last_kernel_name reports the last kernel of the call (ss_refine_de_f64_kernel, ss_refine_de_pt_kernel or
  * ss_refine_de_bla_kernel, or ss_mark_de_kernel when no refine pass runs) and fr_last_kernel_ms the span of the whole call.
- * fr_debug_ss_adaptive_grid sets the grid of these refine kernels too. */
+ * fr_debug_ss_adaptive_grid sets the grid of these refine kernels too.  FR_PT_ROAD_SCALED is out of scope of THESE calls; ADAPTIVE
+ * SUPERSAMPLED SCALED DE below has calls of its own. */
 int fr_ss_adaptive_de_workspace_bytes(const fr_config *cfg, uint32_t supersample, uint32_t y0, uint32_t y1, size_t *bytes);
 int fr_render_rows_ss_adaptive_de_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre,
                                          int road, int bits, double thickness, uint32_t supersample, int threshold, double reach,
@@ -1503,6 +1506,52 @@ int fr_render_rows_ss_adaptive_de_device(const fr_config *cfg, int precision, co
 int fr_render_rows_ss_adaptive_de(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int road,
                                   int bits, double thickness, uint32_t supersample, int threshold, double reach, uint32_t y0, uint32_t y1,
                                   int channels, uint8_t *out, size_t out_len, uint64_t *refined /* may be NULL */);
+
+/* ADAPTIVE SUPERSAMPLED SCALED DE (fr_render_rows_ss_adaptive_de_pt_scaled(_device) below): ADAPTIVE SUPERSAMPLED DE past a scale of
+ * 2^440, on DE ON SCALED PT's road, with its own calls; fr_render_rows_ss_adaptive_de keeps refusing FR_PT_ROAD_SCALED.  It is
+ * ADAPTIVE SUPERSAMPLED DE word for word, with its inputs taken from the scaled road as SUPERSAMPLED SCALED DE takes them.
+ * DEFINITION, for supersample = s, 1 <= s <= FR_SS_MAX, a thickness T in output pixels, an integer threshold t, -1 <= t <= 255, a
+ * reach R in output pixels, bits in {-1, 0, 24 .. 53} and a wide centre, which is REQUIRED:
+ *   cfg_s  = cfg with width * s and height * s, every other field unchanged;
+ *   (z, iters, u) = fr_escape_rows_de_pt_scaled(cfg_s, centre, bits, ...), bit for bit; its Dw is taken over the whole image of
+ *            cfg_s, as the supersampled deep roads define;
+ *   cfg_sv = fr_de_scaled_view(cfg_s): cfg_s with scale = (sre, sim);
+ *   Ts     = T * (double)s, one f64 product;
+ *   H      = the bytes of fr_colour_de_rows_device(cfg_sv, z, iters, u, n, Ts, 3);
+ *   Dist(x, y) = D of "DE" for sample (x, y): fr_distance_rows on cfg_sv, in sample pixels, with the last factor
+ *            (double)(s * height) * min(|sre|, |sim|), one product;
+ *   Rs, p, P, Dp, ip, F, near, edge, out and refined are exactly as ADAPTIVE SUPERSAMPLED DE states them, on this H, Dist and
+ *            iters — the neighbour rule over the 8 neighbours inside the IMAGE and "a capped probe is never near" included.
+ * An algorithm without orbits gives black and refined = 0.  Consequences:
+ *   - t = -1 gives the bytes of fr_render_rows_ss_de_pt_scaled for every R (it is slower than that call: use that call);
+ *   - t = 255 with R = 0 gives the probe image;
+ *   - R = 0 is the colour rule on the shaded bytes;
+ *   - s = 1 is fr_escape_rows_de_pt_scaled followed by fr_colour_de_rows_device(cfg_v, ..., T, channels) for every t and R;
+ *   - T = 0 with R = 0 gives the bytes and the count of fr_render_rows_ss_adaptive with FR_PT_ROAD_SCALED and the same bits;
+ *   - any split of [0, height) into row pieces gives the whole image's bytes and the same total refined;
+ *   - inside WIDE PT's domain, where DE ON SCALED PT's claim 2 holds: with bits = -1 the bytes and the count equal
+ *     fr_render_rows_ss_adaptive_de's on FR_PRECISION_PT, FR_PT_ROAD_PLAIN with the same wide centre; with bits >= 0 they equal
+ *     FR_PT_ROAD_BLA's, subject to SCALED PT's own caveat about a pixel with |w| < 2^-53.
+ * Domain (else FR_ERR_INVALID_ARGUMENT with a message that names the argument, before any device work): SUPERSAMPLED SCALED DE's
+ * ON cfg_s (s in 1 .. FR_SS_MAX; s * width and s * height fit in 32 bits; DE ON SCALED PT's domain by the code the plain calls
+ * run; T finite with 0 <= T * s <= 2^20; channels 3 or 4) and ADAPTIVE SUPERSAMPLED DE's rules: threshold in -1 .. 255; reach
+ * finite with 0 <= R * s <= 2^20; width * (y1 - y0) < 2^32; d_work and a non-NULL d_refined 8-byte aligned; RGBA output 4-byte
+ * aligned.  A work_len under the workspace size or a short out_len give FR_ERR_BUFFER_TOO_SMALL.  y0 == y1 is a no-op that needs
+ * no device and no buffer.
+ * Workspace: ADAPTIVE SUPERSAMPLED DE's layout and size — the probe's z, der (it holds u), iters and colours of rows [ya, yb),
+ * then the edge list and the two counters; fr_ss_adaptive_de_workspace_bytes serves these calls unchanged.
+ * Asynchrony, d_refined and the host form's split above the scratch cap are fr_render_rows_ss_adaptive_de(_device)'s.  With
+ * profiling on, fr_last_kernel_name reports ss_refine_de_scaled_kernel, or ss_mark_de_kernel when no refine pass runs, and
+ * fr_last_kernel_ms the span of the whole call.  fr_debug_ss_adaptive_grid sets the grid of this refine kernel too.  The _tf twins
+ * (LINEAR-LIGHT SUPERSAMPLING below) replace F by that section's filter and nothing else.  No mark, colour or distance kernel is
+ * added or changed.  The command line stays as it is. */
+int fr_render_rows_ss_adaptive_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness,
+                                                   uint32_t supersample, int threshold, double reach, uint32_t y0, uint32_t y1, int channels,
+                                                   void *d_out, size_t out_len, void *d_work, size_t work_len,
+                                                   void *d_refined /* uint64 on the device, may be NULL */, void *hip_stream);
+int fr_render_rows_ss_adaptive_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness, uint32_t supersample,
+                                            int threshold, double reach, uint32_t y0, uint32_t y1, int channels, uint8_t *out, size_t out_len,
+                                            uint64_t *refined /* may be NULL */);
 
 /* LINEAR-LIGHT SUPERSAMPLING (the _tf calls below).  Every supersampled call ends in the same reduction, the average of the s*s
  * sample BYTES.  The bytes are display-encoded (sRGB) values, so that average is not an average of light: one white sample
@@ -1588,6 +1637,13 @@ int fr_render_rows_ss_adaptive_de_tf_device(const fr_config *cfg, int precision,
                                             int road, int bits, double thickness, uint32_t supersample, int transfer, int threshold,
                                             double reach, uint32_t y0, uint32_t y1, int channels, void *d_out, size_t out_len, void *d_work,
                                             size_t work_len, void *d_refined /* uint64 on the device, may be NULL */, void *hip_stream);
+int fr_render_rows_ss_adaptive_de_pt_scaled_tf(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness,
+                                               uint32_t supersample, int transfer, int threshold, double reach, uint32_t y0, uint32_t y1,
+                                               int channels, uint8_t *out, size_t out_len, uint64_t *refined /* may be NULL */);
+int fr_render_rows_ss_adaptive_de_pt_scaled_tf_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, double thickness,
+                                                      uint32_t supersample, int transfer, int threshold, double reach, uint32_t y0,
+                                                      uint32_t y1, int channels, void *d_out, size_t out_len, void *d_work, size_t work_len,
+                                                      void *d_refined /* uint64 on the device, may be NULL */, void *hip_stream);
 /* Host only, no device needed: pointers into the library's own copy of L (256 entries) and of T[1 .. 255] (255 entries, T[k] at
  * index k - 1), so a binding or a test reads the definition from the library itself.  Either argument may be NULL.  fr_ss_table
  * is `const uint16_t *`: the call is int fr_ss_transfer_tables(const uint16_t **decode256, const uint16_t **thresholds255). */

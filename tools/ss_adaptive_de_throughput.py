@@ -8,16 +8,20 @@ work on a stream of the tool's own.  Cases:
   pt-wide   a deep view with structure at every scale on plain PT with a wide centre: the Julia set of -0.8 + 0.156i at its
             repelling fixed point (1 + sqrt(1 - 4 J)) / 2, scale 2^200, n = 5, cap 3000, limit 2 (tools/ss_adaptive_throughput.py's)
   bla-wide  the same view on BLA-PT
+  scaled-plain  the same Julia view at scale 2^900, n = 16 — it has the same structure at every scale — on SCALED PT's plain
+            loop (bits -1) through fr_render_rows_ss_adaptive_de_pt_scaled_device
+  scaled-bla    the same on SCALED PT's table form (bits 0)
 Variants, per (case, s):
-  full      fr_render_rows_ss_de_device with best_bytes: the existing call, the baseline
-  r0, r2    fr_render_rows_ss_adaptive_de_device at reach 0 and 2, with their refined shares
+  full      fr_render_rows_ss_de_device (scaled-*: fr_render_rows_ss_de_pt_scaled_device) with best_bytes: the existing call, the
+            baseline
+  r0, r2    fr_render_rows_ss_adaptive_de_device (scaled-*: its _pt_scaled sibling) at reach 0 and 2, with their refined shares
   all       the same call at threshold -1 (every pixel refined: full's bytes, by the slower way)
   probe     the same call at threshold 255, reach 0: the DE probe, its colours and ss_mark_de_kernel alone, no refine launch
   plain     fr_render_rows_ss_adaptive_device (unshaded, threshold 8), for scale
 The expectation beside each ratio is 1 / s^2 + share: the probe costs one sample of every pixel, the refine pass s^2 of the
 edge pixels; the probe's colours and the mark pass come on top.
 
-    python3 tools/ss_adaptive_de_throughput.py [--reps 7] [--out profiles/ss_adaptive_de_throughput.txt] [--cases f64,pt-wide,bla-wide]"""
+    python3 tools/ss_adaptive_de_throughput.py [--reps 7] [--out profiles/ss_adaptive_de_throughput.txt] [--cases f64,pt-wide,bla-wide,scaled-plain,scaled-bla]"""
 import argparse
 import ctypes as C
 import json
@@ -30,7 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-CASES = ["f64", "pt-wide", "bla-wide"]
+CASES = ["f64", "pt-wide", "bla-wide", "scaled-plain", "scaled-bla"]
 SS = [2, 4]
 T, TAU = 1.0, 8
 CHILD_LIMIT = 300  # seconds, per (case, s)
@@ -59,6 +63,8 @@ def child(case, s, reps):
     cfg = fr.Config.new()
     cfg.width, cfg.height = 1920, 1080
     ce, precision, road = None, 0, 0
+    scaled = case.startswith("scaled-")
+    words, bits = (16, -1 if case == "scaled-plain" else 0) if scaled else (5, 0)
     if case == "f64":
         cfg.iterations = 1024
     else:
@@ -69,14 +75,14 @@ def child(case, s, reps):
 
         cfg.limit = 2.0
         cfg.iterations = 3000
-        cfg.scale.re = cfg.scale.im = 2.0 ** 200
+        cfg.scale.re = cfg.scale.im = 2.0 ** (900 if scaled else 200)
         cfg.algo = 2
         cfg.julia_set.re, cfg.julia_set.im = -0.8, 0.156
         a, b = Fraction(cfg.julia_set.re), Fraction(cfg.julia_set.im)  # the f64 values, exactly
         c0 = (1 + cmath.sqrt(1 - 4 * complex(cfg.julia_set.re, cfg.julia_set.im))) / 2
         # z^2 - z + J = 0 times its conjugate: a real quartic with the fixed point among its roots
-        cst = WO.wide_centre(*WO.newton([1, -2, 1 + 2 * a, -2 * a, a * a + b * b], c0.real, c0.imag), 5).c_struct()
-        ce, precision, road = C.byref(cst), 3, 1 if case == "bla-wide" else 0
+        cst = WO.wide_centre(*WO.newton([1, -2, 1 + 2 * a, -2 * a, a * a + b * b], c0.real, c0.imag), words).c_struct()
+        ce, precision, road = C.byref(cst), 3, 2 if scaled else 1 if case == "bla-wide" else 0
     _mn, best = fr.ss_de_workspace_bytes(cfg, s)
     need = max(best, fr.ss_adaptive_de_workspace_bytes(cfg, s), fr.ss_adaptive_workspace_bytes(cfg, s))
     work = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -86,18 +92,27 @@ def child(case, s, reps):
     counts = {k: torch.zeros(1, dtype=torch.int64, device=dev) for k in ("r0", "r2", "all", "probe", "plain")}
 
     def adaptive_de(key, tau, reach):
+        def run_scaled():
+            _native.check(lib.fr_render_rows_ss_adaptive_de_pt_scaled_device(C.byref(cfg), ce, bits, T, s, tau, reach, 0, cfg.height, 3,
+                                                                             outs[key].data_ptr(), nbytes, work.data_ptr(), work.numel(),
+                                                                             counts[key].data_ptr(), st))
+
         def run():
             _native.check(lib.fr_render_rows_ss_adaptive_de_device(C.byref(cfg), precision, None, ce, road, 0, T, s, tau, reach, 0, cfg.height, 3,
                                                                    outs[key].data_ptr(), nbytes, work.data_ptr(), work.numel(),
                                                                    counts[key].data_ptr(), st))
-        return run
+        return run_scaled if scaled else run
 
     def full():
+        if scaled:
+            _native.check(lib.fr_render_rows_ss_de_pt_scaled_device(C.byref(cfg), ce, bits, T, s, 0, cfg.height, 3, outs["full"].data_ptr(), nbytes,
+                                                                    work.data_ptr(), best, st))
+            return
         _native.check(lib.fr_render_rows_ss_de_device(C.byref(cfg), precision, None, ce, road, 0, T, s, 0, cfg.height, 3, outs["full"].data_ptr(),
                                                       nbytes, work.data_ptr(), best, st))
 
     def plain():
-        _native.check(lib.fr_render_rows_ss_adaptive_device(C.byref(cfg), precision, None, ce, road, 0, s, TAU, 0, cfg.height, 3,
+        _native.check(lib.fr_render_rows_ss_adaptive_device(C.byref(cfg), precision, None, ce, road, bits, s, TAU, 0, cfg.height, 3,
                                                             outs["plain"].data_ptr(), nbytes, work.data_ptr(), work.numel(),
                                                             counts["plain"].data_ptr(), st))
 
