@@ -26,6 +26,29 @@
  *     pixel (x, y) of the image lives at byte 3*(y*width + x).
  *   - There is no CPU fallback: without a usable gfx950 device every compute call fails with
  *     FR_ERR_NO_DEVICE.
+ *
+ * STREAM ORDER — the contract of every entry point with a `void *hip_stream` parameter (a hipStream_t; NULL = the null stream),
+ * stated once; the per-call comments say "asynchronous on `hip_stream`" and mean this.
+ *   - ALL device work of the call — every kernel, every memset (the adaptive calls' counters, the survivor lists' and the
+ *     statistics' zeroing) and every device-to-device copy — is enqueued on `hip_stream`, in the order the call's definition
+ *     needs, and on no other stream (but for a cache miss's own copies, below): work the caller queued on that stream before the call (filling the inputs, an earlier call
+ *     that writes the state) is finished before the call's work starts, and work queued behind it sees its results.  This holds on
+ *     a non-blocking stream (hipStreamNonBlocking), which does not synchronise with the null stream.  The call returns without
+ *     waiting for the stream and allocates no device memory, with these exceptions, all bounded by work already queued:
+ *       a CACHE MISS — a PT, BLA-PT or SCALED PT call whose view's orbit or table the context does not hold (a new view, or a
+ *         higher cap that CONTINUES the cached orbits) computes it on the host, uploads it synchronously and frees the one it
+ *         replaces, which waits for the device.  This is the one place where device work is NOT on `hip_stream`: a continuation
+ *         copies the entries it keeps device-to-device on the NULL stream and the host waits for that stream before anything is
+ *         launched, so the copies are complete — like the synchronous upload — before the call enqueues its first kernel;
+ *       a FULL RING — a render that finds the 16 palette / counter slots or the 3 survivor-list buffers all in flight waits for
+ *         the oldest one's event;
+ *       the FIRST TWO-PASS GROWTH — the first two-pass render that needs survivor lists larger than any before reallocates them;
+ *       and, on F64 / F32, the first render of a view of 131 072 tiles and more, which takes one blocking 40 us sample.
+ *   - Until the stream has drained the caller keeps alive, and does not touch from another stream, every DEVICE buffer it
+ *     passed: outputs, the kept arrays a call reads or continues in place, and the workspace it lends (which holds the call's
+ *     lists and their counters).  Host arguments (cfg, pos_lo, the centre's words, opts) are read before the call returns.
+ *   - fr_render_rgb8_multi_device takes no stream: it renders on streams of its own (see there).
+ *   tests/test_gpu_stream_order.py holds every such entry point to this behind a gate on a non-blocking stream.
  */
 #ifndef FRACTAL_HIP_H
 #define FRACTAL_HIP_H
@@ -607,7 +630,8 @@ int fr_render_rows_rgb8(const fr_config *cfg, int precision, uint32_t y0, uint32
                         size_t out_len);
 
 /* Same, into DEVICE memory, asynchronously on `hip_stream` (a hipStream_t, NULL = the null
- * stream).  For callers that keep the image in HBM (multi-GPU gather, GUI upload). */
+ * stream; STREAM ORDER above is the contract, here and for every call below that takes a stream).
+ * For callers that keep the image in HBM (multi-GPU gather, GUI upload). */
 int fr_render_rows_rgb8_device(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1,
                                void *d_out, size_t out_len, void *hip_stream);
 
