@@ -526,13 +526,9 @@ int bla_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, con
     if (rc != FR_OK) return rc;
     fr_kparams p;
     fill_params(cfg, default_opts(), p);
-    if (cfg->algo == 2) {
-        if (a.linear) ss_refine_bla_kernel<true, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, t);
-        else ss_refine_bla_kernel<true, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, t);
-    } else {
-        if (a.linear) ss_refine_bla_kernel<false, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, t);
-        else ss_refine_bla_kernel<false, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, t);
-    }
+    ss_refine_instance(cfg->algo == 2, a.linear, [&](auto J, auto L) {
+        ss_refine_bla_kernel<J(), L()><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, t);
+    });
     HIP_TRY(hipGetLastError());
     return FR_OK;
 }

@@ -338,34 +338,46 @@ int host_rgb(uint8_t *out, size_t need, Launch &&launch) {
     return FR_OK;
 }
 
-/* Raw results: launch(ctx, d_z, d_iters, d_dz, d_m, stream) over z (zb bytes) and iters (ib bytes) — either may be NULL,
- * its device pointer then is too — and, where dz is given, the PT state's second pair dz / m of the same sizes behind them
- * in the same two scratch buffers.  upload: the arrays go to the device first (the extensions continue them). */
+/* Raw results: launch(ctx, d_z, d_iters, d_dz, d_m, d_der, stream) over z (zb bytes) and iters (ib bytes) — either may be
+ * NULL, its device pointer then is too — and, where they are given, the PT state's second pair dz / m and DE's derivative
+ * der of the same sizes behind them in the same two scratch buffers: z, dz, der in the context's z scratch, iters, m in its
+ * iters scratch, an array that is not given taking no room.  upload: the arrays go to the device first (the extensions
+ * continue them). */
 template <class Launch>
-int host_raw(double *z, size_t zb, uint32_t *iters, size_t ib, double *dz, uint32_t *m, bool upload, Launch &&launch) {
+int host_raw(double *z, size_t zb, uint32_t *iters, size_t ib, double *dz, uint32_t *m, double *der, bool upload, Launch &&launch) {
     LifeShared ls;
     Ctx *ctx;
     int rc = primary(&ctx);
     if (rc != FR_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (z) rc = ctx->reserve(ctx->z, dz ? 2 * zb : zb);
+    if (z) rc = ctx->reserve(ctx->z, (1 + (dz != nullptr) + (der != nullptr)) * zb);
     if (rc == FR_OK && iters) rc = ctx->reserve(ctx->iters, m ? 2 * ib : ib);
     if (rc != FR_OK) return rc;
     char *const d_z = z ? static_cast<char *>(ctx->z.ptr) : nullptr, *const d_iters = iters ? static_cast<char *>(ctx->iters.ptr) : nullptr;
     const struct {
         void *host, *dev;
         size_t bytes;
-    } arrays[4] = {{z, d_z, zb}, {iters, d_iters, ib}, {dz, dz ? d_z + zb : nullptr, zb}, {m, m ? d_iters + ib : nullptr, ib}};
+    } arrays[5] = {{z, d_z, zb}, {iters, d_iters, ib}, {dz, dz ? d_z + zb : nullptr, zb}, {m, m ? d_iters + ib : nullptr, ib},
+                   {der, der ? d_z + (dz ? 2 : 1) * zb : nullptr, zb}};
     if (upload)
         for (const auto &a : arrays)
             if (a.host) HIP_TRY(hipMemcpyAsync(a.dev, a.host, a.bytes, hipMemcpyHostToDevice, ctx->stream));
     rc = launch(*ctx, static_cast<double *>(arrays[0].dev), static_cast<uint32_t *>(arrays[1].dev), static_cast<double *>(arrays[2].dev),
-                static_cast<uint32_t *>(arrays[3].dev), ctx->stream);
+                static_cast<uint32_t *>(arrays[3].dev), static_cast<double *>(arrays[4].dev), ctx->stream);
     if (rc != FR_OK) return rc;
     for (const auto &a : arrays)
         if (a.host) HIP_TRY(hipMemcpyAsync(a.host, a.dev, a.bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FR_OK;
+}
+
+/* the calls without a derivative: launch(ctx, d_z, d_iters, d_dz, d_m, stream) */
+template <class Launch>
+int host_raw(double *z, size_t zb, uint32_t *iters, size_t ib, double *dz, uint32_t *m, bool upload, Launch &&launch) {
+    return host_raw(z, zb, iters, ib, dz, m, nullptr, upload,
+                    [&](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_dz, uint32_t *d_m, double *, hipStream_t stream) {
+                        return launch(ctx, d_z, d_iters, d_dz, d_m, stream);
+                    });
 }
 
 /* ---- the pieces the row calls are made of.  An entry point builds its Centre, runs its road's domain check and hands one

@@ -551,121 +551,8 @@ const char *const kDeScope =
     "raising a DE view's cap with fr_escape_extend* on (z, iters) alone: fr_escape_extend_de(_device) (F64) and "
     "fr_escape_extend_de_pt(_device) (PT) continue the derivative with them";
 
-/* the launch of rows [y0, y1) with their derivatives; arguments already checked */
-int de_launch(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const fr_kparams &p, double *d_z, uint32_t *d_iters,
-              double *d_der, hipStream_t stream, const char *&kname) {
-    const bool julia = cfg->algo == FR_ALGO_JULIA;
-    const bool orbits = julia || cfg->algo == FR_ALGO_MANDELBROT;
-    kname = precision == FR_PRECISION_PT ? "escape_pt_de_kernel" : "escape_de_kernel";
-    if (p.ncols == 0 || p.nrows == 0) return FR_OK;
-    dim3 grid, block;
-    HIP_TRY(fr_deep_grid(p, grid, block));
-    if (precision == FR_PRECISION_PT) {
-        std::shared_ptr<PtOrbit> keep; /* alive until the launch is enqueued */
-        PtOrbitView v;
-        if (orbits) {
-            const int rc = pt_orbit_view(ctx, cfg, c, keep, v);
-            if (rc != FR_OK) return rc;
-        }
-        if (julia)
-            escape_pt_de_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, v.x, v.k, v.x_last, v.k_last);
-        else
-            escape_pt_de_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, v.x, v.k, v.x_last, v.k_last);
-    } else if (julia) {
-        escape_de_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der);
-    } else {
-        escape_de_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der);
-    }
-    HIP_TRY(hipGetLastError());
-    return FR_OK;
-}
-
-/* DE's domain on top of the road's own, and the arrays; *work = false: no rows, nothing to do and no device needed */
-int de_check(const fr_config *cfg, int precision, const Centre &c, bool wide_call, uint32_t y0, uint32_t y1, const void *z, const void *iters,
-             const void *der, bool *work) {
-    *work = false;
-    int rc = check_rows(cfg, y0, y1);
-    if (rc != FR_OK) return rc;
-    if (wide_call) {
-        if (!c.wide) return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_PT, wide centre: centre is NULL");
-    } else if (precision != FR_PRECISION_F64 && precision != FR_PRECISION_PT) {
-        return fail(FR_ERR_INVALID_ARGUMENT, kDeScope);
-    } else if (precision == FR_PRECISION_F64 && c.pos_lo) {
-        return fail(FR_ERR_INVALID_ARGUMENT, "distance estimation: pos_lo is for FR_PRECISION_PT only; the F64 road takes none");
-    }
-    if (precision == FR_PRECISION_PT) {
-        rc = c.check(cfg, FR_PRECISION_PT); /* PT's domain, or WIDE PT's with its |scale| <= 2^440 */
-        if (rc != FR_OK) return rc;
-    }
-    if (!(cfg->limit <= 0x1p20))
-        return fail(FR_ERR_INVALID_ARGUMENT, "distance estimation: limit must be <= 2^20 (the bound that keeps the derivative's overflow "
-                                             "below one pixel rests on it)");
-    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
-    if (!z || !iters || !der) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: a DE render writes z, iters and der, all three");
-    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u))
-        return fail(FR_ERR_INVALID_ARGUMENT, "z and der must be 8-byte aligned, iters 4-byte aligned");
-    *work = true;
-    return FR_OK;
-}
-
-auto de_rows(const fr_config *cfg, int precision, const Centre &c, uint32_t y0, uint32_t y1) {
-    return [=](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_der, uint32_t *, hipStream_t stream) {
-        return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) {
-            return de_launch(ctx, cfg, precision, c, p, d_z, d_iters, d_der, stream, kname);
-        });
-    };
-}
-
-int de_rows_device(const fr_config *cfg, int precision, const Centre &c, bool wide_call, uint32_t y0, uint32_t y1, void *d_z, void *d_iters,
-                   void *d_der, void *hip_stream) {
-    bool work;
-    const int rc = de_check(cfg, precision, c, wide_call, y0, y1, d_z, d_iters, d_der, &work);
-    if (rc != FR_OK || !work) return rc;
-    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
-        return de_rows(cfg, precision, c, y0, y1)(ctx, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters), static_cast<double *>(d_der),
-                                                 nullptr, stream);
-    });
-}
-
-int de_rows_host(const fr_config *cfg, int precision, const Centre &c, bool wide_call, uint32_t y0, uint32_t y1, double *z, uint32_t *iters,
-                 double *der) {
-    bool work;
-    const int rc = de_check(cfg, precision, c, wide_call, y0, y1, z, iters, der, &work);
-    if (rc != FR_OK || !work) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    /* z and der share the context's z scratch, as the PT state's z and dz do */
-    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), der, nullptr, false, de_rows(cfg, precision, c, y0, y1));
-}
-
-/* ---- RESUMABLE DE: the state render of PT and the two extensions ------------------------------------------------------------ */
-
-/* The arrays of a RESUMABLE DE call and what is left of its domain after the road's (check_state's order and its M < N text,
- * fr_ctx.h).  pt: the five arrays of a perturbation road's state (`road` and `d_name` name it and its offset in the texts: PT and
- * dz, SCALED PT and w), else the F64 road's three.  `from` = nullptr: the state render.  *work = false:
- * a legal call with nothing to do (no rows; for an extension also M == N or an algorithm without orbits). */
-int de_state_check(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, bool pt, const void *z, const void *iters,
-                   const void *dz, const void *m, const void *der, bool *work, const char *road = "PT", const char *d_name = "dz") {
-    *work = false;
-    if (from && cfg->iterations < *from)
-        return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from a stored state");
-    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
-    if (pt) {
-        if (!z || !iters || !dz || !m || !der)
-            return fail(FR_ERR_INVALID_ARGUMENT, std::string("NULL array: the DE state of ") + road + " is z, iters, " + d_name + ", m and der, all five");
-        if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(dz) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) ||
-            (reinterpret_cast<uintptr_t>(iters) & 3u) || (reinterpret_cast<uintptr_t>(m) & 3u))
-            return fail(FR_ERR_INVALID_ARGUMENT, std::string("z, ") + d_name + " and der must be 8-byte aligned, iters and m 4-byte aligned");
-    } else {
-        if (!z || !iters || !der) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the extension of a DE view needs z, iters and der, all three");
-        if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u))
-            return fail(FR_ERR_INVALID_ARGUMENT, "z and der must be 8-byte aligned, iters 4-byte aligned");
-    }
-    *work = !from || (cfg->iterations != *from && (cfg->algo == FR_ALGO_MANDELBROT || cfg->algo == FR_ALGO_JULIA));
-    return FR_OK;
-}
-
 /* the domain of the F64 extension short of its arrays */
-int de_extend_f64_check(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1) {
+int de_extend_f64_domain(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1) {
     const int rc = check_rows(cfg, y0, y1);
     if (rc != FR_OK) return rc;
     if (precision == FR_PRECISION_PT)
@@ -673,10 +560,7 @@ int de_extend_f64_check(const fr_config *cfg, int precision, uint32_t y0, uint32
                                              "fr_escape_rows_de; fr_escape_rows_de_pt_state(_device) stores that state and "
                                              "fr_escape_extend_de_pt(_device) continues it");
     if (precision != FR_PRECISION_F64) return fail(FR_ERR_INVALID_ARGUMENT, kDeScope);
-    if (!(cfg->limit <= 0x1p20))
-        return fail(FR_ERR_INVALID_ARGUMENT, "distance estimation: limit must be <= 2^20 (the bound that keeps the derivative's overflow "
-                                             "below one pixel rests on it)");
-    return FR_OK;
+    return check_de_limit(cfg);
 }
 
 /* the domain of the PT state calls short of their arrays: PT's with a dd centre, WIDE PT's with a wide one, and DE's limit */
@@ -686,89 +570,77 @@ int de_pt_state_domain(const fr_config *cfg, const Centre &c, uint32_t y0, uint3
     if (c.wide && c.pos_lo) return fail(FR_ERR_INVALID_ARGUMENT, "distance estimation: pos_lo must be NULL when a wide centre is given");
     rc = c.check(cfg, FR_PRECISION_PT);
     if (rc != FR_OK) return rc;
-    if (!(cfg->limit <= 0x1p20))
-        return fail(FR_ERR_INVALID_ARGUMENT, "distance estimation: limit must be <= 2^20 (the bound that keeps the derivative's overflow "
-                                             "below one pixel rests on it)");
-    return FR_OK;
+    return check_de_limit(cfg);
 }
 
-/* the F64 extension of rows [y0, y1) between the profiling events; arguments already checked, there is work */
-int de_extend_f64_rows(const fr_config *cfg, uint32_t y0, uint32_t y1, uint32_t from, double *d_z, uint32_t *d_iters, double *d_der,
-                       hipStream_t stream) {
-    return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) -> int {
-        kname = "escape_extend_de_kernel";
-        if (p.ncols == 0 || p.nrows == 0 || p.iterations <= from) return FR_OK;
-        dim3 grid, block;
-        HIP_TRY(fr_deep_grid(p, grid, block));
-        if (cfg->algo == FR_ALGO_JULIA)
-            escape_extend_de_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, from);
-        else
-            escape_extend_de_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, from);
-        HIP_TRY(hipGetLastError());
-        return FR_OK;
-    });
-}
-
-/* the PT state render (from == nullptr) or its extension from *from, on the context's orbits of cfg's cap, which the cache
- * continues from those of a lower cap of the same view (fr_pt.hip: orbit_for) */
-int de_pt_state_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, double *d_z,
-                     uint32_t *d_iters, double *d_dz, uint32_t *d_m, double *d_der, hipStream_t stream) {
-    return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) -> int {
-        kname = from ? "escape_extend_pt_de_kernel" : "escape_pt_de_state_kernel";
-        const bool julia = cfg->algo == FR_ALGO_JULIA;
-        const bool orbits = julia || cfg->algo == FR_ALGO_MANDELBROT;
-        if (p.ncols == 0 || p.nrows == 0 || (from && (!orbits || p.iterations <= *from))) return FR_OK;
-        dim3 grid, block;
-        HIP_TRY(fr_deep_grid(p, grid, block));
-        std::shared_ptr<PtOrbit> keep; /* alive until the launch is enqueued */
-        PtOrbitView v;
-        if (orbits) {
-            const int rc = pt_orbit_view(ctx, cfg, c, keep, v);
-            if (rc != FR_OK) return rc;
-        }
-        if (from) {
-            if (julia)
-                escape_extend_pt_de_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_dz, d_m, d_der, *from, v.x, v.k, v.x_last,
-                                                                             v.k_last, v.ended);
+/* de_state_device's / de_state_host's callable: the F64 extension of rows [y0, y1) between the profiling events (there is no
+ * d and no m); arguments already checked, there is work */
+auto de_extend_f64_rows(const fr_config *cfg, uint32_t y0, uint32_t y1, uint32_t from) {
+    return [=](Ctx &, double *d_z, uint32_t *d_iters, double *, uint32_t *, double *d_der, hipStream_t stream) {
+        return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) -> int {
+            kname = "escape_extend_de_kernel";
+            if (p.ncols == 0 || p.nrows == 0 || p.iterations <= from) return FR_OK;
+            dim3 grid, block;
+            HIP_TRY(fr_deep_grid(p, grid, block));
+            if (cfg->algo == FR_ALGO_JULIA)
+                escape_extend_de_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, from);
             else
-                escape_extend_pt_de_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_dz, d_m, d_der, *from, v.x, v.k, v.x_last,
-                                                                              v.k_last, v.ended);
-        } else if (julia) {
-            escape_pt_de_state_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_dz, d_m, d_der, v.x, v.k, v.x_last, v.k_last, v.ended);
-        } else {
-            escape_pt_de_state_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_dz, d_m, d_der, v.x, v.k, v.x_last, v.k_last, v.ended);
-        }
-        HIP_TRY(hipGetLastError());
-        return FR_OK;
-    });
+                escape_extend_de_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, from);
+            HIP_TRY(hipGetLastError());
+            return FR_OK;
+        });
+    };
 }
 
-/* de_pt_state_rows behind fr_de.h's DeStateRows */
-struct PtStateCall {
-    const fr_config *cfg;
-    const Centre *c;
-    uint32_t y0, y1;
-    const uint32_t *from;
-    static int run(const void *self, Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_dz, uint32_t *d_m, double *d_der, hipStream_t stream) {
-        const PtStateCall &a = *static_cast<const PtStateCall *>(self);
-        return de_pt_state_rows(ctx, a.cfg, *a.c, a.y0, a.y1, a.from, d_z, d_iters, d_dz, d_m, d_der, stream);
-    }
-};
+/* the same for the PT state render (from == nullptr) or its extension from *from, on the context's orbits of cfg's cap, which
+ * the cache continues from those of a lower cap of the same view (fr_pt.hip: orbit_for) */
+auto de_pt_state_rows(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from) {
+    return [=](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_dz, uint32_t *d_m, double *d_der, hipStream_t stream) {
+        return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) -> int {
+            kname = from ? "escape_extend_pt_de_kernel" : "escape_pt_de_state_kernel";
+            const bool julia = cfg->algo == FR_ALGO_JULIA;
+            const bool orbits = julia || cfg->algo == FR_ALGO_MANDELBROT;
+            if (p.ncols == 0 || p.nrows == 0 || (from && (!orbits || p.iterations <= *from))) return FR_OK;
+            dim3 grid, block;
+            HIP_TRY(fr_deep_grid(p, grid, block));
+            std::shared_ptr<PtOrbit> keep; /* alive until the launch is enqueued */
+            PtOrbitView v;
+            if (orbits) {
+                const int rc = pt_orbit_view(ctx, cfg, c, keep, v);
+                if (rc != FR_OK) return rc;
+            }
+            if (from) {
+                if (julia)
+                    escape_extend_pt_de_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_dz, d_m, d_der, *from, v.x, v.k, v.x_last,
+                                                                                 v.k_last, v.ended);
+                else
+                    escape_extend_pt_de_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_dz, d_m, d_der, *from, v.x, v.k, v.x_last,
+                                                                                  v.k_last, v.ended);
+            } else if (julia) {
+                escape_pt_de_state_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_dz, d_m, d_der, v.x, v.k, v.x_last, v.k_last,
+                                                                            v.ended);
+            } else {
+                escape_pt_de_state_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_dz, d_m, d_der, v.x, v.k, v.x_last, v.k_last,
+                                                                             v.ended);
+            }
+            HIP_TRY(hipGetLastError());
+            return FR_OK;
+        });
+    };
+}
 
 int de_pt_state_device(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z, void *d_iters,
                        void *d_dz, void *d_m, void *d_der, void *hip_stream) {
     const int rc = de_pt_state_domain(cfg, c, y0, y1);
     if (rc != FR_OK) return rc;
-    const PtStateCall call{cfg, &c, y0, y1, from};
-    return de_state_device(cfg, y0, y1, from, d_z, d_iters, d_dz, d_m, d_der, hip_stream, "PT", "dz", DeStateRows{PtStateCall::run, &call});
+    return de_state_device(cfg, y0, y1, from, d_z, d_iters, d_dz, d_m, d_der, hip_stream, "PT", "dz", de_pt_state_rows(cfg, c, y0, y1, from));
 }
 
 int de_pt_state_host(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from, double *z, uint32_t *iters,
                      double *dz, uint32_t *m, double *der) {
     const int rc = de_pt_state_domain(cfg, c, y0, y1);
     if (rc != FR_OK) return rc;
-    const PtStateCall call{cfg, &c, y0, y1, from};
-    return de_state_host(cfg, y0, y1, from, z, iters, dz, m, der, "PT", "dz", DeStateRows{PtStateCall::run, &call});
+    return de_state_host(cfg, y0, y1, from, z, iters, dz, m, der, "PT", "dz", de_pt_state_rows(cfg, c, y0, y1, from));
 }
 
 /* the domain of the calls over stored results, short of their output */
@@ -776,10 +648,7 @@ int de_stored_check(const fr_config *cfg, const void *z, const void *iters, cons
     if (!cfg) return fail(FR_ERR_INVALID_ARGUMENT, "cfg is NULL");
     if (n > kDeMaxN) return fail(FR_ERR_INVALID_ARGUMENT, "n > 2^40: one call covers one array of at most 2^40 pixels");
     if (n == 0) return FR_OK;
-    if (!z || !iters || !der) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: the distance needs z, iters and der, all three");
-    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u))
-        return fail(FR_ERR_INVALID_ARGUMENT, "z and der must be 8-byte aligned, iters 4-byte aligned");
-    return FR_OK;
+    return check_de_arrays(z, iters, der, "NULL array: the distance needs z, iters and der, all three");
 }
 
 int de_thickness_check(double thickness) {
@@ -810,31 +679,91 @@ hipError_t fr_launch_colour_de_rows(const fr_kparams &p, const double *z, const 
     return hipGetLastError();
 }
 
-/* for the supersampled DE roads (fr_de.h): the domain check and the row launch of the calls above, called */
+/* fr_de.h: DE's own rules, the road of F64 and PT, and what is left of a state call's domain */
 namespace fr {
 
+int check_de_limit(const fr_config *cfg) {
+    if (!(cfg->limit <= 0x1p20))
+        return fail(FR_ERR_INVALID_ARGUMENT, "distance estimation: limit must be <= 2^20 (the bound that keeps the derivative's overflow "
+                                             "below one pixel rests on it)");
+    return FR_OK;
+}
+
+int check_de_arrays(const void *z, const void *iters, const void *der, const char *null_text) {
+    if (!z || !iters || !der)
+        return fail(FR_ERR_INVALID_ARGUMENT, null_text ? null_text : "NULL array: a DE render writes z, iters and der, all three");
+    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u))
+        return fail(FR_ERR_INVALID_ARGUMENT, "z and der must be 8-byte aligned, iters 4-byte aligned");
+    return FR_OK;
+}
+
+/* DE's domain on top of the road's own */
 int de_domain(const fr_config *cfg, int precision, const Centre &c, bool wide_call, uint32_t y0, uint32_t y1) {
-    alignas(8) static const char arrays[8] = {}; /* stands for the three arrays: the caller's are its workspace's, checked there */
-    bool work;
-    return de_check(cfg, precision, c, wide_call, y0, y1, arrays, arrays, arrays, &work);
+    int rc = check_rows(cfg, y0, y1);
+    if (rc != FR_OK) return rc;
+    if (wide_call) {
+        if (!c.wide) return fail(FR_ERR_INVALID_ARGUMENT, "FR_PRECISION_PT, wide centre: centre is NULL");
+    } else if (precision != FR_PRECISION_F64 && precision != FR_PRECISION_PT) {
+        return fail(FR_ERR_INVALID_ARGUMENT, kDeScope);
+    } else if (precision == FR_PRECISION_F64 && c.pos_lo) {
+        return fail(FR_ERR_INVALID_ARGUMENT, "distance estimation: pos_lo is for FR_PRECISION_PT only; the F64 road takes none");
+    }
+    if (precision == FR_PRECISION_PT) {
+        rc = c.check(cfg, FR_PRECISION_PT); /* PT's domain, or WIDE PT's with its |scale| <= 2^440 */
+        if (rc != FR_OK) return rc;
+    }
+    return check_de_limit(cfg);
 }
 
-int de_render_rows(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, uint32_t y0, uint32_t y1, double *d_z, uint32_t *d_iters,
-                   double *d_der, hipStream_t stream) {
-    return de_rows(cfg, precision, c, y0, y1)(ctx, d_z, d_iters, d_der, nullptr, stream);
+int de_launch(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const fr_kparams &p, double *d_z, uint32_t *d_iters,
+              double *d_der, hipStream_t stream, const char *&kname) {
+    const bool julia = cfg->algo == FR_ALGO_JULIA;
+    const bool orbits = julia || cfg->algo == FR_ALGO_MANDELBROT;
+    kname = precision == FR_PRECISION_PT ? "escape_pt_de_kernel" : "escape_de_kernel";
+    if (p.ncols == 0 || p.nrows == 0) return FR_OK;
+    dim3 grid, block;
+    HIP_TRY(fr_deep_grid(p, grid, block));
+    if (precision == FR_PRECISION_PT) {
+        std::shared_ptr<PtOrbit> keep; /* alive until the launch is enqueued */
+        PtOrbitView v;
+        if (orbits) {
+            const int rc = pt_orbit_view(ctx, cfg, c, keep, v);
+            if (rc != FR_OK) return rc;
+        }
+        if (julia)
+            escape_pt_de_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, v.x, v.k, v.x_last, v.k_last);
+        else
+            escape_pt_de_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der, v.x, v.k, v.x_last, v.k_last);
+    } else if (julia) {
+        escape_de_kernel<true><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der);
+    } else {
+        escape_de_kernel<false><<<grid, block, 0, stream>>>(p, d_z, d_iters, d_der);
+    }
+    HIP_TRY(hipGetLastError());
+    return FR_OK;
 }
 
-/* fr_ss_list.h: ADAPTIVE SUPERSAMPLED DE on the F64 road and PT — the probe (the road's DE kernel over the strided map) and the
- * refine pass on the orbits the probe made */
-int de_render_map(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const fr_ss_map &map, double *d_z, uint32_t *d_iters,
-                  double *d_der, hipStream_t stream) {
-    fr_kparams p;
-    fill_params(cfg, default_opts(), p);
-    map.apply(p);
-    const char *kname;
-    return de_launch(ctx, cfg, precision, c, p, d_z, d_iters, d_der, stream, kname);
+int de_state_check(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, const void *z, const void *iters, const void *d,
+                   const void *m, const void *der, const char *road, const char *d_name, bool *work) {
+    *work = false;
+    if (from && cfg->iterations < *from)
+        return fail(FR_ERR_INVALID_ARGUMENT, "cfg->iterations < from_iterations: a lower cap cannot be derived from a stored state");
+    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
+    if (road) {
+        if (!z || !iters || !d || !m || !der)
+            return fail(FR_ERR_INVALID_ARGUMENT, std::string("NULL array: the DE state of ") + road + " is z, iters, " + d_name + ", m and der, all five");
+        if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(d) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) ||
+            (reinterpret_cast<uintptr_t>(iters) & 3u) || (reinterpret_cast<uintptr_t>(m) & 3u))
+            return fail(FR_ERR_INVALID_ARGUMENT, std::string("z, ") + d_name + " and der must be 8-byte aligned, iters and m 4-byte aligned");
+    } else {
+        const int rc = check_de_arrays(z, iters, der, "NULL array: the extension of a DE view needs z, iters and der, all three");
+        if (rc != FR_OK) return rc;
+    }
+    *work = !from || (cfg->iterations != *from && (cfg->algo == FR_ALGO_MANDELBROT || cfg->algo == FR_ALGO_JULIA));
+    return FR_OK;
 }
 
+/* fr_ss_list.h: ADAPTIVE SUPERSAMPLED DE's refine pass on the F64 road and PT, on the orbits the probe made */
 int de_ss_refine(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const fr_ss_refine &a, const fr_ss_de_shade &sh,
                  uint32_t groups, hipStream_t stream) {
     const bool julia = cfg->algo == FR_ALGO_JULIA;
@@ -846,63 +775,13 @@ int de_ss_refine(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c,
         PtOrbitView v;
         const int rc = pt_orbit_view(ctx, cfg, c, keep, v);
         if (rc != FR_OK) return rc;
-        if (julia) {
-            if (a.linear) ss_refine_de_pt_kernel<true, true><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
-            else ss_refine_de_pt_kernel<true, false><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
-        } else {
-            if (a.linear) ss_refine_de_pt_kernel<false, true><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
-            else ss_refine_de_pt_kernel<false, false><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
-        }
-    } else if (julia) {
-        if (a.linear) ss_refine_de_f64_kernel<true, true><<<grid, block, 0, stream>>>(p, a, sh);
-        else ss_refine_de_f64_kernel<true, false><<<grid, block, 0, stream>>>(p, a, sh);
+        ss_refine_instance(julia, a.linear, [&](auto J, auto L) {
+            ss_refine_de_pt_kernel<J(), L()><<<grid, block, 0, stream>>>(p, a, sh, v.x, v.k, v.x_last, v.k_last);
+        });
     } else {
-        if (a.linear) ss_refine_de_f64_kernel<false, true><<<grid, block, 0, stream>>>(p, a, sh);
-        else ss_refine_de_f64_kernel<false, false><<<grid, block, 0, stream>>>(p, a, sh);
+        ss_refine_instance(julia, a.linear, [&](auto J, auto L) { ss_refine_de_f64_kernel<J(), L()><<<grid, block, 0, stream>>>(p, a, sh); });
     }
     HIP_TRY(hipGetLastError());
-    return FR_OK;
-}
-
-int de_state_device(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z, void *d_iters, void *d_d, void *d_m,
-                    void *d_der, void *hip_stream, const char *road, const char *d_name, const DeStateRows &rows) {
-    bool work;
-    const int rc = de_state_check(cfg, y0, y1, from, true, d_z, d_iters, d_d, d_m, d_der, &work, road, d_name);
-    if (rc != FR_OK || !work) return rc;
-    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
-        return rows.fn(rows.self, ctx, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters), static_cast<double *>(d_d),
-                       static_cast<uint32_t *>(d_m), static_cast<double *>(d_der), stream);
-    });
-}
-
-/* The host form of the five arrays, done here as fr_distance_rows does its own (host_raw carries four): z, d and der in the
- * context's z scratch, iters and m in its iters scratch; an extension uploads them first. */
-int de_state_host(const fr_config *cfg, uint32_t y0, uint32_t y1, const uint32_t *from, double *z, uint32_t *iters, double *d, uint32_t *m,
-                  double *der, const char *road, const char *d_name, const DeStateRows &rows) {
-    bool work;
-    int rc = de_state_check(cfg, y0, y1, from, true, z, iters, d, m, der, &work, road, d_name);
-    if (rc != FR_OK || !work) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0), zb = npx * 2 * sizeof(double), ib = npx * sizeof(uint32_t);
-    LifeShared ls;
-    Ctx *ctx;
-    rc = primary(&ctx);
-    if (rc != FR_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    rc = ctx->reserve(ctx->z, 3 * zb);
-    if (rc == FR_OK) rc = ctx->reserve(ctx->iters, 2 * ib);
-    if (rc != FR_OK) return rc;
-    char *const dd = static_cast<char *>(ctx->z.ptr), *const du = static_cast<char *>(ctx->iters.ptr);
-    const struct {
-        void *host, *dev;
-        size_t bytes;
-    } arrays[5] = {{z, dd, zb}, {iters, du, ib}, {d, dd + zb, zb}, {m, du + ib, ib}, {der, dd + 2 * zb, zb}};
-    if (from)
-        for (const auto &a : arrays) HIP_TRY(hipMemcpyAsync(a.dev, a.host, a.bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = rows.fn(rows.self, *ctx, static_cast<double *>(arrays[0].dev), static_cast<uint32_t *>(arrays[1].dev),
-                 static_cast<double *>(arrays[2].dev), static_cast<uint32_t *>(arrays[3].dev), static_cast<double *>(arrays[4].dev), ctx->stream);
-    if (rc != FR_OK) return rc;
-    for (const auto &a : arrays) HIP_TRY(hipMemcpyAsync(a.host, a.dev, a.bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FR_OK;
 }
 
@@ -912,52 +791,53 @@ extern "C" {
 
 int fr_escape_rows_de_device(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, void *d_z,
                              void *d_iters, void *d_der, void *hip_stream) {
-    return de_rows_device(cfg, precision, Centre{pos_lo, nullptr}, false, y0, y1, d_z, d_iters, d_der, hip_stream);
+    const Centre c{pos_lo, nullptr};
+    const int rc = de_domain(cfg, precision, c, false, y0, y1);
+    if (rc != FR_OK) return rc;
+    return de_rows_device(cfg, y0, y1, d_z, d_iters, d_der, hip_stream, de_rows(cfg, y0, y1, de_road(de_launch, cfg, precision, c)));
 }
 
 int fr_escape_rows_de(const fr_config *cfg, int precision, const fr_imaginary *pos_lo, uint32_t y0, uint32_t y1, double *z, uint32_t *iters,
                       double *der) {
-    return de_rows_host(cfg, precision, Centre{pos_lo, nullptr}, false, y0, y1, z, iters, der);
+    const Centre c{pos_lo, nullptr};
+    const int rc = de_domain(cfg, precision, c, false, y0, y1);
+    if (rc != FR_OK) return rc;
+    return de_rows_host(cfg, y0, y1, z, iters, der, de_rows(cfg, y0, y1, de_road(de_launch, cfg, precision, c)));
 }
 
 int fr_escape_rows_de_pt_wide_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, void *d_z, void *d_iters,
                                      void *d_der, void *hip_stream) {
-    return de_rows_device(cfg, FR_PRECISION_PT, Centre{nullptr, centre}, true, y0, y1, d_z, d_iters, d_der, hip_stream);
+    const Centre c{nullptr, centre};
+    const int rc = de_domain(cfg, FR_PRECISION_PT, c, true, y0, y1);
+    if (rc != FR_OK) return rc;
+    return de_rows_device(cfg, y0, y1, d_z, d_iters, d_der, hip_stream, de_rows(cfg, y0, y1, de_road(de_launch, cfg, (int)FR_PRECISION_PT, c)));
 }
 
 int fr_escape_rows_de_pt_wide(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, double *z, uint32_t *iters,
                               double *der) {
-    return de_rows_host(cfg, FR_PRECISION_PT, Centre{nullptr, centre}, true, y0, y1, z, iters, der);
+    const Centre c{nullptr, centre};
+    const int rc = de_domain(cfg, FR_PRECISION_PT, c, true, y0, y1);
+    if (rc != FR_OK) return rc;
+    return de_rows_host(cfg, y0, y1, z, iters, der, de_rows(cfg, y0, y1, de_road(de_launch, cfg, (int)FR_PRECISION_PT, c)));
 }
 
 /* ---- RESUMABLE DE (include/fractal_hip.h) ---- */
 
 int fr_escape_extend_de_device(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint32_t from_iterations, void *d_z,
                                void *d_iters, void *d_der, void *hip_stream) {
-    int rc = de_extend_f64_check(cfg, precision, y0, y1);
+    const int rc = de_extend_f64_domain(cfg, precision, y0, y1);
     if (rc != FR_OK) return rc;
-    bool work;
-    rc = de_state_check(cfg, y0, y1, &from_iterations, false, d_z, d_iters, nullptr, nullptr, d_der, &work);
-    if (rc != FR_OK || !work) return rc;
-    return device_form(hip_stream, [&](Ctx &, hipStream_t stream) {
-        return de_extend_f64_rows(cfg, y0, y1, from_iterations, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
-                                  static_cast<double *>(d_der), stream);
-    });
+    return de_state_device(cfg, y0, y1, &from_iterations, d_z, d_iters, nullptr, nullptr, d_der, hip_stream, nullptr, nullptr,
+                           de_extend_f64_rows(cfg, y0, y1, from_iterations));
 }
 
 int fr_escape_extend_de(const fr_config *cfg, int precision, uint32_t y0, uint32_t y1, uint32_t from_iterations, double *z, uint32_t *iters,
                         double *der) {
-    int rc = de_extend_f64_check(cfg, precision, y0, y1);
+    const int rc = de_extend_f64_domain(cfg, precision, y0, y1);
     if (rc != FR_OK) return rc;
-    bool work;
-    rc = de_state_check(cfg, y0, y1, &from_iterations, false, z, iters, nullptr, nullptr, der, &work);
-    if (rc != FR_OK || !work) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
     /* z and der share the context's z scratch, as in fr_escape_rows_de; uploaded first, as fr_escape_extend does */
-    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), der, nullptr, true,
-                    [&](Ctx &, double *d_z, uint32_t *d_iters, double *d_der, uint32_t *, hipStream_t stream) {
-                        return de_extend_f64_rows(cfg, y0, y1, from_iterations, d_z, d_iters, d_der, stream);
-                    });
+    return de_state_host(cfg, y0, y1, &from_iterations, z, iters, nullptr, nullptr, der, nullptr, nullptr,
+                         de_extend_f64_rows(cfg, y0, y1, from_iterations));
 }
 
 int fr_escape_rows_de_pt_state_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, uint32_t y0,

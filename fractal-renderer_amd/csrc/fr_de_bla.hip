@@ -23,8 +23,9 @@
  * ss_refine_de_bla_kernel<JULIA>: ADAPTIVE SUPERSAMPLED DE's refine pass on this road (fr_ss_adaptive_de.hip; fr_ss_list.h: the
  * claim loop) — orbit_bla_de on the s x s samples of the listed edge pixels, each coloured and shaded through fr_ss_de_sample.h.
  *
- * The calls, at the end of the file: BLA-PT's domain check (fr_bla.h: bla_check), DE's limit and arrays, then the profiled
- * launch through the row-call bodies of fr_ctx.h (device_form, host_raw, profiled_rows).
+ * The host half, at the end of the file, is the three things fr_de.h asks of a road — bla_de_domain (BLA-PT's domain check,
+ * fr_bla.h: bla_check, then DE's limit), bla_de_launch (the kernel on given parameters, on the context's orbits and tables) and
+ * bla_de_ss_refine — and the two calls, each the domain and fr_de.h's device or host form of a three-array row call.
  */
 #include <cmath>
 #include <memory>
@@ -245,9 +246,21 @@ int de_bla_dev_fill(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, s
     return FR_OK;
 }
 
-/* the launch of rows with their derivatives on the context's orbits and tables; arguments already checked */
-int launch_bla_de(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_kparams &p, double *d_z, uint32_t *d_iters,
-                  double *d_der, hipStream_t stream) {
+}  // namespace
+
+/* fr_de.h: the road's domain and its launch; fr_ss_list.h: its refine launch */
+namespace fr {
+
+/* BLA-PT's domain (bits resolved in place), then DE's limit */
+int bla_de_domain(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1) {
+    const int rc = bla_check(cfg, c, bits, y0, y1);
+    return rc != FR_OK ? rc : check_de_limit(cfg);
+}
+
+/* on the context's orbits and tables */
+int bla_de_launch(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_kparams &p, double *d_z, uint32_t *d_iters,
+                  double *d_der, hipStream_t stream, const char *&kname) {
+    kname = "escape_bla_de_kernel";
     if (p.ncols == 0 || p.nrows == 0) return FR_OK;
     dim3 grid, block;
     HIP_TRY(fr_deep_grid(p, grid, block));
@@ -270,59 +283,6 @@ int launch_bla_de(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, con
     return FR_OK;
 }
 
-/* BLA-PT's domain (bits resolved in place), DE's limit, then the arrays; *work = false: no rows, nothing to do and no device
- * needed */
-int check_bla_de(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1, const void *z, const void *iters,
-                 const void *der, bool *work) {
-    *work = false;
-    const int rc = bla_check(cfg, c, bits, y0, y1);
-    if (rc != FR_OK) return rc;
-    if (!(cfg->limit <= 0x1p20))
-        return fail(FR_ERR_INVALID_ARGUMENT, "distance estimation: limit must be <= 2^20 (the bound that keeps the derivative's overflow "
-                                             "below one pixel rests on it)");
-    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
-    if (!z || !iters || !der) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: a DE render writes z, iters and der, all three");
-    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u))
-        return fail(FR_ERR_INVALID_ARGUMENT, "z and der must be 8-byte aligned, iters 4-byte aligned");
-    *work = true;
-    return FR_OK;
-}
-
-/* rows [y0, y1) as one launch between the profiling events: host_raw's callable, with der where it carries dz */
-auto bla_de_rows(const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1) {
-    return [=](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_der, uint32_t *, hipStream_t stream) {
-        return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) {
-            kname = "escape_bla_de_kernel";
-            return launch_bla_de(ctx, cfg, c, bits, p, d_z, d_iters, d_der, stream);
-        });
-    };
-}
-
-}  // namespace
-
-/* for the supersampled DE roads (fr_de.h): the domain check and the row launch of the calls below, called */
-namespace fr {
-
-int bla_de_domain(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1) {
-    alignas(8) static const char arrays[8] = {}; /* stands for the three arrays: the caller's are its workspace's, checked there */
-    bool work;
-    return check_bla_de(cfg, c, bits, y0, y1, arrays, arrays, arrays, &work);
-}
-
-int bla_de_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, double *d_z, uint32_t *d_iters,
-                       double *d_der, hipStream_t stream) {
-    return bla_de_rows(cfg, c, bits, y0, y1)(ctx, d_z, d_iters, d_der, nullptr, stream);
-}
-
-/* fr_ss_list.h: ADAPTIVE SUPERSAMPLED DE on BLA-PT — the probe (the road's DE kernel over the strided map) and the refine pass */
-int bla_de_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_map &map, double *d_z, uint32_t *d_iters,
-                      double *d_der, hipStream_t stream) {
-    fr_kparams p;
-    fill_params(cfg, default_opts(), p);
-    map.apply(p);
-    return launch_bla_de(ctx, cfg, c, bits, p, d_z, d_iters, d_der, stream);
-}
-
 int bla_de_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, const fr_ss_de_shade &sh,
                      uint32_t groups, hipStream_t stream) {
     std::shared_ptr<PtOrbit> orbit; /* alive until the launch is enqueued, like the table */
@@ -332,13 +292,9 @@ int bla_de_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, 
     if (rc != FR_OK) return rc;
     fr_kparams p;
     fill_params(cfg, default_opts(), p);
-    if (cfg->algo == FR_ALGO_JULIA) {
-        if (a.linear) ss_refine_de_bla_kernel<true, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
-        else ss_refine_de_bla_kernel<true, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
-    } else {
-        if (a.linear) ss_refine_de_bla_kernel<false, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
-        else ss_refine_de_bla_kernel<false, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
-    }
+    ss_refine_instance(cfg->algo == FR_ALGO_JULIA, a.linear, [&](auto J, auto L) {
+        ss_refine_de_bla_kernel<J(), L()><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, sh, t);
+    });
     HIP_TRY(hipGetLastError());
     return FR_OK;
 }
@@ -350,24 +306,17 @@ extern "C" {
 int fr_escape_rows_de_pt_bla_device(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
                                     uint32_t y1, void *d_z, void *d_iters, void *d_der, void *hip_stream) {
     const Centre c{pos_lo, centre};
-    bool work;
-    const int rc = check_bla_de(cfg, c, bits, y0, y1, d_z, d_iters, d_der, &work);
-    if (rc != FR_OK || !work) return rc;
-    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
-        return bla_de_rows(cfg, c, bits, y0, y1)(ctx, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
-                                                 static_cast<double *>(d_der), nullptr, stream);
-    });
+    const int rc = bla_de_domain(cfg, c, bits, y0, y1);
+    if (rc != FR_OK) return rc;
+    return de_rows_device(cfg, y0, y1, d_z, d_iters, d_der, hip_stream, de_rows(cfg, y0, y1, de_road(bla_de_launch, cfg, c, bits)));
 }
 
 int fr_escape_rows_de_pt_bla(const fr_config *cfg, const fr_imaginary *pos_lo, const fr_wide_centre *centre, int bits, uint32_t y0,
                              uint32_t y1, double *z, uint32_t *iters, double *der) {
     const Centre c{pos_lo, centre};
-    bool work;
-    const int rc = check_bla_de(cfg, c, bits, y0, y1, z, iters, der, &work);
-    if (rc != FR_OK || !work) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    /* z and der share the context's z scratch, as in fr_escape_rows_de */
-    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), der, nullptr, false, bla_de_rows(cfg, c, bits, y0, y1));
+    const int rc = bla_de_domain(cfg, c, bits, y0, y1);
+    if (rc != FR_OK) return rc;
+    return de_rows_host(cfg, y0, y1, z, iters, der, de_rows(cfg, y0, y1, de_road(bla_de_launch, cfg, c, bits)));
 }
 
 } /* extern "C" */

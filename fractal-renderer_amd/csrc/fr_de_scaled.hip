@@ -30,15 +30,16 @@
  * orbit_pt_scaled_de_state, the one copy of the state step with the derivative.  escape_pt_scaled_de_kernel and orbit_pt_scaled_de
  * stay as they are.  The table form has no state (BLA-PT's reason: i + 2^k <= iterations).  Registers and occupancy: DESIGN.md 3.27.
  *
- * The calls, at the end of the file: SCALED PT's domain check (fr_bla.h: scaled_check), DE's arrays, then the profiled launch
- * through the row-call bodies of fr_ctx.h (device_form, host_raw, profiled_rows); the state calls hand their launch to RESUMABLE
- * DE's five-array road (fr_de.h: de_state_device, de_state_host).  scaled_de_domain and scaled_de_render_rows lend the DE render
- * to SUPERSAMPLED SCALED DE (fr_ss_de.hip).
+ * The host half, at the end of the file, is the three things fr_de.h asks of a road — scaled_de_domain (SCALED PT's domain check,
+ * fr_bla.h: scaled_check), scaled_de_launch (the kernel on given parameters, on the context's orbits and tables) and
+ * scaled_de_ss_refine — and the calls: the rows are the domain and fr_de.h's device or host form of a three-array row call, the
+ * state calls hand their launch, a callable, to RESUMABLE DE's five-array forms (fr_de.h: de_state_device, de_state_host).
+ * SUPERSAMPLED SCALED DE (fr_ss_de.hip) renders through the same domain and launch.
  *
  * ADAPTIVE SUPERSAMPLED SCALED DE (include/fractal_hip.h; fr_ss_adaptive_de.hip): ss_refine_de_scaled_kernel<JULIA, BLA, LINEAR>,
  * persistent waves that run orbit_pt_scaled_de / orbit_bla_scaled_de on the s x s samples of the listed pixels through fr_ss_list.h's
- * claim loop, each sample coloured and shaded through fr_ss_de_sample.h; scaled_de_render_map, the DE launch over the probe's
- * strided map, and scaled_de_ss_refine, the refine launch.  Registers and occupancy: DESIGN.md 3.34.
+ * claim loop, each sample coloured and shaded through fr_ss_de_sample.h; the probe is scaled_de_launch over the strided map
+ * (fr_ss_list.h: de_render_map), and scaled_de_ss_refine is the refine launch.  Registers and occupancy: DESIGN.md 3.34.
  */
 #include <cmath>
 #include <memory>
@@ -321,17 +322,17 @@ __global__ __launch_bounds__(kSsRefineThreads) void ss_refine_de_scaled_kernel(c
     });
 }
 
-template <bool JULIA>
-hipError_t launch_refine(bool bla, const fr_kparams &p, const fr_ss_refine &a, const fr_ss_de_shade &sh, const ScaledDev &t, uint32_t groups,
-                         hipStream_t stream) {
+hipError_t launch_refine(bool julia, bool bla, const fr_kparams &p, const fr_ss_refine &a, const fr_ss_de_shade &sh, const ScaledDev &t,
+                         uint32_t groups, hipStream_t stream) {
     const dim3 grid(groups), block(kSsRefineThreads);
-    if (bla) {
-        if (a.linear) ss_refine_de_scaled_kernel<JULIA, true, true><<<grid, block, 0, stream>>>(p, a, sh, t);
-        else ss_refine_de_scaled_kernel<JULIA, true, false><<<grid, block, 0, stream>>>(p, a, sh, t);
-    } else {
-        if (a.linear) ss_refine_de_scaled_kernel<JULIA, false, true><<<grid, block, 0, stream>>>(p, a, sh, t);
-        else ss_refine_de_scaled_kernel<JULIA, false, false><<<grid, block, 0, stream>>>(p, a, sh, t);
-    }
+    if (bla)
+        fr::ss_refine_instance(julia, a.linear, [&](auto J, auto L) {
+            ss_refine_de_scaled_kernel<J(), true, L()><<<grid, block, 0, stream>>>(p, a, sh, t);
+        });
+    else
+        fr::ss_refine_instance(julia, a.linear, [&](auto J, auto L) {
+            ss_refine_de_scaled_kernel<J(), false, L()><<<grid, block, 0, stream>>>(p, a, sh, t);
+        });
     return hipGetLastError();
 }
 
@@ -529,10 +530,78 @@ using namespace fr;
 
 namespace {
 
-/* the launch of rows with their scaled derivatives on the context's orbits and tables; `p` holds the view's scale, the kernels
- * get a copy with the scaled divisors.  bits < 0: no table.  Arguments already checked. */
-int launch_scaled_de(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_kparams &p, double *d_z, uint32_t *d_iters,
-                     double *d_der, hipStream_t stream) {
+/* ---- RESUMABLE SCALED DE: the plain loop's rows with their DE state, and that state continued to a higher cap ---------------- */
+
+/* de_state_device's / de_state_host's callable (fr_de.h): the state render (from == nullptr) or its extension from *from between
+ * the profiling events, on the context's orbits of cfg's cap, which pt_orbit_view's cache continues from those of a lower cap of
+ * the same view and shares with every other scaled or wide call of it */
+auto scaled_de_state_rows(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1, const uint32_t *from) {
+    return [=](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_w, uint32_t *d_m, double *d_der, hipStream_t stream) {
+        return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) -> int {
+            kname = from ? "escape_extend_pt_scaled_de_kernel" : "escape_pt_scaled_de_state_kernel";
+            const bool julia = cfg->algo == FR_ALGO_JULIA, extend = from != nullptr;
+            if (p.ncols == 0 || p.nrows == 0) return FR_OK;
+            if (cfg->algo != FR_ALGO_MANDELBROT && !julia) { /* no escape-time algorithm: zeros in all five arrays (the extension never gets here) */
+                HIP_TRY(launch_state<false>(p, 0, false, d_z, d_iters, d_w, d_m, d_der, ScaledDev{}, 0, stream));
+                return FR_OK;
+            }
+            const ScaledConsts k = scaled_consts(cfg);
+            p.scale_re = k.sre;
+            p.scale_im = k.sim;
+            std::shared_ptr<PtOrbit> orbit; /* alive until the launch is enqueued */
+            PtOrbitView v;
+            const int rc = pt_orbit_view(ctx, cfg, c, orbit, v);
+            if (rc != FR_OK) return rc;
+            ScaledDev t{};
+            t.x_orbit = v.x;
+            t.k_orbit = v.k;
+            t.x_last = v.x_last;
+            t.k_last = v.k_last;
+            t.S = k.S;
+            t.Sinv = k.Sinv;
+            const uint32_t n = extend ? *from : 0u;
+            HIP_TRY(julia ? launch_state<true>(p, n, extend, d_z, d_iters, d_w, d_m, d_der, t, v.ended, stream)
+                          : launch_state<false>(p, n, extend, d_z, d_iters, d_w, d_m, d_der, t, v.ended, stream));
+            return FR_OK;
+        });
+    };
+}
+
+/* the state calls are the plain loop's: SCALED PT's domain with bits = -1 and the centre required */
+int scaled_de_state_domain(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1) {
+    int bits = -1;
+    return scaled_check(cfg, c, bits, y0, y1);
+}
+
+int scaled_de_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z,
+                           void *d_iters, void *d_w, void *d_m, void *d_der, void *hip_stream) {
+    const Centre c{nullptr, centre, true};
+    const int rc = scaled_de_state_domain(cfg, c, y0, y1);
+    if (rc != FR_OK) return rc;
+    return de_state_device(cfg, y0, y1, from, d_z, d_iters, d_w, d_m, d_der, hip_stream, "SCALED PT", "w",
+                           scaled_de_state_rows(cfg, c, y0, y1, from));
+}
+
+int scaled_de_state_host(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, const uint32_t *from, double *z,
+                         uint32_t *iters, double *w, uint32_t *m, double *der) {
+    const Centre c{nullptr, centre, true};
+    const int rc = scaled_de_state_domain(cfg, c, y0, y1);
+    if (rc != FR_OK) return rc;
+    return de_state_host(cfg, y0, y1, from, z, iters, w, m, der, "SCALED PT", "w", scaled_de_state_rows(cfg, c, y0, y1, from));
+}
+
+}  // namespace
+
+/* fr_de.h: the road's domain and its launch; fr_ss_list.h: its refine launch */
+namespace fr {
+
+/* SCALED PT's domain (bits resolved in place; its limit <= 2^20 is DE's too) */
+int scaled_de_domain(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1) { return scaled_check(cfg, c, bits, y0, y1); }
+
+/* on the context's orbits and tables; `p` holds the view's scale, the kernels get a copy with the scaled divisors */
+int scaled_de_launch(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_kparams &p, double *d_z, uint32_t *d_iters,
+                     double *d_der, hipStream_t stream, const char *&kname) {
+    kname = bits < 0 ? "escape_pt_scaled_de_kernel" : "escape_bla_scaled_de_kernel";
     if (p.ncols == 0 || p.nrows == 0) return FR_OK;
     const bool julia = cfg->algo == FR_ALGO_JULIA, bla = bits >= 0;
     if (cfg->algo != FR_ALGO_MANDELBROT && !julia) { /* no escape-time algorithm: zeros, and no orbit is asked for */
@@ -552,124 +621,6 @@ int launch_scaled_de(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, 
     return FR_OK;
 }
 
-/* SCALED PT's domain (bits resolved in place; its limit <= 2^20 is DE's too), then the arrays; *work = false: no rows, nothing
- * to do and no device needed */
-int check_scaled_de(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1, const void *z, const void *iters,
-                    const void *der, bool *work) {
-    *work = false;
-    const int rc = scaled_check(cfg, c, bits, y0, y1);
-    if (rc != FR_OK) return rc;
-    if ((size_t)cfg->width * (size_t)(y1 - y0) == 0) return FR_OK;
-    if (!z || !iters || !der) return fail(FR_ERR_INVALID_ARGUMENT, "NULL array: a DE render writes z, iters and der, all three");
-    if ((reinterpret_cast<uintptr_t>(z) & 7u) || (reinterpret_cast<uintptr_t>(der) & 7u) || (reinterpret_cast<uintptr_t>(iters) & 3u))
-        return fail(FR_ERR_INVALID_ARGUMENT, "z and der must be 8-byte aligned, iters 4-byte aligned");
-    *work = true;
-    return FR_OK;
-}
-
-/* rows [y0, y1) as one launch between the profiling events: host_raw's callable, with der where it carries dz */
-auto scaled_de_rows(const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1) {
-    return [=](Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_der, uint32_t *, hipStream_t stream) {
-        return profiled_rows(cfg, default_opts(), y0, y1, 0, stream, [&](fr_kparams &p, const char *&kname) {
-            kname = bits < 0 ? "escape_pt_scaled_de_kernel" : "escape_bla_scaled_de_kernel";
-            return launch_scaled_de(ctx, cfg, c, bits, p, d_z, d_iters, d_der, stream);
-        });
-    };
-}
-
-/* ---- RESUMABLE SCALED DE: the plain loop's rows with their DE state, and that state continued to a higher cap ---------------- */
-
-/* The state render (from == nullptr) or its extension from *from between the profiling events, on the context's orbits of
- * cfg's cap, which pt_orbit_view's cache continues from those of a lower cap of the same view and shares with every other scaled
- * or wide call of it.  fr_de.h's DeStateRows: `run` with the call's arguments behind `self`. */
-struct ScaledDeStateCall {
-    const fr_config *cfg;
-    const Centre *c;
-    uint32_t y0, y1;
-    const uint32_t *from;
-    static int run(const void *self, Ctx &ctx, double *d_z, uint32_t *d_iters, double *d_w, uint32_t *d_m, double *d_der, hipStream_t stream) {
-        const ScaledDeStateCall &a = *static_cast<const ScaledDeStateCall *>(self);
-        const fr_config *cfg = a.cfg;
-        return profiled_rows(cfg, default_opts(), a.y0, a.y1, 0, stream, [&](fr_kparams &p, const char *&kname) -> int {
-            kname = a.from ? "escape_extend_pt_scaled_de_kernel" : "escape_pt_scaled_de_state_kernel";
-            const bool julia = cfg->algo == FR_ALGO_JULIA, extend = a.from != nullptr;
-            if (p.ncols == 0 || p.nrows == 0) return FR_OK;
-            if (cfg->algo != FR_ALGO_MANDELBROT && !julia) { /* no escape-time algorithm: zeros in all five arrays (the extension never gets here) */
-                HIP_TRY(launch_state<false>(p, 0, false, d_z, d_iters, d_w, d_m, d_der, ScaledDev{}, 0, stream));
-                return FR_OK;
-            }
-            const ScaledConsts k = scaled_consts(cfg);
-            p.scale_re = k.sre;
-            p.scale_im = k.sim;
-            std::shared_ptr<PtOrbit> orbit; /* alive until the launch is enqueued */
-            PtOrbitView v;
-            const int rc = pt_orbit_view(ctx, cfg, *a.c, orbit, v);
-            if (rc != FR_OK) return rc;
-            ScaledDev t{};
-            t.x_orbit = v.x;
-            t.k_orbit = v.k;
-            t.x_last = v.x_last;
-            t.k_last = v.k_last;
-            t.S = k.S;
-            t.Sinv = k.Sinv;
-            const uint32_t n = extend ? *a.from : 0u;
-            HIP_TRY(julia ? launch_state<true>(p, n, extend, d_z, d_iters, d_w, d_m, d_der, t, v.ended, stream)
-                          : launch_state<false>(p, n, extend, d_z, d_iters, d_w, d_m, d_der, t, v.ended, stream));
-            return FR_OK;
-        });
-    }
-};
-
-/* the state calls are the plain loop's: SCALED PT's domain with bits = -1 and the centre required */
-int scaled_de_state_domain(const fr_config *cfg, const Centre &c, uint32_t y0, uint32_t y1) {
-    int bits = -1;
-    return scaled_check(cfg, c, bits, y0, y1);
-}
-
-int scaled_de_state_device(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, const uint32_t *from, void *d_z,
-                           void *d_iters, void *d_w, void *d_m, void *d_der, void *hip_stream) {
-    const Centre c{nullptr, centre, true};
-    const int rc = scaled_de_state_domain(cfg, c, y0, y1);
-    if (rc != FR_OK) return rc;
-    const ScaledDeStateCall call{cfg, &c, y0, y1, from};
-    return de_state_device(cfg, y0, y1, from, d_z, d_iters, d_w, d_m, d_der, hip_stream, "SCALED PT", "w",
-                           DeStateRows{ScaledDeStateCall::run, &call});
-}
-
-int scaled_de_state_host(const fr_config *cfg, const fr_wide_centre *centre, uint32_t y0, uint32_t y1, const uint32_t *from, double *z,
-                         uint32_t *iters, double *w, uint32_t *m, double *der) {
-    const Centre c{nullptr, centre, true};
-    const int rc = scaled_de_state_domain(cfg, c, y0, y1);
-    if (rc != FR_OK) return rc;
-    const ScaledDeStateCall call{cfg, &c, y0, y1, from};
-    return de_state_host(cfg, y0, y1, from, z, iters, w, m, der, "SCALED PT", "w", DeStateRows{ScaledDeStateCall::run, &call});
-}
-
-}  // namespace
-
-/* for SUPERSAMPLED SCALED DE (fr_de.h): the domain check and the row launch of the calls below, called */
-namespace fr {
-
-int scaled_de_domain(const fr_config *cfg, const Centre &c, int &bits, uint32_t y0, uint32_t y1) {
-    alignas(8) static const char arrays[8] = {}; /* stands for the three arrays: the caller's are its workspace's, checked there */
-    bool work;
-    return check_scaled_de(cfg, c, bits, y0, y1, arrays, arrays, arrays, &work);
-}
-
-int scaled_de_render_rows(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, uint32_t y0, uint32_t y1, double *d_z,
-                          uint32_t *d_iters, double *d_der, hipStream_t stream) {
-    return scaled_de_rows(cfg, c, bits, y0, y1)(ctx, d_z, d_iters, d_der, nullptr, stream);
-}
-
-/* fr_ss_list.h: ADAPTIVE SUPERSAMPLED SCALED DE — the probe (the road's DE kernel over the strided map) and the refine pass */
-int scaled_de_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_map &map, double *d_z, uint32_t *d_iters,
-                         double *d_der, hipStream_t stream) {
-    fr_kparams p;
-    fill_params(cfg, default_opts(), p);
-    map.apply(p);
-    return launch_scaled_de(ctx, cfg, c, bits, p, d_z, d_iters, d_der, stream);
-}
-
 int scaled_de_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, const fr_ss_de_shade &sh,
                         uint32_t groups, hipStream_t stream) {
     const ScaledConsts k = scaled_consts(cfg);
@@ -682,8 +633,7 @@ int scaled_de_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bit
     ScaledDev t;
     const int rc = scaled_dev_fill(ctx, cfg, c, bits, k, orbit, table, t);
     if (rc != FR_OK) return rc;
-    const bool julia = cfg->algo == FR_ALGO_JULIA;
-    HIP_TRY(julia ? launch_refine<true>(bits >= 0, p, a, sh, t, groups, stream) : launch_refine<false>(bits >= 0, p, a, sh, t, groups, stream));
+    HIP_TRY(launch_refine(cfg->algo == FR_ALGO_JULIA, bits >= 0, p, a, sh, t, groups, stream));
     return FR_OK;
 }
 
@@ -717,24 +667,17 @@ int fr_escape_extend_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *ce
 int fr_escape_rows_de_pt_scaled_device(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, void *d_z,
                                        void *d_iters, void *d_der, void *hip_stream) {
     const Centre c{nullptr, centre, true};
-    bool work;
-    const int rc = check_scaled_de(cfg, c, bits, y0, y1, d_z, d_iters, d_der, &work);
-    if (rc != FR_OK || !work) return rc;
-    return device_form(hip_stream, [&](Ctx &ctx, hipStream_t stream) {
-        return scaled_de_rows(cfg, c, bits, y0, y1)(ctx, static_cast<double *>(d_z), static_cast<uint32_t *>(d_iters),
-                                                    static_cast<double *>(d_der), nullptr, stream);
-    });
+    const int rc = scaled_de_domain(cfg, c, bits, y0, y1);
+    if (rc != FR_OK) return rc;
+    return de_rows_device(cfg, y0, y1, d_z, d_iters, d_der, hip_stream, de_rows(cfg, y0, y1, de_road(scaled_de_launch, cfg, c, bits)));
 }
 
 int fr_escape_rows_de_pt_scaled(const fr_config *cfg, const fr_wide_centre *centre, int bits, uint32_t y0, uint32_t y1, double *z,
                                 uint32_t *iters, double *der) {
     const Centre c{nullptr, centre, true};
-    bool work;
-    const int rc = check_scaled_de(cfg, c, bits, y0, y1, z, iters, der, &work);
-    if (rc != FR_OK || !work) return rc;
-    const size_t npx = (size_t)cfg->width * (size_t)(y1 - y0);
-    /* z and der share the context's z scratch, as in fr_escape_rows_de */
-    return host_raw(z, npx * 2 * sizeof(double), iters, npx * sizeof(uint32_t), der, nullptr, false, scaled_de_rows(cfg, c, bits, y0, y1));
+    const int rc = scaled_de_domain(cfg, c, bits, y0, y1);
+    if (rc != FR_OK) return rc;
+    return de_rows_host(cfg, y0, y1, z, iters, der, de_rows(cfg, y0, y1, de_road(scaled_de_launch, cfg, c, bits)));
 }
 
 int fr_de_scaled_view(const fr_config *cfg, fr_config *view) {

@@ -681,13 +681,12 @@ int pt_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, const fr_ss_re
     if (rc != FR_OK) return rc;
     fr_kparams p;
     fill_params(cfg, default_opts(), p);
-    if (cfg->algo == 2) {
-        if (a.linear) ss_refine_pt_kernel<true, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, o->dev + o->k_offset, o->x_last, o->k_last);
-        else ss_refine_pt_kernel<true, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, o->dev + o->k_offset, o->x_last, o->k_last);
-    } else {
-        if (a.linear) ss_refine_pt_kernel<false, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, o->dev, o->x_last, o->x_last);
-        else ss_refine_pt_kernel<false, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, o->dev, o->x_last, o->x_last);
-    }
+    const bool julia = cfg->algo == 2; /* Mandelbrot: K is X */
+    const double2 *const k_orbit = julia ? o->dev + o->k_offset : o->dev;
+    const uint32_t k_last = julia ? o->k_last : o->x_last;
+    ss_refine_instance(julia, a.linear, [&](auto J, auto L) {
+        ss_refine_pt_kernel<J(), L()><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a, o->dev, k_orbit, o->x_last, k_last);
+    });
     HIP_TRY(hipGetLastError());
     return FR_OK;
 }

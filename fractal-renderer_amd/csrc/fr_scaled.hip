@@ -682,23 +682,10 @@ int scaled_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, 
     if (rc != FR_OK) return rc;
     const dim3 grid(groups), block(kSsRefineThreads);
     const bool julia = cfg->algo == 2;
-    if (bits >= 0) {
-        if (julia) {
-            if (a.linear) ss_refine_scaled_kernel<true, true, true><<<grid, block, 0, stream>>>(p, a, t);
-            else ss_refine_scaled_kernel<true, true, false><<<grid, block, 0, stream>>>(p, a, t);
-        } else {
-            if (a.linear) ss_refine_scaled_kernel<false, true, true><<<grid, block, 0, stream>>>(p, a, t);
-            else ss_refine_scaled_kernel<false, true, false><<<grid, block, 0, stream>>>(p, a, t);
-        }
-    } else {
-        if (julia) {
-            if (a.linear) ss_refine_scaled_kernel<true, false, true><<<grid, block, 0, stream>>>(p, a, t);
-            else ss_refine_scaled_kernel<true, false, false><<<grid, block, 0, stream>>>(p, a, t);
-        } else {
-            if (a.linear) ss_refine_scaled_kernel<false, false, true><<<grid, block, 0, stream>>>(p, a, t);
-            else ss_refine_scaled_kernel<false, false, false><<<grid, block, 0, stream>>>(p, a, t);
-        }
-    }
+    if (bits >= 0)
+        ss_refine_instance(julia, a.linear, [&](auto J, auto L) { ss_refine_scaled_kernel<J(), true, L()><<<grid, block, 0, stream>>>(p, a, t); });
+    else
+        ss_refine_instance(julia, a.linear, [&](auto J, auto L) { ss_refine_scaled_kernel<J(), false, L()><<<grid, block, 0, stream>>>(p, a, t); });
     HIP_TRY(hipGetLastError());
     return FR_OK;
 }

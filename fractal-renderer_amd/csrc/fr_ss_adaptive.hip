@@ -260,13 +260,9 @@ int ssa_render(Ctx &ctx, const SsaRoad &r, const fr_config *cfg, uint32_t s, int
         if (r.precision == FR_PRECISION_F64) {
             fr_kparams p;
             fill_params(cs, default_opts(), p);
-            if (cfg->algo == FR_ALGO_JULIA) {
-                if (a.linear) ss_refine_f64_kernel<true, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a);
-                else ss_refine_f64_kernel<true, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a);
-            } else {
-                if (a.linear) ss_refine_f64_kernel<false, true><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a);
-                else ss_refine_f64_kernel<false, false><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a);
-            }
+            ss_refine_instance(cfg->algo == FR_ALGO_JULIA, a.linear, [&](auto J, auto L) {
+                ss_refine_f64_kernel<J(), L()><<<dim3(groups), dim3(kSsRefineThreads), 0, stream>>>(p, a);
+            });
             HIP_TRY(hipGetLastError());
             kname = "ss_refine_f64_kernel";
         } else if (r.road == FR_PT_ROAD_BLA) {

@@ -5,7 +5,7 @@
  * with D < R * s is refined whatever its neighbours look like.  Four passes on the caller's stream, no host read between them:
  *   1. the DE probe: the road's EXISTING DE kernel on cfg_s over the strided pixel map (x_first = p, x_stride = s,
  *      y_first = s ya + p, y_stride = s, block_rows = 1), rows [ya, yb) = [max(y0 - 1, 0), min(y1 + 1, height)), into the
- *      workspace's z, der and iters: the full render's samples by construction (fr_ss_list.h: de_render_map, bla_de_render_map);
+ *      workspace's z, der and iters: the full render's samples by construction (fr_ss_list.h: de_render_map over the road's launch);
  *   2. the probe colours: colour_de_rows_kernel (fr_de.h: fr_launch_colour_de_rows) over those arrays with cfg_s's pixels and the
  *      thickness T * s, into the workspace's colour area;
  *   3. ss_mark_de_kernel: ss_mark_kernel's tile and pieces (fr_ss_list.h) plus `near` from the lane's OWN (z, iters, der) through
@@ -21,7 +21,7 @@
  *
  * ADAPTIVE SUPERSAMPLED SCALED DE (include/fractal_hip.h): fr_render_rows_ss_adaptive_de_pt_scaled and its three other spellings,
  * the road that the calls above keep refusing.  Their own check (ssad_scaled_check: DE ON SCALED PT's domain on cfg_s, `pixels` from
- * the scaled view) and the scaled arm of ssad_render's two switches — the probe is scaled_de_render_map, the refine pass
+ * the scaled view) and the scaled arm of ssad_render's two switches — the probe is de_render_map over scaled_de_launch, the refine pass
  * ss_refine_de_scaled_kernel (fr_de_scaled.hip); passes 2 and 3 run unchanged, the scaled view enters through `pixels` alone.
  */
 #include "fr_bla.h" /* scaled_consts */
@@ -198,11 +198,11 @@ int ssad_render(Ctx &ctx, const SsadRoad &r, const fr_config *cfg, uint32_t s, i
     const uint32_t half = s / 2u;
     const fr_ss_map map{cfg->width, l.yb - l.ya, half, s, s * l.ya + half, s};
     if (r.road == FR_PT_ROAD_SCALED)
-        rc = scaled_de_render_map(ctx, cs, r.c, r.bits, map, d_z, d_iters, d_der, stream);
+        rc = de_render_map(ctx, cs, map, d_z, d_iters, d_der, stream, de_road(scaled_de_launch, cs, r.c, r.bits));
     else if (r.road == FR_PT_ROAD_BLA)
-        rc = bla_de_render_map(ctx, cs, r.c, r.bits, map, d_z, d_iters, d_der, stream);
+        rc = de_render_map(ctx, cs, map, d_z, d_iters, d_der, stream, de_road(bla_de_launch, cs, r.c, r.bits));
     else
-        rc = de_render_map(ctx, cs, r.precision, r.c, map, d_z, d_iters, d_der, stream);
+        rc = de_render_map(ctx, cs, map, d_z, d_iters, d_der, stream, de_road(de_launch, cs, r.precision, r.c));
     if (rc != FR_OK) return rc;
 
     /* 2. the probe colours, shaded as the samples of cfg_s are */

@@ -6,10 +6,10 @@
  *     image of cfg_s in between;
  *   - the entry points: fr_colour_de_rows_ss_device / fr_colour_de_ss_rgb8 (a KEPT anti-aliased DE view recoloured),
  *     fr_ss_de_workspace_bytes, fr_render_rows_ss_de_device (bands of source rows rendered into a workspace the caller lends — the
- *     road's own DE row launch, fr_de.h — each shaded and filtered into its place, all on the caller's stream) and
+ *     road's own DE launch between the profiling events, fr_de.h: de_render_rows — each shaded and filtered into its place, all on the caller's stream) and
  *     fr_render_rows_ss_de (the same into a host buffer, through context scratch), and SUPERSAMPLED SCALED DE's
- *     fr_render_rows_ss_de_pt_scaled(_device): the same band loop and the same fused kernel with DE ON SCALED PT's row launch
- *     (fr_de.h: scaled_de_render_rows) and the scaled view's pixels.
+ *     fr_render_rows_ss_de_pt_scaled(_device): the same band loop and the same fused kernel with DE ON SCALED PT's launch
+ *     (fr_de.h: scaled_de_launch) and the scaled view's pixels.
  * The render kernels are not touched: a band is an ordinary row-range DE render of the large image.  The band loop, the two
  * halves of a banded call and the thickness and pixels of the shade are fr_ss.h's ("3.32"); the recolour's host form
  * goes through host_rgb (fr_ctx.h).
@@ -328,9 +328,10 @@ struct SsDeRoad {
     double ts, pixels;
     /* source rows [ya, yb) of cfg_s with their derivatives on the road */
     int rows(Ctx &ctx, uint32_t ya, uint32_t yb, double *d_z, uint32_t *d_iters, double *d_der, hipStream_t stream) const {
-        if (road == FR_PT_ROAD_SCALED) return scaled_de_render_rows(ctx, &pl.cfg_s, c, bits, ya, yb, d_z, d_iters, d_der, stream);
-        if (road == FR_PT_ROAD_BLA) return bla_de_render_rows(ctx, &pl.cfg_s, c, bits, ya, yb, d_z, d_iters, d_der, stream);
-        return de_render_rows(ctx, &pl.cfg_s, precision, c, ya, yb, d_z, d_iters, d_der, stream);
+        const fr_config *const cs = &pl.cfg_s;
+        if (road == FR_PT_ROAD_SCALED) return de_render_rows(ctx, cs, ya, yb, d_z, d_iters, d_der, stream, de_road(scaled_de_launch, cs, c, bits));
+        if (road == FR_PT_ROAD_BLA) return de_render_rows(ctx, cs, ya, yb, d_z, d_iters, d_der, stream, de_road(bla_de_launch, cs, c, bits));
+        return de_render_rows(ctx, cs, ya, yb, d_z, d_iters, d_der, stream, de_road(de_launch, cs, precision, c));
     }
 };
 

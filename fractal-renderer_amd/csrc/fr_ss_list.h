@@ -1,13 +1,16 @@
 /*
  * fr_ss_list.h — internal: what the pieces of ADAPTIVE SUPERSAMPLING (include/fractal_hip.h) share — the strided pixel map of
- * the probe pass, the mark pass's tile and its pieces, the edge list as a refine kernel sees it, the claim loop of the persistent refine waves, and the road
- * launches that fr_ss_adaptive.hip calls.  The refine kernels themselves sit beside their road's loop (fr_pt.hip, fr_bla.hip,
+ * the probe pass, the mark pass's tile and its pieces, the edge list as a refine kernel sees it, the claim loop of the persistent refine waves, the one
+ * launch of a refine kernel's JULIA x LINEAR instance, the DE probe over a road's launch (fr_de.h), and the road launches that
+ * fr_ss_adaptive.hip and fr_ss_adaptive_de.hip call.  The refine kernels themselves sit beside their road's loop (fr_pt.hip, fr_bla.hip,
  * fr_scaled.hip; the F64 road's in fr_ss_adaptive.hip) — and ADAPTIVE SUPERSAMPLED DE's (fr_ss_adaptive_de.hip) beside their road's
  * DE loop (fr_de.hip, fr_de_bla.hip, fr_de_scaled.hip).  The device code here has internal linkage: each translation unit
  * compiles its own copy into its own kernels.
  */
 #ifndef FR_SS_LIST_H
 #define FR_SS_LIST_H
+
+#include <type_traits>
 
 #include "fr_ctx.h"
 
@@ -242,22 +245,38 @@ fr_ss_refine ss_refine_args(uint8_t *out, const uint32_t *list, unsigned long lo
                             uint32_t bpp, int transfer = 0);
 uint32_t ss_refine_groups(const fr_ss_refine &a, uint32_t rows);
 
+/* The launch of a refine kernel, written once for all eight: launch(J, L) is handed the kernel's JULIA and LINEAR template
+ * arguments for the run-time `julia` and `linear` (a.linear) as std::true_type / std::false_type values, and launches
+ * kernel<J(), L()>, or kernel<J(), BLA, L()> inside the scaled roads' branch on `bla`. */
+template <class Launch>
+void ss_refine_instance(bool julia, bool linear, Launch &&launch) {
+    if (julia) {
+        if (linear) launch(std::true_type{}, std::true_type{});
+        else launch(std::true_type{}, std::false_type{});
+    } else {
+        if (linear) launch(std::false_type{}, std::true_type{});
+        else launch(std::false_type{}, std::false_type{});
+    }
+}
+
 /* ADAPTIVE SUPERSAMPLED DE's road launches (fr_ss_adaptive_de.hip calls them) on cfg_s (`cfg` below), arguments already checked.
- * *_de_render_map: the road's existing DE kernel over the probe's map — the siblings of de_render_rows / bla_de_render_rows
- * (fr_de.h), which build their grid from (y0, y1); no profiling events.  *_de_ss_refine: `groups` workgroups of the road's DE
- * refine kernel, for an escape-time algorithm; the orbit and the table are the context's, made by the probe. */
-int de_render_map(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const fr_ss_map &map, double *d_z, uint32_t *d_iters,
-                  double *d_der, hipStream_t stream);
+ * de_render_map: the probe — a road's DE launch (fr_de.h: de_road) over the strided map, the sibling of de_render_rows, which
+ * builds its grid from (y0, y1); no profiling events.  *_de_ss_refine: `groups` workgroups of the road's DE refine kernel, for an
+ * escape-time algorithm; the orbit and the table are the context's, made by the probe.  The scaled road's: bits < 0 is the plain
+ * scaled loop, no table, and sh.pixels is the scaled view's. */
+template <class Road>
+int de_render_map(Ctx &ctx, const fr_config *cfg, const fr_ss_map &map, double *d_z, uint32_t *d_iters, double *d_der, hipStream_t stream,
+                  Road road) {
+    fr_kparams p;
+    fill_params(cfg, default_opts(), p);
+    map.apply(p);
+    const char *kname;
+    return road(ctx, p, d_z, d_iters, d_der, stream, kname);
+}
 int de_ss_refine(Ctx &ctx, const fr_config *cfg, int precision, const Centre &c, const fr_ss_refine &a, const fr_ss_de_shade &sh,
                  uint32_t groups, hipStream_t stream);
-int bla_de_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_map &map, double *d_z, uint32_t *d_iters,
-                      double *d_der, hipStream_t stream);
 int bla_de_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, const fr_ss_de_shade &sh,
                      uint32_t groups, hipStream_t stream);
-/* ADAPTIVE SUPERSAMPLED SCALED DE's (fr_de_scaled.hip): the sibling of scaled_de_render_rows (fr_de.h) over the probe's map, and
- * ss_refine_de_scaled_kernel's launch; bits < 0: the plain scaled loop, no table.  sh.pixels is the scaled view's. */
-int scaled_de_render_map(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_map &map, double *d_z, uint32_t *d_iters,
-                         double *d_der, hipStream_t stream);
 int scaled_de_ss_refine(Ctx &ctx, const fr_config *cfg, const Centre &c, int bits, const fr_ss_refine &a, const fr_ss_de_shade &sh,
                         uint32_t groups, hipStream_t stream);
 

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Records tests/golden/<table>_call_errors.json: the code and the fr_last_error text of every invalid call in
 tests/<table>_call_cases.py, as the library of a given checkout answers them.  It only records; the tests that compare are
-tests/test_deep_call_errors_cpu.py and tests/test_ss_call_errors_cpu.py.  Run it on the commit whose behaviour is to be pinned,
-before changing the host code:
+tests/test_deep_call_errors_cpu.py, tests/test_ss_call_errors_cpu.py and tests/test_de_call_errors_cpu.py (the plain DE calls).
+Run it on the commit whose behaviour is to be pinned, before changing the host code:
 
-    python tools/record_deep_call_errors.py [--table deep|ss] [--tree CHECKOUT] [--commit ID]
+    python tools/record_deep_call_errors.py [--table deep|ss|de] [--tree CHECKOUT] [--commit ID]
 
 The table (default: deep) is always this repository's; CHECKOUT (default: this repository) is where the BUILT library is loaded
 from.  ID (default: git rev-parse HEAD of CHECKOUT) goes into the file's header.  Needs no device, and refuses to write a file
